@@ -6,9 +6,14 @@ rank per GPU, WORLD_SIZE set) or -- when WORLD_SIZE is unset -- starts that laun
 touches the GPU (task/predict.py:119-135 scales the same way: one process per device).  Fewer than N devices is an error.
 A step = one forward over one per-GPU batch of (query, 5 refs) items already resident in HBM.  Workload =
 BASELINE.json configs[1]: ViT-S/14 encoder, 518x518, 5 refs, batch 8 per GPU (weak scaling: every rank runs its own
-independent batch; no data-path collective -- items never interact).  Rank 0 prints ONE JSON line; it also carries
-BASELINE.json configs[3] (ViT-B/14, 5 refs, 16 items per GPU: the scaling configuration) as `scaling_cfg4`, the
-PyTorch-ROCm eager reference legs and the CPU baseline.
+independent batch; no data-path collective -- items never interact).  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the K steps and prints the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`).  `--full` adds everything else to the same line: one batch at a time, four repeat regions, the other 16-bit operand
+type, BASELINE.json configs[2], configs[3] (ViT-B/14, 5 refs, 16 items per GPU: the scaling configuration, `scaling_cfg4`) and
+configs[4], the per-kernel table and roofline, the score-map MAE against the committed golden, the PyTorch-ROCm eager reference legs
+and the CPU baseline.  `--dump-outputs DIR` writes what the last timed step returned (DIR/<name>.npy, float32): inputs and weights
+come from a fixed seed, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -38,7 +43,7 @@ from crossscore_amd.model import CrossScoreNet  # noqa: E402
 from crossscore_amd.pipeline import ForwardPipeline  # noqa: E402
 from crossscore_amd import parallel  # noqa: E402
 
-PEAK_BF16_TFLOPS = 2500.0  # dense bf16 / fp16 MFMA peak (the F16 forms take the same cycles), /opt/skills/guides/MI355X_MICROARCH.md "Chip-level parameters"
+PEAK_BF16_TFLOPS = 2500.0  # dense bf16 / fp16 MFMA peak (the F16 forms take the same cycles), MI355X chip-level parameters
 PEAK_HBM_GBS = 8000.0      # HBM3E peak, same table
 GEMM_EPI = ["BIAS_F16", "BIAS_GELU_F16", "BIAS_RELU_F16", "BIAS_LEAKY_F16", "RESID_F32", "PATCH_F32", "HEAD_SCORE",
             "LN_F16", "LN_GELU_F16", "RESID_F32_LN"]
@@ -322,6 +327,22 @@ def config_leg(name, rank, world, dev, sync, args, steps=3):
     return leg
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, out):
+    """--dump-outputs: every array the timed path returned for its last step (CrossScoreNet.forward's dict, None entries skipped) as
+    out_dir/<name>.npy in float32.  Weights and inputs come from the workload's seed, so two builds compare output for output."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in out.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than the {DUMP_MAX_BYTES} allowed")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(args) -> int:
     """--gpus N > 1 without a launcher: start N ranks with torch.distributed.run as a CHILD process.  Nothing in this process
     has touched the GPU yet (torch.cuda.device_count() does not initialise it), and it never execs."""
@@ -448,23 +469,25 @@ def plumbing_test(args, rank, world):
                                   host_enqueue_ms_per_forward=1e3 * (time.perf_counter() - t0), launches_per_forward=0)  # (stub: the keys of the real line)
     if os.environ.get("CS_PLUMBING_FAIL_RANK") == str(rank):  # rehearsal of the per-rank failure line
         raise RuntimeError("rehearsed failure")
-    # the strong-scaling leg's plumbing (scaling_cfg4): a fixed global batch split by parallel.shard_bounds, a stub that costs 1 ms per item
-    G = args.global_batch
-    lo, hi = parallel.shard_bounds(G, world, rank)
+    line = {"metric": "plumbing-test (stub forward, no GPU work)", "value": world * 8 * args.steps / elapsed,
+            "unit": "stub-items/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / args.steps, "data": "stub", "scaling": "weak",
+            "gathered_means": means.tolist(), "ranks_seen": census, "process_group": parallel.backend_info()}
+    if args.full:
+        # the strong-scaling leg's plumbing (scaling_cfg4): a fixed global batch split by parallel.shard_bounds, a stub that costs 1 ms per item
+        G = args.global_batch
+        lo, hi = parallel.shard_bounds(G, world, rank)
 
-    def strong_step():
-        time.sleep(0.001 * (hi - lo))
-        return None
+        def strong_step():
+            time.sleep(0.001 * (hi - lo))
+            return None
 
-    e_s, _ = timed_steps(strong_step, lambda: None, args.steps, args.warmup, dev)
-    census_s = parallel.rank_census(dev, shard=[lo, hi], items=hi - lo, ms_per_step=1e3 * timed_steps.last_rank_seconds / args.steps)
+        e_s, _ = timed_steps(strong_step, lambda: None, args.steps, args.warmup, dev)
+        census_s = parallel.rank_census(dev, shard=[lo, hi], items=hi - lo, ms_per_step=1e3 * timed_steps.last_rank_seconds / args.steps)
+        line["scaling_cfg4"] = {"mode": "strong", "global_batch": G, "value": G * args.steps / e_s, "unit": "stub-items/sec",
+                                "ms_per_step": 1e3 * e_s / args.steps, "ranks_seen": census_s}
     if rank == 0:
-        print(json.dumps({"metric": "plumbing-test (stub forward, no GPU work)", "value": world * 8 * args.steps / elapsed,
-                          "unit": "stub-items/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                          "ms_per_step": 1e3 * elapsed / args.steps, "data": "stub", "scaling": "weak",
-                          "gathered_means": means.tolist(), "ranks_seen": census, "process_group": parallel.backend_info(),
-                          "scaling_cfg4": {"mode": "strong", "global_batch": G, "value": G * args.steps / e_s, "unit": "stub-items/sec",
-                                           "ms_per_step": 1e3 * e_s / args.steps, "ranks_seen": census_s}}), flush=True)
+        print(json.dumps(line), flush=True)
     parallel.barrier()
     parallel.shutdown()
 
@@ -475,12 +498,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline (one batch at a time, repeats, the other operand "
+                    "type, BASELINE configs[2-4], per-kernel table and roofline, golden MAE, eager and CPU baselines); the --no-* options "
+                    "below drop single legs of it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32; rank 0's batch)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-eager", action="store_true", help="skip the PyTorch-ROCm eager reference legs (fp32, fp16 autocast, bf16 autocast; all with SDPA)")
     ap.add_argument("--no-cfg4", action="store_true", help="skip the BASELINE scaling configuration (ViT-B, 5 refs, 16 per GPU)")
-    ap.add_argument("--kernels", action="store_true", help="also print the per-kernel table to stderr")
-    ap.add_argument("--cached-refs", action="store_true", help="also time the reference-token cache mode (separate metric)")
-    ap.add_argument("--eager", action="store_true", help="eager legs with materialised attention too (fp32, bf16 autocast)")
+    ap.add_argument("--kernels", action="store_true", help="also print the per-kernel table to stderr (implies --full)")
+    ap.add_argument("--cached-refs", action="store_true", help="also time the reference-token cache mode (separate metric; implies --full)")
+    ap.add_argument("--eager", action="store_true", help="eager legs with materialised attention too (fp32, bf16 autocast; implies --full)")
     ap.add_argument("--lanes", type=int, default=0, help="internal streams of the forward (0 = library default, 2); 1 makes every "
                     "kernel run alone, which is how the per-kernel table below is measured")
     ap.add_argument("--chunk", type=int, default=0, help="encoder chunk in images (0 = library default); the per-kernel table uses "
@@ -499,6 +526,7 @@ def main():
     ap.add_argument("--no-repeats", action="store_true", help="skip the four extra K-step regions behind the timed one (value_median_of_5)")
     ap.add_argument("--plumbing-test", action="store_true", help=argparse.SUPPRESS)  # CPU/gloo rehearsal of the rank plumbing
     args = ap.parse_args()
+    args.full = args.full or args.kernels or args.cached_refs or args.eager
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
@@ -526,10 +554,10 @@ def main():
     wl = Workload(args.workload, rank, dev, args.lanes, args.chunk, inflight=args.inflight, dtype=args.dtype)
     net, arch, B, N, H, W = wl.net, wl.arch, wl.B, wl.N, wl.H, wl.W
     # ---- the same workload with ONE batch at a time (no pipeline; the library's two encoder lanes inside the forward): reported beside
-    #      the headline so that the gain of keeping batches in flight is visible in every line.  Timed first, on the module as a
+    #      the headline so that the gain of keeping batches in flight is visible in every --full line.  Timed first, on the module as a
     #      plain `CrossScoreNet.forward` user finds it. ----
     single = None
-    if wl.inflight > 1 and args.lanes == 0:
+    if args.full and wl.inflight > 1 and args.lanes == 0:
         s_steps = max(3, args.steps // 2)
         lane_cal = wl.net.calibrate_lanes(wl.tq, wl.tr)  # untimed: the two-lane forward must beat the one-lane one, or its streams are re-drawn
         e1, _ = timed_steps(wl.direct, sync, s_steps, 2, dev)
@@ -539,7 +567,10 @@ def main():
                                           "lanes_per_stream_set_tried": [round(1e3 * v, 3) for v in lane_cal["lanes_s"]]}}
     wl.start_pipeline()
     elapsed, ticket = timed_steps(wl.step, sync, args.steps, args.warmup, dev)
-    score = wl.pipe.result(ticket)["score_map_ref_cross"]  # the output of the last timed step
+    out = wl.pipe.result(ticket)  # the output of the last timed step
+    score = out["score_map_ref_cross"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     # who took part: one record per rank (device identity + that rank's own time for the K steps), gathered over the process group
     # what a forward costs THIS rank's CPU thread (cs_forward_stats of the replica that ran the last timed step: kernel launches of one forward
     # and the wall time of the enqueueing call; nothing is waited for inside it) -- the host-side budget of N ranks on one node
@@ -551,7 +582,7 @@ def main():
     # bench contract: exactly K timed steps after W warm-up steps)
     repeats = [elapsed]
     overlap = None
-    for k in range(0 if args.no_repeats else 4):
+    for k in range(4 if args.full and not args.no_repeats else 0):
         if k == 3:  # the last repeat also carries two timing events per forward: how long were two batches really in flight?
             wl.pipe.record_timeline(True)
         e_r, _t = timed_steps(wl.step, sync, args.steps, 1, dev)
@@ -563,7 +594,7 @@ def main():
     # ---- the headline workload again with the other 16-bit operand type (BASELINE words cfg-2 "bf16"; the path's default is fp16): same
     #      K steps, same pipeline; both legs' values and score-map MAEs go into `dtype_legs` ----
     other = None
-    if not args.no_bf16_leg:
+    if args.full and not args.no_bf16_leg:
         odt = "bf16" if args.dtype == "fp16" else "fp16"
         wo = Workload(args.workload, rank, dev, args.lanes, args.chunk, inflight=args.inflight, dtype=odt).start_pipeline()
         eo, to = timed_steps(wo.step, sync, args.steps, args.warmup, dev)
@@ -576,7 +607,7 @@ def main():
     #      (global bs=128 batch-sharded: rank r scores parallel.shard_bounds(128, world, r), in forwards of 16 items with the same batches
     #      in flight; the reference shards a fixed dataset the same way, task/predict.py:119-135), and the weak form (16 items per GPU) ----
     cfg4 = None
-    if not args.no_cfg4 and args.workload != "cfg4":
+    if args.full and not args.no_cfg4 and args.workload != "cfg4":
         w4 = Workload("cfg4", rank, dev, inflight=args.inflight, dtype=args.dtype).start_pipeline()
         steps4 = max(3, args.steps // 2)  # 2 batches in flight: the pipeline's fill and drain weigh on very short runs
         e4, _ = timed_steps(w4.step, sync, steps4, 2, dev)
@@ -608,28 +639,23 @@ def main():
     # ---- BASELINE.json configs[2] and configs[4] (ViT-B with 10 refs; the 1036 x 1036 query) in the same line: short legs with their own roofline
     #      and golden MAE ----
     more_legs = {}
-    if not args.no_more_configs:
+    if args.full and not args.no_more_configs:
         for nm in ("cfg3", "cfg5"):
             if nm != args.workload:
                 more_legs[nm] = config_leg(nm, rank, world, dev, sync, args)
 
-    # ---- per-kernel HIP-event timing (separate pass so the events do not perturb the timed region) ----
     result = None
     if rank == 0:
-        rows, dom = profile_kernels(wl)
         flops_q = wl.flops_per_query()
         value = world * B * args.steps / elapsed
         result = {
             "metric": wl.metric(),
             "value": value, "unit": "query-images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "value_median_of_5": (sorted(world * B * args.steps / e for e in repeats)[len(repeats) // 2] if len(repeats) == 5 else None),
-            "value_repeats": [round(world * B * args.steps / e, 1) for e in repeats],
             "ranks_seen": census, "process_group": parallel.backend_info(),
             "host_enqueue_ms_per_forward": fstats["host_enqueue_ms"], "launches_per_forward": fstats["launches"], "launches_by_kernel": fstats["kernels"],
             "dtype": args.dtype, "data": "synthetic",  # 16-bit MFMA operands (IEEE half by default: the bf16 MFMA rate, 3 more mantissa bits), fp32 accumulate / softmax / LayerNorm / output
             "nonfinite_score_values": wl.pipe.nonfinite_count(),
-            "batches_in_flight_measured": overlap,  # of the fifth K-step region (warm-up step included), HIP events per forward
             "config": {"workload": wl.describe(world),
                        "gflop_per_query": flops_q / 1e9, "parallelism": f"batch-shard x{world} (replicas, no data-path collective); per GPU {wl.inflight} batch(es) in flight x "
                                       f"{wl.lanes if wl.lanes else 2} encoder lane(s)",
@@ -638,9 +664,17 @@ def main():
                                                  "in_flight_per_stream_set_tried": [round(1e3 * v, 3) for v in wl.calibration["in_flight_s"]]}},
             "whole_path": {"achieved_tflops": value * flops_q / 1e12 / world, "peak_tflops": PEAK_BF16_TFLOPS,
                            "frac": value * flops_q / 1e12 / world / PEAK_BF16_TFLOPS},
+        }
+    if rank == 0 and args.full:
+        # ---- per-kernel HIP-event timing (separate pass so the events do not perturb the timed region) ----
+        rows, dom = profile_kernels(wl)
+        result.update({
+            "value_median_of_5": (sorted(world * B * args.steps / e for e in repeats)[len(repeats) // 2] if len(repeats) == 5 else None),
+            "value_repeats": [round(world * B * args.steps / e, 1) for e in repeats],
+            "batches_in_flight_measured": overlap,  # of the fifth K-step region (warm-up step included), HIP events per forward
             "roofline": roofline_of(dom),
             "kernels": [{k: (round(v, 3) if isinstance(v, float) else v) for k, v in x.items() if k not in ("flops", "bytes")} for x in rows],
-        }
+        })
         if args.workload in GOLDEN_OF:
             import numpy as np
             if int(np.load(os.path.join(REPO, "tests", "golden", GOLDEN_OF[args.workload]))["seed"]) == wl.seed:

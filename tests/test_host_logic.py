@@ -214,7 +214,7 @@ def test_bench_launches_its_own_ranks_and_takes_the_slowest(tmp_path):
 
     env = dict(os.environ, PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""))
     env.pop("WORLD_SIZE", None)
-    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--plumbing-test", "--steps", "4", "--warmup", "1",
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--plumbing-test", "--full", "--steps", "4", "--warmup", "1",
                           "--global-batch", "5"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -239,6 +239,21 @@ def test_bench_launches_its_own_ranks_and_takes_the_slowest(tmp_path):
     assert [x["shard"] for x in s4["ranks_seen"]] == [[0, 3], [3, 5]] and [x["items"] for x in s4["ranks_seen"]] == [3, 2]
     assert s4["ms_per_step"] >= 3.0 and s4["ranks_seen"][0]["ms_per_step"] > s4["ranks_seen"][1]["ms_per_step"]  # rank 0 holds 3 items at 1 ms
     assert abs(s4["value"] - 5 / (s4["ms_per_step"] / 1e3)) < 1e-6 * s4["value"]
+
+
+def test_plain_bench_run_times_only_the_headline():
+    """Without --full the line carries the headline and no extra leg: here the strong-scaling leg of the rehearsal (scaling_cfg4)."""
+    import json
+
+    env = dict(os.environ, PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    env.pop("WORLD_SIZE", None)
+    res = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--plumbing-test", "--steps", "3", "--warmup", "1"],
+                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr[-2000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["ms_per_step"] >= 4.0 and "scaling_cfg4" not in r
 
 
 def test_bench_names_the_failing_rank_on_stderr():

@@ -26,8 +26,8 @@ for src, dst, keep in (("panel4_ab.log", "panel4_ab.txt", "impl"), ("panel4_pmc.
 import glob
 for f in glob.glob(os.path.join(O, "stats_panel4", "**", "*kernel_stats.csv"), recursive=True):
     shutil.copy(f, os.path.join(P, f"{tag}_kernel_stats_panel4.csv"))
-for src, dst, cmd in (("alone_hbm_traffic.json", "hbm_traffic.json", "bench.py --no-cpu-baseline --no-eager --no-cfg4 --inflight 1 --lanes 1 --chunk 48 --steps 3 --warmup 1"),
-                      ("alone_cfg4_hbm_traffic.json", "hbm_traffic_cfg4.json", "bench.py --workload cfg4 --no-cpu-baseline --no-eager --no-cfg4 --inflight 1 --lanes 1 --chunk 96 --steps 2 --warmup 1")):
+for src, dst, cmd in (("alone_hbm_traffic.json", "hbm_traffic.json", "bench.py --full --no-cpu-baseline --no-eager --no-cfg4 --inflight 1 --lanes 1 --chunk 48 --steps 3 --warmup 1"),
+                      ("alone_cfg4_hbm_traffic.json", "hbm_traffic_cfg4.json", "bench.py --full --workload cfg4 --no-cpu-baseline --no-eager --no-cfg4 --inflight 1 --lanes 1 --chunk 96 --steps 2 --warmup 1")):
     t = json.load(open(os.path.join(O, src)))
     t["_meta"] = {"commit": commit, "command": f"rocprofv3 --kernel-trace --pmc FETCH_SIZE | WRITE_SIZE -- python3 {cmd} (tools/profile_round.sh)",
                   "note": "FETCH_SIZE counts 64 B per 128-B request on gfx950 (fetch_bytes_corrected = 2 x); hbm_bytes_per_launch = fetch_bytes_corrected + write_bytes"}

@@ -12,7 +12,7 @@ def sample():
     except Exception as e:  # noqa: BLE001
         return {"error": repr(e)}
 print("idle:", json.dumps(sample()), flush=True)
-p = subprocess.Popen([sys.executable, os.path.join(R, "bench.py"), "--no-eager", "--no-cpu-baseline", "--no-cfg4", "--no-more-configs", "--steps", "400"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
+p = subprocess.Popen([sys.executable, os.path.join(R, "bench.py"), "--full", "--no-eager", "--no-cpu-baseline", "--no-cfg4", "--no-more-configs", "--steps", "400"], stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, text=True)
 t0 = time.time()
 while p.poll() is None and time.time() - t0 < 120:
     time.sleep(0.5)
