@@ -76,6 +76,10 @@ hipError_t cs_panel4_pack_launch(const float* wo, const float* ls1, const float*
 hipError_t cs_panel4_launch(const CsPanelParams* p, hipStream_t st);
 hipError_t cs_preprocess_launch(const uint8_t* img, int in_h, int in_w, int row_bytes, int rs_h, int rs_w, int crop_y, int crop_x, int oh,
                                 int ow, const float* mean, const float* stdv, float* out, float* scratch, hipStream_t stream);
+hipError_t cs_metric_map_launch(const uint16_t* maps, int B, int in_h, int in_w, int row_elems, int mode, int rs_h, int rs_w, int crop_y,
+                                int crop_x, int oh, int ow, float* out, float* scratch, hipStream_t stream);
+int cs_score_gt_slabs(size_t hw);
+hipError_t cs_score_gt_stats_launch(const float* score, const float* gt, int B, size_t hw, double* scratch, double* stats, hipStream_t stream);
 }
 
 namespace {
@@ -1713,6 +1717,30 @@ int cs_op_preprocess_u8(const uint8_t* img, int in_h, int in_w, int in_row_bytes
 int cs_op_score_to_gray16(const float* score, long long n, int signed_range, uint16_t* out, cs_stream stream) {
   if (!score || !out || n <= 0 || (signed_range != 0 && signed_range != 1)) return fail(CS_ERR_BAD_ARG, "score_to_gray16: bad arguments");
   HIPCHK(cs_score_gray16_launch(score, (size_t)n, signed_range, out, (hipStream_t)stream));
+  return 0;
+}
+
+int cs_op_metric_map_u16(const uint16_t* maps, int B, int in_h, int in_w, int in_row_elems, int mode, int rs_h, int rs_w, int crop_y,
+                         int crop_x, int out_h, int out_w, float* out, float* scratch, cs_stream stream) {
+  if (!out || B <= 0 || B > 1024 || in_h <= 0 || in_w <= 0 || in_row_elems < in_w || rs_h <= 0 || rs_w <= 0 || out_h <= 0 || out_w <= 0 ||
+      crop_y < 0 || crop_x < 0 || crop_y + out_h > rs_h || crop_x + out_w > rs_w)
+    return fail(CS_ERR_BAD_ARG, "metric_map_u16: bad sizes (1 <= B <= 1024; the crop window must lie inside the resized map)");
+  if (mode < CS_METRIC_SSIM_M1_1 || mode > CS_METRIC_MSE) return fail(CS_ERR_BAD_ARG, "metric_map_u16: mode %d is none of CS_METRIC_*", mode);
+  if (maps && (rs_h != in_h || rs_w != in_w) && !scratch)
+    return fail(CS_ERR_BAD_ARG, "metric_map_u16: a resize needs B*in_h*rs_w floats of scratch");
+  HIPCHK(cs_metric_map_launch(maps, B, in_h, in_w, in_row_elems, mode, rs_h, rs_w, crop_y, crop_x, out_h, out_w, out, scratch, (hipStream_t)stream));
+  return 0;
+}
+
+size_t cs_score_gt_workspace_bytes(int B, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  return (size_t)B * cs_score_gt_slabs((size_t)H * W) * 6 * sizeof(double);
+}
+
+int cs_op_score_gt_stats(const float* score, const float* gt, int B, int H, int W, double* stats, void* scratch, cs_stream stream) {
+  if (!score || !gt || !stats || !scratch || B <= 0 || B > 65535 || H <= 0 || W <= 0)
+    return fail(CS_ERR_BAD_ARG, "score_gt_stats: bad arguments");
+  HIPCHK(cs_score_gt_stats_launch(score, gt, B, (size_t)H * W, (double*)scratch, stats, (hipStream_t)stream));
   return 0;
 }
 

@@ -8,6 +8,7 @@
 // (ATen UpSampleKernel.cpp, _compute_indices_min_size_weights_aa + separable_upsample_generic_Nd_kernel_impl) -> (v - mean) / std.
 // Divisions are IEEE (hipcc's default correctly-rounded fp32 divide), so without a resize the result is bit-identical to the
 // reference's tensor.  HBM-bound byte work: one thread per output pixel, coalesced along x; H2D traffic drops 4x (uint8 in).
+#include "../../include/crossscore_hip.h"
 #include "cs_common.h"
 #include <math.h>
 #include <mutex>
@@ -277,4 +278,170 @@ extern "C" hipError_t cs_preprocess_tables(int in_h, int in_w, int rs_h, int rs_
 extern "C" void cs_preprocess_tables_hold(int on) {
   if (on) g_tabs_mu.lock();
   else g_tabs_mu.unlock();
+}
+
+// ---- test phase (task/test.py): the ground-truth metric map and the score-vs-GT sums ---------------------------------------------------------
+// GT input stage: decoded 16-bit metric map -> the fp32 map NvsDataset hands to the loss.  load_content (nvs_dataset.py:429-457 via
+// utils/io/images.py:32-46) converts first, resize_all + the crop follow (nvs_dataset.py:218-241): the conversion is applied to every source
+// sample as it is read, then the image stage's width and height passes run on the one channel.  IEEE divisions: bit-identical without a resize.
+namespace {
+
+__device__ __forceinline__ float metric_value(uint16_t m, int mode) {
+  if (mode <= CS_METRIC_SSIM_0_1) {
+    const float v = (float)m / 32767.0f - 1.0f;
+    return mode == CS_METRIC_SSIM_0_1 ? fminf(fmaxf(v, 0.0f), 1.0f) : v;  // torch clamp(0, 1)
+  }
+  const float v = (float)m / 65535.0f;
+  return mode == CS_METRIC_MSE ? v * v : v;  // mse: the mae map squared
+}
+
+// One launch covers B maps of one geometry: blockIdx.z is the map, maps are in_h * row_elems samples apart, outputs oh * ow floats, the
+// width pass's rows in_h * rs_w floats.
+__global__ void metric_map_kernel(const uint16_t* __restrict__ maps, int in_h, int row_elems, int mode, int crop_y, int crop_x, int oh, int ow,
+                                  float* __restrict__ out) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  const int y = blockIdx.y, b = blockIdx.z;
+  if (x >= ow) return;
+  const uint16_t* map = maps + (size_t)b * in_h * row_elems;
+  out[((size_t)b * oh + y) * ow + x] = metric_value(map[(size_t)(y + crop_y) * row_elems + x + crop_x], mode);
+}
+
+__global__ void metric_fill_kernel(float v, size_t n, float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = v;
+}
+
+// width pass: tmp[b][y][x'] = sum_j wx[x'][j] * value(map_b[y][xmin[x'] + j])
+__global__ void metric_resize_w_kernel(const uint16_t* __restrict__ maps, int in_h, int row_elems, int mode, int rs_w, int taps,
+                                       const int* __restrict__ xmin, const int* __restrict__ xsize, const float* __restrict__ wx,
+                                       float* __restrict__ tmp) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  const int y = blockIdx.y, b = blockIdx.z;
+  if (x >= rs_w) return;
+  const uint16_t* row = maps + ((size_t)b * in_h + y) * row_elems + xmin[x];
+  const float* w = wx + (size_t)x * taps;
+  const int n = xsize[x];
+  float a = 0.f;
+  for (int j = 0; j < n; ++j) {
+    const float v = metric_value(row[j], mode);
+    a = j == 0 ? v * w[j] : __builtin_fmaf(v, w[j], a);
+  }
+  tmp[((size_t)b * in_h + y) * rs_w + x] = a;
+}
+
+// height pass + crop
+__global__ void metric_resize_h_kernel(const float* __restrict__ tmp, int in_h, int rs_w, int taps, const int* __restrict__ ymin,
+                                       const int* __restrict__ ysize, const float* __restrict__ wy, int crop_y, int crop_x, int oh, int ow,
+                                       float* __restrict__ out) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x;
+  const int y = blockIdx.y, b = blockIdx.z;
+  if (x >= ow) return;
+  const int ry = y + crop_y;
+  const float* w = wy + (size_t)ry * taps;
+  const int n = ysize[ry];
+  const float* col = tmp + ((size_t)b * in_h + ymin[ry]) * rs_w + x + crop_x;
+  float a = 0.f;
+  for (int j = 0; j < n; ++j) a = j == 0 ? col[0] * w[0] : __builtin_fmaf(col[(size_t)j * rs_w], w[j], a);
+  out[((size_t)b * oh + y) * ow + x] = a;
+}
+
+// Score-vs-GT sums: per image  sum|s-g|, sum s, sum g, sum s^2, sum g^2, sum s*g  in fp64.  Launch 1: one workgroup per (slab, image) writes the
+// six sums of its slab of pixels; launch 2: one workgroup per image adds its slabs in slab order.  The slab count depends on H*W only, so an
+// image's sums have the same bits whatever the batch around it.
+constexpr int kStatsThreads = 256;
+
+__global__ void __launch_bounds__(kStatsThreads) score_gt_partial_kernel(const float* __restrict__ score, const float* __restrict__ gt,
+                                                                          size_t hw, int slabs, size_t slab_px, double* __restrict__ partial) {
+  const int s = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
+  const size_t lo = (size_t)s * slab_px, hi = lo + slab_px < hw ? lo + slab_px : hw;
+  const float* sp = score + (size_t)b * hw;
+  const float* gp = gt + (size_t)b * hw;
+  double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  for (size_t i = lo + t; i < hi; i += kStatsThreads) {
+    const double x = sp[i], y = gp[i];
+    a[0] += fabs(x - y);
+    a[1] += x;
+    a[2] += y;
+    a[3] += x * x;
+    a[4] += y * y;
+    a[5] += x * y;
+  }
+  __shared__ double red[6][kStatsThreads];
+  for (int k = 0; k < 6; ++k) red[k][t] = a[k];
+  __syncthreads();
+  for (int half = kStatsThreads / 2; half > 0; half >>= 1) {
+    if (t < half)
+      for (int k = 0; k < 6; ++k) red[k][t] += red[k][t + half];
+    __syncthreads();
+  }
+  if (t < 6) partial[((size_t)b * slabs + s) * 6 + t] = red[t][0];
+}
+
+// one workgroup of 6 waves per image: wave k forms sum k.  Lane l adds slabs l, l + 64, ... in order, then the 64 lane sums are added by a
+// fixed tree: the order depends on the slab count only.
+constexpr int kFinishLanes = 64;
+__global__ void __launch_bounds__(6 * kFinishLanes) score_gt_finish_kernel(const double* __restrict__ partial, int slabs,
+                                                                           double* __restrict__ stats) {
+  const int b = blockIdx.x, k = threadIdx.x / kFinishLanes, l = threadIdx.x % kFinishLanes;
+  const double* p = partial + (size_t)b * slabs * 6 + k;
+  double a = 0.0;
+  for (int s = l; s < slabs; s += kFinishLanes) a += p[(size_t)s * 6];
+  __shared__ double red[6][kFinishLanes];
+  red[k][l] = a;
+  __syncthreads();
+  for (int half = kFinishLanes / 2; half > 0; half >>= 1) {
+    if (l < half) red[k][l] += red[k][l + half];
+    __syncthreads();
+  }
+  if (l == 0) stats[(size_t)b * 6 + k] = red[k][0];
+}
+
+constexpr size_t kStatsSlabPx = 4096;
+
+}  // namespace
+
+// slabs of one image of hw pixels (scratch: B * slabs * 6 doubles)
+extern "C" int cs_score_gt_slabs(size_t hw) { return (int)((hw + kStatsSlabPx - 1) / kStatsSlabPx); }
+
+extern "C" hipError_t cs_score_gt_stats_launch(const float* score, const float* gt, int B, size_t hw, double* scratch, double* stats,
+                                               hipStream_t stream) {
+  const int slabs = cs_score_gt_slabs(hw);
+  hipLaunchKernelGGL(score_gt_partial_kernel, dim3(slabs, B), dim3(kStatsThreads), 0, stream, score, gt, hw, slabs, kStatsSlabPx, scratch);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(score_gt_finish_kernel, dim3(B), dim3(6 * kFinishLanes), 0, stream, scratch, slabs, stats);
+  return hipGetLastError();
+}
+
+// B maps of one geometry, in_h * row_elems samples apart; map == nullptr: B "empty_image" placeholders of the map's mode (0 for SSIM, NaN for
+// MAE / MSE), no read.  `scratch` holds B * in_h * rs_w floats when a resize is requested.
+extern "C" hipError_t cs_metric_map_launch(const uint16_t* maps, int B, int in_h, int in_w, int row_elems, int mode, int rs_h, int rs_w, int crop_y,
+                                           int crop_x, int oh, int ow, float* out, float* scratch, hipStream_t stream) {
+  const dim3 blk(256);
+  if (!maps) {
+    const size_t n = (size_t)B * oh * ow;
+    hipLaunchKernelGGL(metric_fill_kernel, dim3((unsigned)((n + 255) / 256)), blk, 0, stream, mode <= CS_METRIC_SSIM_0_1 ? 0.0f : __builtin_nanf(""),
+                       n, out);
+    return hipGetLastError();
+  }
+  if (rs_h == in_h && rs_w == in_w) {
+    hipLaunchKernelGGL(metric_map_kernel, dim3((ow + 255) / 256, oh, B), blk, 0, stream, maps, in_h, row_elems, mode, crop_y, crop_x, oh, ow, out);
+    return hipGetLastError();
+  }
+  std::lock_guard<std::recursive_mutex> lock(g_tabs_mu);
+  const TableEntry* hit = nullptr;
+  hipError_t e = table_entry(in_h, in_w, rs_h, rs_w, &hit);
+  if (e != hipSuccess) return e;
+  const TableEntry& T = *hit;
+  const int* xmin = T.d_int;
+  const int* xsize = T.d_int + rs_w;
+  const int* ymin = T.d_int + 2 * rs_w;
+  const int* ysize = ymin + rs_h;
+  hipLaunchKernelGGL(metric_resize_w_kernel, dim3((rs_w + 255) / 256, in_h, B), blk, 0, stream, maps, in_h, row_elems, mode, rs_w, T.taps_x, xmin,
+                     xsize, T.d_w, scratch);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(metric_resize_h_kernel, dim3((ow + 255) / 256, oh, B), blk, 0, stream, scratch, in_h, rs_w, T.taps_y, ymin, ysize,
+                     T.d_w + (size_t)rs_w * T.taps_x, crop_y, crop_x, oh, ow, out);
+  return hipGetLastError();
 }

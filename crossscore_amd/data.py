@@ -64,6 +64,32 @@ def read_image_u8(path: str) -> np.ndarray:
     return np.ascontiguousarray(img)
 
 
+def read_metric_map_u16(path: str) -> np.ndarray:
+    """Decoded 16-bit metric map (utils/io/images.py:32-46 reads it with PIL).  PIL returns 16-bit PNGs as "I;16" (uint16) or "I" (int32)
+    depending on its version; both come back as a contiguous uint16 (H, W) array."""
+    from PIL import Image
+
+    m = np.array(Image.open(path))
+    if m.ndim != 2 or m.dtype not in (np.uint16, np.int32):
+        raise ValueError(f"{path}: expected a 16-bit grayscale metric map, got {m.dtype} {m.shape}")
+    if m.dtype == np.int32:
+        if m.size and (m.min() < 0 or m.max() > 65535):
+            raise ValueError(f"{path}: metric map samples outside 0..65535")
+        m = m.astype(np.uint16)
+    return np.ascontiguousarray(m)
+
+
+def metric_mode(metric_type: str, metric_min) -> int:
+    """The GT map's load_content conversion (nvs_dataset.py:439-455) as a cs_op_metric_map_u16 mode."""
+    if metric_type == "ssim":
+        return _lib.METRIC_SSIM_0_1 if metric_min == 0 else _lib.METRIC_SSIM_M1_1
+    if metric_type == "mae":
+        return _lib.METRIC_MAE
+    if metric_type == "mse":
+        return _lib.METRIC_MSE
+    raise ValueError(f"Invalid metric type {metric_type}")
+
+
 class InputStage:
     """uint8 HWC images -> the normalised fp32 batch tensors CrossScoreNet.forward takes, on `device`."""
 
@@ -114,6 +140,60 @@ class InputStage:
         # d_img may be released once the stream has consumed it
         d_img.record_stream(torch.cuda.current_stream(self.device))
 
+
+    def metric_map(self, map_u16: Optional[np.ndarray], query_hw: Tuple[int, int], mode: int, out: torch.Tensor) -> None:
+        """metric_maps for one map: `out` is its (oh, ow) fp32 slice on the device."""
+        self.metric_maps([map_u16], [query_hw], mode, out[None])
+
+    def metric_maps(self, maps: Sequence[Optional[np.ndarray]], query_hws: Sequence[Tuple[int, int]], mode: int, out: torch.Tensor) -> None:
+        """GT stage of the test phase: writes the processed ground-truth maps of B queries of sizes query_hws into `out` ((B, oh, ow) fp32 on
+        the device), each with its query's own resize and crop; None is the "empty_image" placeholder (0 for SSIM, NaN for MAE / MSE).  Queued
+        on the current stream without waiting for it: the maps go up from pinned host memory (non-blocking copies), and one launch pair per
+        source size covers the batch."""
+        lib = _lib.load()
+        B = len(maps)
+        if len(query_hws) != B or B == 0:
+            raise ValueError("metric_maps: one query size per map, at least one map")
+        geo, groups = [], {}
+        for b, (m, hw) in enumerate(zip(maps, query_hws)):
+            h, w = int(hw[0]), int(hw[1])
+            if m is not None:
+                if m.dtype == np.int32:  # PIL's "I" mode for 16-bit PNGs
+                    m = m.astype(np.uint16)
+                if m.dtype != np.uint16 or m.ndim != 2:
+                    raise ValueError(f"metric map must be a uint16 (H, W) array, got {m.dtype} {m.shape}")
+                if tuple(m.shape) != (h, w):
+                    raise ValueError(f"metric map {m.shape[0]}x{m.shape[1]} and its render {h}x{w} differ in size")
+            geo.append(self.geometry(h, w))
+            groups.setdefault(None if m is None else (h, w), []).append((b, m))
+        oh, ow = geo[0][1][2:]
+        if any(g[1][2:] != (oh, ow) for g in geo) or tuple(out.shape) != (B, oh, ow) or not out.is_contiguous() or out.dtype != torch.float32:
+            raise ValueError(f"output must be contiguous fp32 ({B},{oh},{ow}) and every map must give that size, got {tuple(out.shape)}")
+        stream = torch.cuda.current_stream(self.device)
+        st = C.c_void_p(stream.cuda_stream)
+        for key, members in groups.items():
+            idx = [b for b, _ in members]
+            n = len(idx)
+            whole = n == B
+            dst = out if whole else torch.empty((n, oh, ow), dtype=torch.float32, device=self.device)
+            rs, crop = geo[idx[0]]
+            if key is None:
+                _lib.check(lib.cs_op_metric_map_u16(None, n, rs[0], rs[1], rs[1], int(mode), rs[0], rs[1], crop[0], crop[1], oh, ow,
+                                                    C.c_void_p(dst.data_ptr()), None, st))
+            else:
+                h, w = key
+                host = torch.empty((n, h, w), dtype=torch.int16, pin_memory=True)
+                hv = host.numpy()
+                for i, (_, m) in enumerate(members):
+                    hv[i] = np.asarray(m, dtype=np.uint16).view(np.int16)
+                d_maps = host.to(self.device, non_blocking=True)  # pinned source: an asynchronous copy on the current stream
+                scratch = torch.empty((n * h * rs[1],), dtype=torch.float32, device=self.device) if rs != (h, w) else None
+                _lib.check(lib.cs_op_metric_map_u16(C.c_void_p(d_maps.data_ptr()), n, h, w, w, int(mode), rs[0], rs[1], crop[0], crop[1], oh, ow,
+                                                    C.c_void_p(dst.data_ptr()), C.c_void_p(scratch.data_ptr()) if scratch is not None else None,
+                                                    st))
+            if not whole:
+                for i, b in enumerate(idx):
+                    out[b].copy_(dst[i])
 
     # -- the one-pass form (SURVEY.md 8f-4 as worded): nothing is computed here, the patch-embedding launch does the pixel work --------------
     def describe(self, img_u8: np.ndarray):

@@ -1,0 +1,351 @@
+"""`task/test.py`-compatible driver: score every render of an NvsDataset tree against its ground-truth metric map on the GPU.
+
+    python -m crossscore_amd.evaluate data.dataset.path=<tree> [trainer.ckpt_path_to_load=<ckpt>] [any a.b=c override of config/default_test.yaml]
+
+What the reference does (task/test.py:21-140, task/core.py:201-213, 265-293, 379-417) and where it happens here:
+  dataset / sampling                 get_dataset -> NvsDataset -> NeighbourSelector          -> crossscore_amd/nvs.py (NvsItems)
+  images                             load_content, resize_all, crops, T.Normalize            -> data.InputStage (predict's input stage)
+  GT maps                            load_content, resize_all, crops                         -> InputStage.metric_map (cs_op_metric_map_u16)
+  forward                            CrossScoreNet                                           -> ForwardPipeline, reference-token cache, as predict
+  L1 loss, Pearson, PSNR per batch   _core_step, on_test_batch_end, correlation, abs2psnr    -> cs_op_score_gt_stats (fp64 sums) + the host
+  epoch values                       log_dict(on_step=False) -> Lightning's epoch mean        -> epoch_metrics()
+  outputs                            CSVLogger version_<n>/metrics.csv, BatchWriter, score summary
+Per batch the GT stage (the maps go up from pinned host memory with non-blocking copies; one launch pair per source size covers the
+batch) and the statistics kernel are queued on the stream of the batch's forward, behind its score map; nothing waits for the device until
+the batch is consumed (depth - 1 submits later), when its B x 6 sums are copied to the host.
+
+Epoch values: each of test/loss, test/loss_cross, test/corr_cross, test/psnr_cross is the batch-size-weighted mean of its per-batch values,
+sum(bs * v) / sum(bs) -- Lightning's on_epoch mean for log_dict(on_step=False).  With several ranks the pairs (sum(bs * v), sum(bs)) are summed
+over the ranks (parallel.sum_over_ranks) and the global weighted mean is reported; with one rank this is exactly Lightning's value
+(Lightning 2.1.3's own sync_dist arithmetic, a mean of the ranks' means, was not available to compare with).  A NaN ground truth (the MAE / MSE
+placeholder of a render without a metric map) makes its batch's values NaN and, through them, the epoch values: nothing is filtered.
+Not reproduced: Lightning's Trainer and sampler (shuffle: True orders the items by torch.randperm seeded from lightning.seed, which does not
+reproduce Lightning's draws; per-image outputs do not depend on the order, the epoch correlation does, through the batch grouping), the
+interactive batch-size prompt (one line on stderr instead), the vis figure and hparams.yaml.
+"""
+from __future__ import annotations
+
+import csv
+import ctypes as C
+import os
+import sys
+import time
+from datetime import datetime
+from pathlib import Path
+from typing import Dict, Iterable, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, parallel, synth
+from .config import load_config
+from .data import (EMPTY, InputStage, ReferenceTokenCache, decode_items, load_batch, load_batch_u8, load_query_batch, load_query_batch_u8,
+                   metric_mode, read_image_u8, read_metric_map_u16)
+from .model import CrossScoreNet, load_lightning_checkpoint
+from .nvs import NvsItems, random_order
+from .pipeline import ForwardPipeline
+from .predict import seed_everything
+from .writers import BatchWriter, ScoreSummariser
+
+METRIC_KEYS = ("test/loss", "test/loss_cross", "test/corr_cross", "test/psnr_cross")
+CSV_COLUMNS = sorted(METRIC_KEYS + ("epoch", "step"))  # CSVLogger sorts its keys
+BATCH_COLUMNS = ("batch_idx", "rank", "batch_size", "loss", "corr", "psnr")
+
+
+def next_version(root: Path) -> int:
+    """CSVLogger._get_next_version: one past the largest version_<n> under root, 0 when there is none."""
+    ns = []
+    if root.is_dir():
+        for d in os.listdir(root):
+            if d.startswith("version_") and (root / d).is_dir():
+                try:
+                    ns.append(int(d.split("_")[1]))
+                except ValueError:
+                    pass
+    return max(ns) + 1 if ns else 0
+
+
+def resolve_dirs(cfg, now: Optional[str] = None):
+    """task/test.py:48-64: (version dir holding metrics.csv, out_dir).  The log dir is ckpt.parents[1]/test, or log/<now>/test_empty_ckpt
+    without a checkpoint; out_dir is f"{version_dir}_{alias}" (a trailing "_" when alias is "") unless logger.test.out_dir is set."""
+    if cfg.trainer.ckpt_path_to_load is None:
+        now = now or datetime.now().strftime("%Y%m%d_%H%M%S.%f")
+        log_dir, name = Path("log") / now, "test_empty_ckpt"
+    else:
+        log_dir, name = Path(cfg.trainer.ckpt_path_to_load).parents[1], "test"
+    root = log_dir / name
+    version_dir = root / f"version_{next_version(root)}"
+    out_dir = cfg.logger.test.out_dir
+    if out_dir is None:
+        out_dir = f"{version_dir}_{cfg.alias}"
+    return str(version_dir), str(out_dir)
+
+
+def limit_batches(n: int, limit) -> int:
+    """trainer.limit_test_batches as Lightning reads it: an int is a count, a float a fraction of the batches."""
+    if isinstance(limit, bool) or not isinstance(limit, (int, float)) or limit < 0:
+        raise ValueError(f"limit_test_batches must be a non-negative int or float, got {limit!r}")
+    if isinstance(limit, int):
+        return min(n, limit)
+    if limit > 1.0:
+        raise ValueError(f"limit_test_batches {limit} is a float above 1.0")
+    k = int(n * limit)
+    if k == 0 and limit > 0 and n > 0:
+        raise ValueError(f"limit_test_batches={limit} of {n} batches selects none")
+    return k
+
+
+def batch_metrics(stats: np.ndarray, pixels_per_image: int) -> Dict[str, float]:
+    """Per-batch values from the (B, 6) fp64 sums of cs_op_score_gt_stats: the L1 loss (the mean over the batch's pixels, task/core.py:282-285),
+    the Pearson correlation of the batch's flattened pixels (utils/evaluation/metric.py:26-30: the whole batch, not per image) from the
+    pooled sums, and abs2psnr of the loss (core.py:181)."""
+    s = np.asarray(stats, dtype=np.float64).reshape(-1, 6).sum(axis=0)
+    n = float(stats.shape[0]) * float(pixels_per_image)
+    with np.errstate(all="ignore"):
+        loss = s[0] / n
+        cov = n * s[5] - s[1] * s[2]
+        var = (n * s[3] - s[1] * s[1]) * (n * s[4] - s[2] * s[2])
+        corr = cov / np.sqrt(var) if var > 0 else float("nan")
+        psnr = -10.0 * np.log10(loss * loss)
+    return {"loss": float(loss), "corr": float(corr), "psnr": float(psnr)}
+
+
+def weighted_sums(rows: Sequence[Dict[str, float]]) -> List[float]:
+    """(sum bs * loss, sum bs * corr, sum bs * psnr, sum bs) of a rank's batch rows."""
+    return [sum(r["batch_size"] * r[k] for r in rows) for k in ("loss", "corr", "psnr")] + [float(sum(r["batch_size"] for r in rows))]
+
+
+def epoch_metrics(sums: Sequence[float]) -> Dict[str, float]:
+    """The epoch values from the (rank-summed) weighted_sums: see the module docstring."""
+    loss, corr, psnr, w = sums
+    with np.errstate(all="ignore"):
+        m = [float(np.float64(v) / np.float64(w)) if w > 0 else float("nan") for v in (loss, corr, psnr)]
+    return {"test/loss": m[0], "test/loss_cross": m[0], "test/corr_cross": m[1], "test/psnr_cross": m[2]}
+
+
+def write_metrics_csv(version_dir: str, metrics: Dict[str, float], epoch: int = 0, step: int = 0) -> str:
+    Path(version_dir).mkdir(parents=True, exist_ok=True)
+    path = os.path.join(version_dir, "metrics.csv")
+    row = dict(metrics, epoch=epoch, step=step)
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(CSV_COLUMNS)
+        w.writerow([repr(float(row[k])) if k in METRIC_KEYS else row[k] for k in CSV_COLUMNS])
+    return path
+
+
+def write_batches_csv(out_dir: str, rows: Sequence[Dict[str, float]]) -> str:
+    path = os.path.join(out_dir, "test_batches.csv")
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(BATCH_COLUMNS)
+        for r in sorted(rows, key=lambda r: (r["rank"], r["batch_idx"])):
+            w.writerow([r["batch_idx"], r["rank"], r["batch_size"], repr(r["loss"]), repr(r["corr"]), repr(r["psnr"])])
+    return path
+
+
+def decode_eval(items, zero_ref: bool, pool, skip=()):
+    """decode_items plus the GT maps of the queries (None for "empty_image")."""
+    futs = [None if it["query/score_map"] == EMPTY else pool.submit(read_metric_map_u16, it["query/score_map"]) for it in items]
+    decoded = decode_items(items, zero_ref, pool, skip)  # (the maps decode beside the images, on the same workers)
+    return decoded, [None if f is None else f.result() for f in futs]
+
+
+def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None,
+             capture: Optional[list] = None) -> Dict[str, object]:
+    """Runs the test loop; returns {"version_dir", "out_dir", "metrics", "batches", "files", "query_images_per_sec", "input_stage"}.
+    capture (tests, tools): a list that receives per batch {"batch_idx", "item_paths", "score", "gt", "stats"} (host copies)."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("crossscore_amd.evaluate needs a GPU: the scoring path has no CPU fallback")
+    seed_everything(int(cfg.lightning.seed))
+    rank, local_rank, world = parallel.init_from_env()
+    device = torch.device("cuda", local_rank if world > 1 else 0)
+    torch.cuda.set_device(device)
+    bs = int(cfg.data.loader.validation.batch_size)
+    crop_mode = cfg.this_main.crop_mode
+    if not cfg.this_main.get("force_batch_size", False) and bs > 8 and crop_mode in (None, "integer_patches"):
+        # task/test.py:27-45 asks on stdin whether to go on; a batch job cannot answer
+        print(f"[crossscore_amd.evaluate] testing full image resolution in a large batch size {bs}", file=sys.stderr)
+    version_dir, out_dir = parallel.gather_objects(resolve_dirs(cfg, now))[0]  # rank 0's names on every rank
+    cfg.logger.test.out_dir = out_dir
+    Path(out_dir).mkdir(parents=True, exist_ok=True)
+
+    if crop_mode not in (None, "integer_patches", "dataset_default"):
+        raise ValueError(f"crop_mode {crop_mode} not supported (task/test.py:75-91 knows null, integer_patches and dataset_default)")
+    stage = InputStage(device, resize_short_side=int(cfg.this_main.resize_short_side),
+                       crop_size=int(cfg.data.transforms.crop_size) if crop_mode == "dataset_default" else None,
+                       integer_patches=crop_mode == "integer_patches")
+    mode = metric_mode(cfg.model.predict.metric.type, cfg.model.predict.metric.min)
+    if cfg.model.loss.fn != "l1":
+        raise NotImplementedError(f"loss fn {cfg.model.loss.fn} (task/core.py:183-187 knows l1)")
+    items = NvsItems.from_config(cfg)
+
+    net = CrossScoreNet(cfg)
+    if "operand_dtype" not in cfg.model.backbone:
+        net.operand_dtype = "bf16" if str(cfg.trainer.precision).startswith("bf16") else "fp16"
+    if state_dict is None:
+        if cfg.trainer.ckpt_path_to_load is not None:
+            state_dict = load_lightning_checkpoint(cfg.trainer.ckpt_path_to_load)
+        else:
+            print("[crossscore_amd.evaluate] no checkpoint: seeded synthetic weights (scores are meaningless)", file=sys.stderr)
+            state_dict = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(net.arch, int(cfg.lightning.seed)).items()}
+    net.load_state_dict(state_dict, strict=True)
+    net = net.to(device)
+
+    wcfg = cfg.logger.test.write
+    writer = (BatchWriter(cfg, "test", net.img_mean_std, device, workers=max(1, int(cfg.data.loader.validation.num_workers) // 2))
+              if wcfg.flag.batch else None)
+    summariser = ScoreSummariser(cfg.model.predict.metric.type, cfg.model.predict.metric.min, out_dir)
+
+    order = random_order(len(items), int(cfg.lightning.seed)) if cfg.data.loader.validation.shuffle else list(range(len(items)))
+    lo, hi = parallel.shard_bounds(len(order), world, rank)
+    batches = [[items[order[i]] for i in range(start, min(start + bs, hi))] for start in range(lo, hi, bs)]
+    batches = batches[:limit_batches(len(batches), cfg.trainer.limit_test_batches)]
+    zero_ref = bool(cfg.data.dataset.zero_reference)
+    from concurrent.futures import ThreadPoolExecutor
+    pool = ThreadPoolExecutor(max_workers=max(1, int(cfg.data.loader.validation.num_workers)))
+    prefetch = ThreadPoolExecutor(max_workers=1)
+    use_cache = bool(cfg.this_main.get("cache_reference_tokens", True)) and int(cfg.data.neighbour_config.cross) > 0
+    pipe = ForwardPipeline(net, depth=max(1, int(cfg.this_main.get("batches_in_flight", 3))))
+    # the one-pass input stage under the rules of predict.py: "auto" takes it when no processed image is written and the geometry is held
+    want_imgs = writer is not None and bool(wcfg.flag.image_query or wcfg.flag.image_reference)
+    fused_cfg = cfg.this_main.get("fused_input_stage", "auto")
+    fused_in = False
+    if fused_cfg not in (False, "false", "False", 0) and batches and not want_imgs:
+        probe = read_image_u8(batches[0][0]["query/img"])
+        rs0, crop0 = stage.geometry(*probe.shape[:2])
+        from .model import U8Image
+        fused_in = net.u8_input_supported(U8Image(None, probe.shape[0], probe.shape[1], rs0, crop0[0], crop0[1]), crop0[2:], device)
+    if fused_cfg in (True, "true", "True", 1) and not fused_in:
+        raise ValueError("this_main.fused_input_stage=True, but " + ("the writers need the processed images (logger.test.write.flag.image_query / "
+                         "image_reference)" if want_imgs else "this backbone / image geometry is not taken by the one-pass input stage"))
+    cache = ReferenceTokenCache(pipe, stage, keep_images=bool(writer is not None and wcfg.flag.image_reference),
+                                max_images=int(cfg.this_main.get("reference_cache_max_images", 4096)), from_u8=fused_in) if use_cache else None
+    cached_paths = lambda: {k[0] for k in cache.tokens} if cache is not None else ()  # noqa: E731
+    pending = prefetch.submit(decode_eval, batches[0], zero_ref, pool, cached_paths()) if batches else None
+    need_w, head_id = bool(cfg.model.need_attn_weights), int(cfg.model.need_attn_weights_head_id)
+    lib = _lib.load()
+    files: List[str] = []
+    rows: List[Dict[str, float]] = []
+    n_done = 0
+
+    def gt_and_stats(ticket, its, decoded, maps, size):
+        """GT stage + statistics kernel on the forward's stream, behind its score map; returns (gt, stats, event)."""
+        s = ticket.stream if ticket.stream is not None else torch.cuda.current_stream(device)
+        oh, ow = size
+        B = len(its)
+        with torch.cuda.stream(s):
+            gt = torch.empty((B, oh, ow), dtype=torch.float32, device=device)
+            stage.metric_maps(maps, [decoded[it["query/img"]].shape[:2] for it in its], mode, gt)
+            score = ticket.out["score_map_ref_cross"]
+            if tuple(score.shape) != (B, oh, ow):
+                raise ValueError(f"score map {tuple(score.shape)} and GT maps {(B, oh, ow)} differ in shape")
+            stats = torch.empty((B, 6), dtype=torch.float64, device=device)
+            scratch = torch.empty((lib.cs_score_gt_workspace_bytes(B, oh, ow),), dtype=torch.uint8, device=device)
+            _lib.check(lib.cs_op_score_gt_stats(C.c_void_p(score.data_ptr()), C.c_void_p(gt.data_ptr()), B, oh, ow, C.c_void_p(stats.data_ptr()),
+                                                C.c_void_p(scratch.data_ptr()), C.c_void_p(s.cuda_stream)))
+            ev = torch.cuda.Event()
+            ev.record(s)
+        return gt, stats, ev
+
+    def check_size(size):
+        if crop_mode is None and (size[0] % net.arch.patch or size[1] % net.arch.patch):
+            raise ValueError(f"crop_mode null: a {size[0]}x{size[1]} image is no whole number of {net.arch.patch}-pixel patches (the reference "
+                             "fails in the L1 loss' broadcast); use crop_mode=integer_patches")
+
+    def consume(entry):
+        ticket, batch, idx, gt, stats, ev = entry
+        out = pipe.result(ticket)
+        cur = torch.cuda.current_stream(device)
+        cur.wait_event(ev)
+        gt.record_stream(cur)
+        st = stats.cpu().numpy()  # B x 6 doubles: the one host wait of the batch
+        m = batch_metrics(st, gt.shape[1] * gt.shape[2])
+        rows.append(dict(m, batch_idx=idx, rank=rank, batch_size=int(gt.shape[0])))
+        batch["query/score_map"] = gt
+        if capture is not None:
+            capture.append({"batch_idx": idx, "item_paths": batch["item_paths"], "score": out["score_map_ref_cross"].cpu().numpy(),
+                            "gt": gt.cpu().numpy(), "stats": st})
+        summariser.update(batch, out, means=out.get("score_mean_ref_cross"))
+        if writer is not None:
+            files.extend(writer.write_out(batch, out, local_rank, idx))
+
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    queued = []
+    for batch_idx, its in enumerate(batches):
+        decoded, maps = pending.result()
+        if cache is None:
+            pending = prefetch.submit(decode_eval, batches[batch_idx + 1], zero_ref, pool) if batch_idx + 1 < len(batches) else None
+            batch = (load_batch_u8 if fused_in else load_batch)(its, stage, zero_ref, decoded)
+            size = batch["query/img"].size if fused_in else tuple(batch["query/img"].shape[-2:])
+            check_size(size)
+            if fused_in:
+                ticket = pipe.submit_u8(batch["query/img"], batch["reference/cross/imgs"], need_w, head_id, True)
+            else:
+                ticket = pipe.submit(batch["query/img"], batch["reference/cross/imgs"], need_w, head_id, False, return_mean=True)
+        else:
+            batch, size = (load_query_batch_u8 if fused_in else load_query_batch)(its, stage, decoded)
+            check_size(size)
+            tokens, ref_imgs = cache.gather([it["reference/cross/imgs"] for it in its], decoded, size, zero_ref)
+            batch["reference/cross/imgs"] = ref_imgs
+            pending = (prefetch.submit(decode_eval, batches[batch_idx + 1], zero_ref, pool, cached_paths())
+                       if batch_idx + 1 < len(batches) else None)
+            ticket = (pipe.submit_cached_u8 if fused_in else pipe.submit_cached)(batch["query/img"], tokens, need_w, head_id, True)
+        gt, stats, ev = gt_and_stats(ticket, its, decoded, maps, tuple(size))
+        n_done += len(its)
+        queued.append((ticket, batch, batch_idx, gt, stats, ev))
+        while len(queued) >= pipe.depth:
+            consume(queued.pop(0))
+    while queued:
+        consume(queued.pop(0))
+    torch.cuda.synchronize(device)
+    t_loop = time.perf_counter() - t0
+    # outputs first, then one collective that carries the metrics and any failure (a rank that raised on its own before it would leave the
+    # others waiting in it): the failure is re-raised behind the collective, as in predict.py
+    failure: Optional[BaseException] = None
+    try:
+        if writer is not None:
+            writer.finish()
+        files += summariser.summarise()
+    except BaseException as exc:  # noqa: BLE001 -- re-raised below, behind the collective
+        failure = exc
+    finally:
+        prefetch.shutdown()
+        pool.shutdown()
+    bad = pipe.nonfinite_count()
+    tot = parallel.sum_over_ranks(weighted_sums(rows) + [1.0 if failure is not None else 0.0, float(bad)], device)
+    all_rows = [r for rr in parallel.gather_objects(rows) for r in rr]
+    parallel.barrier()
+    if failure is not None:
+        raise failure
+    if tot[4] > 0:
+        raise RuntimeError(f"another rank failed while finishing its outputs (see its traceback); this rank's outputs are under {out_dir}")
+    if tot[5] > 0:
+        raise FloatingPointError(f"{int(tot[5])} non-finite score-map values with {net.operand_dtype} MFMA operands: run with "
+                                 f"trainer.precision=bf16-mixed (model.backbone.operand_dtype=bf16); the outputs written are under {out_dir}")
+    metrics = epoch_metrics(tot[:4])
+    if rank == 0:
+        files.append(write_metrics_csv(version_dir, metrics))
+        files.append(write_batches_csv(out_dir, all_rows))
+    return {"version_dir": version_dir, "out_dir": out_dir, "metrics": metrics, "batches": sorted(rows, key=lambda r: r["batch_idx"]),
+            "files": files, "input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
+            "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}
+
+
+def main(argv: Optional[Iterable[str]] = None) -> int:
+    overrides = list(sys.argv[1:] if argv is None else argv)
+    from . import configure_runtime
+    configure_runtime()
+    cfg = load_config("default_test", overrides)
+    with torch.no_grad():
+        res = evaluate(cfg)
+    m = res["metrics"]
+    print(f"[crossscore_amd.evaluate] {sum(r['batch_size'] for r in res['batches'])} query images: test/loss {m['test/loss']:.6f} "
+          f"test/corr_cross {m['test/corr_cross']:.6f} test/psnr_cross {m['test/psnr_cross']:.4f}; metrics under {res['version_dir']}, outputs "
+          f"under {res['out_dir']}")
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -125,3 +125,22 @@ def shutdown() -> None:
     """Tears the process group down (quiet exit of multi-rank runs)."""
     if dist.is_available() and dist.is_initialized():
         dist.destroy_process_group()
+
+
+def sum_over_ranks(values, device: torch.device | str = "cpu") -> List[float]:
+    """Element-wise fp64 sum of a short list of floats over all ranks (every rank receives the result)."""
+    vals = [float(v) for v in values]
+    if _single():
+        return vals
+    t = torch.tensor(vals, dtype=torch.float64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return [float(v) for v in t.tolist()]
+
+
+def gather_objects(obj) -> List[object]:
+    """Every rank's `obj` (picklable), in rank order, on every rank."""
+    if _single():
+        return [obj]
+    out: List[object] = [None] * dist.get_world_size()
+    dist.all_gather_object(out, obj)
+    return out

@@ -2,8 +2,8 @@
 
 Mirrors
   BatchWriter                                   utils/io/batch_writer.py:26-135,155-270 (score maps, query / reference images, item-path
-                                                json, attention-weight images of the centre query patch; ground-truth score maps do not
-                                                exist in predict and are not written)
+                                                json, attention-weight images of the centre query patch; ground-truth score maps in the
+                                                test phase only, batch_writer.py:137-152)
   attn2rgb                                      utils/misc/image.py:55-77
   get_vrange / metric_map_write / gray2rgb      batch_writer.py:9-21, utils/io/images.py:49-63, utils/misc/image.py:37-52
   SummaryWriterPredictedOnlineTestPrediction    utils/io/score_summariser.py:142-250 (per-image mean -> CSV, "%.4f")
@@ -120,9 +120,12 @@ class BatchWriter:
         # batch_writer.py:42-45: attention images only when the model returns the weights
         self.write_attn = bool(self.write_flag["attn_weights"]) and bool(cfg.model.need_attn_weights)
         self.out_dir_dict = {"batch": Path(self.out_dir, "batch")}
+        self.phase = phase
+        # score_map_gt (batch_writer.py:137-152): the test phase's GT maps, batch_input["query/score_map"] on the device
+        kinds = ("item_path_json", "image_query", "image_reference", "attn_weights") + (("score_map_gt",) if phase == "test" else ())
         if self.write_flag["batch"]:
             for k in self.write_flag.keys():
-                if k not in ("batch", "score_map_prediction") and self.write_flag[k] and k in ("item_path_json", "image_query", "image_reference", "attn_weights"):
+                if k not in ("batch", "score_map_prediction") and self.write_flag[k] and k in kinds:
                     self.out_dir_dict[k] = Path(self.out_dir_dict["batch"], k)
                     self.out_dir_dict[k].mkdir(parents=True, exist_ok=True)
 
@@ -131,6 +134,8 @@ class BatchWriter:
         written: List[str] = []
         if self.write_flag["score_map_prediction"]:
             written += self._write_score_map_prediction(batch_input, batch_output, local_rank, batch_idx)
+        if self.phase == "test" and self.write_flag.get("score_map_gt", False):
+            written += self._write_score_map_gt(batch_input, local_rank, batch_idx)
         if self.write_flag["item_path_json"]:
             out_path = self.out_dir_dict["item_path_json"] / f"r{local_rank}_B{str(batch_idx).zfill(4)}.json"
             item_paths = dict(batch_input["item_paths"])
@@ -205,6 +210,19 @@ class BatchWriter:
                 path = d / f"r{local_rank}_B{batch_idx:04}_b{b:03}_{stem}.png"
                 self._save(path, imgs[b])
                 written.append(str(path))
+        return written
+
+
+    def _write_score_map_gt(self, batch_input, local_rank, batch_idx) -> List[str]:
+        stems = [name_stem(p) for p in batch_input["item_paths"]["query/img"]]
+        if len(stems) != len(batch_input["query/score_map"]):
+            raise ValueError("num of query images and score maps are not equal")
+        imgs = self.encoder(batch_input["query/score_map"])
+        written = []
+        for b, stem in enumerate(stems):
+            path = self.out_dir_dict["score_map_gt"] / f"r{local_rank}_B{batch_idx:04}_b{b:03}_{stem}.png"
+            self._save(path, imgs[b])
+            written.append(str(path))
         return written
 
 

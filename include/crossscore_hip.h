@@ -264,6 +264,24 @@ int cs_op_preprocess_u8(const uint8_t* img, int in_h, int in_w, int in_row_bytes
  * table on the device (matplotlib "turbo" in the reference). */
 int cs_op_score_to_gray16(const float* score, long long n, int signed_range, uint16_t* out, cs_stream stream);
 int cs_op_score_to_rgb(const float* score, long long n, float vmin, float vmax, const uint8_t* lut256x3, uint8_t* out, cs_stream stream);
+/* Test phase (task/test.py): the ground-truth side of the loss.
+ * GT input stage: B device uint16 metric maps of one size (decoded 16-bit PNGs; rows in_row_elems samples apart, maps in_h * in_row_elems
+ * apart) -> fp32 [B][out_h][out_w], the maps NvsDataset compares the score maps with.  load_content (nvs_dataset.py:429-457,
+ * utils/io/images.py:32-46) first, in one of the modes below: SSIM_M1_1 m / 32767 - 1, SSIM_0_1 the same clamped to [0, 1], MAE m / 65535,
+ * MSE the MAE value squared; then the antialiased bilinear resize to (rs_h, rs_w) of cs_op_preprocess_u8 (skipped when equal to the input
+ * size) and the crop window (resize_all, nvs_dataset.py:218-241).  IEEE divisions: without a resize the output is bit-identical to the
+ * reference's map.  maps == NULL gives B "empty_image" placeholders (nvs_dataset.py:441-454): 0 for the SSIM modes, NaN for MAE / MSE,
+ * nothing is read.  1 <= B <= 1024.  scratch (device, B * in_h * rs_w floats) only when resizing; the filter tables are the image stage's
+ * cache. */
+enum { CS_METRIC_SSIM_M1_1 = 0, CS_METRIC_SSIM_0_1 = 1, CS_METRIC_MAE = 2, CS_METRIC_MSE = 3 };
+int cs_op_metric_map_u16(const uint16_t* maps, int B, int in_h, int in_w, int in_row_elems, int mode, int rs_h, int rs_w, int crop_y, int crop_x,
+                         int out_h, int out_w, float* out, float* scratch, cs_stream stream);
+/* Score-vs-GT sums: score, gt (B, H, W) fp32 -> stats (B, 6) fp64 = per image sum|s-g|, sum s, sum g, sum s^2, sum g^2, sum s*g, accumulated
+ * in fp64 (the L1 loss, Pearson correlation and PSNR of task/core.py:265-293, 379-417 follow on the host).  Two launches, a fixed order: an
+ * image's six sums have the same bits alone and at any position of any batch.  NaN propagates.  scratch: device, at least
+ * cs_score_gt_workspace_bytes(B, H, W) bytes. */
+size_t cs_score_gt_workspace_bytes(int B, int H, int W);
+int cs_op_score_gt_stats(const float* score, const float* gt, int B, int H, int W, double* stats, void* scratch, cs_stream stream);
 int cs_op_pos_bicubic(const float* pos, int G, int C, int gh, int gw, float* out, cs_stream stream);
 /* the same with the resize convention as an argument: legacy = 0 F.interpolate(size=(gh, gw)) (cs_op_pos_bicubic), 1 the reference's pinned
  * transformers 4.33.3 form scale_factor=((gh + 0.1) / G, (gw + 0.1) / G) (cs_config.pos_interp_legacy; golden tests/golden/g6_pos_legacy.npz) */
