@@ -69,6 +69,7 @@ SYMBOLS = {
     "cs_op_attention_weights": (_i, [_vp, _vp, _i, _i, _ll, _ll, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp]),
     "cs_op_layernorm": (_i, [_vp, _i, _i, _vp, _vp, _f, _vp, _vp, _vp]),
     "cs_op_ln_finalize": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "cs_op_silu_mul": (_i, [_vp, _i, _i, _i, _vp]),
     "cs_op_im2col": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "cs_op_patch_embed": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "cs_op_patch_embed_fused": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -1609,6 +1609,13 @@ int cs_op_layernorm(const float* x, int M, int C, const float* gamma, const floa
   return 0;
 }
 
+// the SwiGLU gate exactly as the forward launches it (swiglu layers): in place on M rows `ld` apart, x[m][j] = silu(x[m][j]) * x[m][F + j], j < F
+int cs_op_silu_mul(uint16_t* x, int M, int F, int ld, cs_stream stream) {
+  if (!x || M <= 0 || F <= 0 || F % 8 || ld < 2 * F || ld % 8) return fail(CS_ERR_BAD_ARG, "silu_mul: F and ld must be multiples of 8, ld >= 2 F");
+  HIPCHK(cs_silu_mul_launch(x, M, F, ld, g_op_bf16, (hipStream_t)stream));
+  return 0;
+}
+
 int cs_op_ln_finalize(const float* part, int M, int rows_padded, int sp, int C, float eps, float* stat, cs_stream stream) {
   if (!part || !stat || M <= 0 || rows_padded < M || sp <= 0 || C <= 0) return fail(CS_ERR_BAD_ARG, "ln_finalize: bad arguments");
   HIPCHK(cs_ln_finalize_launch(part, M, rows_padded, sp, C, eps, stat, (hipStream_t)stream));

@@ -474,7 +474,7 @@ __global__ __launch_bounds__(256, 2) void cs_gemm_kernel(CsGemmParams p) {
 #pragma unroll
             for (int q = 0; q < NRD; ++q) {
               const int m = mrow0 + q * RPI;
-              seg[q] += *reinterpret_cast<const f32x4_t*>(p.pos + (size_t)(m % p.Np + 1) * p.ldc + n);
+              seg[q] += *reinterpret_cast<const f32x4_t*>(p.pos + (size_t)(m % p.Np + 1) * p.N + n);
               if (p.pmean) seg[q] += patch_dc(p, m, n);
             }
           }
@@ -519,7 +519,7 @@ __global__ __launch_bounds__(256, 2) void cs_gemm_kernel(CsGemmParams p) {
             if constexpr (kResid) {
               if (p.resid) seg[q] += *reinterpret_cast<const f32x4_t*>(p.resid + (size_t)m * p.ldr + n);
             } else {
-              seg[q] += *reinterpret_cast<const f32x4_t*>(p.pos + (size_t)(m % p.Np + 1) * p.ldc + n);
+              seg[q] += *reinterpret_cast<const f32x4_t*>(p.pos + (size_t)(m % p.Np + 1) * p.N + n);
               if (p.pmean) seg[q] += patch_dc(p, m, n);
               row = (size_t)(m + m / p.Np + 1);
             }

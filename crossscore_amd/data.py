@@ -210,7 +210,7 @@ class InputStage:
 
     def batch(self, images, size):
         from .model import U8Batch
-        return U8Batch(images, size, self.mean_std)
+        return U8Batch(images, size, self.mean_std, device=self.device)
 
 
 class SimpleReferenceItems:

@@ -86,12 +86,14 @@ class U8Image:
 
 class U8Batch:
     """The images of a forward as decoded uint8 (CrossScoreNet.forward_u8 and its siblings): `images` in batch order (references item-major:
-    item 0's N views, item 1's, ...), all producing the same (H, W) window; mean_std = the six T.Normalize numbers (task/predict.py:68-74)."""
+    item 0's N views, item 1's, ...), all producing the same (H, W) window; mean_std = the six T.Normalize numbers (task/predict.py:68-74).
+    device: where the batch runs when every image is a placeholder (data None: nothing to take it from), e.g. zero_reference's reference keys."""
 
-    def __init__(self, images, size, mean_std=synth.IMAGENET_MEAN_STD):
+    def __init__(self, images, size, mean_std=synth.IMAGENET_MEAN_STD, device=None):
         self.images, self.size = list(images), (int(size[0]), int(size[1]))
         self.mean = (C.c_float * 3)(*mean_std[:3])
         self.std = (C.c_float * 3)(*mean_std[3:])
+        self._device = torch.device(device) if device is not None else None
 
     def __len__(self) -> int:
         return len(self.images)
@@ -112,7 +114,7 @@ class U8Batch:
         for im in self.images:
             if im.data is not None:
                 return im.data.device
-        return None
+        return self._device
 
 
 class _Node(torch.nn.Module):

@@ -232,6 +232,10 @@ int cs_op_layernorm(const float* x, int M, int C, const float* gamma, const floa
  * sum of squares) of every row's 64-column slices as the CS_EPI_RESID_F32_LN epilogue of that kernel writes them (sp = C / 64) ->
  * stat (rows_padded, 2) = (mean, 1 / sqrt(var + eps)), rows [M, rows_padded) zero (the consuming epilogue fetches whole 256-row tiles). */
 int cs_op_ln_finalize(const float* part, int M, int rows_padded, int sp, int C, float eps, float* stat, cs_stream stream);
+/* The gate of Dinov2SwiGLUFFN (HF modeling_dinov2.py:311-315; cs_config.swiglu) as the forward launches it: in place on M rows of 16-bit values
+ * (the op operand type) `ld` elements apart, x[m][j] = silu(x[m][j]) * x[m][F + j] for j < F, fp32 arithmetic and one rounding; the second half
+ * of each row and the elements behind 2 F are not written.  F and ld multiples of 8 (16-byte accesses), ld >= 2 F. */
+int cs_op_silu_mul(uint16_t* x, int M, int F, int ld, cs_stream stream);
 int cs_op_im2col(const float* x, uint16_t* out, int I, int H, int W, int P, int Kp, cs_stream stream);
 /* The patch embedding exactly as the forward runs it (HF modeling_dinov2.py:141-149: conv patchify = im2col + GEMM, + position rows), with
  * (centred != 0) or without the mean-centred operand form: x (I,3,H,W), w (C,3,P,P), bias (C), pos (1 + Np, C) -> out (I * (1 + Np), C) fp32,

@@ -403,3 +403,13 @@ def test_committed_bench_line_follows_the_contract():
     assert 0 < r["host_enqueue_ms_per_forward"] < r["ms_per_step"] and r["launches_per_forward"] == sum(r["launches_by_kernel"].values())
     assert all("host_enqueue_ms_per_forward" in x and x["launches_per_forward"] > 0 for x in r["ranks_seen"])
     assert r["roofline"]["traffic_source"].startswith("committed profile profiles/r0")
+
+
+def test_all_placeholder_u8_batch_keeps_its_device():
+    """zero_reference with the one-pass input stage makes every reference key a placeholder (data None): the batch's device then comes from the
+    stage that built it, not from its images (encode_references_u8 used to refuse such a batch)."""
+    from crossscore_amd.model import U8Batch, U8Image
+
+    ph = [U8Image(None, 56, 70, (56, 70)) for _ in range(3)]
+    assert U8Batch(ph, (56, 70)).device is None
+    assert U8Batch(ph, (56, 70), device="cuda:0").device == torch.device("cuda:0")
