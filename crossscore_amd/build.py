@@ -13,7 +13,9 @@ SOURCES = ["api.hip", "gemm.hip", "gemm256.hip", "attention.hip", "elementwise.h
 
 # panel.hip: its GELU arithmetic shares one wave's issue stream with the MFMAs; SLP-packed v_pk_fma_f32 (dependent-issue nops)
 # costs more there than scalar fma chains
-EXTRA_FLAGS = {"panel.hip": ["-fno-slp-vectorize"], "panel4.hip": ["-fno-slp-vectorize"]}
+# attention.hip: the same for the row-sum and rescale chains of its 16x16x32 tile loop (v_pk_add_f32 / v_pk_mul_f32 beside MFMAs), and the
+# packed form costs it the registers that hold three waves per SIMD
+EXTRA_FLAGS = {"panel.hip": ["-fno-slp-vectorize"], "panel4.hip": ["-fno-slp-vectorize"], "attention.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

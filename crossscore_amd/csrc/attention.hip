@@ -7,7 +7,8 @@
 // Q/K/V are addressed through (row stride, batch stride, head*dh column offset) so the packed projections the
 // GEMMs emit ([tokens][3C], [tokens][4C]) are consumed in place -- no head-split copies.
 //
-// Structure (wave64, MFMA 32x32x16 fp16): a workgroup = 4 waves = 128 query rows, each wave 32 rows; keys are
+// Structure (wave64; the tile loop is on MFMA 16x16x32 at dh = 48 / 64 and on MFMA 32x32x16, described here, at the other head dims -- the
+// small shape holds a higher clock at the power cap this kernel runs at; its layout is described at its loop): a workgroup = 4 waves = 128 query rows, each wave 32 rows; keys are
 // streamed in 64-key tiles, K and V staged HBM -> VGPR -> LDS (issue early / write late), double buffered, one
 // barrier per tile.  QK^T is computed "swapped" (S^T = K Q^T) so each lane owns one query column: row max and
 // row sum are lane-local plus one cross-half exchange, and the S^T accumulator IS the B operand of the PV MFMA
@@ -18,6 +19,7 @@
 #include "cs_common.h"
 #include <atomic>
 #include <math.h>
+#include <type_traits>
 
 #ifdef CS_ATTN_STAMP
 // phase clocks of the tile loop (tools/attn_phases.py): per (block < 64, wave) the cycles summed over all tiles of
@@ -34,12 +36,21 @@ namespace {
 
 template <int DH>
 struct AttnCfg {
+  static constexpr bool T16 = DH == 48 || DH == 64;  // tile loop on MFMA 16x16x32 (the head dims of the ViT-S pipeline); the others on 32x32x16
   static constexpr int KS = DH / 16;                 // QK^T k-steps (MFMA K = 16)
   static constexpr int DT = (DH + 31) / 32;          // 32-wide d tiles of O^T
+  static constexpr int KS2 = (DH + 31) / 32;         // T16: QK^T k-steps (MFMA K = 32; dh = 48: the second one is half zeros)
+  static constexpr int DT16 = DH / 16;               // T16: 16-wide d tiles of O^T (exact)
   static constexpr int CH = DH / 8;                  // 16-byte chunks per K/V row
-  static constexpr int KROW = DH * 2 + 16;           // bytes; odd multiple of 16 -> ds_read_b128 conflict free
-  static constexpr int VROW = (DH <= 16) ? 64 : (DH <= 96 ? 192 : (DH <= 128 ? 320 : 448)); // bytes; >= DT*64 and == 16 or 48 dwords (mod 64)
-  static_assert(VROW >= DT * 64 && (VROW / 4) % 32 == 16, "V row pitch");
+  // K row pitch, bytes.  32x32x16: odd multiple of 16 -> ds_read_b128 conflict free.  16x16x32: a ds_read_b128 is served in four 16-lane groups
+  // that mix 8 rows of lane group g with the other 8 rows of g + 1 (one 16-byte chunk further): with a pitch of 2 * odd chunks the 16 rows fall
+  // on the even 16-byte bank windows twice over, and the odd chunk offset moves one half to the odd windows -> conflict free (64 keys of d = 64)
+  static constexpr int KROW = T16 ? 160 : DH * 2 + 16;
+  // V row pitch, bytes.  32x32x16: >= DT*64 and == 16 or 48 dwords (mod 64).  16x16x32: a 32-lane half of a transposed read covers 8 consecutive
+  // key rows x 32 bytes, so the pitch is 8 * odd dwords: the 8 rows take the 8 distinct 8-dword bank windows (dh = 48: the packed 96-byte row)
+  static constexpr int VROW = T16 ? (DH == 64 ? 160 : 96) : (DH <= 16) ? 64 : (DH <= 96 ? 192 : (DH <= 128 ? 320 : 448));
+  static_assert(T16 ? (VROW >= DH * 2 && (VROW / 4) % 16 == 8 && KROW >= KS2 * 64 && (KROW / 16) % 4 == 2)
+                    : (VROW >= DT * 64 && (VROW / 4) % 32 == 16), "K / V row pitch");
   static constexpr int KTILE = 64 * KROW;
   static constexpr int VTILE = 64 * VROW;
   static constexpr int STAGE = KTILE + VTILE;
@@ -47,7 +58,8 @@ struct AttnCfg {
 };
 
 template <int DH, bool BF>
-__global__ __launch_bounds__(256, DH > 128 ? 1 : 2) void cs_attn_kernel(CsAttnParams p) {  // (dh = 192: 108 KB of LDS, one workgroup per CU anyway)
+// workgroups per CU: dh = 192 has 108 KB of LDS, one anyway; the 16x16x32 instantiations are held to three waves per SIMD (<= 168 registers)
+__global__ __launch_bounds__(256, DH > 128 ? 1 : (AttnCfg<DH>::T16 ? 3 : 2)) void cs_attn_kernel(CsAttnParams p) {
   using Cfg = AttnCfg<DH>;
   constexpr int KS = Cfg::KS, DT = Cfg::DT, CH = Cfg::CH, NIT = Cfg::NIT;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -70,16 +82,6 @@ __global__ __launch_bounds__(256, DH > 128 ? 1 : 2) void cs_attn_kernel(CsAttnPa
   const h16_t* Qb = p.Q + (size_t)bat * p.q_bs + head * DH;
   const h16_t* Kb = p.K + (size_t)bat * p.k_bs + head * DH;
   const h16_t* Vb = p.V + (size_t)bat * p.v_bs + head * DH;
-
-  // ---- Q^T fragments (B operand of S^T = K Q^T): lane (r,hh) holds Q[q0+r][16s + 8hh .. +7] ----
-  h16x8_t qf[KS];
-  {
-    int qr = q0 + r;
-    qr = qr < p.Lq ? qr : p.Lq - 1;
-    const h16_t* qp = Qb + (size_t)qr * p.ldq + 8 * hh;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) qf[s] = *reinterpret_cast<const h16x8_t*>(qp + 16 * s);
-  }
 
   // ---- staging maps: chunk c = tid + it*256 -> (key = c / CH, ch = c % CH); the last pass may be partial
   //      (whole waves idle: the guard is wave-uniform) ----
@@ -131,6 +133,251 @@ __global__ __launch_bounds__(256, DH > 128 ? 1 : 2) void cs_attn_kernel(CsAttnPa
     }                                                                                              \
   }
 
+  if constexpr (Cfg::T16) {
+    // ======== MFMA 16x16x32 tile loop (dh = 48, 64) ========
+    // A wave's 32 query rows are two 16-row query tiles qt; a 64-key tile is four 16-key tiles kt.  S^T = K Q^T stays swapped: A = K fragment
+    // (lane (li, g): key 16 kt + li, d = 32 s + 8 g .. + 7, one ds_read_b128 shared by both query tiles), B = Q^T from registers, and D gives
+    // lane (li, g) the query column li and the keys 16 kt + 4 g .. + 3.  The scores of key tiles (2s, 2s + 1) packed to 16 bits ARE the B operand
+    // of PV k-step s: contraction slot 8 g + j is key 32 s + 4 g + j (j < 4) or 32 s + 16 + 4 g + (j - 4); the V^T fragment takes the same order
+    // from two transposed reads (the 4-row blocks at those two key offsets).  A query row's statistics live in the four lanes li + 16 g: the
+    // reference point is common to them, the row sum stays four partials until the epilogue, and the common tile has no cross-lane operation.
+    // Rows and keys that do not exist cost nothing: a wave (or its second query tile) beyond Lq, the 16-key tiles at or beyond Lk and a PV k-step
+    // whose two key tiles are both dead are skipped by wave-uniform branches (the transposed read needs EXEC all ones); full tiles of a full
+    // wave run the branch-free instance of the tile body.
+    constexpr int KS2 = Cfg::KS2, DT16 = Cfg::DT16;
+    const int li = lane & 15, g = lane >> 4;
+    const int nqt = __builtin_amdgcn_readfirstlane(q0 >= p.Lq ? 0 : (q0 + 16 >= p.Lq ? 1 : 2));  // live query tiles of this wave
+    if constexpr (DH == 48) {  // columns 48..63 of the K rows' LDS image: the second k-step reads them, the staging never writes them
+      const int zrow = (tid >> 1) & 63;
+      *reinterpret_cast<uint4*>(smem + (tid >> 7) * Cfg::STAGE + zrow * Cfg::KROW + 96 + 16 * (tid & 1)) = make_uint4(0, 0, 0, 0);
+    }
+    // ---- Q^T fragments: lane (li, g) holds Q[q0 + 16 qt + li][32 s + 8 g .. + 7] (zeros beyond dh) ----
+    h16x8_t qf[2][KS2];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      int qr = q0 + 16 * qt + li;
+      qr = qr < p.Lq ? qr : p.Lq - 1;
+      const h16_t* qp = Qb + (size_t)qr * p.ldq + 8 * g;
+#pragma unroll
+      for (int s = 0; s < KS2; ++s) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[qt][s][j] = (_Float16)0.f;
+        if (32 * s + 32 <= DH || 32 * s + 8 * g < DH) qf[qt][s] = *reinterpret_cast<const h16x8_t*>(qp + 32 * s);
+      }
+    }
+    {  // Q is used pre-multiplied by scale*log2e (scale_log2e == 1: the producer already folded it into the Q projection)
+      const float sc = p.scale_log2e;
+      if (sc != 1.0f) {
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+          for (int s = 0; s < KS2; ++s)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              const _Float16 e = qf[qt][s][j];  // (a scalar copy first: __builtin_bit_cast applied to the vector element itself miscompiles, r3)
+              qf[qt][s][j] = __builtin_bit_cast(_Float16, f2o<BF>(o2f<BF>(__builtin_bit_cast(h16_t, e)) * sc));
+            }
+      }
+    }
+    f32x4_t ot[2][DT16];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+      for (int d = 0; d < DT16; ++d)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) ot[qt][d][e] = 0.f;
+    // Online softmax with a lazily moved reference point, as in the 32x32x16 loop below (kTau, negm through the C operand of the tile's first
+    // QK^T MFMA).  Whether to move is decided from the lane-local maxima (some lane above kTau <=> some row above kTau); only the move itself
+    // reduces a row's maximum over its four lanes, so that all four move by the same amount.
+    constexpr float kTau = 8.0f;
+    float m_run[2] = {0.f, 0.f};  // reference point of s*scale*log2e per query tile (set from the first tile)
+    float l_run[2] = {0.f, 0.f};  // running sum over this lane's keys (the other three quarters live in lanes ^16, ^32, ^48)
+    f32x4_t negm[2];
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) negm[qt][e] = 0.f;
+
+    // per-lane LDS byte offsets
+    const int koff = li * Cfg::KROW + g * 16;                        // + kt*16*KROW + s*64
+    const int voff = (4 * g + (li >> 2)) * Cfg::VROW + (li & 3) * 8;  // + (32*s [+16])*VROW + d*32
+
+    const int nt = (p.Lk + 63) / 64;
+    CS_ATTN_LOAD_TILE(0)
+    CS_ATTN_WRITE_TILE(0)
+    __syncthreads();
+#ifdef CS_ATTN_STAMP
+    unsigned long long ph[5] = {0, 0, 0, 0, 0};
+    const unsigned long long tbegin = __builtin_amdgcn_s_memtime(), rbegin = __builtin_amdgcn_s_memrealtime();
+    unsigned long long tlast = tbegin;
+#endif
+    // one 64-key tile for this wave; FULL: both query tiles and all 64 keys live (no branch, no mask), else nqt / nkt say what is
+    auto tile = [&](auto full_c, const int t, const int nkt) __attribute__((always_inline)) {
+      constexpr bool FULL = decltype(full_c)::value;
+      const char* kb = smem + (t & 1) * Cfg::STAGE;
+      const char* vb = kb + Cfg::KTILE;
+      f32x4_t st[2][4];
+      h16x8_t pf[2][2];
+      float tm[2] = {-INFINITY, -INFINITY};
+      // ---- S^T - m = K Q^T - m per 16-key tile (-m_run enters through the C operand), the ragged tail masked; lane-local maxima ----
+#pragma unroll
+      for (int kt = 0; kt < 4; ++kt) {
+        if (FULL || kt < nkt) {
+          if (!FULL) __builtin_amdgcn_sched_barrier(0);  // (the ragged instance: phases kept apart, fewer registers, its speed does not matter)
+#pragma unroll
+          for (int s = 0; s < KS2; ++s) {
+            const h16x8_t kf = *reinterpret_cast<const h16x8_t*>(kb + koff + kt * 16 * Cfg::KROW + s * 64);
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt)
+              if (FULL || qt < nqt) st[qt][kt] = mfma_16x16x32<BF>(kf, qf[qt][s], s == 0 ? negm[qt] : st[qt][kt]);
+          }
+#pragma unroll
+          for (int qt = 0; qt < 2; ++qt)
+            if (FULL || qt < nqt) {
+              if (!FULL) {
+                const int key = t * 64 + kt * 16 + 4 * g;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                  if (key + j >= p.Lk) st[qt][kt][j] = -INFINITY;
+              }
+#pragma unroll
+              for (int j = 0; j < 4; ++j) tm[qt] = fmaxf(tm[qt], st[qt][kt][j]);
+            }
+        }
+      }
+      CS_TS(0);
+      // ---- move the reference (rare after the first tiles): wave-uniform branch; st, l and O follow ----
+      if (t == 0 || __builtin_amdgcn_ballot_w64(fmaxf(tm[0], tm[1]) > kTau) != 0) {
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt)
+          if (FULL || qt < nqt) {
+            float rm = fmaxf(tm[qt], __shfl_xor(tm[qt], 16, 64));
+            rm = fmaxf(rm, __shfl_xor(rm, 32, 64));  // the row's maximum of this tile, relative to m_run
+            const float delta = t == 0 ? rm : fmaxf(rm, 0.f);
+            const float alpha = t == 0 ? 1.0f : __builtin_amdgcn_exp2f(-delta);
+            m_run[qt] += delta;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) negm[qt][e] = -m_run[qt];
+            asm volatile("" : "+v"(negm[qt]));  // keep the copies resident instead of re-materialising them per tile
+#pragma unroll
+            for (int kt = 0; kt < 4; ++kt)
+              if (FULL || kt < nkt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) st[qt][kt][j] -= delta;
+            l_run[qt] *= alpha;
+#pragma unroll
+            for (int d = 0; d < DT16; ++d)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) ot[qt][d][e] *= alpha;
+          }
+      }
+      // ---- p = 2^(s - m), row-sum partials, 16-bit pack into the PV operand (dead key tiles: zeros) ----
+      if (!FULL) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int qt = 0; qt < 2; ++qt)
+        if (FULL || qt < nqt) {
+          float ps0 = 0.f, ps1 = 0.f;  // two chains of plain v_add_f32 (packed f32 adds cost more issue cycles than they save)
+#pragma unroll
+          for (int kt = 0; kt < 4; ++kt) {
+            if (FULL || kt < nkt) {
+#pragma unroll
+              for (int j = 0; j < 4; j += 2) {
+                const float pa = __builtin_amdgcn_exp2f(st[qt][kt][j]);
+                const float pb = __builtin_amdgcn_exp2f(st[qt][kt][j + 1]);
+                ps0 += pa;
+                ps1 += pb;
+                pf[qt][kt >> 1][4 * (kt & 1) + j] = __builtin_bit_cast(_Float16, f2o<BF>(pa));
+                pf[qt][kt >> 1][4 * (kt & 1) + j + 1] = __builtin_bit_cast(_Float16, f2o<BF>(pb));
+              }
+            } else {
+#pragma unroll
+              for (int j = 0; j < 4; ++j) pf[qt][kt >> 1][4 * (kt & 1) + j] = (_Float16)0.f;
+            }
+          }
+          l_run[qt] += ps0 + ps1;
+        }
+      CS_TS(1);
+      // ---- O^T += V^T P^T : V^T fragments via transposed LDS reads, shared by both query tiles ----
+      if (!FULL) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+        if (FULL || 2 * s < nkt) {
+          const char* vrow = vb + voff + 32 * s * Cfg::VROW;
+#pragma unroll
+          for (int d = 0; d < DT16; ++d) {
+            short4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                (__attribute__((address_space(3))) short4_t*)(vrow + d * 32));
+            short4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+                (__attribute__((address_space(3))) short4_t*)(vrow + 16 * Cfg::VROW + d * 32));
+            const short8_t vf8 = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+#pragma unroll
+            for (int qt = 0; qt < 2; ++qt)
+              if (FULL || qt < nqt) ot[qt][d] = mfma_16x16x32<BF>(__builtin_bit_cast(h16x8_t, vf8), pf[qt][s], ot[qt][d]);
+          }
+        }
+      CS_TS(2);
+    };
+    // tiles [t0, t1) with one instance of the body; every wave stages, writes and meets the barrier, a dead wave does nothing else
+    auto run = [&](auto full_c, const int t0, const int t1) __attribute__((always_inline)) {
+      for (int t = t0; t < t1; ++t) {
+        if (t + 1 < nt) { CS_ATTN_LOAD_TILE(t + 1) }
+        if (decltype(full_c)::value || nqt > 0) {
+          const int left = p.Lk - t * 64;
+          tile(full_c, t, left >= 64 ? 4 : (left + 15) >> 4);
+        }
+        if (t + 1 < nt) { CS_ATTN_WRITE_TILE((t + 1) & 1) }
+        CS_TS(3);
+        __syncthreads();
+        CS_TS(4);
+      }
+    };
+    const int ntf = nqt == 2 ? ((p.Lk & 63) ? nt - 1 : nt) : 0;  // the branch-free instance: full tiles of a full wave
+    run(std::true_type{}, 0, ntf);
+    run(std::false_type{}, ntf, nt);
+#ifdef CS_ATTN_STAMP
+    if (blockIdx.x % 50 == 0 && blockIdx.x / 50 < 64 && lane == 0) {  // a sample across the whole grid
+      unsigned long long* d = g_attn_dbg + (blockIdx.x / 50 * 4 + wv) * 8;
+      for (int k = 0; k < 5; ++k) d[k] = ph[k];
+      d[5] = rbegin;
+      d[6] = __builtin_amdgcn_s_memtime() - tbegin;
+      d[7] = __builtin_amdgcn_s_memrealtime() - rbegin;  // 100 MHz
+    }
+#endif
+
+    // ---- epilogue: O[q][head*DH + d] = O^T[d][q] / l ; lane (li, g) holds d = 16 dt + 4 g .. + 3 of query 16 qt + li ----
+    // (the lane index is taken afresh from mbcnt so that no lane-dependent value of the epilogue stays in a register across the tile loop)
+    const int le = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int lie = le & 15, ge = le >> 4;
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      float l_tot = l_run[qt] + __shfl_xor(l_run[qt], 16, 64);
+      l_tot += __shfl_xor(l_tot, 32, 64);
+      const float inv = 1.0f / l_tot;
+      const int q = q0 + 16 * qt + lie;
+      if (q < p.Lq) {
+        h16_t* op = p.O + (size_t)bat * p.o_bs + (size_t)q * p.ldo + head * DH + 4 * ge;
+#pragma unroll
+        for (int d = 0; d < DT16; ++d) {
+          uint2 o;
+          o.x = pack_o16x2<BF>(ot[qt][d][0] * inv, ot[qt][d][1] * inv);
+          o.y = pack_o16x2<BF>(ot[qt][d][2] * inv, ot[qt][d][3] * inv);
+          *reinterpret_cast<uint2*>(op + 16 * d) = o;
+        }
+        if (p.lse && ge == 0) p.lse[((size_t)bat * p.heads + head) * p.Lq + q] = m_run[qt] + log2f(l_tot);
+      }
+    }
+  } else
+  {  // ======== MFMA 32x32x16 tile loop (dh = 16, 96, 128, 192) ========
+  // ---- Q^T fragments (B operand of S^T = K Q^T): lane (r,hh) holds Q[q0+r][16s + 8hh .. +7] ----
+  h16x8_t qf[KS];
+  {
+    int qr = q0 + r;
+    qr = qr < p.Lq ? qr : p.Lq - 1;
+    const h16_t* qp = Qb + (size_t)qr * p.ldq + 8 * hh;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) qf[s] = *reinterpret_cast<const h16x8_t*>(qp + 16 * s);
+  }
+
   f32x16_t ot[DT];
 #pragma unroll
   for (int d = 0; d < DT; ++d)
@@ -174,8 +421,13 @@ __global__ __launch_bounds__(256, DH > 128 ? 1 : 2) void cs_attn_kernel(CsAttnPa
   const unsigned long long tbegin = __builtin_amdgcn_s_memtime(), rbegin = __builtin_amdgcn_s_memrealtime();
   unsigned long long tlast = tbegin;
 #endif
-  for (int t = 0; t < nt; ++t) {
-    if (t + 1 < nt) { CS_ATTN_LOAD_TILE(t + 1) }
+  // Rows and keys that do not exist, at this loop's granularity: a wave whose 32 rows all lie beyond Lq stages, writes and meets the barriers and does
+  // nothing else; in the ragged last tile a second 32-key half that starts at or beyond Lk is skipped in QK^T, the exponentials and PV.  The last
+  // tile is its own instance of the body (LAST), so the full tiles carry neither the mask nor the branch.
+  const bool live_w = q0 < p.Lq;  // wave-uniform (q0 is scalar)
+  auto tile = [&](auto last_c, const int t) __attribute__((always_inline)) {
+    constexpr bool LAST = decltype(last_c)::value;
+    const bool two = !LAST || p.Lk - t * 64 > 32;  // the second 32-key half holds keys
     const char* kb = smem + (t & 1) * Cfg::STAGE;
     const char* vb = kb + Cfg::KTILE;
 
@@ -185,13 +437,18 @@ __global__ __launch_bounds__(256, DH > 128 ? 1 : 2) void cs_attn_kernel(CsAttnPa
     auto scores = [&]() {  // S^T - m = K Q^T - m : two 32-key sub-tiles (-m_run enters through the C operand), ragged tail masked
 #pragma unroll
       for (int k2 = 0; k2 < 2; ++k2) {
+        if (k2 == 0 || two) {
 #pragma unroll
-        for (int s = 0; s < KS; ++s) {
-          h16x8_t kf = *reinterpret_cast<const h16x8_t*>(kb + koff + k2 * 32 * Cfg::KROW + s * 32);
-          st[k2] = mfma_32x32x16<BF>(kf, qf[s], s == 0 ? negm : st[k2]);
+          for (int s = 0; s < KS; ++s) {
+            h16x8_t kf = *reinterpret_cast<const h16x8_t*>(kb + koff + k2 * 32 * Cfg::KROW + s * 32);
+            st[k2] = mfma_32x32x16<BF>(kf, qf[s], s == 0 ? negm : st[k2]);
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) st[k2][e] = -INFINITY;
         }
       }
-      if (t == nt - 1 && (p.Lk & 63)) {  // keys >= Lk : wave-uniform branch
+      if (LAST && (p.Lk & 63)) {  // keys >= Lk : wave-uniform branch
         const int kbase = t * 64 + 4 * hh;
 #pragma unroll
         for (int k2 = 0; k2 < 2; ++k2)
@@ -233,6 +490,7 @@ __global__ __launch_bounds__(256, DH > 128 ? 1 : 2) void cs_attn_kernel(CsAttnPa
       for (int k2 = 0; k2 < 2; ++k2)
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
+          if (k2 == 1 && !two) continue;
 #pragma unroll
           for (int j = 0; j < 8; j += 2) {
             const float pa = __builtin_amdgcn_exp2f(st[k2][8 * s2 + j]);
@@ -261,6 +519,7 @@ __global__ __launch_bounds__(256, DH > 128 ? 1 : 2) void cs_attn_kernel(CsAttnPa
     for (int k2 = 0; k2 < 2; ++k2)
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
+        if (k2 == 1 && !two) continue;
         const char* vrow = vb + voff + (k2 * 32 + 16 * s2) * Cfg::VROW;
 #pragma unroll
         for (int d = 0; d < DT; ++d) {
@@ -274,11 +533,19 @@ __global__ __launch_bounds__(256, DH > 128 ? 1 : 2) void cs_attn_kernel(CsAttnPa
       }
 
     CS_TS(2);
-    if (t + 1 < nt) { CS_ATTN_WRITE_TILE((t + 1) & 1) }
-    CS_TS(3);
-    __syncthreads();
-    CS_TS(4);
-  }
+  };
+  auto run = [&](auto last_c, const int t0, const int t1) __attribute__((always_inline)) {
+    for (int t = t0; t < t1; ++t) {
+      if (t + 1 < nt) { CS_ATTN_LOAD_TILE(t + 1) }
+      if (live_w) tile(last_c, t);
+      if (t + 1 < nt) { CS_ATTN_WRITE_TILE((t + 1) & 1) }
+      CS_TS(3);
+      __syncthreads();
+      CS_TS(4);
+    }
+  };
+  run(std::false_type{}, 0, nt - 1);
+  run(std::true_type{}, nt - 1, nt);
 #ifdef CS_ATTN_STAMP
   if (blockIdx.x % 50 == 0 && blockIdx.x / 50 < 64 && lane == 0) {  // a sample across the whole grid
     unsigned long long* d = g_attn_dbg + (blockIdx.x / 50 * 4 + wv) * 8;
@@ -309,6 +576,7 @@ __global__ __launch_bounds__(256, DH > 128 ? 1 : 2) void cs_attn_kernel(CsAttnPa
         }
       }
     if (p.lse && hh == 0) p.lse[((size_t)bat * p.heads + head) * p.Lq + q] = m_run + log2f(l_tot);
+  }
   }
 }
 

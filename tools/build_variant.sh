@@ -11,7 +11,7 @@ cp $R/crossscore_amd/*.py "$D/crossscore_amd/"
 cp -r $R/crossscore_amd/config "$D/crossscore_amd/" 2>/dev/null || true
 OBJS=""
 for o in $R/crossscore_amd/build/*.o; do b=$(basename $o .o); [ "$b.hip" = "$SRC" ] || OBJS="$OBJS $o"; done
-EXTRA=""; case $SRC in panel.hip|panel4.hip) EXTRA="-fno-slp-vectorize";; esac
+EXTRA=""; case $SRC in panel.hip|panel4.hip|attention.hip) EXTRA="-fno-slp-vectorize";; esac
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value $EXTRA "$@" -c $R/crossscore_amd/csrc/$SRC -o $D/var.o
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $D/crossscore_amd/libcrossscore_hip.so $OBJS $D/var.o
 rm $D/var.o
