@@ -80,6 +80,13 @@ hipError_t cs_metric_map_launch(const uint16_t* maps, int B, int in_h, int in_w,
                                 int crop_x, int oh, int ow, float* out, float* scratch, hipStream_t stream);
 int cs_score_gt_slabs(size_t hw);
 hipError_t cs_score_gt_stats_launch(const float* score, const float* gt, int B, size_t hw, double* scratch, double* stats, hipStream_t stream);
+// png.hip
+int cs_png_size_supported(int H, int W);
+size_t cs_png_bound_bytes(int kind, int H, int W);
+size_t cs_png_staging_bytes(int kind, int I, int H, int W);
+hipError_t cs_png_encode_launch(const void* pixels, int kind, int I, int H, int W, long long image_stride, uint8_t* out, size_t slot_bytes,
+                                uint32_t* lengths, void* workspace, hipStream_t st);
+hipError_t cs_denorm_rgb8_launch(const float* chw, int I, int H, int W, const float* mean3, const float* std3, uint8_t* out, hipStream_t st);
 }
 
 namespace {
@@ -1754,6 +1761,40 @@ int cs_op_score_gt_stats(const float* score, const float* gt, int B, int H, int 
 int cs_op_score_to_rgb(const float* score, long long n, float vmin, float vmax, const uint8_t* lut256x3, uint8_t* out, cs_stream stream) {
   if (!score || !out || !lut256x3 || n <= 0 || !(vmax > vmin)) return fail(CS_ERR_BAD_ARG, "score_to_rgb: bad arguments");
   HIPCHK(cs_score_rgb_launch(score, (size_t)n, vmin, vmax, lut256x3, out, (hipStream_t)stream));
+  return 0;
+}
+
+size_t cs_png_bound(int kind, int H, int W) {
+  if (H <= 0 || W <= 0 || !cs_png_size_supported(H, W)) return 0;
+  return cs_png_bound_bytes(kind, H, W);
+}
+
+size_t cs_png_workspace_bytes(int kind, int I, int H, int W) {
+  if (H <= 0 || W <= 0 || !cs_png_size_supported(H, W)) return 0;
+  return cs_png_staging_bytes(kind, I, H, W);
+}
+
+int cs_op_png_encode(const void* pixels, int kind, int I, int H, int W, long long image_stride_bytes, uint8_t* out, size_t slot_bytes,
+                     uint32_t* lengths, void* workspace, cs_stream stream) {
+  if (kind != CS_PNG_GRAY16 && kind != CS_PNG_RGB8) return fail(CS_ERR_BAD_ARG, "png_encode: kind %d is neither CS_PNG_GRAY16 nor CS_PNG_RGB8", kind);
+  if (I <= 0 || I > 65535 || H <= 0 || W <= 0) return fail(CS_ERR_BAD_ARG, "png_encode: bad sizes (I %d, H %d, W %d; 1 <= I <= 65535)", I, H, W);
+  if (!cs_png_size_supported(H, W)) return fail(CS_ERR_UNSUPPORTED, "png_encode: %d x %d is larger than 4096 x 4096", H, W);
+  const long long image_bytes = (long long)H * W * (kind == CS_PNG_GRAY16 ? 2 : 3);
+  if (image_stride_bytes < image_bytes || (kind == CS_PNG_GRAY16 && (image_stride_bytes & 1)))
+    return fail(CS_ERR_BAD_ARG, "png_encode: image stride %lld is below the image's %lld bytes (or odd for 16-bit samples)", image_stride_bytes, image_bytes);
+  if (slot_bytes < cs_png_bound_bytes(kind, H, W))
+    return fail(CS_ERR_BAD_ARG, "png_encode: slot of %zu bytes is below the bound %zu of this size", slot_bytes, cs_png_bound_bytes(kind, H, W));
+  if (!pixels || !out || !lengths || !workspace) return fail(CS_ERR_BAD_ARG, "png_encode: null pointer");
+  if (kind == CS_PNG_GRAY16 && ((uintptr_t)pixels & 1)) return fail(CS_ERR_BAD_ARG, "png_encode: 16-bit samples must be 2-byte aligned");
+  if ((uintptr_t)workspace & 15) return fail(CS_ERR_BAD_ARG, "png_encode: the workspace must be 16-byte aligned");
+  HIPCHK(cs_png_encode_launch(pixels, kind, I, H, W, image_stride_bytes, out, slot_bytes, lengths, workspace, (hipStream_t)stream));
+  return 0;
+}
+
+int cs_op_denorm_to_rgb8(const float* chw, int I, int H, int W, const float* mean3, const float* std3, uint8_t* out, cs_stream stream) {
+  if (!chw || !out || !mean3 || !std3 || I <= 0 || H <= 0 || W <= 0 || (long long)I * H * W > (1ll << 38))
+    return fail(CS_ERR_BAD_ARG, "denorm_to_rgb8: bad arguments");
+  HIPCHK(cs_denorm_rgb8_launch(chw, I, H, W, mean3, std3, out, (hipStream_t)stream));
   return 0;
 }
 

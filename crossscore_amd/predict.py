@@ -31,7 +31,7 @@ from .data import (InputStage, ReferenceTokenCache, SimpleReferenceItems, decode
                    load_query_batch_u8, read_image_u8)
 from .model import CrossScoreNet, load_lightning_checkpoint
 from .pipeline import ForwardPipeline
-from .writers import BatchWriter, ScoreSummariser
+from .writers import BatchWriter, ScoreSummariser, png_encoder_choice
 
 
 def resolve_out_dir(cfg, now: Optional[str] = None) -> str:
@@ -59,9 +59,12 @@ def seed_everything(seed: int) -> None:
 
 
 def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None) -> Dict[str, object]:
-    """Runs the predict loop; returns {"out_dir", "files", "rows", "query_images_per_sec"}."""
+    """Runs the predict loop; returns {"out_dir", "files", "rows", "input_stage", "png_encoder", "png_files", "query_images_per_sec"}."""
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.predict needs a GPU: the scoring path has no CPU fallback")
+    # this_main.png_encoder (this build's key, default "host"): who compresses the PNG outputs -- PIL on the writer's threads, or the device
+    # (writers.PngEncoder: conversion, de-normalisation and compression queued behind the forward; pixel-exact, not byte-equal)
+    png_encoder = png_encoder_choice(cfg)
     seed_everything(int(cfg.lightning.seed))
     rank, local_rank, world = parallel.init_from_env()
     device = torch.device("cuda", local_rank if world > 1 else 0)
@@ -91,7 +94,8 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
     net.load_state_dict(state_dict, strict=True)
     net = net.to(device)
 
-    writer = (BatchWriter(cfg, "predict", net.img_mean_std, device, workers=max(1, int(cfg.data.loader.validation.num_workers) // 2))
+    writer = (BatchWriter(cfg, "predict", net.img_mean_std, device, workers=max(1, int(cfg.data.loader.validation.num_workers) // 2),
+                          png_encoder=png_encoder)
               if cfg.logger.predict.write.flag.batch else None)
     summariser = ScoreSummariser(cfg.model.predict.metric.type, cfg.model.predict.metric.min, cfg.logger.predict.out_dir)
 
@@ -206,6 +210,7 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
                                  f"{cfg.logger.predict.out_dir}")
     return {"out_dir": cfg.logger.predict.out_dir, "files": files, "rows": summariser.rows,
             "input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
+            "png_encoder": png_encoder, "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
             "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}  # the whole scoring loop: input stage, forwards, output stage
 
 

@@ -8,8 +8,13 @@ Mirrors
   get_vrange / metric_map_write / gray2rgb      batch_writer.py:9-21, utils/io/images.py:49-63, utils/misc/image.py:37-52
   SummaryWriterPredictedOnlineTestPrediction    utils/io/score_summariser.py:142-250 (per-image mean -> CSV, "%.4f")
 The float -> integer image conversion runs on the GPU (cs_op_score_to_gray16 / cs_op_score_to_rgb: 2 or 3 bytes per pixel cross
-PCIe instead of 4); PNG compression is PIL's, as in the reference.  The composite matplotlib "vis" figure (task/core.py:422-434) is
-not reproduced.
+PCIe instead of 4).  PNG compression has two forms, chosen by `this_main.png_encoder`:
+  host (default)   PIL's, on a thread pool, as in the reference (imageio); the processed query / reference images are de-normalised on the host
+  gpu              cs_op_png_encode: score maps and processed images are converted (cs_op_score_to_*, cs_op_denorm_to_rgb8) and compressed on
+                   the device, queued behind the forward; finished files cross PCIe into pinned memory and the pool threads only write them.
+                   Pixel-exact, valid PNGs, not byte-equal to PIL's (independent 16-KiB segments, fixed-Huffman / stored blocks: larger files).
+Attention-weight images and the item-path JSON always take the host path.  The composite matplotlib "vis" figure (task/core.py:422-434)
+is not reproduced.
 """
 from __future__ import annotations
 
@@ -17,6 +22,7 @@ import csv
 import ctypes as C
 import json
 import os
+import threading
 from pathlib import Path
 from typing import Dict, List, Sequence
 
@@ -76,7 +82,8 @@ class ScoreMapEncoder:
         self.device = device
         self._lut = torch.from_numpy(colormap_table("turbo").reshape(-1)).to(device) if colour_mode == "rgb" else None
 
-    def __call__(self, score: torch.Tensor) -> np.ndarray:
+    def device_image(self, score: torch.Tensor) -> torch.Tensor:
+        """The integer image on the device: (B, H, W) int16 (16-bit samples, unsigned in memory) or (B, H, W, 3) uint8."""
         lib = _lib.load()
         score = score.contiguous()
         if score.dtype != torch.float32 or not score.is_cuda:
@@ -86,11 +93,111 @@ class ScoreMapEncoder:
         if self.colour_mode == "gray":
             out = torch.empty(score.shape, dtype=torch.int16, device=score.device)  # 16-bit samples (viewed unsigned on the host)
             _lib.check(lib.cs_op_score_to_gray16(C.c_void_p(score.data_ptr()), n, 1 if self.intrinsic == [-1, 1] else 0, C.c_void_p(out.data_ptr()), st))
-            return out.cpu().numpy().view(np.uint16)
+            return out
         out = torch.empty(tuple(score.shape) + (3,), dtype=torch.uint8, device=score.device)
         _lib.check(lib.cs_op_score_to_rgb(C.c_void_p(score.data_ptr()), n, float(self.vis[0]), float(self.vis[1]), C.c_void_p(self._lut.data_ptr()),
                                          C.c_void_p(out.data_ptr()), st))
-        return out.cpu().numpy()
+        return out
+
+    def __call__(self, score: torch.Tensor) -> np.ndarray:
+        out = self.device_image(score).cpu().numpy()
+        return out.view(np.uint16) if self.colour_mode == "gray" else out
+
+
+class PngHandle:
+    """Files of one asynchronous cs_op_png_encode call: bytes(i) waits for the call's event, then cuts file i out of the pinned block."""
+
+    def __init__(self, event, host_out: torch.Tensor, host_len: torch.Tensor):
+        self._event, self._out, self._len = event, host_out, host_len
+        self._lock = threading.Lock()
+        self._arr = None
+
+    def __len__(self) -> int:
+        return int(self._len.shape[0])
+
+    def bytes(self, i: int) -> bytes:
+        with self._lock:
+            if self._arr is None:
+                self._event.synchronize()
+                self._arr = (self._out.numpy(), self._len.numpy())
+        out, ln = self._arr
+        if int(ln[i]) <= 0:  # the device's sign of a file that did not fit its slot (cs_png_bound would be wrong)
+            raise RuntimeError(f"cs_op_png_encode produced no file for image {i}")
+        return out[i, : int(ln[i])].tobytes()
+
+    def result(self) -> List[bytes]:
+        return [self.bytes(i) for i in range(len(self))]
+
+
+class PngEncoder:
+    """Device integer images -> PNG files, compressed on the device (cs_op_png_encode).  (I, H, W) int16 / uint16 tensors become 16-bit
+    grayscale files, (I, H, W, 3) uint8 tensors 8-bit RGB files; pixel-exact, not byte-equal to PIL's."""
+
+    @staticmethod
+    def _kind(pixels: torch.Tensor):
+        if not pixels.is_cuda:
+            raise ValueError("PngEncoder takes CUDA tensors")
+        if pixels.dim() == 3 and pixels.dtype in (torch.int16, getattr(torch, "uint16", torch.int16)):
+            return _lib.PNG_GRAY16, 2
+        if pixels.dim() == 4 and pixels.shape[-1] == 3 and pixels.dtype == torch.uint8:
+            return _lib.PNG_RGB8, 3
+        raise ValueError(f"PngEncoder takes (I, H, W) 16-bit or (I, H, W, 3) uint8 tensors, not {tuple(pixels.shape)} {pixels.dtype}")
+
+    def encode_async(self, pixels: torch.Tensor) -> PngHandle:
+        """Queues the encode and the copy to pinned memory on the current stream; returns without waiting for either."""
+        lib = _lib.load()
+        kind, bpp = self._kind(pixels)
+        pixels = pixels.contiguous()
+        I, H, W = (int(v) for v in pixels.shape[:3])
+        if I <= 0 or H <= 0 or W <= 0:
+            raise ValueError(f"PngEncoder: empty batch or image {tuple(pixels.shape)}")
+        dev = pixels.device
+        slot = int(lib.cs_png_bound(kind, H, W))
+        if slot == 0:
+            raise NotImplementedError(f"PngEncoder: {H} x {W} images are larger than the encoder takes (4096 x 4096)")
+        slot = (slot + 63) // 64 * 64
+        out = torch.empty((I, slot), dtype=torch.uint8, device=dev)
+        lengths = torch.empty((I,), dtype=torch.int32, device=dev)
+        work = torch.empty((int(lib.cs_png_workspace_bytes(kind, I, H, W)),), dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev)
+        _lib.check(lib.cs_op_png_encode(C.c_void_p(pixels.data_ptr()), kind, I, H, W, H * W * bpp, C.c_void_p(out.data_ptr()), slot,
+                                        C.c_void_p(lengths.data_ptr()), C.c_void_p(work.data_ptr()), C.c_void_p(st.cuda_stream)))
+        host_out = torch.empty((I, slot), dtype=torch.uint8, pin_memory=True)
+        host_len = torch.empty((I,), dtype=torch.int32, pin_memory=True)
+        host_out.copy_(out, non_blocking=True)
+        host_len.copy_(lengths, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(st)
+        return PngHandle(ev, host_out, host_len)
+
+    def encode(self, pixels: torch.Tensor) -> List[bytes]:
+        return self.encode_async(pixels).result()
+
+
+def denorm_to_rgb8(imgs: torch.Tensor, img_mean_std: torch.Tensor) -> torch.Tensor:
+    """cs_op_denorm_to_rgb8: (I, 3, H, W) fp32 processed images on the device -> (I, H, W, 3) uint8, BatchWriter._de_norm_u8 bit for bit."""
+    lib = _lib.load()
+    imgs = imgs.detach().contiguous()
+    if imgs.dtype != torch.float32 or not imgs.is_cuda or imgs.dim() != 4 or imgs.shape[1] != 3:
+        raise ValueError("denorm_to_rgb8 takes (I, 3, H, W) fp32 CUDA tensors")
+    I, _, H, W = (int(v) for v in imgs.shape)
+    ms = [float(v) for v in img_mean_std.detach().float().cpu().tolist()]
+    mean, std = (C.c_float * 3)(*ms[:3]), (C.c_float * 3)(*ms[3:])
+    out = torch.empty((I, H, W, 3), dtype=torch.uint8, device=imgs.device)
+    _lib.check(lib.cs_op_denorm_to_rgb8(C.c_void_p(imgs.data_ptr()), I, H, W, mean, std, C.c_void_p(out.data_ptr()),
+                                        C.c_void_p(torch.cuda.current_stream(imgs.device).cuda_stream)))
+    return out
+
+
+PNG_ENCODERS = ("host", "gpu")
+
+
+def png_encoder_choice(cfg) -> str:
+    """this_main.png_encoder (this build's key): host (default) | gpu."""
+    v = cfg.this_main.get("png_encoder", "host")
+    if v not in PNG_ENCODERS:
+        raise ValueError(f"this_main.png_encoder={v!r} not supported: host | gpu")
+    return v
 
 
 def save_png(path, arr: np.ndarray) -> None:
@@ -100,13 +207,25 @@ def save_png(path, arr: np.ndarray) -> None:
     Image.fromarray(arr).save(path)
 
 
+def save_png_bytes(path, handle: PngHandle, i: int) -> None:
+    data = handle.bytes(i)  # waits for the encode's event in the pool thread
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 class BatchWriter:
     """PNG compression runs on a small thread pool (zlib releases the GIL): the arrays are materialised in the calling thread,
-    the files are complete after finish()."""
+    the files are complete after finish().  With png_encoder="gpu" the score maps and the processed query / reference images are converted
+    and compressed on the device (PngEncoder): write_out only queues that work, the pool threads wait for its event and write the bytes."""
 
-    def __init__(self, cfg, phase: str, img_mean_std: torch.Tensor, device: torch.device, workers: int = 4):
+    def __init__(self, cfg, phase: str, img_mean_std: torch.Tensor, device: torch.device, workers: int = 4, png_encoder: str = "host"):
         if phase not in ("test", "predict"):
             raise ValueError(f"Phase {phase} not supported. Has to be a Lightening phase test/predict.")
+        if png_encoder not in PNG_ENCODERS:
+            raise ValueError(f"png_encoder {png_encoder!r} not supported: host | gpu")
+        self.png_encoder = png_encoder
+        self._png = PngEncoder() if png_encoder == "gpu" else None
+        self._stats = {"png_gpu_files": 0, "png_host_files": 0}
         self.cfg = cfg
         self.out_dir = Path(cfg.logger[phase].out_dir)
         self.write_config = cfg.logger[phase].write.config
@@ -146,20 +265,37 @@ class BatchWriter:
             written.append(str(out_path))
         if self.write_flag["image_query"]:
             stems = [name_stem(p) for p in batch_input["item_paths"]["query/img"]]
+            paths = []
             for b, (stem, img) in enumerate(zip(stems, batch_input["query/img"])):
                 path = self.out_dir_dict["image_query"] / f"r{local_rank}_B{batch_idx:04}_b{b:03}_{stem}.png"
-                self._save(path, self._de_norm_u8(img))
+                paths.append(path)
+                if self._png is None:
+                    self._save(path, self._de_norm_u8(img))
                 written.append(str(path))
+            if self._png is not None and paths:
+                self._save_gpu(paths, denorm_to_rgb8(batch_input["query/img"][: len(paths)], self.img_mean_std))
         if self.write_flag["image_reference"] and len(batch_input["item_paths"]["reference/cross/imgs"]) > 0:
             stems = [name_stem(p) for p in batch_input["item_paths"]["query/img"]]
             ref_paths = np.array(batch_input["item_paths"]["reference/cross/imgs"]).T  # (B, N_ref)
+            paths, picks = [], []
             for b, stem in enumerate(stems):
                 d = self.out_dir_dict["image_reference"] / f"r{local_rank}_B{batch_idx:04}_b{b:03}_{stem}" / "cross"
                 d.mkdir(parents=True, exist_ok=True)
                 for ref_idx, (rp, img) in enumerate(zip(ref_paths[b], batch_input["reference/cross/imgs"][b])):
                     path = d / f"ref{ref_idx:02}_{name_stem(rp)}.png"
-                    self._save(path, self._de_norm_u8(img))
+                    if self._png is None:
+                        self._save(path, self._de_norm_u8(img))
+                    else:
+                        paths.append(path)
+                        picks.append((b, ref_idx))
                     written.append(str(path))
+            if self._png is not None and paths:
+                refs = batch_input["reference/cross/imgs"]
+                n_ref = int(refs.shape[1])
+                flat = refs.reshape((-1,) + tuple(refs.shape[2:]))
+                if picks != [(b, r) for b in range(int(refs.shape[0])) for r in range(n_ref)]:
+                    flat = flat[torch.tensor([b * n_ref + r for b, r in picks], device=flat.device)]
+                self._save_gpu(paths, denorm_to_rgb8(flat, self.img_mean_std))
         if self.write_attn and len(batch_input["item_paths"]["reference/cross/imgs"]) > 0:
             written += self._write_attn_weights(batch_input, batch_output, local_rank, batch_idx)
         return written
@@ -183,7 +319,29 @@ class BatchWriter:
         return written
 
     def _save(self, path, arr: np.ndarray) -> None:
+        self._stats["png_host_files"] += 1
         self._pending.append(self._pool.submit(save_png, path, np.ascontiguousarray(arr)))
+
+    def _save_gpu(self, paths, pixels: torch.Tensor) -> None:
+        """Device integer images -> files at `paths`: the encode and its copy to pinned memory are queued here, waited for in the pool."""
+        if len(paths) != int(pixels.shape[0]):
+            raise ValueError("num of output paths and images are not equal")
+        handle = self._png.encode_async(pixels)
+        self._stats["png_gpu_files"] += len(paths)
+        for i, path in enumerate(paths):
+            self._pending.append(self._pool.submit(save_png_bytes, path, handle, i))
+
+    def _save_score_maps(self, paths, score: torch.Tensor) -> None:
+        if self._png is not None:
+            self._save_gpu(paths, self.encoder.device_image(score))
+            return
+        imgs = self.encoder(score)
+        for b, path in enumerate(paths):
+            self._save(path, imgs[b])
+
+    def stats(self) -> Dict[str, int]:
+        """Files queued so far by encoder: {"png_gpu_files", "png_host_files"}."""
+        return dict(self._stats)
 
     def finish(self) -> None:
         """Waits for every queued file (re-raises the first failure)."""
@@ -205,11 +363,9 @@ class BatchWriter:
             d.mkdir(parents=True, exist_ok=True)
             if len(stems) != len(batch_output[key]):
                 raise ValueError("num of query images and score maps are not equal")
-            imgs = self.encoder(batch_output[key])
-            for b, stem in enumerate(stems):
-                path = d / f"r{local_rank}_B{batch_idx:04}_b{b:03}_{stem}.png"
-                self._save(path, imgs[b])
-                written.append(str(path))
+            paths = [d / f"r{local_rank}_B{batch_idx:04}_b{b:03}_{stem}.png" for b, stem in enumerate(stems)]
+            self._save_score_maps(paths, batch_output[key])
+            written += [str(p) for p in paths]
         return written
 
 
@@ -217,13 +373,9 @@ class BatchWriter:
         stems = [name_stem(p) for p in batch_input["item_paths"]["query/img"]]
         if len(stems) != len(batch_input["query/score_map"]):
             raise ValueError("num of query images and score maps are not equal")
-        imgs = self.encoder(batch_input["query/score_map"])
-        written = []
-        for b, stem in enumerate(stems):
-            path = self.out_dir_dict["score_map_gt"] / f"r{local_rank}_B{batch_idx:04}_b{b:03}_{stem}.png"
-            self._save(path, imgs[b])
-            written.append(str(path))
-        return written
+        paths = [self.out_dir_dict["score_map_gt"] / f"r{local_rank}_B{batch_idx:04}_b{b:03}_{stem}.png" for b, stem in enumerate(stems)]
+        self._save_score_maps(paths, batch_input["query/score_map"])
+        return [str(p) for p in paths]
 
 
 class ScoreSummariser:

@@ -268,6 +268,29 @@ int cs_op_preprocess_u8(const uint8_t* img, int in_h, int in_w, int in_row_bytes
  * table on the device (matplotlib "turbo" in the reference). */
 int cs_op_score_to_gray16(const float* score, long long n, int signed_range, uint16_t* out, cs_stream stream);
 int cs_op_score_to_rgb(const float* score, long long n, float vmin, float vmax, const uint8_t* lut256x3, uint8_t* out, cs_stream stream);
+/* PNG files from the device.  I device images of one size and one kind -> I complete PNG files in device memory, file i at
+ * out + i * slot_bytes, lengths[i] bytes long.  Replaces the compression half of the reference's writers: imageio.imwrite behind
+ * metric_map_write (utils/io/images.py:49-63) and behind the image outputs of batch_writer.py:117-135; the integer images come from
+ * cs_op_score_to_gray16 / cs_op_score_to_rgb / cs_op_denorm_to_rgb8.  kind CS_PNG_GRAY16: native-endian uint16, one sample per pixel (bit depth 16,
+ * colour type 0); CS_PNG_RGB8: uint8 HWC (bit depth 8, colour type 2).  Rows are contiguous, images image_stride_bytes apart.
+ * Every byte of a file is produced on the device (signature, IHDR, IDAT framing, zlib header, deflate data, Adler-32, chunk CRCs, IEND) in two
+ * launches, whatever I is; the call does not wait for the device.  Guaranteed: a valid PNG whose decoded pixels equal the input exactly, and
+ * bytes that depend on the image's pixels, size and kind alone (not on I, its position in the batch or the other images).  NOT guaranteed:
+ * byte equality with any other encoder (PIL, imageio, libpng) -- the stream is cut into independent 16-KiB segments (one IDAT chunk each,
+ * fixed-Huffman or stored blocks, Sub filter), so files are larger than zlib's.
+ * 1 <= H, W <= 4096 (CS_ERR_UNSUPPORTED above), 1 <= I <= 65535.  slot_bytes >= the bound of the size; workspace: device, 16-byte aligned, at
+ * least the workspace size of (kind, I, H, W).  The two size functions are host arithmetic (no device is touched; 0 for sizes the encoder does
+ * not take); bad arguments are rejected before anything is launched. */
+enum { CS_PNG_GRAY16 = 0, CS_PNG_RGB8 = 1 };
+size_t cs_png_bound(int kind, int H, int W);
+size_t cs_png_workspace_bytes(int kind, int I, int H, int W);
+int cs_op_png_encode(const void* pixels, int kind, int I, int H, int W, long long image_stride_bytes, uint8_t* out, size_t slot_bytes,
+                     uint32_t* lengths, void* workspace, cs_stream stream);
+/* de_norm_img + u8 (utils/misc/image.py:25-34, utils/io/images.py:20-23; batch_writer.py:117-135): I processed images fp32 CHW -> uint8 HWC,
+ * x * std, then + mean, then * 255, each rounded on its own (no fma), truncated.  Values are clamped to [0, 255] first (NaN -> 0): that agrees
+ * with the host form (a C cast) on every value the input stage produces (u8 / 255 normalised and de-normalised stays inside [0, 255]); outside
+ * that range the host cast is undefined.  mean3 / std3 are HOST pointers. */
+int cs_op_denorm_to_rgb8(const float* chw, int I, int H, int W, const float* mean3, const float* std3, uint8_t* out, cs_stream stream);
 /* Test phase (task/test.py): the ground-truth side of the loss.
  * GT input stage: B device uint16 metric maps of one size (decoded 16-bit PNGs; rows in_row_elems samples apart, maps in_h * in_row_elems
  * apart) -> fp32 [B][out_h][out_w], the maps NvsDataset compares the score maps with.  load_content (nvs_dataset.py:429-457,

@@ -1,5 +1,6 @@
 """End-to-end predict driver on a synthetic image directory: 32 query PNGs + 20 reference PNGs at 540x720, ViT-S, 5 references per
-query, batch 8 -- wall time per stage with the reference-token cache on / off and with / without PNG outputs."""
+query, batch 8 -- wall time per stage with the reference-token cache on / off, with / without PNG outputs, and (for the legs that write PNGs)
+with the host and the gpu PNG encoder (this_main.png_encoder), alternating inside the one run."""
 import json, os, sys, tempfile, time
 import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
@@ -23,13 +24,14 @@ sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, 1).items()}
 # fused = this_main.fused_input_stage (uint8 in, tokens out; "auto" takes it when no processed image is written)
 for rnd in range(2):  # (the first round pays table builds, stream probes and page-ins)
     for cache in (True, False):
-        for write, fused in (("all", "auto"), ("maps", False), ("maps", "auto"), (False, False), (False, "auto")):
+        for write, fused, enc in (("all", "auto", "host"), ("all", "auto", "gpu"), ("maps", False, "host"), ("maps", False, "gpu"), ("maps", "auto", "host"),
+                                  ("maps", "auto", "gpu"), (False, False, "host"), (False, "auto", "host")):
             over = [f"data.dataset.query_dir={qd}", f"data.dataset.reference_dir={rd}", f"this_main.cache_reference_tokens={cache}",
-                    f"logger.predict.out_dir={root}/out_{rnd}_{cache}_{write}_{fused}", f"logger.predict.write.flag.batch={bool(write)}",
-                    f"this_main.fused_input_stage={fused}"]
+                    f"logger.predict.out_dir={root}/out_{rnd}_{cache}_{write}_{fused}_{enc}", f"logger.predict.write.flag.batch={bool(write)}",
+                    f"this_main.fused_input_stage={fused}", f"this_main.png_encoder={enc}"]
             if write == "maps":
                 over += ["logger.predict.write.flag.image_query=False", "logger.predict.write.flag.image_reference=False"]
             t0 = time.perf_counter(); res = predict(load_config("default_predict", over), state_dict=sd, now="T"); dt = time.perf_counter() - t0
-            print(json.dumps({"round": rnd, "cache_reference_tokens": cache, "write_png": write, "input_stage": res["input_stage"].split(" ")[0],
+            print(json.dumps({"round": rnd, "cache_reference_tokens": cache, "write_png": write, "png_encoder": enc, "input_stage": res["input_stage"].split(" ")[0],
                               "wall_s": round(dt, 2), "query_images_per_sec_wall": round(32 / dt, 1),
                               "query_images_per_sec_loop": round(res["query_images_per_sec"], 1), "files": len(res["files"])}), flush=True)
