@@ -12,6 +12,7 @@ CS_OK, CS_ERR_BAD_ARG, CS_ERR_UNSUPPORTED, CS_ERR_STATE, CS_ERR_HIP = range(5)
 # cs_op_metric_map_u16 modes (CS_METRIC_*): the GT map's load_content conversion, by (metric type, metric min)
 METRIC_SSIM_M1_1, METRIC_SSIM_0_1, METRIC_MAE, METRIC_MSE = range(4)
 PNG_GRAY16, PNG_RGB8 = 0, 1  # cs_op_png_encode kinds (CS_PNG_*)
+GTMAP_SSIM, GTMAP_MAE = 0, 1  # cs_op_gt_metric_map_u8 kinds (CS_GTMAP_*)
 
 # CsEpilogue (csrc/cs_common.h)
 DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2  # cs_set_weight_typed
@@ -90,6 +91,7 @@ SYMBOLS = {
     "cs_op_png_encode": (_i, [_vp, _i, _i, _i, _i, _ll, _vp, _sz, _vp, _vp, _vp]),
     "cs_op_denorm_to_rgb8": (_i, [_vp, _i, _i, _i, _fp, _fp, _vp, _vp]),
     "cs_op_metric_map_u16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "cs_op_gt_metric_map_u8": (_i, [_vp, _vp, _i, _i, _i, _ll, _i, _vp, _i, _vp]),
     "cs_score_gt_workspace_bytes": (_sz, [_i, _i, _i]),
     "cs_op_score_gt_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "cs_op_preprocess_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),

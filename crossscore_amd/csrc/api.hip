@@ -87,6 +87,10 @@ size_t cs_png_staging_bytes(int kind, int I, int H, int W);
 hipError_t cs_png_encode_launch(const void* pixels, int kind, int I, int H, int W, long long image_stride, uint8_t* out, size_t slot_bytes,
                                 uint32_t* lengths, void* workspace, hipStream_t st);
 hipError_t cs_denorm_rgb8_launch(const float* chw, int I, int H, int W, const float* mean3, const float* std3, uint8_t* out, hipStream_t st);
+// gtmap.hip
+int cs_gtmap_max_side();
+hipError_t cs_gtmap_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, int kind, uint16_t* out,
+                           int out_ld, hipStream_t st);
 }
 
 namespace {
@@ -1743,6 +1747,21 @@ int cs_op_metric_map_u16(const uint16_t* maps, int B, int in_h, int in_w, int in
   if (maps && (rs_h != in_h || rs_w != in_w) && !scratch)
     return fail(CS_ERR_BAD_ARG, "metric_map_u16: a resize needs B*in_h*rs_w floats of scratch");
   HIPCHK(cs_metric_map_launch(maps, B, in_h, in_w, in_row_elems, mode, rs_h, rs_w, crop_y, crop_x, out_h, out_w, out, scratch, (hipStream_t)stream));
+  return 0;
+}
+
+int cs_op_gt_metric_map_u8(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride_bytes, int kind, uint16_t* out,
+                           int out_row_elems, cs_stream stream) {
+  if (kind != CS_GTMAP_SSIM && kind != CS_GTMAP_MAE) return fail(CS_ERR_BAD_ARG, "gt_metric_map_u8: kind %d is neither CS_GTMAP_SSIM nor CS_GTMAP_MAE", kind);
+  if (B <= 0 || B > 1024 || H <= 0 || W <= 0) return fail(CS_ERR_BAD_ARG, "gt_metric_map_u8: bad sizes (B %d, H %d, W %d; 1 <= B <= 1024)", B, H, W);
+  if (H > cs_gtmap_max_side() || W > cs_gtmap_max_side())
+    return fail(CS_ERR_UNSUPPORTED, "gt_metric_map_u8: %d x %d has a side above %d", H, W, cs_gtmap_max_side());
+  if (image_stride_bytes < (long long)H * W * 3)
+    return fail(CS_ERR_BAD_ARG, "gt_metric_map_u8: image stride %lld is below the image's %lld bytes", image_stride_bytes, (long long)H * W * 3);
+  if (out_row_elems < W) return fail(CS_ERR_BAD_ARG, "gt_metric_map_u8: output row of %d samples is below the width %d", out_row_elems, W);
+  if (!render || !gt || !out) return fail(CS_ERR_BAD_ARG, "gt_metric_map_u8: null pointer");
+  if ((uintptr_t)out & 1) return fail(CS_ERR_BAD_ARG, "gt_metric_map_u8: 16-bit samples must be 2-byte aligned");
+  HIPCHK(cs_gtmap_launch(render, gt, B, H, W, image_stride_bytes, kind, out, out_row_elems, (hipStream_t)stream));
   return 0;
 }
 

@@ -145,11 +145,60 @@ class InputStage:
         """metric_maps for one map: `out` is its (oh, ow) fp32 slice on the device."""
         self.metric_maps([map_u16], [query_hw], mode, out[None])
 
-    def metric_maps(self, maps: Sequence[Optional[np.ndarray]], query_hws: Sequence[Tuple[int, int]], mode: int, out: torch.Tensor) -> None:
+    def gt_metric_maps(self, renders: Sequence, gts: Sequence, kind: int) -> List[torch.Tensor]:
+        """Ground-truth metric maps from the images themselves (cs_op_gt_metric_map_u8): pair i is (renders[i], gts[i]),
+        each a uint8 (h, w, 3) image, a CUDA tensor or a host array as read_image_u8 returns it; returns per pair its (h, w) int16 device map
+        (16-bit samples, unsigned in memory), the form metric_maps and writers.PngEncoder take.  kind: _lib.GTMAP_SSIM / GTMAP_MAE.  Queued on
+        the current stream without waiting for it: host images go up from pinned memory (non-blocking copies), and one launch per source size
+        covers the batch; the maps of one size are slices of one tensor, in pair order."""
+        lib = _lib.load()
+        if len(renders) != len(gts) or len(renders) == 0:
+            raise ValueError("gt_metric_maps: one captured image per render, at least one pair")
+        groups: Dict[Tuple[int, int], List[int]] = {}
+        for i, (a, b) in enumerate(zip(renders, gts)):
+            for im in (a, b):
+                if im.dtype not in (np.uint8, torch.uint8) or im.ndim != 3 or im.shape[2] != 3:
+                    raise ValueError(f"gt_metric_maps takes uint8 (h, w, 3) images, got {im.dtype} {tuple(im.shape)}")
+            if tuple(a.shape) != tuple(b.shape):
+                raise ValueError(f"render {a.shape[0]}x{a.shape[1]} and captured image {b.shape[0]}x{b.shape[1]} of pair {i} differ in size")
+            groups.setdefault((int(a.shape[0]), int(a.shape[1])), []).append(i)
+        stream = torch.cuda.current_stream(self.device)
+        out: List[Optional[torch.Tensor]] = [None] * len(renders)
+        for (h, w), idx in groups.items():
+            n = len(idx)
+            sides = []
+            for src in (renders, gts):
+                imgs = [src[i] for i in idx]
+                host = [k for k, im in enumerate(imgs) if not isinstance(im, torch.Tensor)]
+                up = None
+                if host:
+                    block = torch.empty((len(host), h, w, 3), dtype=torch.uint8, pin_memory=True)
+                    bv = block.numpy()
+                    for j, k in enumerate(host):
+                        bv[j] = imgs[k]
+                    up = block.to(self.device, non_blocking=True)  # pinned source: an asynchronous copy on the current stream
+                if len(host) == n:
+                    sides.append(up)
+                    continue
+                for j, k in enumerate(host):
+                    imgs[k] = up[j]
+                for im in imgs:
+                    if not im.is_cuda:
+                        raise ValueError("gt_metric_maps takes CUDA tensors or host arrays")
+                    im.record_stream(stream)
+                sides.append(torch.stack(imgs))  # images already on the device (the one-pass input stage's): gathered there
+            maps = torch.empty((n, h, w), dtype=torch.int16, device=self.device)
+            _lib.check(lib.cs_op_gt_metric_map_u8(C.c_void_p(sides[0].data_ptr()), C.c_void_p(sides[1].data_ptr()), n, h, w, h * w * 3, int(kind),
+                                                  C.c_void_p(maps.data_ptr()), w, C.c_void_p(stream.cuda_stream)))
+            for j, i in enumerate(idx):
+                out[i] = maps[j]
+        return out
+
+    def metric_maps(self, maps: Sequence, query_hws: Sequence[Tuple[int, int]], mode: int, out: torch.Tensor) -> None:
         """GT stage of the test phase: writes the processed ground-truth maps of B queries of sizes query_hws into `out` ((B, oh, ow) fp32 on
         the device), each with its query's own resize and crop; None is the "empty_image" placeholder (0 for SSIM, NaN for MAE / MSE).  Queued
         on the current stream without waiting for it: the maps go up from pinned host memory (non-blocking copies), and one launch pair per
-        source size covers the batch."""
+        source size covers the batch.  A map may also be a 16-bit (h, w) CUDA tensor (gt_metric_maps' output): it is used where it is."""
         lib = _lib.load()
         B = len(maps)
         if len(query_hws) != B or B == 0:
@@ -157,7 +206,13 @@ class InputStage:
         geo, groups = [], {}
         for b, (m, hw) in enumerate(zip(maps, query_hws)):
             h, w = int(hw[0]), int(hw[1])
-            if m is not None:
+            on_device = isinstance(m, torch.Tensor)
+            if on_device:
+                if not m.is_cuda or m.dtype not in (torch.int16, getattr(torch, "uint16", torch.int16)) or m.dim() != 2:
+                    raise ValueError(f"a device metric map must be a 16-bit (H, W) CUDA tensor, got {m.dtype} {tuple(m.shape)}")
+                if tuple(m.shape) != (h, w):
+                    raise ValueError(f"metric map {m.shape[0]}x{m.shape[1]} and its render {h}x{w} differ in size")
+            elif m is not None:
                 if m.dtype == np.int32:  # PIL's "I" mode for 16-bit PNGs
                     m = m.astype(np.uint16)
                 if m.dtype != np.uint16 or m.ndim != 2:
@@ -165,7 +220,7 @@ class InputStage:
                 if tuple(m.shape) != (h, w):
                     raise ValueError(f"metric map {m.shape[0]}x{m.shape[1]} and its render {h}x{w} differ in size")
             geo.append(self.geometry(h, w))
-            groups.setdefault(None if m is None else (h, w), []).append((b, m))
+            groups.setdefault(None if m is None else (h, w, True) if on_device else (h, w), []).append((b, m))
         oh, ow = geo[0][1][2:]
         if any(g[1][2:] != (oh, ow) for g in geo) or tuple(out.shape) != (B, oh, ow) or not out.is_contiguous() or out.dtype != torch.float32:
             raise ValueError(f"output must be contiguous fp32 ({B},{oh},{ow}) and every map must give that size, got {tuple(out.shape)}")
@@ -181,12 +236,20 @@ class InputStage:
                 _lib.check(lib.cs_op_metric_map_u16(None, n, rs[0], rs[1], rs[1], int(mode), rs[0], rs[1], crop[0], crop[1], oh, ow,
                                                     C.c_void_p(dst.data_ptr()), None, st))
             else:
-                h, w = key
-                host = torch.empty((n, h, w), dtype=torch.int16, pin_memory=True)
-                hv = host.numpy()
-                for i, (_, m) in enumerate(members):
-                    hv[i] = np.asarray(m, dtype=np.uint16).view(np.int16)
-                d_maps = host.to(self.device, non_blocking=True)  # pinned source: an asynchronous copy on the current stream
+                h, w = key[:2]
+                if len(key) == 3:  # maps already on the device: used in place when they are consecutive slices of one tensor, gathered otherwise
+                    ms = [m for _, m in members]
+                    first = ms[0].data_ptr()
+                    in_place = all(m.is_contiguous() and m.data_ptr() == first + i * h * w * 2 for i, m in enumerate(ms))
+                    d_maps = ms[0] if in_place else torch.stack([m.contiguous() for m in ms])
+                    for m in ms:
+                        m.record_stream(stream)
+                else:
+                    host = torch.empty((n, h, w), dtype=torch.int16, pin_memory=True)
+                    hv = host.numpy()
+                    for i, (_, m) in enumerate(members):
+                        hv[i] = np.asarray(m, dtype=np.uint16).view(np.int16)
+                    d_maps = host.to(self.device, non_blocking=True)  # pinned source: an asynchronous copy on the current stream
                 scratch = torch.empty((n * h * rs[1],), dtype=torch.float32, device=self.device) if rs != (h, w) else None
                 _lib.check(lib.cs_op_metric_map_u16(C.c_void_p(d_maps.data_ptr()), n, h, w, w, int(mode), rs[0], rs[1], crop[0], crop[1], oh, ow,
                                                     C.c_void_p(dst.data_ptr()), C.c_void_p(scratch.data_ptr()) if scratch is not None else None,

@@ -6,6 +6,8 @@ What the reference does (task/test.py:21-140, task/core.py:201-213, 265-293, 379
   dataset / sampling                 get_dataset -> NvsDataset -> NeighbourSelector          -> crossscore_amd/nvs.py (NvsItems)
   images                             load_content, resize_all, crops, T.Normalize            -> data.InputStage (predict's input stage)
   GT maps                            load_content, resize_all, crops                         -> InputStage.metric_map (cs_op_metric_map_u16)
+  GT maps without metric_map/ files  (the reference ships no program that writes them)        -> this_main.gt_metric_maps=compute:
+                                                                                                InputStage.gt_metric_maps (cs_op_gt_metric_map_u8)
   forward                            CrossScoreNet                                           -> ForwardPipeline, reference-token cache, as predict
   L1 loss, Pearson, PSNR per batch   _core_step, on_test_batch_end, correlation, abs2psnr    -> cs_op_score_gt_stats (fp64 sums) + the host
   epoch values                       log_dict(on_step=False) -> Lightning's epoch mean        -> epoch_metrics()
@@ -13,6 +15,12 @@ What the reference does (task/test.py:21-140, task/core.py:201-213, 265-293, 379
 Per batch the GT stage (the maps go up from pinned host memory with non-blocking copies; one launch pair per source size covers the
 batch) and the statistics kernel are queued on the stream of the batch's forward, behind its score map; nothing waits for the device until
 the batch is consumed (depth - 1 submits later), when its B x 6 sums are copied to the host.
+
+this_main.gt_metric_maps (this build's key): files (default) reads <iter>/metric_map/{ssim,mae}/<name>, as the reference does; compute forms
+the same 16-bit map on the device from renders/<name> and gt/<name> of the query's own iteration directory (MSE
+uses the MAE kind) and hands it to the chain above: the captured image is decoded beside the render on the same worker pool and goes up from
+pinned memory without blocking, the one-pass input stage's render bytes are used where they already are, and metric_map/ is never read.
+Every later value is what files mode computes from a PNG of that map (python -m crossscore_amd.metric_maps writes those PNGs).
 
 Epoch values: each of test/loss, test/loss_cross, test/corr_cross, test/psnr_cross is the batch-size-weighted mean of its per-batch values,
 sum(bs * v) / sum(bs) -- Lightning's on_epoch mean for log_dict(on_step=False).  With several ranks the pairs (sum(bs * v), sum(bs)) are summed
@@ -50,6 +58,24 @@ from .writers import BatchWriter, ScoreSummariser, png_encoder_choice
 METRIC_KEYS = ("test/loss", "test/loss_cross", "test/corr_cross", "test/psnr_cross")
 CSV_COLUMNS = sorted(METRIC_KEYS + ("epoch", "step"))  # CSVLogger sorts its keys
 BATCH_COLUMNS = ("batch_idx", "rank", "batch_size", "loss", "corr", "psnr")
+GT_METRIC_MAPS = ("files", "compute")
+
+
+def gt_metric_maps_choice(cfg) -> str:
+    """this_main.gt_metric_maps (this build's key): files (default) | compute."""
+    v = cfg.this_main.get("gt_metric_maps", "files")
+    if v not in GT_METRIC_MAPS:
+        raise ValueError(f"this_main.gt_metric_maps={v!r} not supported: files | compute")
+    return v
+
+
+def gt_map_kind(metric_type: str) -> int:
+    """The cs_op_gt_metric_map_u8 kind behind a metric type, as nvs.metric_load_dir picks the directory: MSE is the MAE map squared."""
+    if metric_type == "ssim":
+        return _lib.GTMAP_SSIM
+    if metric_type in ("mae", "mse"):
+        return _lib.GTMAP_MAE
+    raise ValueError(f"Invalid metric type {metric_type}")
 
 
 def next_version(root: Path) -> int:
@@ -144,9 +170,12 @@ def write_batches_csv(out_dir: str, rows: Sequence[Dict[str, float]]) -> str:
     return path
 
 
-def decode_eval(items, zero_ref: bool, pool, skip=()):
-    """decode_items plus the GT maps of the queries (None for "empty_image")."""
-    futs = [None if it["query/score_map"] == EMPTY else pool.submit(read_metric_map_u16, it["query/score_map"]) for it in items]
+def decode_eval(items, zero_ref: bool, pool, skip=(), compute_gt: bool = False):
+    """decode_items plus the GT maps of the queries (None for "empty_image"); in compute mode the captured images ("query/gt") instead."""
+    if compute_gt:
+        futs = [pool.submit(read_image_u8, it["query/gt"]) for it in items]
+    else:
+        futs = [None if it["query/score_map"] == EMPTY else pool.submit(read_metric_map_u16, it["query/score_map"]) for it in items]
     decoded = decode_items(items, zero_ref, pool, skip)  # (the maps decode beside the images, on the same workers)
     return decoded, [None if f is None else f.result() for f in futs]
 
@@ -154,11 +183,12 @@ def decode_eval(items, zero_ref: bool, pool, skip=()):
 def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None,
              capture: Optional[list] = None) -> Dict[str, object]:
     """Runs the test loop; returns {"version_dir", "out_dir", "metrics", "batches", "files", "query_images_per_sec", "input_stage", "png_encoder",
-    "png_files"}.
+    "png_files", "gt_metric_maps"}.
     capture (tests, tools): a list that receives per batch {"batch_idx", "item_paths", "score", "gt", "stats"} (host copies)."""
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.evaluate needs a GPU: the scoring path has no CPU fallback")
     png_encoder = png_encoder_choice(cfg)  # this_main.png_encoder: host (default) | gpu, as in predict.py
+    compute_gt = gt_metric_maps_choice(cfg) == "compute"  # this_main.gt_metric_maps: files (default) | compute
     seed_everything(int(cfg.lightning.seed))
     rank, local_rank, world = parallel.init_from_env()
     device = torch.device("cuda", local_rank if world > 1 else 0)
@@ -180,7 +210,8 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     mode = metric_mode(cfg.model.predict.metric.type, cfg.model.predict.metric.min)
     if cfg.model.loss.fn != "l1":
         raise NotImplementedError(f"loss fn {cfg.model.loss.fn} (task/core.py:183-187 knows l1)")
-    items = NvsItems.from_config(cfg)
+    items = NvsItems.from_config(cfg, compute_gt)
+    gt_kind = gt_map_kind(cfg.model.predict.metric.type)
 
     net = CrossScoreNet(cfg)
     if "operand_dtype" not in cfg.model.backbone:
@@ -225,20 +256,30 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     cache = ReferenceTokenCache(pipe, stage, keep_images=bool(writer is not None and wcfg.flag.image_reference),
                                 max_images=int(cfg.this_main.get("reference_cache_max_images", 4096)), from_u8=fused_in) if use_cache else None
     cached_paths = lambda: {k[0] for k in cache.tokens} if cache is not None else ()  # noqa: E731
-    pending = prefetch.submit(decode_eval, batches[0], zero_ref, pool, cached_paths()) if batches else None
+    pending = prefetch.submit(decode_eval, batches[0], zero_ref, pool, cached_paths(), compute_gt) if batches else None
     need_w, head_id = bool(cfg.model.need_attn_weights), int(cfg.model.need_attn_weights_head_id)
     lib = _lib.load()
     files: List[str] = []
     rows: List[Dict[str, float]] = []
     n_done = 0
 
-    def gt_and_stats(ticket, its, decoded, maps, size):
+    def gt_and_stats(ticket, its, decoded, maps, size, batch):
         """GT stage + statistics kernel on the forward's stream, behind its score map; returns (gt, stats, event)."""
         s = ticket.stream if ticket.stream is not None else torch.cuda.current_stream(device)
         oh, ow = size
         B = len(its)
+        if compute_gt:  # `maps` holds the captured images
+            for it, g in zip(its, maps):
+                r = decoded[it["query/img"]]
+                if r.shape != g.shape:
+                    raise ValueError(f"{it['query/img']} is {r.shape[0]}x{r.shape[1]} and {it['query/gt']} is {g.shape[0]}x{g.shape[1]}: a render "
+                                     "and the captured image of its view must have one size")
         with torch.cuda.stream(s):
             gt = torch.empty((B, oh, ow), dtype=torch.float32, device=device)
+            if compute_gt:
+                # the render bytes the one-pass input stage already holds on the device, else the decoded host arrays
+                renders = [im.data for im in batch["query/img"].images] if fused_in else [decoded[it["query/img"]] for it in its]
+                maps = stage.gt_metric_maps(renders, maps, gt_kind)
             stage.metric_maps(maps, [decoded[it["query/img"]].shape[:2] for it in its], mode, gt)
             score = ticket.out["score_map_ref_cross"]
             if tuple(score.shape) != (B, oh, ow):
@@ -279,7 +320,8 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     for batch_idx, its in enumerate(batches):
         decoded, maps = pending.result()
         if cache is None:
-            pending = prefetch.submit(decode_eval, batches[batch_idx + 1], zero_ref, pool) if batch_idx + 1 < len(batches) else None
+            pending = (prefetch.submit(decode_eval, batches[batch_idx + 1], zero_ref, pool, (), compute_gt)
+                       if batch_idx + 1 < len(batches) else None)
             batch = (load_batch_u8 if fused_in else load_batch)(its, stage, zero_ref, decoded)
             size = batch["query/img"].size if fused_in else tuple(batch["query/img"].shape[-2:])
             check_size(size)
@@ -292,10 +334,10 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
             check_size(size)
             tokens, ref_imgs = cache.gather([it["reference/cross/imgs"] for it in its], decoded, size, zero_ref)
             batch["reference/cross/imgs"] = ref_imgs
-            pending = (prefetch.submit(decode_eval, batches[batch_idx + 1], zero_ref, pool, cached_paths())
+            pending = (prefetch.submit(decode_eval, batches[batch_idx + 1], zero_ref, pool, cached_paths(), compute_gt)
                        if batch_idx + 1 < len(batches) else None)
             ticket = (pipe.submit_cached_u8 if fused_in else pipe.submit_cached)(batch["query/img"], tokens, need_w, head_id, True)
-        gt, stats, ev = gt_and_stats(ticket, its, decoded, maps, tuple(size))
+        gt, stats, ev = gt_and_stats(ticket, its, decoded, maps, tuple(size), batch)
         n_done += len(its)
         queued.append((ticket, batch, batch_idx, gt, stats, ev))
         while len(queued) >= pipe.depth:
@@ -333,7 +375,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
         files.append(write_batches_csv(out_dir, all_rows))
     return {"version_dir": version_dir, "out_dir": out_dir, "metrics": metrics, "batches": sorted(rows, key=lambda r: r["batch_idx"]),
             "files": files, "input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
-            "png_encoder": png_encoder, "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
+            "png_encoder": png_encoder, "gt_metric_maps": "compute" if compute_gt else "files", "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
             "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}
 
 

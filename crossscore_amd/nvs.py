@@ -9,6 +9,8 @@ The tree under <path>/<resolution>/:
   <scene>/{train,test}/<name>_<iter>/renders/ the query images (renders of that split at that iteration)
   <scene>/{train,test}/<name>_<iter>/gt/      the captured images: the cross references of the OTHER split's queries
   <scene>/{train,test}/<name>_<iter>/metric_map/{ssim,mae}/   GT maps of the renders (16-bit PNG)
+With this_main.gt_metric_maps=compute the maps are formed on the device from renders/<name> and gt/<name> of the same iteration directory
+(cs_op_gt_metric_map_u8): items then carry "query/gt" and metric_map/ is not looked at.
 Pixel work (decoding aside) is the GPU's: data.InputStage for the images and, for the maps, InputStage.metric_map.
 """
 from __future__ import annotations
@@ -16,7 +18,7 @@ from __future__ import annotations
 import json
 import os
 from pathlib import Path
-from typing import Dict, List, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Union
 
 from .data import EMPTY, sample_references
 
@@ -32,10 +34,12 @@ def metric_load_dir(metric_type: str) -> str:
     raise ValueError(f"Invalid metric type {metric_type}")
 
 
-def get_paths(scene_paths: Sequence[Path], num_gaussians_iters: int, metric_dir: str) -> Dict[str, dict]:
+def get_paths(scene_paths: Sequence[Path], num_gaussians_iters: int, metric_dir: Optional[str]) -> Dict[str, dict]:
     """NvsDataset.get_paths (nvs_dataset.py:321-426): per scene and split, iteration -> sorted file lists, with the query / cross-reference
     pairing.  As in the reference, a missing metric directory is filled with as many "empty_image" placeholders as the split has iterations
-    so far (nvs_dataset.py:380), and any list whose length differs from its iteration's gt list raises ValueError."""
+    so far (nvs_dataset.py:380), and any list whose length differs from its iteration's gt list raises ValueError.
+    metric_dir None (compute mode, this build's): no metric directory is looked at, every score map is "empty_image", and each query side
+    also carries "gt", the captured images of its own split."""
     names = sorted(p.name for p in scene_paths)
     kinds = ("renders", "gt", "score_map")
     allp = {n: {s: {k: {} for k in kinds} for s in ("train", "test")} for n in names}
@@ -49,6 +53,9 @@ def get_paths(scene_paths: Sequence[Path], num_gaussians_iters: int, metric_dir:
             for it in iters:
                 num = int(it.split("_")[-1])
                 for k in kinds:
+                    if k == "score_map" and metric_dir is None:
+                        allp[sn][split][k][num] = [EMPTY] * len(allp[sn][split]["gt"][num])
+                        continue
                     img_dir = Path(d, it, metric_dir if k == "score_map" else k)
                     if os.path.exists(img_dir):
                         paths = [str(img_dir / f) for f in sorted(os.listdir(img_dir))]
@@ -69,16 +76,20 @@ def get_paths(scene_paths: Sequence[Path], num_gaussians_iters: int, metric_dir:
                           "N_imgs_per_iter": len(next(iter(renders.values())))},
                 "reference": {"cross": {"images": allp[sn][cross]["gt"]}},
             }
+            if metric_dir is None:
+                out[sn][f"gs_{split}"]["query"]["gt"] = allp[sn][split]["gt"]
     return out
 
 
 class NvsItems:
     """Index -> file paths of one item, like get_dataset(...)[idx]["item_paths"] for the NvsDataset layout (ConcatDataset over the entries
     of `dataset_path`).  References are drawn when an item is asked for, by data.sample_references (numpy's global RNG unless
-    deterministic), as NeighbourSelector.__getitem__ does."""
+    deterministic), as NeighbourSelector.__getitem__ does.
+    compute_gt (this_main.gt_metric_maps=compute): an item also carries "query/gt", the file of the same iteration and index in the gt/ list
+    of the query's own split, its "query/score_map" is "empty_image", and no metric_map/ directory is looked at."""
 
     def __init__(self, dataset_path: Union[str, Sequence[str]], resolution, data_split: str, neighbour_config, metric_type: str,
-                 num_gaussians_iters: int = -1):
+                 num_gaussians_iters: int = -1, compute_gt: bool = False):
         if data_split not in DATA_SPLITS:
             raise ValueError(f"Unknown data_split {data_split}")
         if neighbour_config["strategy"] != "random":
@@ -91,8 +102,11 @@ class NvsItems:
             raise ValueError("cfg.data.dataset.path should be a string or a list")
         self.n_cross = int(neighbour_config["cross"])
         self.deterministic = bool(neighbour_config["deterministic"])
-        mdir = metric_load_dir(metric_type)
-        # (query, score map, cross list) per index, every dataset of the list in turn
+        self.compute_gt = bool(compute_gt)
+        mdir = metric_load_dir(metric_type)  # (validates the metric type in both modes)
+        if self.compute_gt:
+            mdir = None
+        # (query, score map, cross list[, gt]) per index, every dataset of the list in turn
         self._index: List[tuple] = []
         for root in roots:
             res = resolution if resolution is not None else os.listdir(root)[0]
@@ -108,23 +122,26 @@ class NvsItems:
                     iter_names = list(q["query"]["images"].keys())
                     for idx in range(q["query"]["N_iters"] * per_iter):
                         it, im = iter_names[idx // per_iter], idx % per_iter
-                        self._index.append((q["query"]["images"][it][im], q["query"]["score_map"][it][im],
-                                            q["reference"]["cross"]["images"][it]))
+                        entry = (q["query"]["images"][it][im], q["query"]["score_map"][it][im], q["reference"]["cross"]["images"][it])
+                        self._index.append(entry + ((q["query"]["gt"][it][im],) if self.compute_gt else ()))
 
     def __len__(self) -> int:
         return len(self._index)
 
     def __getitem__(self, idx: int) -> Dict[str, object]:
-        query, score_map, cross = self._index[idx]
+        query, score_map, cross = self._index[idx][:3]
         refs = sample_references(cross, self.n_cross, self.deterministic) if self.n_cross > 0 else []
-        return {"query/img": query, "query/score_map": score_map, "reference/cross/imgs": refs}
+        item = {"query/img": query, "query/score_map": score_map, "reference/cross/imgs": refs}
+        if self.compute_gt:
+            item["query/gt"] = self._index[idx][3]
+        return item
 
     @classmethod
-    def from_config(cls, cfg) -> "NvsItems":
+    def from_config(cls, cfg, compute_gt: bool = False) -> "NvsItems":
         """get_dataset(cfg, ..., cfg.this_main.data_split) of task/test.py:95-97."""
         d = cfg.data.dataset
         return cls(d.path, d.get("resolution"), cfg.this_main.data_split, cfg.data.neighbour_config, cfg.model.predict.metric.type,
-                   int(d.get("num_gaussians_iters", -1)))
+                   int(d.get("num_gaussians_iters", -1)), compute_gt)
 
 
 def random_order(n: int, seed: int) -> List[int]:

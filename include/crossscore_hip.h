@@ -303,6 +303,21 @@ int cs_op_denorm_to_rgb8(const float* chw, int I, int H, int W, const float* mea
 enum { CS_METRIC_SSIM_M1_1 = 0, CS_METRIC_SSIM_0_1 = 1, CS_METRIC_MAE = 2, CS_METRIC_MSE = 3 };
 int cs_op_metric_map_u16(const uint16_t* maps, int B, int in_h, int in_w, int in_row_elems, int mode, int rs_h, int rs_w, int crop_y, int crop_x,
                          int out_h, int out_w, float* out, float* scratch, cs_stream stream);
+/* Ground-truth metric maps from the images themselves (csrc/gtmap.hip; DESIGN.md section 6, row f6: the reference ships no program that writes
+ * its metric_map/ files, so this build owns the definition).  B pairs (render, captured image of the same view) of one size, device uint8 HWC
+ * RGB with contiguous rows, images image_stride_bytes apart in both arrays -> B uint16 maps [B][H][out_row_elems], the layout
+ * cs_op_metric_map_u16 takes as maps / in_row_elems and, with out_row_elems == W, cs_op_png_encode as CS_PNG_GRAY16.
+ * CS_GTMAP_SSIM: pixels x / 255; 11 x 11 Gaussian window, sigma 1.5, sum 1; "same" size with zero padding (a pixel outside the image is 0 and
+ * keeps its weight, F.conv2d(padding=5)); per channel ((2 mu_a mu_b + C1)(2 s_ab + C2)) / ((mu_a^2 + mu_b^2 + C1)(s_aa + s_bb + C2)), C1 = 0.01^2,
+ * C2 = 0.03^2; the mean of the three channels m is stored as trunc((m + 1) * 32767) (metric_map_write for [-1, 1], utils/io/images.py:49-63).
+ * fp32 on pixels shifted by a per-tile integer, which removes the cancellation of G*(a*a) - mu_a^2: identical images give 65534 everywhere.
+ * CS_GTMAP_MAE (also the source of MSE): s = sum_c |a_c - b_c|, code (257 * s) / 3 = trunc(65535 * s / 765), integers only.
+ * One launch for the batch, queued on `stream`; nothing is waited for or allocated.  1 <= B <= 1024, 1 <= H, W <= 65535 (CS_ERR_UNSUPPORTED
+ * above); images smaller than the window are legal.  Bad arguments are rejected before anything is launched.  A map's codes depend on its own
+ * pixel pair alone: the same bits alone and at any position of any batch. */
+enum { CS_GTMAP_SSIM = 0, CS_GTMAP_MAE = 1 };
+int cs_op_gt_metric_map_u8(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride_bytes, int kind,
+                           uint16_t* out, int out_row_elems, cs_stream stream);
 /* Score-vs-GT sums: score, gt (B, H, W) fp32 -> stats (B, 6) fp64 = per image sum|s-g|, sum s, sum g, sum s^2, sum g^2, sum s*g, accumulated
  * in fp64 (the L1 loss, Pearson correlation and PSNR of task/core.py:265-293, 379-417 follow on the host).  Two launches, a fixed order: an
  * image's six sums have the same bits alone and at any position of any batch.  NaN propagates.  scratch: device, at least
