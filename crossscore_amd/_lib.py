@@ -12,6 +12,10 @@ CS_OK, CS_ERR_BAD_ARG, CS_ERR_UNSUPPORTED, CS_ERR_STATE, CS_ERR_HIP = range(5)
 # cs_op_metric_map_u16 modes (CS_METRIC_*): the GT map's load_content conversion, by (metric type, metric min)
 METRIC_SSIM_M1_1, METRIC_SSIM_0_1, METRIC_MAE, METRIC_MSE = range(4)
 PNG_GRAY16, PNG_RGB8 = 0, 1  # cs_op_png_encode kinds (CS_PNG_*)
+# status words of cs_op_png_decode (CS_PNGDEC_*)
+(PNGDEC_OK, PNGDEC_BAD_CRC, PNGDEC_BAD_ADLER, PNGDEC_BAD_ZLIB_HEADER, PNGDEC_BAD_BLOCK_TYPE, PNGDEC_BAD_STORED_LEN, PNGDEC_BAD_CODE, PNGDEC_BAD_SYMBOL,
+ PNGDEC_BAD_DISTANCE, PNGDEC_STREAM_SHORT, PNGDEC_STREAM_LONG, PNGDEC_BAD_FILTER, PNGDEC_INPUT_EXHAUSTED, PNGDEC_HEADER_MISMATCH,
+ PNGDEC_BAD_FRAMING) = range(15)
 GTMAP_SSIM, GTMAP_MAE = 0, 1  # cs_op_gt_metric_map_u8 kinds (CS_GTMAP_*)
 
 # CsEpilogue (csrc/cs_common.h)
@@ -34,6 +38,12 @@ class CsU8Image(C.Structure):
     """cs_u8_image: one decoded uint8 HWC image on the device and its resize / crop geometry (cs_forward_u8)."""
     _fields_ = [("data", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("row_bytes", C.c_int), ("rs_h", C.c_int), ("rs_w", C.c_int),
                 ("crop_y", C.c_int), ("crop_x", C.c_int)]
+
+
+class CsPngInfo(C.Structure):
+    """cs_png_info: what cs_png_probe reads from a file's framing and IHDR."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("color_type", C.c_int), ("bit_depth", C.c_int), ("interlace", C.c_int), ("kind", C.c_int),
+                ("num_idat", C.c_int), ("idat_bytes", C.c_ulonglong)]
 
 
 # every symbol include/crossscore_hip.h declares: name -> (restype, argtypes)
@@ -89,6 +99,9 @@ SYMBOLS = {
     "cs_png_bound": (_sz, [_i, _i, _i]),
     "cs_png_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cs_op_png_encode": (_i, [_vp, _i, _i, _i, _i, _ll, _vp, _sz, _vp, _vp, _vp]),
+    "cs_png_probe": (_i, [_vp, _sz, _vp, _vp, _i]),
+    "cs_png_decode_workspace_bytes": (_sz, [_i, _i, _i, _i, _sz]),
+    "cs_op_png_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _ll, _vp, _vp, _vp]),
     "cs_op_denorm_to_rgb8": (_i, [_vp, _i, _i, _i, _fp, _fp, _vp, _vp]),
     "cs_op_metric_map_u16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "cs_op_gt_metric_map_u8": (_i, [_vp, _vp, _i, _i, _i, _ll, _i, _vp, _i, _vp]),

@@ -87,6 +87,11 @@ size_t cs_png_staging_bytes(int kind, int I, int H, int W);
 hipError_t cs_png_encode_launch(const void* pixels, int kind, int I, int H, int W, long long image_stride, uint8_t* out, size_t slot_bytes,
                                 uint32_t* lengths, void* workspace, hipStream_t st);
 hipError_t cs_denorm_rgb8_launch(const float* chw, int I, int H, int W, const float* mean3, const float* std3, uint8_t* out, hipStream_t st);
+// pngdec.hip
+size_t cs_pngdec_workspace(int kind, int I, int H, int W, size_t total_file_bytes);
+hipError_t cs_pngdec_launch(const uint8_t* files, const unsigned long long* file_offsets, const uint32_t* file_lengths, const uint32_t* spans,
+                            const uint32_t* span_offsets, size_t files_bytes, int I, int kind, int H, int W, void* pixels, long long image_stride,
+                            uint32_t* status, void* workspace, hipStream_t st);
 // gtmap.hip
 int cs_gtmap_max_side();
 hipError_t cs_gtmap_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, int kind, uint16_t* out,
@@ -1807,6 +1812,89 @@ int cs_op_png_encode(const void* pixels, int kind, int I, int H, int W, long lon
   if (kind == CS_PNG_GRAY16 && ((uintptr_t)pixels & 1)) return fail(CS_ERR_BAD_ARG, "png_encode: 16-bit samples must be 2-byte aligned");
   if ((uintptr_t)workspace & 15) return fail(CS_ERR_BAD_ARG, "png_encode: the workspace must be 16-byte aligned");
   HIPCHK(cs_png_encode_launch(pixels, kind, I, H, W, image_stride_bytes, out, slot_bytes, lengths, workspace, (hipStream_t)stream));
+  return 0;
+}
+
+// ---- PNG decoder (pngdec.hip): the host probe, the workspace size and the launch
+int cs_png_probe(const uint8_t* file, size_t n, cs_png_info* info, cs_png_span* spans, int max_spans) {
+  static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+  if (!file || !info || max_spans < 0) return fail(CS_ERR_BAD_ARG, "png_probe: null pointer");
+  memset(info, 0, sizeof *info);
+  info->kind = -1;
+  if (memcmp(file, sig, n < 8 ? n : 8) != 0) return fail(CS_ERR_UNSUPPORTED, "png_probe: not a PNG file (no PNG signature)");
+  if (n < 8) return fail(CS_ERR_BAD_ARG, "png_probe: %zu bytes end inside the PNG signature", n);
+  if (n >= ((size_t)1 << 28)) return fail(CS_ERR_UNSUPPORTED, "png_probe: a file of %zu bytes is above the decoder's 256 MiB", n);
+  auto be = [&](size_t p) { return ((uint32_t)file[p] << 24) | ((uint32_t)file[p + 1] << 16) | ((uint32_t)file[p + 2] << 8) | file[p + 3]; };
+  size_t pos = 8;
+  int count = 0;
+  bool have_ihdr = false, have_end = false, palette = false;
+  unsigned long long idat_bytes = 0;
+  while (!have_end) {
+    if (n - pos < 12) return fail(CS_ERR_BAD_ARG, "png_probe: the file ends inside a chunk's framing at byte %zu (no IEND)", pos);
+    const uint32_t len = be(pos);
+    if (len > n - pos - 12) return fail(CS_ERR_BAD_ARG, "png_probe: the chunk at byte %zu is %u bytes long and runs past the file's end", pos, len);
+    const uint8_t* t = file + pos + 4;
+    if (!have_ihdr) {
+      if (memcmp(t, "IHDR", 4) != 0 || len != 13) return fail(CS_ERR_BAD_ARG, "png_probe: the first chunk is not a 13-byte IHDR");
+      have_ihdr = true;
+      info->width = (int)be(pos + 8);
+      info->height = (int)be(pos + 12);
+      if (be(pos + 8) == 0 || be(pos + 12) == 0 || be(pos + 8) > 0x7fffffffu || be(pos + 12) > 0x7fffffffu) return fail(CS_ERR_BAD_ARG, "png_probe: IHDR size 0 or above 2^31 - 1");
+      info->bit_depth = file[pos + 16];
+      info->color_type = file[pos + 17];
+      info->interlace = file[pos + 20];
+      if (file[pos + 18] != 0 || file[pos + 19] != 0) return fail(CS_ERR_UNSUPPORTED, "png_probe: compression / filter method %d / %d", file[pos + 18], file[pos + 19]);
+    } else if (memcmp(t, "IDAT", 4) == 0) {
+      if (spans && count < max_spans) { spans[count].offset = (uint32_t)(pos + 8); spans[count].length = len; }
+      count += 1;
+      idat_bytes += len;
+    } else if (memcmp(t, "IEND", 4) == 0) {
+      have_end = true;
+    } else if (memcmp(t, "PLTE", 4) == 0) {
+      palette = true;
+    } else if (!(t[0] & 0x20)) {
+      return fail(CS_ERR_UNSUPPORTED, "png_probe: unknown critical chunk %.4s", (const char*)t);
+    }
+    pos += 12 + (size_t)len;
+  }
+  (void)palette;
+  info->num_idat = count;
+  info->idat_bytes = idat_bytes;
+  if (count == 0) return fail(CS_ERR_BAD_ARG, "png_probe: no IDAT chunk");
+  if (info->interlace != 0) return fail(CS_ERR_UNSUPPORTED, "png_probe: interlaced files are not decoded on the device");
+  const int ct = info->color_type, d = info->bit_depth;
+  if (d == 8 && (ct == 2 || ct == 6 || ct == 0)) info->kind = CS_PNG_RGB8;
+  else if (d == 16 && ct == 0) info->kind = CS_PNG_GRAY16;
+  else return fail(CS_ERR_UNSUPPORTED, "png_probe: colour type %d with bit depth %d is not decoded on the device (8-bit gray / RGB / RGBA, 16-bit gray)", ct, d);
+  if (!cs_png_size_supported(info->height, info->width)) {
+    info->kind = -1;
+    return fail(CS_ERR_UNSUPPORTED, "png_probe: %d x %d is larger than 4096 x 4096", info->height, info->width);
+  }
+  if (spans && count > max_spans) return fail(CS_ERR_BAD_ARG, "png_probe: %d IDAT chunks, room for %d spans", count, max_spans);
+  return 0;
+}
+
+size_t cs_png_decode_workspace_bytes(int kind, int I, int H, int W, size_t total_file_bytes) {
+  if (H <= 0 || W <= 0 || I <= 0 || I > 65535 || !cs_png_size_supported(H, W)) return 0;
+  return cs_pngdec_workspace(kind, I, H, W, total_file_bytes);
+}
+
+int cs_op_png_decode(const uint8_t* files, const uint64_t* file_offsets, const uint32_t* file_lengths, const cs_png_span* spans,
+                     const uint32_t* span_offsets, size_t total_file_bytes, int I, int kind, int H, int W, void* pixels, long long image_stride_bytes,
+                     uint32_t* status, void* workspace, cs_stream stream) {
+  if (kind != CS_PNG_GRAY16 && kind != CS_PNG_RGB8) return fail(CS_ERR_BAD_ARG, "png_decode: kind %d is neither CS_PNG_GRAY16 nor CS_PNG_RGB8", kind);
+  if (I <= 0 || I > 65535 || H <= 0 || W <= 0) return fail(CS_ERR_BAD_ARG, "png_decode: bad sizes (I %d, H %d, W %d; 1 <= I <= 65535)", I, H, W);
+  if (!cs_png_size_supported(H, W)) return fail(CS_ERR_UNSUPPORTED, "png_decode: %d x %d is larger than 4096 x 4096", H, W);
+  const long long image_bytes = (long long)H * W * (kind == CS_PNG_GRAY16 ? 2 : 3);
+  if (image_stride_bytes < image_bytes || (kind == CS_PNG_GRAY16 && (image_stride_bytes & 1)))
+    return fail(CS_ERR_BAD_ARG, "png_decode: image stride %lld is below the image's %lld bytes (or odd for 16-bit samples)", image_stride_bytes, image_bytes);
+  if (total_file_bytes == 0 || total_file_bytes >= ((size_t)1 << 40)) return fail(CS_ERR_BAD_ARG, "png_decode: %zu file bytes (1 .. 2^40 - 1)", total_file_bytes);
+  if (!files || !file_offsets || !file_lengths || !spans || !span_offsets || !pixels || !status || !workspace) return fail(CS_ERR_BAD_ARG, "png_decode: null pointer");
+  if (kind == CS_PNG_GRAY16 && ((uintptr_t)pixels & 1)) return fail(CS_ERR_BAD_ARG, "png_decode: 16-bit samples must be 2-byte aligned");
+  if ((uintptr_t)workspace & 15) return fail(CS_ERR_BAD_ARG, "png_decode: the workspace must be 16-byte aligned");
+  static_assert(sizeof(cs_png_span) == 8, "span layout");
+  HIPCHK(cs_pngdec_launch(files, (const unsigned long long*)file_offsets, file_lengths, (const uint32_t*)spans, span_offsets, total_file_bytes, I, kind, H, W,
+                          pixels, image_stride_bytes, status, workspace, (hipStream_t)stream));
   return 0;
 }
 

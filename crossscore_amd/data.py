@@ -5,7 +5,8 @@ Mirrors, for the predict path only:
   NeighbourSelector + SamplerRandom    dataloading/dataset/nvs_dataset.py:14-84, utils/neighbour/sampler.py:15-38
   load_content / resize_all / crops / T.Normalize   nvs_dataset.py:218-279,429-470, task/predict.py:68-93
 The pixel work (x/255, antialiased resize, crop, normalise) runs on the GPU through cs_op_preprocess_u8 straight from the decoded
-uint8 image; only PNG/JPEG decoding stays on the host (PIL, as in utils/io/images.py:26-29).
+uint8 image; PNG/JPEG decoding stays on the host (PIL, as in utils/io/images.py:26-29) unless this_main.png_decoder=gpu hands the PNG files
+to PngDecoder (cs_op_png_decode: the compressed bytes go up and the decoded images appear in device memory).
 """
 from __future__ import annotations
 
@@ -90,6 +91,244 @@ def metric_mode(metric_type: str, metric_min) -> int:
     raise ValueError(f"Invalid metric type {metric_type}")
 
 
+PNG_DECODERS = ("host", "gpu")
+PNGDEC_STATUS = ("ok", "bad CRC-32", "bad Adler-32", "bad zlib header", "reserved block type", "stored LEN/NLEN mismatch",
+                 "over-subscribed or incomplete code", "invalid symbol", "distance before the start of the stream", "stream too short",
+                 "stream too long", "filter type above 4", "input exhausted", "IHDR differs from the size or format asked for", "bad chunk framing")
+
+
+def png_decoder_choice(cfg) -> str:
+    """this_main.png_decoder (this build's key): host (default) | gpu."""
+    v = cfg.this_main.get("png_decoder", "host")
+    if v not in PNG_DECODERS:
+        raise ValueError(f"this_main.png_decoder={v!r} not supported: host | gpu")
+    return v
+
+
+def png_decode_window_choice(cfg) -> int:
+    """this_main.png_decode_window (this build's key): files handed to the device decoder at once, default 64."""
+    v = cfg.this_main.get("png_decode_window", 64)
+    if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+        raise ValueError(f"this_main.png_decode_window={v!r} must be a positive integer")
+    return v
+
+
+def read_file_bytes(path: str) -> bytes:
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def probe_png(data: bytes):
+    """cs_png_probe on a file's bytes: (info, spans (n, 2) uint32) when the device decoder takes the file, else (None, reason)."""
+    lib = _lib.load()
+    info = _lib.CsPngInfo()
+    buf = bytes(data)  # ctypes passes the object's own buffer
+    rc = lib.cs_png_probe(buf, len(data), C.byref(info), None, 0)
+    if rc != _lib.CS_OK:
+        return None, _lib.last_error()
+    spans = np.zeros((info.num_idat, 2), dtype=np.uint32)
+    rc = lib.cs_png_probe(buf, len(data), C.byref(info), C.c_void_p(spans.ctypes.data), info.num_idat)
+    if rc != _lib.CS_OK:
+        return None, _lib.last_error()
+    return info, spans
+
+
+class PngDecodeHandle:
+    """One PngDecoder.decode request: `tensors[i]` is the device image of `paths[i]`; `event` is recorded behind the last launch (and behind the
+    copy of the status words to pinned memory).  wait(stream) orders a consumer stream behind the decode without waiting on the host;
+    check() is the host wait: it raises ValueError naming the first file whose status is not zero."""
+
+    def __init__(self, paths, tensors, event, groups, host_paths):
+        self.paths, self.tensors, self.event, self._groups, self.host_paths = list(paths), list(tensors), event, groups, list(host_paths)
+        self._checked = False
+
+    def wait(self, stream=None) -> None:
+        stream = stream if stream is not None else torch.cuda.current_stream()
+        if self.event is not None:
+            stream.wait_event(self.event)
+            for t in self.tensors:
+                t.record_stream(stream)
+
+    def check(self) -> None:
+        if self._checked:
+            return
+        if self.event is not None:
+            self.event.synchronize()
+        for paths, status in self._groups:
+            st = status.numpy()
+            bad = np.nonzero(st)[0]
+            if bad.size:
+                i = int(bad[0])
+                code = int(st[i])
+                what = PNGDEC_STATUS[code] if code < len(PNGDEC_STATUS) else "unknown"
+                raise ValueError(f"{paths[i]}: the device PNG decoder rejected the file with status {code} ({what})")
+        self._checked = True
+
+
+class PngDecoder:
+    """Counterpart of writers.PngEncoder on the input side: PNG files -> decoded images in device memory (cs_op_png_decode).
+
+    decode(paths, gray16) reads the files' bytes on `pool`, probes them on the host (cs_png_probe), groups them by (H, W, kind), uploads each
+    group from pinned memory with non-blocking copies and queues one decode launch per group on the decoder's own stream; nothing waits for the
+    device.  Per path the handle holds a (H, W, 3) uint8 tensor (read_image_u8's array) or, with gray16=True, a (H, W) int16 tensor holding
+    uint16 samples (the convention of InputStage.metric_maps).  A file the probe does not take (interlaced, palette, JPEG, ...) is decoded by
+    PIL exactly as without the decoder and uploaded.  The status words travel to pinned memory behind the same event; handle.check() reads them."""
+
+    def __init__(self, device, pool=None):
+        self.device = torch.device(device)
+        self.pool = pool
+        self.stream = torch.cuda.Stream(self.device)
+        self.files_gpu = 0
+        self.files_host = 0
+
+    def _map(self, fn, xs):
+        return list(self.pool.map(fn, xs)) if self.pool is not None else [fn(x) for x in xs]
+
+    def decode(self, paths: Sequence[str], gray16: "bool | Sequence[bool]" = False) -> PngDecodeHandle:
+        lib = _lib.load()
+        paths = list(paths)
+        kinds = [bool(gray16)] * len(paths) if isinstance(gray16, (bool, int)) else [bool(g) for g in gray16]
+        if len(kinds) != len(paths):
+            raise ValueError("PngDecoder.decode: one gray16 flag per path")
+
+        def load(p):
+            data = read_file_bytes(p)
+            info, spans = probe_png(data)
+            return data, info, spans
+
+        loaded = self._map(load, paths)
+        tensors: List[Optional[torch.Tensor]] = [None] * len(paths)
+        groups: Dict[Tuple[int, int, int], List[int]] = {}
+        host_idx = []
+        for i, (data, info, spans) in enumerate(loaded):
+            want = _lib.PNG_GRAY16 if kinds[i] else _lib.PNG_RGB8
+            if info is None or info.kind != want:
+                host_idx.append(i)  # not built on the device (or not the kind asked for): PIL, which also raises what it raised before
+            else:
+                groups.setdefault((info.height, info.width, info.kind), []).append(i)
+        host_imgs = self._map(lambda i: (read_metric_map_u16 if kinds[i] else read_image_u8)(paths[i]), host_idx)
+        done = []
+        with torch.cuda.device(self.device), torch.cuda.stream(self.stream):
+            st = C.c_void_p(self.stream.cuda_stream)
+            for i, im in zip(host_idx, host_imgs):
+                pinned = torch.empty(im.shape, dtype=torch.int16 if kinds[i] else torch.uint8, pin_memory=True)
+                pinned.numpy()[...] = im.view(np.int16) if kinds[i] else im
+                tensors[i] = pinned.to(self.device, non_blocking=True)
+            for (h, w, kind), idx in groups.items():
+                n = len(idx)
+                lengths = np.array([len(loaded[i][0]) for i in idx], dtype=np.uint32)
+                offsets = np.zeros((n,), dtype=np.uint64)
+                offsets[1:] = np.cumsum(lengths.astype(np.uint64))[:-1]
+                total = int(lengths.astype(np.uint64).sum())
+                nspans = np.array([len(loaded[i][2]) for i in idx], dtype=np.uint32)
+                span_off = np.zeros((n + 1,), dtype=np.uint32)
+                span_off[1:] = np.cumsum(nspans)
+                # one pinned block: file bytes | offsets (u64) | lengths | span offsets | spans, each part 8-byte aligned
+                parts = [("files", total, 1), ("offsets", n * 8, 8), ("lengths", n * 4, 4), ("span_off", (n + 1) * 4, 4), ("spans", int(span_off[-1]) * 8, 4)]
+                at, pos = {}, 0
+                for name, nbytes, _ in parts:
+                    at[name] = pos
+                    pos += (nbytes + 7) // 8 * 8
+                block = torch.empty((pos,), dtype=torch.uint8, pin_memory=True)
+                bv = block.numpy()
+                for j, i in enumerate(idx):
+                    bv[int(offsets[j]):int(offsets[j]) + int(lengths[j])] = np.frombuffer(loaded[i][0], dtype=np.uint8)
+                bv[at["offsets"]:at["offsets"] + n * 8] = offsets.view(np.uint8)
+                bv[at["lengths"]:at["lengths"] + n * 4] = lengths.view(np.uint8)
+                bv[at["span_off"]:at["span_off"] + (n + 1) * 4] = span_off.view(np.uint8)
+                bv[at["spans"]:at["spans"] + int(span_off[-1]) * 8] = np.concatenate([loaded[i][2] for i in idx]).reshape(-1).view(np.uint8)
+                d_block = block.to(self.device, non_blocking=True)
+                base = d_block.data_ptr()
+                out = torch.empty((n, h, w) if kind == _lib.PNG_GRAY16 else (n, h, w, 3), dtype=torch.int16 if kind == _lib.PNG_GRAY16 else torch.uint8,
+                                  device=self.device)
+                status = torch.empty((n,), dtype=torch.int32, device=self.device)
+                work = torch.empty((lib.cs_png_decode_workspace_bytes(kind, n, h, w, total),), dtype=torch.uint8, device=self.device)
+                _lib.check(lib.cs_op_png_decode(C.c_void_p(base + at["files"]), C.c_void_p(base + at["offsets"]), C.c_void_p(base + at["lengths"]),
+                                                C.c_void_p(base + at["spans"]), C.c_void_p(base + at["span_off"]), total, n, kind, h, w,
+                                                C.c_void_p(out.data_ptr()), h * w * (2 if kind == _lib.PNG_GRAY16 else 3),
+                                                C.c_void_p(status.data_ptr()), C.c_void_p(work.data_ptr()), st))
+                host_status = torch.empty((n,), dtype=torch.int32, pin_memory=True)
+                host_status.copy_(status, non_blocking=True)
+                for j, i in enumerate(idx):
+                    tensors[i] = out[j]
+                done.append(([paths[i] for i in idx], host_status))
+            event = torch.cuda.Event()
+            event.record(self.stream)
+        self.files_gpu += sum(len(g) for g in groups.values())
+        self.files_host += len(host_idx)
+        return PngDecodeHandle(paths, tensors, event, done, [paths[i] for i in host_idx])
+
+    def stats(self) -> Dict[str, int]:
+        return {"png_decoded_gpu": self.files_gpu, "png_decoded_host": self.files_host}
+
+
+def plan_decodes(batches, zero_reference: bool, once_per_reference: bool, extra=None) -> List[List[Tuple[str, bool]]]:
+    """Per batch the (path, gray16) list of the files it reads, in the order decode_items reads them: queries and references (with a
+    reference-token cache a reference is read by the first batch that names it only: later ones find its tokens), then extra(item)."""
+    seen, plan = set(), []
+    for its in batches:
+        files: List[Tuple[str, bool]] = []
+        for it in its:
+            files.append((it["query/img"], False))
+            if not zero_reference:
+                for p in it["reference/cross/imgs"]:
+                    if p == EMPTY or (once_per_reference and p in seen):
+                        continue
+                    seen.add(p)
+                    files.append((p, False))
+            if extra is not None:
+                files += extra(it)
+        plan.append(files)
+    return plan
+
+
+class DecodeWindow:
+    """The drivers' loader with this_main.png_decoder=gpu: the files of all batches are known up front, so the decoder is handed a window of
+    upcoming files (this_main.png_decode_window, independent of the batch size) and a file's decode latency hides behind earlier forwards.
+
+    plan: per batch the ordered (path, gray16) list of what that batch reads.  fetch(b) returns {path: device tensor} for batch b with the
+    current stream ordered behind the decodes it needs; whenever batch b holds a file that is not queued yet, windows of `window` files are
+    queued from the first such file on (so a window smaller than a batch is several calls, a larger one reaches into the next batches).
+    check(b) is the host side of batch b's status words: call it where the loop waits for that batch anyway."""
+
+    def __init__(self, decoder: PngDecoder, plan: Sequence[Sequence[Tuple[str, bool]]], window: int):
+        self.decoder, self.window = decoder, max(1, int(window))
+        self.plan = [list(dict.fromkeys(p)) for p in plan]
+        self.queue = [(b, path, g) for b, files in enumerate(self.plan) for path, g in files]
+        self.next = 0  # first entry of the queue not handed to the decoder yet
+        self.ready: Dict[Tuple[int, str, bool], Tuple[torch.Tensor, PngDecodeHandle]] = {}
+        self.handles: Dict[int, List[PngDecodeHandle]] = {}
+
+    def _queue_window(self) -> None:
+        entries = self.queue[self.next:self.next + self.window]
+        self.next += len(entries)
+        uniq = list(dict.fromkeys((path, g) for _, path, g in entries))  # a file named by two batches of one window is decoded once
+        handle = self.decoder.decode([p for p, _ in uniq], [g for _, g in uniq])
+        where = {k: i for i, k in enumerate(uniq)}
+        for b, path, g in entries:
+            self.ready[(b, path, g)] = (handle.tensors[where[(path, g)]], handle)
+
+    def fetch(self, b: int) -> Dict[str, torch.Tensor]:
+        need = [(b, path, g) for path, g in self.plan[b]]
+        while any(k not in self.ready for k in need):
+            self._queue_window()
+        out, handles = {}, []
+        for k in need:
+            t, h = self.ready.pop(k)
+            out[k[1]] = t
+            if all(h is not x for x in handles):
+                handles.append(h)
+        cur = torch.cuda.current_stream(self.decoder.device)
+        for h in handles:
+            h.wait(cur)
+        self.handles[b] = handles
+        return out
+
+    def check(self, b: int) -> None:
+        for h in self.handles.pop(b, []):
+            h.check()
+
+
 class InputStage:
     """uint8 HWC images -> the normalised fp32 batch tensors CrossScoreNet.forward takes, on `device`."""
 
@@ -120,14 +359,23 @@ class InputStage:
             oh, ow = rs[0] - rs[0] % self.patch, rs[1] - rs[1] % self.patch
         return rs, (0, 0, oh, ow)
 
-    def __call__(self, img_u8: np.ndarray, out: torch.Tensor) -> None:
-        """Writes the processed image into `out` ((3, oh, ow) fp32 slice on the device)."""
+    def _device_image(self, img_u8) -> torch.Tensor:
+        """The decoded image on the device: a host array goes up (a blocking pageable copy), a CUDA uint8 (h, w, 3) tensor (data.PngDecoder's
+        output) is used where it is."""
+        if isinstance(img_u8, torch.Tensor):
+            if not img_u8.is_cuda or img_u8.dtype != torch.uint8 or img_u8.dim() != 3 or img_u8.shape[2] != 3 or not img_u8.is_contiguous():
+                raise ValueError(f"a device image must be a contiguous uint8 (h, w, 3) CUDA tensor, got {img_u8.dtype} {tuple(img_u8.shape)}")
+            return img_u8
+        return torch.from_numpy(img_u8).to(self.device, non_blocking=False)
+
+    def __call__(self, img_u8, out: torch.Tensor) -> None:
+        """Writes the processed image into `out` ((3, oh, ow) fp32 slice on the device).  img_u8: a host array or a CUDA uint8 tensor."""
         lib = _lib.load()
-        h, w, _ = img_u8.shape
+        h, w, _ = (int(v) for v in img_u8.shape)
         rs, crop = self.geometry(h, w)
         if tuple(out.shape) != (3, crop[2], crop[3]) or not out.is_contiguous() or out.dtype != torch.float32:
             raise ValueError(f"output slice must be contiguous fp32 (3,{crop[2]},{crop[3]}), got {tuple(out.shape)}")
-        d_img = torch.from_numpy(img_u8).to(self.device, non_blocking=False)
+        d_img = self._device_image(img_u8)
         scratch = None
         if rs != (h, w):
             need = h * rs[1] * 3
@@ -259,12 +507,13 @@ class InputStage:
                     out[b].copy_(dst[i])
 
     # -- the one-pass form (SURVEY.md 8f-4 as worded): nothing is computed here, the patch-embedding launch does the pixel work --------------
-    def describe(self, img_u8: np.ndarray):
-        """The decoded image on the device with its geometry (model.U8Image) for CrossScoreNet.forward_u8 and its siblings."""
+    def describe(self, img_u8):
+        """The decoded image on the device with its geometry (model.U8Image) for CrossScoreNet.forward_u8 and its siblings.  img_u8: a host
+        array or a CUDA uint8 tensor (no copy)."""
         from .model import U8Image
-        h, w, _ = img_u8.shape
+        h, w, _ = (int(v) for v in img_u8.shape)
         rs, crop = self.geometry(h, w)
-        return U8Image(torch.from_numpy(img_u8).to(self.device, non_blocking=False), h, w, rs, crop[0], crop[1])
+        return U8Image(self._device_image(img_u8), h, w, rs, crop[0], crop[1])
 
     def placeholder(self, size):
         """The all-zero image (placeholders of short reference lists, zero_reference: nvs_dataset.py:459-470) of the processed size."""

@@ -47,8 +47,8 @@ import torch
 
 from . import _lib, parallel, synth
 from .config import load_config
-from .data import (EMPTY, InputStage, ReferenceTokenCache, decode_items, load_batch, load_batch_u8, load_query_batch, load_query_batch_u8,
-                   metric_mode, read_image_u8, read_metric_map_u16)
+from .data import (EMPTY, DecodeWindow, InputStage, PngDecoder, ReferenceTokenCache, decode_items, load_batch, load_batch_u8, load_query_batch,
+                   load_query_batch_u8, metric_mode, plan_decodes, png_decode_window_choice, png_decoder_choice, read_image_u8, read_metric_map_u16)
 from .model import CrossScoreNet, load_lightning_checkpoint
 from .nvs import NvsItems, random_order
 from .pipeline import ForwardPipeline
@@ -183,12 +183,15 @@ def decode_eval(items, zero_ref: bool, pool, skip=(), compute_gt: bool = False):
 def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None,
              capture: Optional[list] = None) -> Dict[str, object]:
     """Runs the test loop; returns {"version_dir", "out_dir", "metrics", "batches", "files", "query_images_per_sec", "input_stage", "png_encoder",
-    "png_files", "gt_metric_maps"}.
+    "png_files", "gt_metric_maps", "png_decoder", "png_decoded"}.
     capture (tests, tools): a list that receives per batch {"batch_idx", "item_paths", "score", "gt", "stats"} (host copies)."""
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.evaluate needs a GPU: the scoring path has no CPU fallback")
     png_encoder = png_encoder_choice(cfg)  # this_main.png_encoder: host (default) | gpu, as in predict.py
     compute_gt = gt_metric_maps_choice(cfg) == "compute"  # this_main.gt_metric_maps: files (default) | compute
+    # this_main.png_decoder: host (default) | gpu, as in predict.py; here the window also holds the 16-bit metric maps (files) or the captured
+    # images (compute)
+    png_decoder, decode_window = png_decoder_choice(cfg), png_decode_window_choice(cfg)
     seed_everything(int(cfg.lightning.seed))
     rank, local_rank, world = parallel.init_from_env()
     device = torch.device("cuda", local_rank if world > 1 else 0)
@@ -256,7 +259,28 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     cache = ReferenceTokenCache(pipe, stage, keep_images=bool(writer is not None and wcfg.flag.image_reference),
                                 max_images=int(cfg.this_main.get("reference_cache_max_images", 4096)), from_u8=fused_in) if use_cache else None
     cached_paths = lambda: {k[0] for k in cache.tokens} if cache is not None else ()  # noqa: E731
-    pending = prefetch.submit(decode_eval, batches[0], zero_ref, pool, cached_paths(), compute_gt) if batches else None
+    decoder = PngDecoder(device, pool) if png_decoder == "gpu" else None
+
+    def gt_files(it):
+        if compute_gt:
+            return [(it["query/gt"], False)]
+        return [] if it["query/score_map"] == EMPTY else [(it["query/score_map"], True)]
+
+    window = DecodeWindow(decoder, plan_decodes(batches, zero_ref, cache is not None, gt_files), decode_window) if decoder is not None else None
+
+    def fetch_eval(i):
+        """decode_eval through the decode window: device tensors for the images and for the maps / captured images"""
+        d = window.fetch(i)
+        if compute_gt:
+            return d, [d[it["query/gt"]] for it in batches[i]]
+        return d, [None if it["query/score_map"] == EMPTY else d[it["query/score_map"]] for it in batches[i]]
+
+    def submit_decode(i):
+        if window is not None:
+            return prefetch.submit(fetch_eval, i)
+        return prefetch.submit(decode_eval, batches[i], zero_ref, pool, cached_paths(), compute_gt)
+
+    pending = submit_decode(0) if batches else None
     need_w, head_id = bool(cfg.model.need_attn_weights), int(cfg.model.need_attn_weights_head_id)
     lib = _lib.load()
     files: List[str] = []
@@ -300,6 +324,8 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     def consume(entry):
         ticket, batch, idx, gt, stats, ev = entry
         out = pipe.result(ticket)
+        if window is not None:
+            window.check(idx)  # the status words of the files this batch read
         cur = torch.cuda.current_stream(device)
         cur.wait_event(ev)
         gt.record_stream(cur)
@@ -320,8 +346,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     for batch_idx, its in enumerate(batches):
         decoded, maps = pending.result()
         if cache is None:
-            pending = (prefetch.submit(decode_eval, batches[batch_idx + 1], zero_ref, pool, (), compute_gt)
-                       if batch_idx + 1 < len(batches) else None)
+            pending = submit_decode(batch_idx + 1) if batch_idx + 1 < len(batches) else None
             batch = (load_batch_u8 if fused_in else load_batch)(its, stage, zero_ref, decoded)
             size = batch["query/img"].size if fused_in else tuple(batch["query/img"].shape[-2:])
             check_size(size)
@@ -334,8 +359,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
             check_size(size)
             tokens, ref_imgs = cache.gather([it["reference/cross/imgs"] for it in its], decoded, size, zero_ref)
             batch["reference/cross/imgs"] = ref_imgs
-            pending = (prefetch.submit(decode_eval, batches[batch_idx + 1], zero_ref, pool, cached_paths(), compute_gt)
-                       if batch_idx + 1 < len(batches) else None)
+            pending = submit_decode(batch_idx + 1) if batch_idx + 1 < len(batches) else None
             ticket = (pipe.submit_cached_u8 if fused_in else pipe.submit_cached)(batch["query/img"], tokens, need_w, head_id, True)
         gt, stats, ev = gt_and_stats(ticket, its, decoded, maps, tuple(size), batch)
         n_done += len(its)
@@ -375,7 +399,9 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
         files.append(write_batches_csv(out_dir, all_rows))
     return {"version_dir": version_dir, "out_dir": out_dir, "metrics": metrics, "batches": sorted(rows, key=lambda r: r["batch_idx"]),
             "files": files, "input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
-            "png_encoder": png_encoder, "gt_metric_maps": "compute" if compute_gt else "files", "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
+            "png_encoder": png_encoder, "gt_metric_maps": "compute" if compute_gt else "files",
+            "png_decoder": png_decoder, "png_decoded": decoder.stats() if decoder is not None else {"png_decoded_gpu": 0, "png_decoded_host": 0},
+            "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
             "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}
 
 
@@ -388,7 +414,7 @@ def main(argv: Optional[Iterable[str]] = None) -> int:
         res = evaluate(cfg)
     m = res["metrics"]
     print(f"[crossscore_amd.evaluate] {sum(r['batch_size'] for r in res['batches'])} query images: test/loss {m['test/loss']:.6f} "
-          f"test/corr_cross {m['test/corr_cross']:.6f} test/psnr_cross {m['test/psnr_cross']:.4f}; metrics under {res['version_dir']}, outputs "
+          f"test/corr_cross {m['test/corr_cross']:.6f} test/psnr_cross {m['test/psnr_cross']:.4f} (png_decoder {res['png_decoder']}); metrics under {res['version_dir']}, outputs "
           f"under {res['out_dir']}")
     return 0
 

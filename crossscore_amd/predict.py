@@ -27,8 +27,8 @@ import torch
 
 from . import parallel, synth
 from .config import load_config
-from .data import (InputStage, ReferenceTokenCache, SimpleReferenceItems, decode_items, load_batch, load_batch_u8, load_query_batch,
-                   load_query_batch_u8, read_image_u8)
+from .data import (DecodeWindow, InputStage, PngDecoder, ReferenceTokenCache, SimpleReferenceItems, decode_items, load_batch, load_batch_u8,
+                   load_query_batch, load_query_batch_u8, plan_decodes, png_decode_window_choice, png_decoder_choice, read_image_u8)
 from .model import CrossScoreNet, load_lightning_checkpoint
 from .pipeline import ForwardPipeline
 from .writers import BatchWriter, ScoreSummariser, png_encoder_choice
@@ -59,12 +59,17 @@ def seed_everything(seed: int) -> None:
 
 
 def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None) -> Dict[str, object]:
-    """Runs the predict loop; returns {"out_dir", "files", "rows", "input_stage", "png_encoder", "png_files", "query_images_per_sec"}."""
+    """Runs the predict loop; returns {"out_dir", "files", "rows", "input_stage", "png_encoder", "png_files", "png_decoder", "png_decoded",
+    "query_images_per_sec"}."""
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.predict needs a GPU: the scoring path has no CPU fallback")
     # this_main.png_encoder (this build's key, default "host"): who compresses the PNG outputs -- PIL on the writer's threads, or the device
     # (writers.PngEncoder: conversion, de-normalisation and compression queued behind the forward; pixel-exact, not byte-equal)
     png_encoder = png_encoder_choice(cfg)
+    # this_main.png_decoder (this build's key, default "host"): who decodes the PNG inputs -- PIL on the loader's threads, or the device
+    # (data.PngDecoder: the compressed bytes go up, a window of this_main.png_decode_window upcoming files is decoded beside earlier forwards;
+    # the same pixels, bit for bit; files the device decoder does not take still go through PIL)
+    png_decoder, decode_window = png_decoder_choice(cfg), png_decode_window_choice(cfg)
     seed_everything(int(cfg.lightning.seed))
     rank, local_rank, world = parallel.init_from_env()
     device = torch.device("cuda", local_rank if world > 1 else 0)
@@ -134,13 +139,24 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
     cache = ReferenceTokenCache(pipe, stage, keep_images=bool(writer is not None and cfg.logger.predict.write.flag.image_reference),
                                 max_images=int(cfg.this_main.get("reference_cache_max_images", 4096)), from_u8=fused_in) if use_cache else None
     cached_paths = lambda: {k[0] for k in cache.tokens} if cache is not None else ()  # noqa: E731
-    pending = prefetch.submit(decode_items, batches[0], zero_ref, pool, cached_paths()) if batches else None
+    decoder = PngDecoder(device, pool) if png_decoder == "gpu" else None
+    window = DecodeWindow(decoder, plan_decodes(batches, zero_ref, cache is not None), decode_window) if decoder is not None else None
+
+    def submit_decode(i):
+        """the decoded images of batch i, read on the loader's thread: {path: host array}, or {path: device tensor} from the decode window"""
+        if window is not None:
+            return prefetch.submit(window.fetch, i)
+        return prefetch.submit(decode_items, batches[i], zero_ref, pool, cached_paths())
+
+    pending = submit_decode(0) if batches else None
     need_w, head_id = bool(cfg.model.need_attn_weights), int(cfg.model.need_attn_weights_head_id)
     files, n_done = [], 0
 
     def consume(entry):
         ticket, batch, idx = entry
         out = pipe.result(ticket)
+        if window is not None:
+            window.check(idx)  # the status words of the files this batch read: a rejected file raises here, naming its path
         summariser.update(batch, out, means=out.get("score_mean_ref_cross"))  # the per-image means the head launch left (score_summariser.py:180-192)
         if writer is not None:
             files.extend(writer.write_out(batch, out, local_rank, idx))
@@ -151,7 +167,7 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
     for batch_idx, its in enumerate(batches):
         decoded = pending.result()
         if cache is None:
-            pending = prefetch.submit(decode_items, batches[batch_idx + 1], zero_ref, pool) if batch_idx + 1 < len(batches) else None
+            pending = submit_decode(batch_idx + 1) if batch_idx + 1 < len(batches) else None
             batch = (load_batch_u8 if fused_in else load_batch)(its, stage, zero_ref, decoded)
             if batch_idx == 0 and len(batches) >= 16:  # a long run: make sure the batches in flight really overlap (pipeline.py)
                 pipe.calibrate(batch["query/img"], batch["reference/cross/imgs"], u8=fused_in)
@@ -166,8 +182,7 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
             tokens, ref_imgs = cache.gather([it["reference/cross/imgs"] for it in its], decoded, size, zero_ref)
             batch["reference/cross/imgs"] = ref_imgs
             # (submitted after gather so that the set of cached paths is current; decoding overlaps the forward below)
-            pending = (prefetch.submit(decode_items, batches[batch_idx + 1], zero_ref, pool, cached_paths())
-                       if batch_idx + 1 < len(batches) else None)
+            pending = submit_decode(batch_idx + 1) if batch_idx + 1 < len(batches) else None
             if batch_idx == 0 and len(batches) >= 16:  # the same check for the (default) cached mode
                 pipe.calibrate(batch["query/img"], tokens, cached=True, u8=fused_in)
             ticket = (pipe.submit_cached_u8 if fused_in else pipe.submit_cached)(batch["query/img"], tokens, need_w, head_id, True)
@@ -211,6 +226,7 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
     return {"out_dir": cfg.logger.predict.out_dir, "files": files, "rows": summariser.rows,
             "input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
             "png_encoder": png_encoder, "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
+            "png_decoder": png_decoder, "png_decoded": decoder.stats() if decoder is not None else {"png_decoded_gpu": 0, "png_decoded_host": 0},
             "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}  # the whole scoring loop: input stage, forwards, output stage
 
 
@@ -225,8 +241,8 @@ def main(argv: Optional[Iterable[str]] = None) -> int:
         return 2
     with torch.no_grad():
         res = predict(cfg)
-    print(f"[crossscore_amd.predict] {len(res['rows'])} query images, {res['query_images_per_sec']:.1f} query-images/s through the scoring loop, "
-          f"outputs under {res['out_dir']}")
+    print(f"[crossscore_amd.predict] {len(res['rows'])} query images, {res['query_images_per_sec']:.1f} query-images/s through the scoring loop "
+          f"(png_decoder {res['png_decoder']}), outputs under {res['out_dir']}")
     return 0
 
 

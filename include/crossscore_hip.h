@@ -286,6 +286,51 @@ size_t cs_png_bound(int kind, int H, int W);
 size_t cs_png_workspace_bytes(int kind, int I, int H, int W);
 int cs_op_png_encode(const void* pixels, int kind, int I, int H, int W, long long image_stride_bytes, uint8_t* out, size_t slot_bytes,
                      uint32_t* lengths, void* workspace, cs_stream stream);
+/* PNG files decoded on the device (csrc/pngdec.hip): the mirror of cs_op_png_encode.  I compressed files of one
+ * decoded size (H, W) and one output kind -> I images in device memory, image i at pixels + i * image_stride_bytes with contiguous rows:
+ * CS_PNG_RGB8 uint8 HWC from colour type 2 / depth 8, colour type 6 / depth 8 (alpha dropped) and colour type 0 / depth 8 (the sample
+ * replicated); CS_PNG_GRAY16 native-endian uint16 from colour type 0 / depth 16.  Non-interlaced files only; any number of IDAT chunks, split
+ * at any byte; stored, fixed and dynamic deflate blocks; all five filter types.  Everything else is not built: cs_png_probe says so
+ * (CS_ERR_UNSUPPORTED) and the caller decodes that file elsewhere.
+ * cs_png_probe is host arithmetic over the file's bytes (no device is touched): signature, chunk framing within n, IHDR; it fills info and,
+ * when spans is not NULL, the (offset, length) of every IDAT payload relative to the file's first byte.  CS_ERR_BAD_ARG for framing that runs
+ * past the end (or more IDAT chunks than max_spans; info->num_idat then holds the count).
+ * cs_op_png_decode: files is ONE device buffer of total_file_bytes bytes holding the files back to back, file i at file_offsets[i],
+ * file_lengths[i] long, its spans at spans[span_offsets[i] .. span_offsets[i + 1]) (all four arrays in device memory).  One launch, one
+ * workgroup per file; the call does not wait for the device.  status[i] (device) is 0 for a complete, verified image -- CRC-32 of IHDR and of
+ * every IDAT chunk, Adler-32 of the zlib stream, stream length exactly H * (1 + row bytes) -- or one of CS_PNGDEC_*; a file with a non-zero
+ * status has written no pixel and has not disturbed the other files of the call.  The kernel re-checks every span against its file's length and
+ * never reads past a file, so untrusted bytes cannot make it fault.  workspace: device, 16-byte aligned, cs_png_decode_workspace_bytes(...)
+ * bytes (host arithmetic; 0 for kinds and sizes the decoder does not take).  1 <= H, W <= 4096 (CS_ERR_UNSUPPORTED above), 1 <= I <= 65535. */
+typedef struct cs_png_info {
+  int width, height, color_type, bit_depth, interlace;
+  int kind;      /* CS_PNG_GRAY16 / CS_PNG_RGB8, -1 when the decoder does not take the file */
+  int num_idat;  /* IDAT chunks in the file */
+  unsigned long long idat_bytes;
+} cs_png_info;
+typedef struct cs_png_span { uint32_t offset, length; } cs_png_span;
+enum {
+  CS_PNGDEC_OK = 0,
+  CS_PNGDEC_BAD_CRC = 1,         /* IHDR's or an IDAT chunk's CRC-32 */
+  CS_PNGDEC_BAD_ADLER = 2,       /* Adler-32 of the inflated stream */
+  CS_PNGDEC_BAD_ZLIB_HEADER = 3, /* CMF / FLG: method, window, check bits, preset dictionary */
+  CS_PNGDEC_BAD_BLOCK_TYPE = 4,  /* reserved block type 3 */
+  CS_PNGDEC_BAD_STORED_LEN = 5,  /* LEN / NLEN of a stored block disagree */
+  CS_PNGDEC_BAD_CODE = 6,        /* over-subscribed or incomplete code, too many lengths, bad repeat, no end-of-block code */
+  CS_PNGDEC_BAD_SYMBOL = 7,      /* bits that are no code of the set, length symbols 286 / 287, distance symbols 30 / 31 */
+  CS_PNGDEC_BAD_DISTANCE = 8,    /* a distance before the start of the stream */
+  CS_PNGDEC_STREAM_SHORT = 9,    /* the stream ends before H * (1 + row bytes) */
+  CS_PNGDEC_STREAM_LONG = 10,    /* ... or goes on behind it */
+  CS_PNGDEC_BAD_FILTER = 11,     /* filter type above 4 */
+  CS_PNGDEC_INPUT_EXHAUSTED = 12,/* the IDAT bytes end inside the stream */
+  CS_PNGDEC_HEADER_MISMATCH = 13,/* IHDR's size or format is not the call's (H, W, kind) */
+  CS_PNGDEC_BAD_FRAMING = 14     /* signature, IHDR framing or a span outside its file */
+};
+int cs_png_probe(const uint8_t* file, size_t n, cs_png_info* info, cs_png_span* spans, int max_spans);
+size_t cs_png_decode_workspace_bytes(int kind, int I, int H, int W, size_t total_file_bytes);
+int cs_op_png_decode(const uint8_t* files, const uint64_t* file_offsets, const uint32_t* file_lengths, const cs_png_span* spans,
+                     const uint32_t* span_offsets, size_t total_file_bytes, int I, int kind, int H, int W, void* pixels, long long image_stride_bytes,
+                     uint32_t* status, void* workspace, cs_stream stream);
 /* de_norm_img + u8 (utils/misc/image.py:25-34, utils/io/images.py:20-23; batch_writer.py:117-135): I processed images fp32 CHW -> uint8 HWC,
  * x * std, then + mean, then * 255, each rounded on its own (no fma), truncated.  Values are clamped to [0, 255] first (NaN -> 0): that agrees
  * with the host form (a C cast) on every value the input stage produces (u8 / 255 normalised and de-normalised stays inside [0, 255]); outside

@@ -4,7 +4,8 @@ stage and the score-vs-GT sums on top of predict's work); predict scores the sam
 query-images/s through the scoring loop and over the wall, and the GPU-busy fraction of the loop (HIP events around every forward, from
 ForwardPipeline.record_timeline, which the evaluate loop's extra launches sit behind on the same streams), and for evaluate the host time
 spent queueing each batch's GT stage (it waits for nothing: a fraction of a millisecond against the forward's ~6 ms).
-usage: python tools/evaluate_e2e.py [--images-per-split 16] [--rounds 2] [--size 540x720]"""
+--png-decoders host,gpu runs every phase once per this_main.png_decoder value, alternating inside the round.
+usage: python tools/evaluate_e2e.py [--images-per-split 16] [--rounds 2] [--size 540x720] [--png-decoders host,gpu]"""
 import argparse, json, os, sys, tempfile, time
 import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
@@ -19,6 +20,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--images-per-split", type=int, default=16)
 ap.add_argument("--rounds", type=int, default=2)
 ap.add_argument("--size", default="540x720", help="render size HxW (518x518: cfg-2's geometry, no resize)")
+ap.add_argument("--png-decoders", default="host", help="comma-separated this_main.png_decoder values, one leg each per phase")
 args = ap.parse_args()
 root = tempfile.mkdtemp(prefix="eval_e2e_")
 base = os.path.join(root, "tree", "res_540")
@@ -65,12 +67,13 @@ def _maps_timed(self, *a, **k):
 data_mod.InputStage.metric_maps = _maps_timed
 
 for rnd in range(args.rounds):  # (the first round pays table builds, stream probes and page-ins)
-    for phase in ("evaluate", "predict"):
+    for phase, dec in [(ph, d) for ph in ("evaluate", "predict") for d in args.png_decoders.split(",")]:
         spans.clear()
         gt_host.clear()
         t0 = time.perf_counter()
         if phase == "evaluate":
-            over = [f"data.dataset.path={root}/tree", "data.loader.validation.shuffle=False", f"logger.test.out_dir={root}/out_{rnd}_eval"]
+            over = [f"data.dataset.path={root}/tree", "data.loader.validation.shuffle=False", f"logger.test.out_dir={root}/out_{rnd}_eval_{dec}",
+                    f"this_main.png_decoder={dec}"]
             res = evaluate(load_config("default_test", over + [c.format("test") for c in common]), state_dict=sd, now="T")
             loop = res["query_images_per_sec"]
         else:
@@ -78,14 +81,15 @@ for rnd in range(args.rounds):  # (the first round pays table builds, stream pro
             for split, other in (("train", "test"), ("test", "train")):
                 d = os.path.join(base, "s00000")
                 over = [f"data.dataset.query_dir={d}/{split}/ours_1000/renders", f"data.dataset.reference_dir={d}/{other}/ours_1000/gt",
-                        f"logger.predict.out_dir={root}/out_{rnd}_{split}_pred", "logger.predict.write.config.score_map_colour_mode=gray"]
+                        f"logger.predict.out_dir={root}/out_{rnd}_{split}_pred_{dec}", "logger.predict.write.config.score_map_colour_mode=gray",
+                        f"this_main.png_decoder={dec}"]
                 r = predict(load_config("default_predict", over + [c.format("predict") for c in common]), state_dict=sd, now="T")
                 rates.append(r["query_images_per_sec"])
             loop = n / sum(args.images_per_split / x for x in rates)
         dt = time.perf_counter() - t0
         fr = [p.in_flight_fractions() for p in spans]
         busy = sum(f["window_ms"] * (1 - f["fraction_idle"]) for f in fr if f) / max(sum(f["window_ms"] for f in fr if f), 1e-9)
-        print(json.dumps({"round": rnd, "phase": phase, "size": args.size, "query_images": n, "query_images_per_sec_loop": round(loop, 1),
+        print(json.dumps({"round": rnd, "phase": phase, "png_decoder": dec, "size": args.size, "query_images": n, "query_images_per_sec_loop": round(loop, 1),
                           "query_images_per_sec_wall": round(n / dt, 1), "gpu_busy_fraction_of_forward_window": round(busy, 3),
                           **({"gt_stage_host_ms_per_batch_median": round(1e3 * sorted(gt_host)[len(gt_host) // 2], 3),
                               "gt_stage_host_ms_per_batch_max": round(1e3 * max(gt_host), 3)} if gt_host else {})}), flush=True)

@@ -1,6 +1,7 @@
 """End-to-end predict driver on a synthetic image directory: 32 query PNGs + 20 reference PNGs at 540x720, ViT-S, 5 references per
 query, batch 8 -- wall time per stage with the reference-token cache on / off, with / without PNG outputs, and (for the legs that write PNGs)
-with the host and the gpu PNG encoder (this_main.png_encoder), alternating inside the one run."""
+with the host and the gpu PNG encoder (this_main.png_encoder), alternating inside the one run.  --png-decoder-legs runs the input side instead:
+write_png false and maps, token cache on / off, both input stages, this_main.png_decoder host and gpu alternating inside the one run."""
 import json, os, sys, tempfile, time
 import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
@@ -22,16 +23,19 @@ arch = CrossScoreNet(model_config()).arch
 sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, 1).items()}
 # write: "all" = the reference's default flags (score maps + the processed query / reference images), "maps" = score maps only, False = nothing;
 # fused = this_main.fused_input_stage (uint8 in, tokens out; "auto" takes it when no processed image is written)
+LEGS = [("all", "auto", "host", "host"), ("all", "auto", "gpu", "host"), ("maps", False, "host", "host"), ("maps", False, "gpu", "host"), ("maps", "auto", "host", "host"),
+        ("maps", "auto", "gpu", "host"), (False, False, "host", "host"), (False, "auto", "host", "host")]
+if "--png-decoder-legs" in sys.argv:
+    LEGS = [(write, fused, "host", dec) for write in (False, "maps") for fused in ("auto", False) for dec in ("host", "gpu")]
 for rnd in range(2):  # (the first round pays table builds, stream probes and page-ins)
     for cache in (True, False):
-        for write, fused, enc in (("all", "auto", "host"), ("all", "auto", "gpu"), ("maps", False, "host"), ("maps", False, "gpu"), ("maps", "auto", "host"),
-                                  ("maps", "auto", "gpu"), (False, False, "host"), (False, "auto", "host")):
+        for write, fused, enc, dec in LEGS:
             over = [f"data.dataset.query_dir={qd}", f"data.dataset.reference_dir={rd}", f"this_main.cache_reference_tokens={cache}",
-                    f"logger.predict.out_dir={root}/out_{rnd}_{cache}_{write}_{fused}_{enc}", f"logger.predict.write.flag.batch={bool(write)}",
+                    f"logger.predict.out_dir={root}/out_{rnd}_{cache}_{write}_{fused}_{enc}_{dec}", f"this_main.png_decoder={dec}", f"logger.predict.write.flag.batch={bool(write)}",
                     f"this_main.fused_input_stage={fused}", f"this_main.png_encoder={enc}"]
             if write == "maps":
                 over += ["logger.predict.write.flag.image_query=False", "logger.predict.write.flag.image_reference=False"]
             t0 = time.perf_counter(); res = predict(load_config("default_predict", over), state_dict=sd, now="T"); dt = time.perf_counter() - t0
-            print(json.dumps({"round": rnd, "cache_reference_tokens": cache, "write_png": write, "png_encoder": enc, "input_stage": res["input_stage"].split(" ")[0],
+            print(json.dumps({"round": rnd, "cache_reference_tokens": cache, "write_png": write, "png_encoder": enc, "png_decoder": dec, "input_stage": res["input_stage"].split(" ")[0],
                               "wall_s": round(dt, 2), "query_images_per_sec_wall": round(32 / dt, 1),
                               "query_images_per_sec_loop": round(res["query_images_per_sec"], 1), "files": len(res["files"])}), flush=True)
