@@ -14,7 +14,7 @@ def configure_runtime(hw_queues: int = 8) -> bool:
 
     Importing the package no longer sets this (a library should not edit process-wide runtime configuration on import): overlap
     does not depend on it -- every stream the path uses is PROBED for real concurrency when it is created (cs_op_streams_overlap,
-    pipeline.py, csrc/api.hip) and replaced until it overlaps, which works with 2, 4 or 8 queues."""
+    pipeline.py, csrc/forward.hip) and replaced until it overlaps, which works with 2, 4 or 8 queues."""
     try:
         import torch
         if torch.cuda.is_initialized():

@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcrossscore_hip.so")
-SOURCES = ["api.hip", "gemm.hip", "gemm256.hip", "attention.hip", "elementwise.hip", "preprocess.hip", "panel.hip", "panel4.hip", "patch.hip", "rowln.hip", "png.hip", "pngdec.hip", "gtmap.hip"]
+SOURCES = ["api.hip", "forward.hip", "ops.hip", "gemm.hip", "gemm256.hip", "attention.hip", "elementwise.hip", "preprocess.hip", "panel.hip", "panel4.hip", "patch.hip", "rowln.hip", "png.hip", "pngdec.hip", "gtmap.hip"]
 
 
 # panel.hip: its GELU arithmetic shares one wave's issue stream with the MFMAs; SLP-packed v_pk_fma_f32 (dependent-issue nops)
@@ -33,16 +33,19 @@ def needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True) -> str:
-    if not force and not needs_build():
-        return LIB
+def compile_library(lib: str, extra=None, csrc: str = CSRC, objdir=None, verbose: bool = True) -> str:
+    """Compiles every file of SOURCES from `csrc` (with its EXTRA_FLAGS, plus extra[file] where given: the -D switches of a measurement build)
+    into `objdir` and links the objects into `lib`.  The one place that knows how the library is put together: build() below and the tools
+    that need a variant of it (tools/gemm_phases.py, tools/panel_ablate.py, ...) all come through here."""
+    objdir = objdir or os.path.join(HERE, "build")
+    os.makedirs(objdir, exist_ok=True)
     objs = []
     procs = []
-    os.makedirs(os.path.join(HERE, "build"), exist_ok=True)
     for s in SOURCES:
-        o = os.path.join(HERE, "build", s.replace(".hip", ".o"))
+        o = os.path.join(objdir, s.replace(".hip", ".o"))
         objs.append(o)
-        cmd = [_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"] + EXTRA_FLAGS.get(s, []) + ["-c", os.path.join(CSRC, s), "-o", o]
+        cmd = ([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"] + EXTRA_FLAGS.get(s, []) + (extra or {}).get(s, []) +
+               ["-c", os.path.join(csrc, s), "-o", o])
         procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
     for cmd, p in procs:
         out, _ = p.communicate()
@@ -50,11 +53,17 @@ def build(force: bool = False, verbose: bool = True) -> str:
             raise RuntimeError("hipcc failed: " + " ".join(cmd) + "\n" + out)
         if verbose and out.strip():
             print(out, file=sys.stderr)
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+    cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
         raise RuntimeError("link failed: " + r.stdout)
-    return LIB
+    return lib
+
+
+def build(force: bool = False, verbose: bool = True) -> str:
+    if not force and not needs_build():
+        return LIB
+    return compile_library(LIB, verbose=verbose)
 
 
 if __name__ == "__main__":

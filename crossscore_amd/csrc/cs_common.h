@@ -239,3 +239,95 @@ struct CsRowLnParams {
   h16_t* out2; int ld2;         // [M][ld2]
   int n2, act2;                 // act2: 0 none, 1 ReLU, 2 LeakyReLU(0.01)
 };
+
+// ---- The launch surface between the kernel files and the host files (api.hip, forward.hip, ops.hip): every cs_*_launch / cs_*_check /
+// cs_*_supported / size helper that one .hip defines and another calls, declared ONCE.  Every defining file includes this header, so a changed
+// parameter list fails to compile there instead of linking (most of these are extern "C") and misbehaving at run time. ----
+
+// patch.hip (C++ linkage)
+size_t cs_patch_pack_elems(int C);
+hipError_t cs_patch_pack_launch(const float* w, int C, h16_t* out, int bf, hipStream_t st);
+int cs_patch_fused_supported(int H, int W, int P, int C);
+hipError_t cs_patch_fused_u8_launch(const CsU8Desc* descs, int nq, int N, int img0, int I, int H, int W, int C, int row_span, const float* mean3,
+                                    const float* std3, const h16_t* wfrag, const float* bias, const float* pos, const float* wsum, float* x, int bf,
+                                    hipStream_t st);
+int cs_patch_u8_runs(int W, int row_span);
+hipError_t cs_patch_fused_launch(const float* xq, const float* xr, int N, int img0, int I, int H, int W, int C, const h16_t* wfrag,
+                                 const float* bias, const float* pos, const float* wsum, float* x, int bf, hipStream_t st);
+
+extern "C" {
+// gemm.hip, gemm256.hip
+int cs_gemm_column_tiles(int N);
+const char* cs_gemm_check(const CsGemmParams* p, int epi);
+hipError_t cs_gemm_launch(const CsGemmParams* p, int epi, hipStream_t stream);
+int cs_gemm256_supported(const CsGemmParams* p, int epi);  // the shapes cs_gemm_launch routes to the 256-tile kernel
+hipError_t cs_gemm256_launch(const CsGemmParams* p, int epi, int bf16, hipStream_t st);
+// attention.hip
+const char* cs_attn_check(const CsAttnParams* p, int dh, int batch);
+hipError_t cs_attn_launch(const CsAttnParams* p, int dh, int batch, hipStream_t stream);
+// elementwise.hip
+hipError_t cs_im2col_launch(const float* q, const float* refs, int N, int img0, h16_t* out, int I, int H, int W, int P, int Kp,
+                            float* pmean, int bf, hipStream_t st);
+hipError_t cs_patch_wsum_launch(const float* w, int C, int P, float* wsum, hipStream_t st);
+hipError_t cs_ln_finalize_launch(const float* part, int M, int rows_padded, int sp, int C, float eps, float* stat, hipStream_t st);
+hipError_t cs_layernorm_launch(const float* x, int M, int C, const float* g, const float* b, float eps, float* of32, h16_t* obf,
+                               int bf, hipStream_t st);
+hipError_t cs_final_ln_split_launch(const float* x, int I, int img0, int Np, int C, int N, const float* g, const float* b, float eps,
+                                    const float* pe, float* q_f32, h16_t* q_bf, h16_t* mem_bf, int bf, hipStream_t st);
+hipError_t cs_cls_rows_launch(float* x, int I, int T, int C, const float* cls, const float* pos, h16_t* xb, float* stats, int sp,
+                              int bf, hipStream_t st);
+hipError_t cs_ln_fold_consts_launch(const h16_t* wp, int ldp, const float* w, const float* beta, const float* bias, int N, int K,
+                                    float* s_out, float* c_out, int bf, hipStream_t st);
+hipError_t cs_pos_bicubic_launch(const float* pos, int G, int C, int gh, int gw, float grow, float* out, hipStream_t st);
+hipError_t cs_pe_bilinear_launch(const float* pe, int ph, int pw, int C, int gh, int gw, float* out, hipStream_t st);
+hipError_t cs_pe_interp_launch(const float* pe, int ph, int pw, int C, int gh, int gw, int mode, float* out, hipStream_t st);
+hipError_t cs_pack_f16_launch(const float* w, int rows, int K, h16_t* out, int ldo, const float* row_scale, const float* col_scale,
+                              int bf, hipStream_t st);
+hipError_t cs_score_check_launch(const float* score, size_t n, unsigned* counter, hipStream_t st);
+hipError_t cs_silu_mul_launch(h16_t* x, int M, int F, int ld, int bf, hipStream_t st);
+hipError_t cs_vec_mul_launch(const float* a, const float* b, float* out, int n, hipStream_t st);
+hipError_t cs_spin_launch(unsigned long long ticks, int blocks, int lds_bytes, hipStream_t st);
+hipError_t cs_attn_weights_launch(const CsAttnParams* p, int dh, int batch, int head, float* out, hipStream_t st);
+// preprocess.hip
+hipError_t cs_preprocess_tables(int in_h, int in_w, int rs_h, int rs_w, int crop_y, int gh, int P, CsU8Tables* out, int* row_span, unsigned* generation);
+void cs_preprocess_tables_hold(int on);
+hipError_t cs_score_gray16_launch(const float* score, size_t n, int signed_range, uint16_t* out, hipStream_t stream);
+hipError_t cs_score_rgb_launch(const float* score, size_t n, float vmin, float vmax, const uint8_t* lut, uint8_t* out, hipStream_t stream);
+hipError_t cs_preprocess_launch(const uint8_t* img, int in_h, int in_w, int row_bytes, int rs_h, int rs_w, int crop_y, int crop_x, int oh,
+                                int ow, const float* mean, const float* stdv, float* out, float* scratch, hipStream_t stream);
+hipError_t cs_metric_map_launch(const uint16_t* maps, int B, int in_h, int in_w, int row_elems, int mode, int rs_h, int rs_w, int crop_y,
+                                int crop_x, int oh, int ow, float* out, float* scratch, hipStream_t stream);
+int cs_score_gt_slabs(size_t hw);
+hipError_t cs_score_gt_stats_launch(const float* score, const float* gt, int B, size_t hw, double* scratch, double* stats, hipStream_t stream);
+// panel.hip (eight waves) and panel4.hip (the four-wave form of the same kernel, its own weight image)
+int cs_panel_supported(int C, int mlp_ratio);
+size_t cs_panel8_image_bytes(int with_outproj);
+hipError_t cs_panel_pack_launch(const float* wo, const float* ls1, const float* w1, const float* g2, const float* w2, const float* ls2,
+                                h16_t* img, int bf16, hipStream_t st);
+const char* cs_panel_check(const CsPanelParams* p);
+hipError_t cs_panel_launch(const CsPanelParams* p, hipStream_t st);
+size_t cs_panel4_image_bytes(int with_outproj);
+hipError_t cs_panel4_pack_launch(const float* wo, const float* ls1, const float* w1, const float* g2, const float* w2, const float* ls2,
+                                 h16_t* img, int bf16, hipStream_t st);
+hipError_t cs_panel4_launch(const CsPanelParams* p, hipStream_t st);
+// rowln.hip
+int cs_rowln_supported(int C);
+const char* cs_rowln_check(const CsRowLnParams* p, int C);
+hipError_t cs_rowln_launch(const CsRowLnParams* p, int C, int bf16, hipStream_t st);
+// png.hip
+int cs_png_size_supported(int H, int W);
+size_t cs_png_bound_bytes(int kind, int H, int W);
+size_t cs_png_staging_bytes(int kind, int I, int H, int W);
+hipError_t cs_png_encode_launch(const void* pixels, int kind, int I, int H, int W, long long image_stride, uint8_t* out, size_t slot_bytes,
+                                uint32_t* lengths, void* workspace, hipStream_t st);
+hipError_t cs_denorm_rgb8_launch(const float* chw, int I, int H, int W, const float* mean3, const float* std3, uint8_t* out, hipStream_t st);
+// pngdec.hip
+size_t cs_pngdec_workspace(int kind, int I, int H, int W, size_t total_file_bytes);
+hipError_t cs_pngdec_launch(const uint8_t* files, const unsigned long long* file_offsets, const uint32_t* file_lengths, const uint32_t* spans,
+                            const uint32_t* span_offsets, size_t files_bytes, int I, int kind, int H, int W, void* pixels, long long image_stride,
+                            uint32_t* status, void* workspace, hipStream_t st);
+// gtmap.hip
+int cs_gtmap_max_side();
+hipError_t cs_gtmap_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, int kind, uint16_t* out,
+                           int out_ld, hipStream_t st);
+}

@@ -440,7 +440,7 @@ __global__ __launch_bounds__(256) void attn_weights_kernel(CsAttnParams p, int h
   }
 }
 
-// One wave per workgroup that does nothing for `ticks` of the 100 MHz wall clock: the probes of streams_overlap (api.hip).  Launched
+// One wave per workgroup that does nothing for `ticks` of the 100 MHz wall clock: the probes of streams_overlap (forward.hip).  Launched
 // with dynamic LDS it also limits how many workgroups a CU holds, which is what makes the dispatch of a large grid last.
 __global__ void spin_kernel(unsigned long long ticks) {
   extern __shared__ char spin_lds[];

@@ -807,8 +807,6 @@ namespace {
 }  // namespace
 
 // Host-side shape contract (checked here so a bad call fails loudly instead of faulting on the GPU).
-extern "C" int cs_gemm_column_tiles(int N);
-extern "C" int cs_gemm256_supported(const CsGemmParams* p, int epi);
 extern "C" const char* cs_gemm_check(const CsGemmParams* p, int epi) {
   // the LayerNorm-folded forms of the 256-tile kernel (gemm256.hip) have their own statistics layout: finalised (mean, rstd) rows on the consumer
   // side (ln_sp == 1), N / 64 partial slots per row on the producer side; both operand types
@@ -842,8 +840,6 @@ extern "C" const char* cs_gemm_check(const CsGemmParams* p, int epi) {
 #ifdef CS_ABLATE
 extern "C" int cs_gemm_dbg_set(long long* buf) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_cs_dbg), &buf, sizeof(buf)); }
 #endif
-
-extern "C" hipError_t cs_gemm256_launch(const CsGemmParams* p, int epi, int bf16, hipStream_t st);
 
 extern "C" hipError_t cs_gemm_launch(const CsGemmParams* p0, int epi, hipStream_t stream) {
   // K >= 512 with whole 256-column tiles (the ViT-B projections, the decoder's K/V projection at C = 768): the large-tile kernel

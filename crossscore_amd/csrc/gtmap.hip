@@ -231,7 +231,7 @@ __global__ __launch_bounds__(kThreads) void gt_mae_kernel(const uint8_t* __restr
 // the largest H and W the two grids take (rows and 16-row tiles ride in gridDim.y)
 extern "C" int cs_gtmap_max_side() { return 65535; }
 
-// kind 0 = SSIM, 1 = MAE (CS_GTMAP_*); arguments are checked by the caller (api.hip)
+// kind 0 = SSIM, 1 = MAE (CS_GTMAP_*); arguments are checked by the caller (ops.hip)
 extern "C" hipError_t cs_gtmap_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, int kind, uint16_t* out,
                                       int out_ld, hipStream_t st) {
   if (kind == 1) {

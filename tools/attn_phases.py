@@ -43,12 +43,7 @@ tmp = tempfile.mkdtemp(prefix="attn_ph_")
 pkg = os.path.join(tmp, "crossscore_amd")
 shutil.copytree(os.path.join(R, "crossscore_amd"), pkg, ignore=shutil.ignore_patterns("*.so", "build", "__pycache__"))
 shutil.copytree(os.path.join(R, "include"), os.path.join(tmp, "include"))
-objs, procs = [], []
-for s in build.SOURCES if hasattr(build, "SOURCES") else ["api.hip", "gemm.hip", "attention.hip", "elementwise.hip", "preprocess.hip", "panel.hip"]:
-    o = os.path.join(tmp, s + ".o"); objs.append(o)
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"] + build.EXTRA_FLAGS.get(s, [])
-    if s == "attention.hip": cmd += ["-DCS_ATTN_STAMP"] + ["-DCS_ATTN_" + d for d in os.environ.get("CS_ATTN_DEFS", "").split("+") if d]
-    procs.append(subprocess.Popen(cmd + ["-c", os.path.join(pkg, "csrc", s), "-o", o]))
-for pr in procs: assert pr.wait() == 0
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(pkg, "libcrossscore_hip.so")] + objs)
+build.compile_library(os.path.join(pkg, "libcrossscore_hip.so"),
+                      extra={"attention.hip": ["-DCS_ATTN_STAMP"] + ["-DCS_ATTN_" + d for d in os.environ.get("CS_ATTN_DEFS", "").split("+") if d]},
+                      csrc=os.path.join(pkg, "csrc"), objdir=tmp)
 sys.exit(subprocess.call([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, CS_ATTN_CHILD=tmp)))

@@ -1,13 +1,12 @@
 """Timing-only ablation of the GEMM kernel (run on the GPU box): which phase sets the time of one launch?
 Builds a debug copy of the library with -DCS_ABLATE into /tmp and times the encoder shapes with phases removed."""
-import ctypes as C, os, subprocess, sys, time
+import ctypes as C, os, sys, tempfile, time
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-src = os.path.join(REPO, "crossscore_amd", "csrc")
 out = "/tmp/libcs_ablate.so"
-subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DCS_ABLATE", "-Wno-unused-value", "-I" + os.path.join(REPO, "include"),
-                       "-o", out] + [os.path.join(src, f) for f in ("api.hip", "gemm.hip", "attention.hip", "elementwise.hip", "preprocess.hip", "panel.hip")])
+from crossscore_amd import build
+build.compile_library(out, extra={"gemm.hip": ["-DCS_ABLATE"]}, objdir=tempfile.mkdtemp(prefix="gemm_abl_"))
 from crossscore_amd import _lib
 _lib.LIB_PATH = out
 

@@ -1,12 +1,11 @@
 """Per-wave phase clocks of the GEMM kernel (debug build, -DCS_ABLATE): where does a wave's time go inside a K slice?"""
-import ctypes as C, os, subprocess, sys
+import ctypes as C, os, sys, tempfile
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-src = os.path.join(REPO, "crossscore_amd", "csrc")
 out = "/tmp/libcs_ablate.so"
-subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DCS_ABLATE", "-Wno-unused-value", "-I" + os.path.join(REPO, "include"),
-                       "-o", out] + [os.path.join(src, f) for f in ("api.hip", "gemm.hip", "attention.hip", "elementwise.hip", "preprocess.hip", "panel.hip")])
+from crossscore_amd import build
+build.compile_library(out, extra={"gemm.hip": ["-DCS_ABLATE"]}, objdir=tempfile.mkdtemp(prefix="gemm_abl_"))
 from crossscore_amd import _lib
 _lib.LIB_PATH = out
 sys.path.insert(0, os.path.join(REPO, "tests"))

@@ -86,16 +86,8 @@ tmp = tempfile.mkdtemp(prefix="panel_abl_")
 pkg = os.path.join(tmp, "crossscore_amd")
 shutil.copytree(os.path.join(R, "crossscore_amd"), pkg, ignore=shutil.ignore_patterns("*.so", "build", "__pycache__"))
 shutil.copytree(os.path.join(R, "include"), os.path.join(tmp, "include"))
-srcs = ["api.hip", "gemm.hip", "gemm256.hip", "attention.hip", "elementwise.hip", "preprocess.hip", "panel.hip", "patch.hip", "rowln.hip"]
-objs = []
-procs = []
-for s in srcs:
-    o = os.path.join(tmp, s + ".o"); objs.append(o)
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
-    if s == "panel.hip":
-        cmd += ["-fno-slp-vectorize", "-DCS_PANEL_ABLATE"] + os.environ.get("CS_PANEL_EXTRA", "").split()
-    procs.append(subprocess.Popen(cmd + ["-c", os.path.join(pkg, "csrc", s), "-o", o]))
-for p in procs:
-    assert p.wait() == 0
-subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", os.path.join(pkg, "libcrossscore_hip.so")] + objs)
+sys.path.insert(0, R)
+from crossscore_amd import build
+build.compile_library(os.path.join(pkg, "libcrossscore_hip.so"), extra={"panel.hip": ["-DCS_PANEL_ABLATE"] + os.environ.get("CS_PANEL_EXTRA", "").split()},
+                      csrc=os.path.join(pkg, "csrc"), objdir=tmp)
 sys.exit(subprocess.call([sys.executable, os.path.abspath(__file__)], env=dict(os.environ, CS_ABL_PKG=tmp)))
