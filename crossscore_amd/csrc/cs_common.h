@@ -84,7 +84,14 @@ __device__ __forceinline__ float wave_max(float v) {
 // GELU(x) = x * Phi(x) with the exact (erf) Phi of HF ACT2FN["gelu"] (HF modeling_dinov2.py:293-297) approximated by
 // Phi(x) ~ 0.5 + x * P(x^2), x clamped to +-4.2; P is a degree-7 minimax fit of the GELU error:
 // max |GELU_fit - GELU_erf| = 6.7e-5 (2.1e-4 as evaluated in fp32 Horner form, near |x| = 4 where y ~ x; an fp16 half-ulp is
-// 4.9e-4 at |y| = 1 and 2e-3 at 4).  12 plain VALU ops, no
+// 4.9e-4 at |y| = 1 and 2e-3 at 4).  The factor in front of Phi is clamped from below as well: y = max(x, -4.2) * Phi_fit(clamp(x, +-4.2)).
+// Phi_fit(-4.2) is 3.0e-5, not 0, so below -4.2 the result is the constant -4.2 * 3.0e-5 = -1.26e-4 (the true GELU is -0 there) and the
+// 2.1e-4 holds for every finite x <= 4.2.  Above 4.2 y = x * Phi_fit(4.2) = x (1 - 3.0e-5): a relative error, below the 16-bit store's
+// half ulp.  (tests/test_hip_activations.py and tests/test_gelu_pk16.py evaluate it on every finite 16-bit input.)
+// Non-finite pre-activations: +inf gives FLT_MAX (1 - 3.0e-5), which the store rounds to inf in both 16-bit types; -inf gives the tail;
+// a NaN comes out as the tail -1.26e-4, NOT as NaN (v_med3_f32 with a NaN operand returns the smallest of the three): an fc1 that has
+// diverged does not show as NaN behind this epilogue.
+// Plain VALU ops only (the lower clamp of the factor is a second v_med3_f32 per value), no
 // transcendentals: the fc1 epilogue was spending more issue slots on erf (v_exp + v_rcp) than its K loop on MFMAs
 // (PMC: SQ_ACTIVE_INST_VALU 51 % vs MFMA pipe busy 26 % with the Abramowitz-Stegun erf).
 // Four values per call as two packed-fp32 Horner chains (v_pk_fma_f32) issued alternately from one asm block: a lone chain pays
@@ -92,7 +99,12 @@ __device__ __forceinline__ float wave_max(float v) {
 // order.  The fitted Phi stays inside [-1.2e-6, 1 + 1.2e-6] on the clamped range, so it is not clamped again.
 __device__ __forceinline__ unsigned long long gelu_c(float c) { return (unsigned long long)__float_as_uint(c); }
 __device__ __forceinline__ void gelu_erf4(float (&v)[4]) {
-  const f32x2_t xa = {v[0], v[1]}, xb = {v[2], v[3]};
+  // max(x, -4.2) as a second v_med3_f32, the median of x, -4.2 and FLT_MAX (x itself for every finite x >= -4.2): fmaxf (and a median
+  // with +inf, which hipcc folds into it) costs two instructions per value here -- x comes straight out of an MFMA accumulator and gets a
+  // canonicalising v_max_f32 x, x in front
+  const float kMax = 3.402823466e+38f;
+  const f32x2_t xa = {__builtin_amdgcn_fmed3f(v[0], -4.2f, kMax), __builtin_amdgcn_fmed3f(v[1], -4.2f, kMax)};
+  const f32x2_t xb = {__builtin_amdgcn_fmed3f(v[2], -4.2f, kMax), __builtin_amdgcn_fmed3f(v[3], -4.2f, kMax)};
   const f32x2_t ca = {__builtin_amdgcn_fmed3f(v[0], -4.2f, 4.2f), __builtin_amdgcn_fmed3f(v[1], -4.2f, 4.2f)};
   const f32x2_t cb = {__builtin_amdgcn_fmed3f(v[2], -4.2f, 4.2f), __builtin_amdgcn_fmed3f(v[3], -4.2f, 4.2f)};
   const f32x2_t ta = ca * ca, tb = cb * cb;
@@ -127,7 +139,7 @@ __device__ __forceinline__ void gelu_erf4(float (&v)[4]) {
 // ---- kernel parameter blocks (plain structs; launchers live in the matching .hip files) -------------
 enum CsEpilogue {
   CS_EPI_BIAS_F16 = 0,        // out_f16[m][n] = acc + bias[n]
-  CS_EPI_BIAS_GELU_F16 = 1,   // erf-GELU, degree-7 minimax fit of Phi (gelu_erf4 below: max abs error 2.1e-4 in fp32)
+  CS_EPI_BIAS_GELU_F16 = 1,   // erf-GELU, degree-7 minimax fit of Phi (gelu_erf4 above: max abs error 2.1e-4 in fp32 for x <= 4.2, -1.26e-4 below -4.2)
   CS_EPI_BIAS_RELU_F16 = 2,
   CS_EPI_BIAS_LEAKY_F16 = 3,  // slope 0.01
   CS_EPI_RESID_F32 = 4,        // out_f32[m][n] = (resid? resid[m][n]:0) + (scale? scale[n]:1)*(acc+bias[n])

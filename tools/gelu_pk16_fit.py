@@ -43,9 +43,8 @@ def fit(D=6, n=20001):
     return minimax(np.stack([z ** k for k in range(D + 1)], 1), -(R * ap) * psi(R * ap))
 
 
-def kernel_gelu(x32, c):
-    """The eleven instructions of pk_gelu_block<0..5>, per value."""
-    xh = r16(x32)
+def _p6(xh, c):
+    """Stages 0..8 of pk_gelu_block on the half-rounded input: the correction term -|x| Phi(-|x|) ~ P6(z), a half."""
     t = np.maximum(xh, -xh)                      # v_pk_max_f16 x, -x
     t = np.clip(r16(t * r16(-1 / R) + 1.0), 0, 1)  # v_pk_fma_f16 t, -1/4, 1.0 clamp
     t = r16(t * t - 0.5)                         # v_pk_fma_f16 t, t, -0.5
@@ -53,7 +52,32 @@ def kernel_gelu(x32, c):
     q = r16(t * ch[6] + ch[5])
     for k in (4, 3, 2, 1, 0):
         q = r16(q * t + ch[k])
-    return r16(q + np.maximum(xh, 0))            # v_pk_max_f16 x, 0; v_pk_add_f16
+    return q
+
+
+def kernel_gelu(x32, c):
+    """The eleven instructions of pk_gelu_block<0..5>, per value."""
+    xh = r16(x32)
+    return r16(_p6(xh, c) + np.maximum(xh, 0))   # v_pk_max_f16 x, 0; v_pk_add_f16
+
+
+def rbf16(x):
+    """fp32 -> bfloat16, round to nearest even (v_cvt_pk_bf16_f32), returned as float64; finite values and infinities."""
+    b = np.asarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    b = ((b + 0x7FFF + ((b >> 16) & 1)) >> 16) << 16
+    return b.astype(np.uint32).view(np.float32).astype(np.float64)
+
+
+def kernel_gelu_bf16(a32, c):
+    """pk_gelu_block<.., true> (bf16 operand mode), per value: the correction term in half arithmetic on the half-rounded pre-activation
+    (beyond 65504 that is +-inf, d = 0 and the term is P6(-1/2)), then v_max_f32 0, a and one v_fma_mix_f32 -- the half term times 1.0 plus the
+    fp32 relu, ONE fp32 rounding -- and v_cvt_pk_bf16_f32."""
+    a = np.asarray(a32, dtype=np.float32)
+    with np.errstate(over="ignore"):
+        q = _p6(r16(a), c)
+    # (the float64 sum is exact whenever q can move the fp32 rounding: a half term and an fp32 value less than 2^29 apart span under 53 bits)
+    y32 = (q + np.maximum(a.astype(np.float64), 0.0)).astype(np.float32)
+    return rbf16(y32)
 
 
 def naive_gelu(x32, D=7, Rn=4.2):
