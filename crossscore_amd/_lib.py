@@ -105,6 +105,8 @@ SYMBOLS = {
     "cs_op_denorm_to_rgb8": (_i, [_vp, _i, _i, _i, _fp, _fp, _vp, _vp]),
     "cs_op_metric_map_u16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "cs_op_gt_metric_map_u8": (_i, [_vp, _vp, _i, _i, _i, _ll, _i, _vp, _i, _vp]),
+    "cs_op_metric_map_sums_u16": (_i, [_vp, _vp, _i, _i, _i, _i, _ll, _vp, _vp]),
+    "cs_op_gt_metric_sums_u8": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp]),
     "cs_score_gt_workspace_bytes": (_sz, [_i, _i, _i]),
     "cs_op_score_gt_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "cs_op_preprocess_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),

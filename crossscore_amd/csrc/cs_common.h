@@ -342,4 +342,8 @@ hipError_t cs_pngdec_launch(const uint8_t* files, const unsigned long long* file
 int cs_gtmap_max_side();
 hipError_t cs_gtmap_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, int kind, uint16_t* out,
                            int out_ld, hipStream_t st);
+hipError_t cs_gtsums_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, uint64_t* sums, hipStream_t st);
+// gtsum.hip
+hipError_t cs_metric_map_sums_launch(const uint16_t* ssim, const uint16_t* mae, int B, int H, int W, int row_elems, long long image_stride,
+                                     uint64_t* sums, hipStream_t st);
 }

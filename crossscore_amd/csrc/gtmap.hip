@@ -20,6 +20,7 @@
 // MAE kind (gt_mae_kernel): a thread forms four pixels of a row from aligned dwords: s = sum_c |a_c - b_c|, code (257 * s) / 3.
 // A map's codes depend on its own pixel pair alone: tiles are anchored at the image's origin, and no value crosses images.
 #include "cs_common.h"
+#include "gtsum_shared.h"
 #include <math.h>
 
 namespace {
@@ -49,8 +50,19 @@ __device__ __forceinline__ int wave_sum(int v) {
   return v;
 }
 
+// the stored SSIM sample of a pixel from the sum of its three channels' terms: one expression for the map form and the sums form
+__device__ __forceinline__ int ssim_code(float acc) {
+#pragma clang fp contract(off)
+  const float v = (acc / 3.0f + 1.0f) * 32767.0f;
+  return (int)fminf(fmaxf(v, 0.0f), 65535.0f);
+}
+
+// SUMS = false: the map form, codes stored to `out`.  SUMS = true: the same codes, never stored: with the MAE code of the same pixel (formed from
+// the bytes the tile holds in LDS) they go into the frame's four sums (cs_op_gt_metric_sums_u8), `out` is not touched.
+template <bool SUMS>
 __global__ __launch_bounds__(kThreads) void gt_ssim_kernel(const uint8_t* __restrict__ render, const uint8_t* __restrict__ gt, int H, int W,
-                                                           long long image_stride, GtTaps taps, uint16_t* __restrict__ out, int out_ld) {
+                                                           long long image_stride, GtTaps taps, uint16_t* __restrict__ out, int out_ld,
+                                                           unsigned long long* __restrict__ sums) {
 #pragma clang fp contract(off)  // see the head of the file: numerator and denominator must not be fused differently
   __shared__ uint32_t px[2][kRegH][kRowDw];
   __shared__ float plane[5][kRegH][kTileW];
@@ -171,15 +183,42 @@ __global__ __launch_bounds__(kThreads) void gt_ssim_kernel(const uint8_t* __rest
 
   // d. codes
   const int gx = x0 + ox;
-  if (gx < W) {
+  if constexpr (!SUMS) {
+    if (gx < W) {
+#pragma unroll
+      for (int o = 0; o < kRowsPerThread; ++o) {
+        const int gy = y0 + oy + o;
+        if (gy >= H) break;
+        out[((long long)b * H + gy) * out_ld + gx] = (uint16_t)ssim_code(acc[o]);
+      }
+    }
+  } else {
+    // a thread without a pixel inside the image adds zeros and still arrives at the barrier of cs_sums_block_add
+    __shared__ unsigned long long red[kThreads / 64][4];
+    uint32_t s1 = 0, s2 = 0, s3 = 0;  // at most four codes each
+    unsigned long long s4 = 0;
 #pragma unroll
     for (int o = 0; o < kRowsPerThread; ++o) {
       const int gy = y0 + oy + o;
-      if (gy >= H) break;
-      const float v = (acc[o] / 3.0f + 1.0f) * 32767.0f;
-      const int code = (int)fminf(fmaxf(v, 0.0f), 65535.0f);
-      out[((long long)b * H + gy) * out_ld + gx] = (uint16_t)code;
+      if (gx < W && gy < H) {
+        const uint32_t cs = (uint32_t)ssim_code(acc[o]);
+        const int r = oy + o + kHalo, col = (gx - xs) * 3;
+        const int oa = row_off(0, r) + col, ob = row_off(1, r) + col;
+        int s = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int va = bytes[0][oa + c], vb = bytes[1][ob + c];
+          s += va > vb ? va - vb : vb - va;
+        }
+        const uint32_t cm = (uint32_t)((257 * s) / 3);  // gt_mae_kernel's code
+        s1 += cs;
+        s2 += cs < 32767u ? 32767u : (cs > 65534u ? 65534u : cs);
+        s3 += cm;
+        s4 += (unsigned long long)(cm * cm);
+      }
     }
+    const unsigned long long v[4] = {s1, s2, s3, s4};
+    cs_sums_block_add<kThreads / 64>(v, red, sums + 4 * (long long)b);
   }
 }
 
@@ -226,6 +265,19 @@ __global__ __launch_bounds__(kThreads) void gt_mae_kernel(const uint8_t* __restr
   }
 }
 
+// 11 x 11 Gaussian, sigma 1.5, as the outer product of the 11 taps normalised to sum 1 (fp64, then rounded)
+GtTaps gt_taps() {
+  GtTaps taps;
+  double g[kTaps], sum = 0.0;
+  for (int k = 0; k < kTaps; ++k) {
+    const double d = k - kHalo;
+    g[k] = exp(-d * d / (2.0 * 1.5 * 1.5));
+    sum += g[k];
+  }
+  for (int k = 0; k < kTaps; ++k) taps.g[k] = (float)(g[k] / sum);
+  return taps;
+}
+
 }  // namespace
 
 // the largest H and W the two grids take (rows and 16-row tiles ride in gridDim.y)
@@ -239,16 +291,18 @@ extern "C" hipError_t cs_gtmap_launch(const uint8_t* render, const uint8_t* gt, 
                        image_stride, out, out_ld);
     return hipGetLastError();
   }
-  // 11 x 11 Gaussian, sigma 1.5, as the outer product of the 11 taps normalised to sum 1 (fp64, then rounded)
-  GtTaps taps;
-  double g[kTaps], sum = 0.0;
-  for (int k = 0; k < kTaps; ++k) {
-    const double d = k - kHalo;
-    g[k] = exp(-d * d / (2.0 * 1.5 * 1.5));
-    sum += g[k];
-  }
-  for (int k = 0; k < kTaps; ++k) taps.g[k] = (float)(g[k] / sum);
-  hipLaunchKernelGGL(gt_ssim_kernel, dim3((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH, B), dim3(kThreads), 0, st, render, gt, H, W,
-                     image_stride, taps, out, out_ld);
+  const GtTaps taps = gt_taps();
+  hipLaunchKernelGGL(gt_ssim_kernel<false>, dim3((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH, B), dim3(kThreads), 0, st, render, gt, H,
+                     W, image_stride, taps, out, out_ld, (unsigned long long*)nullptr);
+  return hipGetLastError();
+}
+
+// the four sums of cs_op_gt_metric_sums_u8 per pair, zeroed on the stream ahead of the one launch; arguments are checked by the caller (ops.hip)
+extern "C" hipError_t cs_gtsums_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, uint64_t* sums,
+                                       hipStream_t st) {
+  hipError_t e = hipMemsetAsync(sums, 0, (size_t)B * 4 * sizeof(uint64_t), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(gt_ssim_kernel<true>, dim3((W + kTileW - 1) / kTileW, (H + kTileH - 1) / kTileH, B), dim3(kThreads), 0, st, render, gt, H,
+                     W, image_stride, gt_taps(), (uint16_t*)nullptr, 0, reinterpret_cast<unsigned long long*>(sums));
   return hipGetLastError();
 }

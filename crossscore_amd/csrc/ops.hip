@@ -237,6 +237,35 @@ int cs_op_gt_metric_map_u8(const uint8_t* render, const uint8_t* gt, int B, int 
   return 0;
 }
 
+int cs_op_metric_map_sums_u16(const uint16_t* ssim, const uint16_t* mae, int B, int H, int W, int row_elems, long long image_stride_elems,
+                              uint64_t* sums, cs_stream stream) {
+  if (B <= 0 || B > 1024 || H <= 0 || W <= 0) return fail(CS_ERR_BAD_ARG, "metric_map_sums_u16: bad sizes (B %d, H %d, W %d; 1 <= B <= 1024)", B, H, W);
+  if (H > cs_gtmap_max_side() || W > cs_gtmap_max_side())
+    return fail(CS_ERR_UNSUPPORTED, "metric_map_sums_u16: %d x %d has a side above %d", H, W, cs_gtmap_max_side());
+  if (row_elems < W) return fail(CS_ERR_BAD_ARG, "metric_map_sums_u16: row of %d samples is below the width %d", row_elems, W);
+  if (image_stride_elems < (long long)(H - 1) * row_elems + W)
+    return fail(CS_ERR_BAD_ARG, "metric_map_sums_u16: map stride %lld is below the map's %lld samples", image_stride_elems,
+                (long long)(H - 1) * row_elems + W);
+  if (!ssim || !mae || !sums) return fail(CS_ERR_BAD_ARG, "metric_map_sums_u16: null pointer");
+  if (((uintptr_t)ssim | (uintptr_t)mae) & 1) return fail(CS_ERR_BAD_ARG, "metric_map_sums_u16: 16-bit samples must be 2-byte aligned");
+  if ((uintptr_t)sums & 7) return fail(CS_ERR_BAD_ARG, "metric_map_sums_u16: the sums must be 8-byte aligned");
+  HIPCHK(cs_metric_map_sums_launch(ssim, mae, B, H, W, row_elems, image_stride_elems, sums, (hipStream_t)stream));
+  return 0;
+}
+
+int cs_op_gt_metric_sums_u8(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride_bytes, uint64_t* sums,
+                            cs_stream stream) {
+  if (B <= 0 || B > 1024 || H <= 0 || W <= 0) return fail(CS_ERR_BAD_ARG, "gt_metric_sums_u8: bad sizes (B %d, H %d, W %d; 1 <= B <= 1024)", B, H, W);
+  if (H > cs_gtmap_max_side() || W > cs_gtmap_max_side())
+    return fail(CS_ERR_UNSUPPORTED, "gt_metric_sums_u8: %d x %d has a side above %d", H, W, cs_gtmap_max_side());
+  if (image_stride_bytes < (long long)H * W * 3)
+    return fail(CS_ERR_BAD_ARG, "gt_metric_sums_u8: image stride %lld is below the image's %lld bytes", image_stride_bytes, (long long)H * W * 3);
+  if (!render || !gt || !sums) return fail(CS_ERR_BAD_ARG, "gt_metric_sums_u8: null pointer");
+  if ((uintptr_t)sums & 7) return fail(CS_ERR_BAD_ARG, "gt_metric_sums_u8: the sums must be 8-byte aligned");
+  HIPCHK(cs_gtsums_launch(render, gt, B, H, W, image_stride_bytes, sums, (hipStream_t)stream));
+  return 0;
+}
+
 size_t cs_score_gt_workspace_bytes(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
   return (size_t)B * cs_score_gt_slabs((size_t)H * W) * 6 * sizeof(double);

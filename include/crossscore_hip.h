@@ -363,6 +363,25 @@ int cs_op_metric_map_u16(const uint16_t* maps, int B, int in_h, int in_w, int in
 enum { CS_GTMAP_SSIM = 0, CS_GTMAP_MAE = 1 };
 int cs_op_gt_metric_map_u8(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride_bytes, int kind,
                            uint16_t* out, int out_row_elems, cs_stream stream);
+/* Per-frame sums of the ground-truth maps, the device side of the ground-truth score summary (crossscore_amd/summarise_gt.py; DESIGN.md
+ * section 6, row f8).  Over a frame's n = H * W pairs of 16-bit samples (c_ssim from metric_map/ssim, c_mae from metric_map/mae):
+ *   sums[b][0] = S1 = sum c_ssim
+ *   sums[b][1] = S2 = sum min(max(c_ssim, 32767), 65534)   the clip of c / 32767 - 1 to [0, 1]: below 32767 reads negative, 65535 as 1.00003
+ *   sums[b][2] = S3 = sum c_mae
+ *   sums[b][3] = S4 = sum c_mae^2                          <= 65535^2 * 65535^2 < 2^64
+ * unsigned 64-bit integers, exact; nothing is formed in floating point on the device.  The host forms (score_summariser.py:33-53)
+ *   ssim_-1_1 = S1 / (32767 n) - 1, ssim_0_1 = (S2 - 32767 n) / (32767 n), mae = S3 / (65535 n), mse = S4 / (65535^2 n), psnr = -10 log10(mse).
+ * Integer addition is associative: a frame's sums are the same numbers alone and at any position of any batch, whatever the order of tiles
+ * and atomics.  Both ops zero `sums` (device, B * 4 words, 8-byte aligned) on `stream` and then queue one launch; nothing is waited for or
+ * allocated.  1 <= B <= 1024, 1 <= H, W <= 65535 (CS_ERR_UNSUPPORTED above); bad arguments are rejected before anything is queued.
+ * cs_op_metric_map_sums_u16: the maps as stored, two arrays [B][H][row_elems] of uint16 (2-byte aligned at least), row_elems >= W, frames
+ * image_stride_elems >= (H - 1) * row_elems + W samples apart in both; only [row, row + W) of a row is read.
+ * cs_op_gt_metric_sums_u8: the same four sums of the maps cs_op_gt_metric_map_u8 would write for the B pairs (CS_GTMAP_SSIM and CS_GTMAP_MAE,
+ * same arguments), exactly, in one launch and without the maps in memory. */
+int cs_op_metric_map_sums_u16(const uint16_t* ssim, const uint16_t* mae, int B, int H, int W, int row_elems, long long image_stride_elems,
+                              uint64_t* sums, cs_stream stream);
+int cs_op_gt_metric_sums_u8(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride_bytes, uint64_t* sums,
+                            cs_stream stream);
 /* Score-vs-GT sums: score, gt (B, H, W) fp32 -> stats (B, 6) fp64 = per image sum|s-g|, sum s, sum g, sum s^2, sum g^2, sum s*g, accumulated
  * in fp64 (the L1 loss, Pearson correlation and PSNR of task/core.py:265-293, 379-417 follow on the host).  Two launches, a fixed order: an
  * image's six sums have the same bits alone and at any position of any batch.  NaN propagates.  scratch: device, at least
