@@ -12,6 +12,7 @@ CS_OK, CS_ERR_BAD_ARG, CS_ERR_UNSUPPORTED, CS_ERR_STATE, CS_ERR_HIP = range(5)
 # cs_op_metric_map_u16 modes (CS_METRIC_*): the GT map's load_content conversion, by (metric type, metric min)
 METRIC_SSIM_M1_1, METRIC_SSIM_0_1, METRIC_MAE, METRIC_MSE = range(4)
 PNG_GRAY16, PNG_RGB8 = 0, 1  # cs_op_png_encode kinds (CS_PNG_*)
+PNG_DYNAMIC, PNG_ADAPTIVE_FILTER = 1, 2  # cs_op_png_encode_ex flags (CS_PNG_*)
 # status words of cs_op_png_decode (CS_PNGDEC_*)
 (PNGDEC_OK, PNGDEC_BAD_CRC, PNGDEC_BAD_ADLER, PNGDEC_BAD_ZLIB_HEADER, PNGDEC_BAD_BLOCK_TYPE, PNGDEC_BAD_STORED_LEN, PNGDEC_BAD_CODE, PNGDEC_BAD_SYMBOL,
  PNGDEC_BAD_DISTANCE, PNGDEC_STREAM_SHORT, PNGDEC_STREAM_LONG, PNGDEC_BAD_FILTER, PNGDEC_INPUT_EXHAUSTED, PNGDEC_HEADER_MISMATCH,
@@ -99,6 +100,7 @@ SYMBOLS = {
     "cs_png_bound": (_sz, [_i, _i, _i]),
     "cs_png_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cs_op_png_encode": (_i, [_vp, _i, _i, _i, _i, _ll, _vp, _sz, _vp, _vp, _vp]),
+    "cs_op_png_encode_ex": (_i, [_vp, _i, _i, _i, _i, _ll, _vp, _sz, _vp, _vp, _vp, _i]),
     "cs_png_probe": (_i, [_vp, _sz, _vp, _vp, _i]),
     "cs_png_decode_workspace_bytes": (_sz, [_i, _i, _i, _i, _sz]),
     "cs_op_png_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _ll, _vp, _vp, _vp]),

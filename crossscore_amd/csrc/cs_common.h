@@ -331,7 +331,7 @@ int cs_png_size_supported(int H, int W);
 size_t cs_png_bound_bytes(int kind, int H, int W);
 size_t cs_png_staging_bytes(int kind, int I, int H, int W);
 hipError_t cs_png_encode_launch(const void* pixels, int kind, int I, int H, int W, long long image_stride, uint8_t* out, size_t slot_bytes,
-                                uint32_t* lengths, void* workspace, hipStream_t st);
+                                uint32_t* lengths, void* workspace, int flags, hipStream_t st);
 hipError_t cs_denorm_rgb8_launch(const float* chw, int I, int H, int W, const float* mean3, const float* std3, uint8_t* out, hipStream_t st);
 // pngdec.hip
 size_t cs_pngdec_workspace(int kind, int I, int H, int W, size_t total_file_bytes);

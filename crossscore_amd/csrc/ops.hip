@@ -294,8 +294,10 @@ size_t cs_png_workspace_bytes(int kind, int I, int H, int W) {
   return cs_png_staging_bytes(kind, I, H, W);
 }
 
-int cs_op_png_encode(const void* pixels, int kind, int I, int H, int W, long long image_stride_bytes, uint8_t* out, size_t slot_bytes,
-                     uint32_t* lengths, void* workspace, cs_stream stream) {
+int cs_op_png_encode_ex(const void* pixels, int kind, int I, int H, int W, long long image_stride_bytes, uint8_t* out, size_t slot_bytes,
+                        uint32_t* lengths, void* workspace, cs_stream stream, int flags) {
+  if (flags < 0 || flags > (CS_PNG_DYNAMIC | CS_PNG_ADAPTIVE_FILTER))
+    return fail(CS_ERR_BAD_ARG, "png_encode: flags %d outside 0 .. 3 (CS_PNG_DYNAMIC | CS_PNG_ADAPTIVE_FILTER)", flags);
   if (kind != CS_PNG_GRAY16 && kind != CS_PNG_RGB8) return fail(CS_ERR_BAD_ARG, "png_encode: kind %d is neither CS_PNG_GRAY16 nor CS_PNG_RGB8", kind);
   if (I <= 0 || I > 65535 || H <= 0 || W <= 0) return fail(CS_ERR_BAD_ARG, "png_encode: bad sizes (I %d, H %d, W %d; 1 <= I <= 65535)", I, H, W);
   if (!cs_png_size_supported(H, W)) return fail(CS_ERR_UNSUPPORTED, "png_encode: %d x %d is larger than 4096 x 4096", H, W);
@@ -307,8 +309,13 @@ int cs_op_png_encode(const void* pixels, int kind, int I, int H, int W, long lon
   if (!pixels || !out || !lengths || !workspace) return fail(CS_ERR_BAD_ARG, "png_encode: null pointer");
   if (kind == CS_PNG_GRAY16 && ((uintptr_t)pixels & 1)) return fail(CS_ERR_BAD_ARG, "png_encode: 16-bit samples must be 2-byte aligned");
   if ((uintptr_t)workspace & 15) return fail(CS_ERR_BAD_ARG, "png_encode: the workspace must be 16-byte aligned");
-  HIPCHK(cs_png_encode_launch(pixels, kind, I, H, W, image_stride_bytes, out, slot_bytes, lengths, workspace, (hipStream_t)stream));
+  HIPCHK(cs_png_encode_launch(pixels, kind, I, H, W, image_stride_bytes, out, slot_bytes, lengths, workspace, flags, (hipStream_t)stream));
   return 0;
+}
+
+int cs_op_png_encode(const void* pixels, int kind, int I, int H, int W, long long image_stride_bytes, uint8_t* out, size_t slot_bytes,
+                     uint32_t* lengths, void* workspace, cs_stream stream) {
+  return cs_op_png_encode_ex(pixels, kind, I, H, W, image_stride_bytes, out, slot_bytes, lengths, workspace, stream, 0);
 }
 
 // ---- PNG decoder (pngdec.hip): the host probe, the workspace size and the launch

@@ -12,6 +12,16 @@
 //
 // Filter: Sub (type 1) for both kinds, on every row.  Filtering reads raw pixels only.
 //
+// Two opt-in flags (cs_op_png_encode_ex) change what a segment's workgroup emits; without them the bytes are the ones described above.
+//   CS_PNG_ADAPTIVE_FILTER  every row takes the filter type (None, Sub, Up, Average, Paeth) whose filtered bytes have the smallest
+//      sum of min(f, 256 - f), ties to the lowest type.  A wave scores a whole row from the raw pixels (the row above row 0 is zeros), so the
+//      two segments that share a straddling row reach the same type without talking to each other.
+//   CS_PNG_DYNAMIC  after the parse the workgroup counts, with LDS integer atomics, the symbols of the parse's tokens and the plain bytes of
+//      the segment (the literals-only form), builds a length-limited prefix code for each (png_huff.h: rank sort by (count, symbol), one lane
+//      per code set for the serial construction over <= 320 symbols), prices stored / fixed + tokens / dynamic + tokens / dynamic + literals
+//      exactly from the counts, and emits the smallest (a later form wins only when strictly smaller in bytes).  No form is longer than the
+//      stored one, so cs_png_bound holds as it is.
+//
 // Kernel 1 (png_segment_kernel, one workgroup per (segment, image)):
 //   a. filtered bytes -> LDS; the segment's Adler sums S = sum b_i, T = sum (n - i) b_i
 //   b. LZ77 candidates: a 4096-entry hash table over 3-byte prefixes, filled 512 positions at a time (atomicMax: the result does not depend
@@ -25,6 +35,7 @@
 //   chunk is copied there.  Segment 0's workgroup also writes signature + IHDR, the last segment's the Adler chunk, IEND and the file length.
 // Two launches per call whatever I is; nothing waits for the device.  The bytes of an image depend on its pixels, size and kind alone.
 #include "cs_common.h"
+#include "png_huff.h"
 
 #define CS_PNG_SEG 16384
 #define CS_PNG_SLOT (CS_PNG_SEG + 64)   // staging bytes per segment: 16-byte record + chunk (<= 12 + 2 + 5 + SEG) + slack for word reads
@@ -77,6 +88,22 @@ __device__ __forceinline__ uint32_t filtered_byte(const uint8_t* img, const PngG
   const uint32_t a = raw_byte(r, g.kind, j);
   const uint32_t b = j >= g.bpp ? raw_byte(r, g.kind, j - g.bpp) : 0u;
   return (a - b) & 0xffu;
+}
+
+// the same with the row's own filter type: ftype[row - r0], chosen by step a0 of the kernel
+__device__ __forceinline__ uint32_t filtered_byte_adaptive(const uint8_t* img, const PngGeom& g, unsigned p, const uint8_t* ftype, unsigned r0) {
+  const unsigned row = p / (unsigned)g.rl;
+  const int col = (int)(p - row * (unsigned)g.rl);
+  const int type = ftype[row - r0];
+  if (col == 0) return (uint32_t)type;
+  const int j = col - 1;
+  const uint8_t* r = img + (size_t)row * g.rb;
+  const bool left = j >= g.bpp, up = row > 0 && type >= 2;
+  const uint32_t x = raw_byte(r, g.kind, j);
+  const uint32_t a = left ? raw_byte(r, g.kind, j - g.bpp) : 0u;
+  const uint32_t b = up ? raw_byte(r - g.rb, g.kind, j) : 0u;
+  const uint32_t c = up && left ? raw_byte(r - g.rb, g.kind, j - g.bpp) : 0u;
+  return cs_huff::png_filter(type, x, a, b, c);
 }
 
 // four bytes at any byte offset of a word array (little-endian)
@@ -136,6 +163,24 @@ constexpr int kOutWords = (CS_PNG_SEG + 64) / 4;          // chunk image capacit
 constexpr int kLdsBytes = kInBytes + kLdBytes + kUBytes + 1024 + 64 + 256;
 static_assert(kUBytes % 4 == 0 && kUBytes >= kOutWords * 4 && kUBytes >= 4096 * 4, "union region");
 
+// LDS behind the image above, CS_PNG_DYNAMIC only.  Code sets: 0 = the parse's tokens, 1 = literals only, 2 = the fixed code (lengths preset,
+// so that one emitter serves all three); sort trees: 0 = set 0 literal/length, 1 = set 0 distance, 2 = set 1 literal/length.
+struct DynLds {
+  uint32_t hist[2][cs_huff::kAlpha];
+  uint32_t key[3][cs_huff::kLL];
+  uint16_t sym[3][cs_huff::kLL];
+  uint16_t code[3][cs_huff::kAlpha];
+  uint8_t len[3][cs_huff::kAlpha];
+  uint32_t hdr[2][cs_huff::kHdrWords];
+  cs_huff::HeaderScratch hs[2];
+  uint32_t num[3][16];
+  uint32_t used[3];
+  uint32_t hdrbits[2];
+  uint32_t bits[3];  // payload bits with the end-of-block code: set 0, set 1, set 2 with set 0's counts
+};
+static_assert(kLdsBytes % 16 == 0 && kLdsBytes + sizeof(DynLds) <= 160 * 1024, "LDS of the dynamic form");
+
+template <int FLAGS>
 __global__ __launch_bounds__(CS_PNG_THREADS) void png_segment_kernel(const uint8_t* __restrict__ pixels, long long image_stride, PngGeom g,
                                                                      uint8_t* __restrict__ staging) {
   extern __shared__ __attribute__((aligned(16))) unsigned char png_lds[];
@@ -169,6 +214,37 @@ __global__ __launch_bounds__(CS_PNG_THREADS) void png_segment_kernel(const uint8
     for (int k = 0; k < (tid - 256) + 3; ++k) p = crc_mulmod(p, p);
     cpow[tid - 256] = p;
   }
+  // ---- a0. adaptive filter: a wave scores each row that has bytes in this segment, over the whole row (the types sit in ld's bytes until b)
+  const uint8_t* ftype = reinterpret_cast<const uint8_t*>(ld);
+  const unsigned row0 = seg0 / (unsigned)g.rl;
+  if constexpr ((FLAGS & 2) != 0) {
+    const unsigned row1 = (seg0 + (unsigned)n - 1u) / (unsigned)g.rl;
+    for (unsigned row = row0 + wv; row <= row1; row += NW) {
+      const uint8_t* cur = src + (size_t)row * g.rb;
+      uint32_t sc[5] = {0u, 0u, 0u, 0u, 0u};
+      for (int j = lane; j < g.rb; j += 64) {
+        const bool left = j >= g.bpp, up = row > 0;
+        const uint32_t x = raw_byte(cur, g.kind, j);
+        const uint32_t a = left ? raw_byte(cur, g.kind, j - g.bpp) : 0u;
+        const uint32_t b = up ? raw_byte(cur - g.rb, g.kind, j) : 0u;
+        const uint32_t c = up && left ? raw_byte(cur - g.rb, g.kind, j - g.bpp) : 0u;
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+          const uint32_t f = cs_huff::png_filter(t, x, a, b, c);
+          sc[t] += min(f, 256u - f);
+        }
+      }
+      int best = 0;
+      uint32_t best_score = 0xffffffffu;
+#pragma unroll
+      for (int t = 0; t < 5; ++t) {
+        for (int o = 32; o >= 1; o >>= 1) sc[t] += __shfl_xor(sc[t], o, 64);
+        if (sc[t] < best_score) { best_score = sc[t]; best = t; }
+      }
+      if (lane == 0) reinterpret_cast<uint8_t*>(ld)[row - row0] = (uint8_t)best;
+    }
+    __syncthreads();
+  }
   // ---- a. filtered bytes, Adler sums
   uint32_t s_sum = 0;
   unsigned long long t_sum = 0;
@@ -178,7 +254,7 @@ __global__ __launch_bounds__(CS_PNG_THREADS) void png_segment_kernel(const uint8
     for (int e = 0; e < 4; ++e) {
       const int t = w * 4 + e;
       if (t < n) {
-        const uint32_t b = filtered_byte(src, g, seg0 + t);
+        const uint32_t b = (FLAGS & 2) ? filtered_byte_adaptive(src, g, seg0 + t, ftype, row0) : filtered_byte(src, g, seg0 + t);
         v |= b << (8 * e);
         s_sum += b;
         t_sum += (unsigned long long)(n - t) * b;
@@ -267,53 +343,198 @@ __global__ __launch_bounds__(CS_PNG_THREADS) void png_segment_kernel(const uint8
   __syncthreads();
   const int pay0 = 8 + (first ? 2 : 0);             // byte offset of the deflate data in the chunk image
   const int stored_bytes = 5 + n;
-  uint32_t bitpos = (uint32_t)pay0 * 8u + 3u;       // running bit offset; 3 header bits first
-  for (int base = 0; base < n; base += CS_PNG_THREADS) {
-    const int i = base + tid;
-    uint2 tb = make_uint2(0u, 0u);
-    if (i < n) {
-      const uint32_t e = ld[i];
-      if (e & 0x80000000u) tb = token_bits(in8[i], (int)(e & 0x1ffu), (int)((e >> 9) & 0x3fffu));
-    }
-    uint32_t inc = tb.y;  // inclusive wave scan
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t u = __shfl_up(inc, o, 64);
-      if (lane >= o) inc += u;
-    }
-    if (lane == 63) red[wv] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int k = 0; k < NW; ++k) { const uint32_t u = red[k]; if (k < wv) before += u; all += u; }
-    const uint32_t o = bitpos + before + inc - tb.y;
-    if (tb.y && (int)(o >> 5) + 1 < kOutWords) {
-      const uint64_t v = (uint64_t)tb.x << (o & 31u);
-      atomicOr(&out32[o >> 5], (uint32_t)v);
-      if ((uint32_t)(v >> 32)) atomicOr(&out32[(o >> 5) + 1], (uint32_t)(v >> 32));
-    }
-    bitpos += all;
-    __syncthreads();
-  }
-  // end-of-block (7 zero bits), then either BFINAL's padding or the empty stored block 000 | pad | 00 00 FF FF
-  const uint32_t endbits = bitpos + 7u + (last ? 0u : 3u);
-  const int fixed_bytes = (int)((endbits + 7u) / 8u) - pay0 + (last ? 0 : 4);
-  const bool use_fixed = fixed_bytes < stored_bytes;
   int plen;  // chunk data bytes
-  if (use_fixed) {
-    plen = (first ? 2 : 0) + fixed_bytes;
-    if (tid == 0) {
-      atomicOr(&out32[(pay0 * 8) >> 5], (uint32_t)((last ? 1u : 0u) | 2u) << ((pay0 * 8) & 31));  // BFINAL, BTYPE = 01
-      if (!last) { out8[8 + plen - 2] = 0xff; out8[8 + plen - 1] = 0xff; }
+  if constexpr ((FLAGS & 1) == 0) {
+    uint32_t bitpos = (uint32_t)pay0 * 8u + 3u;       // running bit offset; 3 header bits first
+    for (int base = 0; base < n; base += CS_PNG_THREADS) {
+      const int i = base + tid;
+      uint2 tb = make_uint2(0u, 0u);
+      if (i < n) {
+        const uint32_t e = ld[i];
+        if (e & 0x80000000u) tb = token_bits(in8[i], (int)(e & 0x1ffu), (int)((e >> 9) & 0x3fffu));
+      }
+      uint32_t inc = tb.y;  // inclusive wave scan
+      for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t u = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += u;
+      }
+      if (lane == 63) red[wv] = inc;
+      __syncthreads();
+      uint32_t before = 0, all = 0;
+      for (int k = 0; k < NW; ++k) { const uint32_t u = red[k]; if (k < wv) before += u; all += u; }
+      const uint32_t o = bitpos + before + inc - tb.y;
+      if (tb.y && (int)(o >> 5) + 1 < kOutWords) {
+        const uint64_t v = (uint64_t)tb.x << (o & 31u);
+        atomicOr(&out32[o >> 5], (uint32_t)v);
+        if ((uint32_t)(v >> 32)) atomicOr(&out32[(o >> 5) + 1], (uint32_t)(v >> 32));
+      }
+      bitpos += all;
+      __syncthreads();
+    }
+    // end-of-block (7 zero bits), then either BFINAL's padding or the empty stored block 000 | pad | 00 00 FF FF
+    const uint32_t endbits = bitpos + 7u + (last ? 0u : 3u);
+    const int fixed_bytes = (int)((endbits + 7u) / 8u) - pay0 + (last ? 0 : 4);
+    const bool use_fixed = fixed_bytes < stored_bytes;
+    if (use_fixed) {
+      plen = (first ? 2 : 0) + fixed_bytes;
+      if (tid == 0) {
+        atomicOr(&out32[(pay0 * 8) >> 5], (uint32_t)((last ? 1u : 0u) | 2u) << ((pay0 * 8) & 31));  // BFINAL, BTYPE = 01
+        if (!last) { out8[8 + plen - 2] = 0xff; out8[8 + plen - 1] = 0xff; }
+      }
+    } else {
+      plen = (first ? 2 : 0) + stored_bytes;
+      for (int w = tid; w < kOutWords; w += CS_PNG_THREADS) out32[w] = 0;
+      __syncthreads();
+      if (tid == 0) {
+        out8[pay0] = last ? 1 : 0;
+        out8[pay0 + 1] = (uint8_t)(n & 0xff); out8[pay0 + 2] = (uint8_t)(n >> 8);
+        out8[pay0 + 3] = (uint8_t)(~n & 0xff); out8[pay0 + 4] = (uint8_t)((~n >> 8) & 0xff);
+      }
+      for (int t = tid; t < n; t += CS_PNG_THREADS) out8[pay0 + 5 + t] = in8[t];
     }
   } else {
-    plen = (first ? 2 : 0) + stored_bytes;
-    for (int w = tid; w < kOutWords; w += CS_PNG_THREADS) out32[w] = 0;
+    using namespace cs_huff;
+    DynLds& D = *reinterpret_cast<DynLds*>(png_lds + kLdsBytes);
+    // d1. counts of both forms, each with one end-of-block; the fixed set's lengths
+    for (int t = tid; t < 2 * kAlpha; t += CS_PNG_THREADS) (&D.hist[0][0])[t] = 0;
+    for (int t = tid; t < 3 * kAlpha; t += CS_PNG_THREADS) (&D.len[0][0])[t] = t >= 2 * kAlpha ? (uint8_t)fixed_length(t - 2 * kAlpha) : (uint8_t)0;
+    if (tid < 3) D.bits[tid] = 0;
     __syncthreads();
-    if (tid == 0) {
-      out8[pay0] = last ? 1 : 0;
-      out8[pay0 + 1] = (uint8_t)(n & 0xff); out8[pay0 + 2] = (uint8_t)(n >> 8);
-      out8[pay0 + 3] = (uint8_t)(~n & 0xff); out8[pay0 + 4] = (uint8_t)((~n >> 8) & 0xff);
+    for (int i = tid; i < n; i += CS_PNG_THREADS) {
+      const uint32_t byte = in8[i], e = ld[i];
+      atomicAdd(&D.hist[1][byte], 1u);
+      if (e & 0x80000000u) {
+        const int l = (int)(e & 0x1ffu);
+        if (l < 3) atomicAdd(&D.hist[0][byte], 1u);
+        else {
+          uint32_t sy, eb, ev, dc, db, dv;
+          length_symbol(l, &sy, &eb, &ev);
+          dist_symbol((int)((e >> 9) & 0x3fffu), &dc, &db, &dv);
+          atomicAdd(&D.hist[0][sy], 1u);
+          atomicAdd(&D.hist[0][kLL + dc], 1u);
+        }
+      }
     }
-    for (int t = tid; t < n; t += CS_PNG_THREADS) out8[pay0 + 5 + t] = in8[t];
+    if (tid == 0) { atomicAdd(&D.hist[0][256], 1u); atomicAdd(&D.hist[1][256], 1u); }
+    __syncthreads();
+    // d2. the used symbols of each tree in ascending (count, symbol) order: every symbol finds its own rank
+    for (int w = tid; w < kAlpha + kLL; w += CS_PNG_THREADS) {
+      const int tree = w < kLL ? 0 : w < kAlpha ? 1 : 2;
+      const uint32_t* h = D.hist[tree == 2 ? 1 : 0];
+      const int t = tree == 2 ? w - kAlpha : w, lo = tree == 1 ? kLL : 0, hi = tree == 1 ? kAlpha : kLL;
+      if (h[t] || t == lo) {
+        int used;
+        const int r = sort_rank(h, lo, hi, t, &used);
+        if (h[t]) { D.key[tree][r] = h[t]; D.sym[tree][r] = (uint16_t)t; }
+        if (t == lo) D.used[tree] = (uint32_t)used;
+      }
+    }
+    __syncthreads();
+    // d3. code lengths, codes and block header: one lane per set, serial over symbols
+    if (tid == 0 || tid == 64) {
+      const int s = tid >> 6;
+      code_lengths(D.key[2 * s], D.sym[2 * s], (int)D.used[2 * s], 0, 15, D.num[s], D.len[s]);
+      if (s == 0) code_lengths(D.key[1], D.sym[1], (int)D.used[1], kLL, 15, D.num[s], D.len[s]);
+      canonical_codes(D.len[s], kLL, 15, D.num[s], D.code[s]);
+      canonical_codes(D.len[s] + kLL, kD, 15, D.num[s], D.code[s] + kLL);
+      D.hdrbits[s] = dynamic_header(D.len[s], &D.hs[s], D.hdr[s]);
+    } else if (tid == 128) {
+      canonical_codes(D.len[2], kLL, 15, D.num[2], D.code[2]);
+      canonical_codes(D.len[2] + kLL, kD, 15, D.num[2], D.code[2] + kLL);
+    }
+    __syncthreads();
+    // d4. exact sizes from the counts; the smallest form wins, a later one only when strictly smaller in bytes
+    if (tid < kAlpha) {
+      const uint32_t h0 = D.hist[0][tid], h1 = D.hist[1][tid], x = extra_bits(tid);
+      if (h0) { atomicAdd(&D.bits[0], h0 * (D.len[0][tid] + x)); atomicAdd(&D.bits[2], h0 * (fixed_length(tid) + x)); }
+      if (h1) atomicAdd(&D.bits[1], h1 * D.len[1][tid]);
+    }
+    __syncthreads();
+    auto block_bytes = [&](uint32_t bits) { return (int)(last ? (3u + bits + 7u) / 8u : (3u + bits + 3u + 7u) / 8u + 4u); };
+    int choice = 0, best_bytes = stored_bytes;  // 0 stored, 1 fixed + tokens, 2 dynamic + tokens, 3 dynamic + literals
+    { const int c = block_bytes(D.bits[2]); if (c < best_bytes) { best_bytes = c; choice = 1; } }
+    { const int c = block_bytes(D.hdrbits[0] + D.bits[0]); if (c < best_bytes) { best_bytes = c; choice = 2; } }
+    { const int c = block_bytes(D.hdrbits[1] + D.bits[1]); if (c < best_bytes) { best_bytes = c; choice = 3; } }
+    if (choice != 0) {
+      // d5. the winner's bits: header words, then a token per reached position (or a literal per byte), then end-of-block
+      const int set = choice == 1 ? 2 : choice == 2 ? 0 : 1;
+      const bool literals = choice == 3;
+      const uint16_t* code = D.code[set];
+      const uint8_t* len = D.len[set];
+      uint32_t bitpos = (uint32_t)pay0 * 8u + 3u;
+      if (choice >= 2) {
+        const uint32_t hb = D.hdrbits[set];
+        if (tid < kHdrWords && (uint32_t)tid * 32u < hb) {
+          const uint32_t o = bitpos + 32u * (uint32_t)tid;
+          const uint64_t v = (uint64_t)D.hdr[set][tid] << (o & 31u);
+          if ((int)(o >> 5) + 1 < kOutWords) {
+            if ((uint32_t)v) atomicOr(&out32[o >> 5], (uint32_t)v);
+            if ((uint32_t)(v >> 32)) atomicOr(&out32[(o >> 5) + 1], (uint32_t)(v >> 32));
+          }
+        }
+        bitpos += hb;
+      }
+      for (int base = 0; base < n; base += CS_PNG_THREADS) {
+        const int i = base + tid;
+        uint64_t v = 0;   // a dynamic-coded match is up to 15 + 5 + 15 + 13 = 48 bits
+        uint32_t nb = 0;
+        if (i < n) {
+          const uint32_t e = ld[i], byte = in8[i];
+          const int l = (int)(e & 0x1ffu);
+          if (literals || ((e & 0x80000000u) && l < 3)) { v = code[byte]; nb = len[byte]; }
+          else if (e & 0x80000000u) {
+            uint32_t sy, eb, ev, dc, db, dv;
+            length_symbol(l, &sy, &eb, &ev);
+            dist_symbol((int)((e >> 9) & 0x3fffu), &dc, &db, &dv);
+            v = code[sy]; nb = len[sy];
+            v |= (uint64_t)ev << nb; nb += eb;
+            v |= (uint64_t)code[kLL + dc] << nb; nb += len[kLL + dc];
+            v |= (uint64_t)dv << nb; nb += db;
+          }
+        }
+        uint32_t inc = nb;  // inclusive wave scan
+        for (int o = 1; o < 64; o <<= 1) {
+          const uint32_t u = __shfl_up(inc, o, 64);
+          if (lane >= o) inc += u;
+        }
+        if (lane == 63) red[wv] = inc;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (int k = 0; k < NW; ++k) { const uint32_t u = red[k]; if (k < wv) before += u; all += u; }
+        const uint32_t o = bitpos + before + inc - nb;
+        if (nb && (int)(o >> 5) + 2 < kOutWords) {  // up to three words
+          const uint32_t sh = o & 31u;
+          const uint64_t lo = v << sh;
+          const uint32_t hi = sh ? (uint32_t)(v >> (64u - sh)) : 0u;
+          if ((uint32_t)lo) atomicOr(&out32[o >> 5], (uint32_t)lo);
+          if ((uint32_t)(lo >> 32)) atomicOr(&out32[(o >> 5) + 1], (uint32_t)(lo >> 32));
+          if (hi) atomicOr(&out32[(o >> 5) + 2], hi);
+        }
+        bitpos += all;
+        __syncthreads();
+      }
+      const uint32_t endbits = bitpos + len[256] + (last ? 0u : 3u);
+      // equals the priced size, which is below the stored form's; the min keeps the chunk inside its staging slot whatever happens
+      const int block = min((int)((endbits + 7u) / 8u) - pay0 + (last ? 0 : 4), stored_bytes);
+      plen = (first ? 2 : 0) + block;
+      if (tid == 0) {
+        if ((int)(bitpos >> 5) + 1 < kOutWords) {
+          const uint64_t v = (uint64_t)code[256] << (bitpos & 31u);
+          atomicOr(&out32[bitpos >> 5], (uint32_t)v);
+          if ((uint32_t)(v >> 32)) atomicOr(&out32[(bitpos >> 5) + 1], (uint32_t)(v >> 32));
+        }
+        atomicOr(&out32[(pay0 * 8) >> 5], (uint32_t)((last ? 1u : 0u) | (choice == 1 ? 2u : 4u)) << ((pay0 * 8) & 31));  // BFINAL, BTYPE = 01 / 10
+        if (!last) { out8[8 + plen - 2] = 0xff; out8[8 + plen - 1] = 0xff; }
+      }
+    } else {
+      plen = (first ? 2 : 0) + stored_bytes;
+      if (tid == 0) {
+        out8[pay0] = last ? 1 : 0;
+        out8[pay0 + 1] = (uint8_t)(n & 0xff); out8[pay0 + 2] = (uint8_t)(n >> 8);
+        out8[pay0 + 3] = (uint8_t)(~n & 0xff); out8[pay0 + 4] = (uint8_t)((~n >> 8) & 0xff);
+      }
+      for (int t = tid; t < n; t += CS_PNG_THREADS) out8[pay0 + 5 + t] = in8[t];
+    }
   }
   __syncthreads();
   if (tid == 0) {
@@ -478,6 +699,16 @@ bool png_geom(int kind, int H, int W, PngGeom* g) {
   return true;
 }
 
+template <int FLAGS>
+hipError_t png_launch_segments(const uint8_t* pixels, long long image_stride, const PngGeom& g, int I, uint8_t* staging, hipStream_t st) {
+  constexpr int lds = kLdsBytes + ((FLAGS & 1) ? (int)sizeof(DynLds) : 0);
+  // more than 64 KiB of dynamic LDS needs the attribute on the current device; set on every call (a host-side table write, no device work)
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(png_segment_kernel<FLAGS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(png_segment_kernel<FLAGS>, dim3(g.nseg, I), dim3(CS_PNG_THREADS), lds, st, pixels, image_stride, g, staging);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 extern "C" {
@@ -499,14 +730,15 @@ size_t cs_png_staging_bytes(int kind, int I, int H, int W) {
 }
 
 hipError_t cs_png_encode_launch(const void* pixels, int kind, int I, int H, int W, long long image_stride, uint8_t* out, size_t slot_bytes,
-                                uint32_t* lengths, void* workspace, hipStream_t st) {
+                                uint32_t* lengths, void* workspace, int flags, hipStream_t st) {
   PngGeom g;
-  if (!png_geom(kind, H, W, &g) || I <= 0 || I > 65535) return hipErrorInvalidValue;
-  // more than 64 KiB of dynamic LDS needs the attribute on the current device; set on every call (a host-side table write, no device work)
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(png_segment_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(png_segment_kernel, dim3(g.nseg, I), dim3(CS_PNG_THREADS), kLdsBytes, st, (const uint8_t*)pixels, image_stride, g, (uint8_t*)workspace);
-  e = hipGetLastError();
+  if (!png_geom(kind, H, W, &g) || I <= 0 || I > 65535 || flags < 0 || flags > 3) return hipErrorInvalidValue;
+  const uint8_t* px = (const uint8_t*)pixels;
+  uint8_t* stg = (uint8_t*)workspace;
+  hipError_t e = flags == 0   ? png_launch_segments<0>(px, image_stride, g, I, stg, st)
+                 : flags == 1 ? png_launch_segments<1>(px, image_stride, g, I, stg, st)
+                 : flags == 2 ? png_launch_segments<2>(px, image_stride, g, I, stg, st)
+                              : png_launch_segments<3>(px, image_stride, g, I, stg, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(png_assemble_kernel, dim3(g.nseg, I), dim3(256), 0, st, (const uint8_t*)workspace, g, out, slot_bytes, lengths);
   return hipGetLastError();

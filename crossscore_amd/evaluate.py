@@ -53,7 +53,7 @@ from .model import CrossScoreNet, load_lightning_checkpoint
 from .nvs import NvsItems, random_order
 from .pipeline import ForwardPipeline
 from .predict import seed_everything
-from .writers import BatchWriter, ScoreSummariser, png_encoder_choice
+from .writers import BatchWriter, ScoreSummariser, png_compression_choice, png_encoder_choice
 
 METRIC_KEYS = ("test/loss", "test/loss_cross", "test/corr_cross", "test/psnr_cross")
 CSV_COLUMNS = sorted(METRIC_KEYS + ("epoch", "step"))  # CSVLogger sorts its keys
@@ -182,12 +182,13 @@ def decode_eval(items, zero_ref: bool, pool, skip=(), compute_gt: bool = False):
 
 def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None,
              capture: Optional[list] = None) -> Dict[str, object]:
-    """Runs the test loop; returns {"version_dir", "out_dir", "metrics", "batches", "files", "query_images_per_sec", "input_stage", "png_encoder",
+    """Runs the test loop; returns {"version_dir", "out_dir", "metrics", "batches", "files", "query_images_per_sec", "input_stage", "png_encoder", "png_compression",
     "png_files", "gt_metric_maps", "png_decoder", "png_decoded"}.
     capture (tests, tools): a list that receives per batch {"batch_idx", "item_paths", "score", "gt", "stats"} (host copies)."""
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.evaluate needs a GPU: the scoring path has no CPU fallback")
     png_encoder = png_encoder_choice(cfg)  # this_main.png_encoder: host (default) | gpu, as in predict.py
+    png_compression = png_compression_choice(cfg)  # this_main.png_compression: fast (default) | compact, the gpu encoder's form
     compute_gt = gt_metric_maps_choice(cfg) == "compute"  # this_main.gt_metric_maps: files (default) | compute
     # this_main.png_decoder: host (default) | gpu, as in predict.py; here the window also holds the 16-bit metric maps (files) or the captured
     # images (compute)
@@ -230,7 +231,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
 
     wcfg = cfg.logger.test.write
     writer = (BatchWriter(cfg, "test", net.img_mean_std, device, workers=max(1, int(cfg.data.loader.validation.num_workers) // 2),
-                          png_encoder=png_encoder)
+                          png_encoder=png_encoder, png_compression=png_compression)
               if wcfg.flag.batch else None)
     summariser = ScoreSummariser(cfg.model.predict.metric.type, cfg.model.predict.metric.min, out_dir)
 
@@ -399,7 +400,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
         files.append(write_batches_csv(out_dir, all_rows))
     return {"version_dir": version_dir, "out_dir": out_dir, "metrics": metrics, "batches": sorted(rows, key=lambda r: r["batch_idx"]),
             "files": files, "input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
-            "png_encoder": png_encoder, "gt_metric_maps": "compute" if compute_gt else "files",
+            "png_encoder": png_encoder, "png_compression": png_compression, "gt_metric_maps": "compute" if compute_gt else "files",
             "png_decoder": png_decoder, "png_decoded": decoder.stats() if decoder is not None else {"png_decoded_gpu": 0, "png_decoded_host": 0},
             "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
             "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}

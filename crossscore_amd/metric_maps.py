@@ -29,7 +29,7 @@ from . import _lib, parallel
 from .config import load_config
 from .data import InputStage, read_image_u8
 from .nvs import DATA_SPLITS
-from .writers import PngEncoder, save_png, save_png_bytes
+from .writers import PngEncoder, png_compression_choice, save_png, save_png_bytes
 
 KINDS = (("ssim", _lib.GTMAP_SSIM), ("mae", _lib.GTMAP_MAE))
 GROUP = 8  # pairs per launch and encode: bounds the pinned and device blocks of a directory of large images
@@ -65,7 +65,7 @@ def pairs_of(it_dir: Path) -> List[Tuple[str, str, str]]:
 
 
 def generate(cfg) -> Dict[str, object]:
-    """Returns {"written": [paths], "skipped": [paths], "seconds", "png_gpu_files", "png_host_files"} of this rank."""
+    """Returns {"written": [paths], "skipped": [paths], "seconds", "png_gpu_files", "png_host_files", "png_compression"} of this rank."""
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.metric_maps needs a GPU: the maps have no CPU fallback")
     rank, local_rank, world = parallel.init_from_env()
@@ -75,7 +75,8 @@ def generate(cfg) -> Dict[str, object]:
     dirs = iteration_dirs(cfg)
     lo, hi = parallel.shard_bounds(len(dirs), world, rank)
     stage = InputStage(device, resize_short_side=-1)
-    enc = PngEncoder()
+    png_compression = png_compression_choice(cfg)  # this_main.png_compression: fast (default) | compact
+    enc = PngEncoder(png_compression)
     lib = _lib.load()
     workers = max(1, int(cfg.data.loader.validation.num_workers))
     pool = ThreadPoolExecutor(max_workers=workers)
@@ -133,7 +134,8 @@ def generate(cfg) -> Dict[str, object]:
         pool.shutdown()
     torch.cuda.synchronize(device)
     parallel.barrier()
-    return {"written": written, "skipped": skipped, "seconds": time.perf_counter() - t0, "png_gpu_files": n_gpu, "png_host_files": n_host}
+    return {"written": written, "skipped": skipped, "seconds": time.perf_counter() - t0, "png_gpu_files": n_gpu, "png_host_files": n_host,
+            "png_compression": png_compression}
 
 
 def main(argv: Optional[Iterable[str]] = None) -> int:

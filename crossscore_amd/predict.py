@@ -31,7 +31,7 @@ from .data import (DecodeWindow, InputStage, PngDecoder, ReferenceTokenCache, Si
                    load_query_batch, load_query_batch_u8, plan_decodes, png_decode_window_choice, png_decoder_choice, read_image_u8)
 from .model import CrossScoreNet, load_lightning_checkpoint
 from .pipeline import ForwardPipeline
-from .writers import BatchWriter, ScoreSummariser, png_encoder_choice
+from .writers import BatchWriter, ScoreSummariser, png_compression_choice, png_encoder_choice
 
 
 def resolve_out_dir(cfg, now: Optional[str] = None) -> str:
@@ -59,13 +59,16 @@ def seed_everything(seed: int) -> None:
 
 
 def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None) -> Dict[str, object]:
-    """Runs the predict loop; returns {"out_dir", "files", "rows", "input_stage", "png_encoder", "png_files", "png_decoder", "png_decoded",
+    """Runs the predict loop; returns {"out_dir", "files", "rows", "input_stage", "png_encoder", "png_compression", "png_files", "png_decoder", "png_decoded",
     "query_images_per_sec"}."""
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.predict needs a GPU: the scoring path has no CPU fallback")
     # this_main.png_encoder (this build's key, default "host"): who compresses the PNG outputs -- PIL on the writer's threads, or the device
     # (writers.PngEncoder: conversion, de-normalisation and compression queued behind the forward; pixel-exact, not byte-equal)
     png_encoder = png_encoder_choice(cfg)
+    # this_main.png_compression (this build's key, default "fast"): the device encoder's form -- fast (Sub filter, fixed-Huffman / stored blocks)
+    # or compact (per-row adaptive filter, dynamic-Huffman blocks); ignored with png_encoder=host
+    png_compression = png_compression_choice(cfg)
     # this_main.png_decoder (this build's key, default "host"): who decodes the PNG inputs -- PIL on the loader's threads, or the device
     # (data.PngDecoder: the compressed bytes go up, a window of this_main.png_decode_window upcoming files is decoded beside earlier forwards;
     # the same pixels, bit for bit; files the device decoder does not take still go through PIL)
@@ -100,7 +103,7 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
     net = net.to(device)
 
     writer = (BatchWriter(cfg, "predict", net.img_mean_std, device, workers=max(1, int(cfg.data.loader.validation.num_workers) // 2),
-                          png_encoder=png_encoder)
+                          png_encoder=png_encoder, png_compression=png_compression)
               if cfg.logger.predict.write.flag.batch else None)
     summariser = ScoreSummariser(cfg.model.predict.metric.type, cfg.model.predict.metric.min, cfg.logger.predict.out_dir)
 
@@ -225,7 +228,7 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
                                  f"{cfg.logger.predict.out_dir}")
     return {"out_dir": cfg.logger.predict.out_dir, "files": files, "rows": summariser.rows,
             "input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
-            "png_encoder": png_encoder, "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
+            "png_encoder": png_encoder, "png_compression": png_compression, "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
             "png_decoder": png_decoder, "png_decoded": decoder.stats() if decoder is not None else {"png_decoded_gpu": 0, "png_decoded_host": 0},
             "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}  # the whole scoring loop: input stage, forwards, output stage
 

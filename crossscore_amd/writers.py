@@ -12,7 +12,8 @@ PCIe instead of 4).  PNG compression has two forms, chosen by `this_main.png_enc
   host (default)   PIL's, on a thread pool, as in the reference (imageio); the processed query / reference images are de-normalised on the host
   gpu              cs_op_png_encode: score maps and processed images are converted (cs_op_score_to_*, cs_op_denorm_to_rgb8) and compressed on
                    the device, queued behind the forward; finished files cross PCIe into pinned memory and the pool threads only write them.
-                   Pixel-exact, valid PNGs, not byte-equal to PIL's (independent 16-KiB segments, fixed-Huffman / stored blocks: larger files).
+                   Pixel-exact, valid PNGs, not byte-equal to PIL's (independent 16-KiB segments).  `this_main.png_compression`: fast =
+                   Sub filter, fixed-Huffman / stored blocks (larger files); compact = per-row adaptive filter, dynamic-Huffman blocks.
 Attention-weight images and the item-path JSON always take the host path.  The composite matplotlib "vis" figure (task/core.py:422-434)
 is not reproduced.
 """
@@ -129,9 +130,20 @@ class PngHandle:
         return [self.bytes(i) for i in range(len(self))]
 
 
+PNG_COMPRESSIONS = {"fast": 0, "compact": _lib.PNG_DYNAMIC | _lib.PNG_ADAPTIVE_FILTER}  # cs_op_png_encode_ex flags
+
+
 class PngEncoder:
-    """Device integer images -> PNG files, compressed on the device (cs_op_png_encode).  (I, H, W) int16 / uint16 tensors become 16-bit
-    grayscale files, (I, H, W, 3) uint8 tensors 8-bit RGB files; pixel-exact, not byte-equal to PIL's."""
+    """Device integer images -> PNG files, compressed on the device (cs_op_png_encode_ex).  (I, H, W) int16 / uint16 tensors become 16-bit
+    grayscale files, (I, H, W, 3) uint8 tensors 8-bit RGB files; pixel-exact, not byte-equal to PIL's.  compression: "fast" (Sub filter,
+    fixed-Huffman / stored blocks: the bytes of cs_op_png_encode) or "compact" (per-row adaptive filter, dynamic-Huffman blocks: smaller
+    files, more device time)."""
+
+    def __init__(self, compression: str = "fast"):
+        if compression not in PNG_COMPRESSIONS:
+            raise ValueError(f"PngEncoder: compression {compression!r} not supported: fast | compact")
+        self.compression = compression
+        self.flags = PNG_COMPRESSIONS[compression]
 
     @staticmethod
     def _kind(pixels: torch.Tensor):
@@ -160,8 +172,8 @@ class PngEncoder:
         lengths = torch.empty((I,), dtype=torch.int32, device=dev)
         work = torch.empty((int(lib.cs_png_workspace_bytes(kind, I, H, W)),), dtype=torch.uint8, device=dev)
         st = torch.cuda.current_stream(dev)
-        _lib.check(lib.cs_op_png_encode(C.c_void_p(pixels.data_ptr()), kind, I, H, W, H * W * bpp, C.c_void_p(out.data_ptr()), slot,
-                                        C.c_void_p(lengths.data_ptr()), C.c_void_p(work.data_ptr()), C.c_void_p(st.cuda_stream)))
+        _lib.check(lib.cs_op_png_encode_ex(C.c_void_p(pixels.data_ptr()), kind, I, H, W, H * W * bpp, C.c_void_p(out.data_ptr()), slot,
+                                           C.c_void_p(lengths.data_ptr()), C.c_void_p(work.data_ptr()), C.c_void_p(st.cuda_stream), self.flags))
         host_out = torch.empty((I, slot), dtype=torch.uint8, pin_memory=True)
         host_len = torch.empty((I,), dtype=torch.int32, pin_memory=True)
         host_out.copy_(out, non_blocking=True)
@@ -200,6 +212,14 @@ def png_encoder_choice(cfg) -> str:
     return v
 
 
+def png_compression_choice(cfg) -> str:
+    """this_main.png_compression (this build's key): fast (default) | compact.  Takes effect with png_encoder=gpu only; ignored with host."""
+    v = cfg.this_main.get("png_compression", "fast")
+    if v not in PNG_COMPRESSIONS:
+        raise ValueError(f"this_main.png_compression={v!r} not supported: fast | compact")
+    return v
+
+
 def save_png(path, arr: np.ndarray) -> None:
     from PIL import Image
 
@@ -218,13 +238,17 @@ class BatchWriter:
     the files are complete after finish().  With png_encoder="gpu" the score maps and the processed query / reference images are converted
     and compressed on the device (PngEncoder): write_out only queues that work, the pool threads wait for its event and write the bytes."""
 
-    def __init__(self, cfg, phase: str, img_mean_std: torch.Tensor, device: torch.device, workers: int = 4, png_encoder: str = "host"):
+    def __init__(self, cfg, phase: str, img_mean_std: torch.Tensor, device: torch.device, workers: int = 4, png_encoder: str = "host",
+                 png_compression: str = "fast"):
         if phase not in ("test", "predict"):
             raise ValueError(f"Phase {phase} not supported. Has to be a Lightening phase test/predict.")
         if png_encoder not in PNG_ENCODERS:
             raise ValueError(f"png_encoder {png_encoder!r} not supported: host | gpu")
         self.png_encoder = png_encoder
-        self._png = PngEncoder() if png_encoder == "gpu" else None
+        if png_compression not in PNG_COMPRESSIONS:
+            raise ValueError(f"png_compression {png_compression!r} not supported: fast | compact")
+        self.png_compression = png_compression
+        self._png = PngEncoder(png_compression) if png_encoder == "gpu" else None
         self._stats = {"png_gpu_files": 0, "png_host_files": 0}
         self.cfg = cfg
         self.out_dir = Path(cfg.logger[phase].out_dir)

@@ -286,6 +286,18 @@ size_t cs_png_bound(int kind, int H, int W);
 size_t cs_png_workspace_bytes(int kind, int I, int H, int W);
 int cs_op_png_encode(const void* pixels, int kind, int I, int H, int W, long long image_stride_bytes, uint8_t* out, size_t slot_bytes,
                      uint32_t* lengths, void* workspace, cs_stream stream);
+/* cs_op_png_encode with opt-in compression flags; flags == 0 is cs_op_png_encode byte for byte, flags outside 0 .. 3 are CS_ERR_BAD_ARG
+ * (decided on the host before anything is launched).  The contract above holds for every flags value, with flags joining pixels, size and
+ * kind in what an image's bytes depend on.
+ * CS_PNG_ADAPTIVE_FILTER: each row takes the filter type 0 .. 4 whose filtered bytes f have the smallest sum of min(f, 256 - f) over the row
+ * (integers; ties to the lowest type; the row above row 0 and the bytes left of the first pixel are zero; Paeth ties in the order a, b, c).
+ * CS_PNG_DYNAMIC: each 16-KiB segment is priced exactly in four forms -- stored, fixed Huffman with the segment's LZ77 tokens (the flags == 0
+ * form), dynamic Huffman with those tokens, dynamic Huffman with literals only -- and the smallest is written; a later form of that list wins
+ * only when it is strictly smaller in bytes.  No segment is therefore longer than its stored form and no file longer than its flags == 0
+ * file with the same filter, so cs_png_bound and cs_png_workspace_bytes hold for every flags value as they are. */
+enum { CS_PNG_DYNAMIC = 1, CS_PNG_ADAPTIVE_FILTER = 2 };
+int cs_op_png_encode_ex(const void* pixels, int kind, int I, int H, int W, long long image_stride_bytes, uint8_t* out, size_t slot_bytes,
+                        uint32_t* lengths, void* workspace, cs_stream stream, int flags);
 /* PNG files decoded on the device (csrc/pngdec.hip): the mirror of cs_op_png_encode.  I compressed files of one
  * decoded size (H, W) and one output kind -> I images in device memory, image i at pixels + i * image_stride_bytes with contiguous rows:
  * CS_PNG_RGB8 uint8 HWC from colour type 2 / depth 8, colour type 6 / depth 8 (alpha dropped) and colour type 0 / depth 8 (the sample

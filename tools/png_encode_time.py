@@ -3,7 +3,9 @@ query images + 40 processed reference images, all RGB.  Prints
   * the HIP-event time of cs_op_png_encode alone for the three groups (and for the 8 gray16 maps of score_map_colour_mode=gray), beside the
     event time of the same batch's forward and of the conversions that feed the encoder;
   * the produced file sizes against PIL's default output (Image.fromarray(a).save) for the same arrays.
-The images are the generator of tools/predict_e2e.py (540 x 720, smooth structure + noise of sigma 8) through the real input stage."""
+The images are the generator of tools/predict_e2e.py (540 x 720, smooth structure + noise of sigma 8) through the real input stage.
+Every group is encoded in the fast (cs_op_png_encode_ex flags 0) and the compact (flags 3) form; --parent-lib <libcrossscore_hip.so of the
+parent commit> adds that library's cs_op_png_encode on the same arrays, the three forms alternating in three rounds."""
 import ctypes as C, io, json, os, sys, time
 import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
@@ -46,7 +48,12 @@ t_conv, groups = timed(lambda: {"score_map_rgb": enc_rgb.device_image(score), "i
 groups["score_map_gray16"] = enc_gray.device_image(score)
 
 lib = _lib.load()
-def raw_encode(pixels):
+parent = None
+if "--parent-lib" in sys.argv:
+    parent = C.CDLL(sys.argv[sys.argv.index("--parent-lib") + 1])
+    for name in ("cs_png_bound", "cs_png_workspace_bytes", "cs_op_png_encode"):
+        getattr(parent, name).restype, getattr(parent, name).argtypes = _lib.SYMBOLS[name]
+def raw_encode(pixels, flags=0, use=None):
     kind, bpp = (_lib.PNG_GRAY16, 2) if pixels.dtype == torch.int16 else (_lib.PNG_RGB8, 3)
     I, H, W = (int(v) for v in pixels.shape[:3])
     slot = lib.cs_png_bound(kind, H, W)
@@ -54,29 +61,40 @@ def raw_encode(pixels):
     ws = torch.empty((lib.cs_png_workspace_bytes(kind, I, H, W),), dtype=torch.uint8, device=dev)
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     def go():
-        _lib.check(lib.cs_op_png_encode(C.c_void_p(pixels.data_ptr()), kind, I, H, W, H * W * bpp, C.c_void_p(o.data_ptr()), slot, C.c_void_p(ln.data_ptr()),
-                                        C.c_void_p(ws.data_ptr()), st))
+        args = (C.c_void_p(pixels.data_ptr()), kind, I, H, W, H * W * bpp, C.c_void_p(o.data_ptr()), slot, C.c_void_p(ln.data_ptr()), C.c_void_p(ws.data_ptr()), st)
+        rc = use.cs_op_png_encode(*args) if use is not None else lib.cs_op_png_encode_ex(*args, flags)
+        assert rc == 0, rc
         return ln
     return go
 
 res = {"forward_ms": round(t_fwd, 3), "convert_ms": round(t_conv, 3), "score_std": round(float(score.std()), 4)}
-total = 0.0
+FORMS = [("fast", 0, None), ("compact", 3, None)] + ([("parent", 0, parent)] if parent is not None else [])
+total = {f: [0.0, 0.0, 0.0] for f, _, _ in FORMS}
 for name, px in groups.items():
-    t, ln = timed(raw_encode(px))
-    ours = ln.cpu().numpy().astype(np.int64)
     arr = px.cpu().numpy(); arr = arr.view(np.uint16) if arr.dtype == np.int16 else arr
     pil, t0 = [], time.perf_counter()
     for a in arr:
         buf = io.BytesIO(); Image.fromarray(a).save(buf, format="PNG"); pil.append(buf.tell())
     t_pil = (time.perf_counter() - t0) / len(arr)
     raw = int(np.prod(arr.shape[1:])) * arr.dtype.itemsize
-    if name != "score_map_gray16": total += t
-    print(json.dumps({"group": name, "images": len(arr), "encode_ms": round(t, 3), "encode_us_per_image": round(1e3 * t / len(arr), 1),
-                      "bytes_ours_mean": int(ours.mean()), "bytes_pil_mean": int(np.mean(pil)), "ratio_to_pil": round(float(ours.sum() / np.sum(pil)), 3),
-                      "ratio_to_raw": round(float(ours.mean() / raw), 3), "pil_host_ms_per_image": round(1e3 * t_pil, 1)}), flush=True)
+    row = {"group": name, "images": len(arr), "bytes_pil_mean": int(np.mean(pil)), "pil_host_ms_per_image": round(1e3 * t_pil, 1)}
+    times = {f: [] for f, _, _ in FORMS}
+    for rnd in range(3):  # the forms alternate: a drift of the box shows as spread inside every form, not as a difference between them
+        for form, flags, use in FORMS:
+            t, ln = timed(raw_encode(px, flags, use))
+            times[form].append(round(t, 3))
+            if name != "score_map_gray16": total[form][rnd] += t
+            if rnd == 0:
+                ours = ln.cpu().numpy().astype(np.int64)
+                row.update({f"bytes_{form}_mean": int(ours.mean()), f"{form}_ratio_to_pil": round(float(ours.sum() / np.sum(pil)), 3),
+                            f"{form}_ratio_to_raw": round(float(ours.mean() / raw), 3)})
+    row.update({f"encode_ms_{form}": times[form] for form in times})
+    print(json.dumps(row), flush=True)
 # the asynchronous form end to end (encode + copy of the slots to pinned memory), as the writer queues it
-pe = PngEncoder()
-t_async, _ = timed(lambda: [pe.encode_async(groups[k]) for k in ("score_map_rgb", "image_query", "image_reference")], k=5)
-res.update({"encode_ms_default_outputs": round(total, 3), "encode_plus_copy_ms_default_outputs": round(t_async, 3),
-            "encode_over_forward": round(total / t_fwd, 2)})
+for form in ("fast", "compact"):
+    pe = PngEncoder(form)
+    t_async, _ = timed(lambda: [pe.encode_async(groups[k]) for k in ("score_map_rgb", "image_query", "image_reference")], k=5)
+    res[f"encode_plus_copy_ms_default_outputs_{form}"] = round(t_async, 3)
+res.update({f"encode_ms_default_outputs_{form}": [round(v, 3) for v in total[form]] for form in total})
+res["compact_encode_over_forward"] = round(min(total["compact"]) / t_fwd, 2)
 print(json.dumps(res), flush=True)

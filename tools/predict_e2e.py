@@ -1,7 +1,8 @@
 """End-to-end predict driver on a synthetic image directory: 32 query PNGs + 20 reference PNGs at 540x720, ViT-S, 5 references per
 query, batch 8 -- wall time per stage with the reference-token cache on / off, with / without PNG outputs, and (for the legs that write PNGs)
 with the host and the gpu PNG encoder (this_main.png_encoder), alternating inside the one run.  --png-decoder-legs runs the input side instead:
-write_png false and maps, token cache on / off, both input stages, this_main.png_decoder host and gpu alternating inside the one run."""
+write_png false and maps, token cache on / off, both input stages, this_main.png_decoder host and gpu alternating inside the one run.
+--png-compression-legs: write_png all with png_encoder gpu, this_main.png_compression fast and compact alternating, beside the host leg."""
 import json, os, sys, tempfile, time
 import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
@@ -27,15 +28,19 @@ LEGS = [("all", "auto", "host", "host"), ("all", "auto", "gpu", "host"), ("maps"
         ("maps", "auto", "gpu", "host"), (False, False, "host", "host"), (False, "auto", "host", "host")]
 if "--png-decoder-legs" in sys.argv:
     LEGS = [(write, fused, "host", dec) for write in (False, "maps") for fused in ("auto", False) for dec in ("host", "gpu")]
+LEGS = [leg + ("fast",) for leg in LEGS]
+if "--png-compression-legs" in sys.argv:
+    LEGS = [("all", "auto", "host", "host", "fast"), ("all", "auto", "gpu", "host", "fast"), ("all", "auto", "gpu", "host", "compact")]
 for rnd in range(2):  # (the first round pays table builds, stream probes and page-ins)
     for cache in (True, False):
-        for write, fused, enc, dec in LEGS:
+        for write, fused, enc, dec, comp in LEGS:
             over = [f"data.dataset.query_dir={qd}", f"data.dataset.reference_dir={rd}", f"this_main.cache_reference_tokens={cache}",
-                    f"logger.predict.out_dir={root}/out_{rnd}_{cache}_{write}_{fused}_{enc}_{dec}", f"this_main.png_decoder={dec}", f"logger.predict.write.flag.batch={bool(write)}",
+                    f"logger.predict.out_dir={root}/out_{rnd}_{cache}_{write}_{fused}_{enc}_{dec}_{comp}", f"this_main.png_compression={comp}", f"this_main.png_decoder={dec}", f"logger.predict.write.flag.batch={bool(write)}",
                     f"this_main.fused_input_stage={fused}", f"this_main.png_encoder={enc}"]
             if write == "maps":
                 over += ["logger.predict.write.flag.image_query=False", "logger.predict.write.flag.image_reference=False"]
             t0 = time.perf_counter(); res = predict(load_config("default_predict", over), state_dict=sd, now="T"); dt = time.perf_counter() - t0
-            print(json.dumps({"round": rnd, "cache_reference_tokens": cache, "write_png": write, "png_encoder": enc, "png_decoder": dec, "input_stage": res["input_stage"].split(" ")[0],
+            print(json.dumps({"round": rnd, "cache_reference_tokens": cache, "write_png": write, "png_encoder": enc, "png_compression": comp, "png_decoder": dec, "input_stage": res["input_stage"].split(" ")[0],
                               "wall_s": round(dt, 2), "query_images_per_sec_wall": round(32 / dt, 1),
-                              "query_images_per_sec_loop": round(res["query_images_per_sec"], 1), "files": len(res["files"])}), flush=True)
+                              "query_images_per_sec_loop": round(res["query_images_per_sec"], 1), "files": len(res["files"]),
+                              "out_bytes": sum(os.path.getsize(os.path.join(d, f)) for d, _, fs in os.walk(res["out_dir"]) for f in fs)}), flush=True)
