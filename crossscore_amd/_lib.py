@@ -17,6 +17,10 @@ PNG_DYNAMIC, PNG_ADAPTIVE_FILTER = 1, 2  # cs_op_png_encode_ex flags (CS_PNG_*)
 (PNGDEC_OK, PNGDEC_BAD_CRC, PNGDEC_BAD_ADLER, PNGDEC_BAD_ZLIB_HEADER, PNGDEC_BAD_BLOCK_TYPE, PNGDEC_BAD_STORED_LEN, PNGDEC_BAD_CODE, PNGDEC_BAD_SYMBOL,
  PNGDEC_BAD_DISTANCE, PNGDEC_STREAM_SHORT, PNGDEC_STREAM_LONG, PNGDEC_BAD_FILTER, PNGDEC_INPUT_EXHAUSTED, PNGDEC_HEADER_MISMATCH,
  PNGDEC_BAD_FRAMING) = range(15)
+JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = range(4)  # cs_jpeg_info.sampling (CS_JPEG_*)
+# status words of cs_op_jpeg_decode (CS_JPGDEC_*)
+(JPGDEC_OK, JPGDEC_BAD_FRAMING, JPGDEC_HEADER_MISMATCH, JPGDEC_BAD_TABLE, JPGDEC_BAD_CODE, JPGDEC_BAD_SYMBOL, JPGDEC_INPUT_EXHAUSTED,
+ JPGDEC_BAD_RESTART) = range(8)
 GTMAP_SSIM, GTMAP_MAE = 0, 1  # cs_op_gt_metric_map_u8 kinds (CS_GTMAP_*)
 
 # CsEpilogue (csrc/cs_common.h)
@@ -45,6 +49,12 @@ class CsPngInfo(C.Structure):
     """cs_png_info: what cs_png_probe reads from a file's framing and IHDR."""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("color_type", C.c_int), ("bit_depth", C.c_int), ("interlace", C.c_int), ("kind", C.c_int),
                 ("num_idat", C.c_int), ("idat_bytes", C.c_ulonglong)]
+
+
+class CsJpegInfo(C.Structure):
+    """cs_jpeg_info: what cs_jpeg_probe reads from a file's marker segments."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("components", C.c_int), ("sampling", C.c_int), ("restart_interval", C.c_int),
+                ("entropy_offset", C.c_ulonglong)]
 
 
 # every symbol include/crossscore_hip.h declares: name -> (restype, argtypes)
@@ -104,6 +114,9 @@ SYMBOLS = {
     "cs_png_probe": (_i, [_vp, _sz, _vp, _vp, _i]),
     "cs_png_decode_workspace_bytes": (_sz, [_i, _i, _i, _i, _sz]),
     "cs_op_png_decode": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _vp, _ll, _vp, _vp, _vp]),
+    "cs_jpeg_probe": (_i, [_vp, _sz, _vp]),
+    "cs_jpeg_decode_workspace_bytes": (_sz, [_i, _i, _i, _sz]),
+    "cs_op_jpeg_decode": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp, _ll, _vp, _vp, _vp]),
     "cs_op_denorm_to_rgb8": (_i, [_vp, _i, _i, _i, _fp, _fp, _vp, _vp]),
     "cs_op_metric_map_u16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "cs_op_gt_metric_map_u8": (_i, [_vp, _vp, _i, _i, _i, _ll, _i, _vp, _i, _vp]),

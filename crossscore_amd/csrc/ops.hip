@@ -1,6 +1,7 @@
 // Single-op entry points of the C ABI (cs_op_*): each kernel of the forward on its own, for the op-level tests and the measurement tools, and
 // the PNG, ground-truth-map and score helpers the predict / evaluate drivers call.  Host-side only: argument checks, then one launch.
 #include "cs_model.h"
+#include "jpeg_probe.h"
 
 #include <cmath>
 #include <cstring>
@@ -398,6 +399,37 @@ int cs_op_png_decode(const uint8_t* files, const uint64_t* file_offsets, const u
   static_assert(sizeof(cs_png_span) == 8, "span layout");
   HIPCHK(cs_pngdec_launch(files, (const unsigned long long*)file_offsets, file_lengths, (const uint32_t*)spans, span_offsets, total_file_bytes, I, kind, H, W,
                           pixels, image_stride_bytes, status, workspace, (hipStream_t)stream));
+  return 0;
+}
+
+// ---- JPEG decoder (jpegdec.hip): the host probe (jpeg_probe.h), the workspace size and the launches
+int cs_jpeg_probe(const uint8_t* file, size_t n, cs_jpeg_info* info) {
+  if (!file || !info) return fail(CS_ERR_BAD_ARG, "jpeg_probe: null pointer");
+  cs_jpeg_probe_result r;
+  char why[256];
+  const int rc = cs_jpeg_probe_walk(file, n, &r, why, sizeof why);
+  info->width = r.width; info->height = r.height; info->components = r.components; info->sampling = r.sampling;
+  info->restart_interval = r.restart_interval; info->entropy_offset = r.entropy_offset;
+  if (rc != CS_JPEG_PROBE_OK) return fail(rc == CS_JPEG_PROBE_BAD_ARG ? CS_ERR_BAD_ARG : CS_ERR_UNSUPPORTED, "%s", why);
+  return 0;
+}
+
+size_t cs_jpeg_decode_workspace_bytes(int I, int H, int W, size_t total_file_bytes) {
+  if (H <= 0 || W <= 0 || I <= 0 || I > 65535 || total_file_bytes == 0 || !cs_png_size_supported(H, W)) return 0;
+  return cs_jpgdec_workspace(I, H, W);
+}
+
+int cs_op_jpeg_decode(const uint8_t* files, const uint64_t* file_offsets, const uint32_t* file_lengths, size_t total_file_bytes, int I, int H,
+                      int W, void* pixels, long long image_stride_bytes, uint32_t* status, void* workspace, cs_stream stream) {
+  if (I <= 0 || I > 65535 || H <= 0 || W <= 0) return fail(CS_ERR_BAD_ARG, "jpeg_decode: bad sizes (I %d, H %d, W %d; 1 <= I <= 65535)", I, H, W);
+  if (H > 4096 || W > 4096) return fail(CS_ERR_UNSUPPORTED, "jpeg_decode: %d x %d is larger than 4096 x 4096", H, W);
+  const long long image_bytes = (long long)H * W * 3;
+  if (image_stride_bytes < image_bytes) return fail(CS_ERR_BAD_ARG, "jpeg_decode: image stride %lld is below the image's %lld bytes", image_stride_bytes, image_bytes);
+  if (total_file_bytes == 0 || total_file_bytes >= ((size_t)1 << 40)) return fail(CS_ERR_BAD_ARG, "jpeg_decode: %zu file bytes (1 .. 2^40 - 1)", total_file_bytes);
+  if (!files || !file_offsets || !file_lengths || !pixels || !status || !workspace) return fail(CS_ERR_BAD_ARG, "jpeg_decode: null pointer");
+  if ((uintptr_t)workspace & 15) return fail(CS_ERR_BAD_ARG, "jpeg_decode: the workspace must be 16-byte aligned");
+  HIPCHK(cs_jpgdec_launch(files, (const unsigned long long*)file_offsets, file_lengths, total_file_bytes, I, H, W, pixels, image_stride_bytes, status,
+                          workspace, (hipStream_t)stream));
   return 0;
 }
 

@@ -6,7 +6,9 @@ Mirrors, for the predict path only:
   load_content / resize_all / crops / T.Normalize   nvs_dataset.py:218-279,429-470, task/predict.py:68-93
 The pixel work (x/255, antialiased resize, crop, normalise) runs on the GPU through cs_op_preprocess_u8 straight from the decoded
 uint8 image; PNG/JPEG decoding stays on the host (PIL, as in utils/io/images.py:26-29) unless this_main.png_decoder=gpu hands the PNG files
-to PngDecoder (cs_op_png_decode: the compressed bytes go up and the decoded images appear in device memory).
+and / or this_main.jpeg_decoder=gpu the baseline JPEG files to PngDecoder (cs_op_png_decode, cs_op_jpeg_decode: the compressed bytes go up and
+the decoded images appear in device memory, the pixels PIL gives, bit for bit).  Files neither device decoder takes (interlaced or palette PNG,
+progressive / CMYK / Adobe JPEG, ...) still go through PIL.
 """
 from __future__ import annotations
 
@@ -105,6 +107,18 @@ def png_decoder_choice(cfg) -> str:
     return v
 
 
+JPGDEC_STATUS = ("ok", "bad framing (SOI, a segment length past the file, no SOF / SOS)", "SOF differs from the size asked for, or a form the decoder does not take",
+                 "bad Huffman or quantisation table", "bits that are no code of the table", "invalid symbol", "input exhausted", "missing, misnumbered or surplus restart marker")
+
+
+def jpeg_decoder_choice(cfg) -> str:
+    """this_main.jpeg_decoder (this build's key): host (default) | gpu."""
+    v = cfg.this_main.get("jpeg_decoder", "host")
+    if v not in PNG_DECODERS:
+        raise ValueError(f"this_main.jpeg_decoder={v!r} not supported: host | gpu")
+    return v
+
+
 def png_decode_window_choice(cfg) -> int:
     """this_main.png_decode_window (this build's key): files handed to the device decoder at once, default 64."""
     v = cfg.this_main.get("png_decode_window", 64)
@@ -133,6 +147,16 @@ def probe_png(data: bytes):
     return info, spans
 
 
+def probe_jpeg(data: bytes):
+    """cs_jpeg_probe on a file's bytes: (info, None) when the device decoder takes the file, else (None, reason)."""
+    lib = _lib.load()
+    info = _lib.CsJpegInfo()
+    rc = lib.cs_jpeg_probe(bytes(data), len(data), C.byref(info))
+    if rc != _lib.CS_OK:
+        return None, _lib.last_error()
+    return info, None
+
+
 class PngDecodeHandle:
     """One PngDecoder.decode request: `tensors[i]` is the device image of `paths[i]`; `event` is recorded behind the last launch (and behind the
     copy of the status words to pinned memory).  wait(stream) orders a consumer stream behind the decode without waiting on the host;
@@ -154,14 +178,15 @@ class PngDecodeHandle:
             return
         if self.event is not None:
             self.event.synchronize()
-        for paths, status in self._groups:
+        for paths, status, fmt in self._groups:
             st = status.numpy()
             bad = np.nonzero(st)[0]
             if bad.size:
                 i = int(bad[0])
                 code = int(st[i])
-                what = PNGDEC_STATUS[code] if code < len(PNGDEC_STATUS) else "unknown"
-                raise ValueError(f"{paths[i]}: the device PNG decoder rejected the file with status {code} ({what})")
+                table = JPGDEC_STATUS if fmt == "JPEG" else PNGDEC_STATUS
+                what = table[code] if code < len(table) else "unknown"
+                raise ValueError(f"{paths[i]}: the device {fmt} decoder rejected the file with status {code} ({what})")
         self._checked = True
 
 
@@ -172,14 +197,22 @@ class PngDecoder:
     group from pinned memory with non-blocking copies and queues one decode launch per group on the decoder's own stream; nothing waits for the
     device.  Per path the handle holds a (H, W, 3) uint8 tensor (read_image_u8's array) or, with gray16=True, a (H, W) int16 tensor holding
     uint16 samples (the convention of InputStage.metric_maps).  A file the probe does not take (interlaced, palette, JPEG, ...) is decoded by
-    PIL exactly as without the decoder and uploaded.  The status words travel to pinned memory behind the same event; handle.check() reads them."""
+    PIL exactly as without the decoder and uploaded.  The status words travel to pinned memory behind the same event; handle.check() reads them.
 
-    def __init__(self, device, pool=None):
+    jpeg=True (this_main.jpeg_decoder=gpu) adds baseline JPEG: a file that begins FF D8 (sniffed by content, as PIL does, not by its name) and
+    passes cs_jpeg_probe is grouped by (H, W) -- sampling is per file -- and decoded by cs_op_jpeg_decode through the same pinned block, event and
+    status copy; a refused JPEG (progressive, CMYK, Adobe, ...) and any JPEG asked for as gray16 go through PIL as before.  Such files count in
+    jpeg_stats() and not in stats().  png=False leaves the PNG files on the host path inside the decoder."""
+
+    def __init__(self, device, pool=None, png=True, jpeg=False):
         self.device = torch.device(device)
         self.pool = pool
+        self.png, self.jpeg = bool(png), bool(jpeg)
         self.stream = torch.cuda.Stream(self.device)
         self.files_gpu = 0
         self.files_host = 0
+        self.jpeg_gpu = 0
+        self.jpeg_host = 0
 
     def _map(self, fn, xs):
         return list(self.pool.map(fn, xs)) if self.pool is not None else [fn(x) for x in xs]
@@ -191,8 +224,15 @@ class PngDecoder:
         if len(kinds) != len(paths):
             raise ValueError("PngDecoder.decode: one gray16 flag per path")
 
+        JPEG = -1  # the group kind of cs_op_jpeg_decode, beside _lib.PNG_GRAY16 / PNG_RGB8
+        jpeg_mark = object()  # in the place of a PNG's span table
+
         def load(p):
             data = read_file_bytes(p)
+            if self.jpeg and data[:2] == b"\xff\xd8":
+                return data, probe_jpeg(data)[0], jpeg_mark
+            if not self.png:
+                return data, None, None
             info, spans = probe_png(data)
             return data, info, spans
 
@@ -200,9 +240,15 @@ class PngDecoder:
         tensors: List[Optional[torch.Tensor]] = [None] * len(paths)
         groups: Dict[Tuple[int, int, int], List[int]] = {}
         host_idx = []
+        is_jpeg = [spans is jpeg_mark for _, _, spans in loaded]
         for i, (data, info, spans) in enumerate(loaded):
             want = _lib.PNG_GRAY16 if kinds[i] else _lib.PNG_RGB8
-            if info is None or info.kind != want:
+            if is_jpeg[i]:
+                if info is None or kinds[i]:
+                    host_idx.append(i)  # a JPEG the device decoder does not take, or one asked for as a 16-bit map: PIL
+                else:
+                    groups.setdefault((info.height, info.width, JPEG), []).append(i)
+            elif info is None or info.kind != want:
                 host_idx.append(i)  # not built on the device (or not the kind asked for): PIL, which also raises what it raised before
             else:
                 groups.setdefault((info.height, info.width, info.kind), []).append(i)
@@ -220,6 +266,29 @@ class PngDecoder:
                 offsets = np.zeros((n,), dtype=np.uint64)
                 offsets[1:] = np.cumsum(lengths.astype(np.uint64))[:-1]
                 total = int(lengths.astype(np.uint64).sum())
+                if kind == JPEG:
+                    # one pinned block: file bytes | offsets (u64) | lengths, each part 8-byte aligned
+                    at_off = (total + 7) // 8 * 8
+                    at_len = at_off + n * 8
+                    block = torch.empty((at_len + (n * 4 + 7) // 8 * 8,), dtype=torch.uint8, pin_memory=True)
+                    bv = block.numpy()
+                    for j, i in enumerate(idx):
+                        bv[int(offsets[j]):int(offsets[j]) + int(lengths[j])] = np.frombuffer(loaded[i][0], dtype=np.uint8)
+                    bv[at_off:at_off + n * 8] = offsets.view(np.uint8)
+                    bv[at_len:at_len + n * 4] = lengths.view(np.uint8)
+                    d_block = block.to(self.device, non_blocking=True)
+                    base = d_block.data_ptr()
+                    out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device)
+                    status = torch.empty((n,), dtype=torch.int32, device=self.device)
+                    work = torch.empty((lib.cs_jpeg_decode_workspace_bytes(n, h, w, total),), dtype=torch.uint8, device=self.device)
+                    _lib.check(lib.cs_op_jpeg_decode(C.c_void_p(base), C.c_void_p(base + at_off), C.c_void_p(base + at_len), total, n, h, w,
+                                                     C.c_void_p(out.data_ptr()), h * w * 3, C.c_void_p(status.data_ptr()), C.c_void_p(work.data_ptr()), st))
+                    host_status = torch.empty((n,), dtype=torch.int32, pin_memory=True)
+                    host_status.copy_(status, non_blocking=True)
+                    for j, i in enumerate(idx):
+                        tensors[i] = out[j]
+                    done.append(([paths[i] for i in idx], host_status, "JPEG"))
+                    continue
                 nspans = np.array([len(loaded[i][2]) for i in idx], dtype=np.uint32)
                 span_off = np.zeros((n + 1,), dtype=np.uint32)
                 span_off[1:] = np.cumsum(nspans)
@@ -251,15 +320,23 @@ class PngDecoder:
                 host_status.copy_(status, non_blocking=True)
                 for j, i in enumerate(idx):
                     tensors[i] = out[j]
-                done.append(([paths[i] for i in idx], host_status))
+                done.append(([paths[i] for i in idx], host_status, "PNG"))
             event = torch.cuda.Event()
             event.record(self.stream)
-        self.files_gpu += sum(len(g) for g in groups.values())
-        self.files_host += len(host_idx)
+        jpeg_gpu = sum(len(g) for (_, _, kind), g in groups.items() if kind == JPEG)
+        jpeg_host = sum(1 for i in host_idx if is_jpeg[i])
+        self.jpeg_gpu += jpeg_gpu
+        self.jpeg_host += jpeg_host
+        self.files_gpu += sum(len(g) for g in groups.values()) - jpeg_gpu
+        self.files_host += len(host_idx) - jpeg_host
         return PngDecodeHandle(paths, tensors, event, done, [paths[i] for i in host_idx])
 
     def stats(self) -> Dict[str, int]:
         return {"png_decoded_gpu": self.files_gpu, "png_decoded_host": self.files_host}
+
+    def jpeg_stats(self) -> Dict[str, int]:
+        """Files that begin FF D8, counted only with jpeg=True (without it a JPEG is one more file of stats()' host count)."""
+        return {"jpeg_decoded_gpu": self.jpeg_gpu, "jpeg_decoded_host": self.jpeg_host}
 
 
 def plan_decodes(batches, zero_reference: bool, once_per_reference: bool, extra=None) -> List[List[Tuple[str, bool]]]:
@@ -283,7 +360,7 @@ def plan_decodes(batches, zero_reference: bool, once_per_reference: bool, extra=
 
 
 class DecodeWindow:
-    """The drivers' loader with this_main.png_decoder=gpu: the files of all batches are known up front, so the decoder is handed a window of
+    """The drivers' loader with this_main.png_decoder=gpu or this_main.jpeg_decoder=gpu: the files of all batches are known up front, so the decoder is handed a window of
     upcoming files (this_main.png_decode_window, independent of the batch size) and a file's decode latency hides behind earlier forwards.
 
     plan: per batch the ordered (path, gray16) list of what that batch reads.  fetch(b) returns {path: device tensor} for batch b with the

@@ -48,7 +48,7 @@ import torch
 from . import _lib, parallel, synth
 from .config import load_config
 from .data import (EMPTY, DecodeWindow, InputStage, PngDecoder, ReferenceTokenCache, decode_items, load_batch, load_batch_u8, load_query_batch,
-                   load_query_batch_u8, metric_mode, plan_decodes, png_decode_window_choice, png_decoder_choice, read_image_u8, read_metric_map_u16)
+                   load_query_batch_u8, jpeg_decoder_choice, metric_mode, plan_decodes, png_decode_window_choice, png_decoder_choice, read_image_u8, read_metric_map_u16)
 from .model import CrossScoreNet, load_lightning_checkpoint
 from .nvs import NvsItems, random_order
 from .pipeline import ForwardPipeline
@@ -183,7 +183,7 @@ def decode_eval(items, zero_ref: bool, pool, skip=(), compute_gt: bool = False):
 def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None,
              capture: Optional[list] = None) -> Dict[str, object]:
     """Runs the test loop; returns {"version_dir", "out_dir", "metrics", "batches", "files", "query_images_per_sec", "input_stage", "png_encoder", "png_compression",
-    "png_files", "gt_metric_maps", "png_decoder", "png_decoded"}.
+    "png_files", "gt_metric_maps", "png_decoder", "png_decoded", "jpeg_decoder", "jpeg_decoded"}.
     capture (tests, tools): a list that receives per batch {"batch_idx", "item_paths", "score", "gt", "stats"} (host copies)."""
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.evaluate needs a GPU: the scoring path has no CPU fallback")
@@ -193,6 +193,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     # this_main.png_decoder: host (default) | gpu, as in predict.py; here the window also holds the 16-bit metric maps (files) or the captured
     # images (compute)
     png_decoder, decode_window = png_decoder_choice(cfg), png_decode_window_choice(cfg)
+    jpeg_decoder = jpeg_decoder_choice(cfg)  # this_main.jpeg_decoder: host (default) | gpu, baseline JPEG inputs through the same window
     seed_everything(int(cfg.lightning.seed))
     rank, local_rank, world = parallel.init_from_env()
     device = torch.device("cuda", local_rank if world > 1 else 0)
@@ -260,7 +261,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     cache = ReferenceTokenCache(pipe, stage, keep_images=bool(writer is not None and wcfg.flag.image_reference),
                                 max_images=int(cfg.this_main.get("reference_cache_max_images", 4096)), from_u8=fused_in) if use_cache else None
     cached_paths = lambda: {k[0] for k in cache.tokens} if cache is not None else ()  # noqa: E731
-    decoder = PngDecoder(device, pool) if png_decoder == "gpu" else None
+    decoder = PngDecoder(device, pool, png=png_decoder == "gpu", jpeg=jpeg_decoder == "gpu") if "gpu" in (png_decoder, jpeg_decoder) else None
 
     def gt_files(it):
         if compute_gt:
@@ -401,7 +402,8 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     return {"version_dir": version_dir, "out_dir": out_dir, "metrics": metrics, "batches": sorted(rows, key=lambda r: r["batch_idx"]),
             "files": files, "input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
             "png_encoder": png_encoder, "png_compression": png_compression, "gt_metric_maps": "compute" if compute_gt else "files",
-            "png_decoder": png_decoder, "png_decoded": decoder.stats() if decoder is not None else {"png_decoded_gpu": 0, "png_decoded_host": 0},
+            "png_decoder": png_decoder, "png_decoded": decoder.stats() if png_decoder == "gpu" else {"png_decoded_gpu": 0, "png_decoded_host": 0},
+            "jpeg_decoder": jpeg_decoder, "jpeg_decoded": decoder.jpeg_stats() if jpeg_decoder == "gpu" else {"jpeg_decoded_gpu": 0, "jpeg_decoded_host": 0},
             "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
             "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}
 
@@ -415,7 +417,7 @@ def main(argv: Optional[Iterable[str]] = None) -> int:
         res = evaluate(cfg)
     m = res["metrics"]
     print(f"[crossscore_amd.evaluate] {sum(r['batch_size'] for r in res['batches'])} query images: test/loss {m['test/loss']:.6f} "
-          f"test/corr_cross {m['test/corr_cross']:.6f} test/psnr_cross {m['test/psnr_cross']:.4f} (png_decoder {res['png_decoder']}); metrics under {res['version_dir']}, outputs "
+          f"test/corr_cross {m['test/corr_cross']:.6f} test/psnr_cross {m['test/psnr_cross']:.4f} (png_decoder {res['png_decoder']}, jpeg_decoder {res['jpeg_decoder']}); metrics under {res['version_dir']}, outputs "
           f"under {res['out_dir']}")
     return 0
 

@@ -28,7 +28,7 @@ import torch
 from . import parallel, synth
 from .config import load_config
 from .data import (DecodeWindow, InputStage, PngDecoder, ReferenceTokenCache, SimpleReferenceItems, decode_items, load_batch, load_batch_u8,
-                   load_query_batch, load_query_batch_u8, plan_decodes, png_decode_window_choice, png_decoder_choice, read_image_u8)
+                   jpeg_decoder_choice, load_query_batch, load_query_batch_u8, plan_decodes, png_decode_window_choice, png_decoder_choice, read_image_u8)
 from .model import CrossScoreNet, load_lightning_checkpoint
 from .pipeline import ForwardPipeline
 from .writers import BatchWriter, ScoreSummariser, png_compression_choice, png_encoder_choice
@@ -60,7 +60,7 @@ def seed_everything(seed: int) -> None:
 
 def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None) -> Dict[str, object]:
     """Runs the predict loop; returns {"out_dir", "files", "rows", "input_stage", "png_encoder", "png_compression", "png_files", "png_decoder", "png_decoded",
-    "query_images_per_sec"}."""
+    "jpeg_decoder", "jpeg_decoded", "query_images_per_sec"}."""
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.predict needs a GPU: the scoring path has no CPU fallback")
     # this_main.png_encoder (this build's key, default "host"): who compresses the PNG outputs -- PIL on the writer's threads, or the device
@@ -73,6 +73,9 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
     # (data.PngDecoder: the compressed bytes go up, a window of this_main.png_decode_window upcoming files is decoded beside earlier forwards;
     # the same pixels, bit for bit; files the device decoder does not take still go through PIL)
     png_decoder, decode_window = png_decoder_choice(cfg), png_decode_window_choice(cfg)
+    # this_main.jpeg_decoder (this build's key, default "host"): the same choice for baseline JPEG inputs (cs_op_jpeg_decode); either key set to gpu
+    # builds the decoder and its window, and each format goes to the device only under its own key
+    jpeg_decoder = jpeg_decoder_choice(cfg)
     seed_everything(int(cfg.lightning.seed))
     rank, local_rank, world = parallel.init_from_env()
     device = torch.device("cuda", local_rank if world > 1 else 0)
@@ -142,7 +145,7 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
     cache = ReferenceTokenCache(pipe, stage, keep_images=bool(writer is not None and cfg.logger.predict.write.flag.image_reference),
                                 max_images=int(cfg.this_main.get("reference_cache_max_images", 4096)), from_u8=fused_in) if use_cache else None
     cached_paths = lambda: {k[0] for k in cache.tokens} if cache is not None else ()  # noqa: E731
-    decoder = PngDecoder(device, pool) if png_decoder == "gpu" else None
+    decoder = PngDecoder(device, pool, png=png_decoder == "gpu", jpeg=jpeg_decoder == "gpu") if "gpu" in (png_decoder, jpeg_decoder) else None
     window = DecodeWindow(decoder, plan_decodes(batches, zero_ref, cache is not None), decode_window) if decoder is not None else None
 
     def submit_decode(i):
@@ -229,7 +232,8 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
     return {"out_dir": cfg.logger.predict.out_dir, "files": files, "rows": summariser.rows,
             "input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
             "png_encoder": png_encoder, "png_compression": png_compression, "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
-            "png_decoder": png_decoder, "png_decoded": decoder.stats() if decoder is not None else {"png_decoded_gpu": 0, "png_decoded_host": 0},
+            "png_decoder": png_decoder, "png_decoded": decoder.stats() if png_decoder == "gpu" else {"png_decoded_gpu": 0, "png_decoded_host": 0},
+            "jpeg_decoder": jpeg_decoder, "jpeg_decoded": decoder.jpeg_stats() if jpeg_decoder == "gpu" else {"jpeg_decoded_gpu": 0, "jpeg_decoded_host": 0},
             "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}  # the whole scoring loop: input stage, forwards, output stage
 
 
@@ -245,7 +249,7 @@ def main(argv: Optional[Iterable[str]] = None) -> int:
     with torch.no_grad():
         res = predict(cfg)
     print(f"[crossscore_amd.predict] {len(res['rows'])} query images, {res['query_images_per_sec']:.1f} query-images/s through the scoring loop "
-          f"(png_decoder {res['png_decoder']}), outputs under {res['out_dir']}")
+          f"(png_decoder {res['png_decoder']}, jpeg_decoder {res['jpeg_decoder']}: {res['jpeg_decoded']['jpeg_decoded_gpu']} files on the device), outputs under {res['out_dir']}")
     return 0
 
 

@@ -343,6 +343,45 @@ size_t cs_png_decode_workspace_bytes(int kind, int I, int H, int W, size_t total
 int cs_op_png_decode(const uint8_t* files, const uint64_t* file_offsets, const uint32_t* file_lengths, const cs_png_span* spans,
                      const uint32_t* span_offsets, size_t total_file_bytes, int I, int kind, int H, int W, void* pixels, long long image_stride_bytes,
                      uint32_t* status, void* workspace, cs_stream stream);
+/* Baseline JPEG files decoded on the device (csrc/jpegdec.hip).  I compressed files of one decoded size (H, W)
+ * -> I uint8 HWC RGB images in device memory (gray replicated: what data.read_image_u8 makes of PIL's array), image i at
+ * pixels + i * image_stride_bytes with contiguous rows.  The contract: the pixels PIL (libjpeg-turbo: jpeg_idct_islow, fancy upsampling) gives,
+ * exactly, or a status word and no pixel.  Accepted: SOF0, 8-bit samples, one interleaved scan of all components; 1 component, or 3 (YCbCr:
+ * a JFIF APP0 or component ids 1, 2, 3) with chroma 1x1 and luma 1x1 (4:4:4), 2x1 (4:2:2) or 2x2 (4:2:0); 8-bit quantisation tables, at most
+ * two DC and two AC Huffman tables, any number of DQT / DHT segments; DRI with any interval; APPn / COM skipped.  Not taken (cs_jpeg_probe
+ * says CS_ERR_UNSUPPORTED and the caller decodes the file elsewhere): every other SOFn, 4 components, 12-bit, other samplings, a file with an
+ * Adobe APP14 segment, subsampled files with W <= 4 (libjpeg's replication upsampler).  No equality with PIL is claimed for hand-made
+ * coefficient blocks whose IDCT leaves the sample range by more than a few hundred; such files stay memory-safe and deterministic.
+ * cs_jpeg_probe is host arithmetic over the file's bytes (no device is touched): the marker segments within n up to SOS.  CS_ERR_BAD_ARG for
+ * framing that runs past n; it never reads at or beyond file + n.
+ * cs_op_jpeg_decode: files is ONE device buffer of total_file_bytes bytes holding the files back to back, file i at file_offsets[i],
+ * file_lengths[i] long (all arrays in device memory).  Sampling is per file: the kernel reads the headers itself and trusts nothing the host
+ * said.  Three launches on `stream`, whatever I is; the call does not wait for the device.  status[i] (device) is 0 for a complete image or
+ * one of CS_JPGDEC_*; a file with a non-zero status has written no pixel and has not disturbed the other files of the call.  Bytes behind the
+ * last MCU are not examined.  workspace: device, 16-byte aligned, cs_jpeg_decode_workspace_bytes(...) bytes (host arithmetic; 0 for sizes the
+ * decoder does not take).  1 <= H, W <= 4096 (CS_ERR_UNSUPPORTED above), 1 <= I <= 65535. */
+enum { CS_JPEG_GRAY = 0, CS_JPEG_444 = 1, CS_JPEG_422 = 2, CS_JPEG_420 = 3 };
+typedef struct cs_jpeg_info {
+  int width, height, components;
+  int sampling;          /* CS_JPEG_*, -1 when the decoder does not take the file */
+  int restart_interval;  /* MCUs between restart markers, 0 without DRI */
+  unsigned long long entropy_offset; /* first byte behind the SOS segment */
+} cs_jpeg_info;
+enum {
+  CS_JPGDEC_OK = 0,
+  CS_JPGDEC_BAD_FRAMING = 1,     /* SOI, a segment length past the file, no SOF / SOS */
+  CS_JPGDEC_HEADER_MISMATCH = 2, /* SOF is not the call's H, W (or a form the decoder does not take) */
+  CS_JPGDEC_BAD_TABLE = 3,       /* DHT with more codes than a length allows, more than 256 symbols or counts past the segment; a DQT
+                                    index or precision; a table that a component selects but no segment defined */
+  CS_JPGDEC_BAD_CODE = 4,        /* 16 bits that are no code of the table */
+  CS_JPGDEC_BAD_SYMBOL = 5,      /* DC category above 11, AC size above 10, or a run past coefficient 63 */
+  CS_JPGDEC_INPUT_EXHAUSTED = 6, /* the entropy data ends, or a marker other than the expected one appears, before the last MCU */
+  CS_JPGDEC_BAD_RESTART = 7      /* a missing, misnumbered or surplus RSTn */
+};
+int cs_jpeg_probe(const uint8_t* file, size_t n, cs_jpeg_info* info);
+size_t cs_jpeg_decode_workspace_bytes(int I, int H, int W, size_t total_file_bytes);
+int cs_op_jpeg_decode(const uint8_t* files, const uint64_t* file_offsets, const uint32_t* file_lengths, size_t total_file_bytes, int I, int H,
+                      int W, void* pixels, long long image_stride_bytes, uint32_t* status, void* workspace, cs_stream stream);
 /* de_norm_img + u8 (utils/misc/image.py:25-34, utils/io/images.py:20-23; batch_writer.py:117-135): I processed images fp32 CHW -> uint8 HWC,
  * x * std, then + mean, then * 255, each rounded on its own (no fma), truncated.  Values are clamped to [0, 255] first (NaN -> 0): that agrees
  * with the host form (a C cast) on every value the input stage produces (u8 / 255 normalised and de-normalised stays inside [0, 255]); outside
