@@ -33,6 +33,14 @@ class Cfg(dict):
         return Cfg({k: copy.deepcopy(v, memo) for k, v in self.items()})
 
 
+def this_main_choice(cfg, key: str, options) -> str:
+    """this_main.<key> (this build's keys), one of `options`; the first is the default."""
+    v = cfg.this_main.get(key, options[0])
+    if v not in options:
+        raise ValueError(f"this_main.{key}={v!r} not supported: {' | '.join(options)}")
+    return v
+
+
 def _wrap(v: Any) -> Any:
     if isinstance(v, dict) and not isinstance(v, Cfg):
         return Cfg({k: _wrap(x) for k, x in v.items()})

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .config import this_main_choice
 from .synth import IMAGENET_MEAN_STD
 
 EMPTY = "empty_image"  # placeholder path the reference pads short reference lists with (sampler.py:22-27)
@@ -101,10 +102,7 @@ PNGDEC_STATUS = ("ok", "bad CRC-32", "bad Adler-32", "bad zlib header", "reserve
 
 def png_decoder_choice(cfg) -> str:
     """this_main.png_decoder (this build's key): host (default) | gpu."""
-    v = cfg.this_main.get("png_decoder", "host")
-    if v not in PNG_DECODERS:
-        raise ValueError(f"this_main.png_decoder={v!r} not supported: host | gpu")
-    return v
+    return this_main_choice(cfg, "png_decoder", PNG_DECODERS)
 
 
 JPGDEC_STATUS = ("ok", "bad framing (SOI, a segment length past the file, no SOF / SOS)", "SOF differs from the size asked for, or a form the decoder does not take",
@@ -113,10 +111,7 @@ JPGDEC_STATUS = ("ok", "bad framing (SOI, a segment length past the file, no SOF
 
 def jpeg_decoder_choice(cfg) -> str:
     """this_main.jpeg_decoder (this build's key): host (default) | gpu."""
-    v = cfg.this_main.get("jpeg_decoder", "host")
-    if v not in PNG_DECODERS:
-        raise ValueError(f"this_main.jpeg_decoder={v!r} not supported: host | gpu")
-    return v
+    return this_main_choice(cfg, "jpeg_decoder", PNG_DECODERS)
 
 
 def png_decode_window_choice(cfg) -> int:
@@ -339,23 +334,26 @@ class PngDecoder:
         return {"jpeg_decoded_gpu": self.jpeg_gpu, "jpeg_decoded_host": self.jpeg_host}
 
 
+def batch_files(items, zero_reference: bool = False, extra=None, skip=()) -> List[Tuple[str, bool]]:
+    """The (path, gray16) list of the files a batch reads, in reading order: per item its query, its references in slot order (not the
+    "empty_image" placeholders, not the paths in `skip`, none at all with zero_reference), then extra(item).  A file named twice is listed twice."""
+    files: List[Tuple[str, bool]] = []
+    for it in items:
+        files.append((it["query/img"], False))
+        if not zero_reference:
+            files += [(p, False) for p in it["reference/cross/imgs"] if p != EMPTY and p not in skip]
+        if extra is not None:
+            files += extra(it)
+    return files
+
+
 def plan_decodes(batches, zero_reference: bool, once_per_reference: bool, extra=None) -> List[List[Tuple[str, bool]]]:
-    """Per batch the (path, gray16) list of the files it reads, in the order decode_items reads them: queries and references (with a
-    reference-token cache a reference is read by the first batch that names it only: later ones find its tokens), then extra(item)."""
+    """Per batch its batch_files, the list decode_items reads; with a reference-token cache (once_per_reference) a reference is read by the first
+    batch that names it only: later ones find its tokens.  (Fixed up front; the host path's `skip` follows the cache as it is at run time.)"""
     seen, plan = set(), []
     for its in batches:
-        files: List[Tuple[str, bool]] = []
-        for it in its:
-            files.append((it["query/img"], False))
-            if not zero_reference:
-                for p in it["reference/cross/imgs"]:
-                    if p == EMPTY or (once_per_reference and p in seen):
-                        continue
-                    seen.add(p)
-                    files.append((p, False))
-            if extra is not None:
-                files += extra(it)
-        plan.append(files)
+        plan.append(batch_files(its, zero_reference, extra, seen if once_per_reference else ()))
+        seen.update(p for it in its for p in it["reference/cross/imgs"])
     return plan
 
 
@@ -624,74 +622,58 @@ def decode_items(items: List[Dict[str, object]], zero_reference: bool = False, p
     """path -> decoded uint8 image for every file the items name (host side; PIL releases the GIL while decoding, so a thread pool
     plays the role of the reference's DataLoader workers, task/predict.py:110-117).  Reference paths in `skip` (already in the
     token cache) are not decoded."""
-    paths = []
-    for it in items:
-        paths.append(it["query/img"])
-        if not zero_reference:
-            paths += [p for p in it["reference/cross/imgs"] if p != EMPTY and p not in skip]
-    uniq = list(dict.fromkeys(paths))
+    uniq = list(dict.fromkeys(p for p, _ in batch_files(items, zero_reference, skip=skip)))
     imgs = list(pool.map(read_image_u8, uniq)) if pool is not None else [read_image_u8(p) for p in uniq]
     return dict(zip(uniq, imgs))
 
 
-def load_batch(items: List[Dict[str, object]], stage: InputStage, zero_reference: bool = False,
-               decoded: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, object]:
-    """One batch dict with the keys `_core_step` reads (task/core.py:265-272) plus `item_paths` in the collated layout the
-    writers expect (default_collate turns the per-item list of N reference paths into N lists of B paths).  `decoded` holds
-    images already read by decode_items (a reference image shared by several items of the batch is decoded once)."""
-    B = len(items)
+def item_paths(items: List[Dict[str, object]]) -> Dict[str, list]:
+    """The batch's file paths in the collated layout the writers expect (default_collate turns the per-item list of N reference paths into N
+    lists of B paths)."""
+    N = len(items[0]["reference/cross/imgs"])
+    return {"query/img": [it["query/img"] for it in items], "query/score_map": [it["query/score_map"] for it in items],
+            "reference/cross/imgs": [[it["reference/cross/imgs"][n] for it in items] for n in range(N)]}
+
+
+def _reference_image(path: str, decoded, stage: InputStage, size):
+    """The decoded reference image (from `decoded`, else read here), checked against the query's processed size."""
+    img = decoded[path] if path in decoded else read_image_u8(path)
+    if stage.geometry(*img.shape[:2])[1][2:] != tuple(size):
+        raise ValueError(f"{path}: processed size differs from the query's {size[0]}x{size[1]}")
+    return img
+
+
+def load_batch(items: List[Dict[str, object]], stage: InputStage, decoded: Optional[Dict[str, np.ndarray]] = None, u8: bool = False,
+               references: bool = True, zero_reference: bool = False):
+    """(batch, processed size): one batch dict with the keys `_core_step` reads (task/core.py:265-272) plus `item_paths`.  `decoded` holds
+    images already read by decode_items (a reference image shared by several items of the batch is decoded once).
+    u8: the one-pass input stage -- "query/img" and "reference/cross/imgs" are model.U8Batch objects (decoded images on the device + geometry) for
+    CrossScoreNet.forward_u8 and no processed fp32 tensor exists; else (B, 3, oh, ow) and (B, N, 3, oh, ow) fp32 tensors.
+    references=False: the references come from a ReferenceTokenCache and "reference/cross/imgs" is None."""
     decoded = decoded if decoded is not None else {}
-    get = lambda p: decoded[p] if p in decoded else read_image_u8(p)  # noqa: E731
-    q_imgs = [get(it["query/img"]) for it in items]
+    q_imgs = [decoded[it["query/img"]] if it["query/img"] in decoded else read_image_u8(it["query/img"]) for it in items]
     geo = {stage.geometry(*im.shape[:2])[1][2:] for im in q_imgs}
     if len(geo) != 1:
         raise ValueError(f"query images of one batch must share the processed size, got {sorted(geo)}")
-    oh, ow = next(iter(geo))
-    N = len(items[0]["reference/cross/imgs"])
-    query = torch.empty((B, 3, oh, ow), dtype=torch.float32, device=stage.device)
-    refs = torch.empty((B, N, 3, oh, ow), dtype=torch.float32, device=stage.device)
-    for b, (it, qi) in enumerate(zip(items, q_imgs)):
-        stage(qi, query[b])
-        for n, p in enumerate(it["reference/cross/imgs"]):
-            if p == EMPTY or zero_reference:
-                # nvs_dataset.py:459-470: placeholders and zero_reference are all-zero images BEFORE T.Normalize -> (0 - mean) / std
-                refs[b, n] = stage.zero_image_value[:, None, None]
-                continue
-            ri = get(p)
-            if stage.geometry(*ri.shape[:2])[1][2:] != (oh, ow):
-                raise ValueError(f"{p}: processed size differs from the query's {oh}x{ow}")
-            stage(ri, refs[b, n])
-    item_paths = {"query/img": [it["query/img"] for it in items], "query/score_map": [it["query/score_map"] for it in items],
-                  "reference/cross/imgs": [[it["reference/cross/imgs"][n] for it in items] for n in range(N)]}
-    return {"query/img": query, "reference/cross/imgs": refs, "item_paths": item_paths}
-
-
-def load_batch_u8(items: List[Dict[str, object]], stage: InputStage, zero_reference: bool = False,
-                  decoded: Optional[Dict[str, np.ndarray]] = None) -> Dict[str, object]:
-    """load_batch for the one-pass input stage: "query/img" and "reference/cross/imgs" are model.U8Batch objects (decoded images on the device +
-    geometry) for CrossScoreNet.forward_u8; no processed fp32 tensor exists."""
-    decoded = decoded if decoded is not None else {}
-    get = lambda p: decoded[p] if p in decoded else read_image_u8(p)  # noqa: E731
-    q_imgs = [get(it["query/img"]) for it in items]
-    geo = {stage.geometry(*im.shape[:2])[1][2:] for im in q_imgs}
-    if len(geo) != 1:
-        raise ValueError(f"query images of one batch must share the processed size, got {sorted(geo)}")
-    size = next(iter(geo))
-    N = len(items[0]["reference/cross/imgs"])
-    refs = []
-    for it in items:
-        for p in it["reference/cross/imgs"]:
-            if p == EMPTY or zero_reference:
-                refs.append(stage.placeholder(size))
-                continue
-            ri = get(p)
-            if stage.geometry(*ri.shape[:2])[1][2:] != size:
-                raise ValueError(f"{p}: processed size differs from the query's {size[0]}x{size[1]}")
-            refs.append(stage.describe(ri))
-    item_paths = {"query/img": [it["query/img"] for it in items], "query/score_map": [it["query/score_map"] for it in items],
-                  "reference/cross/imgs": [[it["reference/cross/imgs"][n] for it in items] for n in range(N)]}
-    return {"query/img": stage.batch([stage.describe(qi) for qi in q_imgs], size), "reference/cross/imgs": stage.batch(refs, size),
-            "item_paths": item_paths}
+    size = oh, ow = next(iter(geo))
+    ref_lists = [it["reference/cross/imgs"] if references else () for it in items]
+    # nvs_dataset.py:459-470: placeholders and zero_reference are all-zero images BEFORE T.Normalize -> (0 - mean) / std
+    blank = lambda p: p == EMPTY or zero_reference  # noqa: E731
+    if u8:
+        refs = stage.batch([stage.placeholder(size) if blank(p) else stage.describe(_reference_image(p, decoded, stage, size))
+                            for ps in ref_lists for p in ps], size) if references else None
+        query = stage.batch([stage.describe(qi) for qi in q_imgs], size)
+    else:
+        query = torch.empty((len(items), 3, oh, ow), dtype=torch.float32, device=stage.device)
+        refs = torch.empty((len(items), len(ref_lists[0]), 3, oh, ow), dtype=torch.float32, device=stage.device) if references else None
+        for b, (ps, qi) in enumerate(zip(ref_lists, q_imgs)):
+            stage(qi, query[b])
+            for n, p in enumerate(ps):
+                if blank(p):
+                    refs[b, n] = stage.zero_image_value[:, None, None]
+                else:
+                    stage(_reference_image(p, decoded, stage, size), refs[b, n])
+    return {"query/img": query, "reference/cross/imgs": refs, "item_paths": item_paths(items)}, size
 
 
 class ReferenceTokenCache:
@@ -718,30 +700,18 @@ class ReferenceTokenCache:
                 self.tokens.clear()
                 self.images.clear()
                 missing = list(dict.fromkeys(k for ks in keys for k in ks))
+            imgs = [None if k[0] == EMPTY else _reference_image(k[0], decoded, self.stage, (oh, ow)) for k in missing]
             if self.from_u8:
-                descs = []
-                for k in missing:
-                    if k[0] == EMPTY:
-                        descs.append(self.stage.placeholder((oh, ow)))
-                        continue
-                    img = decoded[k[0]] if k[0] in decoded else read_image_u8(k[0])
-                    if self.stage.geometry(*img.shape[:2])[1][2:] != (oh, ow):
-                        raise ValueError(f"{k[0]}: processed size differs from the query's {oh}x{ow}")
-                    descs.append(self.stage.describe(img))
-                tok = self.net.encode_references_u8(self.stage.batch(descs, (oh, ow)))
-                for i, k in enumerate(missing):
-                    self.tokens[k] = tok[i]
-                missing = []
-            buf = torch.empty((len(missing), 3, oh, ow), dtype=torch.float32, device=self.stage.device) if missing else None
-            for i, k in enumerate(missing):
-                if k[0] == EMPTY:
-                    buf[i] = self.stage.zero_image_value[:, None, None]
-                    continue
-                img = decoded[k[0]] if k[0] in decoded else read_image_u8(k[0])
-                if self.stage.geometry(*img.shape[:2])[1][2:] != (oh, ow):
-                    raise ValueError(f"{k[0]}: processed size differs from the query's {oh}x{ow}")
-                self.stage(img, buf[i])
-            tok = self.net.encode_references(buf) if missing else None
+                tok = self.net.encode_references_u8(self.stage.batch(
+                    [self.stage.placeholder((oh, ow)) if im is None else self.stage.describe(im) for im in imgs], (oh, ow)))
+            else:
+                buf = torch.empty((len(missing), 3, oh, ow), dtype=torch.float32, device=self.stage.device)
+                for i, im in enumerate(imgs):
+                    if im is None:
+                        buf[i] = self.stage.zero_image_value[:, None, None]
+                    else:
+                        self.stage(im, buf[i])
+                tok = self.net.encode_references(buf)
             for i, k in enumerate(missing):
                 self.tokens[k] = tok[i]
                 if self.keep_images:
@@ -749,32 +719,3 @@ class ReferenceTokenCache:
         tokens = torch.stack([torch.stack([self.tokens[k] for k in ks]) for ks in keys])
         images = torch.stack([torch.stack([self.images[k] for k in ks]) for ks in keys]) if self.keep_images else None
         return tokens, images
-
-
-def load_query_batch(items: List[Dict[str, object]], stage: InputStage, decoded: Dict[str, np.ndarray]):
-    """Query tensors + item paths of one batch (the references come from a ReferenceTokenCache)."""
-    q_imgs = [decoded[it["query/img"]] if it["query/img"] in decoded else read_image_u8(it["query/img"]) for it in items]
-    geo = {stage.geometry(*im.shape[:2])[1][2:] for im in q_imgs}
-    if len(geo) != 1:
-        raise ValueError(f"query images of one batch must share the processed size, got {sorted(geo)}")
-    oh, ow = next(iter(geo))
-    query = torch.empty((len(items), 3, oh, ow), dtype=torch.float32, device=stage.device)
-    for b, qi in enumerate(q_imgs):
-        stage(qi, query[b])
-    N = len(items[0]["reference/cross/imgs"])
-    item_paths = {"query/img": [it["query/img"] for it in items], "query/score_map": [it["query/score_map"] for it in items],
-                  "reference/cross/imgs": [[it["reference/cross/imgs"][n] for it in items] for n in range(N)]}
-    return {"query/img": query, "reference/cross/imgs": None, "item_paths": item_paths}, (oh, ow)
-
-
-def load_query_batch_u8(items: List[Dict[str, object]], stage: InputStage, decoded: Dict[str, np.ndarray]):
-    """load_query_batch for the one-pass input stage: "query/img" is a model.U8Batch."""
-    q_imgs = [decoded[it["query/img"]] if it["query/img"] in decoded else read_image_u8(it["query/img"]) for it in items]
-    geo = {stage.geometry(*im.shape[:2])[1][2:] for im in q_imgs}
-    if len(geo) != 1:
-        raise ValueError(f"query images of one batch must share the processed size, got {sorted(geo)}")
-    size = next(iter(geo))
-    N = len(items[0]["reference/cross/imgs"])
-    item_paths = {"query/img": [it["query/img"] for it in items], "query/score_map": [it["query/score_map"] for it in items],
-                  "reference/cross/imgs": [[it["reference/cross/imgs"][n] for it in items] for n in range(N)]}
-    return {"query/img": stage.batch([stage.describe(qi) for qi in q_imgs], size), "reference/cross/imgs": None, "item_paths": item_paths}, size

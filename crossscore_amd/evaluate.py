@@ -37,7 +37,6 @@ import csv
 import ctypes as C
 import os
 import sys
-import time
 from datetime import datetime
 from pathlib import Path
 from typing import Dict, Iterable, List, Optional, Sequence
@@ -45,15 +44,10 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, parallel, synth
-from .config import load_config
-from .data import (EMPTY, DecodeWindow, InputStage, PngDecoder, ReferenceTokenCache, decode_items, load_batch, load_batch_u8, load_query_batch,
-                   load_query_batch_u8, jpeg_decoder_choice, metric_mode, plan_decodes, png_decode_window_choice, png_decoder_choice, read_image_u8, read_metric_map_u16)
-from .model import CrossScoreNet, load_lightning_checkpoint
+from . import _lib, parallel, scoring
+from .config import load_config, this_main_choice
+from .data import EMPTY, InputStage, decode_items, metric_mode, read_image_u8, read_metric_map_u16
 from .nvs import NvsItems, random_order
-from .pipeline import ForwardPipeline
-from .predict import seed_everything
-from .writers import BatchWriter, ScoreSummariser, png_compression_choice, png_encoder_choice
 
 METRIC_KEYS = ("test/loss", "test/loss_cross", "test/corr_cross", "test/psnr_cross")
 CSV_COLUMNS = sorted(METRIC_KEYS + ("epoch", "step"))  # CSVLogger sorts its keys
@@ -63,10 +57,7 @@ GT_METRIC_MAPS = ("files", "compute")
 
 def gt_metric_maps_choice(cfg) -> str:
     """this_main.gt_metric_maps (this build's key): files (default) | compute."""
-    v = cfg.this_main.get("gt_metric_maps", "files")
-    if v not in GT_METRIC_MAPS:
-        raise ValueError(f"this_main.gt_metric_maps={v!r} not supported: files | compute")
-    return v
+    return this_main_choice(cfg, "gt_metric_maps", GT_METRIC_MAPS)
 
 
 def gt_map_kind(metric_type: str) -> int:
@@ -185,19 +176,10 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     """Runs the test loop; returns {"version_dir", "out_dir", "metrics", "batches", "files", "query_images_per_sec", "input_stage", "png_encoder", "png_compression",
     "png_files", "gt_metric_maps", "png_decoder", "png_decoded", "jpeg_decoder", "jpeg_decoded"}.
     capture (tests, tools): a list that receives per batch {"batch_idx", "item_paths", "score", "gt", "stats"} (host copies)."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("crossscore_amd.evaluate needs a GPU: the scoring path has no CPU fallback")
-    png_encoder = png_encoder_choice(cfg)  # this_main.png_encoder: host (default) | gpu, as in predict.py
-    png_compression = png_compression_choice(cfg)  # this_main.png_compression: fast (default) | compact, the gpu encoder's form
+    opts = scoring.options(cfg, "test")
     compute_gt = gt_metric_maps_choice(cfg) == "compute"  # this_main.gt_metric_maps: files (default) | compute
-    # this_main.png_decoder: host (default) | gpu, as in predict.py; here the window also holds the 16-bit metric maps (files) or the captured
-    # images (compute)
-    png_decoder, decode_window = png_decoder_choice(cfg), png_decode_window_choice(cfg)
-    jpeg_decoder = jpeg_decoder_choice(cfg)  # this_main.jpeg_decoder: host (default) | gpu, baseline JPEG inputs through the same window
-    seed_everything(int(cfg.lightning.seed))
-    rank, local_rank, world = parallel.init_from_env()
-    device = torch.device("cuda", local_rank if world > 1 else 0)
-    torch.cuda.set_device(device)
+    scoring.start(cfg, opts)
+    rank, device = opts.rank, opts.device
     bs = int(cfg.data.loader.validation.batch_size)
     crop_mode = cfg.this_main.crop_mode
     if not cfg.this_main.get("force_batch_size", False) and bs > 8 and crop_mode in (None, "integer_patches"):
@@ -217,77 +199,25 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
         raise NotImplementedError(f"loss fn {cfg.model.loss.fn} (task/core.py:183-187 knows l1)")
     items = NvsItems.from_config(cfg, compute_gt)
     gt_kind = gt_map_kind(cfg.model.predict.metric.type)
-
-    net = CrossScoreNet(cfg)
-    if "operand_dtype" not in cfg.model.backbone:
-        net.operand_dtype = "bf16" if str(cfg.trainer.precision).startswith("bf16") else "fp16"
-    if state_dict is None:
-        if cfg.trainer.ckpt_path_to_load is not None:
-            state_dict = load_lightning_checkpoint(cfg.trainer.ckpt_path_to_load)
-        else:
-            print("[crossscore_amd.evaluate] no checkpoint: seeded synthetic weights (scores are meaningless)", file=sys.stderr)
-            state_dict = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(net.arch, int(cfg.lightning.seed)).items()}
-    net.load_state_dict(state_dict, strict=True)
-    net = net.to(device)
-
-    wcfg = cfg.logger.test.write
-    writer = (BatchWriter(cfg, "test", net.img_mean_std, device, workers=max(1, int(cfg.data.loader.validation.num_workers) // 2),
-                          png_encoder=png_encoder, png_compression=png_compression)
-              if wcfg.flag.batch else None)
-    summariser = ScoreSummariser(cfg.model.predict.metric.type, cfg.model.predict.metric.min, out_dir)
+    patch = int(cfg.model.patch_size)
 
     order = random_order(len(items), int(cfg.lightning.seed)) if cfg.data.loader.validation.shuffle else list(range(len(items)))
-    lo, hi = parallel.shard_bounds(len(order), world, rank)
+    lo, hi = parallel.shard_bounds(len(order), opts.world, rank)
     batches = [[items[order[i]] for i in range(start, min(start + bs, hi))] for start in range(lo, hi, bs)]
     batches = batches[:limit_batches(len(batches), cfg.trainer.limit_test_batches)]
-    zero_ref = bool(cfg.data.dataset.zero_reference)
-    from concurrent.futures import ThreadPoolExecutor
-    pool = ThreadPoolExecutor(max_workers=max(1, int(cfg.data.loader.validation.num_workers)))
-    prefetch = ThreadPoolExecutor(max_workers=1)
-    use_cache = bool(cfg.this_main.get("cache_reference_tokens", True)) and int(cfg.data.neighbour_config.cross) > 0
-    pipe = ForwardPipeline(net, depth=max(1, int(cfg.this_main.get("batches_in_flight", 3))))
-    # the one-pass input stage under the rules of predict.py: "auto" takes it when no processed image is written and the geometry is held
-    want_imgs = writer is not None and bool(wcfg.flag.image_query or wcfg.flag.image_reference)
-    fused_cfg = cfg.this_main.get("fused_input_stage", "auto")
-    fused_in = False
-    if fused_cfg not in (False, "false", "False", 0) and batches and not want_imgs:
-        probe = read_image_u8(batches[0][0]["query/img"])
-        rs0, crop0 = stage.geometry(*probe.shape[:2])
-        from .model import U8Image
-        fused_in = net.u8_input_supported(U8Image(None, probe.shape[0], probe.shape[1], rs0, crop0[0], crop0[1]), crop0[2:], device)
-    if fused_cfg in (True, "true", "True", 1) and not fused_in:
-        raise ValueError("this_main.fused_input_stage=True, but " + ("the writers need the processed images (logger.test.write.flag.image_query / "
-                         "image_reference)" if want_imgs else "this backbone / image geometry is not taken by the one-pass input stage"))
-    cache = ReferenceTokenCache(pipe, stage, keep_images=bool(writer is not None and wcfg.flag.image_reference),
-                                max_images=int(cfg.this_main.get("reference_cache_max_images", 4096)), from_u8=fused_in) if use_cache else None
-    cached_paths = lambda: {k[0] for k in cache.tokens} if cache is not None else ()  # noqa: E731
-    decoder = PngDecoder(device, pool, png=png_decoder == "gpu", jpeg=jpeg_decoder == "gpu") if "gpu" in (png_decoder, jpeg_decoder) else None
+    lib = _lib.load()
+    rows: List[Dict[str, float]] = []
 
     def gt_files(it):
         if compute_gt:
             return [(it["query/gt"], False)]
         return [] if it["query/score_map"] == EMPTY else [(it["query/score_map"], True)]
 
-    window = DecodeWindow(decoder, plan_decodes(batches, zero_ref, cache is not None, gt_files), decode_window) if decoder is not None else None
-
-    def fetch_eval(i):
-        """decode_eval through the decode window: device tensors for the images and for the maps / captured images"""
-        d = window.fetch(i)
+    def fetch_eval(d, its):
+        """decode_eval's second value out of the decode window's tensors: device tensors for the maps / captured images"""
         if compute_gt:
-            return d, [d[it["query/gt"]] for it in batches[i]]
-        return d, [None if it["query/score_map"] == EMPTY else d[it["query/score_map"]] for it in batches[i]]
-
-    def submit_decode(i):
-        if window is not None:
-            return prefetch.submit(fetch_eval, i)
-        return prefetch.submit(decode_eval, batches[i], zero_ref, pool, cached_paths(), compute_gt)
-
-    pending = submit_decode(0) if batches else None
-    need_w, head_id = bool(cfg.model.need_attn_weights), int(cfg.model.need_attn_weights_head_id)
-    lib = _lib.load()
-    files: List[str] = []
-    rows: List[Dict[str, float]] = []
-    n_done = 0
+            return [d[it["query/gt"]] for it in its]
+        return [None if it["query/score_map"] == EMPTY else d[it["query/score_map"]] for it in its]
 
     def gt_and_stats(ticket, its, decoded, maps, size, batch):
         """GT stage + statistics kernel on the forward's stream, behind its score map; returns (gt, stats, event)."""
@@ -304,7 +234,8 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
             gt = torch.empty((B, oh, ow), dtype=torch.float32, device=device)
             if compute_gt:
                 # the render bytes the one-pass input stage already holds on the device, else the decoded host arrays
-                renders = [im.data for im in batch["query/img"].images] if fused_in else [decoded[it["query/img"]] for it in its]
+                on_device = hasattr(batch["query/img"], "images")  # (a model.U8Batch)
+                renders = [im.data for im in batch["query/img"].images] if on_device else [decoded[it["query/img"]] for it in its]
                 maps = stage.gt_metric_maps(renders, maps, gt_kind)
             stage.metric_maps(maps, [decoded[it["query/img"]].shape[:2] for it in its], mode, gt)
             score = ticket.out["score_map_ref_cross"]
@@ -319,15 +250,12 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
         return gt, stats, ev
 
     def check_size(size):
-        if crop_mode is None and (size[0] % net.arch.patch or size[1] % net.arch.patch):
-            raise ValueError(f"crop_mode null: a {size[0]}x{size[1]} image is no whole number of {net.arch.patch}-pixel patches (the reference "
+        if crop_mode is None and (size[0] % patch or size[1] % patch):
+            raise ValueError(f"crop_mode null: a {size[0]}x{size[1]} image is no whole number of {patch}-pixel patches (the reference "
                              "fails in the L1 loss' broadcast); use crop_mode=integer_patches")
 
-    def consume(entry):
-        ticket, batch, idx, gt, stats, ev = entry
-        out = pipe.result(ticket)
-        if window is not None:
-            window.check(idx)  # the status words of the files this batch read
+    def batch_stats(idx, batch, out, state):
+        gt, stats, ev = state
         cur = torch.cuda.current_stream(device)
         cur.wait_event(ev)
         gt.record_stream(cur)
@@ -338,54 +266,16 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
         if capture is not None:
             capture.append({"batch_idx": idx, "item_paths": batch["item_paths"], "score": out["score_map_ref_cross"].cpu().numpy(),
                             "gt": gt.cpu().numpy(), "stats": st})
-        summariser.update(batch, out, means=out.get("score_mean_ref_cross"))
-        if writer is not None:
-            files.extend(writer.write_out(batch, out, local_rank, idx))
 
-    torch.cuda.synchronize(device)
-    t0 = time.perf_counter()
-    queued = []
-    for batch_idx, its in enumerate(batches):
-        decoded, maps = pending.result()
-        if cache is None:
-            pending = submit_decode(batch_idx + 1) if batch_idx + 1 < len(batches) else None
-            batch = (load_batch_u8 if fused_in else load_batch)(its, stage, zero_ref, decoded)
-            size = batch["query/img"].size if fused_in else tuple(batch["query/img"].shape[-2:])
-            check_size(size)
-            if fused_in:
-                ticket = pipe.submit_u8(batch["query/img"], batch["reference/cross/imgs"], need_w, head_id, True)
-            else:
-                ticket = pipe.submit(batch["query/img"], batch["reference/cross/imgs"], need_w, head_id, False, return_mean=True)
-        else:
-            batch, size = (load_query_batch_u8 if fused_in else load_query_batch)(its, stage, decoded)
-            check_size(size)
-            tokens, ref_imgs = cache.gather([it["reference/cross/imgs"] for it in its], decoded, size, zero_ref)
-            batch["reference/cross/imgs"] = ref_imgs
-            pending = submit_decode(batch_idx + 1) if batch_idx + 1 < len(batches) else None
-            ticket = (pipe.submit_cached_u8 if fused_in else pipe.submit_cached)(batch["query/img"], tokens, need_w, head_id, True)
-        gt, stats, ev = gt_and_stats(ticket, its, decoded, maps, tuple(size), batch)
-        n_done += len(its)
-        queued.append((ticket, batch, batch_idx, gt, stats, ev))
-        while len(queued) >= pipe.depth:
-            consume(queued.pop(0))
-    while queued:
-        consume(queued.pop(0))
-    torch.cuda.synchronize(device)
-    t_loop = time.perf_counter() - t0
-    # outputs first, then one collective that carries the metrics and any failure (a rank that raised on its own before it would leave the
-    # others waiting in it): the failure is re-raised behind the collective, as in predict.py
-    failure: Optional[BaseException] = None
-    try:
-        if writer is not None:
-            writer.finish()
-        files += summariser.summarise()
-    except BaseException as exc:  # noqa: BLE001 -- re-raised below, behind the collective
-        failure = exc
-    finally:
-        prefetch.shutdown()
-        pool.shutdown()
-    bad = pipe.nonfinite_count()
-    tot = parallel.sum_over_ranks(weighted_sums(rows) + [1.0 if failure is not None else 0.0, float(bad)], device)
+    run = scoring.score(cfg, opts, stage, batches, state_dict, batches[0][0]["query/img"] if batches else None,
+                        calibrate=False,  # inherited: the test loop has never calibrated its batches in flight
+                        extra_files=gt_files, decode_host=lambda its, zr, pool, skip: decode_eval(its, zr, pool, skip, compute_gt),
+                        from_window=fetch_eval,
+                        check_size=check_size, after_submit=gt_and_stats, on_consume=batch_stats)
+    # one collective that carries the metrics and any failure of a rank's output stage (a rank that raised on its own before it would leave
+    # the others waiting in it): the failure is re-raised behind the collective, as in predict.py
+    failure, files = run.failure, run.files
+    tot = parallel.sum_over_ranks(weighted_sums(rows) + [1.0 if failure is not None else 0.0, float(run.nonfinite)], device)
     all_rows = [r for rr in parallel.gather_objects(rows) for r in rr]
     parallel.barrier()
     if failure is not None:
@@ -393,19 +283,14 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     if tot[4] > 0:
         raise RuntimeError(f"another rank failed while finishing its outputs (see its traceback); this rank's outputs are under {out_dir}")
     if tot[5] > 0:
-        raise FloatingPointError(f"{int(tot[5])} non-finite score-map values with {net.operand_dtype} MFMA operands: run with "
+        raise FloatingPointError(f"{int(tot[5])} non-finite score-map values with {run.operand_dtype} MFMA operands: run with "
                                  f"trainer.precision=bf16-mixed (model.backbone.operand_dtype=bf16); the outputs written are under {out_dir}")
     metrics = epoch_metrics(tot[:4])
     if rank == 0:
         files.append(write_metrics_csv(version_dir, metrics))
         files.append(write_batches_csv(out_dir, all_rows))
     return {"version_dir": version_dir, "out_dir": out_dir, "metrics": metrics, "batches": sorted(rows, key=lambda r: r["batch_idx"]),
-            "files": files, "input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
-            "png_encoder": png_encoder, "png_compression": png_compression, "gt_metric_maps": "compute" if compute_gt else "files",
-            "png_decoder": png_decoder, "png_decoded": decoder.stats() if png_decoder == "gpu" else {"png_decoded_gpu": 0, "png_decoded_host": 0},
-            "jpeg_decoder": jpeg_decoder, "jpeg_decoded": decoder.jpeg_stats() if jpeg_decoder == "gpu" else {"jpeg_decoded_gpu": 0, "jpeg_decoded_host": 0},
-            "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
-            "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}
+            "files": files, "gt_metric_maps": "compute" if compute_gt else "files", **run.result}
 
 
 def main(argv: Optional[Iterable[str]] = None) -> int:

@@ -268,6 +268,22 @@ class CrossScoreNet(torch.nn.Module):
         return h
 
     # -- forward ----------------------------------------------------------------------------------------------
+    def _alloc_outputs(self, B, N, H, W, dev, need_attn_weights, return_mean):
+        """(score, attn, mean_out) of the four forward calls: the score map, and the attention map / per-image means when asked for."""
+        P = self.arch.patch
+        h, w = H // P, W // P
+        score = torch.empty((B, h * P, w * P), dtype=torch.float32, device=dev)
+        attn = torch.empty((B, h, w, N, h, w), dtype=torch.float32, device=dev) if need_attn_weights else None
+        mean_out = torch.empty((B,), dtype=torch.float32, device=dev) if return_mean else None
+        return score, attn, mean_out
+
+    @staticmethod
+    def _results(score, attn, mean_out):
+        results = {"score_map_ref_cross": score, "attn_weights_map_ref_cross": attn}
+        if mean_out is not None:
+            results["score_mean_ref_cross"] = mean_out  # key does not start with "score_map": writers ignore it
+        return results
+
     @torch.no_grad()
     def forward(self, query_img, ref_cross_imgs, need_attn_weights=False, need_attn_weights_head_id=0, norm_img=False,
                 return_mean=False):
@@ -308,9 +324,7 @@ class CrossScoreNet(torch.nn.Module):
         lib = _lib.load()
         handle = self._ensure_handle(dev)
         with torch.cuda.device(dev):
-            score = torch.empty((B, h * P, w * P), dtype=torch.float32, device=dev)
-            attn = torch.empty((B, h, w, N, h, w), dtype=torch.float32, device=dev) if need_attn_weights else None
-            mean_out = torch.empty((B,), dtype=torch.float32, device=dev) if return_mean else None
+            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
             stream = torch.cuda.current_stream(dev).cuda_stream
             for b0, b1 in self._sub_batches(B, N, h * w):
                 rc = lib.cs_forward(handle, C.c_void_p(q[b0:b1].data_ptr()), C.c_void_p(r[b0:b1].data_ptr()), b1 - b0, N, H, W,
@@ -320,10 +334,7 @@ class CrossScoreNet(torch.nn.Module):
                                     C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None,
                                     C.c_void_p(stream))
                 _lib.check(rc)
-        results = {"score_map_ref_cross": score, "attn_weights_map_ref_cross": attn}
-        if return_mean:
-            results["score_mean_ref_cross"] = mean_out  # key does not start with "score_map": writers ignore it
-        return results
+        return self._results(score, attn, mean_out)
 
     def _sub_batches(self, B: int, N: int, Np: int):
         """Items are independent, so a batch whose decoder buffers would overflow the kernels' 32-bit element offsets
@@ -374,9 +385,7 @@ class CrossScoreNet(torch.nn.Module):
         handle = self._ensure_handle(dev)
         lib = _lib.load()
         with torch.cuda.device(dev):
-            score = torch.empty((B, h * P, w * P), dtype=torch.float32, device=dev)
-            attn = torch.empty((B, h, w, N, h, w), dtype=torch.float32, device=dev) if need_attn_weights else None
-            mean_out = torch.empty((B,), dtype=torch.float32, device=dev) if return_mean else None
+            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
             stream = torch.cuda.current_stream(dev).cuda_stream
             for b0, b1 in self._sub_batches(B, N, h * w):
                 _lib.check(lib.cs_forward_cached(
@@ -384,10 +393,7 @@ class CrossScoreNet(torch.nn.Module):
                     C.c_void_p(score[b0:b1].data_ptr()),
                     C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None, int(need_attn_weights_head_id),
                     C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None, C.c_void_p(stream)))
-        results = {"score_map_ref_cross": score, "attn_weights_map_ref_cross": attn}
-        if return_mean:
-            results["score_mean_ref_cross"] = mean_out
-        return results
+        return self._results(score, attn, mean_out)
 
     # -- the same three calls fed from decoded uint8 images (SURVEY.md 8f-4 as worded: uint8 in, tokens out) --------------------------------
     def u8_input_supported(self, img: U8Image, size, device=None) -> bool:
@@ -397,14 +403,6 @@ class CrossScoreNet(torch.nn.Module):
             return False
         st = img.c_struct()
         return bool(_lib.load().cs_u8_input_supported(self._ensure_handle(dev), C.byref(st), int(size[0]), int(size[1])))
-
-    def _u8_out(self, B, N, H, W, dev, need_attn_weights, return_mean):
-        P = self.arch.patch
-        h, w = H // P, W // P
-        score = torch.empty((B, h * P, w * P), dtype=torch.float32, device=dev)
-        attn = torch.empty((B, h, w, N, h, w), dtype=torch.float32, device=dev) if need_attn_weights else None
-        mean_out = torch.empty((B,), dtype=torch.float32, device=dev) if return_mean else None
-        return score, attn, mean_out
 
     @torch.no_grad()
     def forward_u8(self, query: U8Batch, refs: U8Batch, need_attn_weights=False, need_attn_weights_head_id=0, return_mean=False):
@@ -423,17 +421,14 @@ class CrossScoreNet(torch.nn.Module):
         handle = self._ensure_handle(dev)
         P = self.arch.patch
         with torch.cuda.device(dev):
-            score, attn, mean_out = self._u8_out(B, N, H, W, dev, need_attn_weights, return_mean)
+            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
             stream = torch.cuda.current_stream(dev).cuda_stream
             for b0, b1 in self._sub_batches(B, N, (H // P) * (W // P)):
                 _lib.check(lib.cs_forward_u8(handle, query.c_array(b0, b1), refs.c_array(b0 * N, b1 * N), b1 - b0, N, H, W, query.mean, query.std,
                                              C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
                                              int(need_attn_weights_head_id),
                                              C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None, C.c_void_p(stream)))
-        results = {"score_map_ref_cross": score, "attn_weights_map_ref_cross": attn}
-        if return_mean:
-            results["score_mean_ref_cross"] = mean_out
-        return results
+        return self._results(score, attn, mean_out)
 
     @torch.no_grad()
     def encode_references_u8(self, imgs: U8Batch):
@@ -469,17 +464,14 @@ class CrossScoreNet(torch.nn.Module):
         lib = _lib.load()
         handle = self._ensure_handle(dev)
         with torch.cuda.device(dev):
-            score, attn, mean_out = self._u8_out(B, N, H, W, dev, need_attn_weights, return_mean)
+            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
             stream = torch.cuda.current_stream(dev).cuda_stream
             for b0, b1 in self._sub_batches(B, N, (H // P) * (W // P)):
                 _lib.check(lib.cs_forward_cached_u8(handle, query.c_array(b0, b1), C.c_void_p(t[b0:b1].data_ptr()), b1 - b0, N, H, W, query.mean, query.std,
                                                     C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
                                                     int(need_attn_weights_head_id),
                                                     C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None, C.c_void_p(stream)))
-        results = {"score_map_ref_cross": score, "attn_weights_map_ref_cross": attn}
-        if return_mean:
-            results["score_mean_ref_cross"] = mean_out
-        return results
+        return self._results(score, attn, mean_out)
 
     def calibrate_lanes(self, query_img, ref_cross_imgs, tries: int = 3, steps: int = 4, min_gain: float = 0.08) -> Dict[str, Any]:
         """Checks that this module's multi-lane forward really overlaps its lanes, and repairs it if not.  The lanes' streams are probed

@@ -127,13 +127,13 @@ class ForwardPipeline:
             return {"serial_s": None, "in_flight_s": []}
         import time
 
+        method = {(False, False): "forward", (True, False): "forward_cached", (False, True): "forward_u8", (True, True): "forward_cached_u8"}[bool(cached), bool(u8)]
+        args = (query_img, ref_cross_imgs) + ((False, 0, False) if method == "forward" else ())
+
         def in_flight(n):
             last = None
             for _ in range(n):
-                if u8:
-                    last = self.submit_cached_u8(query_img, ref_cross_imgs) if cached else self.submit_u8(query_img, ref_cross_imgs)
-                else:
-                    last = self.submit_cached(query_img, ref_cross_imgs) if cached else self.submit(query_img, ref_cross_imgs, False, 0, False)
+                last = self._run(method, args, {})
             self.result(last)
             torch.cuda.synchronize(self.device)
 
@@ -141,12 +141,7 @@ class ForwardPipeline:
         t0 = time.perf_counter()
         with torch.cuda.stream(self.streams[0]):
             for _ in range(steps):
-                if u8:
-                    (self.nets[0].forward_cached_u8 if cached else self.nets[0].forward_u8)(query_img, ref_cross_imgs)
-                elif cached:
-                    self.nets[0].forward_cached(query_img, ref_cross_imgs)
-                else:
-                    self.nets[0](query_img, ref_cross_imgs, False, 0, False)
+                getattr(self.nets[0], method)(*args)
         torch.cuda.synchronize(self.device)
         serial = (time.perf_counter() - t0) / steps
         seen, best = [], None

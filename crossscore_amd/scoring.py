@@ -1,0 +1,237 @@
+"""The scoring run predict.py and evaluate.py share: this build's options, device, net and weights, writers, the input-stage decision, the
+reference-token cache, the decode window and the batch loop with its batches in flight.
+
+    opts = options(cfg, "predict")          # this_main.* keys, validated before anything is created or the device is touched
+    start(cfg, opts)                        # seeds, process group, device
+    ... the driver's own directories, InputStage, items and batch lists ...
+    run = score(cfg, opts, stage, batches, ...)
+    ... the driver's collective over the ranks, which re-raises run.failure behind it ...
+
+A driver adds what differs as plain arguments and two hooks: after_submit (right after a batch's forward is queued) and on_consume (when its
+outputs are taken, depth - 1 submits later).
+"""
+from __future__ import annotations
+
+import random
+import sys
+import time
+from concurrent.futures import ThreadPoolExecutor
+from types import SimpleNamespace
+from typing import Dict, NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import parallel, synth
+from .data import (DecodeWindow, PngDecoder, ReferenceTokenCache, decode_items, jpeg_decoder_choice, load_batch, plan_decodes,
+                   png_decode_window_choice, png_decoder_choice, read_image_u8)
+from .model import CrossScoreNet, U8Image, load_lightning_checkpoint
+from .pipeline import ForwardPipeline
+from .writers import BatchWriter, ScoreSummariser, png_compression_choice, png_encoder_choice
+
+DRIVER = {"predict": "predict", "test": "evaluate"}  # cfg.logger.<phase> -> the module that runs it
+
+
+def seed_everything(seed: int) -> None:
+    """lightning.seed_everything (task/predict.py:23): python, numpy and torch global generators."""
+    random.seed(seed)
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+
+
+def options(cfg, phase: str) -> SimpleNamespace:
+    """This build's this_main.* keys of a scoring run; an unknown value raises ValueError here."""
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"crossscore_amd.{DRIVER[phase]} needs a GPU: the scoring path has no CPU fallback")
+    o = SimpleNamespace(phase=phase)
+    # this_main.png_encoder (default "host"): who compresses the PNG outputs -- PIL on the writer's threads, or the device
+    # (writers.PngEncoder: conversion, de-normalisation and compression queued behind the forward; pixel-exact, not byte-equal)
+    o.png_encoder = png_encoder_choice(cfg)
+    # this_main.png_compression (default "fast"): the device encoder's form -- fast (Sub filter, fixed-Huffman / stored blocks)
+    # or compact (per-row adaptive filter, dynamic-Huffman blocks); ignored with png_encoder=host
+    o.png_compression = png_compression_choice(cfg)
+    # this_main.png_decoder (default "host"): who decodes the PNG inputs -- PIL on the loader's threads, or the device
+    # (data.PngDecoder: the compressed bytes go up, a window of this_main.png_decode_window upcoming files is decoded beside earlier forwards;
+    # the same pixels, bit for bit; files the device decoder does not take still go through PIL).  In evaluate the window also holds the 16-bit
+    # metric maps (gt_metric_maps=files) or the captured images (compute)
+    o.png_decoder, o.decode_window = png_decoder_choice(cfg), png_decode_window_choice(cfg)
+    # this_main.jpeg_decoder (default "host"): the same choice for baseline JPEG inputs (cs_op_jpeg_decode); either key set to gpu
+    # builds the decoder and its window, and each format goes to the device only under its own key
+    o.jpeg_decoder = jpeg_decoder_choice(cfg)
+    # this_main.cache_reference_tokens (default on): every reference image goes through the encoder once per run
+    # instead of once per query that samples it; the score maps are bit-identical
+    o.use_cache = bool(cfg.this_main.get("cache_reference_tokens", True)) and int(cfg.data.neighbour_config.cross) > 0
+    o.cache_max_images = int(cfg.this_main.get("reference_cache_max_images", 4096))
+    # this_main.batches_in_flight (default 3: with cached reference tokens a batch is 1/3 decoder, measured 2837 /
+    # 4152 / 4473 query-images/s with 1 / 2 / 3 in flight): the batch loop keeps that many forwards queued on replicas of the
+    # module (pipeline.py), so one batch's decoder runs beside the next batch's encoder; outputs are consumed depth-1 submits later,
+    # in batch order, bit-identical to the one-at-a-time loop
+    o.depth = max(1, int(cfg.this_main.get("batches_in_flight", 3)))
+    # this_main.fused_input_stage (default "auto"): uint8 in, tokens out -- the resize / crop / normalise of the
+    # input stage happens inside the patch-embedding launch and no processed fp32 image is written.  The writers' image_query / image_reference
+    # outputs (on by default, as in the reference's config) ARE that processed image, so "auto" takes the one-pass form only when neither is
+    # written, and only for geometries it holds (cs_u8_input_supported); True insists, False never.  Results are bit-identical either way.
+    o.fused = cfg.this_main.get("fused_input_stage", "auto")
+    return o
+
+
+def start(cfg, o: SimpleNamespace) -> None:
+    """Seeds, process group and device of the run: o.rank, o.local_rank, o.world, o.device.  The seeding comes before the driver indexes its
+    items: with neighbour_config.deterministic=False they draw their references from numpy's global generator as the batch lists are formed."""
+    seed_everything(int(cfg.lightning.seed))
+    o.rank, o.local_rank, o.world = parallel.init_from_env()
+    o.device = torch.device("cuda", o.local_rank if o.world > 1 else 0)
+    torch.cuda.set_device(o.device)
+
+
+class Scored(NamedTuple):
+    result: Dict[str, object]  # the result keys both drivers report
+    files: list                # what the writers and the summariser wrote
+    rows: list                 # the summariser's per-image rows
+    failure: Optional[BaseException]  # what this rank's output stage raised: the driver re-raises it behind its collective
+    nonfinite: int             # non-finite score-map values over the replicas
+    operand_dtype: str
+
+
+def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: Optional[str] = None, *, calibrate: bool = False,
+          extra_files=None, decode_host=None, from_window=None, check_size=None, after_submit=None, on_consume=None) -> Scored:
+    """Scores `batches` (lists of item dictionaries; cfg.logger.<phase>.out_dir exists) and finishes the outputs.
+
+    probe_path: the first query of this rank, whose geometry decides about the one-pass input stage (None: no image to look at).
+    calibrate: at batch 0 of a run of >= 16 batches, make sure the batches in flight (at depth 1 the forward's lanes) really overlap.
+    extra_files(item) -> [(path, gray16)]: files the decode window reads beside the item's images.
+    decode_host(items, zero_ref, pool, skip) -> (decoded, extras) replaces decode_items on the host path; from_window(decoded, items) -> extras
+    picks the same extras out of the window's tensors.
+    check_size(size) may refuse a batch's processed size before anything of it is queued.
+    after_submit(ticket, items, decoded, extras, size, batch) -> state; on_consume(idx, batch, out, state) runs before the summariser and writer."""
+    phase, device = o.phase, o.device
+    log = cfg.logger[phase]
+    net = CrossScoreNet(cfg)
+    # trainer.precision (config/default_predict.yaml:25, the reference's own key; Lightning names): "16-mixed" (default) / "16" -> IEEE
+    # half MFMA operands, "bf16-mixed" / "bf16" -> bfloat16 operands (fp32's range: for checkpoints whose activations leave the half
+    # range).  "32" / "32-true" have no counterpart here (the MFMA operands are 16 bits wide; everything else is fp32 already) and
+    # select the more accurate of the two, half.  An explicit model.backbone.operand_dtype wins.
+    if "operand_dtype" not in cfg.model.backbone:
+        net.operand_dtype = "bf16" if str(cfg.trainer.precision).startswith("bf16") else "fp16"
+    if state_dict is None:
+        if cfg.trainer.ckpt_path_to_load is not None:
+            state_dict = load_lightning_checkpoint(cfg.trainer.ckpt_path_to_load)
+        else:  # the reference would start from the hub's DINOv2 weights + a random decoder; there is no hub here
+            print(f"[crossscore_amd.{DRIVER[phase]}] no checkpoint: seeded synthetic weights (scores are meaningless)", file=sys.stderr)
+            state_dict = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(net.arch, int(cfg.lightning.seed)).items()}
+    net.load_state_dict(state_dict, strict=True)
+    net = net.to(device)
+
+    writer = (BatchWriter(cfg, phase, net.img_mean_std, device, workers=max(1, int(cfg.data.loader.validation.num_workers) // 2),
+                          png_encoder=o.png_encoder, png_compression=o.png_compression)
+              if log.write.flag.batch else None)
+    summariser = ScoreSummariser(cfg.model.predict.metric.type, cfg.model.predict.metric.min, log.out_dir)
+    zero_ref = bool(cfg.data.dataset.zero_reference)
+    # Host side of the loader: the file lists of all batches are fixed up front, images are decoded by `num_workers` threads, and the next
+    # batch is decoded while the GPU scores this one.
+    pool = ThreadPoolExecutor(max_workers=max(1, int(cfg.data.loader.validation.num_workers)))
+    prefetch = ThreadPoolExecutor(max_workers=1)
+    pipe = ForwardPipeline(net, depth=o.depth)
+    want_imgs = writer is not None and bool(log.write.flag.image_query or log.write.flag.image_reference)
+    fused_in = False
+    if o.fused not in (False, "false", "False", 0) and probe_path is not None and not want_imgs:
+        probe = read_image_u8(probe_path)
+        rs0, crop0 = stage.geometry(*probe.shape[:2])
+        fused_in = net.u8_input_supported(U8Image(None, probe.shape[0], probe.shape[1], rs0, crop0[0], crop0[1]), crop0[2:], device)
+    if o.fused in (True, "true", "True", 1) and not fused_in:
+        raise ValueError("this_main.fused_input_stage=True, but " + (f"the writers need the processed images (logger.{phase}.write.flag.image_query / "
+                         "image_reference)" if want_imgs else "this backbone / image geometry is not taken by the one-pass input stage"))
+    cache = ReferenceTokenCache(pipe, stage, keep_images=bool(writer is not None and log.write.flag.image_reference),
+                                max_images=o.cache_max_images, from_u8=fused_in) if o.use_cache else None
+    decoder = PngDecoder(device, pool, png=o.png_decoder == "gpu", jpeg=o.jpeg_decoder == "gpu") if "gpu" in (o.png_decoder, o.jpeg_decoder) else None
+    window = DecodeWindow(decoder, plan_decodes(batches, zero_ref, cache is not None, extra_files), o.decode_window) if decoder is not None else None
+
+    def decode(i, skip):
+        """(decoded images of batch i, the driver's extras), on the loader's thread: {path: device tensor} from the decode window, else
+        {path: host array}"""
+        if window is not None:
+            d = window.fetch(i)
+            return d, from_window(d, batches[i]) if from_window is not None else None
+        if decode_host is not None:
+            return decode_host(batches[i], zero_ref, pool, skip)
+        return decode_items(batches[i], zero_ref, pool, skip), None
+
+    def submit_decode(i):
+        if i >= len(batches):
+            return None
+        return prefetch.submit(decode, i, {k[0] for k in cache.tokens} if cache is not None else ())  # (skip: the paths cached by now)
+
+    need_w, head_id = bool(cfg.model.need_attn_weights), int(cfg.model.need_attn_weights_head_id)
+    files, n_done = [], 0
+
+    def consume(entry):
+        ticket, batch, idx, state = entry
+        out = pipe.result(ticket)
+        if window is not None:
+            window.check(idx)  # the status words of the files this batch read: a rejected file raises here, naming its path
+        if on_consume is not None:
+            on_consume(idx, batch, out, state)
+        summariser.update(batch, out, means=out.get("score_mean_ref_cross"))  # the per-image means the head launch left (score_summariser.py:180-192)
+        if writer is not None:
+            files.extend(writer.write_out(batch, out, o.local_rank, idx))
+
+    long_run = calibrate and len(batches) >= 16
+    pending = submit_decode(0)
+    torch.cuda.synchronize(device)
+    t0 = time.perf_counter()
+    queued = []  # batches submitted and not yet consumed, oldest first: depth of them stay in flight
+    for batch_idx, its in enumerate(batches):
+        decoded, extras = pending.result()
+        if cache is None:
+            pending = submit_decode(batch_idx + 1)
+            batch, size = load_batch(its, stage, decoded, fused_in, zero_reference=zero_ref)
+            if check_size is not None:
+                check_size(size)
+            refs = batch["reference/cross/imgs"]
+            if batch_idx == 0 and long_run:  # make sure the batches in flight really overlap (pipeline.py)
+                pipe.calibrate(batch["query/img"], refs, u8=fused_in)
+                if pipe.depth == 1 and not fused_in:  # one batch at a time: then it is the forward's two lanes that have to overlap (model.py)
+                    net.calibrate_lanes(batch["query/img"], refs)
+            if fused_in:
+                ticket = pipe.submit_u8(batch["query/img"], refs, need_w, head_id, True)
+            else:
+                ticket = pipe.submit(batch["query/img"], refs, need_w, head_id, False, return_mean=True)
+        else:
+            batch, size = load_batch(its, stage, decoded, fused_in, references=False)
+            if check_size is not None:
+                check_size(size)
+            tokens, batch["reference/cross/imgs"] = cache.gather([it["reference/cross/imgs"] for it in its], decoded, size, zero_ref)
+            # (submitted after gather so that the set of cached paths is current; decoding overlaps the forward below)
+            pending = submit_decode(batch_idx + 1)
+            if batch_idx == 0 and long_run:  # the same check for the (default) cached mode
+                pipe.calibrate(batch["query/img"], tokens, cached=True, u8=fused_in)
+            ticket = (pipe.submit_cached_u8 if fused_in else pipe.submit_cached)(batch["query/img"], tokens, need_w, head_id, True)
+        state = after_submit(ticket, its, decoded, extras, tuple(size), batch) if after_submit is not None else None
+        n_done += len(its)
+        queued.append((ticket, batch, batch_idx, state))
+        while len(queued) >= pipe.depth:
+            consume(queued.pop(0))
+    while queued:
+        consume(queued.pop(0))
+    torch.cuda.synchronize(device)
+    t_loop = time.perf_counter() - t0
+    # Finish the outputs and the pools first; the driver then decides together with the other ranks.  A rank whose output stage raises must
+    # still take part in the driver's collective, or the other ranks wait in it forever: the exception is kept and the driver
+    # re-raises it behind the collective, and the files written so far are worth keeping either way.
+    failure: Optional[BaseException] = None
+    try:
+        if writer is not None:
+            writer.finish()
+        files += summariser.summarise()
+    except BaseException as exc:  # noqa: BLE001 -- re-raised by the driver, behind its collective
+        failure = exc
+    finally:
+        prefetch.shutdown()
+        pool.shutdown()
+    result = {"input_stage": "one-pass (uint8 in, tokens out)" if fused_in else "two-launch (uint8 -> fp32 image -> tokens)",
+              "png_encoder": o.png_encoder, "png_compression": o.png_compression,
+              "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
+              "png_decoder": o.png_decoder, "png_decoded": decoder.stats() if o.png_decoder == "gpu" else {"png_decoded_gpu": 0, "png_decoded_host": 0},
+              "jpeg_decoder": o.jpeg_decoder, "jpeg_decoded": decoder.jpeg_stats() if o.jpeg_decoder == "gpu" else {"jpeg_decoded_gpu": 0, "jpeg_decoded_host": 0},
+              "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}  # the whole scoring loop: input stage, forwards, output stage
+    return Scored(result, files, summariser.rows, failure, pipe.nonfinite_count(), net.operand_dtype)

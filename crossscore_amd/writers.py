@@ -31,6 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .config import this_main_choice
 
 
 def get_vrange(metric_type: str, metric_min: float, metric_max: float):
@@ -206,18 +207,12 @@ PNG_ENCODERS = ("host", "gpu")
 
 def png_encoder_choice(cfg) -> str:
     """this_main.png_encoder (this build's key): host (default) | gpu."""
-    v = cfg.this_main.get("png_encoder", "host")
-    if v not in PNG_ENCODERS:
-        raise ValueError(f"this_main.png_encoder={v!r} not supported: host | gpu")
-    return v
+    return this_main_choice(cfg, "png_encoder", PNG_ENCODERS)
 
 
 def png_compression_choice(cfg) -> str:
     """this_main.png_compression (this build's key): fast (default) | compact.  Takes effect with png_encoder=gpu only; ignored with host."""
-    v = cfg.this_main.get("png_compression", "fast")
-    if v not in PNG_COMPRESSIONS:
-        raise ValueError(f"this_main.png_compression={v!r} not supported: fast | compact")
-    return v
+    return this_main_choice(cfg, "png_compression", tuple(PNG_COMPRESSIONS))
 
 
 def save_png(path, arr: np.ndarray) -> None:

@@ -277,3 +277,33 @@ def test_output_stage_kernels_bit_exact():
         assert np.array_equal(g, wo.gray16(s, vr_i))
         c = ScoreMapEncoder(mtype, mmin, 1, "rgb", t.device)(t)
         assert np.array_equal(c, wo.rgb(score, vr_v, wo.turbo_table()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cache,fused,in_flight", [(True, "auto", 3), (False, False, 3), (False, False, 1)])
+def test_calibration_of_a_long_run_leaves_the_outputs_unchanged(tmp_path, cache, fused, in_flight):
+    """A run of >= 16 batches calibrates at its first batch (the pipeline's streams; with one batch in flight, uncached and two-launch, the forward's
+    lanes): 16 queries against the same directory holding the first 15 (no calibration) give equal rows and equal score-map bytes for those 15."""
+    from crossscore_amd.config import model_config
+    from crossscore_amd.model import CrossScoreNet
+    from crossscore_amd.predict import predict
+
+    back = "synthetic/dinov2-small-2l" if fused == "auto" else TINY
+    qd, rd = _make_scene(str(tmp_path / "data"), n_query=16, n_ref=4, h=70, w=90)
+    arch = CrossScoreNet(model_config(**{"backbone.from_pretrained": back})).arch
+    sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, 6).items()}
+    common = [f"data.dataset.query_dir={qd}", f"data.dataset.reference_dir={rd}", f"model.backbone.from_pretrained={back}",
+              "this_main.resize_short_side=56", "data.neighbour_config.cross=2", "data.neighbour_config.deterministic=True",
+              "data.loader.validation.batch_size=1", f"this_main.cache_reference_tokens={cache}", f"this_main.fused_input_stage={fused}",
+              f"this_main.batches_in_flight={in_flight}", "logger.predict.write.config.score_map_colour_mode=gray",
+              "logger.predict.write.flag.image_query=False", "logger.predict.write.flag.image_reference=False"]
+    a = predict(load_config("default_predict", common + [f"logger.predict.out_dir={tmp_path}/out_16"]), state_dict=sd, now="T")
+    os.remove(os.path.join(qd, "frame_00015.png"))  # the same directory (the rows name it), now 15 batches
+    b = predict(load_config("default_predict", common + [f"logger.predict.out_dir={tmp_path}/out_15"]), state_dict=sd, now="T")
+    assert a["input_stage"] == b["input_stage"] and a["input_stage"].startswith("one-pass" if fused == "auto" else "two-launch")
+    assert len(a["rows"]) == 16 and len(b["rows"]) == 15 and a["rows"][:15] == b["rows"]
+    maps = sorted(os.listdir(os.path.join(b["out_dir"], "batch", "score_map_ref_cross")))
+    assert len(maps) == 15 and maps == sorted(os.listdir(os.path.join(a["out_dir"], "batch", "score_map_ref_cross")))[:15]
+    for name in maps:
+        pa, pb = (os.path.join(r["out_dir"], "batch", "score_map_ref_cross", name) for r in (a, b))
+        assert open(pa, "rb").read() == open(pb, "rb").read(), name

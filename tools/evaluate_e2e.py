@@ -53,8 +53,6 @@ def _init_timed(self, *a, **k):
     self.record_timeline(True)
     spans.append(self)
 pipeline.ForwardPipeline.__init__ = _init_timed
-import crossscore_amd.evaluate as ev_mod, crossscore_amd.predict as pr_mod
-ev_mod.ForwardPipeline = pr_mod.ForwardPipeline = pipeline.ForwardPipeline
 
 # host time spent queueing the GT stage (InputStage.metric_maps): it must not wait for the forward ahead of it on the same stream
 from crossscore_amd import data as data_mod
