@@ -21,6 +21,8 @@ JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = range(4)  # cs_jpeg_info.sampling (CS_
 # status words of cs_op_jpeg_decode (CS_JPGDEC_*)
 (JPGDEC_OK, JPGDEC_BAD_FRAMING, JPGDEC_HEADER_MISMATCH, JPGDEC_BAD_TABLE, JPGDEC_BAD_CODE, JPGDEC_BAD_SYMBOL, JPGDEC_INPUT_EXHAUSTED,
  JPGDEC_BAD_RESTART) = range(8)
+JPGDEC_BAD_SCAN = 8  # cs_op_jpeg_decode_ex with JPEG_PROGRESSIVE only (CS_JPGDEC_BAD_SCAN)
+JPEG_PROGRESSIVE = 1  # flag of cs_jpeg_probe_ex / cs_jpeg_decode_workspace_bytes_ex / cs_op_jpeg_decode_ex (CS_JPEG_PROGRESSIVE)
 GTMAP_SSIM, GTMAP_MAE = 0, 1  # cs_op_gt_metric_map_u8 kinds (CS_GTMAP_*)
 
 # CsEpilogue (csrc/cs_common.h)
@@ -55,6 +57,11 @@ class CsJpegInfo(C.Structure):
     """cs_jpeg_info: what cs_jpeg_probe reads from a file's marker segments."""
     _fields_ = [("width", C.c_int), ("height", C.c_int), ("components", C.c_int), ("sampling", C.c_int), ("restart_interval", C.c_int),
                 ("entropy_offset", C.c_ulonglong)]
+
+
+class CsJpegScanInfo(C.Structure):
+    """cs_jpeg_scan_info: what cs_jpeg_probe_ex adds to cs_jpeg_info."""
+    _fields_ = [("process", C.c_int), ("scans", C.c_int), ("entropy_offset", C.c_ulonglong)]
 
 
 # every symbol include/crossscore_hip.h declares: name -> (restype, argtypes)
@@ -117,6 +124,10 @@ SYMBOLS = {
     "cs_jpeg_probe": (_i, [_vp, _sz, _vp]),
     "cs_jpeg_decode_workspace_bytes": (_sz, [_i, _i, _i, _sz]),
     "cs_op_jpeg_decode": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp, _ll, _vp, _vp, _vp]),
+    "cs_jpeg_probe_ex": (_i, [_vp, _sz, _i, _vp, _vp]),
+    "cs_jpeg_decode_workspace_bytes_ex": (_sz, [_i, _i, _i, _sz, _i]),
+    "cs_op_jpeg_decode_ex": (_i, [_vp, _vp, _vp, _sz, _i, _i, _i, _vp, _ll, _vp, _vp, _i, _vp]),
+    "cs_debug_jpeg_scan_levels": (None, [_i]),
     "cs_op_denorm_to_rgb8": (_i, [_vp, _i, _i, _i, _fp, _fp, _vp, _vp]),
     "cs_op_metric_map_u16": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "cs_op_gt_metric_map_u8": (_i, [_vp, _vp, _i, _i, _i, _ll, _i, _vp, _i, _vp]),

@@ -338,10 +338,11 @@ size_t cs_pngdec_workspace(int kind, int I, int H, int W, size_t total_file_byte
 hipError_t cs_pngdec_launch(const uint8_t* files, const unsigned long long* file_offsets, const uint32_t* file_lengths, const uint32_t* spans,
                             const uint32_t* span_offsets, size_t files_bytes, int I, int kind, int H, int W, void* pixels, long long image_stride,
                             uint32_t* status, void* workspace, hipStream_t st);
-// jpegdec.hip
-size_t cs_jpgdec_workspace(int I, int H, int W);
+// jpegdec.hip (flags: CS_JPEG_PROGRESSIVE adds jpegprog.hip's entropy launch and its workspace; levels: its schedule, 1 unless a test says 0)
+size_t cs_jpgdec_workspace(int I, int H, int W, int flags);
 hipError_t cs_jpgdec_launch(const uint8_t* files, const unsigned long long* file_offsets, const uint32_t* file_lengths, size_t files_bytes, int I,
-                            int H, int W, void* pixels, long long image_stride, uint32_t* status, void* workspace, hipStream_t st);
+                            int H, int W, void* pixels, long long image_stride, uint32_t* status, void* workspace, int flags, int levels,
+                            hipStream_t st);
 // gtmap.hip
 int cs_gtmap_max_side();
 hipError_t cs_gtmap_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, int kind, uint16_t* out,

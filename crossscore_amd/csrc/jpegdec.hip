@@ -18,62 +18,9 @@
 // Untrusted input: every read of a file is at an index below its length; the bit reader hands out zeros past the end of an interval and the
 // loops stop on "input exhausted"; the MCU and block counts come from the call's H, W and the sampling (1 or 2), never from a length in the
 // file, so coefficient stores stay inside the file's own planes; the restart table holds at most MCUs - 1 entries, which its slot has.
-#include "cs_common.h"
-
-#define CS_JPGDEC_THREADS 256
-#define CS_JPGDEC_PB 9  // bits of the primary lookup
+#include "jpeg_shared.h"
 
 namespace {
-
-// status words (include/crossscore_hip.h: CS_JPGDEC_*)
-enum { ST_OK = 0, ST_FRAMING = 1, ST_HEADER = 2, ST_TABLE = 3, ST_CODE = 4, ST_SYMBOL = 5, ST_EXHAUSTED = 6, ST_RESTART = 7 };
-
-struct JpgDecArgs {
-  const uint8_t* files;
-  const unsigned long long* file_offsets;
-  const uint32_t* file_lengths;
-  unsigned long long files_bytes;
-  int H, W;
-  uint8_t* pixels;
-  long long image_stride;
-  uint32_t* status;
-  uint32_t* info;  // workspace: 4 words per file, what the entropy stage read from it (components, luma sampling)
-  uint32_t* rst;   // workspace: rst_slot restart-marker positions per file
-  unsigned long long rst_slot;
-  int16_t* coef;  // workspace: blocks_slot * 64 coefficients per file
-  uint8_t* samples;  // workspace: blocks_slot * 64 samples per file
-  unsigned long long blocks_slot;
-};
-
-// planes of one file: component c has bw[c] x bh[c] blocks, its first at block off[c]
-struct Geometry {
-  int ncomp, hs, vs, mcux, mcuy;
-  int bw[3], bh[3];
-  uint32_t off[3], nblocks;
-};
-
-__device__ __forceinline__ Geometry geometry(int H, int W, int ncomp, int hs, int vs) {
-  Geometry g;
-  g.ncomp = ncomp; g.hs = hs; g.vs = vs;
-  g.mcux = (W + 8 * hs - 1) / (8 * hs);
-  g.mcuy = (H + 8 * vs - 1) / (8 * vs);
-  g.bw[0] = g.mcux * hs; g.bh[0] = g.mcuy * vs;
-  g.bw[1] = g.bw[2] = g.mcux; g.bh[1] = g.bh[2] = g.mcuy;
-  g.off[0] = 0;
-  g.off[1] = (uint32_t)(g.bw[0] * g.bh[0]);
-  g.off[2] = g.off[1] + (uint32_t)(g.mcux * g.mcuy);
-  g.nblocks = ncomp == 1 ? g.off[1] : g.off[2] + (uint32_t)(g.mcux * g.mcuy);
-  return g;
-}
-
-__device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// orders one wave's LDS traffic: what its lanes wrote before is what they read behind
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 struct JpgLds {
   uint16_t look[4][1 << CS_JPGDEC_PB];  // per table (DC0, DC1, AC0, AC1): symbol | length << 8, 0 = walk the canonical code
@@ -90,12 +37,14 @@ struct JpgLds {
   int status;
 };
 
+__device__ __forceinline__ Huff huff_of(JpgLds& s, int t) { return Huff{s.look[t], s.first[t], s.cnt[t], s.start[t], s.syms[t]}; }
+
+enum { ST_OTHER_PROCESS = -1 };  // parse_header: a SOF2 file in a call that has the progressive kernel behind this one
+
 enum { HD_NCOMP = 0, HD_HS, HD_VS, HD_RI, HD_SCAN, HD_TQ, HD_TD, HD_TA };  // HD_TQ / TD / TA: one byte per component
 
-__device__ __forceinline__ uint32_t be16(const uint8_t* p) { return ((uint32_t)p[0] << 8) | p[1]; }
-
 // The header, by one thread: 0 or a status.  Reads below flen only.
-__device__ int parse_header(JpgLds& s, const uint8_t* file, uint32_t flen, int H, int W) {
+__device__ int parse_header(JpgLds& s, const uint8_t* file, uint32_t flen, int H, int W, int flags) {
   if (flen < 4u || file[0] != 0xFF || file[1] != 0xD8) return ST_FRAMING;
   uint32_t pos = 2, ri = 0, qdef = 0, hdef = 0;
   int nc = 0, hs = 1, vs = 1;
@@ -131,6 +80,7 @@ __device__ int parse_header(JpgLds& s, const uint8_t* file, uint32_t flen, int H
       if (hs == 2 && W <= 4) return ST_HEADER;  // libjpeg's replication upsampler: not built
       have_sof = true;
     } else if (m >= 0xC1 && m <= 0xCF && m != 0xC4 && m != 0xC8) {
+      if (m == 0xC2 && (flags & CS_JPGDEC_PROGRESSIVE)) return ST_OTHER_PROCESS;
       return ST_HEADER;  // another process (progressive, extended, lossless, arithmetic)
     } else if (m == 0xC4) {
       uint32_t p = seg;
@@ -139,19 +89,8 @@ __device__ int parse_header(JpgLds& s, const uint8_t* file, uint32_t flen, int H
         const uint32_t tc = file[p] >> 4, th = file[p] & 15u;
         if (tc > 1u || th > 1u) return ST_TABLE;
         const int t = (int)(tc * 2u + th);
-        uint32_t total = 0, code = 0;
-        for (int l = 1; l <= 16; ++l) {
-          const uint32_t c = file[p + l];
-          s.cnt[t][l] = (uint16_t)c;
-          s.first[t][l] = code;
-          s.start[t][l] = (uint16_t)total;
-          total += c;
-          code += c;
-          if (code > (1u << l)) return ST_TABLE;  // more codes than the length allows
-          code <<= 1;
-        }
-        if (total > 256u || 17u + total > send - p) return ST_TABLE;
-        for (uint32_t j = 0; j < total; ++j) s.syms[t][j] = file[p + 17 + j];
+        uint32_t total = 0;
+        if (huff_define(huff_of(s, t), file, p, send, &total)) return ST_TABLE;
         s.nsym[t] = (uint16_t)total;
         hdef |= 1u << t;
         p += 17u + total;
@@ -196,105 +135,7 @@ __device__ int parse_header(JpgLds& s, const uint8_t* file, uint32_t flen, int H
   }
 }
 
-// The bit reader of one wave: wave-uniform state.  bb holds nb valid bits, the next one at bit nb - 1; the last `fake` of them are zeros handed
-// out behind the end of the interval (a marker, or `end`).
-struct Bits {
-  unsigned long long bb;
-  int nb, fake;
-  uint32_t pos, end, flen, wbase;
-  bool eof;
-  const uint8_t* file;
-  uint32_t* win;
-};
-
-__device__ __forceinline__ void load_window(Bits& r, int lane) {
-  wave_sync();
-  uint32_t w = 0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t idx = r.wbase + 4u * (uint32_t)lane + (uint32_t)j;
-    if (idx < r.flen) w |= (uint32_t)r.file[idx] << (8 * j);
-  }
-  r.win[lane] = w;
-  wave_sync();
-}
-
-__device__ __forceinline__ uint32_t window_word(Bits& r, uint32_t p, int lane) {  // the aligned word that holds byte p
-  if (p - r.wbase >= 256u) {
-    r.wbase = p & ~3u;
-    load_window(r, lane);
-  }
-  return rfl(r.win[(p - r.wbase) >> 2]);
-}
-
-__device__ __forceinline__ uint32_t get_byte(Bits& r, uint32_t p, int lane) { return (window_word(r, p, lane) >> (8u * (p & 3u))) & 255u; }
-
-__device__ __forceinline__ void start_interval(Bits& r, uint32_t start, uint32_t end, int lane) {
-  r.bb = 0; r.nb = 0; r.fake = 0; r.pos = start; r.end = end; r.eof = false;
-  r.wbase = start & ~3u;
-  load_window(r, lane);
-}
-
-// at least 57 valid bits afterwards
-__device__ __forceinline__ void refill(Bits& r, int lane) {
-  if (r.nb <= 32 && !r.eof && (r.pos & 3u) == 0u && r.end - r.pos >= 4u && r.pos < r.end) {
-    const uint32_t w = window_word(r, r.pos, lane);
-    const uint32_t t = ~w;
-    if (((t - 0x01010101u) & ~t & 0x80808080u) == 0u) {  // no FF among the four bytes
-      r.bb = (r.bb << 32) | (unsigned long long)__builtin_bswap32(w);
-      r.nb += 32;
-      r.pos += 4u;
-    }
-  }
-  while (r.nb <= 56) {
-    if (r.eof || r.pos >= r.end) {
-      r.eof = true;
-      r.bb <<= 8;
-      r.nb += 8;
-      r.fake += 8;
-      continue;
-    }
-    const uint32_t b = get_byte(r, r.pos, lane);
-    if (b == 0xFFu) {
-      const uint32_t b2 = r.pos + 1u < r.end ? get_byte(r, r.pos + 1u, lane) : 0xFFu;
-      if (b2 != 0u) { r.eof = true; continue; }  // a marker: the interval's data ends here
-      r.pos += 2u;
-    } else {
-      r.pos += 1u;
-    }
-    r.bb = (r.bb << 8) | (unsigned long long)b;
-    r.nb += 8;
-  }
-}
-
-__device__ __forceinline__ uint32_t take(Bits& r, int n) {  // n <= 16 bits that refill() has made available
-  r.nb -= n;
-  return (uint32_t)(r.bb >> r.nb) & ((1u << n) - 1u);
-}
-
-// one symbol of table t: the primary lookup, else the canonical walk.  -1: the next 16 bits are no code of the table.
-__device__ __forceinline__ int decode_sym(const JpgLds& s, Bits& r, int t) {
-  const uint32_t w16 = (uint32_t)(r.bb >> (r.nb - 16)) & 0xffffu;
-  const uint32_t e = rfl(s.look[t][w16 >> (16 - CS_JPGDEC_PB)]);
-  if (e) {
-    r.nb -= (int)(e >> 8);
-    return (int)(e & 255u);
-  }
-  for (int l = CS_JPGDEC_PB + 1; l <= 16; ++l) {
-    const uint32_t code = w16 >> (16 - l);
-    const uint32_t f = rfl(s.first[t][l]), c = rfl(s.cnt[t][l]);
-    if (code >= f && code - f < c) {
-      r.nb -= l;
-      return (int)rfl(s.syms[t][rfl(s.start[t][l]) + (code - f)]);
-    }
-  }
-  return -1;
-}
-
-__device__ __forceinline__ int extend(uint32_t v, int n) { return v < (1u << (n - 1)) ? (int)v - (1 << n) + 1 : (int)v; }
-__device__ __forceinline__ int sat16(int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
-
-__global__ __launch_bounds__(CS_JPGDEC_THREADS) void jpeg_entropy_kernel(JpgDecArgs a) {
+__global__ __launch_bounds__(CS_JPGDEC_THREADS) void jpeg_entropy_kernel(CsJpgDecArgs a) {
   __shared__ __attribute__((aligned(16))) JpgLds s;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -306,35 +147,20 @@ __global__ __launch_bounds__(CS_JPGDEC_THREADS) void jpeg_entropy_kernel(JpgDecA
   const bool framed = flen >= 4u && flen < (1u << 28) && foff <= a.files_bytes && (unsigned long long)flen <= a.files_bytes - foff;
   const uint8_t* file = a.files + (framed ? foff : 0ull);
 
-  if (tid < 64) {
-    const uint8_t zz[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-                            35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-    s.zz[tid] = zz[tid];
-  }
+  zigzag_to_lds(s.zz, tid);
   for (int k = tid; k < 4 * (1 << CS_JPGDEC_PB); k += CS_JPGDEC_THREADS) (&s.look[0][0])[k] = 0;
   if (tid < 4) s.nsym[tid] = 0;
   if (tid == 0) s.status = ST_OK;
   __syncthreads();
 
   // ---- the header: tables into LDS
-  if (tid == 0) s.status = framed ? parse_header(s, file, flen, a.H, a.W) : ST_FRAMING;
+  if (tid == 0) s.status = framed ? parse_header(s, file, flen, a.H, a.W, a.flags) : ST_FRAMING;
   __syncthreads();
   if (s.status != ST_OK) {  // uniform over the workgroup
-    if (tid == 0) a.status[img] = (uint32_t)s.status;
+    if (tid == 0) a.status[img] = s.status == ST_OTHER_PROCESS ? CS_JPGDEC_PENDING : (uint32_t)s.status;  // pending: jpegprog.hip's file
     return;
   }
-  for (int t = 0; t < 4; ++t) {
-    const int n = s.nsym[t];
-    for (int j = tid; j < n; j += CS_JPGDEC_THREADS) {
-      int l = 1;
-      while (l < 16 && j >= (int)s.start[t][l] + (int)s.cnt[t][l]) ++l;
-      if (l <= CS_JPGDEC_PB) {
-        const uint32_t code = s.first[t][l] + (uint32_t)(j - (int)s.start[t][l]);
-        const uint32_t lo = code << (CS_JPGDEC_PB - l), span = 1u << (CS_JPGDEC_PB - l);
-        for (uint32_t k = 0; k < span && lo + k < (1u << CS_JPGDEC_PB); ++k) s.look[t][lo + k] = (uint16_t)(s.syms[t][j] | ((uint32_t)l << 8));
-      }
-    }
-  }
+  for (int t = 0; t < 4; ++t) huff_fill_lookup(huff_of(s, t), s.nsym[t], tid, CS_JPGDEC_THREADS);
   __syncthreads();
 
   const Geometry g = geometry(a.H, a.W, (int)s.hdr[HD_NCOMP], (int)s.hdr[HD_HS], (int)s.hdr[HD_VS]);
@@ -348,39 +174,8 @@ __global__ __launch_bounds__(CS_JPGDEC_THREADS) void jpeg_entropy_kernel(JpgDecA
   // ---- the restart markers, in file order: count and numbering before anything is decoded
   if (nint > 1u) {
     uint32_t count = 0;
-    int misnumbered = 0, par = 0;
-    for (uint32_t base = scan; base < flen; base += CS_JPGDEC_THREADS, par ^= 1) {
-      const uint32_t i = base + (uint32_t)tid;
-      const uint32_t b0 = i < flen ? file[i] : 0u, b1 = i + 1u < flen && i + 1u > i ? file[i + 1u] : 0u;
-      const bool is_rst = b0 == 0xFFu && (b1 & 0xF8u) == 0xD0u;
-      const bool is_term = b0 == 0xFFu && b1 != 0u && b1 != 0xFFu && !is_rst;
-      unsigned long long mr = __ballot(is_rst);
-      const unsigned long long mt = __ballot(is_term);
-      uint32_t term = 0xffffffffu;
-      if (mt) {
-        const int f = __ffsll((long long)mt) - 1;
-        mr &= (1ull << f) - 1ull;
-        term = base + 64u * (uint32_t)wave + (uint32_t)f;
-      }
-      if (lane == 0) { s.wcnt[par][wave] = (uint32_t)__popcll(mr); s.wterm[par][wave] = term; }
-      __syncthreads();
-      uint32_t tpos = 0xffffffffu, before = count, all = count;
-      for (int w = 0; w < 4; ++w) {
-        tpos = min(tpos, s.wterm[par][w]);
-        const uint32_t c = (base + 64u * (uint32_t)w > tpos) ? 0u : s.wcnt[par][w];
-        if (w < wave) before += c;
-        all += c;
-      }
-      if (is_rst && i < tpos) {
-        const uint32_t idx = before + (uint32_t)__popcll(mr & ((1ull << lane) - 1ull));
-        if (idx < nint - 1u) {
-          rst[idx] = i;
-          if (((b1 - 0xD0u) & 7u) != (idx & 7u)) misnumbered = 1;
-        }
-      }
-      count = all;
-      if (tpos != 0xffffffffu) { scan_end = tpos; break; }  // uniform: every thread sees the same tpos
-    }
+    int misnumbered = 0;
+    restart_positions(file, flen, scan, nint, rst, s.wcnt, s.wterm, tid, lane, wave, scan_end, count, misnumbered);
     if (misnumbered || count != nint - 1u) atomicCAS(&s.status, ST_OK, ST_RESTART);
     __syncthreads();
     if (s.status != ST_OK) {
@@ -416,7 +211,7 @@ __global__ __launch_bounds__(CS_JPGDEC_THREADS) void jpeg_entropy_kernel(JpgDecA
             blk[lane] = 0;
             wave_sync();
             refill(r, lane);
-            int sym = decode_sym(s, r, td);
+            int sym = decode_sym(huff_of(s, td), r);
             if (sym < 0) st = ST_CODE;
             else if (sym > 11) st = ST_SYMBOL;
             else if (sym) pred[c] += extend(take(r, sym), sym);
@@ -424,7 +219,7 @@ __global__ __launch_bounds__(CS_JPGDEC_THREADS) void jpeg_entropy_kernel(JpgDecA
             int kk = 1;
             while (kk < 64 && !st) {
               refill(r, lane);
-              sym = decode_sym(s, r, ta);
+              sym = decode_sym(huff_of(s, ta), r);
               if (sym < 0) { st = ST_CODE; break; }
               const int run = sym >> 4, size = sym & 15;
               if (size == 0) {
@@ -483,7 +278,7 @@ __device__ __forceinline__ void idct8(const uint32_t c[8], uint32_t o[8]) {
 
 __device__ __forceinline__ uint32_t descale(uint32_t x, int n) { return (uint32_t)((int32_t)(x + (1u << (n - 1))) >> n); }
 
-__global__ __launch_bounds__(CS_JPGDEC_THREADS) void jpeg_idct_kernel(JpgDecArgs a) {
+__global__ __launch_bounds__(CS_JPGDEC_THREADS) void jpeg_idct_kernel(CsJpgDecArgs a) {
   __shared__ uint32_t ws[32][65];  // 32 blocks between the passes, padded against bank conflicts
   const int img = blockIdx.y;
   if (a.status[img] != 0u) return;  // uniform over the workgroup
@@ -544,7 +339,7 @@ __device__ __forceinline__ int chroma_at(const uint8_t* p, int pitch, int rows, 
   return (3 * sj + (3 * in[j - 1] + ot[j - 1]) + 8) >> 4;
 }
 
-__global__ __launch_bounds__(CS_JPGDEC_THREADS) void jpeg_pixels_kernel(JpgDecArgs a) {
+__global__ __launch_bounds__(CS_JPGDEC_THREADS) void jpeg_pixels_kernel(CsJpgDecArgs a) {
   const int img = blockIdx.y;
   if (a.status[img] != 0u) return;
   const unsigned long long idx = (unsigned long long)blockIdx.x * CS_JPGDEC_THREADS + threadIdx.x;
@@ -578,14 +373,17 @@ static size_t jpgdec_blocks(int H, int W) { return 12 * (size_t)((H + 15) / 16) 
 static size_t jpgdec_rst_slot(int H, int W) { return (((size_t)((H + 7) / 8) * (size_t)((W + 7) / 8)) + 3) & ~(size_t)3; }
 static size_t round16(size_t v) { return (v + 15) & ~(size_t)15; }
 
-size_t cs_jpgdec_workspace(int I, int H, int W) {
+// flags & CS_JPGDEC_PROGRESSIVE: behind everything else, one restart table per scan of each file (its size from H, W, I alone)
+size_t cs_jpgdec_workspace(int I, int H, int W, int flags) {
   if (I <= 0 || H <= 0 || W <= 0) return 0;
-  return round16((size_t)I * 16) + (size_t)I * jpgdec_rst_slot(H, W) * 4 + (size_t)I * jpgdec_blocks(H, W) * (128 + 64);
+  const size_t base = round16((size_t)I * 16) + (size_t)I * jpgdec_rst_slot(H, W) * 4 + (size_t)I * jpgdec_blocks(H, W) * (128 + 64);
+  return base + ((flags & CS_JPGDEC_PROGRESSIVE) ? (size_t)I * CS_JPGDEC_MAX_SCANS * jpgdec_rst_slot(H, W) * 4 : 0);
 }
 
 hipError_t cs_jpgdec_launch(const uint8_t* files, const unsigned long long* file_offsets, const uint32_t* file_lengths, size_t files_bytes, int I,
-                            int H, int W, void* pixels, long long image_stride, uint32_t* status, void* workspace, hipStream_t st) {
-  JpgDecArgs a;
+                            int H, int W, void* pixels, long long image_stride, uint32_t* status, void* workspace, int flags, int levels,
+                            hipStream_t st) {
+  CsJpgDecArgs a;
   a.files = files; a.file_offsets = file_offsets; a.file_lengths = file_lengths; a.files_bytes = files_bytes;
   a.H = H; a.W = W;
   a.pixels = (uint8_t*)pixels; a.image_stride = image_stride; a.status = status;
@@ -599,7 +397,14 @@ hipError_t cs_jpgdec_launch(const uint8_t* files, const unsigned long long* file
   a.coef = (int16_t*)w;
   w += (size_t)I * a.blocks_slot * 128;
   a.samples = w;
+  w += (size_t)I * a.blocks_slot * 64;
+  a.flags = flags; a.levels = levels;
+  a.scan_rst = (flags & CS_JPGDEC_PROGRESSIVE) ? (uint32_t*)w : nullptr;
   hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(I), dim3(CS_JPGDEC_THREADS), 0, st, a);
+  if (flags & CS_JPGDEC_PROGRESSIVE) {  // each file goes to the entropy kernel of its own process
+    const hipError_t e = cs_jpgprog_launch(a, I, st);
+    if (e != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((a.blocks_slot + 31) / 32), I), dim3(CS_JPGDEC_THREADS), 0, st, a);
   hipLaunchKernelGGL(jpeg_pixels_kernel, dim3((unsigned)(((size_t)H * W + CS_JPGDEC_THREADS - 1) / CS_JPGDEC_THREADS), I), dim3(CS_JPGDEC_THREADS), 0, st, a);
   return hipGetLastError();

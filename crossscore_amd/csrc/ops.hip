@@ -403,34 +403,64 @@ int cs_op_png_decode(const uint8_t* files, const uint64_t* file_offsets, const u
 }
 
 // ---- JPEG decoder (jpegdec.hip): the host probe (jpeg_probe.h), the workspace size and the launches
-int cs_jpeg_probe(const uint8_t* file, size_t n, cs_jpeg_info* info) {
-  if (!file || !info) return fail(CS_ERR_BAD_ARG, "jpeg_probe: null pointer");
-  cs_jpeg_probe_result r;
-  char why[256];
-  const int rc = cs_jpeg_probe_walk(file, n, &r, why, sizeof why);
+static int jpeg_probe_result(int rc, const cs_jpeg_probe_result& r, const cs_jpeg_probe_scans& x, const char* why, cs_jpeg_info* info,
+                             cs_jpeg_scan_info* scans) {
   info->width = r.width; info->height = r.height; info->components = r.components; info->sampling = r.sampling;
   info->restart_interval = r.restart_interval; info->entropy_offset = r.entropy_offset;
+  if (scans) { scans->process = x.process; scans->scans = x.scans; scans->entropy_offset = x.entropy_offset; }
   if (rc != CS_JPEG_PROBE_OK) return fail(rc == CS_JPEG_PROBE_BAD_ARG ? CS_ERR_BAD_ARG : CS_ERR_UNSUPPORTED, "%s", why);
   return 0;
 }
 
-size_t cs_jpeg_decode_workspace_bytes(int I, int H, int W, size_t total_file_bytes) {
-  if (H <= 0 || W <= 0 || I <= 0 || I > 65535 || total_file_bytes == 0 || !cs_png_size_supported(H, W)) return 0;
-  return cs_jpgdec_workspace(I, H, W);
+int cs_jpeg_probe(const uint8_t* file, size_t n, cs_jpeg_info* info) {
+  if (!file || !info) return fail(CS_ERR_BAD_ARG, "jpeg_probe: null pointer");
+  cs_jpeg_probe_result r;
+  cs_jpeg_probe_scans x;
+  char why[256];
+  const int rc = cs_jpeg_probe_walk_ex(file, n, 0, &r, &x, why, sizeof why);
+  return jpeg_probe_result(rc, r, x, why, info, nullptr);
 }
 
-int cs_op_jpeg_decode(const uint8_t* files, const uint64_t* file_offsets, const uint32_t* file_lengths, size_t total_file_bytes, int I, int H,
-                      int W, void* pixels, long long image_stride_bytes, uint32_t* status, void* workspace, cs_stream stream) {
+int cs_jpeg_probe_ex(const uint8_t* file, size_t n, int flags, cs_jpeg_info* info, cs_jpeg_scan_info* scans) {
+  if (!file || !info) return fail(CS_ERR_BAD_ARG, "jpeg_probe: null pointer");
+  if (flags & ~CS_JPEG_PROGRESSIVE) return fail(CS_ERR_BAD_ARG, "jpeg_probe: unknown flags %d", flags);
+  cs_jpeg_probe_result r;
+  cs_jpeg_probe_scans x;
+  char why[256];
+  const int rc = cs_jpeg_probe_walk_ex(file, n, flags, &r, &x, why, sizeof why);
+  return jpeg_probe_result(rc, r, x, why, info, scans);
+}
+
+size_t cs_jpeg_decode_workspace_bytes_ex(int I, int H, int W, size_t total_file_bytes, int flags) {
+  if (H <= 0 || W <= 0 || I <= 0 || I > 65535 || total_file_bytes == 0 || !cs_png_size_supported(H, W) || (flags & ~CS_JPEG_PROGRESSIVE)) return 0;
+  return cs_jpgdec_workspace(I, H, W, flags);
+}
+
+size_t cs_jpeg_decode_workspace_bytes(int I, int H, int W, size_t total_file_bytes) {
+  return cs_jpeg_decode_workspace_bytes_ex(I, H, W, total_file_bytes, 0);
+}
+
+static int g_jpeg_scan_levels = 1;
+void cs_debug_jpeg_scan_levels(int on) { g_jpeg_scan_levels = on ? 1 : 0; }
+
+int cs_op_jpeg_decode_ex(const uint8_t* files, const uint64_t* file_offsets, const uint32_t* file_lengths, size_t total_file_bytes, int I, int H,
+                         int W, void* pixels, long long image_stride_bytes, uint32_t* status, void* workspace, int flags, cs_stream stream) {
   if (I <= 0 || I > 65535 || H <= 0 || W <= 0) return fail(CS_ERR_BAD_ARG, "jpeg_decode: bad sizes (I %d, H %d, W %d; 1 <= I <= 65535)", I, H, W);
   if (H > 4096 || W > 4096) return fail(CS_ERR_UNSUPPORTED, "jpeg_decode: %d x %d is larger than 4096 x 4096", H, W);
+  if (flags & ~CS_JPEG_PROGRESSIVE) return fail(CS_ERR_BAD_ARG, "jpeg_decode: unknown flags %d", flags);
   const long long image_bytes = (long long)H * W * 3;
   if (image_stride_bytes < image_bytes) return fail(CS_ERR_BAD_ARG, "jpeg_decode: image stride %lld is below the image's %lld bytes", image_stride_bytes, image_bytes);
   if (total_file_bytes == 0 || total_file_bytes >= ((size_t)1 << 40)) return fail(CS_ERR_BAD_ARG, "jpeg_decode: %zu file bytes (1 .. 2^40 - 1)", total_file_bytes);
   if (!files || !file_offsets || !file_lengths || !pixels || !status || !workspace) return fail(CS_ERR_BAD_ARG, "jpeg_decode: null pointer");
   if ((uintptr_t)workspace & 15) return fail(CS_ERR_BAD_ARG, "jpeg_decode: the workspace must be 16-byte aligned");
   HIPCHK(cs_jpgdec_launch(files, (const unsigned long long*)file_offsets, file_lengths, total_file_bytes, I, H, W, pixels, image_stride_bytes, status,
-                          workspace, (hipStream_t)stream));
+                          workspace, flags, g_jpeg_scan_levels, (hipStream_t)stream));
   return 0;
+}
+
+int cs_op_jpeg_decode(const uint8_t* files, const uint64_t* file_offsets, const uint32_t* file_lengths, size_t total_file_bytes, int I, int H,
+                      int W, void* pixels, long long image_stride_bytes, uint32_t* status, void* workspace, cs_stream stream) {
+  return cs_op_jpeg_decode_ex(files, file_offsets, file_lengths, total_file_bytes, I, H, W, pixels, image_stride_bytes, status, workspace, 0, stream);
 }
 
 int cs_op_denorm_to_rgb8(const float* chw, int I, int H, int W, const float* mean3, const float* std3, uint8_t* out, cs_stream stream) {

@@ -8,7 +8,7 @@ The pixel work (x/255, antialiased resize, crop, normalise) runs on the GPU thro
 uint8 image; PNG/JPEG decoding stays on the host (PIL, as in utils/io/images.py:26-29) unless this_main.png_decoder=gpu hands the PNG files
 and / or this_main.jpeg_decoder=gpu the baseline JPEG files to PngDecoder (cs_op_png_decode, cs_op_jpeg_decode: the compressed bytes go up and
 the decoded images appear in device memory, the pixels PIL gives, bit for bit).  Files neither device decoder takes (interlaced or palette PNG,
-progressive / CMYK / Adobe JPEG, ...) still go through PIL.
+progressive / CMYK / Adobe JPEG, ...) still go through PIL; this_main.jpeg_progressive=gpu adds complete progressive files (cs_op_jpeg_decode_ex).
 """
 from __future__ import annotations
 
@@ -106,12 +106,21 @@ def png_decoder_choice(cfg) -> str:
 
 
 JPGDEC_STATUS = ("ok", "bad framing (SOI, a segment length past the file, no SOF / SOS)", "SOF differs from the size asked for, or a form the decoder does not take",
-                 "bad Huffman or quantisation table", "bits that are no code of the table", "invalid symbol", "input exhausted", "missing, misnumbered or surplus restart marker")
+                 "bad Huffman or quantisation table", "bits that are no code of the table", "invalid symbol", "input exhausted", "missing, misnumbered or surplus restart marker",
+                 "illegal scan, DQT / DRI behind the first scan, or an incomplete progression")
 
 
 def jpeg_decoder_choice(cfg) -> str:
     """this_main.jpeg_decoder (this build's key): host (default) | gpu."""
     return this_main_choice(cfg, "jpeg_decoder", PNG_DECODERS)
+
+
+def jpeg_progressive_choice(cfg) -> str:
+    """this_main.jpeg_progressive (this build's key): host (default) | gpu.  gpu needs this_main.jpeg_decoder=gpu."""
+    choice = this_main_choice(cfg, "jpeg_progressive", PNG_DECODERS)
+    if choice == "gpu" and jpeg_decoder_choice(cfg) != "gpu":
+        raise ValueError("this_main.jpeg_progressive=gpu needs this_main.jpeg_decoder=gpu: the progressive files join the device decoder's calls")
+    return choice
 
 
 def png_decode_window_choice(cfg) -> int:
@@ -142,10 +151,15 @@ def probe_png(data: bytes):
     return info, spans
 
 
-def probe_jpeg(data: bytes):
-    """cs_jpeg_probe on a file's bytes: (info, None) when the device decoder takes the file, else (None, reason)."""
+def probe_jpeg(data: bytes, progressive: bool = False):
+    """cs_jpeg_probe on a file's bytes: (info, None) when the device decoder takes the file, else (None, reason).  progressive=True is
+    cs_jpeg_probe_ex with CS_JPEG_PROGRESSIVE: complete progressive files are taken too, and the first element is then (info, scan info)."""
     lib = _lib.load()
     info = _lib.CsJpegInfo()
+    if progressive:
+        scans = _lib.CsJpegScanInfo()
+        rc = lib.cs_jpeg_probe_ex(bytes(data), len(data), _lib.JPEG_PROGRESSIVE, C.byref(info), C.byref(scans))
+        return ((info, scans), None) if rc == _lib.CS_OK else (None, _lib.last_error())
     rc = lib.cs_jpeg_probe(bytes(data), len(data), C.byref(info))
     if rc != _lib.CS_OK:
         return None, _lib.last_error()
@@ -197,12 +211,20 @@ class PngDecoder:
     jpeg=True (this_main.jpeg_decoder=gpu) adds baseline JPEG: a file that begins FF D8 (sniffed by content, as PIL does, not by its name) and
     passes cs_jpeg_probe is grouped by (H, W) -- sampling is per file -- and decoded by cs_op_jpeg_decode through the same pinned block, event and
     status copy; a refused JPEG (progressive, CMYK, Adobe, ...) and any JPEG asked for as gray16 go through PIL as before.  Such files count in
-    jpeg_stats() and not in stats().  png=False leaves the PNG files on the host path inside the decoder."""
+    jpeg_stats() and not in stats().  png=False leaves the PNG files on the host path inside the decoder.
 
-    def __init__(self, device, pool=None, png=True, jpeg=False):
+    progressive=True (this_main.jpeg_progressive=gpu; needs jpeg=True) probes with cs_jpeg_probe_ex: a complete progressive file joins the
+    (H, W) group of the baseline files and the group goes through cs_op_jpeg_decode_ex with CS_JPEG_PROGRESSIVE.  Such files count in
+    jpeg_stats()' jpeg_decoded_gpu like any JPEG decoded on the device; progressive_stats() says how many of the progressive files went where."""
+
+    def __init__(self, device, pool=None, png=True, jpeg=False, progressive=False):
+        if progressive and not jpeg:
+            raise ValueError("PngDecoder: progressive=True needs jpeg=True")
         self.device = torch.device(device)
         self.pool = pool
-        self.png, self.jpeg = bool(png), bool(jpeg)
+        self.png, self.jpeg, self.progressive = bool(png), bool(jpeg), bool(progressive)
+        self.progressive_gpu = 0
+        self.progressive_host = 0
         self.stream = torch.cuda.Stream(self.device)
         self.files_gpu = 0
         self.files_host = 0
@@ -221,10 +243,15 @@ class PngDecoder:
 
         JPEG = -1  # the group kind of cs_op_jpeg_decode, beside _lib.PNG_GRAY16 / PNG_RGB8
         jpeg_mark = object()  # in the place of a PNG's span table
+        progressive_mark = object()  # the same for a SOF2 file, with progressive=True
+        flags = _lib.JPEG_PROGRESSIVE if self.progressive else 0
 
         def load(p):
             data = read_file_bytes(p)
             if self.jpeg and data[:2] == b"\xff\xd8":
+                if self.progressive:
+                    taken = probe_jpeg(data, True)[0]
+                    return data, taken and taken[0], progressive_mark if is_progressive_jpeg(data) else jpeg_mark
                 return data, probe_jpeg(data)[0], jpeg_mark
             if not self.png:
                 return data, None, None
@@ -235,7 +262,7 @@ class PngDecoder:
         tensors: List[Optional[torch.Tensor]] = [None] * len(paths)
         groups: Dict[Tuple[int, int, int], List[int]] = {}
         host_idx = []
-        is_jpeg = [spans is jpeg_mark for _, _, spans in loaded]
+        is_jpeg = [spans is jpeg_mark or spans is progressive_mark for _, _, spans in loaded]
         for i, (data, info, spans) in enumerate(loaded):
             want = _lib.PNG_GRAY16 if kinds[i] else _lib.PNG_RGB8
             if is_jpeg[i]:
@@ -275,9 +302,10 @@ class PngDecoder:
                     base = d_block.data_ptr()
                     out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device)
                     status = torch.empty((n,), dtype=torch.int32, device=self.device)
-                    work = torch.empty((lib.cs_jpeg_decode_workspace_bytes(n, h, w, total),), dtype=torch.uint8, device=self.device)
-                    _lib.check(lib.cs_op_jpeg_decode(C.c_void_p(base), C.c_void_p(base + at_off), C.c_void_p(base + at_len), total, n, h, w,
-                                                     C.c_void_p(out.data_ptr()), h * w * 3, C.c_void_p(status.data_ptr()), C.c_void_p(work.data_ptr()), st))
+                    work = torch.empty((lib.cs_jpeg_decode_workspace_bytes_ex(n, h, w, total, flags),), dtype=torch.uint8, device=self.device)
+                    _lib.check(lib.cs_op_jpeg_decode_ex(C.c_void_p(base), C.c_void_p(base + at_off), C.c_void_p(base + at_len), total, n, h, w,
+                                                        C.c_void_p(out.data_ptr()), h * w * 3, C.c_void_p(status.data_ptr()),
+                                                        C.c_void_p(work.data_ptr()), flags, st))
                     host_status = torch.empty((n,), dtype=torch.int32, pin_memory=True)
                     host_status.copy_(status, non_blocking=True)
                     for j, i in enumerate(idx):
@@ -322,6 +350,9 @@ class PngDecoder:
         jpeg_host = sum(1 for i in host_idx if is_jpeg[i])
         self.jpeg_gpu += jpeg_gpu
         self.jpeg_host += jpeg_host
+        progressive_host = sum(1 for i in host_idx if loaded[i][2] is progressive_mark)
+        self.progressive_host += progressive_host
+        self.progressive_gpu += sum(1 for _, _, spans in loaded if spans is progressive_mark) - progressive_host
         self.files_gpu += sum(len(g) for g in groups.values()) - jpeg_gpu
         self.files_host += len(host_idx) - jpeg_host
         return PngDecodeHandle(paths, tensors, event, done, [paths[i] for i in host_idx])
@@ -332,6 +363,28 @@ class PngDecoder:
     def jpeg_stats(self) -> Dict[str, int]:
         """Files that begin FF D8, counted only with jpeg=True (without it a JPEG is one more file of stats()' host count)."""
         return {"jpeg_decoded_gpu": self.jpeg_gpu, "jpeg_decoded_host": self.jpeg_host}
+
+
+    def progressive_stats(self) -> Dict[str, int]:
+        """Of the progressive (SOF2) files seen with progressive=True: decoded on the device / left to PIL (refused by cs_jpeg_probe_ex, or asked
+        for as a 16-bit map)."""
+        return {"jpeg_progressive_gpu": self.progressive_gpu, "jpeg_progressive_host": self.progressive_host}
+
+
+def is_progressive_jpeg(data: bytes) -> bool:
+    """True when the first frame header of a JPEG file's bytes is SOF2 (a walk over the marker segments; for progressive_stats())."""
+    pos, n = 2, len(data)
+    while pos + 4 <= n and data[pos] == 0xFF:
+        m = data[pos + 1]
+        if m == 0xFF:
+            pos += 1
+        elif 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            return m == 0xC2
+        elif m == 0xDA or m in (0x00, 0x01) or 0xD0 <= m <= 0xD9:
+            return False
+        else:
+            pos += 2 + ((data[pos + 2] << 8) | data[pos + 3])
+    return False
 
 
 def batch_files(items, zero_reference: bool = False, extra=None, skip=()) -> List[Tuple[str, bool]]:

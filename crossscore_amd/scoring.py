@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import parallel, synth
-from .data import (DecodeWindow, PngDecoder, ReferenceTokenCache, decode_items, jpeg_decoder_choice, load_batch, plan_decodes,
+from .data import (DecodeWindow, PngDecoder, ReferenceTokenCache, decode_items, jpeg_decoder_choice, jpeg_progressive_choice, load_batch, plan_decodes,
                    png_decode_window_choice, png_decoder_choice, read_image_u8)
 from .model import CrossScoreNet, U8Image, load_lightning_checkpoint
 from .pipeline import ForwardPipeline
@@ -58,6 +58,9 @@ def options(cfg, phase: str) -> SimpleNamespace:
     # this_main.jpeg_decoder (default "host"): the same choice for baseline JPEG inputs (cs_op_jpeg_decode); either key set to gpu
     # builds the decoder and its window, and each format goes to the device only under its own key
     o.jpeg_decoder = jpeg_decoder_choice(cfg)
+    # this_main.jpeg_progressive (default "host"): with jpeg_decoder=gpu, complete progressive files join the device decoder's calls
+    # (cs_op_jpeg_decode_ex); gpu without jpeg_decoder=gpu is a ValueError
+    o.jpeg_progressive = jpeg_progressive_choice(cfg)
     # this_main.cache_reference_tokens (default on): every reference image goes through the encoder once per run
     # instead of once per query that samples it; the score maps are bit-identical
     o.use_cache = bool(cfg.this_main.get("cache_reference_tokens", True)) and int(cfg.data.neighbour_config.cross) > 0
@@ -143,7 +146,8 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
                          "image_reference)" if want_imgs else "this backbone / image geometry is not taken by the one-pass input stage"))
     cache = ReferenceTokenCache(pipe, stage, keep_images=bool(writer is not None and log.write.flag.image_reference),
                                 max_images=o.cache_max_images, from_u8=fused_in) if o.use_cache else None
-    decoder = PngDecoder(device, pool, png=o.png_decoder == "gpu", jpeg=o.jpeg_decoder == "gpu") if "gpu" in (o.png_decoder, o.jpeg_decoder) else None
+    decoder = PngDecoder(device, pool, png=o.png_decoder == "gpu", jpeg=o.jpeg_decoder == "gpu",
+                         progressive=o.jpeg_progressive == "gpu") if "gpu" in (o.png_decoder, o.jpeg_decoder) else None
     window = DecodeWindow(decoder, plan_decodes(batches, zero_ref, cache is not None, extra_files), o.decode_window) if decoder is not None else None
 
     def decode(i, skip):
@@ -233,5 +237,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
               "png_files": writer.stats() if writer is not None else {"png_gpu_files": 0, "png_host_files": 0},
               "png_decoder": o.png_decoder, "png_decoded": decoder.stats() if o.png_decoder == "gpu" else {"png_decoded_gpu": 0, "png_decoded_host": 0},
               "jpeg_decoder": o.jpeg_decoder, "jpeg_decoded": decoder.jpeg_stats() if o.jpeg_decoder == "gpu" else {"jpeg_decoded_gpu": 0, "jpeg_decoded_host": 0},
+              "jpeg_progressive": o.jpeg_progressive,
+              "jpeg_progressive_decoded": decoder.progressive_stats() if o.jpeg_progressive == "gpu" else {"jpeg_progressive_gpu": 0, "jpeg_progressive_host": 0},
               "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}  # the whole scoring loop: input stage, forwards, output stage
     return Scored(result, files, summariser.rows, failure, pipe.nonfinite_count(), net.operand_dtype)

@@ -3,7 +3,7 @@ reference's utils/evaluation/summarise_score_gt.py writes (utils/io/score_summar
 CSV of predict / evaluate (writers.ScoreSummariser).
 
     python -m crossscore_amd.summarise_gt --dir_in <.../res_540> --dir_out <dir> [-n workers] [-f True|False] [--fast_debug N]
-                                          [--source files|compute] [--png_decoder host|gpu] [--jpeg_decoder host|gpu]
+                                          [--source files|compute] [--png_decoder host|gpu] [--jpeg_decoder host|gpu] [--jpeg_progressive host|gpu]
 
 --source files (default) reads <iter>/metric_map/{ssim,mae}/ as the reference does; --source compute needs only renders/ and gt/ and forms the
 same numbers from the image pairs, without the maps in memory or on disk.  The device returns four exact integer sums per frame
@@ -141,7 +141,7 @@ def _block(items: Sequence, device):
 
 
 def frame_sums(frames: Sequence[Frame], source: str = "files", png_decoder: str = "host", workers: int = 16,
-               device=None, jpeg_decoder: str = "host") -> Tuple[List[Tuple[int, int, int, int]], List[Tuple[int, int]]]:
+               device=None, jpeg_decoder: str = "host", jpeg_progressive: str = "host") -> Tuple[List[Tuple[int, int, int, int]], List[Tuple[int, int]]]:
     """(sums, sizes) of the frames: per frame its four integer sums and its (H, W).  png_decoder / jpeg_decoder: who decodes the PNG / baseline JPEG
     files (data.PngDecoder when either is gpu)."""
     import torch
@@ -156,6 +156,10 @@ def frame_sums(frames: Sequence[Frame], source: str = "files", png_decoder: str 
         raise ValueError(f"png_decoder={png_decoder!r} not supported: host | gpu")
     if jpeg_decoder not in PNG_DECODERS:
         raise ValueError(f"jpeg_decoder={jpeg_decoder!r} not supported: host | gpu")
+    if jpeg_progressive not in PNG_DECODERS:
+        raise ValueError(f"jpeg_progressive={jpeg_progressive!r} not supported: host | gpu")
+    if jpeg_progressive == "gpu" and jpeg_decoder != "gpu":
+        raise ValueError("jpeg_progressive=gpu needs jpeg_decoder=gpu")
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.summarise_gt needs a GPU: the frame sums have no CPU fallback")
     device = torch.device("cuda", 0) if device is None else torch.device(device)
@@ -176,7 +180,8 @@ def frame_sums(frames: Sequence[Frame], source: str = "files", png_decoder: str 
 
     pool = ThreadPoolExecutor(max_workers=max(1, int(workers)))
     try:
-        decoder = PngDecoder(device, pool, png=png_decoder == "gpu", jpeg=jpeg_decoder == "gpu") if "gpu" in (png_decoder, jpeg_decoder) else None
+        decoder = PngDecoder(device, pool, png=png_decoder == "gpu", jpeg=jpeg_decoder == "gpu",
+                             progressive=jpeg_progressive == "gpu") if "gpu" in (png_decoder, jpeg_decoder) else None
         stream = torch.cuda.current_stream(device)
         st = C.c_void_p(stream.cuda_stream)
         groups: List[List[int]] = []  # runs of at most GROUP frames of one directory
@@ -235,7 +240,7 @@ def frame_sums(frames: Sequence[Frame], source: str = "files", png_decoder: str 
 
 
 def summarise(dir_in, dir_out, num_workers: int = 16, force: bool = False, fast_debug: int = -1, source: str = "files",
-              png_decoder: str = "host", jpeg_decoder: str = "host") -> Dict[str, object]:
+              png_decoder: str = "host", jpeg_decoder: str = "host", jpeg_progressive: str = "host") -> Dict[str, object]:
     """Writes the CSV; returns {"csv": its path or None (SKIP), "frames", "seconds"}."""
     dir_in = str(Path(dir_in).expanduser())
     res: Dict[str, object] = {"frames": 0, "seconds": 0.0}
@@ -245,7 +250,7 @@ def summarise(dir_in, dir_out, num_workers: int = 16, force: bool = False, fast_
         frames = list_frames(dir_in, source)
         if fast_debug > 0:
             frames = frames[:(fast_debug + 1) * BATCH_ROWS]
-        sums, sizes = frame_sums(frames, source, png_decoder, num_workers, jpeg_decoder=jpeg_decoder)
+        sums, sizes = frame_sums(frames, source, png_decoder, num_workers, jpeg_decoder=jpeg_decoder, jpeg_progressive=jpeg_progressive)
         res["frames"], res["seconds"] = len(frames), time.perf_counter() - t0
         return rows_from_sums(frames, sums, sizes)
 
@@ -269,6 +274,7 @@ def parse_args(argv=None):
     p.add_argument("--source", choices=SOURCES, default="files", help="files: read metric_map/; compute: form the sums from renders/ and gt/")
     p.add_argument("--png_decoder", choices=("host", "gpu"), default="host")
     p.add_argument("--jpeg_decoder", choices=("host", "gpu"), default="host", help="gpu: baseline JPEG files (captured images) are decoded on the device")
+    p.add_argument("--jpeg_progressive", choices=("host", "gpu"), default="host", help="gpu: progressive JPEG files too (needs --jpeg_decoder gpu)")
     return p.parse_args(argv)
 
 
@@ -276,7 +282,7 @@ def main(argv: Optional[Iterable[str]] = None) -> int:
     a = parse_args(None if argv is None else list(argv))
     from . import configure_runtime
     configure_runtime()
-    res = summarise(a.dir_in, a.dir_out, a.num_workers, a.force, a.fast_debug, a.source, a.png_decoder, a.jpeg_decoder)
+    res = summarise(a.dir_in, a.dir_out, a.num_workers, a.force, a.fast_debug, a.source, a.png_decoder, a.jpeg_decoder, a.jpeg_progressive)
     if res["csv"] is not None:
         rate = res["frames"] / res["seconds"] if res["seconds"] > 0 else 0.0
         print(f"[crossscore_amd.summarise_gt] {res['frames']} frames ({a.source}, png_decoder={a.png_decoder}, jpeg_decoder={a.jpeg_decoder}), {rate:.1f} frames/s -> {res['csv']}")

@@ -382,6 +382,35 @@ int cs_jpeg_probe(const uint8_t* file, size_t n, cs_jpeg_info* info);
 size_t cs_jpeg_decode_workspace_bytes(int I, int H, int W, size_t total_file_bytes);
 int cs_op_jpeg_decode(const uint8_t* files, const uint64_t* file_offsets, const uint32_t* file_lengths, size_t total_file_bytes, int I, int H,
                       int W, void* pixels, long long image_stride_bytes, uint32_t* status, void* workspace, cs_stream stream);
+/* Progressive JPEG files on the device (csrc/jpegprog.hip): the _ex forms of the three entry points above.  With
+ * flags = 0 each is the plain entry point: same results, statuses and error texts.  CS_JPEG_PROGRESSIVE adds SOF2 files:
+ * cs_jpeg_probe_ex walks such a file to its EOI and takes it when the frame-level rules above hold, it has at most 32 scans, no DQT / DRI
+ * behind the first SOS, every scan is legal by T.81 G.1.1.1.1 (a DC scan has Ss = Se = 0 and a subset of the components in frame order; an AC
+ * scan one component and 1 <= Ss <= Se <= 63; Al <= 13; Ah = 0, or Ah = Al + 1 and equal to the Al the coefficients were last coded with; no
+ * coefficient first-coded twice; AC behind the component's first DC scan -- what libjpeg only warns about is refused) and the progression is
+ * complete: at EOI every coefficient of every component is coded down to bit 0 (an incomplete file is where libjpeg's block smoothing starts,
+ * which is not built).  Anything else is CS_ERR_UNSUPPORTED with the reason; framing past n is CS_ERR_BAD_ARG.  `scans` (may be NULL) receives
+ * the process, the number of scans (1 for a baseline file) and the offset of the first scan's data.
+ * cs_op_jpeg_decode_ex with CS_JPEG_PROGRESSIVE takes baseline and progressive files of one (H, W) mixed in any order: four launches, whatever
+ * I is (the baseline entropy kernel, the progressive one -- each leaves the files of the other process at once --, then the IDCT and the pixel
+ * kernel once for the call); nothing waits for the device.  The contract is cs_op_jpeg_decode's: PIL's pixels exactly, or a status word and no
+ * pixel, and a bad file does not disturb its neighbours.  The progressive kernel walks every segment again and re-checks every rule of the
+ * probe; a violation is CS_JPGDEC_BAD_SCAN (8; a macro, the seven codes of the enum above keep their meaning).  The workspace is
+ * cs_jpeg_decode_workspace_bytes_ex(..., flags) bytes: with the flag it also holds one restart table per scan, sized from H, W, I alone.
+ * cs_debug_jpeg_scan_levels(0) makes the progressive kernel run one scan per level instead of its dependency levels (1, the default, restores
+ * them): process-wide, for tests and tools that compare the two orders; the bits are the same. */
+#define CS_JPEG_PROGRESSIVE 1
+#define CS_JPGDEC_BAD_SCAN 8 /* an illegal or a 33rd scan, DQT / DRI behind the first SOS, or an incomplete progression */
+typedef struct cs_jpeg_scan_info {
+  int process; /* 0 baseline, 1 progressive */
+  int scans;
+  unsigned long long entropy_offset; /* the first scan's data */
+} cs_jpeg_scan_info;
+int cs_jpeg_probe_ex(const uint8_t* file, size_t n, int flags, cs_jpeg_info* info, cs_jpeg_scan_info* scans);
+size_t cs_jpeg_decode_workspace_bytes_ex(int I, int H, int W, size_t total_file_bytes, int flags);
+int cs_op_jpeg_decode_ex(const uint8_t* files, const uint64_t* file_offsets, const uint32_t* file_lengths, size_t total_file_bytes, int I, int H,
+                         int W, void* pixels, long long image_stride_bytes, uint32_t* status, void* workspace, int flags, cs_stream stream);
+void cs_debug_jpeg_scan_levels(int on);
 /* de_norm_img + u8 (utils/misc/image.py:25-34, utils/io/images.py:20-23; batch_writer.py:117-135): I processed images fp32 CHW -> uint8 HWC,
  * x * std, then + mean, then * 255, each rounded on its own (no fma), truncated.  Values are clamped to [0, 255] first (NaN -> 0): that agrees
  * with the host form (a C cast) on every value the input stage produces (u8 / 255 normalised and de-normalised stays inside [0, 255]); outside
