@@ -54,20 +54,26 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ x
 // which is then streamed out as one contiguous piece.  (The gather kernel above reads 56-byte runs: 2.3 TB/s; this one 4+.)
 // With `pmean`, each patch's per-channel mean (fp32, fixed summation order) is removed before the fp16 rounding and stored as
 // pmean[row][ch]; the patch GEMM adds mean * sum(W) back in fp32 (gemm.hip patch_dc).
+// A patch row whose LDS image would not fit is cut into nch runs of near-equal length (block = (image, patch row, run)): every patch is
+// centred whatever the image's width, and a patch's values do not depend on the cut.
 template <int P>
 __global__ __launch_bounds__(256) void im2col_rows_kernel(const float* __restrict__ xq, const float* __restrict__ xr, int N, int img0,
-                                                           h16_t* __restrict__ out, int H, int W, int gh, int gw, int Kp,
+                                                           h16_t* __restrict__ out, int H, int W, int gh, int gwf, int nch, int Kp,
                                                            float* __restrict__ pmean, int bf) {
   extern __shared__ __attribute__((aligned(16))) char im_smem[];
+  const int prow = blockIdx.x / nch, run = blockIdx.x - prow * nch;
+  const int base = gwf / nch, rem = gwf - base * nch;
+  const int gw = base + (run < rem ? 1 : 0);                  // patches of this run
+  const int pj0 = run * base + (run < rem ? run : rem);       // its first patch (column index in the patch row)
   h16_t* tile = reinterpret_cast<h16_t*>(im_smem);                                   // [gw][Kp]
   const int Wu = gw * P;
   float* stage = reinterpret_cast<float*>(im_smem + (size_t)gw * Kp * sizeof(h16_t));  // [P][Wu] one channel (centring only)
   float* mean = stage + (size_t)P * Wu;                                                // [gw]
   float* part = mean + gw;                                                             // [gw][P] row sums
-  const int img = blockIdx.x / gh, pi = blockIdx.x - img * gh;
+  const int img = prow / gh, pi = prow - img * gh;
   const int g_img = img0 + img;
   const int bb = g_img / (1 + N), vv = g_img - bb * (1 + N);
-  const float* x = vv == 0 ? xq + (size_t)bb * 3 * H * W : xr + ((size_t)bb * N + (vv - 1)) * 3 * H * W;
+  const float* x = (vv == 0 ? xq + (size_t)bb * 3 * H * W : xr + ((size_t)bb * N + (vv - 1)) * 3 * H * W) + pj0 * P;
   constexpr int KK = 3 * P * P;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   for (int i = tid; i < gw * (Kp - KK); i += 256) {  // zero padding columns
@@ -103,8 +109,8 @@ __global__ __launch_bounds__(256) void im2col_rows_kernel(const float* __restric
         for (int dy = 0; dy < P; ++dy) sacc += part[tid * P + dy];
         const float mu = sacc / (float)(P * P);
         mean[tid] = mu;
-        pmean[(((size_t)img * gh + pi) * gw + tid) * 4 + ch] = mu;
-        if (ch == 0) pmean[(((size_t)img * gh + pi) * gw + tid) * 4 + 3] = 0.f;
+        pmean[(((size_t)img * gh + pi) * gwf + pj0 + tid) * 4 + ch] = mu;
+        if (ch == 0) pmean[(((size_t)img * gh + pi) * gwf + pj0 + tid) * 4 + 3] = 0.f;
       }
       __syncthreads();
       for (int dy = wv; dy < P; dy += 4)
@@ -116,7 +122,7 @@ __global__ __launch_bounds__(256) void im2col_rows_kernel(const float* __restric
     }
   }
   __syncthreads();
-  uint4* dst = reinterpret_cast<uint4*>(out + ((size_t)img * gh + pi) * gw * Kp);
+  uint4* dst = reinterpret_cast<uint4*>(out + (((size_t)img * gh + pi) * gwf + pj0) * Kp);
   const uint4* srcv = reinterpret_cast<const uint4*>(tile);
   for (int i = tid; i < gw * Kp / 8; i += 256) dst[i] = srcv[i];
 }
@@ -530,13 +536,16 @@ hipError_t cs_patch_wsum_launch(const float* w, int C, int P, float* wsum, hipSt
   return hipGetLastError();
 }
 
-// pmean: [I*gh*gw][4] fp32 or nullptr.  With pmean the patches are mean-centred; when the gather fallback has to be used the
-// means are written as zeros (nothing removed, nothing to add back).
+// pmean: [I*gh*gw][4] fp32 or nullptr.  With pmean the patches are mean-centred; only where the gather fallback has to be used (another
+// patch size) the means are written as zeros (nothing removed, nothing to add back).
 hipError_t cs_im2col_launch(const float* xq, const float* xr, int N, int img0, h16_t* out, int I, int H, int W, int P, int Kp,
                             float* pmean, int bf, hipStream_t st) {
   const int gh = H / P, gw = W / P;
-  const size_t lds = (size_t)gw * Kp * sizeof(h16_t) + (pmean ? ((size_t)P * gw * P + gw + (size_t)gw * P) * sizeof(float) : 0);
-  if (P == 14 && Kp >= 3 * P * P && lds <= 156 * 1024 && (long long)I * gh < (1ll << 31) && gw <= 256) {
+  const size_t per_patch = (size_t)Kp * sizeof(h16_t) + (pmean ? ((size_t)P * P + 1 + P) * sizeof(float) : 0);  // tile row (+ stage, mean, row sums)
+  const int fit = (int)((156 * 1024) / per_patch);           // patches whose LDS image one workgroup holds (75 centred at Kp = 640)
+  const int nch = fit > 0 ? (gw + fit - 1) / fit : 0;        // runs per patch row: 1 up to `fit` patches
+  if (P == 14 && Kp >= 3 * P * P && nch > 0 && (long long)I * gh * nch < (1ll << 31) && fit <= 256) {
+    const size_t lds = (size_t)((gw + nch - 1) / nch) * per_patch;
     static std::atomic<bool> attr_done[16];  // (zero-initialised; hipFuncSetAttribute is idempotent, a racing second caller only repeats it)  // per device
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return hipErrorInvalidDevice;
@@ -545,7 +554,7 @@ hipError_t cs_im2col_launch(const float* xq, const float* xr, int N, int img0, h
       if (e != hipSuccess) return e;
       attr_done[dev] = true;
     }
-    hipLaunchKernelGGL(im2col_rows_kernel<14>, dim3(I * gh), dim3(256), lds, st, xq, xr, N, img0, out, H, W, gh, gw, Kp, pmean, bf);
+    hipLaunchKernelGGL(im2col_rows_kernel<14>, dim3(I * gh * nch), dim3(256), lds, st, xq, xr, N, img0, out, H, W, gh, gw, nch, Kp, pmean, bf);
     return hipGetLastError();
   }
   if (pmean) {

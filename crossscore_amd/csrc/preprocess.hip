@@ -28,6 +28,12 @@ float tri(float x) {  // HelperInterpLinear::aa_filter
   return x < 1.0f ? 1.0f - x : 0.0f;
 }
 
+// _compute_indices_min_size_weights_aa with scalar_t = float.  ATen forms three expressions in float before they meet a double:
+//   center - support  and  center + support   (the bounds: each rounded to float, then + 0.5 in double, then truncated)
+//   (j + xmin) - center                       (the filter argument: rounded to float, then + 0.5 and * invscale in double)
+// Forming them in double instead moves a bound across an integer, or a weight by an ulp, at about one geometry in seven (a tap set that differs,
+// weights off by up to 1.5e-6), so the casts are written out.  tests/test_resize_tables.py reads these tables back through the kernels and
+// compares them with F.interpolate's bit for bit.
 void build_axis(int in, int out, AxisTable& t) {
   t.in = in;
   t.out = out;
@@ -40,15 +46,15 @@ void build_axis(int in, int out, AxisTable& t) {
   const float invscale = scale >= 1.0f ? 1.0f / scale : 1.0f;
   for (int i = 0; i < out; ++i) {
     const float center = (float)((double)scale * ((double)i + 0.5));
-    long long lo = (long long)((double)center - (double)support + 0.5);
+    long long lo = (long long)((double)(float)(center - support) + 0.5);
     if (lo < 0) lo = 0;
-    long long hi = (long long)((double)center + (double)support + 0.5);
+    long long hi = (long long)((double)(float)(center + support) + 0.5);
     if (hi > in) hi = in;
     const int n = (int)(hi - lo);
     float total = 0.f;
     float* wr = &t.w[(size_t)i * t.taps];
     for (int j = 0; j < n && j < t.taps; ++j) {
-      const float wv = tri((float)(((double)j + (double)lo - (double)center + 0.5) * (double)invscale));
+      const float wv = tri((float)(((double)(float)((float)(j + lo) - center) + 0.5) * (double)invscale));
       wr[j] = wv;
       total += wv;
     }

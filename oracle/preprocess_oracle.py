@@ -6,8 +6,16 @@ product path).  numpy, fp32, one function per reference step:
       -> torchvision computes (short, int(short * long / short_side)) and calls
          torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=True); the arithmetic restated here is
          ATen/native/cpu/UpSampleKernel.cpp (_compute_indices_min_size_weights_aa, separable: width pass, then height pass).
+         With scalar_t = float ATen keeps scale, support, invscale and center in float and forms three more expressions in float
+         before they meet a double:
+             center - support,  center + support     the bounds xmin / xmax: rounded to float, then + 0.5 in double, truncated
+             (j + xmin) - center                     the filter argument: rounded to float, then + 0.5 and * invscale in double
+         Until these were rounded here (they were formed in double) the tables differed from ATen's at 927 of 6 879 axis pairs
+         (a tap set that differs at 479, a weight off by up to 1.46e-6; EXPERIMENTS.md).  tests/test_resize_tables.py now holds
+         aa_axis_table bit-equal to the weights F.interpolate applies to an identity matrix over that sweep.
          torchvision is not vendored in the reference (environment.yaml pins 0.16.2) and absent here: PINNED against
-         torch 2.10 F.interpolate outputs (tests/golden/make_golden_preprocess.py -> tests/golden/p*.npz).
+         torch 2.10 F.interpolate: the tables as above, outputs by tests/test_resize_tables.py (a 2-D sweep, CPU) and by
+         tests/golden/make_golden_preprocess.py -> tests/golden/p*.npz.
   deterministic crop         dataloading/transformation/crop.py:8-25 (i = j = 0), nvs_dataset.py:227-241 (integer patches)
   T.Normalize(mean, std)     task/predict.py:68-74              (x - mean) / std
 """
@@ -37,10 +45,11 @@ def aa_axis_table(n_in: int, n_out: int):
     w = np.zeros((n_out, taps), np.float32)
     for i in range(n_out):
         center = np.float32(np.float64(scale) * (i + 0.5))
-        lo = max(int(np.float64(center) - np.float64(support) + 0.5), 0)
-        hi = min(int(np.float64(center) + np.float64(support) + 0.5), n_in)
+        lo = max(int(np.float64(np.float32(center - support)) + 0.5), 0)  # (float32 - float32 -> float32)
+        hi = min(int(np.float64(np.float32(center + support)) + 0.5), n_in)
         n = hi - lo
-        x = np.float32((np.arange(n, dtype=np.float64) + lo - np.float64(center) + 0.5) * np.float64(invscale))
+        d = (np.arange(lo, lo + n, dtype=np.int64).astype(np.float32) - center).astype(np.float32)  # float(j + xmin) - center, in float
+        x = np.float32((d.astype(np.float64) + 0.5) * np.float64(invscale))
         ww = np.maximum(np.float32(1.0) - np.abs(x), np.float32(0.0)).astype(np.float32)
         tot = np.float32(0.0)
         for v in ww:

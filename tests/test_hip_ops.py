@@ -444,12 +444,17 @@ def test_patch_embed_mean_centred_vs_fp32_conv():
 
 
 @pytest.mark.parametrize("I,H,W,Cc", [(3, 518, 518, 384), (2, 518, 686, 384), (1, 1036, 1036, 384), (2, 224, 238, 768), (1, 14, 28, 384),
-                                      (2, 75, 90, 384)])  # (trailing pixels past the last whole patch are ignored, HF:141-149)
+                                      (2, 75, 90, 384)]  # (trailing pixels past the last whole patch are ignored, HF:141-149)
+                         # one patch row of 37 / 38 / 48 patches (the LDS layout changes at 38, a run holds 48), then runs of 25+24, 48+47, 48+48, 33+32+32
+                         + [(2, 14, 14 * gw, 384) for gw in (37, 38, 48, 49, 95, 96, 97)]
+                         + [(2, 14, 14 * gw, 384) for gw in (75, 76)])  # (the last patch row the centring im2col kernel holds whole, the first it cuts)
 def test_patch_embed_one_launch_matches_two_kernel_path_and_conv(I, H, W, Cc):
     """csrc/patch.hip (strip -> centred 16-bit tile in LDS -> MFMA -> token rows) against (a) the im2col + GEMM pair it replaces -- the A
     operand has the same bits (same mean, same rounding), only the fp32 summation order of the products differs -- and (b) an fp64
     convolution (HF modeling_dinov2.py:141-149).  Shapes: the benchmark's 37-patch rows, rows cut into two runs (49 and 74 patches), a
-    two-pass width (768), a single-patch-row image; smooth images, where the mean term carries most of the value."""
+    two-pass width (768), a single-patch-row image; smooth images, where the mean term carries most of the value.  One patch row of 37 .. 97
+    patches: the one-launch form's LDS layout changes between 37 and 38 patches per run and a run holds 48; from 76 patches on the im2col
+    kernel cuts the row into runs too (until it did, it stopped centring there and this comparison missed by 3e-3)."""
     P = 14
     gh, gw = H // P, W // P
     Np = gh * gw
@@ -472,6 +477,21 @@ def test_patch_embed_one_launch_matches_two_kernel_path_and_conv(I, H, W, Cc):
     e1 = (one[:, 1:].double() - ref).abs().mean()
     e2 = (two[:, 1:].double() - ref).abs().mean()
     assert e1 < 1.05 * e2 + 1e-7 and e1 < 3e-4, (float(e1), float(e2))
+
+
+@pytest.mark.parametrize("gw", [124, 125, 251])
+def test_im2col_cuts_wide_patch_rows_into_runs(gw):
+    """The coalesced im2col kernel holds 124 patches of a row in LDS (75 when it centres: the patch-embedding test above); wider rows are
+    cut into runs of near-equal length (125 -> 63 + 62, 251 -> 84 + 84 + 83).  Every element is the image's pixel rounded to fp16, wherever
+    the cut falls; two patch rows and two images, so a run's offset into the output is checked in both directions."""
+    I, H, P, Kp = 2, 28, 14, 640
+    W = gw * P + 3  # (trailing pixels past the last whole patch are ignored)
+    x = _t(_rng(gw).standard_normal((I, 3, H, W), dtype=np.float32))
+    A = hh.im2col(x, P, Kp)
+    torch.cuda.synchronize()
+    want = x[:, :, :, :gw * P].reshape(I, 3, H // P, P, gw, P).permute(0, 2, 4, 1, 3, 5).reshape(I * (H // P) * gw, 588).half()
+    assert torch.equal(A[:, :588], want)
+    assert (A[:, 588:] == 0).all()
 
 
 def test_patch_embed_one_launch_refuses_what_it_does_not_take():

@@ -194,29 +194,135 @@ def test_patch_embedding_straight_from_uint8_is_bit_identical(h, w, short, crop,
     """SURVEY.md 8f-4 as worded (uint8 in, tokens out; task/predict.py:68-93, nvs_dataset.py:218-241): the one-pass form repeats the operations of
     cs_op_preprocess_u8 inside the patch-embedding launch, so its token rows are those of the two-launch path bit for bit -- whatever the scale,
     the crop, the row padding and the number of runs a patch row is cut into."""
+    rs = po.resized_output_size(h, w, short) if short else (h, w)
+    if crop is None:
+        crop = (0, 0, rs[0] - rs[0] % 14, rs[1] - rs[1] % 14)
+    if crop[3] % 2:
+        crop = (crop[0], crop[1], crop[2], crop[3] - 14)  # (the one-launch patch embedding takes even widths)
+    _one_pass_against_two_launches(h, w, rs, crop, pad)
+
+
+def _one_pass_against_two_launches(h, w, rs, crop, pad, bf16=False):
+    """tokens of cs_op_patch_embed_fused_u8 == tokens of cs_op_preprocess_u8 + cs_op_patch_embed_fused, two images, bit for bit"""
     import torch
     import hip_helpers as hh
+    from crossscore_amd import _lib
 
     P, Cc = 14, 384
     rng = np.random.Generator(np.random.PCG64(h * 7 + w))
     imgs = rng.integers(0, 256, size=(2, h, w, 3), dtype=np.uint8)
     imgs[1, ..., 1] = ((np.arange(h)[:, None] * 3 + np.arange(w)[None, :] * 2) % 256).astype(np.uint8)
-    rs = po.resized_output_size(h, w, short) if short else (h, w)
-    if crop is None:
-        crop = (0, 0, rs[0] - rs[0] % P, rs[1] - rs[1] % P)
-    if crop[3] % 2:
-        crop = (crop[0], crop[1], crop[2], crop[3] - P)  # (the one-launch patch embedding takes even widths)
     y0, x0, H, W = crop
     two = np.stack([_hip_preprocess(im, rs, crop, pad_row=pad) for im in imgs])
     wgt = torch.from_numpy((rng.standard_normal((Cc, 3, P, P)) / 24).astype(np.float32)).cuda()
     bias = torch.from_numpy(rng.standard_normal(Cc).astype(np.float32)).cuda()
     pos = torch.from_numpy(rng.standard_normal((1 + (H // P) * (W // P), Cc)).astype(np.float32)).cuda()
-    ref = hh.patch_embed_fused(torch.from_numpy(two).cuda(), wgt, bias, pos, P)
     buf = np.zeros((2, h, w * 3 + pad), np.uint8)
     buf[:, :, : w * 3] = imgs.reshape(2, h, w * 3)
-    got = hh.patch_embed_fused_u8(torch.from_numpy(buf).cuda(), rs, (y0, x0, H, W, w), po.IMAGENET_MEAN, po.IMAGENET_STD, wgt, bias, pos, P)
-    torch.cuda.synchronize()
+    lib = _lib.load()
+    lib.cs_debug_set_op_operand_dtype(1 if bf16 else 0)
+    try:
+        ref = hh.patch_embed_fused(torch.from_numpy(two).cuda(), wgt, bias, pos, P)
+        got = hh.patch_embed_fused_u8(torch.from_numpy(buf).cuda(), rs, (y0, x0, H, W, w), po.IMAGENET_MEAN, po.IMAGENET_STD, wgt, bias, pos, P)
+        torch.cuda.synchronize()
+    finally:
+        lib.cs_debug_set_op_operand_dtype(0)
+    assert torch.isfinite(got[1:1 + (H // P) * (W // P)]).all()
     assert torch.equal(got, ref)
+
+
+U8_TMP_BYTES, U8_MAX_RUN = 64 * 1024, 48  # csrc/patch.hip: the one-pass form's horizontal-pass buffer in LDS, patches per workgroup
+
+
+def _row_span(in_h, rs_h, crop_y, H, P=14):
+    """source rows a patch row reaches (first tap of its first pixel row .. last tap of its last), the largest over the window's patch rows"""
+    ymin, ysize, _ = po.aa_axis_table(in_h, rs_h)
+    return max(int((ymin[r0:r0 + P] + ysize[r0:r0 + P]).max() - ymin[r0]) for r0 in range(crop_y, crop_y + H - P + 1, P))
+
+
+def _u8_runs(W, span, P=14):
+    """patches per run of a patch row: as few runs as hold span source rows x run width fp32 in the buffer, of near-equal size; None: not even one patch"""
+    gw = W // P
+    for nsx in range(-(-gw // U8_MAX_RUN), gw + 1):
+        if span * -(-gw // nsx) * P * 4 <= U8_TMP_BYTES:
+            return [gw // nsx + (1 if k < gw % nsx else 0) for k in range(nsx)]
+    return None
+
+
+def _xsize_max(in_w, rs_w, crop_x, W):
+    return int(po.aa_axis_table(in_w, rs_w)[1][crop_x:crop_x + W].max())
+
+
+# name: (h, w, rs, window (y, x, H, W), pad, bf16, the property the case is there for: f(span, runs) -> bool)
+_wide = {37: [37], 38: [38], 48: [48], 49: [25, 24], 95: [48, 47], 96: [48, 48], 97: [33, 32, 32]}
+U8_EDGES = {
+    # 14 pixel rows reach all 1 170 source rows: one patch per run, the x / 255 table exactly 64 KiB into LDS
+    "at_the_limit": (1170, 60, (14, 28), (0, 0, 14, 28), 0, False, lambda span, runs: span == 1170 and runs == [1, 1] and (span * 14 * 4 + 255) // 256 * 256 == U8_TMP_BYTES),
+    "unequal_runs": (500, 120, (14, 98), (0, 0, 14, 98), 1, False, lambda span, runs: 390 < span <= 585 and runs == [2, 2, 2, 1]),
+    "unequal_runs_bf16": (500, 120, (14, 98), (0, 0, 14, 98), 1, True, lambda span, runs: runs == [2, 2, 2, 1]),
+    # the width pass keeps up to 8 weights in registers and loops over the table from 9 taps on.  A scale s reaches floor(2 s) + 1 taps (2 s when
+    # that is an integer): 343 -> 98 (3.5 x) has 7, 350 -> 98 has 8 (the register path at its limit), 393 -> 98 (4.01 x) has columns of 8 and of 9
+    # taps side by side, so both paths run in one launch
+    "taps_7": (20, 343, (14, 98), (0, 0, 14, 98), 0, False, lambda span, runs: _xsize_max(343, 98, 0, 98) == 7),
+    "register_path": (20, 350, (14, 98), (0, 0, 14, 98), 0, False, lambda span, runs: _xsize_max(350, 98, 0, 98) == 8),
+    "loop_path": (20, 393, (14, 98), (0, 0, 14, 98), 0, False, lambda span, runs: _xsize_max(393, 98, 0, 98) == 9),
+    "loop_path_bf16": (20, 393, (14, 98), (0, 0, 14, 98), 5, True, lambda span, runs: _xsize_max(393, 98, 0, 98) == 9),
+    # 3 x up: consecutive resized rows start at the same source row
+    "up_3x": (10, 20, (30, 60), (0, 0, 28, 56), 0, False, lambda span, runs: (np.diff(po.aa_axis_table(10, 30)[0][:28]) == 0).any()),
+    # the window ends on the last resized row and column: the clamped last taps
+    "bottom_right": (100, 160, (45, 72), (17, 16, 28, 56), 3, False, lambda span, runs: 17 + 28 == 45 and 16 + 56 == 72),
+}
+for _gw, _runs in _wide.items():  # no resize, one patch row: the LDS layout changes between 37 and 38 patches per run, a run holds 48
+    U8_EDGES[f"wide_{_gw}"] = (14, 14 * _gw, (14, 14 * _gw), (0, 0, 14, 14 * _gw), 0, False, lambda span, runs, want=_runs: span == 14 and runs == want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", list(U8_EDGES))
+def test_patch_embedding_straight_from_uint8_at_its_edges(name):
+    """The one-pass form where its code changes path: the largest row span it holds, runs of unequal length, 8 and 9 taps (registers / loop), an
+    up-scale, a window in the bottom-right corner, patch rows of 37 .. 97 patches.  Each case first proves, from the oracle's table, that it is
+    where it claims to be; the assertion is that of test_patch_embedding_straight_from_uint8_is_bit_identical."""
+    h, w, rs, crop, pad, bf16, prop = U8_EDGES[name]
+    span = _row_span(h, rs[0], crop[0], crop[2])
+    assert prop(span, _u8_runs(crop[3], span)), (span, _u8_runs(crop[3], span))
+    _one_pass_against_two_launches(h, w, rs, crop, pad, bf16)
+
+
+@pytest.mark.gpu
+def test_patch_embedding_straight_from_uint8_refuses_one_row_past_the_limit():
+    """1 171 source rows under one patch row do not fit even one patch per run: cs_op_patch_embed_fused_u8 says CS_ERR_UNSUPPORTED and writes
+    nothing, cs_u8_input_supported says 0 (and 1 at 1 170)."""
+    import ctypes as C
+    import torch
+    import guard
+    from crossscore_amd import _lib, synth
+    from crossscore_amd.config import model_config
+    from crossscore_amd.model import CrossScoreNet, U8Image
+
+    h, w, rs, P, Cc = 1171, 60, (14, 28), 14, 384
+    span = _row_span(h, rs[0], 0, 14)
+    assert span == 1171 and _u8_runs(28, span) is None and _u8_runs(28, span - 1) == [1, 1]
+    rng = np.random.Generator(np.random.PCG64(1171))
+    imgs = torch.from_numpy(rng.integers(0, 256, size=(2, h, w * 3), dtype=np.uint8)).cuda()
+    wgt = torch.from_numpy((rng.standard_normal((Cc, 3, P, P)) / 24).astype(np.float32)).cuda()
+    bias = torch.from_numpy(rng.standard_normal(Cc).astype(np.float32)).cuda()
+    pos = torch.from_numpy(rng.standard_normal((1 + 2, Cc)).astype(np.float32)).cuda()
+    gg = guard.guarded((2 * (1 + 2), Cc), torch.float32)
+    lib = _lib.load()
+    p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+    rc = lib.cs_op_patch_embed_fused_u8(p(imgs), 2, h, w, w * 3, rs[0], rs[1], 0, 0, 14, 28, (C.c_float * 3)(*po.IMAGENET_MEAN),
+                                        (C.c_float * 3)(*po.IMAGENET_STD), p(wgt), p(bias), p(pos), P, Cc, p(gg.view),
+                                        C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    assert rc == _lib.CS_ERR_UNSUPPORTED, (rc, _lib.last_error())
+    gg.check("refused launch")
+    assert (gg.view.view(torch.int32) == gg.sentinel).all()
+    net = CrossScoreNet(model_config(**{"backbone.from_pretrained": "synthetic/dinov2-small-2l"}))
+    net.load_numpy_state_dict(synth.make_state_dict(net.arch, 3))
+    net = net.cuda()
+    dev = torch.device("cuda:0")
+    assert not net.u8_input_supported(U8Image(None, 1171, 60, rs, 0, 0), (14, 28), dev)
+    assert net.u8_input_supported(U8Image(None, 1170, 60, rs, 0, 0), (14, 28), dev)
 
 
 @pytest.mark.gpu
