@@ -83,6 +83,13 @@ SYMBOLS = {
     "cs_encode_references_u8": (_i, [_vp, _vp, _i, _i, _i, _fp, _fp, _vp, _vp]),
     "cs_forward_cached_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _fp, _fp, _vp, _vp, _i, _vp, _vp]),
     "cs_u8_input_supported": (_i, [_vp, _vp, _i, _i]),
+    "cs_op_token_descriptors": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "cs_op_descriptor_centre": (_i, [_vp, _i, _i, _vp, _vp]),
+    "cs_op_descriptor_unit": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "cs_op_select_references": (_i, [_vp, _i, _vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "cs_op_gather_tokens": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
+    "cs_forward_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cs_forward_select_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _fp, _fp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "cs_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "cs_nonfinite_count": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "cs_forward_stats": (_i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_char_p, _sz]),

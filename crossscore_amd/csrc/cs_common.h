@@ -348,6 +348,13 @@ int cs_gtmap_max_side();
 hipError_t cs_gtmap_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, int kind, uint16_t* out,
                            int out_ld, hipStream_t st);
 hipError_t cs_gtsums_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, uint64_t* sums, hipStream_t st);
+// select.hip
+hipError_t cs_token_descriptors_launch(const h16_t* tok, int I, int Np, int C, int bf, float* mean, hipStream_t st);
+hipError_t cs_descriptor_centre_launch(const float* mean, int R, int C, float* centre, hipStream_t st);
+hipError_t cs_descriptor_unit_launch(const float* mean, int I, int C, const float* centre, float* unit, hipStream_t st);
+hipError_t cs_similarity_launch(const float* q, int B, const float* bank, int R, int C, float* sim, hipStream_t st);
+hipError_t cs_topn_launch(const float* sim, int B, int R, const int32_t* exclude, int N, int32_t* index, hipStream_t st);
+hipError_t cs_gather_tokens_launch(const h16_t* bank, int R, int Np, int C, const int32_t* index, int slots, h16_t* out, hipStream_t st);
 // gtsum.hip
 hipError_t cs_metric_map_sums_launch(const uint16_t* ssim, const uint16_t* mae, int B, int H, int W, int row_elems, long long image_stride,
                                      uint64_t* sums, hipStream_t st);

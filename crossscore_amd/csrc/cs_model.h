@@ -121,6 +121,16 @@ inline int ffn_hidden(const cs_config& c) {
   return c.swiglu ? ((int)((double)f * 2 / 3) + 7) / 8 * 8 : f;
 }
 
+// the sizes cs_op_select_references and cs_forward_select take: B queries against a bank of R unit descriptors C wide, N picks per query.  The
+// exclusions live on the device, so with an `exclude` array every query may carry one and only R - 1 entries count as eligible.
+inline int select_check(int B, int R, int C, int N, bool has_exclude) {
+  if (B <= 0 || R <= 0 || C <= 0 || N <= 0) return fail(CS_ERR_BAD_ARG, "select_references: empty batch, bank or selection");
+  if (N > 32 || R > 65536 || C % 4 || B > 65535) return fail(CS_ERR_UNSUPPORTED, "select_references: built for N <= 32, R <= 65536, C a multiple of 4 (N %d, R %d, C %d)", N, R, C);
+  if (N > R - (has_exclude ? 1 : 0))
+    return fail(CS_ERR_BAD_ARG, "select_references: N = %d exceeds the %d eligible bank entries (R = %d%s)", N, R - (has_exclude ? 1 : 0), R, has_exclude ? ", one excluded" : "");
+  return 0;
+}
+
 inline bool supported_dh(int dh) { return dh == 16 || dh == 48 || dh == 64 || dh == 96 || dh == 128 || dh == 192; }
 
 // forward.hip
@@ -140,6 +150,7 @@ struct Plan {
   float *xq, *y, *lse; h16_t *q_bf, *mem_bf, *kv, *dqkv, *dq, *dob, *dhid;
   float* mean_part; unsigned* mean_cnt;  // the head launch's per-image mean (CsGemmParams::mean_*)
   CsU8Desc* u8desc;                      // one-pass input stage: B query descriptors, then B * N_enc reference descriptors
+  float *sel_mean, *sel_unit, *sel_sim;  // cs_forward_select: the queries' pooled / unit descriptors (B, C), similarities (B, R) unless the caller keeps them
 };
 
 inline CsGemmParams gp(const h16_t* A, int lda, const h16_t* W, int ldw, int M, int N, int K, const float* bias, void* out, int ldc) {

@@ -72,7 +72,7 @@ struct Arena {  // carve 256-byte aligned pieces out of the workspace
   }
 };
 
-Plan make_plan(const cs_model* m, int B, int N, int N_enc, int H, int W, char* base) {
+Plan make_plan(const cs_model* m, int B, int N, int N_enc, int H, int W, char* base, int R_sel = 0, bool own_sim = false) {
   Plan p{};
   const cs_config& c = m->cfg;
   p.B = B; p.N = N; p.H = H; p.W = W; p.C = c.hidden;
@@ -121,6 +121,11 @@ Plan make_plan(const cs_model* m, int B, int N, int N_enc, int H, int W, char* b
   p.mean_part = a.take<float>(M * 4 * (size_t)cs_gemm_column_tiles(c.patch * c.patch));
   p.mean_cnt = a.take<unsigned>((size_t)B);
   p.u8desc = a.take<CsU8Desc>((size_t)p.I);
+  // cs_forward_select (R_sel > 0): the queries' pooled and unit descriptors, and the similarities when the caller keeps none; the gathered rows
+  // are mem_bf above.  Nothing for the other modes: their plan and cs_workspace_bytes stay as they were.
+  p.sel_mean = a.take<float>(R_sel > 0 ? (size_t)B * C : 0);
+  p.sel_unit = a.take<float>(R_sel > 0 ? (size_t)B * C : 0);
+  p.sel_sim = a.take<float>(own_sim ? (size_t)B * R_sel : 0);
   p.total = a.off;
   return p;
 }
@@ -205,7 +210,9 @@ struct Chunk {
 
 // One forward-class call: its arguments, and what the steps below work out for the later ones.
 // mode 0: full forward (query + reference images); mode 1: query images + cached reference tokens (`ref_tokens`, fp16
-// [B][N][Np][C]); mode 2: encode `B` images as references into `tokens_out` (fp16 [B][Np][C]), no decoder.
+// [B][N][Np][C]); mode 2: encode `B` images as references into `tokens_out` (fp16 [B][Np][C]), no decoder; mode 3: query images + a bank of
+// reference tokens (`ref_tokens`, [R][Np][C]) from which each query's N views are selected by similarity and gathered (`sel`).
+struct SelectIn { const float *bank_unit, *centre; int R; const int32_t* exclude; int32_t* index_out; float* sim_out; };
 struct Fwd {
   cs_model* h; int mode;
   const float *query, *refs; const h16_t* ref_tokens; h16_t* tokens_out;
@@ -213,6 +220,7 @@ struct Fwd {
   float *score_out, *attn_out; int head_id; float* mean_out;
   hipStream_t st;    // the caller's stream
   const U8In* u8;    // null: fp32 images
+  const SelectIn* sel = nullptr;  // mode 3
   int bf = 0;        // 16-bit operand type of every activation buffer and packed weight: 0 IEEE half, 1 bfloat16
   int N_enc = 0;     // reference views that go through the encoder with their query
   Plan p{};          // (workspace)
@@ -232,6 +240,12 @@ struct Fwd {
     if (mode == 0 && (!have_q || !have_r || !score_out)) return fail(CS_ERR_BAD_ARG, "null tensor (ref_cross_imgs is required when do_reference_cross)");
     if (mode == 1 && (!have_q || !ref_tokens || !score_out)) return fail(CS_ERR_BAD_ARG, "null tensor");
     if (mode == 2 && (!have_q || !tokens_out)) return fail(CS_ERR_BAD_ARG, "null tensor");
+    if (mode == 3) {
+      if (!have_q || !ref_tokens || !score_out || !sel || !sel->bank_unit || !sel->centre || !sel->index_out) return fail(CS_ERR_BAD_ARG, "null tensor");
+      if (B > 0 && N > 0)
+        if (int r = select_check(B, sel->R, c.hidden, N, sel->exclude != nullptr)) return r;
+      if ((long long)B * N > 65535) return fail(CS_ERR_UNSUPPORTED, "cs_forward_select: more than 65535 reference slots in one call; split the batch");
+    }
     if (u8 && (!u8->mean3 || !u8->std3 || !(u8->std3[0] > 0.f) || !(u8->std3[1] > 0.f) || !(u8->std3[2] > 0.f)))
       return fail(CS_ERR_BAD_ARG, "uint8 input: mean / std missing or std not positive");
     if (B <= 0 || (mode != 2 && N <= 0)) return fail(CS_ERR_BAD_ARG, "empty batch or no reference views");
@@ -248,7 +262,9 @@ struct Fwd {
   // ---- step 2: workspace (grown when this call needs more), carved into p ----
   int ensure_workspace() {
     const int N_plan = mode == 2 ? 0 : N;
-    const size_t need = make_plan(h, B, N_plan, N_enc, H, W, nullptr).total;
+    const int R_sel = mode == 3 ? sel->R : 0;
+    const bool own_sim = mode == 3 && !sel->sim_out;
+    const size_t need = make_plan(h, B, N_plan, N_enc, H, W, nullptr, R_sel, own_sim).total;
     reap_retired(h, false);
     if (need > h->ws_bytes) {
       // grow: the old workspace may still be in use by work queued earlier (on this or another stream), so it is retired behind an
@@ -263,7 +279,7 @@ struct Fwd {
       HIPCHK(hipMalloc(&h->ws, need));
       h->ws_bytes = need;
     }
-    p = make_plan(h, B, N_plan, N_enc, H, W, h->ws);
+    p = make_plan(h, B, N_plan, N_enc, H, W, h->ws, R_sel, own_sim);
     return 0;
   }
 
@@ -585,6 +601,18 @@ struct Fwd {
     return 0;
   }
 
+  // ---- step 8b (mode 3): the queries' descriptors from the 16-bit copy of their decoder input -- the rows final_ln_split rounds exactly as it
+  // rounds a reference's (one ln_store for both) -- then similarities against the bank, the N best per query, and their token rows -> mem_bf ----
+  void select_references(Launcher& L) {
+    const int C = p.C;
+    float* sim = sel->sim_out ? sel->sim_out : p.sel_sim;
+    L.small("select_desc", [&] { return cs_token_descriptors_launch(p.q_bf, B, p.Np, C, bf, p.sel_mean, L.st); });
+    L.small("select_unit", [&] { return cs_descriptor_unit_launch(p.sel_mean, B, C, sel->centre, p.sel_unit, L.st); });
+    L.small("select_sim", [&] { return cs_similarity_launch(p.sel_unit, B, sel->bank_unit, sel->R, C, sim, L.st); });
+    L.small("select_topn", [&] { return cs_topn_launch(sim, B, sel->R, sel->exclude, N, sel->index_out, L.st); });
+    L.misc("select_gather", 32, 0, 4.0 * B * N * p.Np * C, [&] { return cs_gather_tokens_launch(ref_tokens, sel->R, p.Np, C, sel->index_out, B * N, p.mem_bf, L.st); });
+  }
+
   // ---- step 9: taps: the decoder's inputs = final LayerNorm of the patch tokens + multi-view PE (core.py:141-153,93-98): query rows fp32, reference rows 16 bit ----
   int tap_featmaps() {
     if (!h->capture) return 0;
@@ -593,6 +621,10 @@ struct Fwd {
     if (mode == 2)
       return tap_copy(h, "featmap_ref", tokens_out, 0, (size_t)B * p.Np * C * 2, (size_t)B * p.Np * C * 2, dt16, {B, p.Np, C}, st);
     if (int r = tap_copy(h, "featmap_query", p.xq, 0, (size_t)B * p.Np * C * 4, (size_t)B * p.Np * C * 4, 0, {B, p.Np, C}, st)) return r;
+    if (mode == 3) {
+      if (int r = tap_copy(h, "select_query_mean", p.sel_mean, 0, (size_t)B * C * 4, (size_t)B * C * 4, 0, {B, C}, st)) return r;
+      if (int r = tap_copy(h, "select_query_unit", p.sel_unit, 0, (size_t)B * C * 4, (size_t)B * C * 4, 0, {B, C}, st)) return r;
+    }
     const h16_t* mem = mode == 1 ? ref_tokens : p.mem_bf;
     return tap_copy(h, "featmap_ref", mem, 0, (size_t)B * N * p.Np * C * 2, (size_t)B * N * p.Np * C * 2, dt16, {B, (int64_t)N * p.Np, C}, st);
   }
@@ -706,9 +738,13 @@ struct Fwd {
     if (int r = encoder_rounds(LL)) return r;
     if (int r = join_lanes()) return r;
     for (const Launcher& L : LL) if (L.rc) return L.rc;
+    Launcher LD{h, st};  // every image's tokens are in place (join above) before the decoder starts
+    if (mode == 3) {
+      select_references(LD);
+      if (LD.rc) return LD.rc;
+    }
     if (int r = tap_featmaps()) return r;
     if (mode == 2) return 0;
-    Launcher LD{h, st};  // every image's tokens are in place (join above) before the decoder starts
     decoder(LD);
     if (LD.rc) return LD.rc;
     if (!h->cfg.skip_finite_check)
@@ -776,6 +812,25 @@ int cs_forward_cached_u8(cs_handle h, const cs_u8_image* query, const uint16_t* 
                          const float* std3, float* score_out, float* attn_out, int head_id, float* mean_out, cs_stream stream) {
   const U8In u{query, nullptr, mean3, std3};
   return forward_impl(Fwd{h, 1, nullptr, nullptr, ref_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, &u});
+}
+
+int cs_forward_select(cs_handle h, const float* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre, int R,
+                      const int32_t* exclude, int B, int N, int H, int W, float* score_out, float* attn_out, int head_id, float* mean_out,
+                      int32_t* index_out, float* sim_out, cs_stream stream) {
+  const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out};
+  Fwd f{h, 3, query, nullptr, bank_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, nullptr};
+  f.sel = &s;
+  return forward_impl(f);
+}
+
+int cs_forward_select_u8(cs_handle h, const cs_u8_image* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre, int R,
+                         const int32_t* exclude, int B, int N, int H, int W, const float* mean3, const float* std3, float* score_out,
+                         float* attn_out, int head_id, float* mean_out, int32_t* index_out, float* sim_out, cs_stream stream) {
+  const U8In u{query, nullptr, mean3, std3};
+  const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out};
+  Fwd f{h, 3, nullptr, nullptr, bank_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, &u};
+  f.sel = &s;
+  return forward_impl(f);
 }
 
 int cs_u8_input_supported(cs_handle h, const cs_u8_image* im, int H, int W) {

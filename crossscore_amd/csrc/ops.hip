@@ -537,4 +537,42 @@ int cs_op_ln_fold_consts(const uint16_t* w_packed, int ldp, const float* w, cons
   return 0;
 }
 
+// ---- reference selection by similarity (select.hip) ----
+int cs_op_token_descriptors(const uint16_t* tokens, int I, int Np, int C, int dtype, float* mean_out, cs_stream stream) {
+  if (!tokens || !mean_out || I <= 0 || Np <= 0 || C <= 0) return fail(CS_ERR_BAD_ARG, "token_descriptors: bad arguments");
+  if (dtype != CS_DTYPE_F16 && dtype != CS_DTYPE_BF16) return fail(CS_ERR_BAD_ARG, "token_descriptors: dtype must be CS_DTYPE_F16 or CS_DTYPE_BF16");
+  if (C % 64 || I > 65535) return fail(CS_ERR_UNSUPPORTED, "token_descriptors: C must be a multiple of 64 and I <= 65535");
+  HIPCHK(cs_token_descriptors_launch(tokens, I, Np, C, dtype == CS_DTYPE_BF16, mean_out, (hipStream_t)stream));
+  return 0;
+}
+
+int cs_op_descriptor_centre(const float* mean, int R, int C, float* centre_out, cs_stream stream) {
+  if (!mean || !centre_out || R <= 0 || C <= 0) return fail(CS_ERR_BAD_ARG, "descriptor_centre: bad arguments");
+  if (C % 64) return fail(CS_ERR_UNSUPPORTED, "descriptor_centre: C must be a multiple of 64");
+  HIPCHK(cs_descriptor_centre_launch(mean, R, C, centre_out, (hipStream_t)stream));
+  return 0;
+}
+
+int cs_op_descriptor_unit(const float* mean, int I, int C, const float* centre, float* unit_out, cs_stream stream) {
+  if (!mean || !centre || !unit_out || I <= 0 || C <= 0) return fail(CS_ERR_BAD_ARG, "descriptor_unit: bad arguments");
+  HIPCHK(cs_descriptor_unit_launch(mean, I, C, centre, unit_out, (hipStream_t)stream));
+  return 0;
+}
+
+int cs_op_select_references(const float* q_unit, int B, const float* bank_unit, int R, int C, const int32_t* exclude, int N, int32_t* index_out,
+                            float* sim_out, cs_stream stream) {
+  if (!q_unit || !bank_unit || !index_out || !sim_out) return fail(CS_ERR_BAD_ARG, "select_references: null tensor");
+  if (int r = select_check(B, R, C, N, exclude != nullptr)) return r;
+  HIPCHK(cs_similarity_launch(q_unit, B, bank_unit, R, C, sim_out, (hipStream_t)stream));
+  HIPCHK(cs_topn_launch(sim_out, B, R, exclude, N, index_out, (hipStream_t)stream));
+  return 0;
+}
+
+int cs_op_gather_tokens(const uint16_t* bank, int R, int Np, int C, const int32_t* index, int B, int N, uint16_t* out, cs_stream stream) {
+  if (!bank || !index || !out || R <= 0 || Np <= 0 || C <= 0 || B <= 0 || N <= 0) return fail(CS_ERR_BAD_ARG, "gather_tokens: bad arguments");
+  if (((long long)Np * C) % 8 || (long long)B * N > 65535) return fail(CS_ERR_UNSUPPORTED, "gather_tokens: Np * C must be a multiple of 8 and B * N <= 65535");
+  HIPCHK(cs_gather_tokens_launch(bank, R, Np, C, index, B * N, out, (hipStream_t)stream));
+  return 0;
+}
+
 }  // extern "C"

@@ -394,7 +394,7 @@ def batch_files(items, zero_reference: bool = False, extra=None, skip=()) -> Lis
     for it in items:
         files.append((it["query/img"], False))
         if not zero_reference:
-            files += [(p, False) for p in it["reference/cross/imgs"] if p != EMPTY and p not in skip]
+            files += [(p, False) for p in (it["reference/cross/imgs"] or ()) if p != EMPTY and p not in skip]  # (None: chosen on the device)
         if extra is not None:
             files += extra(it)
     return files
@@ -406,7 +406,7 @@ def plan_decodes(batches, zero_reference: bool, once_per_reference: bool, extra=
     seen, plan = set(), []
     for its in batches:
         plan.append(batch_files(its, zero_reference, extra, seen if once_per_reference else ()))
-        seen.update(p for it in its for p in it["reference/cross/imgs"])
+        seen.update(p for it in its for p in (it["reference/cross/imgs"] or ()))
     return plan
 
 
@@ -653,12 +653,16 @@ class InputStage:
         return U8Batch(images, size, self.mean_std, device=self.device)
 
 
+STRATEGIES = ("random", "similar")  # data.neighbour_config.strategy: the reference's sampler, and this build's choice by DINOv2 similarity (predict only)
+
+
 class SimpleReferenceItems:
     """Index -> file paths of one item, like NeighbourSelector.__getitem__ for the single-scene layout of SimpleReference."""
 
     def __init__(self, query_dir: str, reference_dir: str, neighbour_config) -> None:
-        if neighbour_config["strategy"] != "random":
-            raise NotImplementedError(f"neighbour strategy {neighbour_config['strategy']} (sampler.py:60-66 only knows 'random')")
+        if neighbour_config["strategy"] not in STRATEGIES:
+            raise NotImplementedError(f"neighbour strategy {neighbour_config['strategy']} (sampler.py:60-66 knows 'random'; this build adds 'similar')")
+        self.strategy = str(neighbour_config["strategy"])
         self.query_paths, self.reference_paths = list_paths(query_dir, reference_dir)
         self.n_cross = int(neighbour_config["cross"])
         self.deterministic = bool(neighbour_config["deterministic"])
@@ -667,6 +671,8 @@ class SimpleReferenceItems:
         return len(self.query_paths)
 
     def __getitem__(self, idx: int) -> Dict[str, object]:
+        if self.strategy == "similar":  # the views are chosen on the device (ReferenceBank, forward_select); no RNG is drawn
+            return {"query/img": self.query_paths[idx], "query/score_map": EMPTY, "reference/cross/imgs": None}
         refs = sample_references(self.reference_paths, self.n_cross, self.deterministic) if self.n_cross > 0 else []
         return {"query/img": self.query_paths[idx], "query/score_map": EMPTY, "reference/cross/imgs": refs}
 
@@ -683,9 +689,13 @@ def decode_items(items: List[Dict[str, object]], zero_reference: bool = False, p
 def item_paths(items: List[Dict[str, object]]) -> Dict[str, list]:
     """The batch's file paths in the collated layout the writers expect (default_collate turns the per-item list of N reference paths into N
     lists of B paths)."""
-    N = len(items[0]["reference/cross/imgs"])
+    if items[0]["reference/cross/imgs"] is None:  # strategy similar: scoring's consume fills the lists in from the batch's reference_index
+        refs = None
+    else:
+        N = len(items[0]["reference/cross/imgs"])
+        refs = [[it["reference/cross/imgs"][n] for it in items] for n in range(N)]
     return {"query/img": [it["query/img"] for it in items], "query/score_map": [it["query/score_map"] for it in items],
-            "reference/cross/imgs": [[it["reference/cross/imgs"][n] for it in items] for n in range(N)]}
+            "reference/cross/imgs": refs}
 
 
 def _reference_image(path: str, decoded, stage: InputStage, size):
@@ -772,3 +782,63 @@ class ReferenceTokenCache:
         tokens = torch.stack([torch.stack([self.tokens[k] for k in ks]) for ks in keys])
         images = torch.stack([torch.stack([self.images[k] for k in ks]) for ks in keys]) if self.keep_images else None
         return tokens, images
+
+
+class ReferenceBank:
+    """data.neighbour_config.strategy=similar: every file of reference_dir is encoded ONCE, in chunks, into one contiguous
+    (R, h*w, C) token tensor; the descriptors forward_select compares a query with are formed from it (CrossScoreNet.reference_descriptors).
+    `bank` is the model.SelectionBank the forwards take, `paths` the files in bank order, `images` their processed fp32 images (R, 3, h, w) when
+    keep_images (the writer's image_reference output) -- else None.
+
+    decoder: the run's PngDecoder (this_main.png_decoder / jpeg_decoder = gpu): a chunk's files are decoded on the device, `window` files per
+    call; else PIL on `pool`.  from_u8: the one-pass input stage (encode_references_u8; no processed image exists, so not with keep_images)."""
+
+    def __init__(self, net, stage: InputStage, paths: Sequence[str], size: Tuple[int, int], n_references: int, keep_images: bool = False,
+                 max_images: int = 4096, from_u8: bool = False, decoder: Optional[PngDecoder] = None, pool=None, chunk: int = 32, window: int = 64):
+        from .model import SelectionBank
+        self.paths = list(paths)
+        R = len(self.paths)
+        if R == 0:
+            raise ValueError("neighbour strategy similar: reference_dir holds no file")
+        if R > max_images:
+            raise ValueError(f"neighbour strategy similar keeps every reference's tokens: reference_dir holds {R} files, more than "
+                             f"this_main.reference_cache_max_images={max_images}")
+        if n_references > R:
+            raise ValueError(f"neighbour strategy similar: neighbour_config.cross={n_references} exceeds the {R} files of reference_dir")
+        oh, ow = size
+        from_u8 = bool(from_u8) and not keep_images
+        step = max(1, min(int(chunk), int(window) if decoder is not None else int(chunk)))
+        tokens = None
+        self.images = torch.empty((R, 3, oh, ow), dtype=torch.float32, device=stage.device) if keep_images else None
+        for r0 in range(0, R, step):
+            part = self.paths[r0:r0 + step]
+            if decoder is not None:
+                handle = decoder.decode(part)
+                handle.wait(torch.cuda.current_stream(stage.device))
+                handle.check()  # (set-up: the bank is complete before the first query is scored)
+                imgs = handle.tensors
+            else:
+                imgs = list(pool.map(read_image_u8, part)) if pool is not None else [read_image_u8(p) for p in part]
+            for p, im in zip(part, imgs):
+                if stage.geometry(int(im.shape[0]), int(im.shape[1]))[1][2:] != (oh, ow):
+                    raise ValueError(f"{p}: processed size differs from the query's {oh}x{ow}")
+            if from_u8:
+                tok = net.encode_references_u8(stage.batch([stage.describe(im) for im in imgs], (oh, ow)))
+            else:
+                buf = self.images[r0:r0 + len(part)] if keep_images else torch.empty((len(part), 3, oh, ow), dtype=torch.float32, device=stage.device)
+                for i, im in enumerate(imgs):
+                    stage(im, buf[i])
+                tok = net.encode_references(buf)
+            if tokens is None:
+                tokens = torch.empty((R,) + tuple(tok.shape[1:]), dtype=tok.dtype, device=tok.device)
+            tokens[r0:r0 + len(part)] = tok
+        mean, centre, unit = net.reference_descriptors(tokens)
+        self.bank = SelectionBank(tokens, mean, centre, unit, n_references)
+        self._real = {os.path.realpath(p): i for i, p in reversed(list(enumerate(self.paths)))}
+
+    def __len__(self) -> int:
+        return len(self.paths)
+
+    def index_of(self, path: str) -> int:
+        """The bank index of the file `path` names (by real path), or -1."""
+        return self._real.get(os.path.realpath(path), -1)

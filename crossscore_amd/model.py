@@ -117,6 +117,24 @@ class U8Batch:
         return self._device
 
 
+class SelectionBank:
+    """What forward_select chooses from: tokens (R, h*w, C) in the module's operand type (encode_references of every candidate, contiguous),
+    their descriptors mean / unit (R, C) and centre (C) fp32 (CrossScoreNet.reference_descriptors), and n_references, the views a query takes."""
+    __slots__ = ("tokens", "mean", "centre", "unit", "n_references")
+
+    def __init__(self, tokens: torch.Tensor, mean: torch.Tensor, centre: torch.Tensor, unit: torch.Tensor, n_references: int):
+        if tokens.dim() != 3 or not tokens.is_cuda or not tokens.is_contiguous():
+            raise ValueError("SelectionBank.tokens must be a contiguous CUDA tensor (R, h*w, C)")
+        R, _, Cc = tokens.shape
+        for name, t, shape in (("mean", mean, (R, Cc)), ("centre", centre, (Cc,)), ("unit", unit, (R, Cc))):
+            if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != tokens.device or not t.is_contiguous():
+                raise ValueError(f"SelectionBank.{name} must be a contiguous fp32 tensor {shape} on the tokens' device")
+        self.tokens, self.mean, self.centre, self.unit, self.n_references = tokens, mean, centre, unit, int(n_references)
+
+    def __len__(self) -> int:
+        return int(self.tokens.shape[0])
+
+
 class _Node(torch.nn.Module):
     """Parameter container; the tree of _Nodes reproduces the reference module paths."""
 
@@ -472,6 +490,99 @@ class CrossScoreNet(torch.nn.Module):
                                                     int(need_attn_weights_head_id),
                                                     C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None, C.c_void_p(stream)))
         return self._results(score, attn, mean_out)
+
+    # -- reference selection by similarity: the choice of each query's views is made on the device ----------------------
+    @torch.no_grad()
+    def reference_descriptors(self, tokens):
+        """(R, h*w, C) tokens from encode_references -> (mean (R, C), centre (C), unit (R, C)) fp32: the pooled descriptors of the candidates,
+        their mean over the bank and the centred unit vectors forward_select compares a query's descriptor with."""
+        if tokens.dim() != 3 or not tokens.is_cuda or tokens.dtype not in (torch.float16, torch.bfloat16):
+            raise ValueError("expected CUDA tokens (R, h*w, C) in a 16-bit operand type")
+        t = tokens.contiguous()
+        R, Np, Cc = t.shape
+        dev = t.device
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            mean = torch.empty((R, Cc), dtype=torch.float32, device=dev)
+            centre = torch.empty((Cc,), dtype=torch.float32, device=dev)
+            unit = torch.empty((R, Cc), dtype=torch.float32, device=dev)
+            code = _lib.DTYPE_BF16 if t.dtype == torch.bfloat16 else _lib.DTYPE_F16
+            for r0 in range(0, R, 32768):  # (an image's mean does not depend on the launch it is part of)
+                r1 = min(R, r0 + 32768)
+                _lib.check(lib.cs_op_token_descriptors(C.c_void_p(t[r0:r1].data_ptr()), r1 - r0, Np, Cc, code, C.c_void_p(mean[r0:r1].data_ptr()), st))
+            _lib.check(lib.cs_op_descriptor_centre(C.c_void_p(mean.data_ptr()), R, Cc, C.c_void_p(centre.data_ptr()), st))
+            _lib.check(lib.cs_op_descriptor_unit(C.c_void_p(mean.data_ptr()), R, Cc, C.c_void_p(centre.data_ptr()), C.c_void_p(unit.data_ptr()), st))
+        return mean, centre, unit
+
+    def _forward_select(self, query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, u8):
+        N = int(bank.n_references if n_references is None else n_references)
+        t = bank.tokens
+        dev = t.device
+        if t.dtype != self.token_dtype:
+            raise ValueError(f"the bank's tokens are {t.dtype}, this module's operand type is {self.token_dtype}: encode them with the same module")
+        if u8:
+            B = len(query)
+            H, W = query.size
+            if B == 0:
+                raise ValueError("expected at least one query image")
+        else:
+            if query.dim() != 4 or query.shape[1] != 3:
+                raise ValueError("expected query_img (B,3,H,W)")
+            if not query.is_cuda or query.device != dev:
+                raise _lib.CrossScoreHipError("forward_select needs the query and the bank on one CUDA(HIP) device: the hot path has no CPU fallback")
+            q = query.to(torch.float32).contiguous()
+            B, _, H, W = q.shape
+        P = self.arch.patch
+        h, w = H // P, W // P
+        R = len(bank)
+        if t.shape[1] != h * w or t.shape[2] != self.arch.hidden:
+            raise ValueError("the bank's tokens do not match the query's patch grid / hidden size")
+        if N < 1:
+            raise ValueError("forward_select needs at least one reference view per query")
+        ex = None
+        if exclude is not None:
+            if tuple(exclude.shape) != (B,) or exclude.device != dev:
+                raise ValueError("exclude must hold one bank index (or -1) per query, on the bank's device")
+            ex = exclude.to(torch.int32).contiguous()
+        self._check_pe_mode(H, W)
+        lib = _lib.load()
+        handle = self._ensure_handle(dev)
+        with torch.cuda.device(dev):
+            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
+            index = torch.empty((B, N), dtype=torch.int32, device=dev)
+            sim = torch.empty((B, R), dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for b0, b1 in self._sub_batches(B, N, h * w):
+                tail = (C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
+                        int(need_attn_weights_head_id), C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None,
+                        C.c_void_p(index[b0:b1].data_ptr()), C.c_void_p(sim[b0:b1].data_ptr()), C.c_void_p(stream))
+                head = (C.c_void_p(t.data_ptr()), C.c_void_p(bank.unit.data_ptr()), C.c_void_p(bank.centre.data_ptr()), R,
+                        C.c_void_p(ex[b0:b1].data_ptr()) if ex is not None else None, b1 - b0, N, H, W)
+                if u8:
+                    _lib.check(lib.cs_forward_select_u8(handle, query.c_array(b0, b1), *head, query.mean, query.std, *tail))
+                else:
+                    _lib.check(lib.cs_forward_select(handle, C.c_void_p(q[b0:b1].data_ptr()), *head, *tail))
+            results = self._results(score, attn, mean_out)
+            results["reference_index"] = index
+            # the similarities of the chosen entries, in the order chosen (an index of -1, a query that ran out of candidates, reads entry 0)
+            results["reference_similarity"] = torch.gather(sim, 1, index.clamp(min=0).to(torch.int64))
+        return results
+
+    @torch.no_grad()
+    def forward_select(self, query_img, bank: "SelectionBank", exclude=None, need_attn_weights=False, need_attn_weights_head_id=0,
+                       return_mean=False, n_references=None):
+        """forward_cached() with each query's N = bank.n_references views chosen on the device: the bank entries most similar to the query's own
+        pooled descriptor, descending, ties to the lower index, exclude[b] (int32 (B), -1 = none) left out.  The result also holds
+        "reference_index" (B, N) int32 and "reference_similarity" (B, N) fp32; the score map, mean and attention weights are bit-identical to
+        forward_cached(query_img, bank.tokens[reference_index])."""
+        return self._forward_select(query_img, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, False)
+
+    @torch.no_grad()
+    def forward_select_u8(self, query: U8Batch, bank: "SelectionBank", exclude=None, need_attn_weights=False, need_attn_weights_head_id=0,
+                          return_mean=False, n_references=None):
+        """forward_select() with the query images as decoded uint8."""
+        return self._forward_select(query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, True)
 
     def calibrate_lanes(self, query_img, ref_cross_imgs, tries: int = 3, steps: int = 4, min_gain: float = 0.08) -> Dict[str, Any]:
         """Checks that this module's multi-lane forward really overlaps its lanes, and repairs it if not.  The lanes' streams are probed

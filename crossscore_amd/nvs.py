@@ -92,6 +92,9 @@ class NvsItems:
                  num_gaussians_iters: int = -1, compute_gt: bool = False):
         if data_split not in DATA_SPLITS:
             raise ValueError(f"Unknown data_split {data_split}")
+        if neighbour_config["strategy"] == "similar":
+            raise NotImplementedError("neighbour strategy similar is built for predict only (data.SimpleReferenceItems): per-scene candidate sets "
+                                      "in a multi-scene batch are not")
         if neighbour_config["strategy"] != "random":
             raise NotImplementedError(f"neighbour strategy {neighbour_config['strategy']} (sampler.py:60-66 only knows 'random')")
         if isinstance(dataset_path, str):

@@ -232,6 +232,19 @@ class ForwardPipeline:
         """CrossScoreNet.forward_cached_u8 on the next replica."""
         return self._run("forward_cached_u8", (query, ref_tokens) + args, kwargs)
 
+    def submit_select(self, query_img, bank, *args, **kwargs) -> Ticket:
+        """CrossScoreNet.forward_select on the next replica; the bank (model.SelectionBank) may have been built on any replica and must be
+        complete on the current stream (the replica's stream waits for that one)."""
+        return self._run("forward_select", (query_img, bank) + args, kwargs)
+
+    def submit_select_u8(self, query, bank, *args, **kwargs) -> Ticket:
+        """CrossScoreNet.forward_select_u8 on the next replica."""
+        return self._run("forward_select_u8", (query, bank) + args, kwargs)
+
+    def reference_descriptors(self, tokens: torch.Tensor):
+        """CrossScoreNet.reference_descriptors on the current stream (single-op launches: no handle, no workspace)."""
+        return self.nets[0].reference_descriptors(tokens)
+
     def encode_references_u8(self, imgs) -> torch.Tensor:
         """CrossScoreNet.encode_references_u8 through replica 0 (see encode_references)."""
         net = self.nets[0]

@@ -64,7 +64,8 @@ def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opti
     # the file lists of all batches are fixed up front (sampling order = item order, like a shuffle=False DataLoader)
     batches = [[items[i] for i in range(start, min(start + bs, hi))] for start in range(lo, hi, bs)]
     # a long run (>= 16 batches) calibrates at its first batch: the batches in flight, or at depth 1 the forward's lanes, must really overlap
-    run = scoring.score(cfg, opts, stage, batches, state_dict, items.query_paths[lo] if len(items) > lo else None, calibrate=True)
+    run = scoring.score(cfg, opts, stage, batches, state_dict, items.query_paths[lo] if len(items) > lo else None, calibrate=True,
+                        reference_paths=items.reference_paths)
     # A rank whose output stage raised still takes part in the collective below, or the other ranks wait in it forever: the
     # failure travels with the overflow count (one max-reduction: value = count + 1e12 for a failed rank) and is re-raised behind the
     # barrier -- on the failing rank as it was, on the others as a RuntimeError naming the situation.

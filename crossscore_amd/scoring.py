@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import parallel, synth
-from .data import (DecodeWindow, PngDecoder, ReferenceTokenCache, decode_items, jpeg_decoder_choice, jpeg_progressive_choice, load_batch, plan_decodes,
+from .data import (STRATEGIES, DecodeWindow, PngDecoder, ReferenceBank, ReferenceTokenCache, decode_items, jpeg_decoder_choice, jpeg_progressive_choice, load_batch, plan_decodes,
                    png_decode_window_choice, png_decoder_choice, read_image_u8)
 from .model import CrossScoreNet, U8Image, load_lightning_checkpoint
 from .pipeline import ForwardPipeline
@@ -75,6 +75,23 @@ def options(cfg, phase: str) -> SimpleNamespace:
     # outputs (on by default, as in the reference's config) ARE that processed image, so "auto" takes the one-pass form only when neither is
     # written, and only for geometries it holds (cs_u8_input_supported); True insists, False never.  Results are bit-identical either way.
     o.fused = cfg.this_main.get("fused_input_stage", "auto")
+    # data.neighbour_config.strategy: random (the reference's sampler) | similar (this build, predict only): each query is scored
+    # against the neighbour_config.cross files of reference_dir whose pooled DINOv2 descriptor is most similar to its own, chosen on the device
+    # from the tokens of ALL reference files (data.ReferenceBank).  this_main.similar_exclude_self (default on): a query never takes the
+    # reference file that is itself (same real path), e.g. with query_dir == reference_dir.
+    o.strategy = str(cfg.data.neighbour_config.strategy)
+    o.exclude_self = bool(cfg.this_main.get("similar_exclude_self", True))
+    if o.strategy == "similar":
+        if phase != "predict":
+            raise NotImplementedError("neighbour strategy similar is built for predict only")
+        if bool(cfg.data.dataset.zero_reference):
+            raise ValueError("data.neighbour_config.strategy=similar with data.dataset.zero_reference=True: there is nothing to choose between")
+        if not bool(cfg.this_main.get("cache_reference_tokens", True)):
+            raise ValueError("data.neighbour_config.strategy=similar chooses from the cached reference tokens: this_main.cache_reference_tokens=False is not possible with it")
+        if int(cfg.data.neighbour_config.cross) < 1:
+            raise ValueError("data.neighbour_config.strategy=similar needs data.neighbour_config.cross >= 1")
+    elif o.strategy not in STRATEGIES:
+        raise NotImplementedError(f"neighbour strategy {o.strategy} (sampler.py:60-66 knows 'random'; this build adds 'similar')")
     return o
 
 
@@ -87,6 +104,22 @@ def start(cfg, o: SimpleNamespace) -> None:
     torch.cuda.set_device(o.device)
 
 
+def write_reference_selection(out_dir: str, selection) -> str:
+    """reference_selection.csv of a run with neighbour strategy similar: per query its file name, then the chosen references' file names in the
+    order chosen, then their similarities as %.4f."""
+    import csv
+    import os
+
+    path = os.path.join(str(out_dir), "reference_selection.csv")
+    n = len(selection[0][1]) if selection else 0
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["query"] + [f"reference_{k}" for k in range(n)] + [f"similarity_{k}" for k in range(n)])
+        for query, refs, sims in selection:
+            w.writerow([os.path.basename(query)] + [os.path.basename(p) for p in refs] + ["%.4f" % v for v in sims])
+    return path
+
+
 class Scored(NamedTuple):
     result: Dict[str, object]  # the result keys both drivers report
     files: list                # what the writers and the summariser wrote
@@ -97,7 +130,8 @@ class Scored(NamedTuple):
 
 
 def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: Optional[str] = None, *, calibrate: bool = False,
-          extra_files=None, decode_host=None, from_window=None, check_size=None, after_submit=None, on_consume=None) -> Scored:
+          extra_files=None, decode_host=None, from_window=None, check_size=None, after_submit=None, on_consume=None,
+          reference_paths=None) -> Scored:
     """Scores `batches` (lists of item dictionaries; cfg.logger.<phase>.out_dir exists) and finishes the outputs.
 
     probe_path: the first query of this rank, whose geometry decides about the one-pass input stage (None: no image to look at).
@@ -106,6 +140,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     decode_host(items, zero_ref, pool, skip) -> (decoded, extras) replaces decode_items on the host path; from_window(decoded, items) -> extras
     picks the same extras out of the window's tensors.
     check_size(size) may refuse a batch's processed size before anything of it is queued.
+    reference_paths: the files of reference_dir, in the driver's order: the candidates of neighbour strategy similar.
     after_submit(ticket, items, decoded, extras, size, batch) -> state; on_consume(idx, batch, out, state) runs before the summariser and writer."""
     phase, device = o.phase, o.device
     log = cfg.logger[phase]
@@ -144,11 +179,16 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     if o.fused in (True, "true", "True", 1) and not fused_in:
         raise ValueError("this_main.fused_input_stage=True, but " + (f"the writers need the processed images (logger.{phase}.write.flag.image_query / "
                          "image_reference)" if want_imgs else "this backbone / image geometry is not taken by the one-pass input stage"))
-    cache = ReferenceTokenCache(pipe, stage, keep_images=bool(writer is not None and log.write.flag.image_reference),
-                                max_images=o.cache_max_images, from_u8=fused_in) if o.use_cache else None
+    similar = o.strategy == "similar"
+    keep_ref_images = bool(writer is not None and log.write.flag.image_reference)
+    cache = ReferenceTokenCache(pipe, stage, keep_images=keep_ref_images,
+                                max_images=o.cache_max_images, from_u8=fused_in) if o.use_cache and not similar else None
+    bank = None  # neighbour strategy similar: data.ReferenceBank, built when the first batch tells the processed size
+    selection = []  # ... and per query (path, chosen reference paths, their similarities), in consumption order
     decoder = PngDecoder(device, pool, png=o.png_decoder == "gpu", jpeg=o.jpeg_decoder == "gpu",
                          progressive=o.jpeg_progressive == "gpu") if "gpu" in (o.png_decoder, o.jpeg_decoder) else None
     window = DecodeWindow(decoder, plan_decodes(batches, zero_ref, cache is not None, extra_files), o.decode_window) if decoder is not None else None
+    n_cross = int(cfg.data.neighbour_config.cross)
 
     def decode(i, skip):
         """(decoded images of batch i, the driver's extras), on the loader's thread: {path: device tensor} from the decode window, else
@@ -173,6 +213,16 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
         out = pipe.result(ticket)
         if window is not None:
             window.check(idx)  # the status words of the files this batch read: a rejected file raises here, naming its path
+        if similar:
+            # the views this batch was scored against, read now that the batch is taken anyway: paths for the item-path JSON, the reference PNGs'
+            # and the attention images' names; the processed images from the bank where they are written
+            index = out["reference_index"].cpu()
+            sims = out["reference_similarity"].cpu().numpy()
+            chosen = [[bank.paths[int(i)] for i in row] for row in index.tolist()]
+            batch["item_paths"]["reference/cross/imgs"] = [[row[n] for row in chosen] for n in range(n_cross)]
+            if bank.images is not None:
+                batch["reference/cross/imgs"] = bank.images[index.to(device=device, dtype=torch.int64)]
+            selection.extend(zip(batch["item_paths"]["query/img"], chosen, sims.tolist()))
         if on_consume is not None:
             on_consume(idx, batch, out, state)
         summariser.update(batch, out, means=out.get("score_mean_ref_cross"))  # the per-image means the head launch left (score_summariser.py:180-192)
@@ -186,7 +236,23 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     queued = []  # batches submitted and not yet consumed, oldest first: depth of them stay in flight
     for batch_idx, its in enumerate(batches):
         decoded, extras = pending.result()
-        if cache is None:
+        if similar:
+            batch, size = load_batch(its, stage, decoded, fused_in, references=False)
+            if check_size is not None:
+                check_size(size)
+            if bank is None:
+                bank = ReferenceBank(pipe, stage, reference_paths, tuple(size), n_cross, keep_images=keep_ref_images, max_images=o.cache_max_images,
+                                     from_u8=fused_in, decoder=decoder, pool=pool, window=o.decode_window)
+            if tuple(bank.bank.tokens.shape[1:2]) != ((size[0] // net.arch.patch) * (size[1] // net.arch.patch),):
+                raise ValueError(f"neighbour strategy similar: this batch's processed size {size[0]}x{size[1]} differs from the reference bank's")
+            pending = submit_decode(batch_idx + 1)  # (behind the bank's own decodes: the decoder serves one thread at a time)
+            exclude = None
+            if o.exclude_self:
+                ex = [bank.index_of(it["query/img"]) for it in its]
+                if any(e >= 0 for e in ex):  # (an array makes every query of the call count as carrying an exclusion: cs_forward_select)
+                    exclude = torch.tensor(ex, dtype=torch.int32).to(device)
+            ticket = (pipe.submit_select_u8 if fused_in else pipe.submit_select)(batch["query/img"], bank.bank, exclude, need_w, head_id, True)
+        elif cache is None:
             pending = submit_decode(batch_idx + 1)
             batch, size = load_batch(its, stage, decoded, fused_in, zero_reference=zero_ref)
             if check_size is not None:
@@ -227,6 +293,8 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
         if writer is not None:
             writer.finish()
         files += summariser.summarise()
+        if similar:
+            files.append(write_reference_selection(log.out_dir, selection))
     except BaseException as exc:  # noqa: BLE001 -- re-raised by the driver, behind its collective
         failure = exc
     finally:
@@ -239,5 +307,6 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
               "jpeg_decoder": o.jpeg_decoder, "jpeg_decoded": decoder.jpeg_stats() if o.jpeg_decoder == "gpu" else {"jpeg_decoded_gpu": 0, "jpeg_decoded_host": 0},
               "jpeg_progressive": o.jpeg_progressive,
               "jpeg_progressive_decoded": decoder.progressive_stats() if o.jpeg_progressive == "gpu" else {"jpeg_progressive_gpu": 0, "jpeg_progressive_host": 0},
+              "reference_strategy": o.strategy,
               "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}  # the whole scoring loop: input stage, forwards, output stage
     return Scored(result, files, summariser.rows, failure, pipe.nonfinite_count(), net.operand_dtype)

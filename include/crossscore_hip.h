@@ -149,6 +149,40 @@ int cs_forward_cached_u8(cs_handle h, const cs_u8_image* query, const uint16_t* 
                          const float* std3, float* score_out, float* attn_out, int head_id, float* mean_out, cs_stream stream);
 /* 1 when the three calls above take this image geometry on this handle, 0 when not (then: cs_op_preprocess_u8 + the fp32 entry points) */
 int cs_u8_input_supported(cs_handle h, const cs_u8_image* img, int H, int W);
+/* Reference selection by DINOv2 similarity (this build's definition, the reference's sampler only draws at random).  An image's
+ * descriptor is pooled from its decoder-input rows t (Np, C), 16 bit, exactly what cs_encode_references writes:
+ *   mean   m[c] = (1 / Np) sum_p t[p][c]        fp32, in an order that depends on Np and C only (not on the launch's image count or the image's place)
+ *   centre mu[c] = (1 / R) sum_r m_r[c]         over the R images of a bank (removes the pooled multi-view PE, a constant every image carries)
+ *   unit   e = (m - mu) / max(|m - mu|, 1e-12)
+ *   s(q, r) = sum_c e_q[c] e_r[c]               the same instruction sequence for every pair: equal bank rows give equal bits
+ * and a query takes the N bank entries of largest s, in descending order, ties to the lower index, exclude[b] (when >= 0) left out.
+ *   cs_op_token_descriptors   tokens (I, Np, C) 16 bit, dtype CS_DTYPE_F16 / CS_DTYPE_BF16 -> mean_out (I, C); C a multiple of 64, I <= 65535
+ *   cs_op_descriptor_centre   mean (R, C) -> centre_out (C)
+ *   cs_op_descriptor_unit     mean (I, C), centre (C) -> unit_out (I, C); a row equal to the centre gives zeros
+ *   cs_op_select_references   q_unit (B, C), bank_unit (R, C) -> sim_out (B, R) (required here) and index_out (B, N) int32.  N <= 32 and
+ *                             R <= 65536, else CS_ERR_UNSUPPORTED.  CS_ERR_BAD_ARG when N exceeds the eligible entries: R without `exclude`,
+ *                             R - 1 with it (the array lives on the device and is not read by the host, so any query may carry an exclusion).
+ *                             A query with fewer than N candidates (NaN similarities never qualify) gets -1 in the remaining places.
+ *   cs_op_gather_tokens       out (B, N, Np, C) <- bank (R, Np, C) rows named by index (B, N), 16-byte vectors (Np * C a multiple of 8); an index
+ *                             outside [0, R) reads nothing and its slot becomes zeros; B * N <= 65535
+ * cs_forward_select* is cs_forward_cached* with the choice made on the device: behind the encoder the query's descriptors are pooled from the
+ * 16-bit copy of its decoder input (the rounding cs_encode_references applies, so a query that is also a bank image gets that row's mean bit for
+ * bit), the N entries are selected against bank_unit (R, C) / centre (C) and their rows of bank_tokens (R, Np, C) are gathered into the workspace;
+ * decoder and head then run as in cs_forward_cached on those rows (bit-identical to it).  index_out (B, N) is required; sim_out NULL keeps the
+ * similarities in the workspace.  Every pointer is device memory; nothing is copied to the host or waited for.  Debug taps: "select_query_mean",
+ * "select_query_unit" fp32 (B, C). */
+int cs_op_token_descriptors(const uint16_t* tokens, int I, int Np, int C, int dtype, float* mean_out, cs_stream stream);
+int cs_op_descriptor_centre(const float* mean, int R, int C, float* centre_out, cs_stream stream);
+int cs_op_descriptor_unit(const float* mean, int I, int C, const float* centre, float* unit_out, cs_stream stream);
+int cs_op_select_references(const float* q_unit, int B, const float* bank_unit, int R, int C, const int32_t* exclude /* NULL or (B), -1 = none */,
+                            int N, int32_t* index_out /* (B, N) */, float* sim_out /* (B, R) */, cs_stream stream);
+int cs_op_gather_tokens(const uint16_t* bank, int R, int Np, int C, const int32_t* index, int B, int N, uint16_t* out, cs_stream stream);
+int cs_forward_select(cs_handle h, const float* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre, int R,
+                      const int32_t* exclude, int B, int N, int H, int W, float* score_out, float* attn_out, int head_id, float* mean_out,
+                      int32_t* index_out, float* sim_out /* NULL or (B, R) */, cs_stream stream);
+int cs_forward_select_u8(cs_handle h, const cs_u8_image* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre, int R,
+                         const int32_t* exclude, int B, int N, int H, int W, const float* mean3, const float* std3, float* score_out,
+                         float* attn_out, int head_id, float* mean_out, int32_t* index_out, float* sim_out, cs_stream stream);
 /* Overflow report.  With fp16 operands an activation beyond 65504 becomes inf and reaches the score map as NaN (nothing clamps in
  * the hot kernels); every forward counts the non-finite values of its score map on the device.  This call waits for the handle's last
  * forward, returns the count since the previous call in *count and resets it: > 0 means "switch to operand_dtype = 1 (bf16)". */

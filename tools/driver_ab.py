@@ -1,6 +1,6 @@
 """A/B of the predict and evaluate drivers of two source trees, same box: do both trees write the same bytes and return the same results?
 
-usage: driver_ab.py <parent tree> <new tree> [--jobs N] [--only predict|evaluate]
+usage: driver_ab.py <parent tree> <new tree> [--jobs N] [--only predict|evaluate] [--match TEXT] [--drop-result-key KEY ...]
 
 Each tree is a checkout with its own built library (the parent e.g. as a `git worktree`).  The input trees are generated once (the geometry of the
 driver tests: 5 queries and 4 references of 70 x 90 -> 56 x 72, batch 2, ViT-S two-layer synthetic weights; tests/nvs_tree.py for evaluate).  One
@@ -11,6 +11,9 @@ case directory; the long values -- files, rows, batches, metrics -- as a count a
 predict:  cache on / off x fused_input_stage auto / False x png_decoder host / gpu x batches_in_flight 1 / 3; every writer flag on; JPEG queries
           with jpeg_decoder=gpu.
 evaluate: cache x fused x png_decoder x gt_metric_maps files / compute x shuffle on / off; limit_test_batches=2.
+
+--match keeps the cases whose name holds TEXT; --drop-result-key leaves a key out of both trees' result dictionaries (one that only the new
+tree reports, e.g. reference_strategy: profiles/r15_reference_selection.txt).
 
 Every child runs under its own time limit; the script stops at the first one that ends with a non-zero status (it may have faulted the GPU: nothing
 more is started on it).  Written for the move of both drivers' loop into crossscore_amd/scoring.py (profiles/r13_driver_loop.txt).
@@ -30,8 +33,8 @@ BACK = "synthetic/dinov2-small-2l"
 
 CHILD = r'''
 import hashlib, json, os, sys
-tree, driver, case_dir = sys.argv[1], sys.argv[2], sys.argv[3]
-overrides = sys.argv[4:]
+tree, driver, case_dir, drop = sys.argv[1], sys.argv[2], sys.argv[3], [k for k in sys.argv[4].split(",") if k]
+overrides = sys.argv[5:]
 sys.path.insert(0, tree)
 os.makedirs(case_dir)
 os.chdir(case_dir)  # (evaluate's version directory is relative: log/<now>/test_empty_ckpt/version_0)
@@ -60,6 +63,8 @@ for d, ds, fs in os.walk(case_dir):
         n += 1
 rel = lambda v: os.path.relpath(v, case_dir) if os.path.isabs(v) else v
 res.pop("query_images_per_sec")
+for k in drop:
+    res.pop(k, None)
 res["files"] = sorted(rel(f) for f in res["files"])
 for k in ("out_dir", "version_dir"):
     if k in res:
@@ -121,6 +126,8 @@ def main():
     ap.add_argument("new")
     ap.add_argument("--jobs", type=int, default=1, help="children running side by side (each opens the GPU: keep it small)")
     ap.add_argument("--only", choices=("predict", "evaluate"))
+    ap.add_argument("--match", help="only the cases whose name holds this text")
+    ap.add_argument("--drop-result-key", action="append", default=[], help="a result key to leave out of the comparison (reported by one tree only)")
     args = ap.parse_args()
     trees = (("parent", os.path.abspath(args.parent)), ("new", os.path.abspath(args.new)))
     failed = []
@@ -128,7 +135,7 @@ def main():
     def child(tag, tree, root, k, driver, overrides):
         if failed:
             return None
-        r = subprocess.run(["timeout", "-k", "10", "240", sys.executable, "-c", CHILD, tree, driver, os.path.join(root, tag, f"case_{k:02}")] + overrides,
+        r = subprocess.run(["timeout", "-k", "10", "240", sys.executable, "-c", CHILD, tree, driver, os.path.join(root, tag, f"case_{k:02}"), ",".join(args.drop_result_key)] + overrides,
                            capture_output=True, text=True)
         if r.returncode != 0:
             failed.append((tag, k, r.returncode, r.stdout[-1500:], r.stderr[-1500:]))
@@ -136,7 +143,7 @@ def main():
         return r.stdout.strip().splitlines()[-1]
 
     with tempfile.TemporaryDirectory() as root:
-        todo = [c for c in cases(*make_inputs(root)) if args.only in (None, c[0])]
+        todo = [c for c in cases(*make_inputs(root)) if args.only in (None, c[0]) and (args.match is None or args.match in c[1])]
         with ThreadPoolExecutor(max_workers=max(1, args.jobs)) as ex:
             futs = [[ex.submit(child, tag, tree, root, k, driver, over) for tag, tree in trees] for k, (driver, _, over) in enumerate(todo)]
             differ = 0
