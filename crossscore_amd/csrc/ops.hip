@@ -78,6 +78,10 @@ int cs_op_attention_weights(const uint16_t* Q, const uint16_t* K, int ldq, int l
                             int heads, int Lq, int Lk, int dh, float q_scale, const float* lse, int head, float* out, cs_stream stream) {
   if (!Q || !K || !lse || !out || !supported_dh(dh) || !(q_scale >= 0.f) || head < 0 || head >= heads || Lq <= 0 || Lk <= 0 || Lq > 65535 || batch <= 0 || batch > 65535)
     return fail(CS_ERR_BAD_ARG, "attention_weights: bad arguments");
+  // the kernel reads Q and K rows in 16-byte chunks, like cs_attn_kernel: what cs_attn_check refuses for Q and K is refused here
+  if (ldq % 8 || ldk % 8) return fail(CS_ERR_BAD_ARG, "attention_weights: row strides must keep 16-byte rows");
+  if (q_bs % 8 || k_bs % 8) return fail(CS_ERR_BAD_ARG, "attention_weights: batch strides must keep 16-byte rows");
+  if ((long long)Lk * ldk >= (1ll << 30)) return fail(CS_ERR_BAD_ARG, "attention_weights: Lk * row stride must stay below 2^30 elements");
   CsAttnParams a{};
   a.Q = Q; a.K = K; a.ldq = ldq; a.ldk = ldk; a.q_bs = q_bs; a.k_bs = k_bs; a.Lq = Lq; a.Lk = Lk; a.heads = heads;
   a.scale_log2e = q_scale == 0.f ? LOG2E / std::sqrt((float)dh) : q_scale; a.lse = const_cast<float*>(lse);

@@ -257,6 +257,8 @@ int cs_op_head_score(const uint16_t* A, int lda, const uint16_t* W, int ldw, int
 int cs_op_attention(const uint16_t* Q, const uint16_t* K, const uint16_t* V, uint16_t* O, int ldq, int ldk, int ldv,
                     int ldo, long long q_bs, long long k_bs, long long v_bs, long long o_bs, int batch, int heads,
                     int Lq, int Lk, int dh, float q_scale, float* lse, cs_stream stream);
+/* out[b][q][k] = 2^(q_scale * q.k - lse[b][head][q]) for ONE head, lse from cs_op_attention.  Q and K as there: row and batch strides
+ * multiples of 8 elements, Lk * ldk below 2^30 (CS_ERR_BAD_ARG otherwise, before any launch). */
 int cs_op_attention_weights(const uint16_t* Q, const uint16_t* K, int ldq, int ldk, long long q_bs, long long k_bs,
                             int batch, int heads, int Lq, int Lk, int dh, float q_scale, const float* lse, int head,
                             float* out, cs_stream stream);

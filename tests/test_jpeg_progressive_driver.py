@@ -100,7 +100,11 @@ def _jpeg_gt(tree):
     from PIL import Image
 
     n = 0
-    for d, _, fs in os.walk(tree):
+    for d, dirs, fs in os.walk(tree):
+        # the file system's directory order must not decide which file gets which options: PIL cannot write the two 720 x 540 noise frames as a
+        # progressive file at 4:4:4, or at 4:2:2 with restart markers (its whole-file buffer of width x height bytes is too small: "Suspension not
+        # allowed here").  In sorted order they get 4:2:2 progressive and 4:2:0 baseline with restart markers
+        dirs.sort()
         if os.path.basename(d) != "gt":
             continue
         for f in sorted(fs):
