@@ -90,6 +90,12 @@ SYMBOLS = {
     "cs_op_gather_tokens": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "cs_forward_select": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "cs_forward_select_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _fp, _fp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cs_op_group_descriptors": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "cs_op_select_references_grouped": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    "cs_op_gather_tokens_ex": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp, _i]),
+    "cs_forward_select_grouped": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cs_forward_select_grouped_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _fp, _fp, _vp, _vp, _i, _vp, _vp,
+                                          _vp, _vp]),
     "cs_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "cs_nonfinite_count": (_i, [_vp, C.POINTER(C.c_longlong)]),
     "cs_forward_stats": (_i, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_char_p, _sz]),

@@ -131,6 +131,7 @@ void cs_destroy(cs_handle h) {
   if (h->ev_fork) hipEventDestroy(h->ev_fork);
   if (h->nonfinite) hipFree(h->nonfinite);
   for (auto& u : h->u8_slot) { if (u.host) hipHostFree(u.host); if (u.ev) hipEventDestroy(u.ev); }
+  stage_free(h->sel_ring);
   for (auto& r : h->recs) { hipEventDestroy(r.a); hipEventDestroy(r.b); }
   for (auto& kv : h->taps) if (kv.second.d) hipFree(kv.second.d);
   delete h;

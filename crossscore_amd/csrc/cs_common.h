@@ -217,6 +217,10 @@ struct CsU8Desc {
   int row_bytes, crop_y, crop_x, pad_;
 };
 
+// Grouped reference selection (select.hip): what the host resolves per query -- the first bank row of its group, the group's rows, the row of
+// the (G, C) centres it is centred with.  Checked on the host, uploaded with the call, clamped again where the device reads it.
+struct CsSelTriple { int start, len, centre; };
+
 // Encoder "token panel" kernel (panel.hip): one launch per DINOv2 layer does, for 128-row panels of the residual stream,
 //   x += attn_o Wo'^T + bo'                 (attention output projection, LayerScale folded; HF modeling_dinov2.py:249-252,365-370)
 //   x += GELU(LN2(x) W1'^T + b1') W2'^T + b2'   (norm2 + MLP + LayerScale; HF:373-378, 293-297)
@@ -354,7 +358,12 @@ hipError_t cs_descriptor_centre_launch(const float* mean, int R, int C, float* c
 hipError_t cs_descriptor_unit_launch(const float* mean, int I, int C, const float* centre, float* unit, hipStream_t st);
 hipError_t cs_similarity_launch(const float* q, int B, const float* bank, int R, int C, float* sim, hipStream_t st);
 hipError_t cs_topn_launch(const float* sim, int B, int R, const int32_t* exclude, int N, int32_t* index, hipStream_t st);
-hipError_t cs_gather_tokens_launch(const h16_t* bank, int R, int Np, int C, const int32_t* index, int slots, h16_t* out, hipStream_t st);
+hipError_t cs_gather_tokens_launch(const h16_t* bank, int R, int Np, int C, const int32_t* index, int slots, int blank, h16_t* out, hipStream_t st);
+hipError_t cs_group_centre_launch(const float* mean, const int32_t* offsets, int G, int R, int C, float* centre, hipStream_t st);
+hipError_t cs_group_unit_launch(const float* mean, const int32_t* offsets, int G, int rows, int R, int C, const float* centre, float* unit, hipStream_t st);
+hipError_t cs_query_unit_launch(const float* mean, int B, int C, const CsSelTriple* trip, int R, int G, const float* centre, float* unit, hipStream_t st);
+hipError_t cs_group_similarity_launch(const float* q, int B, const float* bank, int R, int G, int C, const CsSelTriple* trip, int S, float* sim, hipStream_t st);
+hipError_t cs_group_topn_launch(const float* sim, int B, int S, int R, int G, const CsSelTriple* trip, const int32_t* exclude, int N, int32_t* index, hipStream_t st);
 // gtsum.hip
 hipError_t cs_metric_map_sums_launch(const uint16_t* ssim, const uint16_t* mae, int B, int H, int W, int row_elems, long long image_stride,
                                      uint64_t* sums, hipStream_t st);

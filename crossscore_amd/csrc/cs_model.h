@@ -51,6 +51,19 @@ struct DecLayer {
 
 struct ProfRec { hipEvent_t a, b; int family; double flops; double bytes; };
 
+// Small host arrays on their way to the device (the grouped selection's offsets and per-query triples): a ring of pinned buffers, each reused
+// only behind the event recorded after its asynchronous copy -- the copy of SLOTS calls ago, long done -- so that no call waits for its own.
+// A slot can also own device memory: where the copy lands, and scratch of the kernels that read it (the single-op entry points have no
+// workspace); its event is then recorded behind those kernels.
+struct StageRing {
+  static constexpr int SLOTS = 4;
+  struct Slot { void* host = nullptr; void* dev = nullptr; size_t cap = 0, dev_cap = 0; int device = -1; hipEvent_t ev = nullptr; bool used = false; };
+  Slot slot[SLOTS];
+  int next = 0;
+};
+int stage_take(StageRing& r, size_t bytes, size_t dev_bytes, StageRing::Slot** out);  // forward.hip
+void stage_free(StageRing& r);
+
 }  // namespace cs_host
 using namespace cs_host;
 
@@ -98,6 +111,7 @@ struct cs_model {
   struct U8Slot { CsU8Desc* host = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; };
   U8Slot u8_slot[U8_SLOTS];
   int u8_next = 0;
+  StageRing sel_ring;  // cs_forward_select_grouped: the queries' triples on their way to the workspace, staged the same way
   std::vector<hipStream_t> lane_st_old;  // given back by cs_redraw_lane_streams; destroyed once the next forward has drawn their replacements
   int lanes_now = 0;  // cs_set_lanes: lanes of the next forwards (0 = as configured)
   hipStream_t last_stream = nullptr; hipEvent_t ev_done = nullptr;  // ordering of calls that arrive on different streams
@@ -131,6 +145,48 @@ inline int select_check(int B, int R, int C, int N, bool has_exclude) {
   return 0;
 }
 
+// ... and the grouped forms: N may exceed a group (the places left over are padded), so only the sizes are checked here
+inline int select_check_grouped(int B, int R, int C, int N) {
+  if (B <= 0 || R <= 0 || C <= 0 || N <= 0) return fail(CS_ERR_BAD_ARG, "select_references_grouped: empty batch, bank or selection");
+  if (N > 32 || R > 65536 || C % 4 || B > 65535) return fail(CS_ERR_UNSUPPORTED, "select_references_grouped: built for N <= 32, R <= 65536, C a multiple of 4 (N %d, R %d, C %d)", N, R, C);
+  return 0;
+}
+
+// offsets (G + 1) of a grouped bank of R rows: start at 0, increase strictly, end inside the bank.  *S_out: the longest group.
+inline int group_offsets_check(const int32_t* offsets, int G, int R, int* S_out) {
+  if (!offsets || G <= 0 || G > 65535 || R <= 0) return fail(CS_ERR_BAD_ARG, "grouped bank: offsets missing, or G = %d outside [1, 65535]", G);
+  if (offsets[0] != 0) return fail(CS_ERR_BAD_ARG, "grouped bank: offsets[0] = %d, must be 0", offsets[0]);
+  int S = 0;
+  for (int g = 0; g < G; ++g) {
+    if (offsets[g + 1] <= offsets[g]) return fail(CS_ERR_BAD_ARG, "grouped bank: offsets must increase strictly (offsets[%d] = %d, offsets[%d] = %d)", g, offsets[g], g + 1, offsets[g + 1]);
+    S = std::max(S, offsets[g + 1] - offsets[g]);
+  }
+  if (offsets[G] > R) return fail(CS_ERR_BAD_ARG, "grouped bank: offsets[G] = %d exceeds the bank's %d rows", offsets[G], R);
+  if (S_out) *S_out = S;
+  return 0;
+}
+
+// the row whose tokens fill a query's missing places: -1 (zeros), or a bank row that belongs to no group
+inline int blank_row_check(int blank_row, const int32_t* offsets, int G, int R) {
+  if (blank_row < -1 || blank_row >= R || (blank_row >= 0 && blank_row < offsets[G]))
+    return fail(CS_ERR_BAD_ARG, "grouped bank: blank_row = %d must be -1 or a row in [%d, %d), behind every group", blank_row, offsets[G], R);
+  return 0;
+}
+
+inline int query_groups_check(const int32_t* query_group, int B, int G) {
+  if (!query_group) return fail(CS_ERR_BAD_ARG, "grouped selection: query_group missing");
+  for (int b = 0; b < B; ++b)
+    if (query_group[b] < 0 || query_group[b] >= G) return fail(CS_ERR_BAD_ARG, "grouped selection: query %d names group %d of %d", b, query_group[b], G);
+  return 0;
+}
+
+inline void fill_triples(const int32_t* query_group, int B, const int32_t* offsets, CsSelTriple* trip) {
+  for (int b = 0; b < B; ++b) {
+    const int g = query_group[b];
+    trip[b] = CsSelTriple{offsets[g], offsets[g + 1] - offsets[g], g};
+  }
+}
+
 inline bool supported_dh(int dh) { return dh == 16 || dh == 48 || dh == 64 || dh == 96 || dh == 128 || dh == 192; }
 
 // forward.hip
@@ -151,6 +207,7 @@ struct Plan {
   float* mean_part; unsigned* mean_cnt;  // the head launch's per-image mean (CsGemmParams::mean_*)
   CsU8Desc* u8desc;                      // one-pass input stage: B query descriptors, then B * N_enc reference descriptors
   float *sel_mean, *sel_unit, *sel_sim;  // cs_forward_select: the queries' pooled / unit descriptors (B, C), similarities (B, R) unless the caller keeps them
+  CsSelTriple* sel_trip;                 // cs_forward_select_grouped: the queries' triples (B)
 };
 
 inline CsGemmParams gp(const h16_t* A, int lda, const h16_t* W, int ldw, int M, int N, int K, const float* bias, void* out, int ldc) {

@@ -59,6 +59,42 @@ int streams_overlap(hipStream_t a, hipStream_t b, bool* yes) {
   return rc;
 }
 
+// the next slot of the ring with at least `bytes` of pinned memory and, on the current device, `dev_bytes` of device memory
+int stage_take(StageRing& r, size_t bytes, size_t dev_bytes, StageRing::Slot** out) {
+  StageRing::Slot& s = r.slot[r.next];
+  r.next = (r.next + 1) % StageRing::SLOTS;
+  if (s.used) HIPCHK(hipEventSynchronize(s.ev));  // the work of four calls ago: long done
+  s.used = false;
+  int dev = -1;
+  if (dev_bytes) HIPCHK(hipGetDevice(&dev));
+  if (s.cap < bytes) {
+    if (s.host) HIPCHK(hipHostFree(s.host));
+    s.host = nullptr; s.cap = 0;
+    const size_t cap = std::max(bytes, (size_t)4096);
+    HIPCHK(hipHostMalloc(&s.host, cap, hipHostMallocDefault));
+    s.cap = cap;
+  }
+  if (dev_bytes && (s.dev_cap < dev_bytes || s.device != dev)) {
+    if (s.dev) HIPCHK(hipFree(s.dev));
+    s.dev = nullptr; s.dev_cap = 0;
+    const size_t cap = std::max(dev_bytes, (size_t)4096);
+    HIPCHK(hipMalloc(&s.dev, cap));
+    s.dev_cap = cap; s.device = dev;
+  }
+  if (!s.ev) HIPCHK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+  *out = &s;
+  return 0;
+}
+
+void stage_free(StageRing& r) {
+  for (StageRing::Slot& s : r.slot) {
+    if (s.host) hipHostFree(s.host);
+    if (s.dev) hipFree(s.dev);
+    if (s.ev) hipEventDestroy(s.ev);
+    s = StageRing::Slot{};
+  }
+}
+
 }  // namespace cs_host
 
 namespace {
@@ -72,7 +108,7 @@ struct Arena {  // carve 256-byte aligned pieces out of the workspace
   }
 };
 
-Plan make_plan(const cs_model* m, int B, int N, int N_enc, int H, int W, char* base, int R_sel = 0, bool own_sim = false) {
+Plan make_plan(const cs_model* m, int B, int N, int N_enc, int H, int W, char* base, int R_sel = 0, bool own_sim = false, bool grouped = false) {
   Plan p{};
   const cs_config& c = m->cfg;
   p.B = B; p.N = N; p.H = H; p.W = W; p.C = c.hidden;
@@ -126,6 +162,7 @@ Plan make_plan(const cs_model* m, int B, int N, int N_enc, int H, int W, char* b
   p.sel_mean = a.take<float>(R_sel > 0 ? (size_t)B * C : 0);
   p.sel_unit = a.take<float>(R_sel > 0 ? (size_t)B * C : 0);
   p.sel_sim = a.take<float>(own_sim ? (size_t)B * R_sel : 0);
+  p.sel_trip = a.take<CsSelTriple>(grouped ? (size_t)B : 0);  // (a grouped call's R_sel is the longest group: its similarities are (B, S))
   p.total = a.off;
   return p;
 }
@@ -212,7 +249,11 @@ struct Chunk {
 // mode 0: full forward (query + reference images); mode 1: query images + cached reference tokens (`ref_tokens`, fp16
 // [B][N][Np][C]); mode 2: encode `B` images as references into `tokens_out` (fp16 [B][Np][C]), no decoder; mode 3: query images + a bank of
 // reference tokens (`ref_tokens`, [R][Np][C]) from which each query's N views are selected by similarity and gathered (`sel`).
-struct SelectIn { const float *bank_unit, *centre; int R; const int32_t* exclude; int32_t* index_out; float* sim_out; };
+// Grouped (offsets != null): centre is (G, C), sim_out (B, S); offsets (G + 1) and query_group (B) are HOST arrays, blank_row fills missing places.
+struct SelectIn {
+  const float *bank_unit, *centre; int R; const int32_t* exclude; int32_t* index_out; float* sim_out;
+  const int32_t* offsets = nullptr; int G = 0; const int32_t* query_group = nullptr; int blank_row = -1;
+};
 struct Fwd {
   cs_model* h; int mode;
   const float *query, *refs; const h16_t* ref_tokens; h16_t* tokens_out;
@@ -223,6 +264,7 @@ struct Fwd {
   const SelectIn* sel = nullptr;  // mode 3
   int bf = 0;        // 16-bit operand type of every activation buffer and packed weight: 0 IEEE half, 1 bfloat16
   int N_enc = 0;     // reference views that go through the encoder with their query
+  int S_sel = 0;     // (grouped selection) rows of the longest group
   Plan p{};          // (workspace)
   int u8_span = 0;   // (uint8 descriptors) source rows one patch row reaches, at most
   int NL = 1;        // (lanes) lanes of this call, and their streams: the caller's when there is one lane
@@ -242,8 +284,15 @@ struct Fwd {
     if (mode == 2 && (!have_q || !tokens_out)) return fail(CS_ERR_BAD_ARG, "null tensor");
     if (mode == 3) {
       if (!have_q || !ref_tokens || !score_out || !sel || !sel->bank_unit || !sel->centre || !sel->index_out) return fail(CS_ERR_BAD_ARG, "null tensor");
-      if (B > 0 && N > 0)
+      if (sel->offsets) {
+        if (B > 0 && N > 0)
+          if (int r = select_check_grouped(B, sel->R, c.hidden, N)) return r;
+        if (int r = group_offsets_check(sel->offsets, sel->G, sel->R, &S_sel)) return r;
+        if (int r = blank_row_check(sel->blank_row, sel->offsets, sel->G, sel->R)) return r;
+        if (int r = query_groups_check(sel->query_group, B, sel->G)) return r;
+      } else if (B > 0 && N > 0) {
         if (int r = select_check(B, sel->R, c.hidden, N, sel->exclude != nullptr)) return r;
+      }
       if ((long long)B * N > 65535) return fail(CS_ERR_UNSUPPORTED, "cs_forward_select: more than 65535 reference slots in one call; split the batch");
     }
     if (u8 && (!u8->mean3 || !u8->std3 || !(u8->std3[0] > 0.f) || !(u8->std3[1] > 0.f) || !(u8->std3[2] > 0.f)))
@@ -262,9 +311,10 @@ struct Fwd {
   // ---- step 2: workspace (grown when this call needs more), carved into p ----
   int ensure_workspace() {
     const int N_plan = mode == 2 ? 0 : N;
-    const int R_sel = mode == 3 ? sel->R : 0;
+    const bool grouped = mode == 3 && sel->offsets;
+    const int R_sel = mode == 3 ? (grouped ? S_sel : sel->R) : 0;
     const bool own_sim = mode == 3 && !sel->sim_out;
-    const size_t need = make_plan(h, B, N_plan, N_enc, H, W, nullptr, R_sel, own_sim).total;
+    const size_t need = make_plan(h, B, N_plan, N_enc, H, W, nullptr, R_sel, own_sim, grouped).total;
     reap_retired(h, false);
     if (need > h->ws_bytes) {
       // grow: the old workspace may still be in use by work queued earlier (on this or another stream), so it is retired behind an
@@ -279,7 +329,19 @@ struct Fwd {
       HIPCHK(hipMalloc(&h->ws, need));
       h->ws_bytes = need;
     }
-    p = make_plan(h, B, N_plan, N_enc, H, W, h->ws, R_sel, own_sim);
+    p = make_plan(h, B, N_plan, N_enc, H, W, h->ws, R_sel, own_sim, grouped);
+    return 0;
+  }
+
+  // ---- step 3 (grouped selection): the queries' triples -> workspace, the way the uint8 descriptors travel below ----
+  int stage_select_triples() {
+    if (mode != 3 || !sel->offsets) return 0;
+    StageRing::Slot* sl = nullptr;
+    if (int r = stage_take(h->sel_ring, (size_t)B * sizeof(CsSelTriple), 0, &sl)) return r;
+    fill_triples(sel->query_group, B, sel->offsets, static_cast<CsSelTriple*>(sl->host));
+    HIPCHK(hipMemcpyAsync(p.sel_trip, sl->host, (size_t)B * sizeof(CsSelTriple), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(sl->ev, st));
+    sl->used = true;
     return 0;
   }
 
@@ -607,10 +669,19 @@ struct Fwd {
     const int C = p.C;
     float* sim = sel->sim_out ? sel->sim_out : p.sel_sim;
     L.small("select_desc", [&] { return cs_token_descriptors_launch(p.q_bf, B, p.Np, C, bf, p.sel_mean, L.st); });
+    if (sel->offsets) {  // every query against its own slice of the bank and that slice's centre; missing places take the blank row's tokens
+      const int R = sel->R, G = sel->G, S = S_sel;
+      L.small("select_unit_grouped", [&] { return cs_query_unit_launch(p.sel_mean, B, C, p.sel_trip, R, G, sel->centre, p.sel_unit, L.st); });
+      L.small("select_sim_grouped", [&] { return cs_group_similarity_launch(p.sel_unit, B, sel->bank_unit, R, G, C, p.sel_trip, S, sim, L.st); });
+      L.small("select_topn_grouped", [&] { return cs_group_topn_launch(sim, B, S, R, G, p.sel_trip, sel->exclude, N, sel->index_out, L.st); });
+      L.misc("select_gather_blank", 32, 0, 4.0 * B * N * p.Np * C,
+             [&] { return cs_gather_tokens_launch(ref_tokens, R, p.Np, C, sel->index_out, B * N, sel->blank_row, p.mem_bf, L.st); });
+      return;
+    }
     L.small("select_unit", [&] { return cs_descriptor_unit_launch(p.sel_mean, B, C, sel->centre, p.sel_unit, L.st); });
     L.small("select_sim", [&] { return cs_similarity_launch(p.sel_unit, B, sel->bank_unit, sel->R, C, sim, L.st); });
     L.small("select_topn", [&] { return cs_topn_launch(sim, B, sel->R, sel->exclude, N, sel->index_out, L.st); });
-    L.misc("select_gather", 32, 0, 4.0 * B * N * p.Np * C, [&] { return cs_gather_tokens_launch(ref_tokens, sel->R, p.Np, C, sel->index_out, B * N, p.mem_bf, L.st); });
+    L.misc("select_gather", 32, 0, 4.0 * B * N * p.Np * C, [&] { return cs_gather_tokens_launch(ref_tokens, sel->R, p.Np, C, sel->index_out, B * N, -1, p.mem_bf, L.st); });
   }
 
   // ---- step 9: taps: the decoder's inputs = final LayerNorm of the patch tokens + multi-view PE (core.py:141-153,93-98): query rows fp32, reference rows 16 bit ----
@@ -728,6 +799,7 @@ struct Fwd {
     // the head launch's arrival counters (per-image mean in the same launch) start from zero; its finisher waves leave them at zero again, but the
     // workspace may have been carved differently by the previous call
     if (mean_out && mode != 2) HIPCHK(hipMemsetAsync(p.mean_cnt, 0, (size_t)B * sizeof(unsigned), st));
+    if (int r = stage_select_triples()) return r;
     if (int r = stage_u8_descriptors()) return r;
     if (int r = ensure_lanes()) return r;
     Launcher LL[CS_MAX_LANES] = {Launcher{h, lst[0]}, Launcher{h, lst[1]}, Launcher{h, lst[2]}, Launcher{h, lst[3]}};
@@ -828,6 +900,29 @@ int cs_forward_select_u8(cs_handle h, const cs_u8_image* query, const uint16_t* 
                          float* attn_out, int head_id, float* mean_out, int32_t* index_out, float* sim_out, cs_stream stream) {
   const U8In u{query, nullptr, mean3, std3};
   const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out};
+  Fwd f{h, 3, nullptr, nullptr, bank_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, &u};
+  f.sel = &s;
+  return forward_impl(f);
+}
+
+int cs_forward_select_grouped(cs_handle h, const float* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre, int R,
+                              const int32_t* offsets, int G, const int32_t* query_group, int blank_row, const int32_t* exclude, int B, int N, int H,
+                              int W, float* score_out, float* attn_out, int head_id, float* mean_out, int32_t* index_out, float* sim_out,
+                              cs_stream stream) {
+  if (!offsets) return fail(CS_ERR_BAD_ARG, "cs_forward_select_grouped: offsets missing");
+  const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out, offsets, G, query_group, blank_row};
+  Fwd f{h, 3, query, nullptr, bank_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, nullptr};
+  f.sel = &s;
+  return forward_impl(f);
+}
+
+int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre,
+                                 int R, const int32_t* offsets, int G, const int32_t* query_group, int blank_row, const int32_t* exclude, int B,
+                                 int N, int H, int W, const float* mean3, const float* std3, float* score_out, float* attn_out, int head_id,
+                                 float* mean_out, int32_t* index_out, float* sim_out, cs_stream stream) {
+  if (!offsets) return fail(CS_ERR_BAD_ARG, "cs_forward_select_grouped_u8: offsets missing");
+  const U8In u{query, nullptr, mean3, std3};
+  const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out, offsets, G, query_group, blank_row};
   Fwd f{h, 3, nullptr, nullptr, bank_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, &u};
   f.sel = &s;
   return forward_impl(f);

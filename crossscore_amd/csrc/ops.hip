@@ -5,6 +5,8 @@
 
 #include <cmath>
 #include <cstring>
+#include <mutex>
+#include <vector>
 
 extern "C" {
 
@@ -572,11 +574,75 @@ int cs_op_select_references(const float* q_unit, int B, const float* bank_unit, 
   return 0;
 }
 
-int cs_op_gather_tokens(const uint16_t* bank, int R, int Np, int C, const int32_t* index, int B, int N, uint16_t* out, cs_stream stream) {
+int cs_op_gather_tokens_ex(const uint16_t* bank, int R, int Np, int C, const int32_t* index, int B, int N, uint16_t* out, cs_stream stream,
+                           int blank_row) {
   if (!bank || !index || !out || R <= 0 || Np <= 0 || C <= 0 || B <= 0 || N <= 0) return fail(CS_ERR_BAD_ARG, "gather_tokens: bad arguments");
+  if (blank_row < -1 || blank_row >= R) return fail(CS_ERR_BAD_ARG, "gather_tokens: blank_row = %d outside [-1, %d)", blank_row, R);
   if (((long long)Np * C) % 8 || (long long)B * N > 65535) return fail(CS_ERR_UNSUPPORTED, "gather_tokens: Np * C must be a multiple of 8 and B * N <= 65535");
-  HIPCHK(cs_gather_tokens_launch(bank, R, Np, C, index, B * N, out, (hipStream_t)stream));
+  HIPCHK(cs_gather_tokens_launch(bank, R, Np, C, index, B * N, blank_row, out, (hipStream_t)stream));
   return 0;
+}
+
+int cs_op_gather_tokens(const uint16_t* bank, int R, int Np, int C, const int32_t* index, int B, int N, uint16_t* out, cs_stream stream) {
+  return cs_op_gather_tokens_ex(bank, R, Np, C, index, B, N, out, stream, -1);
+}
+
+// The grouped forms have no handle and no workspace: the host arrays they resolve travel through a process-wide ring whose slots own the device
+// side of the copy and the kernels' scratch (StageRing).  Every check comes first: a refused call has queued nothing.
+namespace {
+std::mutex g_stage_mutex;
+StageRing g_stage;
+
+// `bytes` of src -> the head of a slot's device memory of bytes (rounded up to 256) + scratch_bytes, asynchronously on st
+int stage_upload(const void* src, size_t bytes, size_t scratch_bytes, hipStream_t st, StageRing::Slot** sl) {
+  if (int r = stage_take(g_stage, bytes, ((bytes + 255) & ~size_t(255)) + scratch_bytes, sl)) return r;
+  memcpy((*sl)->host, src, bytes);
+  HIPCHK(hipMemcpyAsync((*sl)->dev, (*sl)->host, bytes, hipMemcpyHostToDevice, st));
+  return 0;
+}
+// behind the last kernel that reads the slot's device memory
+int stage_done(StageRing::Slot* sl, hipStream_t st) {
+  HIPCHK(hipEventRecord(sl->ev, st));
+  sl->used = true;
+  return 0;
+}
+}  // namespace
+
+int cs_op_group_descriptors(const float* mean, int R, int C, const int32_t* offsets, int G, float* centre_out, float* unit_out, cs_stream stream) {
+  if (!mean || !centre_out || !unit_out || R <= 0 || C <= 0) return fail(CS_ERR_BAD_ARG, "group_descriptors: bad arguments");
+  if (C % 64 || R > 65536) return fail(CS_ERR_UNSUPPORTED, "group_descriptors: C must be a multiple of 64 and R <= 65536");
+  if (int r = group_offsets_check(offsets, G, R, nullptr)) return r;
+  hipStream_t st = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(g_stage_mutex);
+  StageRing::Slot* sl = nullptr;
+  if (int r = stage_upload(offsets, (size_t)(G + 1) * sizeof(int32_t), 0, st, &sl)) return r;
+  const int32_t* d_off = static_cast<const int32_t*>(sl->dev);
+  HIPCHK(cs_group_centre_launch(mean, d_off, G, R, C, centre_out, st));
+  HIPCHK(cs_group_unit_launch(mean, d_off, G, offsets[G], R, C, centre_out, unit_out, st));
+  return stage_done(sl, st);
+}
+
+int cs_op_select_references_grouped(const float* q_mean, int B, const int32_t* query_group, const float* bank_unit, const float* centre,
+                                    const int32_t* offsets, int G, int R, int C, const int32_t* exclude, int N, int32_t* index_out, float* sim_out,
+                                    cs_stream stream) {
+  if (!q_mean || !bank_unit || !centre || !index_out || !sim_out) return fail(CS_ERR_BAD_ARG, "select_references_grouped: null tensor");
+  if (int r = select_check_grouped(B, R, C, N)) return r;
+  int S = 0;
+  if (int r = group_offsets_check(offsets, G, R, &S)) return r;
+  if (int r = query_groups_check(query_group, B, G)) return r;
+  std::vector<CsSelTriple> trip((size_t)B);
+  fill_triples(query_group, B, offsets, trip.data());
+  hipStream_t st = (hipStream_t)stream;
+  std::lock_guard<std::mutex> lock(g_stage_mutex);
+  StageRing::Slot* sl = nullptr;
+  const size_t tb = (size_t)B * sizeof(CsSelTriple);
+  if (int r = stage_upload(trip.data(), tb, (size_t)B * C * sizeof(float), st, &sl)) return r;
+  const CsSelTriple* t = static_cast<const CsSelTriple*>(sl->dev);
+  float* q_unit = reinterpret_cast<float*>(static_cast<char*>(sl->dev) + ((tb + 255) & ~size_t(255)));  // the queries' units: scratch
+  HIPCHK(cs_query_unit_launch(q_mean, B, C, t, R, G, centre, q_unit, st));
+  HIPCHK(cs_group_similarity_launch(q_unit, B, bank_unit, R, G, C, t, S, sim_out, st));
+  HIPCHK(cs_group_topn_launch(sim_out, B, S, R, G, t, exclude, N, index_out, st));
+  return stage_done(sl, st);
 }
 
 }  // extern "C"

@@ -653,7 +653,7 @@ class InputStage:
         return U8Batch(images, size, self.mean_std, device=self.device)
 
 
-STRATEGIES = ("random", "similar")  # data.neighbour_config.strategy: the reference's sampler, and this build's choice by DINOv2 similarity (predict only)
+STRATEGIES = ("random", "similar")  # data.neighbour_config.strategy: the reference's sampler, and this build's choice by DINOv2 similarity
 
 
 class SimpleReferenceItems:
@@ -790,28 +790,47 @@ class ReferenceBank:
     `bank` is the model.SelectionBank the forwards take, `paths` the files in bank order, `images` their processed fp32 images (R, 3, h, w) when
     keep_images (the writer's image_reference output) -- else None.
 
+    groups (the test phase: nvs.NvsItems.groups, the candidate lists of the scenes this run scores) instead of paths: the bank holds the groups'
+    files one group after the other -- `offsets` -- and behind them one more row, `blank_row`: the all-zero placeholder image ("empty_image",
+    nvs_dataset.py:459-470), whose tokens stand in where a query's group has fewer than n_references files.  A query then chooses inside its own
+    group only (CrossScoreNet.forward_select(group=...)); a file that several groups list is held once per group.
+
     decoder: the run's PngDecoder (this_main.png_decoder / jpeg_decoder = gpu): a chunk's files are decoded on the device, `window` files per
     call; else PIL on `pool`.  from_u8: the one-pass input stage (encode_references_u8; no processed image exists, so not with keep_images)."""
 
     def __init__(self, net, stage: InputStage, paths: Sequence[str], size: Tuple[int, int], n_references: int, keep_images: bool = False,
-                 max_images: int = 4096, from_u8: bool = False, decoder: Optional[PngDecoder] = None, pool=None, chunk: int = 32, window: int = 64):
+                 max_images: int = 4096, from_u8: bool = False, decoder: Optional[PngDecoder] = None, pool=None, chunk: int = 32, window: int = 64,
+                 groups: Optional[Sequence[Sequence[str]]] = None):
         from .model import SelectionBank
-        self.paths = list(paths)
-        R = len(self.paths)
-        if R == 0:
-            raise ValueError("neighbour strategy similar: reference_dir holds no file")
-        if R > max_images:
-            raise ValueError(f"neighbour strategy similar keeps every reference's tokens: reference_dir holds {R} files, more than "
-                             f"this_main.reference_cache_max_images={max_images}")
-        if n_references > R:
-            raise ValueError(f"neighbour strategy similar: neighbour_config.cross={n_references} exceeds the {R} files of reference_dir")
+        self.offsets = None
+        if groups is not None:
+            groups = [[p for p in g if p != EMPTY] for g in groups]
+            if not groups or any(len(g) == 0 for g in groups):
+                raise ValueError("neighbour strategy similar: a query's candidate list holds no file")
+            self.offsets = np.concatenate([[0], np.cumsum([len(g) for g in groups])]).astype(np.int32)
+            self.paths = [p for g in groups for p in g] + [EMPTY]
+            R = len(self.paths)
+            if R > max_images:
+                raise ValueError(f"neighbour strategy similar keeps every candidate's tokens: the {len(groups)} candidate lists of this run hold "
+                                 f"{R - 1} files (+ 1 placeholder), more than this_main.reference_cache_max_images={max_images}")
+        else:
+            self.paths = list(paths)
+            R = len(self.paths)
+            if R == 0:
+                raise ValueError("neighbour strategy similar: reference_dir holds no file")
+            if R > max_images:
+                raise ValueError(f"neighbour strategy similar keeps every reference's tokens: reference_dir holds {R} files, more than "
+                                 f"this_main.reference_cache_max_images={max_images}")
+            if n_references > R:
+                raise ValueError(f"neighbour strategy similar: neighbour_config.cross={n_references} exceeds the {R} files of reference_dir")
+        n_files = R if groups is None else R - 1  # (the placeholder is no file)
         oh, ow = size
         from_u8 = bool(from_u8) and not keep_images
         step = max(1, min(int(chunk), int(window) if decoder is not None else int(chunk)))
         tokens = None
         self.images = torch.empty((R, 3, oh, ow), dtype=torch.float32, device=stage.device) if keep_images else None
-        for r0 in range(0, R, step):
-            part = self.paths[r0:r0 + step]
+        for r0 in range(0, n_files, step):
+            part = self.paths[r0:min(r0 + step, n_files)]
             if decoder is not None:
                 handle = decoder.decode(part)
                 handle.wait(torch.cuda.current_stream(stage.device))
@@ -821,7 +840,9 @@ class ReferenceBank:
                 imgs = list(pool.map(read_image_u8, part)) if pool is not None else [read_image_u8(p) for p in part]
             for p, im in zip(part, imgs):
                 if stage.geometry(int(im.shape[0]), int(im.shape[1]))[1][2:] != (oh, ow):
-                    raise ValueError(f"{p}: processed size differs from the query's {oh}x{ow}")
+                    raise ValueError(f"{p}: processed size differs from the query's {oh}x{ow}" +
+                                     (": one bank has one patch grid; this_main.crop_mode=dataset_default gives the images of every scene one size"
+                                      if groups is not None else ""))
             if from_u8:
                 tok = net.encode_references_u8(stage.batch([stage.describe(im) for im in imgs], (oh, ow)))
             else:
@@ -832,13 +853,27 @@ class ReferenceBank:
             if tokens is None:
                 tokens = torch.empty((R,) + tuple(tok.shape[1:]), dtype=tok.dtype, device=tok.device)
             tokens[r0:r0 + len(part)] = tok
-        mean, centre, unit = net.reference_descriptors(tokens)
-        self.bank = SelectionBank(tokens, mean, centre, unit, n_references)
-        self._real = {os.path.realpath(p): i for i, p in reversed(list(enumerate(self.paths)))}
+        if groups is not None:  # the placeholder's row: zeros BEFORE T.Normalize, as load_batch and ReferenceTokenCache feed "empty_image"
+            if from_u8:
+                tokens[R - 1] = net.encode_references_u8(stage.batch([stage.placeholder((oh, ow))], (oh, ow)))[0]
+            else:
+                buf = self.images[R - 1:] if keep_images else torch.empty((1, 3, oh, ow), dtype=torch.float32, device=stage.device)
+                buf[0] = stage.zero_image_value[:, None, None]
+                tokens[R - 1] = net.encode_references(buf)[0]
+            mean, centre, unit = net.reference_descriptors(tokens, self.offsets)
+            self.bank = SelectionBank(tokens, mean, centre, unit, n_references, self.offsets, R - 1)
+        else:
+            mean, centre, unit = net.reference_descriptors(tokens)
+            self.bank = SelectionBank(tokens, mean, centre, unit, n_references)
+        self._real = {os.path.realpath(p): i for i, p in reversed(list(enumerate(self.paths[:n_files])))}
 
     def __len__(self) -> int:
         return len(self.paths)
 
-    def index_of(self, path: str) -> int:
-        """The bank index of the file `path` names (by real path), or -1."""
-        return self._real.get(os.path.realpath(path), -1)
+    def index_of(self, path: str, group: Optional[int] = None) -> int:
+        """The bank index of the file `path` names (by real path), or -1; with `group`, its row inside that group of a grouped bank."""
+        if group is None or self.offsets is None:
+            return self._real.get(os.path.realpath(path), -1)
+        real = os.path.realpath(path)
+        lo, hi = int(self.offsets[group]), int(self.offsets[group + 1])
+        return next((i for i in range(lo, hi) if os.path.realpath(self.paths[i]) == real), -1)

@@ -271,7 +271,8 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
                         calibrate=False,  # inherited: the test loop has never calibrated its batches in flight
                         extra_files=gt_files, decode_host=lambda its, zr, pool, skip: decode_eval(its, zr, pool, skip, compute_gt),
                         from_window=fetch_eval,
-                        check_size=check_size, after_submit=gt_and_stats, on_consume=batch_stats)
+                        check_size=check_size, after_submit=gt_and_stats, on_consume=batch_stats,
+                        reference_groups=items.groups if items.candidates else None)  # neighbour strategy similar: each scene's candidate lists
     # one collective that carries the metrics and any failure of a rank's output stage (a rank that raised on its own before it would leave
     # the others waiting in it): the failure is re-raised behind the collective, as in predict.py
     failure, files = run.failure, run.files

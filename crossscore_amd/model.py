@@ -119,20 +119,53 @@ class U8Batch:
 
 class SelectionBank:
     """What forward_select chooses from: tokens (R, h*w, C) in the module's operand type (encode_references of every candidate, contiguous),
-    their descriptors mean / unit (R, C) and centre (C) fp32 (CrossScoreNet.reference_descriptors), and n_references, the views a query takes."""
-    __slots__ = ("tokens", "mean", "centre", "unit", "n_references")
+    their descriptors mean / unit (R, C) and centre (C) fp32 (CrossScoreNet.reference_descriptors), and n_references, the views a query takes.
+    A grouped bank also has `offsets` (G + 1 host integers: group g is the rows offsets[g] .. offsets[g + 1] - 1, the rows from offsets[G] on
+    belong to no group), a centre per group (G, C), and `blank_row`: -1, or the row behind every group whose tokens stand in where a query's
+    group is shorter than n_references (the encoder's tokens of the all-zero placeholder image)."""
+    __slots__ = ("tokens", "mean", "centre", "unit", "n_references", "offsets", "blank_row", "row_place")
 
-    def __init__(self, tokens: torch.Tensor, mean: torch.Tensor, centre: torch.Tensor, unit: torch.Tensor, n_references: int):
+    def __init__(self, tokens: torch.Tensor, mean: torch.Tensor, centre: torch.Tensor, unit: torch.Tensor, n_references: int, offsets=None,
+                 blank_row: int = -1):
         if tokens.dim() != 3 or not tokens.is_cuda or not tokens.is_contiguous():
             raise ValueError("SelectionBank.tokens must be a contiguous CUDA tensor (R, h*w, C)")
         R, _, Cc = tokens.shape
-        for name, t, shape in (("mean", mean, (R, Cc)), ("centre", centre, (Cc,)), ("unit", unit, (R, Cc))):
+        if offsets is None:
+            if int(blank_row) != -1:
+                raise ValueError("SelectionBank.blank_row needs a grouped bank (offsets)")
+            centre_shape = (Cc,)
+        else:
+            offsets = _group_offsets(offsets, R)
+            centre_shape = (len(offsets) - 1, Cc)
+            if not (int(blank_row) == -1 or int(offsets[-1]) <= int(blank_row) < R):
+                raise ValueError(f"SelectionBank.blank_row = {blank_row} must be -1 or a row in [{int(offsets[-1])}, {R}), behind every group")
+        for name, t, shape in (("mean", mean, (R, Cc)), ("centre", centre, centre_shape), ("unit", unit, (R, Cc))):
             if tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != tokens.device or not t.is_contiguous():
                 raise ValueError(f"SelectionBank.{name} must be a contiguous fp32 tensor {shape} on the tokens' device")
         self.tokens, self.mean, self.centre, self.unit, self.n_references = tokens, mean, centre, unit, int(n_references)
+        self.offsets, self.blank_row = offsets, int(blank_row)
+        # (R) int64 on the device: a row's place inside its group = its column of a query's similarities (0 for the rows behind the groups)
+        self.row_place = None
+        if offsets is not None:
+            place = np.zeros(R, dtype=np.int64)
+            for lo, hi in zip(offsets[:-1], offsets[1:]):
+                place[lo:hi] = np.arange(hi - lo)
+            self.row_place = torch.from_numpy(place).to(tokens.device)
+
+    @property
+    def longest_group(self) -> int:
+        return int(len(self)) if self.offsets is None else int(np.diff(self.offsets).max())
 
     def __len__(self) -> int:
         return int(self.tokens.shape[0])
+
+
+def _group_offsets(offsets, R: int) -> np.ndarray:
+    """offsets of a grouped bank of R rows as a contiguous int32 array, checked: they start at 0, increase strictly and end inside the bank"""
+    o = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+    if o.size < 2 or o[0] != 0 or np.any(np.diff(o) <= 0) or o[-1] > R:
+        raise ValueError(f"group offsets must start at 0, increase strictly and end inside the bank's {R} rows: {o.tolist()[:8]}{'...' if o.size > 8 else ''}")
+    return o.astype(np.int32)
 
 
 class _Node(torch.nn.Module):
@@ -493,9 +526,10 @@ class CrossScoreNet(torch.nn.Module):
 
     # -- reference selection by similarity: the choice of each query's views is made on the device ----------------------
     @torch.no_grad()
-    def reference_descriptors(self, tokens):
+    def reference_descriptors(self, tokens, offsets=None):
         """(R, h*w, C) tokens from encode_references -> (mean (R, C), centre (C), unit (R, C)) fp32: the pooled descriptors of the candidates,
-        their mean over the bank and the centred unit vectors forward_select compares a query's descriptor with."""
+        their mean over the bank and the centred unit vectors forward_select compares a query's descriptor with.  With `offsets` (G + 1, see
+        SelectionBank) every group has its own centre, (G, C), and the unit rows behind the last group are zeros."""
         if tokens.dim() != 3 or not tokens.is_cuda or tokens.dtype not in (torch.float16, torch.bfloat16):
             raise ValueError("expected CUDA tokens (R, h*w, C) in a 16-bit operand type")
         t = tokens.contiguous()
@@ -506,16 +540,23 @@ class CrossScoreNet(torch.nn.Module):
             st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             mean = torch.empty((R, Cc), dtype=torch.float32, device=dev)
             centre = torch.empty((Cc,), dtype=torch.float32, device=dev)
-            unit = torch.empty((R, Cc), dtype=torch.float32, device=dev)
+            if offsets is not None:
+                off = _group_offsets(offsets, R)
+                centre = torch.empty((len(off) - 1, Cc), dtype=torch.float32, device=dev)
+            unit = (torch.empty if offsets is None else torch.zeros)((R, Cc), dtype=torch.float32, device=dev)
             code = _lib.DTYPE_BF16 if t.dtype == torch.bfloat16 else _lib.DTYPE_F16
             for r0 in range(0, R, 32768):  # (an image's mean does not depend on the launch it is part of)
                 r1 = min(R, r0 + 32768)
                 _lib.check(lib.cs_op_token_descriptors(C.c_void_p(t[r0:r1].data_ptr()), r1 - r0, Np, Cc, code, C.c_void_p(mean[r0:r1].data_ptr()), st))
+            if offsets is not None:
+                _lib.check(lib.cs_op_group_descriptors(C.c_void_p(mean.data_ptr()), R, Cc, off.ctypes.data_as(C.c_void_p), len(off) - 1,
+                                                       C.c_void_p(centre.data_ptr()), C.c_void_p(unit.data_ptr()), st))
+                return mean, centre, unit
             _lib.check(lib.cs_op_descriptor_centre(C.c_void_p(mean.data_ptr()), R, Cc, C.c_void_p(centre.data_ptr()), st))
             _lib.check(lib.cs_op_descriptor_unit(C.c_void_p(mean.data_ptr()), R, Cc, C.c_void_p(centre.data_ptr()), C.c_void_p(unit.data_ptr()), st))
         return mean, centre, unit
 
-    def _forward_select(self, query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, u8):
+    def _forward_select(self, query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, u8, group=None):
         N = int(bank.n_references if n_references is None else n_references)
         t = bank.tokens
         dev = t.device
@@ -545,15 +586,37 @@ class CrossScoreNet(torch.nn.Module):
             if tuple(exclude.shape) != (B,) or exclude.device != dev:
                 raise ValueError("exclude must hold one bank index (or -1) per query, on the bank's device")
             ex = exclude.to(torch.int32).contiguous()
+        grouped = bank.offsets is not None
+        if grouped:
+            if group is None:
+                raise ValueError("a grouped bank needs `group`: the group each query chooses from")
+            grp = np.ascontiguousarray(np.asarray(group.cpu() if isinstance(group, torch.Tensor) else group, dtype=np.int64).reshape(-1))
+            if grp.shape != (B,) or np.any(grp < 0) or np.any(grp >= len(bank.offsets) - 1):
+                raise ValueError(f"group must hold one group id in [0, {len(bank.offsets) - 1}) per query")
+            grp = grp.astype(np.int32)
+        elif group is not None:
+            raise ValueError("`group` needs a grouped bank (SelectionBank with offsets)")
         self._check_pe_mode(H, W)
         lib = _lib.load()
         handle = self._ensure_handle(dev)
         with torch.cuda.device(dev):
             score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
             index = torch.empty((B, N), dtype=torch.int32, device=dev)
-            sim = torch.empty((B, R), dtype=torch.float32, device=dev)
+            sim = torch.empty((B, bank.longest_group), dtype=torch.float32, device=dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
             for b0, b1 in self._sub_batches(B, N, h * w):
+                if grouped:  # (the host arrays are copied into a pinned slot inside the call: they need not outlive it)
+                    sel = (C.c_void_p(t.data_ptr()), C.c_void_p(bank.unit.data_ptr()), C.c_void_p(bank.centre.data_ptr()), R,
+                           bank.offsets.ctypes.data_as(C.c_void_p), len(bank.offsets) - 1, grp[b0:b1].ctypes.data_as(C.c_void_p), bank.blank_row,
+                           C.c_void_p(ex[b0:b1].data_ptr()) if ex is not None else None, b1 - b0, N, H, W)
+                    rest = (C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
+                            int(need_attn_weights_head_id), C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None,
+                            C.c_void_p(index[b0:b1].data_ptr()), C.c_void_p(sim[b0:b1].data_ptr()), C.c_void_p(stream))
+                    if u8:
+                        _lib.check(lib.cs_forward_select_grouped_u8(handle, query.c_array(b0, b1), *sel, query.mean, query.std, *rest))
+                    else:
+                        _lib.check(lib.cs_forward_select_grouped(handle, C.c_void_p(q[b0:b1].data_ptr()), *sel, *rest))
+                    continue
                 tail = (C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
                         int(need_attn_weights_head_id), C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None,
                         C.c_void_p(index[b0:b1].data_ptr()), C.c_void_p(sim[b0:b1].data_ptr()), C.c_void_p(stream))
@@ -566,23 +629,29 @@ class CrossScoreNet(torch.nn.Module):
             results = self._results(score, attn, mean_out)
             results["reference_index"] = index
             # the similarities of the chosen entries, in the order chosen (an index of -1, a query that ran out of candidates, reads entry 0)
-            results["reference_similarity"] = torch.gather(sim, 1, index.clamp(min=0).to(torch.int64))
+            if grouped:  # a column of sim is a place in the query's group; a padded place (-1) is NaN
+                picked = torch.gather(sim, 1, bank.row_place[index.clamp(min=0).to(torch.int64)])
+                results["reference_similarity"] = torch.where(index >= 0, picked, float("nan"))
+            else:
+                results["reference_similarity"] = torch.gather(sim, 1, index.clamp(min=0).to(torch.int64))
         return results
 
     @torch.no_grad()
     def forward_select(self, query_img, bank: "SelectionBank", exclude=None, need_attn_weights=False, need_attn_weights_head_id=0,
-                       return_mean=False, n_references=None):
+                       return_mean=False, n_references=None, group=None):
         """forward_cached() with each query's N = bank.n_references views chosen on the device: the bank entries most similar to the query's own
         pooled descriptor, descending, ties to the lower index, exclude[b] (int32 (B), -1 = none) left out.  The result also holds
         "reference_index" (B, N) int32 and "reference_similarity" (B, N) fp32; the score map, mean and attention weights are bit-identical to
-        forward_cached(query_img, bank.tokens[reference_index])."""
-        return self._forward_select(query_img, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, False)
+        forward_cached(query_img, bank.tokens[reference_index]).  A grouped bank needs `group`, one group id per query (host integers): the
+        query chooses among that group's rows only, a group shorter than N leaves -1 in reference_index and NaN in reference_similarity, and
+        those places are fed bank.blank_row's tokens (zeros when it is -1)."""
+        return self._forward_select(query_img, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, False, group)
 
     @torch.no_grad()
     def forward_select_u8(self, query: U8Batch, bank: "SelectionBank", exclude=None, need_attn_weights=False, need_attn_weights_head_id=0,
-                          return_mean=False, n_references=None):
+                          return_mean=False, n_references=None, group=None):
         """forward_select() with the query images as decoded uint8."""
-        return self._forward_select(query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, True)
+        return self._forward_select(query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, True, group)
 
     def calibrate_lanes(self, query_img, ref_cross_imgs, tries: int = 3, steps: int = 4, min_gain: float = 0.08) -> Dict[str, Any]:
         """Checks that this module's multi-lane forward really overlaps its lanes, and repairs it if not.  The lanes' streams are probed

@@ -86,17 +86,21 @@ class NvsItems:
     of `dataset_path`).  References are drawn when an item is asked for, by data.sample_references (numpy's global RNG unless
     deterministic), as NeighbourSelector.__getitem__ does.
     compute_gt (this_main.gt_metric_maps=compute): an item also carries "query/gt", the file of the same iteration and index in the gt/ list
-    of the query's own split, its "query/score_map" is "empty_image", and no metric_map/ directory is looked at."""
+    of the query's own split, its "query/score_map" is "empty_image", and no metric_map/ directory is looked at.
+    candidates (neighbour strategy similar): nothing is drawn.  An item carries "reference/cross/imgs": None and
+    "reference/cross/group", the place in `groups` of the `cross` list random would draw from -- the captured images of the other split of the
+    query's scene and iteration; `groups` lists each distinct `cross` list once, in index order.  The views are chosen on the device."""
 
     def __init__(self, dataset_path: Union[str, Sequence[str]], resolution, data_split: str, neighbour_config, metric_type: str,
-                 num_gaussians_iters: int = -1, compute_gt: bool = False):
+                 num_gaussians_iters: int = -1, compute_gt: bool = False, candidates: bool = False):
         if data_split not in DATA_SPLITS:
             raise ValueError(f"Unknown data_split {data_split}")
-        if neighbour_config["strategy"] == "similar":
-            raise NotImplementedError("neighbour strategy similar is built for predict only (data.SimpleReferenceItems): per-scene candidate sets "
-                                      "in a multi-scene batch are not")
-        if neighbour_config["strategy"] != "random":
-            raise NotImplementedError(f"neighbour strategy {neighbour_config['strategy']} (sampler.py:60-66 only knows 'random')")
+        if neighbour_config["strategy"] == "similar" and not candidates:
+            raise NotImplementedError("neighbour strategy similar: without candidates=True this class draws an item's references on the host, "
+                                      "which is what random does; the choice on the device needs the candidate lists (from_config asks for "
+                                      "them).  Items without candidate lists serve similar for predict only (data.SimpleReferenceItems)")
+        if neighbour_config["strategy"] not in (("random", "similar") if candidates else ("random",)):
+            raise NotImplementedError(f"neighbour strategy {neighbour_config['strategy']} (sampler.py:60-66 only knows 'random'; this build adds 'similar')")
         if isinstance(dataset_path, str):
             roots = [dataset_path]
         elif isinstance(dataset_path, (list, tuple)):
@@ -106,6 +110,10 @@ class NvsItems:
         self.n_cross = int(neighbour_config["cross"])
         self.deterministic = bool(neighbour_config["deterministic"])
         self.compute_gt = bool(compute_gt)
+        self.candidates = bool(candidates)
+        self.groups: List[List[str]] = []
+        self._group_of: List[int] = []
+        seen: Dict[tuple, int] = {}
         mdir = metric_load_dir(metric_type)  # (validates the metric type in both modes)
         if self.compute_gt:
             mdir = None
@@ -127,14 +135,23 @@ class NvsItems:
                         it, im = iter_names[idx // per_iter], idx % per_iter
                         entry = (q["query"]["images"][it][im], q["query"]["score_map"][it][im], q["reference"]["cross"]["images"][it])
                         self._index.append(entry + ((q["query"]["gt"][it][im],) if self.compute_gt else ()))
+                        if self.candidates:
+                            key = tuple(entry[2])
+                            if key not in seen:
+                                seen[key] = len(self.groups)
+                                self.groups.append(list(key))
+                            self._group_of.append(seen[key])
 
     def __len__(self) -> int:
         return len(self._index)
 
     def __getitem__(self, idx: int) -> Dict[str, object]:
         query, score_map, cross = self._index[idx][:3]
-        refs = sample_references(cross, self.n_cross, self.deterministic) if self.n_cross > 0 else []
-        item = {"query/img": query, "query/score_map": score_map, "reference/cross/imgs": refs}
+        if self.candidates:  # no RNG is drawn
+            item = {"query/img": query, "query/score_map": score_map, "reference/cross/imgs": None, "reference/cross/group": self._group_of[idx]}
+        else:
+            refs = sample_references(cross, self.n_cross, self.deterministic) if self.n_cross > 0 else []
+            item = {"query/img": query, "query/score_map": score_map, "reference/cross/imgs": refs}
         if self.compute_gt:
             item["query/gt"] = self._index[idx][3]
         return item
@@ -144,7 +161,7 @@ class NvsItems:
         """get_dataset(cfg, ..., cfg.this_main.data_split) of task/test.py:95-97."""
         d = cfg.data.dataset
         return cls(d.path, d.get("resolution"), cfg.this_main.data_split, cfg.data.neighbour_config, cfg.model.predict.metric.type,
-                   int(d.get("num_gaussians_iters", -1)), compute_gt)
+                   int(d.get("num_gaussians_iters", -1)), compute_gt, candidates=str(cfg.data.neighbour_config.strategy) == "similar")
 
 
 def random_order(n: int, seed: int) -> List[int]:

@@ -241,9 +241,9 @@ class ForwardPipeline:
         """CrossScoreNet.forward_select_u8 on the next replica."""
         return self._run("forward_select_u8", (query, bank) + args, kwargs)
 
-    def reference_descriptors(self, tokens: torch.Tensor):
+    def reference_descriptors(self, tokens: torch.Tensor, offsets=None):
         """CrossScoreNet.reference_descriptors on the current stream (single-op launches: no handle, no workspace)."""
-        return self.nets[0].reference_descriptors(tokens)
+        return self.nets[0].reference_descriptors(tokens, offsets)
 
     def encode_references_u8(self, imgs) -> torch.Tensor:
         """CrossScoreNet.encode_references_u8 through replica 0 (see encode_references)."""

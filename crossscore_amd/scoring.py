@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import parallel, synth
-from .data import (STRATEGIES, DecodeWindow, PngDecoder, ReferenceBank, ReferenceTokenCache, decode_items, jpeg_decoder_choice, jpeg_progressive_choice, load_batch, plan_decodes,
+from .data import (EMPTY, STRATEGIES, DecodeWindow, PngDecoder, ReferenceBank, ReferenceTokenCache, decode_items, jpeg_decoder_choice, jpeg_progressive_choice, load_batch, plan_decodes,
                    png_decode_window_choice, png_decoder_choice, read_image_u8)
 from .model import CrossScoreNet, U8Image, load_lightning_checkpoint
 from .pipeline import ForwardPipeline
@@ -75,15 +75,15 @@ def options(cfg, phase: str) -> SimpleNamespace:
     # outputs (on by default, as in the reference's config) ARE that processed image, so "auto" takes the one-pass form only when neither is
     # written, and only for geometries it holds (cs_u8_input_supported); True insists, False never.  Results are bit-identical either way.
     o.fused = cfg.this_main.get("fused_input_stage", "auto")
-    # data.neighbour_config.strategy: random (the reference's sampler) | similar (this build, predict only): each query is scored
-    # against the neighbour_config.cross files of reference_dir whose pooled DINOv2 descriptor is most similar to its own, chosen on the device
-    # from the tokens of ALL reference files (data.ReferenceBank).  this_main.similar_exclude_self (default on): a query never takes the
-    # reference file that is itself (same real path), e.g. with query_dir == reference_dir.
+    # data.neighbour_config.strategy: random (the reference's sampler) | similar (this build): each query is scored against the
+    # neighbour_config.cross candidates whose pooled DINOv2 descriptor is most similar to its own, chosen on the device from the tokens of ALL
+    # candidates (data.ReferenceBank).  predict: the files of reference_dir; evaluate: per query the captured images of the other split of its
+    # own scene and iteration (the list random draws from), a list shorter than cross padded with "empty_image" as the reference's sampler pads.
+    # this_main.similar_exclude_self (default on): a query never takes the candidate that is itself (same real path), e.g. with
+    # query_dir == reference_dir.
     o.strategy = str(cfg.data.neighbour_config.strategy)
     o.exclude_self = bool(cfg.this_main.get("similar_exclude_self", True))
     if o.strategy == "similar":
-        if phase != "predict":
-            raise NotImplementedError("neighbour strategy similar is built for predict only")
         if bool(cfg.data.dataset.zero_reference):
             raise ValueError("data.neighbour_config.strategy=similar with data.dataset.zero_reference=True: there is nothing to choose between")
         if not bool(cfg.this_main.get("cache_reference_tokens", True)):
@@ -104,11 +104,17 @@ def start(cfg, o: SimpleNamespace) -> None:
     torch.cuda.set_device(o.device)
 
 
-def write_reference_selection(out_dir: str, selection) -> str:
+def write_reference_selection(out_dir: str, selection, path_parts: int = 1) -> str:
     """reference_selection.csv of a run with neighbour strategy similar: per query its file name, then the chosen references' file names in the
-    order chosen, then their similarities as %.4f."""
+    order chosen, then their similarities as %.4f.  path_parts: how many trailing parts of a path name a file, joined with "/" -- 1 for predict's
+    two directories, 5 for evaluate (<scene>/<split>/<name>_<iter>/<kind>/<file>: base names repeat across scenes).  A padded place (a query
+    whose candidate list is shorter than the views it takes) is written as empty_image with an empty similarity."""
     import csv
     import os
+    from pathlib import Path
+
+    def name(p):
+        return EMPTY if p == EMPTY else "/".join(Path(p).parts[-path_parts:])
 
     path = os.path.join(str(out_dir), "reference_selection.csv")
     n = len(selection[0][1]) if selection else 0
@@ -116,7 +122,7 @@ def write_reference_selection(out_dir: str, selection) -> str:
         w = csv.writer(f)
         w.writerow(["query"] + [f"reference_{k}" for k in range(n)] + [f"similarity_{k}" for k in range(n)])
         for query, refs, sims in selection:
-            w.writerow([os.path.basename(query)] + [os.path.basename(p) for p in refs] + ["%.4f" % v for v in sims])
+            w.writerow([name(query)] + [name(p) for p in refs] + ["" if p == EMPTY else "%.4f" % v for p, v in zip(refs, sims)])
     return path
 
 
@@ -131,7 +137,7 @@ class Scored(NamedTuple):
 
 def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: Optional[str] = None, *, calibrate: bool = False,
           extra_files=None, decode_host=None, from_window=None, check_size=None, after_submit=None, on_consume=None,
-          reference_paths=None) -> Scored:
+          reference_paths=None, reference_groups=None) -> Scored:
     """Scores `batches` (lists of item dictionaries; cfg.logger.<phase>.out_dir exists) and finishes the outputs.
 
     probe_path: the first query of this rank, whose geometry decides about the one-pass input stage (None: no image to look at).
@@ -141,6 +147,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     picks the same extras out of the window's tensors.
     check_size(size) may refuse a batch's processed size before anything of it is queued.
     reference_paths: the files of reference_dir, in the driver's order: the candidates of neighbour strategy similar.
+    reference_groups (instead): candidate lists, of which each item names its own by "reference/cross/group" (nvs.NvsItems.groups).
     after_submit(ticket, items, decoded, extras, size, batch) -> state; on_consume(idx, batch, out, state) runs before the summariser and writer."""
     phase, device = o.phase, o.device
     log = cfg.logger[phase]
@@ -184,6 +191,9 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     cache = ReferenceTokenCache(pipe, stage, keep_images=keep_ref_images,
                                 max_images=o.cache_max_images, from_u8=fused_in) if o.use_cache and not similar else None
     bank = None  # neighbour strategy similar: data.ReferenceBank, built when the first batch tells the processed size
+    grouped = similar and reference_groups is not None
+    # ... from the candidate lists THIS rank's batches name, in their order: bank_group maps an item's "reference/cross/group" to the bank's
+    bank_group = {g: k for k, g in enumerate(sorted({it["reference/cross/group"] for its in batches for it in its}))} if grouped else None
     selection = []  # ... and per query (path, chosen reference paths, their similarities), in consumption order
     decoder = PngDecoder(device, pool, png=o.png_decoder == "gpu", jpeg=o.jpeg_decoder == "gpu",
                          progressive=o.jpeg_progressive == "gpu") if "gpu" in (o.png_decoder, o.jpeg_decoder) else None
@@ -216,12 +226,14 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
         if similar:
             # the views this batch was scored against, read now that the batch is taken anyway: paths for the item-path JSON, the reference PNGs'
             # and the attention images' names; the processed images from the bank where they are written
+            # (a grouped bank: -1, a place the query's candidate list could not fill, is "empty_image" and the bank's placeholder row)
             index = out["reference_index"].cpu()
             sims = out["reference_similarity"].cpu().numpy()
-            chosen = [[bank.paths[int(i)] for i in row] for row in index.tolist()]
+            chosen = [[bank.paths[int(i)] if i >= 0 else EMPTY for i in row] for row in index.tolist()]
             batch["item_paths"]["reference/cross/imgs"] = [[row[n] for row in chosen] for n in range(n_cross)]
             if bank.images is not None:
-                batch["reference/cross/imgs"] = bank.images[index.to(device=device, dtype=torch.int64)]
+                rows = index.to(device=device, dtype=torch.int64)
+                batch["reference/cross/imgs"] = bank.images[torch.where(rows < 0, bank.bank.blank_row, rows) if grouped else rows]
             selection.extend(zip(batch["item_paths"]["query/img"], chosen, sims.tolist()))
         if on_consume is not None:
             on_consume(idx, batch, out, state)
@@ -242,16 +254,21 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
                 check_size(size)
             if bank is None:
                 bank = ReferenceBank(pipe, stage, reference_paths, tuple(size), n_cross, keep_images=keep_ref_images, max_images=o.cache_max_images,
-                                     from_u8=fused_in, decoder=decoder, pool=pool, window=o.decode_window)
-            if tuple(bank.bank.tokens.shape[1:2]) != ((size[0] // net.arch.patch) * (size[1] // net.arch.patch),):
-                raise ValueError(f"neighbour strategy similar: this batch's processed size {size[0]}x{size[1]} differs from the reference bank's")
+                                     from_u8=fused_in, decoder=decoder, pool=pool, window=o.decode_window,
+                                     groups=[reference_groups[g] for g in bank_group] if grouped else None)
+                bank_size = tuple(size)
+            if tuple(bank.bank.tokens.shape[1:2]) != ((size[0] // net.arch.patch) * (size[1] // net.arch.patch),) or (grouped and tuple(size) != bank_size):
+                raise ValueError(f"neighbour strategy similar: this batch's processed size {size[0]}x{size[1]} differs from the reference bank's" +
+                                 (f" {bank_size[0]}x{bank_size[1]}: one bank has one patch grid; this_main.crop_mode=dataset_default gives the images of "
+                                  "every scene one size" if grouped else ""))
             pending = submit_decode(batch_idx + 1)  # (behind the bank's own decodes: the decoder serves one thread at a time)
             exclude = None
             if o.exclude_self:
-                ex = [bank.index_of(it["query/img"]) for it in its]
+                ex = [bank.index_of(it["query/img"], bank_group[it["reference/cross/group"]] if grouped else None) for it in its]
                 if any(e >= 0 for e in ex):  # (an array makes every query of the call count as carrying an exclusion: cs_forward_select)
                     exclude = torch.tensor(ex, dtype=torch.int32).to(device)
-            ticket = (pipe.submit_select_u8 if fused_in else pipe.submit_select)(batch["query/img"], bank.bank, exclude, need_w, head_id, True)
+            group = np.array([bank_group[it["reference/cross/group"]] for it in its], dtype=np.int32) if grouped else None
+            ticket = (pipe.submit_select_u8 if fused_in else pipe.submit_select)(batch["query/img"], bank.bank, exclude, need_w, head_id, True, group=group)
         elif cache is None:
             pending = submit_decode(batch_idx + 1)
             batch, size = load_batch(its, stage, decoded, fused_in, zero_reference=zero_ref)
@@ -294,7 +311,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
             writer.finish()
         files += summariser.summarise()
         if similar:
-            files.append(write_reference_selection(log.out_dir, selection))
+            files.append(write_reference_selection(log.out_dir, selection, 5 if grouped else 1))
     except BaseException as exc:  # noqa: BLE001 -- re-raised by the driver, behind its collective
         failure = exc
     finally:

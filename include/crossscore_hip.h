@@ -183,6 +183,39 @@ int cs_forward_select(cs_handle h, const float* query, const uint16_t* bank_toke
 int cs_forward_select_u8(cs_handle h, const cs_u8_image* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre, int R,
                          const int32_t* exclude, int B, int N, int H, int W, const float* mean3, const float* std3, float* score_out,
                          float* attn_out, int head_id, float* mean_out, int32_t* index_out, float* sim_out, cs_stream stream);
+/* Grouped banks (the test phase, where a query chooses among the images of its own scene).  A bank of R rows carries G groups:
+ * group g is the rows offsets[g] .. offsets[g + 1] - 1, offsets[0] = 0, strictly increasing, offsets[G] <= R; the rows from offsets[G] on
+ * belong to no group and are never selected.  Every group has its own centre -- the centre of an ungrouped bank made of that slice, bit for bit --
+ * a bank row's unit uses its group's centre, query b the centre of its group query_group[b], and b is compared with the rows of that group only:
+ * order, ties, the NaN rule and exclude[b] (a bank row; one outside the group has no effect) as above.  index_out holds bank rows, -1 where the
+ * group ran out (N may exceed a group).  sim_out is (B, S), S the longest group: column j of query b is bank row offsets[query_group[b]] + j, the
+ * columns behind its group a quiet NaN.  Every result equals, bit for bit, what the ungrouped calls give on the sliced group.
+ * offsets (G + 1) and query_group (B) are HOST arrays: they are checked here, resolved per query and uploaded asynchronously on the call's stream
+ * from a pinned slot; nothing is read back and no call waits.  CS_ERR_BAD_ARG for a group outside [0, G), offsets that do not start at 0 or do
+ * not increase, offsets[G] > R, a blank_row inside a group or outside [-1, R); a refused call queues nothing.
+ *   cs_op_group_descriptors          mean (R, C) -> centre_out (G, C) and unit_out (R, C), one launch each; unit_out's rows from offsets[G] on are
+ *                                    left alone.  C a multiple of 64, R <= 65536
+ *   cs_op_select_references_grouped  takes the queries' MEANS q_mean (B, C): the unit depends on the group.  N <= 32, R <= 65536
+ *   cs_op_gather_tokens_ex           cs_op_gather_tokens with blank_row: an index outside [0, R) takes bank row blank_row's tokens when
+ *                                    blank_row >= 0 (the encoder's tokens of the all-zero placeholder image), zeros when it is -1
+ *   cs_forward_select_grouped*       cs_forward_select* on such a bank: centre is (G, C), sim_out NULL or (B, S); the gather takes blank_row.  With
+ *                                    G = 1 over all rows and blank_row = -1 every output has the bits of cs_forward_select*. */
+int cs_op_group_descriptors(const float* mean, int R, int C, const int32_t* offsets /* HOST (G + 1) */, int G, float* centre_out /* (G, C) */,
+                            float* unit_out /* (R, C) */, cs_stream stream);
+int cs_op_select_references_grouped(const float* q_mean, int B, const int32_t* query_group /* HOST (B) */, const float* bank_unit,
+                                    const float* centre /* (G, C) */, const int32_t* offsets /* HOST (G + 1) */, int G, int R, int C,
+                                    const int32_t* exclude /* NULL or (B), bank rows, -1 = none */, int N, int32_t* index_out /* (B, N) */,
+                                    float* sim_out /* (B, S) */, cs_stream stream);
+int cs_op_gather_tokens_ex(const uint16_t* bank, int R, int Np, int C, const int32_t* index, int B, int N, uint16_t* out, cs_stream stream,
+                           int blank_row);
+int cs_forward_select_grouped(cs_handle h, const float* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre, int R,
+                              const int32_t* offsets, int G, const int32_t* query_group, int blank_row, const int32_t* exclude, int B, int N, int H,
+                              int W, float* score_out, float* attn_out, int head_id, float* mean_out, int32_t* index_out, float* sim_out,
+                              cs_stream stream);
+int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre,
+                                 int R, const int32_t* offsets, int G, const int32_t* query_group, int blank_row, const int32_t* exclude, int B,
+                                 int N, int H, int W, const float* mean3, const float* std3, float* score_out, float* attn_out, int head_id,
+                                 float* mean_out, int32_t* index_out, float* sim_out, cs_stream stream);
 /* Overflow report.  With fp16 operands an activation beyond 65504 becomes inf and reaches the score map as NaN (nothing clamps in
  * the hot kernels); every forward counts the non-finite values of its score map on the device.  This call waits for the handle's last
  * forward, returns the count since the previous call in *count and resets it: > 0 means "switch to operand_dtype = 1 (bf16)". */

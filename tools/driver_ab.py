@@ -9,7 +9,7 @@ a digest over (relative path, file bytes) of everything it wrote, and the result
 case directory; the long values -- files, rows, batches, metrics -- as a count and a digest).  The two trees' listings must be identical.
 
 predict:  cache on / off x fused_input_stage auto / False x png_decoder host / gpu x batches_in_flight 1 / 3; every writer flag on; JPEG queries
-          with jpeg_decoder=gpu.
+          with jpeg_decoder=gpu; neighbour strategy similar over input stage, decoder and batches in flight.
 evaluate: cache x fused x png_decoder x gt_metric_maps files / compute x shuffle on / off; limit_test_batches=2.
 
 --match keeps the cases whose name holds TEXT; --drop-result-key leaves a key out of both trees' result dictionaries (one that only the new
@@ -114,6 +114,9 @@ def cases(pred, ev, jpeg_dir):
         ["model.need_attn_weights=True", "model.need_attn_weights_head_id=1"]
     yield "predict", "predict JPEG queries jpeg_decoder=gpu", [o for o in pred if not o.startswith("data.dataset.query_dir=")] + no_imgs + \
         [f"data.dataset.query_dir={jpeg_dir}", "this_main.jpeg_decoder=gpu"]
+    for f, d, depth in (("auto", "host", 3), (False, "gpu", 3), (False, "host", 1), ("auto", "gpu", 1)):
+        yield "predict", f"predict strategy=similar fused={f} png_decoder={d} in_flight={depth}", \
+            pred + no_imgs + knobs(True, f, d) + [f"this_main.batches_in_flight={depth}", "data.neighbour_config.strategy=similar", "logger.predict.write.flag.item_path_json=True"]
     for (c, f, d), gt, shuffle in itertools.product(grid, ("files", "compute"), (False, True)):
         yield "evaluate", f"evaluate cache={c} fused={f} png_decoder={d} gt_metric_maps={gt} shuffle={shuffle}", \
             ev + knobs(c, f, d) + [f"this_main.gt_metric_maps={gt}", f"data.loader.validation.shuffle={shuffle}"]

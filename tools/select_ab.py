@@ -5,6 +5,9 @@ alternating inside every round, the median over the rounds:
   select   forward_select: descriptors, similarities, top-N and gather between encoder and decoder
   stack    the parent's cached path: torch.stack of the N token tensors per query on the host's say-so (ReferenceTokenCache.gather), forward_cached
   cached   forward_cached on tokens gathered beforehand (neither a choice nor a gather: the floor the two above add to)
+  grouped1 forward_select(group=...) on the same bank as ONE group over all rows, blank_row -1 (the test phase's form: per-query slices, the
+           triples uploaded with the call); the same bits as select
+  grouped16 (banks of at least 16 x N rows) the bank as 16 equal groups, query b in group b % 16: similarities and top-N over R / 16 rows
 
 and the bank build per reference: encode_references in chunks of 32 alone, and with the copy into the contiguous bank and the descriptors behind it.
 Needs the GPU; prints what it measured (--out FILE: also written there)."""
@@ -14,6 +17,7 @@ import statistics
 import sys
 import time
 
+import numpy as np
 import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -89,11 +93,23 @@ def main():
             tok = torch.stack([torch.stack([tokens[i] for i in row]) for row in index])
             return net.forward_cached(q, tok, False, 0, True)
 
+        whole = np.array([0, R], dtype=np.int32)
+        bank1 = SelectionBank(tokens, *net.reference_descriptors(tokens, whole), N, whole, -1)
+        zeros = np.zeros(B, dtype=np.int32)
         forms = {"select": lambda: net.forward_select(q, bank, None, False, 0, True), "stack": stack,
-                 "cached": lambda: net.forward_cached(q, pre, False, 0, True)}
+                 "cached": lambda: net.forward_cached(q, pre, False, 0, True),
+                 "grouped1": lambda: net.forward_select(q, bank1, None, False, 0, True, group=zeros)}
         for k, fn in forms.items():
             out = fn()
-            assert torch.equal(out["score_map_ref_cross"], first["score_map_ref_cross"]), k  # the three forms score the same rows: the same bits
+            assert torch.equal(out["score_map_ref_cross"], first["score_map_ref_cross"]), k  # the forms score the same rows: the same bits
+        if R >= 16 * N and R % 16 == 0:
+            sixteen = np.arange(0, R + 1, R // 16, dtype=np.int32)
+            gdesc = statistics.median(timed(lambda: net.reference_descriptors(tokens, sixteen), 5) for _ in range(3))
+            say(f"R = {R}: the descriptors of the whole bank in 16 groups {gdesc * 1e6:.1f} us (ungrouped {desc * 1e6:.1f} us)")
+            bank16 = SelectionBank(tokens, *net.reference_descriptors(tokens, sixteen), N, sixteen, -1)
+            groups16 = (np.arange(B) % 16).astype(np.int32)
+            forms["grouped16"] = lambda: net.forward_select(q, bank16, None, False, 0, True, group=groups16)
+            forms["grouped16"]()
         seen = {k: [] for k in forms}
         for _ in range(args.rounds):
             for k, fn in forms.items():
@@ -103,10 +119,12 @@ def main():
             f"{med['cached'] * 1e3:.3f} ms   (spread of the rounds: " + ", ".join(f"{k} {min(v) * 1e3:.3f}-{max(v) * 1e3:.3f}" for k, v in seen.items()) + ")")
         say(f"R = {R}: the choice and the gather on the device add {(med['select'] - med['cached']) * 1e6:.0f} us to the cached forward, the host-side "
             f"stack adds {(med['stack'] - med['cached']) * 1e6:.0f} us")
+        say(f"R = {R}: per batch  grouped (G = 1) {med['grouped1'] * 1e3:.3f} ms = select {(med['grouped1'] - med['select']) * 1e6:+.0f} us" +
+            (f"   grouped (G = 16) {med['grouped16'] * 1e3:.3f} ms = select {(med['grouped16'] - med['select']) * 1e6:+.0f} us" if "grouped16" in med else ""))
         net.forward_select(q, bank, None, False, 0, True)
         st = net.forward_stats()
         say(f"R = {R}: forward_select enqueues {st['launches']} launches in {st['host_enqueue_ms']:.2f} ms of host time")
-        bank = tokens = pre = imgs = None
+        bank = bank1 = bank16 = tokens = pre = imgs = None
         torch.cuda.empty_cache()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
