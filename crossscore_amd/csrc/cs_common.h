@@ -354,16 +354,12 @@ hipError_t cs_gtmap_launch(const uint8_t* render, const uint8_t* gt, int B, int 
 hipError_t cs_gtsums_launch(const uint8_t* render, const uint8_t* gt, int B, int H, int W, long long image_stride, uint64_t* sums, hipStream_t st);
 // select.hip
 hipError_t cs_token_descriptors_launch(const h16_t* tok, int I, int Np, int C, int bf, float* mean, hipStream_t st);
-hipError_t cs_descriptor_centre_launch(const float* mean, int R, int C, float* centre, hipStream_t st);
-hipError_t cs_descriptor_unit_launch(const float* mean, int I, int C, const float* centre, float* unit, hipStream_t st);
-hipError_t cs_similarity_launch(const float* q, int B, const float* bank, int R, int C, float* sim, hipStream_t st);
-hipError_t cs_topn_launch(const float* sim, int B, int R, const int32_t* exclude, int N, int32_t* index, hipStream_t st);
-hipError_t cs_gather_tokens_launch(const h16_t* bank, int R, int Np, int C, const int32_t* index, int slots, int blank, h16_t* out, hipStream_t st);
-hipError_t cs_group_centre_launch(const float* mean, const int32_t* offsets, int G, int R, int C, float* centre, hipStream_t st);
-hipError_t cs_group_unit_launch(const float* mean, const int32_t* offsets, int G, int rows, int R, int C, const float* centre, float* unit, hipStream_t st);
+hipError_t cs_centre_launch(const float* mean, const int32_t* offsets, int G, int R, int C, float* centre, hipStream_t st);
+hipError_t cs_bank_unit_launch(const float* mean, const int32_t* offsets, int G, int rows, int R, int C, const float* centre, float* unit, hipStream_t st);
 hipError_t cs_query_unit_launch(const float* mean, int B, int C, const CsSelTriple* trip, int R, int G, const float* centre, float* unit, hipStream_t st);
-hipError_t cs_group_similarity_launch(const float* q, int B, const float* bank, int R, int G, int C, const CsSelTriple* trip, int S, float* sim, hipStream_t st);
-hipError_t cs_group_topn_launch(const float* sim, int B, int S, int R, int G, const CsSelTriple* trip, const int32_t* exclude, int N, int32_t* index, hipStream_t st);
+hipError_t cs_similarity_launch(const float* q, int B, const float* bank, int R, int G, int C, const CsSelTriple* trip, int S, float* sim, hipStream_t st);
+hipError_t cs_topn_launch(const float* sim, int B, int S, int R, int G, const CsSelTriple* trip, const int32_t* exclude, int N, int32_t* index, hipStream_t st);
+hipError_t cs_gather_tokens_launch(const h16_t* bank, int R, int Np, int C, const int32_t* index, int slots, int blank, h16_t* out, hipStream_t st);
 // gtsum.hip
 hipError_t cs_metric_map_sums_launch(const uint16_t* ssim, const uint16_t* mae, int B, int H, int W, int row_elems, long long image_stride,
                                      uint64_t* sums, hipStream_t st);

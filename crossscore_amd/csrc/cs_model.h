@@ -136,19 +136,14 @@ inline int ffn_hidden(const cs_config& c) {
 }
 
 // the sizes cs_op_select_references and cs_forward_select take: B queries against a bank of R unit descriptors C wide, N picks per query.  The
-// exclusions live on the device, so with an `exclude` array every query may carry one and only R - 1 entries count as eligible.
-inline int select_check(int B, int R, int C, int N, bool has_exclude) {
-  if (B <= 0 || R <= 0 || C <= 0 || N <= 0) return fail(CS_ERR_BAD_ARG, "select_references: empty batch, bank or selection");
-  if (N > 32 || R > 65536 || C % 4 || B > 65535) return fail(CS_ERR_UNSUPPORTED, "select_references: built for N <= 32, R <= 65536, C a multiple of 4 (N %d, R %d, C %d)", N, R, C);
-  if (N > R - (has_exclude ? 1 : 0))
+// exclusions live on the device, so with an `exclude` array every query may carry one and only R - 1 entries count as eligible.  In the grouped
+// forms N may exceed a group (the places left over are padded), so only the sizes are checked.
+inline int select_check(int B, int R, int C, int N, bool grouped, bool has_exclude) {
+  const char* op = grouped ? "select_references_grouped" : "select_references";
+  if (B <= 0 || R <= 0 || C <= 0 || N <= 0) return fail(CS_ERR_BAD_ARG, "%s: empty batch, bank or selection", op);
+  if (N > 32 || R > 65536 || C % 4 || B > 65535) return fail(CS_ERR_UNSUPPORTED, "%s: built for N <= 32, R <= 65536, C a multiple of 4 (N %d, R %d, C %d)", op, N, R, C);
+  if (!grouped && N > R - (has_exclude ? 1 : 0))
     return fail(CS_ERR_BAD_ARG, "select_references: N = %d exceeds the %d eligible bank entries (R = %d%s)", N, R - (has_exclude ? 1 : 0), R, has_exclude ? ", one excluded" : "");
-  return 0;
-}
-
-// ... and the grouped forms: N may exceed a group (the places left over are padded), so only the sizes are checked here
-inline int select_check_grouped(int B, int R, int C, int N) {
-  if (B <= 0 || R <= 0 || C <= 0 || N <= 0) return fail(CS_ERR_BAD_ARG, "select_references_grouped: empty batch, bank or selection");
-  if (N > 32 || R > 65536 || C % 4 || B > 65535) return fail(CS_ERR_UNSUPPORTED, "select_references_grouped: built for N <= 32, R <= 65536, C a multiple of 4 (N %d, R %d, C %d)", N, R, C);
   return 0;
 }
 

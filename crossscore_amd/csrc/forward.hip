@@ -284,14 +284,12 @@ struct Fwd {
     if (mode == 2 && (!have_q || !tokens_out)) return fail(CS_ERR_BAD_ARG, "null tensor");
     if (mode == 3) {
       if (!have_q || !ref_tokens || !score_out || !sel || !sel->bank_unit || !sel->centre || !sel->index_out) return fail(CS_ERR_BAD_ARG, "null tensor");
+      if (B > 0 && N > 0)
+        if (int r = select_check(B, sel->R, c.hidden, N, sel->offsets != nullptr, sel->exclude != nullptr)) return r;
       if (sel->offsets) {
-        if (B > 0 && N > 0)
-          if (int r = select_check_grouped(B, sel->R, c.hidden, N)) return r;
         if (int r = group_offsets_check(sel->offsets, sel->G, sel->R, &S_sel)) return r;
         if (int r = blank_row_check(sel->blank_row, sel->offsets, sel->G, sel->R)) return r;
         if (int r = query_groups_check(sel->query_group, B, sel->G)) return r;
-      } else if (B > 0 && N > 0) {
-        if (int r = select_check(B, sel->R, c.hidden, N, sel->exclude != nullptr)) return r;
       }
       if ((long long)B * N > 65535) return fail(CS_ERR_UNSUPPORTED, "cs_forward_select: more than 65535 reference slots in one call; split the batch");
     }
@@ -668,20 +666,17 @@ struct Fwd {
   void select_references(Launcher& L) {
     const int C = p.C;
     float* sim = sel->sim_out ? sel->sim_out : p.sel_sim;
+    // grouped: every query against its own slice of the bank and that slice's centre, missing places take the blank row's tokens; plain: no
+    // triples, which the kernels read as "the whole bank" (select.hip)
+    const bool grouped = sel->offsets != nullptr;
+    const CsSelTriple* trip = grouped ? p.sel_trip : nullptr;
+    const int R = sel->R, G = grouped ? sel->G : 1, S = grouped ? S_sel : R, blank = grouped ? sel->blank_row : -1;
     L.small("select_desc", [&] { return cs_token_descriptors_launch(p.q_bf, B, p.Np, C, bf, p.sel_mean, L.st); });
-    if (sel->offsets) {  // every query against its own slice of the bank and that slice's centre; missing places take the blank row's tokens
-      const int R = sel->R, G = sel->G, S = S_sel;
-      L.small("select_unit_grouped", [&] { return cs_query_unit_launch(p.sel_mean, B, C, p.sel_trip, R, G, sel->centre, p.sel_unit, L.st); });
-      L.small("select_sim_grouped", [&] { return cs_group_similarity_launch(p.sel_unit, B, sel->bank_unit, R, G, C, p.sel_trip, S, sim, L.st); });
-      L.small("select_topn_grouped", [&] { return cs_group_topn_launch(sim, B, S, R, G, p.sel_trip, sel->exclude, N, sel->index_out, L.st); });
-      L.misc("select_gather_blank", 32, 0, 4.0 * B * N * p.Np * C,
-             [&] { return cs_gather_tokens_launch(ref_tokens, R, p.Np, C, sel->index_out, B * N, sel->blank_row, p.mem_bf, L.st); });
-      return;
-    }
-    L.small("select_unit", [&] { return cs_descriptor_unit_launch(p.sel_mean, B, C, sel->centre, p.sel_unit, L.st); });
-    L.small("select_sim", [&] { return cs_similarity_launch(p.sel_unit, B, sel->bank_unit, sel->R, C, sim, L.st); });
-    L.small("select_topn", [&] { return cs_topn_launch(sim, B, sel->R, sel->exclude, N, sel->index_out, L.st); });
-    L.misc("select_gather", 32, 0, 4.0 * B * N * p.Np * C, [&] { return cs_gather_tokens_launch(ref_tokens, sel->R, p.Np, C, sel->index_out, B * N, -1, p.mem_bf, L.st); });
+    L.small(grouped ? "select_unit_grouped" : "select_unit", [&] { return cs_query_unit_launch(p.sel_mean, B, C, trip, R, G, sel->centre, p.sel_unit, L.st); });
+    L.small(grouped ? "select_sim_grouped" : "select_sim", [&] { return cs_similarity_launch(p.sel_unit, B, sel->bank_unit, R, G, C, trip, S, sim, L.st); });
+    L.small(grouped ? "select_topn_grouped" : "select_topn", [&] { return cs_topn_launch(sim, B, S, R, G, trip, sel->exclude, N, sel->index_out, L.st); });
+    L.misc(grouped ? "select_gather_blank" : "select_gather", 32, 0, 4.0 * B * N * p.Np * C,
+           [&] { return cs_gather_tokens_launch(ref_tokens, R, p.Np, C, sel->index_out, B * N, blank, p.mem_bf, L.st); });
   }
 
   // ---- step 9: taps: the decoder's inputs = final LayerNorm of the patch tokens + multi-view PE (core.py:141-153,93-98): query rows fp32, reference rows 16 bit ----
@@ -844,6 +839,14 @@ int forward_impl(Fwd f) {
   return rc;
 }
 
+// The four cs_forward_select* entry points: mode 3 over fp32 (`query`) or uint8 (`u8`) queries, `s` plain or grouped
+int forward_select(cs_handle h, const float* query, const U8In* u8, const uint16_t* bank_tokens, const SelectIn& s, int B, int N, int H, int W,
+                   float* score_out, float* attn_out, int head_id, float* mean_out, cs_stream stream) {
+  Fwd f{h, 3, query, nullptr, bank_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, u8};
+  f.sel = &s;
+  return forward_impl(f);
+}
+
 }  // namespace
 
 extern "C" {
@@ -890,9 +893,7 @@ int cs_forward_select(cs_handle h, const float* query, const uint16_t* bank_toke
                       const int32_t* exclude, int B, int N, int H, int W, float* score_out, float* attn_out, int head_id, float* mean_out,
                       int32_t* index_out, float* sim_out, cs_stream stream) {
   const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out};
-  Fwd f{h, 3, query, nullptr, bank_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, nullptr};
-  f.sel = &s;
-  return forward_impl(f);
+  return forward_select(h, query, nullptr, bank_tokens, s, B, N, H, W, score_out, attn_out, head_id, mean_out, stream);
 }
 
 int cs_forward_select_u8(cs_handle h, const cs_u8_image* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre, int R,
@@ -900,9 +901,7 @@ int cs_forward_select_u8(cs_handle h, const cs_u8_image* query, const uint16_t* 
                          float* attn_out, int head_id, float* mean_out, int32_t* index_out, float* sim_out, cs_stream stream) {
   const U8In u{query, nullptr, mean3, std3};
   const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out};
-  Fwd f{h, 3, nullptr, nullptr, bank_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, &u};
-  f.sel = &s;
-  return forward_impl(f);
+  return forward_select(h, nullptr, &u, bank_tokens, s, B, N, H, W, score_out, attn_out, head_id, mean_out, stream);
 }
 
 int cs_forward_select_grouped(cs_handle h, const float* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre, int R,
@@ -911,9 +910,7 @@ int cs_forward_select_grouped(cs_handle h, const float* query, const uint16_t* b
                               cs_stream stream) {
   if (!offsets) return fail(CS_ERR_BAD_ARG, "cs_forward_select_grouped: offsets missing");
   const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out, offsets, G, query_group, blank_row};
-  Fwd f{h, 3, query, nullptr, bank_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, nullptr};
-  f.sel = &s;
-  return forward_impl(f);
+  return forward_select(h, query, nullptr, bank_tokens, s, B, N, H, W, score_out, attn_out, head_id, mean_out, stream);
 }
 
 int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const uint16_t* bank_tokens, const float* bank_unit, const float* centre,
@@ -923,9 +920,7 @@ int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const ui
   if (!offsets) return fail(CS_ERR_BAD_ARG, "cs_forward_select_grouped_u8: offsets missing");
   const U8In u{query, nullptr, mean3, std3};
   const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out, offsets, G, query_group, blank_row};
-  Fwd f{h, 3, nullptr, nullptr, bank_tokens, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, &u};
-  f.sel = &s;
-  return forward_impl(f);
+  return forward_select(h, nullptr, &u, bank_tokens, s, B, N, H, W, score_out, attn_out, head_id, mean_out, stream);
 }
 
 int cs_u8_input_supported(cs_handle h, const cs_u8_image* im, int H, int W) {

@@ -555,22 +555,22 @@ int cs_op_token_descriptors(const uint16_t* tokens, int I, int Np, int C, int dt
 int cs_op_descriptor_centre(const float* mean, int R, int C, float* centre_out, cs_stream stream) {
   if (!mean || !centre_out || R <= 0 || C <= 0) return fail(CS_ERR_BAD_ARG, "descriptor_centre: bad arguments");
   if (C % 64) return fail(CS_ERR_UNSUPPORTED, "descriptor_centre: C must be a multiple of 64");
-  HIPCHK(cs_descriptor_centre_launch(mean, R, C, centre_out, (hipStream_t)stream));
+  HIPCHK(cs_centre_launch(mean, nullptr, 1, R, C, centre_out, (hipStream_t)stream));
   return 0;
 }
 
 int cs_op_descriptor_unit(const float* mean, int I, int C, const float* centre, float* unit_out, cs_stream stream) {
   if (!mean || !centre || !unit_out || I <= 0 || C <= 0) return fail(CS_ERR_BAD_ARG, "descriptor_unit: bad arguments");
-  HIPCHK(cs_descriptor_unit_launch(mean, I, C, centre, unit_out, (hipStream_t)stream));
+  HIPCHK(cs_bank_unit_launch(mean, nullptr, 1, I, I, C, centre, unit_out, (hipStream_t)stream));
   return 0;
 }
 
 int cs_op_select_references(const float* q_unit, int B, const float* bank_unit, int R, int C, const int32_t* exclude, int N, int32_t* index_out,
                             float* sim_out, cs_stream stream) {
   if (!q_unit || !bank_unit || !index_out || !sim_out) return fail(CS_ERR_BAD_ARG, "select_references: null tensor");
-  if (int r = select_check(B, R, C, N, exclude != nullptr)) return r;
-  HIPCHK(cs_similarity_launch(q_unit, B, bank_unit, R, C, sim_out, (hipStream_t)stream));
-  HIPCHK(cs_topn_launch(sim_out, B, R, exclude, N, index_out, (hipStream_t)stream));
+  if (int r = select_check(B, R, C, N, false, exclude != nullptr)) return r;
+  HIPCHK(cs_similarity_launch(q_unit, B, bank_unit, R, 1, C, nullptr, R, sim_out, (hipStream_t)stream));
+  HIPCHK(cs_topn_launch(sim_out, B, R, R, 1, nullptr, exclude, N, index_out, (hipStream_t)stream));
   return 0;
 }
 
@@ -617,8 +617,8 @@ int cs_op_group_descriptors(const float* mean, int R, int C, const int32_t* offs
   StageRing::Slot* sl = nullptr;
   if (int r = stage_upload(offsets, (size_t)(G + 1) * sizeof(int32_t), 0, st, &sl)) return r;
   const int32_t* d_off = static_cast<const int32_t*>(sl->dev);
-  HIPCHK(cs_group_centre_launch(mean, d_off, G, R, C, centre_out, st));
-  HIPCHK(cs_group_unit_launch(mean, d_off, G, offsets[G], R, C, centre_out, unit_out, st));
+  HIPCHK(cs_centre_launch(mean, d_off, G, R, C, centre_out, st));
+  HIPCHK(cs_bank_unit_launch(mean, d_off, G, offsets[G], R, C, centre_out, unit_out, st));
   return stage_done(sl, st);
 }
 
@@ -626,7 +626,7 @@ int cs_op_select_references_grouped(const float* q_mean, int B, const int32_t* q
                                     const int32_t* offsets, int G, int R, int C, const int32_t* exclude, int N, int32_t* index_out, float* sim_out,
                                     cs_stream stream) {
   if (!q_mean || !bank_unit || !centre || !index_out || !sim_out) return fail(CS_ERR_BAD_ARG, "select_references_grouped: null tensor");
-  if (int r = select_check_grouped(B, R, C, N)) return r;
+  if (int r = select_check(B, R, C, N, true, false)) return r;
   int S = 0;
   if (int r = group_offsets_check(offsets, G, R, &S)) return r;
   if (int r = query_groups_check(query_group, B, G)) return r;
@@ -640,8 +640,8 @@ int cs_op_select_references_grouped(const float* q_mean, int B, const int32_t* q
   const CsSelTriple* t = static_cast<const CsSelTriple*>(sl->dev);
   float* q_unit = reinterpret_cast<float*>(static_cast<char*>(sl->dev) + ((tb + 255) & ~size_t(255)));  // the queries' units: scratch
   HIPCHK(cs_query_unit_launch(q_mean, B, C, t, R, G, centre, q_unit, st));
-  HIPCHK(cs_group_similarity_launch(q_unit, B, bank_unit, R, G, C, t, S, sim_out, st));
-  HIPCHK(cs_group_topn_launch(sim_out, B, S, R, G, t, exclude, N, index_out, st));
+  HIPCHK(cs_similarity_launch(q_unit, B, bank_unit, R, G, C, t, S, sim_out, st));
+  HIPCHK(cs_topn_launch(sim_out, B, S, R, G, t, exclude, N, index_out, st));
   return stage_done(sl, st);
 }
 

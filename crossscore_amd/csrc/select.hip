@@ -53,20 +53,18 @@ __device__ __forceinline__ void centre_columns(const float* __restrict__ mean, i
   if (w == 0) centre[c] = ((part[0][col] + part[1][col]) + (part[2][col] + part[3][col])) / (float)R;
 }
 
-__global__ __launch_bounds__(256) void descriptor_centre_kernel(const float* __restrict__ mean, int R, int C, float* __restrict__ centre) {
-  centre_columns(mean, R, C, centre);
-}
-
-// Grouped banks: group g is the rows offsets[g] .. offsets[g + 1] - 1 of a bank of R rows.  The host has checked the offsets; the
-// device still clamps what it reads from them, so that no address leaves [0, R) whatever the array holds.
+// Which rows: group g of a grouped bank is the rows offsets[g] .. offsets[g + 1] - 1 of its R rows; without offsets (null) the
+// bank is one group of all R rows.  The branch is uniform over the launch.  The host has checked the offsets; the device still clamps what it
+// reads from them, so that no address leaves [0, R) whatever the array holds.
 __device__ __forceinline__ void group_rows(const int* __restrict__ offsets, int g, int R, int& lo, int& n) {
+  if (!offsets) { lo = 0; n = R; return; }
   lo = min(max(offsets[g], 0), R);
   n = min(max(offsets[g + 1], lo), R) - lo;
 }
 
 // centre[g] = the centre of group g's rows alone, in the order above: workgroup (64 columns, g).  The group's place enters the addresses only.
-__global__ __launch_bounds__(256) void group_centre_kernel(const float* __restrict__ mean, const int* __restrict__ offsets, int R, int C,
-                                                           float* __restrict__ centre) {
+__global__ __launch_bounds__(256) void centre_kernel(const float* __restrict__ mean, const int* __restrict__ offsets, int R, int C,
+                                                     float* __restrict__ centre) {
   int lo, n;
   group_rows(offsets, blockIdx.y, R, lo, n);
   centre_columns(mean + (size_t)lo * C, n, C, centre + (size_t)blockIdx.y * C);
@@ -86,20 +84,13 @@ __device__ __forceinline__ void unit_row(const float* __restrict__ m, const floa
   for (int c = lane; c < C; c += 64) unit[c] = (m[c] - centre[c]) * inv;
 }
 
-__global__ __launch_bounds__(256) void descriptor_unit_kernel(const float* __restrict__ mean, int I, int C, const float* __restrict__ centre,
-                                                              float* __restrict__ unit) {
-  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= I) return;
-  unit_row(mean + (size_t)i * C, centre, C, unit + (size_t)i * C);
-}
-
 // the bank's units, every row against its own group's centre (G, C): one wave per row below offsets[G]; the rows behind are left alone.  A wave
-// finds its row's group by bisection of the offsets (wave-uniform).
-__global__ __launch_bounds__(256) void group_unit_kernel(const float* __restrict__ mean, const int* __restrict__ offsets, int G, int R, int C,
-                                                         const float* __restrict__ centre, float* __restrict__ unit) {
+// finds its row's group by bisection of the offsets (wave-uniform).  Without offsets: every row of R against the one centre.
+__global__ __launch_bounds__(256) void bank_unit_kernel(const float* __restrict__ mean, const int* __restrict__ offsets, int G, int R, int C,
+                                                        const float* __restrict__ centre, float* __restrict__ unit) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= min(offsets[G], R)) return;
-  int g = 0, hi = G;  // the last g with offsets[g] <= i
+  if (i >= (offsets ? min(offsets[G], R) : R)) return;
+  int g = 0, hi = offsets ? G : 1;  // the last g with offsets[g] <= i
   while (hi - g > 1) {
     const int mid = (g + hi) >> 1;
     if (offsets[mid] <= i) g = mid; else hi = mid;
@@ -107,8 +98,10 @@ __global__ __launch_bounds__(256) void group_unit_kernel(const float* __restrict
   unit_row(mean + (size_t)i * C, centre + (size_t)g * C, C, unit + (size_t)i * C);
 }
 
-// What the host resolves per query of a grouped call: its group's first row, its rows and its centre (SelTriple of cs_common.h)
+// What the host resolves per query of a grouped call: its group's first row, its rows and its centre (SelTriple of cs_common.h).  Without
+// triples (null, uniform over the launch) every query has the whole bank and the one centre.
 __device__ __forceinline__ void query_slice(const CsSelTriple* __restrict__ trip, int b, int R, int G, int& lo, int& n, int& g) {
+  if (!trip) { lo = 0; n = R; g = 0; return; }
   const CsSelTriple t = trip[b];
   lo = min(max(t.start, 0), R);
   n = min(max(t.len, 0), R - lo);
@@ -139,17 +132,9 @@ __device__ __forceinline__ float wave_dot(const float* __restrict__ q, const flo
   return wave_sum(acc);
 }
 
-__global__ __launch_bounds__(256) void similarity_kernel(const float* __restrict__ q, const float* __restrict__ bank, int R, int C,
-                                                         float* __restrict__ sim) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
-  if (r >= R) return;
-  const float acc = wave_dot(q + (size_t)b * C, bank + (size_t)r * C, C);
-  if ((threadIdx.x & 63) == 0) sim[(size_t)b * R + r] = acc;
-}
-
 // sim[b][j], j = 0 .. S - 1: query b against row j of its own slice of the bank; the columns behind the slice become a quiet NaN
-__global__ __launch_bounds__(256) void group_similarity_kernel(const float* __restrict__ q, const float* __restrict__ bank, int R, int G, int C,
-                                                               const CsSelTriple* __restrict__ trip, int S, float* __restrict__ sim) {
+__global__ __launch_bounds__(256) void similarity_kernel(const float* __restrict__ q, const float* __restrict__ bank, int R, int G, int C,
+                                                         const CsSelTriple* __restrict__ trip, int S, float* __restrict__ sim) {
   const int j = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
   if (j >= S) return;
   int lo, n, g;
@@ -205,18 +190,10 @@ __device__ __forceinline__ void topn_row(const float* __restrict__ s, int R, int
   }
 }
 
-// one workgroup per query over the whole bank
-__global__ __launch_bounds__(TOPN_THREADS) void topn_kernel(const float* __restrict__ sim, int R, const int* __restrict__ exclude, int N,
-                                                            int* __restrict__ index) {
-  const int b = blockIdx.x;
-  topn_row(sim + (size_t)b * R, R, exclude ? exclude[b] : -1, N, 0, index + (size_t)b * N);
-}
-
-// ... and over the query's slice: sim is (B, S), the picks are reported as bank rows, exclude[b] is a bank row (one outside the slice matches
-// no place of it)
-__global__ __launch_bounds__(TOPN_THREADS) void group_topn_kernel(const float* __restrict__ sim, int S, int R, int G,
-                                                                  const CsSelTriple* __restrict__ trip, const int* __restrict__ exclude, int N,
-                                                                  int* __restrict__ index) {
+// one workgroup per query over its slice of the bank: sim is (B, S), the picks are reported as bank rows, exclude[b] is a bank row (one outside
+// the slice matches no place of it)
+__global__ __launch_bounds__(TOPN_THREADS) void topn_kernel(const float* __restrict__ sim, int S, int R, int G, const CsSelTriple* __restrict__ trip,
+                                                            const int* __restrict__ exclude, int N, int* __restrict__ index) {
   const int b = blockIdx.x;
   int lo, n, g;
   query_slice(trip, b, R, G, lo, n, g);
@@ -254,35 +231,15 @@ hipError_t cs_token_descriptors_launch(const h16_t* tok, int I, int Np, int C, i
   return hipGetLastError();
 }
 
-hipError_t cs_descriptor_centre_launch(const float* mean, int R, int C, float* centre, hipStream_t st) {
-  hipLaunchKernelGGL(descriptor_centre_kernel, dim3((unsigned)(C / 64)), dim3(256), 0, st, mean, R, C, centre);
+// offsets (G + 1) and trip (B) are DEVICE copies of what the host resolved and checked, G <= 65535, G >= 1; null for a plain bank: one group of
+// all R rows (G = 1, S = R)
+hipError_t cs_centre_launch(const float* mean, const int32_t* offsets, int G, int R, int C, float* centre, hipStream_t st) {
+  hipLaunchKernelGGL(centre_kernel, dim3((unsigned)(C / 64), (unsigned)G), dim3(256), 0, st, mean, offsets, R, C, centre);
   return hipGetLastError();
 }
 
-hipError_t cs_descriptor_unit_launch(const float* mean, int I, int C, const float* centre, float* unit, hipStream_t st) {
-  hipLaunchKernelGGL(descriptor_unit_kernel, dim3((unsigned)((I + 3) / 4)), dim3(256), 0, st, mean, I, C, centre, unit);
-  return hipGetLastError();
-}
-
-// sim (B, R) = q (B, C) x bank (R, C)^T; C a multiple of 4, B <= 65535
-hipError_t cs_similarity_launch(const float* q, int B, const float* bank, int R, int C, float* sim, hipStream_t st) {
-  hipLaunchKernelGGL(similarity_kernel, dim3((unsigned)((R + 3) / 4), (unsigned)B), dim3(256), 0, st, q, bank, R, C, sim);
-  return hipGetLastError();
-}
-
-hipError_t cs_topn_launch(const float* sim, int B, int R, const int32_t* exclude, int N, int32_t* index, hipStream_t st) {
-  hipLaunchKernelGGL(topn_kernel, dim3((unsigned)B), dim3(TOPN_THREADS), 0, st, sim, R, exclude, N, index);
-  return hipGetLastError();
-}
-
-// the grouped forms: offsets (G + 1) and trip (B) are DEVICE copies of what the host resolved and checked; G <= 65535, G >= 1
-hipError_t cs_group_centre_launch(const float* mean, const int32_t* offsets, int G, int R, int C, float* centre, hipStream_t st) {
-  hipLaunchKernelGGL(group_centre_kernel, dim3((unsigned)(C / 64), (unsigned)G), dim3(256), 0, st, mean, offsets, R, C, centre);
-  return hipGetLastError();
-}
-
-hipError_t cs_group_unit_launch(const float* mean, const int32_t* offsets, int G, int rows, int R, int C, const float* centre, float* unit, hipStream_t st) {
-  hipLaunchKernelGGL(group_unit_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, mean, offsets, G, R, C, centre, unit);
+hipError_t cs_bank_unit_launch(const float* mean, const int32_t* offsets, int G, int rows, int R, int C, const float* centre, float* unit, hipStream_t st) {
+  hipLaunchKernelGGL(bank_unit_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, mean, offsets, G, R, C, centre, unit);
   return hipGetLastError();
 }
 
@@ -291,14 +248,14 @@ hipError_t cs_query_unit_launch(const float* mean, int B, int C, const CsSelTrip
   return hipGetLastError();
 }
 
-// sim (B, S): the grid is sized by the longest slice, not by the bank
-hipError_t cs_group_similarity_launch(const float* q, int B, const float* bank, int R, int G, int C, const CsSelTriple* trip, int S, float* sim, hipStream_t st) {
-  hipLaunchKernelGGL(group_similarity_kernel, dim3((unsigned)((S + 3) / 4), (unsigned)B), dim3(256), 0, st, q, bank, R, G, C, trip, S, sim);
+// sim (B, S) = q (B, C) x each query's slice of bank (R, C)^T: the grid is sized by the longest slice, not by the bank; C a multiple of 4, B <= 65535
+hipError_t cs_similarity_launch(const float* q, int B, const float* bank, int R, int G, int C, const CsSelTriple* trip, int S, float* sim, hipStream_t st) {
+  hipLaunchKernelGGL(similarity_kernel, dim3((unsigned)((S + 3) / 4), (unsigned)B), dim3(256), 0, st, q, bank, R, G, C, trip, S, sim);
   return hipGetLastError();
 }
 
-hipError_t cs_group_topn_launch(const float* sim, int B, int S, int R, int G, const CsSelTriple* trip, const int32_t* exclude, int N, int32_t* index, hipStream_t st) {
-  hipLaunchKernelGGL(group_topn_kernel, dim3((unsigned)B), dim3(TOPN_THREADS), 0, st, sim, S, R, G, trip, exclude, N, index);
+hipError_t cs_topn_launch(const float* sim, int B, int S, int R, int G, const CsSelTriple* trip, const int32_t* exclude, int N, int32_t* index, hipStream_t st) {
+  hipLaunchKernelGGL(topn_kernel, dim3((unsigned)B), dim3(TOPN_THREADS), 0, st, sim, S, R, G, trip, exclude, N, index);
   return hipGetLastError();
 }
 

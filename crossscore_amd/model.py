@@ -335,6 +335,19 @@ class CrossScoreNet(torch.nn.Module):
             results["score_mean_ref_cross"] = mean_out  # key does not start with "score_map": writers ignore it
         return results
 
+    def _score(self, call, B, N, H, W, dev, need_attn_weights, head_id, return_mean):
+        """The plumbing every forward call shares: the outputs, the sub-batches (_sub_batches) and the result dict.  call(b0, b1, tail) makes
+        the C call for the items b0 .. b1 - 1 and returns its code; tail = (score, attn | None, head id, mean | None, stream) of those items."""
+        P = self.arch.patch
+        with torch.cuda.device(dev):
+            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            for b0, b1 in self._sub_batches(B, N, (H // P) * (W // P)):
+                _lib.check(call(b0, b1, (C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
+                                         int(head_id), C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None,
+                                         C.c_void_p(stream))))
+        return self._results(score, attn, mean_out)
+
     @torch.no_grad()
     def forward(self, query_img, ref_cross_imgs, need_attn_weights=False, need_attn_weights_head_id=0, norm_img=False,
                 return_mean=False):
@@ -369,23 +382,12 @@ class CrossScoreNet(torch.nn.Module):
         r = ref_cross_imgs.to(device=dev, dtype=torch.float32).contiguous()
         B, _, H, W = q.shape
         N = r.shape[1]
-        P = self.arch.patch
-        h, w = H // P, W // P
         self._check_pe_mode(H, W)
         lib = _lib.load()
         handle = self._ensure_handle(dev)
-        with torch.cuda.device(dev):
-            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for b0, b1 in self._sub_batches(B, N, h * w):
-                rc = lib.cs_forward(handle, C.c_void_p(q[b0:b1].data_ptr()), C.c_void_p(r[b0:b1].data_ptr()), b1 - b0, N, H, W,
-                                    C.c_void_p(score[b0:b1].data_ptr()),
-                                    C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
-                                    int(need_attn_weights_head_id),
-                                    C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None,
-                                    C.c_void_p(stream))
-                _lib.check(rc)
-        return self._results(score, attn, mean_out)
+        return self._score(lambda b0, b1, tail: lib.cs_forward(handle, C.c_void_p(q[b0:b1].data_ptr()), C.c_void_p(r[b0:b1].data_ptr()),
+                                                               b1 - b0, N, H, W, *tail),
+                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean)
 
     def _sub_batches(self, B: int, N: int, Np: int):
         """Items are independent, so a batch whose decoder buffers would overflow the kernels' 32-bit element offsets
@@ -435,16 +437,9 @@ class CrossScoreNet(torch.nn.Module):
             raise ValueError("ref_tokens do not match the query's patch grid / hidden size")
         handle = self._ensure_handle(dev)
         lib = _lib.load()
-        with torch.cuda.device(dev):
-            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for b0, b1 in self._sub_batches(B, N, h * w):
-                _lib.check(lib.cs_forward_cached(
-                    handle, C.c_void_p(q[b0:b1].data_ptr()), C.c_void_p(t[b0:b1].data_ptr()), b1 - b0, N, H, W,
-                    C.c_void_p(score[b0:b1].data_ptr()),
-                    C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None, int(need_attn_weights_head_id),
-                    C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None, C.c_void_p(stream)))
-        return self._results(score, attn, mean_out)
+        return self._score(lambda b0, b1, tail: lib.cs_forward_cached(handle, C.c_void_p(q[b0:b1].data_ptr()), C.c_void_p(t[b0:b1].data_ptr()),
+                                                                      b1 - b0, N, H, W, *tail),
+                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean)
 
     # -- the same three calls fed from decoded uint8 images (SURVEY.md 8f-4 as worded: uint8 in, tokens out) --------------------------------
     def u8_input_supported(self, img: U8Image, size, device=None) -> bool:
@@ -470,16 +465,9 @@ class CrossScoreNet(torch.nn.Module):
         self._check_pe_mode(H, W)
         lib = _lib.load()
         handle = self._ensure_handle(dev)
-        P = self.arch.patch
-        with torch.cuda.device(dev):
-            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for b0, b1 in self._sub_batches(B, N, (H // P) * (W // P)):
-                _lib.check(lib.cs_forward_u8(handle, query.c_array(b0, b1), refs.c_array(b0 * N, b1 * N), b1 - b0, N, H, W, query.mean, query.std,
-                                             C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
-                                             int(need_attn_weights_head_id),
-                                             C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None, C.c_void_p(stream)))
-        return self._results(score, attn, mean_out)
+        return self._score(lambda b0, b1, tail: lib.cs_forward_u8(handle, query.c_array(b0, b1), refs.c_array(b0 * N, b1 * N),
+                                                                  b1 - b0, N, H, W, query.mean, query.std, *tail),
+                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean)
 
     @torch.no_grad()
     def encode_references_u8(self, imgs: U8Batch):
@@ -514,15 +502,9 @@ class CrossScoreNet(torch.nn.Module):
         self._check_pe_mode(H, W)
         lib = _lib.load()
         handle = self._ensure_handle(dev)
-        with torch.cuda.device(dev):
-            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for b0, b1 in self._sub_batches(B, N, (H // P) * (W // P)):
-                _lib.check(lib.cs_forward_cached_u8(handle, query.c_array(b0, b1), C.c_void_p(t[b0:b1].data_ptr()), b1 - b0, N, H, W, query.mean, query.std,
-                                                    C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
-                                                    int(need_attn_weights_head_id),
-                                                    C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None, C.c_void_p(stream)))
-        return self._results(score, attn, mean_out)
+        return self._score(lambda b0, b1, tail: lib.cs_forward_cached_u8(handle, query.c_array(b0, b1), C.c_void_p(t[b0:b1].data_ptr()),
+                                                                         b1 - b0, N, H, W, query.mean, query.std, *tail),
+                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean)
 
     # -- reference selection by similarity: the choice of each query's views is made on the device ----------------------
     @torch.no_grad()
@@ -538,22 +520,21 @@ class CrossScoreNet(torch.nn.Module):
         lib = _lib.load()
         with torch.cuda.device(dev):
             st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            grouped = offsets is not None
+            off = _group_offsets(offsets, R) if grouped else None
             mean = torch.empty((R, Cc), dtype=torch.float32, device=dev)
-            centre = torch.empty((Cc,), dtype=torch.float32, device=dev)
-            if offsets is not None:
-                off = _group_offsets(offsets, R)
-                centre = torch.empty((len(off) - 1, Cc), dtype=torch.float32, device=dev)
-            unit = (torch.empty if offsets is None else torch.zeros)((R, Cc), dtype=torch.float32, device=dev)
+            centre = torch.empty((len(off) - 1, Cc) if grouped else (Cc,), dtype=torch.float32, device=dev)
+            unit = (torch.zeros if grouped else torch.empty)((R, Cc), dtype=torch.float32, device=dev)
             code = _lib.DTYPE_BF16 if t.dtype == torch.bfloat16 else _lib.DTYPE_F16
             for r0 in range(0, R, 32768):  # (an image's mean does not depend on the launch it is part of)
                 r1 = min(R, r0 + 32768)
                 _lib.check(lib.cs_op_token_descriptors(C.c_void_p(t[r0:r1].data_ptr()), r1 - r0, Np, Cc, code, C.c_void_p(mean[r0:r1].data_ptr()), st))
-            if offsets is not None:
+            if grouped:
                 _lib.check(lib.cs_op_group_descriptors(C.c_void_p(mean.data_ptr()), R, Cc, off.ctypes.data_as(C.c_void_p), len(off) - 1,
                                                        C.c_void_p(centre.data_ptr()), C.c_void_p(unit.data_ptr()), st))
-                return mean, centre, unit
-            _lib.check(lib.cs_op_descriptor_centre(C.c_void_p(mean.data_ptr()), R, Cc, C.c_void_p(centre.data_ptr()), st))
-            _lib.check(lib.cs_op_descriptor_unit(C.c_void_p(mean.data_ptr()), R, Cc, C.c_void_p(centre.data_ptr()), C.c_void_p(unit.data_ptr()), st))
+            else:
+                _lib.check(lib.cs_op_descriptor_centre(C.c_void_p(mean.data_ptr()), R, Cc, C.c_void_p(centre.data_ptr()), st))
+                _lib.check(lib.cs_op_descriptor_unit(C.c_void_p(mean.data_ptr()), R, Cc, C.c_void_p(centre.data_ptr()), C.c_void_p(unit.data_ptr()), st))
         return mean, centre, unit
 
     def _forward_select(self, query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, u8, group=None):
@@ -599,34 +580,21 @@ class CrossScoreNet(torch.nn.Module):
         self._check_pe_mode(H, W)
         lib = _lib.load()
         handle = self._ensure_handle(dev)
+        fn = getattr(lib, "cs_forward_select" + ("_grouped" if grouped else "") + ("_u8" if u8 else ""))
+        bank_args = (C.c_void_p(t.data_ptr()), C.c_void_p(bank.unit.data_ptr()), C.c_void_p(bank.centre.data_ptr()), R)
         with torch.cuda.device(dev):
-            score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
             index = torch.empty((B, N), dtype=torch.int32, device=dev)
             sim = torch.empty((B, bank.longest_group), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            for b0, b1 in self._sub_batches(B, N, h * w):
-                if grouped:  # (the host arrays are copied into a pinned slot inside the call: they need not outlive it)
-                    sel = (C.c_void_p(t.data_ptr()), C.c_void_p(bank.unit.data_ptr()), C.c_void_p(bank.centre.data_ptr()), R,
-                           bank.offsets.ctypes.data_as(C.c_void_p), len(bank.offsets) - 1, grp[b0:b1].ctypes.data_as(C.c_void_p), bank.blank_row,
-                           C.c_void_p(ex[b0:b1].data_ptr()) if ex is not None else None, b1 - b0, N, H, W)
-                    rest = (C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
-                            int(need_attn_weights_head_id), C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None,
-                            C.c_void_p(index[b0:b1].data_ptr()), C.c_void_p(sim[b0:b1].data_ptr()), C.c_void_p(stream))
-                    if u8:
-                        _lib.check(lib.cs_forward_select_grouped_u8(handle, query.c_array(b0, b1), *sel, query.mean, query.std, *rest))
-                    else:
-                        _lib.check(lib.cs_forward_select_grouped(handle, C.c_void_p(q[b0:b1].data_ptr()), *sel, *rest))
-                    continue
-                tail = (C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
-                        int(need_attn_weights_head_id), C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None,
-                        C.c_void_p(index[b0:b1].data_ptr()), C.c_void_p(sim[b0:b1].data_ptr()), C.c_void_p(stream))
-                head = (C.c_void_p(t.data_ptr()), C.c_void_p(bank.unit.data_ptr()), C.c_void_p(bank.centre.data_ptr()), R,
-                        C.c_void_p(ex[b0:b1].data_ptr()) if ex is not None else None, b1 - b0, N, H, W)
-                if u8:
-                    _lib.check(lib.cs_forward_select_u8(handle, query.c_array(b0, b1), *head, query.mean, query.std, *tail))
-                else:
-                    _lib.check(lib.cs_forward_select(handle, C.c_void_p(q[b0:b1].data_ptr()), *head, *tail))
-            results = self._results(score, attn, mean_out)
+
+            def call(b0, b1, tail):
+                # (a grouped bank's host arrays are copied into a pinned slot inside the call: they need not outlive it)
+                groups = (bank.offsets.ctypes.data_as(C.c_void_p), len(bank.offsets) - 1, grp[b0:b1].ctypes.data_as(C.c_void_p),
+                          bank.blank_row) if grouped else ()
+                return fn(handle, query.c_array(b0, b1) if u8 else C.c_void_p(q[b0:b1].data_ptr()), *bank_args, *groups,
+                          C.c_void_p(ex[b0:b1].data_ptr()) if ex is not None else None, b1 - b0, N, H, W, *((query.mean, query.std) if u8 else ()),
+                          *tail[:4], C.c_void_p(index[b0:b1].data_ptr()), C.c_void_p(sim[b0:b1].data_ptr()), tail[4])
+
+            results = self._score(call, B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean)
             results["reference_index"] = index
             # the similarities of the chosen entries, in the order chosen (an index of -1, a query that ran out of candidates, reads entry 0)
             if grouped:  # a column of sim is a place in the query's group; a padded place (-1) is NaN

@@ -199,7 +199,8 @@ int cs_forward_select_u8(cs_handle h, const cs_u8_image* query, const uint16_t* 
  *   cs_op_gather_tokens_ex           cs_op_gather_tokens with blank_row: an index outside [0, R) takes bank row blank_row's tokens when
  *                                    blank_row >= 0 (the encoder's tokens of the all-zero placeholder image), zeros when it is -1
  *   cs_forward_select_grouped*       cs_forward_select* on such a bank: centre is (G, C), sim_out NULL or (B, S); the gather takes blank_row.  With
- *                                    G = 1 over all rows and blank_row = -1 every output has the bits of cs_forward_select*. */
+ *                                    G = 1 over all rows and blank_row = -1 every output has the bits of cs_forward_select*: the ungrouped
+ *                                    calls run the same kernels, told "one group of all R rows" by a NULL slice, and upload nothing. */
 int cs_op_group_descriptors(const float* mean, int R, int C, const int32_t* offsets /* HOST (G + 1) */, int G, float* centre_out /* (G, C) */,
                             float* unit_out /* (R, C) */, cs_stream stream);
 int cs_op_select_references_grouped(const float* q_mean, int B, const int32_t* query_group /* HOST (B) */, const float* bank_unit,
