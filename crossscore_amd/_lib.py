@@ -155,6 +155,7 @@ SYMBOLS = {
     "cs_gemm_column_tiles": (_i, [_i]),
     "cs_debug_gemm256_enable": (None, [_i]),
     "cs_debug_gemm256_kmin": (None, [_i]),
+    "cs_debug_gemm_grid": (None, [_i]),
     "cs_debug_panel_impl": (None, [_i]),
     "cs_panel_supported": (_i, [_i, _i]),
     "cs_panel_image_bytes": (_sz, [_i]),

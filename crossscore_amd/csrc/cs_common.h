@@ -278,6 +278,7 @@ const char* cs_gemm_check(const CsGemmParams* p, int epi);
 hipError_t cs_gemm_launch(const CsGemmParams* p, int epi, hipStream_t stream);
 int cs_gemm256_supported(const CsGemmParams* p, int epi);  // the shapes cs_gemm_launch routes to the 256-tile kernel
 hipError_t cs_gemm256_launch(const CsGemmParams* p, int epi, int bf16, hipStream_t st);
+extern int g_gemm_grid;  // cs_debug_gemm_grid: > 0 replaces the CU-derived block count of both GEMM launchers (before their clamps); 0 = off
 // attention.hip
 const char* cs_attn_check(const CsAttnParams* p, int dh, int batch);
 hipError_t cs_attn_launch(const CsAttnParams* p, int dh, int batch, hipStream_t stream);

@@ -736,7 +736,8 @@ hipError_t launch_nb(const CsGemmParams& p, hipStream_t stream) {
   // p.bpc > 2 oversubscribes the CUs (only two blocks are resident per CU; the rest queue behind them): each block then walks
   // fewer tiles and gives its slot back sooner, which pays when a second stream's kernels share the GPU (two encoder lanes:
   // -2 % step time with 3..16 blocks per CU) and costs when the kernel runs alone (+1..5 %).
-  int grid = ((p.bpc > 0 ? p.bpc : 2) * g_num_cus[dev] / 8) * 8;
+  const int dbg_grid = g_gemm_grid;  // cs_debug_gemm_grid (tests): a block count in place of the CU-derived one, same clamps
+  int grid = ((dbg_grid > 0 ? dbg_grid : (p.bpc > 0 ? p.bpc : 2) * g_num_cus[dev]) / 8) * 8;
 #ifdef CS_ABLATE
   if (const char* e = getenv("CS_GEMM_GRID")) grid = atoi(e);
 #endif
@@ -802,9 +803,9 @@ hipError_t launch(const CsGemmParams& p, hipStream_t stream) {
 // column tile the launcher picks for N (the LayerNorm partial-sum slots of a producer are 4 per column tile)
 extern "C" int cs_gemm_column_tiles(int N) { return N % 192 == 0 ? N / 192 : (N + 127) / 128; }
 
-namespace {
-
-}  // namespace
+// tests: block count of the persistent grids of this kernel and of gemm256.hip's, read at every launch; 0 = from the CU count
+int g_gemm_grid = 0;
+extern "C" void cs_debug_gemm_grid(int blocks) { g_gemm_grid = blocks > 0 ? blocks : 0; }
 
 // Host-side shape contract (checked here so a bad call fails loudly instead of faulting on the GPU).
 extern "C" const char* cs_gemm_check(const CsGemmParams* p, int epi) {

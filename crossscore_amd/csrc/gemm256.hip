@@ -522,7 +522,8 @@ hipError_t launch256(const CsGemmParams& p, hipStream_t st) {
   }
   const int tiles_n = p.N / G_BN, tiles_m = (p.M + G_BM - 1) / G_BM;
   // one persistent workgroup per CU (LDS and registers admit one); the grid is a multiple of 8 so that b % 8 labels the XCD group
-  int grid = (num_cus[dev] / 8) * 8;
+  const int dbg_grid = g_gemm_grid;  // cs_debug_gemm_grid (tests)
+  int grid = ((dbg_grid > 0 ? dbg_grid : num_cus[dev]) / 8) * 8;
   const int need = ((tiles_m + 7) / 8) * tiles_n * 8;
   if (grid > need) grid = need;
   if (grid < 8) grid = 8;

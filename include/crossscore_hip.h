@@ -580,6 +580,11 @@ int cs_op_encoder_panel(float* x, const uint16_t* attn_o, const uint16_t* img, c
 void cs_debug_gemm256_enable(int on);
 /* debug switch, process-wide: the smallest K the 256-tile kernel takes (default 384; tools/qkv_k384_try.py compares 384 with 512) */
 void cs_debug_gemm256_kmin(int k);
+/* debug switch, process-wide, read at every launch (single ops and whole forwards alike): the block count of the persistent grids of both GEMM
+ * kernels in place of the CU-derived one (2 x CUs for the 128-row kernel, 1 x CUs for the 256-tile kernel).  The launchers' clamps still apply:
+ * rounded down to a multiple of 8, at most one block per tile of the fullest XCD, at least 8.  0 (the default) = from the CU count.  With 8 blocks
+ * each XCD's single block walks all of its tiles; with 16 two blocks of an XCD interleave.  The results do not depend on it (tested). */
+void cs_debug_gemm_grid(int blocks);
 /* The decoder's sub-block closing  x = LN(x + Linear(y))  (model/customised_transformer/transformer.py:157-173) in one launch (csrc/rowln.hip;
  * K = N = C = 384: the ViT-S decoder): out_f32 / out_f16 (M, C) = LayerNorm(resid + A W^T + bias; gamma, beta, eps); resid may be NULL
  * (decoder_do_short_cut off) and may alias out_f32.  CS_ERR_BAD_ARG for other widths (the forward then runs GEMM + LayerNorm).

@@ -136,14 +136,15 @@ def _gemm_case(M, N, K, epi, pad=0, inplace=False, bf16=False, g256=False, rando
 _E = {"bias": _lib.EPI_BIAS_F16, "gelu": _lib.EPI_BIAS_GELU_F16, "relu": _lib.EPI_BIAS_RELU_F16, "leaky": _lib.EPI_BIAS_LEAKY_F16,
       "resid": _lib.EPI_RESID_F32}
 
-# (M, N, K, epilogue, pad, in place): the 128-row kernel; 128- / 192-column tiles, BK = 64, residual prefetch (PIPE) at K / 64 >= 9
+# (M, N, K, epilogue, pad, in place): the 128-row kernel; 128- / 192-column tiles, BK = 32, residual prefetch (PIPE) at K / 32 >= 9 (K >= 320)
 GEMM128 = [
     # rows: one row, a partial tile, one short of / at / one past a tile edge, many tiles; ragged N = 136 (128-column tiles)
     *[(M, 136, 64, "bias", 0, False) for M in (1, 17, 127, 128, 129, 1000)],
     # columns: ragged (136, 200), narrow 128-multiples (128, 256, 384), 192-multiples (576, 1152), > 1536 (1664: 128 tiles, 1728: 192 tiles)
     *[(129, N, 576, "resid", 0, False) for N in (136, 200, 128, 256, 384, 576, 1152, 1664, 1728)],
-    # K below / at / above the residual-prefetch threshold (9 K slices), PIPE x ragged N, in place and with poisoned pitches
-    *[(129, 200, K, "resid", 0, True) for K in (64, 512, 576, 1536)],
+    # K below / at / above the residual-prefetch threshold (K = 256: 8 slices, the last without PIPE; K = 320: 10 slices, the first with it),
+    # PIPE x ragged N, in place and with poisoned pitches
+    *[(129, 200, K, "resid", 0, True) for K in (64, 256, 320, 512, 576, 1536)],
     (300, 136, 1536, "resid", 8, False), (17, 200, 576, "resid", 24, True), (1000, 1728, 576, "resid", 8, True),
     # tiles_m in {1, 7, 8, 9} with two or more column tiles
     *[(M, 256, 64, "bias", 0, False) for M in (100, 7 * 128 - 3, 8 * 128, 9 * 128 - 5)],
