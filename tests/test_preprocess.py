@@ -202,13 +202,13 @@ def test_patch_embedding_straight_from_uint8_is_bit_identical(h, w, short, crop,
     _one_pass_against_two_launches(h, w, rs, crop, pad)
 
 
-def _one_pass_against_two_launches(h, w, rs, crop, pad, bf16=False):
+def _one_pass_against_two_launches(h, w, rs, crop, pad, bf16=False, Cc=384):
     """tokens of cs_op_patch_embed_fused_u8 == tokens of cs_op_preprocess_u8 + cs_op_patch_embed_fused, two images, bit for bit"""
     import torch
     import hip_helpers as hh
     from crossscore_amd import _lib
 
-    P, Cc = 14, 384
+    P = 14
     rng = np.random.Generator(np.random.PCG64(h * 7 + w))
     imgs = rng.integers(0, 256, size=(2, h, w, 3), dtype=np.uint8)
     imgs[1, ..., 1] = ((np.arange(h)[:, None] * 3 + np.arange(w)[None, :] * 2) % 256).astype(np.uint8)
@@ -274,6 +274,9 @@ U8_EDGES = {
 }
 for _gw, _runs in _wide.items():  # no resize, one patch row: the LDS layout changes between 37 and 38 patches per run, a run holds 48
     U8_EDGES[f"wide_{_gw}"] = (14, 14 * _gw, (14, 14 * _gw), (0, 0, 14, 14 * _gw), 0, False, lambda span, runs, want=_runs: span == 14 and runs == want)
+# C = 768: the uint8 form's second 384-column pass (it shares phases B and C with the float form), on two unequal runs
+U8_EDGES["wide_49_two_passes"] = U8_EDGES["wide_49"]
+U8_EDGE_WIDTH = {"wide_49_two_passes": 768}  # every other case: 384
 
 
 @pytest.mark.gpu
@@ -285,7 +288,7 @@ def test_patch_embedding_straight_from_uint8_at_its_edges(name):
     h, w, rs, crop, pad, bf16, prop = U8_EDGES[name]
     span = _row_span(h, rs[0], crop[0], crop[2])
     assert prop(span, _u8_runs(crop[3], span)), (span, _u8_runs(crop[3], span))
-    _one_pass_against_two_launches(h, w, rs, crop, pad, bf16)
+    _one_pass_against_two_launches(h, w, rs, crop, pad, bf16, U8_EDGE_WIDTH.get(name, 384))
 
 
 @pytest.mark.gpu
