@@ -1,5 +1,5 @@
 // The host's walk over a JPEG file's marker segments (cs_jpeg_probe, cs_jpeg_probe_ex): plain C++ over untrusted bytes, no device and no HIP,
-// so that it also builds into a stand-alone program under sanitizers (tools/jpeg_probe_fuzz.cpp).  It never reads at or beyond file + n.
+// so that it also builds into a stand-alone program under sanitizers (tools/probe_fuzz.cpp).  It never reads at or beyond file + n.
 //
 // Without CS_JPEG_PROBE_PROGRESSIVE the walk ends at the SOS of a baseline file.  With it a SOF2 file is walked to its EOI: every scan is
 // checked against T.81 G.1.1.1.1 (what libjpeg only warns about is refused here) and the progression has to be complete, because an incomplete

@@ -2,6 +2,7 @@
 // the PNG, ground-truth-map and score helpers the predict / evaluate drivers call.  Host-side only: argument checks, then one launch.
 #include "cs_model.h"
 #include "jpeg_probe.h"
+#include "png_probe.h"
 
 #include <cmath>
 #include <cstring>
@@ -325,63 +326,12 @@ int cs_op_png_encode(const void* pixels, int kind, int I, int H, int W, long lon
   return cs_op_png_encode_ex(pixels, kind, I, H, W, image_stride_bytes, out, slot_bytes, lengths, workspace, stream, 0);
 }
 
-// ---- PNG decoder (pngdec.hip): the host probe, the workspace size and the launch
+// ---- PNG decoder (pngdec.hip): the host probe (png_probe.h), the workspace size and the launch
 int cs_png_probe(const uint8_t* file, size_t n, cs_png_info* info, cs_png_span* spans, int max_spans) {
-  static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
   if (!file || !info || max_spans < 0) return fail(CS_ERR_BAD_ARG, "png_probe: null pointer");
-  memset(info, 0, sizeof *info);
-  info->kind = -1;
-  if (memcmp(file, sig, n < 8 ? n : 8) != 0) return fail(CS_ERR_UNSUPPORTED, "png_probe: not a PNG file (no PNG signature)");
-  if (n < 8) return fail(CS_ERR_BAD_ARG, "png_probe: %zu bytes end inside the PNG signature", n);
-  if (n >= ((size_t)1 << 28)) return fail(CS_ERR_UNSUPPORTED, "png_probe: a file of %zu bytes is above the decoder's 256 MiB", n);
-  auto be = [&](size_t p) { return ((uint32_t)file[p] << 24) | ((uint32_t)file[p + 1] << 16) | ((uint32_t)file[p + 2] << 8) | file[p + 3]; };
-  size_t pos = 8;
-  int count = 0;
-  bool have_ihdr = false, have_end = false, palette = false;
-  unsigned long long idat_bytes = 0;
-  while (!have_end) {
-    if (n - pos < 12) return fail(CS_ERR_BAD_ARG, "png_probe: the file ends inside a chunk's framing at byte %zu (no IEND)", pos);
-    const uint32_t len = be(pos);
-    if (len > n - pos - 12) return fail(CS_ERR_BAD_ARG, "png_probe: the chunk at byte %zu is %u bytes long and runs past the file's end", pos, len);
-    const uint8_t* t = file + pos + 4;
-    if (!have_ihdr) {
-      if (memcmp(t, "IHDR", 4) != 0 || len != 13) return fail(CS_ERR_BAD_ARG, "png_probe: the first chunk is not a 13-byte IHDR");
-      have_ihdr = true;
-      info->width = (int)be(pos + 8);
-      info->height = (int)be(pos + 12);
-      if (be(pos + 8) == 0 || be(pos + 12) == 0 || be(pos + 8) > 0x7fffffffu || be(pos + 12) > 0x7fffffffu) return fail(CS_ERR_BAD_ARG, "png_probe: IHDR size 0 or above 2^31 - 1");
-      info->bit_depth = file[pos + 16];
-      info->color_type = file[pos + 17];
-      info->interlace = file[pos + 20];
-      if (file[pos + 18] != 0 || file[pos + 19] != 0) return fail(CS_ERR_UNSUPPORTED, "png_probe: compression / filter method %d / %d", file[pos + 18], file[pos + 19]);
-    } else if (memcmp(t, "IDAT", 4) == 0) {
-      if (spans && count < max_spans) { spans[count].offset = (uint32_t)(pos + 8); spans[count].length = len; }
-      count += 1;
-      idat_bytes += len;
-    } else if (memcmp(t, "IEND", 4) == 0) {
-      have_end = true;
-    } else if (memcmp(t, "PLTE", 4) == 0) {
-      palette = true;
-    } else if (!(t[0] & 0x20)) {
-      return fail(CS_ERR_UNSUPPORTED, "png_probe: unknown critical chunk %.4s", (const char*)t);
-    }
-    pos += 12 + (size_t)len;
-  }
-  (void)palette;
-  info->num_idat = count;
-  info->idat_bytes = idat_bytes;
-  if (count == 0) return fail(CS_ERR_BAD_ARG, "png_probe: no IDAT chunk");
-  if (info->interlace != 0) return fail(CS_ERR_UNSUPPORTED, "png_probe: interlaced files are not decoded on the device");
-  const int ct = info->color_type, d = info->bit_depth;
-  if (d == 8 && (ct == 2 || ct == 6 || ct == 0)) info->kind = CS_PNG_RGB8;
-  else if (d == 16 && ct == 0) info->kind = CS_PNG_GRAY16;
-  else return fail(CS_ERR_UNSUPPORTED, "png_probe: colour type %d with bit depth %d is not decoded on the device (8-bit gray / RGB / RGBA, 16-bit gray)", ct, d);
-  if (!cs_png_size_supported(info->height, info->width)) {
-    info->kind = -1;
-    return fail(CS_ERR_UNSUPPORTED, "png_probe: %d x %d is larger than 4096 x 4096", info->height, info->width);
-  }
-  if (spans && count > max_spans) return fail(CS_ERR_BAD_ARG, "png_probe: %d IDAT chunks, room for %d spans", count, max_spans);
-  return 0;
+  char why[256];
+  const int rc = cs_png_probe_walk(file, n, info, spans, max_spans, why, sizeof why);
+  return rc == CS_OK ? 0 : fail(rc, "%s", why);
 }
 
 size_t cs_png_decode_workspace_bytes(int kind, int I, int H, int W, size_t total_file_bytes) {

@@ -36,6 +36,7 @@
 // Two launches per call whatever I is; nothing waits for the device.  The bytes of an image depend on its pixels, size and kind alone.
 #include "cs_common.h"
 #include "png_huff.h"
+#include "png_probe.h"
 
 #define CS_PNG_SEG 16384
 #define CS_PNG_SLOT (CS_PNG_SEG + 64)   // staging bytes per segment: 16-byte record + chunk (<= 12 + 2 + 5 + SEG) + slack for word reads
@@ -714,7 +715,7 @@ hipError_t png_launch_segments(const uint8_t* pixels, long long image_stride, co
 extern "C" {
 
 // 4096 x 4096 RGB: 50 335 744 filtered bytes, 3073 segments
-int cs_png_size_supported(int H, int W) { return H <= 4096 && W <= 4096; }
+int cs_png_size_supported(int H, int W) { return H <= CS_PNG_MAX_SIDE && W <= CS_PNG_MAX_SIDE; }
 
 size_t cs_png_bound_bytes(int kind, int H, int W) {
   PngGeom g;

@@ -46,7 +46,8 @@ import torch
 
 from . import _lib, parallel, scoring
 from .config import load_config, this_main_choice
-from .data import EMPTY, InputStage, decode_items, metric_mode, read_image_u8, read_metric_map_u16
+from .data import EMPTY, InputStage, decode_items, metric_mode
+from .decode import read_image_u8, read_metric_map_u16
 from .nvs import NvsItems, random_order
 
 METRIC_KEYS = ("test/loss", "test/loss_cross", "test/corr_cross", "test/psnr_cross")

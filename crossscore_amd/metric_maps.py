@@ -27,7 +27,8 @@ import torch
 
 from . import _lib, parallel
 from .config import load_config
-from .data import InputStage, read_image_u8
+from .data import InputStage
+from .decode import read_image_u8
 from .nvs import DATA_SPLITS
 from .writers import PngEncoder, png_compression_choice, save_png, save_png_bytes
 

@@ -23,8 +23,8 @@ import numpy as np
 import torch
 
 from . import parallel, synth
-from .data import (EMPTY, STRATEGIES, DecodeWindow, PngDecoder, ReferenceBank, ReferenceTokenCache, decode_items, jpeg_decoder_choice, jpeg_progressive_choice, load_batch, plan_decodes,
-                   png_decode_window_choice, png_decoder_choice, read_image_u8)
+from .data import EMPTY, STRATEGIES, ReferenceBank, ReferenceTokenCache, decode_items, load_batch, plan_decodes
+from .decode import DecodeWindow, ImageDecoder, jpeg_decoder_choice, jpeg_progressive_choice, png_decode_window_choice, png_decoder_choice, read_image_u8
 from .model import CrossScoreNet, U8Image, load_lightning_checkpoint
 from .pipeline import ForwardPipeline
 from .writers import BatchWriter, ScoreSummariser, png_compression_choice, png_encoder_choice
@@ -51,7 +51,7 @@ def options(cfg, phase: str) -> SimpleNamespace:
     # or compact (per-row adaptive filter, dynamic-Huffman blocks); ignored with png_encoder=host
     o.png_compression = png_compression_choice(cfg)
     # this_main.png_decoder (default "host"): who decodes the PNG inputs -- PIL on the loader's threads, or the device
-    # (data.PngDecoder: the compressed bytes go up, a window of this_main.png_decode_window upcoming files is decoded beside earlier forwards;
+    # (decode.ImageDecoder: the compressed bytes go up, a window of this_main.png_decode_window upcoming files is decoded beside earlier forwards;
     # the same pixels, bit for bit; files the device decoder does not take still go through PIL).  In evaluate the window also holds the 16-bit
     # metric maps (gt_metric_maps=files) or the captured images (compute)
     o.png_decoder, o.decode_window = png_decoder_choice(cfg), png_decode_window_choice(cfg)
@@ -195,7 +195,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     # ... from the candidate lists THIS rank's batches name, in their order: bank_group maps an item's "reference/cross/group" to the bank's
     bank_group = {g: k for k, g in enumerate(sorted({it["reference/cross/group"] for its in batches for it in its}))} if grouped else None
     selection = []  # ... and per query (path, chosen reference paths, their similarities), in consumption order
-    decoder = PngDecoder(device, pool, png=o.png_decoder == "gpu", jpeg=o.jpeg_decoder == "gpu",
+    decoder = ImageDecoder(device, pool, png=o.png_decoder == "gpu", jpeg=o.jpeg_decoder == "gpu",
                          progressive=o.jpeg_progressive == "gpu") if "gpu" in (o.png_decoder, o.jpeg_decoder) else None
     window = DecodeWindow(decoder, plan_decodes(batches, zero_ref, cache is not None, extra_files), o.decode_window) if decoder is not None else None
     n_cross = int(cfg.data.neighbour_config.cross)

@@ -143,20 +143,20 @@ def _block(items: Sequence, device):
 def frame_sums(frames: Sequence[Frame], source: str = "files", png_decoder: str = "host", workers: int = 16,
                device=None, jpeg_decoder: str = "host", jpeg_progressive: str = "host") -> Tuple[List[Tuple[int, int, int, int]], List[Tuple[int, int]]]:
     """(sums, sizes) of the frames: per frame its four integer sums and its (H, W).  png_decoder / jpeg_decoder: who decodes the PNG / baseline JPEG
-    files (data.PngDecoder when either is gpu)."""
+    files (decode.ImageDecoder when either is gpu)."""
     import torch
 
     from . import _lib
-    from .data import PNG_DECODERS, PngDecoder, read_image_u8, read_metric_map_u16
+    from .decode import DECODER_CHOICES, ImageDecoder, read_image_u8, read_metric_map_u16
     from .metric_maps import GROUP
 
     if source not in SOURCES:
         raise ValueError(f"source={source!r} not supported: files | compute")
-    if png_decoder not in PNG_DECODERS:
+    if png_decoder not in DECODER_CHOICES:
         raise ValueError(f"png_decoder={png_decoder!r} not supported: host | gpu")
-    if jpeg_decoder not in PNG_DECODERS:
+    if jpeg_decoder not in DECODER_CHOICES:
         raise ValueError(f"jpeg_decoder={jpeg_decoder!r} not supported: host | gpu")
-    if jpeg_progressive not in PNG_DECODERS:
+    if jpeg_progressive not in DECODER_CHOICES:
         raise ValueError(f"jpeg_progressive={jpeg_progressive!r} not supported: host | gpu")
     if jpeg_progressive == "gpu" and jpeg_decoder != "gpu":
         raise ValueError("jpeg_progressive=gpu needs jpeg_decoder=gpu")
@@ -180,7 +180,7 @@ def frame_sums(frames: Sequence[Frame], source: str = "files", png_decoder: str 
 
     pool = ThreadPoolExecutor(max_workers=max(1, int(workers)))
     try:
-        decoder = PngDecoder(device, pool, png=png_decoder == "gpu", jpeg=jpeg_decoder == "gpu",
+        decoder = ImageDecoder(device, pool, png=png_decoder == "gpu", jpeg=jpeg_decoder == "gpu",
                              progressive=jpeg_progressive == "gpu") if "gpu" in (png_decoder, jpeg_decoder) else None
         stream = torch.cuda.current_stream(device)
         st = C.c_void_p(stream.cuda_stream)

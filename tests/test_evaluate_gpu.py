@@ -46,7 +46,7 @@ def _map_path(tree, query_rel, mode):
 @pytest.mark.parametrize("case,short,patches", [("a_noresize", -1, True), ("a_s518", 518, True), ("a_s37", 37, False), ("c_s518", 518, True)])
 @pytest.mark.parametrize("mode", list(MODES))
 def test_metric_map_kernel_matches_reference(tree, case, short, patches, mode):
-    from crossscore_amd.data import read_metric_map_u16
+    from crossscore_amd.decode import read_metric_map_u16
 
     g = np.load(MAPS)
     key = f"{case}/{mode}"
@@ -96,7 +96,7 @@ def test_metric_map_placeholders_and_bad_arguments():
 @pytest.mark.parametrize("short", [-1, 56])
 def test_metric_maps_batched_equal_one_at_a_time(tree, short):
     """One launch pair over a batch (maps of two source sizes, placeholders between them) gives each map's bits of the one-map call."""
-    from crossscore_amd.data import read_metric_map_u16
+    from crossscore_amd.decode import read_metric_map_u16
 
     stage = _stage(short, True)
     base = os.path.join(tree, "res_540", "scene_a", "test")
@@ -119,7 +119,7 @@ def test_metric_maps_batched_equal_one_at_a_time(tree, short):
 @pytest.mark.gpu
 def test_metric_maps_do_not_wait_for_the_stream(tree):
     """The GT stage queues behind work already on the stream without waiting for it (pinned, non-blocking uploads)."""
-    from crossscore_amd.data import read_metric_map_u16
+    from crossscore_amd.decode import read_metric_map_u16
 
     if not hasattr(torch.cuda, "_sleep"):
         pytest.skip("torch.cuda._sleep is not available")
@@ -215,7 +215,8 @@ def _read_csv(path):
 def test_evaluate_end_to_end(tree, tmp_path):
     from PIL import Image
 
-    from crossscore_amd.data import InputStage, read_image_u8
+    from crossscore_amd.data import InputStage
+    from crossscore_amd.decode import read_image_u8
     from crossscore_amd.evaluate import batch_metrics
     from crossscore_amd.writers import ScoreMapEncoder
     from oracle import crossscore_oracle as orc

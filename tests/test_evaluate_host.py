@@ -83,7 +83,7 @@ def test_gt_stage_rejects_a_map_of_another_size():
 def test_read_metric_map_accepts_i16_and_i32(tmp_path, monkeypatch):
     from PIL import Image
 
-    from crossscore_amd.data import read_metric_map_u16
+    from crossscore_amd.decode import read_metric_map_u16
 
     m = (np.arange(12 * 7, dtype=np.uint32) * 781 % 65536).astype(np.uint16).reshape(12, 7)
     Image.fromarray(m).save(tmp_path / "a.png")

@@ -278,7 +278,7 @@ def test_generator_fills_a_bare_tree(trees):
 
     from crossscore_amd import _lib
     from crossscore_amd.config import load_config
-    from crossscore_amd.data import read_image_u8, read_metric_map_u16
+    from crossscore_amd.decode import read_image_u8, read_metric_map_u16
     from crossscore_amd.metric_maps import generate
 
     bare, filled, res = trees

@@ -33,7 +33,7 @@ def numpy_sums(ssim_u16, mae_u16):
 
 
 def sums_of_files(frames):
-    from crossscore_amd.data import read_metric_map_u16
+    from crossscore_amd.decode import read_metric_map_u16
 
     sums, sizes = [], []
     for fr in frames:

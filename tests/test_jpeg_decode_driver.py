@@ -1,5 +1,5 @@
 """this_main.jpeg_decoder through the drivers: predict and evaluate compute the same thing, bit for bit, whether the baseline JPEG inputs are decoded
-by PIL on the loader's threads (host) or on the device (gpu: data.PngDecoder(jpeg=True) behind the window of upcoming files) -- the same output
+by PIL on the loader's threads (host) or on the device (gpu: decode.ImageDecoder(jpeg=True) behind the window of upcoming files) -- the same output
 files byte for byte, the same CSV rows, the same ground-truth tensors."""
 import io
 import os

@@ -1,4 +1,4 @@
-"""The device JPEG decoder (csrc/jpegdec.hip, cs_op_jpeg_decode, data.PngDecoder(jpeg=True)): every decoded image equals, bit for bit, what
+"""The device JPEG decoder (csrc/jpegdec.hip, cs_op_jpeg_decode, decode.ImageDecoder(jpeg=True)): every decoded image equals, bit for bit, what
 read_image_u8 makes of PIL's array for the same bytes.  No tolerances.  Malformed files end with their documented status beside good files that
 still decode; pixels, status words and workspace sit inside guard bands."""
 import ctypes as C
@@ -21,7 +21,7 @@ from test_jpeg_host import SAMPLINGS, content, grid_files, jpeg_bytes, probe  # 
 
 
 def expected(data: bytes) -> np.ndarray:
-    from crossscore_amd.data import read_image_u8
+    from crossscore_amd.decode import read_image_u8
 
     return read_image_u8(io.BytesIO(data))
 
@@ -186,7 +186,7 @@ def test_malformed_files_beside_good_ones():
 def test_png_decoder_class_takes_jpeg_files(tmp_path):
     from PIL import Image
 
-    from crossscore_amd.data import PngDecoder, read_image_u8
+    from crossscore_amd.decode import ImageDecoder, read_image_u8
 
     paths = []
 
@@ -221,7 +221,7 @@ def test_png_decoder_class_takes_jpeg_files(tmp_path):
             assert np.array_equal(t.cpu().numpy(), want), p
         return sorted(os.path.basename(p) for p in handle.host_paths)
 
-    dec = PngDecoder("cuda", jpeg=True)
+    dec = ImageDecoder("cuda", jpeg=True)
     handle = dec.decode(paths)
     assert check(handle) == ["d_progressive.jpg"]
     assert dec.stats() == {"png_decoded_gpu": 2, "png_decoded_host": 0}
@@ -229,11 +229,11 @@ def test_png_decoder_class_takes_jpeg_files(tmp_path):
     b, c, e = (handle.tensors[k] for k in (1, 2, 4))  # the JPEG files of one size are slices of one tensor, in request order
     assert c.data_ptr() == b.data_ptr() + 20 * 30 * 3 and e.data_ptr() == c.data_ptr() + 20 * 30 * 3
     # the default-constructed decoder is what it was: every JPEG goes through PIL and counts as a host file
-    dec0 = PngDecoder("cuda")
+    dec0 = ImageDecoder("cuda")
     assert check(dec0.decode(paths)) == ["b_photo_20x30.jpg", "c_photo_20x30.JPG", "d_progressive.jpg", "e_named_png_is_jpeg.png", "f_gray_9x11.jpeg"]
     assert dec0.stats() == {"png_decoded_gpu": 2, "png_decoded_host": 5} and dec0.jpeg_stats() == {"jpeg_decoded_gpu": 0, "jpeg_decoded_host": 0}
     # png=False: the PNG files take the host path inside the decoder
-    dec1 = PngDecoder("cuda", png=False, jpeg=True)
+    dec1 = ImageDecoder("cuda", png=False, jpeg=True)
     assert check(dec1.decode(paths)) == ["a_rgb_20x30.png", "d_progressive.jpg", "g_rgb_9x11.png"]
     assert dec1.stats() == {"png_decoded_gpu": 0, "png_decoded_host": 2} and dec1.jpeg_stats() == {"jpeg_decoded_gpu": 4, "jpeg_decoded_host": 1}
     # a damaged scan raises, naming the path and the status; a JPEG asked for as a 16-bit map is the host reader's error, as before

@@ -215,7 +215,7 @@ def test_workspace_and_arguments_are_checked_on_the_host():
 
 
 def test_jpeg_decoder_key_is_validated():
-    from crossscore_amd.data import jpeg_decoder_choice, png_decoder_choice
+    from crossscore_amd.decode import jpeg_decoder_choice, png_decoder_choice
 
     for name in ("default_predict", "default_test"):
         assert jpeg_decoder_choice(load_config(name)) == "host"

@@ -1,5 +1,5 @@
 """The progressive JPEG decoder on the device (csrc/jpegprog.hip, cs_op_jpeg_decode_ex with CS_JPEG_PROGRESSIVE,
-data.PngDecoder(jpeg=True, progressive=True)): every decoded image equals, bit for bit, what read_image_u8 makes of PIL's array for the same
+decode.ImageDecoder(jpeg=True, progressive=True)): every decoded image equals, bit for bit, what read_image_u8 makes of PIL's array for the same
 bytes and what the baseline twin gives in the same call.  No tolerances.  Malformed files end with their documented status beside good files
 that still decode; pixels, status words and workspace sit inside guard bands."""
 import ctypes as C
@@ -26,7 +26,7 @@ P = _lib.JPEG_PROGRESSIVE
 
 
 def expected(data: bytes) -> np.ndarray:
-    from crossscore_amd.data import read_image_u8
+    from crossscore_amd.decode import read_image_u8
 
     return read_image_u8(io.BytesIO(data))
 
@@ -223,7 +223,7 @@ def test_malformed_files_beside_good_ones():
 def test_decoder_class_takes_progressive_files(tmp_path):
     from PIL import Image
 
-    from crossscore_amd.data import PngDecoder, read_image_u8
+    from crossscore_amd.decode import ImageDecoder, read_image_u8
 
     paths = []
 
@@ -255,7 +255,7 @@ def test_decoder_class_takes_progressive_files(tmp_path):
             assert np.array_equal(t.cpu().numpy(), want), p
         return sorted(os.path.basename(p) for p in handle.host_paths)
 
-    dec = PngDecoder("cuda", jpeg=True, progressive=True)
+    dec = ImageDecoder("cuda", jpeg=True, progressive=True)
     assert check(dec.decode(paths)) == []
     assert dec.stats() == {"png_decoded_gpu": 2, "png_decoded_host": 0}
     assert dec.jpeg_stats() == {"jpeg_decoded_gpu": 5, "jpeg_decoded_host": 0}
@@ -267,8 +267,8 @@ def test_decoder_class_takes_progressive_files(tmp_path):
     assert check(dec.decode(paths)) == ["h_incomplete.jpg"]
     assert dec.progressive_stats() == {"jpeg_progressive_gpu": 2, "jpeg_progressive_host": 1}
     paths.pop()
-    old = PngDecoder("cuda", jpeg=True)  # as before
+    old = ImageDecoder("cuda", jpeg=True)  # as before
     assert check(old.decode(paths)) == ["d_progressive.jpg"]
     assert old.jpeg_stats() == {"jpeg_decoded_gpu": 4, "jpeg_decoded_host": 1} and old.progressive_stats() == {"jpeg_progressive_gpu": 0, "jpeg_progressive_host": 0}
     with pytest.raises(ValueError, match="jpeg=True"):
-        PngDecoder("cuda", progressive=True)
+        ImageDecoder("cuda", progressive=True)

@@ -212,7 +212,7 @@ def test_recoder_scripts_satisfy_the_pil_condition(name):
 
 
 def test_jpeg_progressive_key_is_validated():
-    from crossscore_amd.data import jpeg_progressive_choice
+    from crossscore_amd.decode import jpeg_progressive_choice
 
     for name in ("default_predict", "default_test"):
         assert jpeg_progressive_choice(load_config(name)) == "host"

@@ -1,5 +1,5 @@
 """this_main.png_decoder through the drivers: predict and evaluate compute the same thing, bit for bit, whether the PNG inputs are decoded by PIL
-on the loader's threads (host) or on the device (gpu: data.PngDecoder behind a window of upcoming files) -- the same files byte for byte, the same
+on the loader's threads (host) or on the device (gpu: decode.ImageDecoder behind a window of upcoming files) -- the same files byte for byte, the same
 CSV rows, the same ground-truth tensors."""
 import os
 import sys

@@ -1,4 +1,4 @@
-"""The device PNG decoder (csrc/pngdec.hip, cs_png_probe / cs_op_png_decode, data.PngDecoder): every decoded image equals, bit for bit, what
+"""The device PNG decoder (csrc/pngdec.hip, cs_png_probe / cs_op_png_decode, decode.ImageDecoder): every decoded image equals, bit for bit, what
 read_image_u8 / read_metric_map_u16 make of PIL's array for the same bytes; hand-made streams are checked against zlib.decompress plus the
 un-filter of tests/test_png_encoder.py.  No tolerances.  Malformed files end with their documented status beside good files that still decode."""
 import ctypes as C
@@ -114,7 +114,7 @@ def pil_png(img, **kw) -> bytes:
 
 def expected(data: bytes, kind: int) -> np.ndarray:
     """the host readers' array for a file's bytes (they take anything PIL opens)"""
-    from crossscore_amd.data import read_image_u8, read_metric_map_u16
+    from crossscore_amd.decode import read_image_u8, read_metric_map_u16
 
     return (read_metric_map_u16 if kind == GRAY16 else read_image_u8)(io.BytesIO(data))
 
@@ -326,7 +326,7 @@ def test_png_decode_rejects_bad_arguments_on_the_host():
 
 
 def test_png_decoder_keys_are_validated():
-    from crossscore_amd.data import png_decode_window_choice, png_decoder_choice
+    from crossscore_amd.decode import png_decode_window_choice, png_decoder_choice
 
     for name in ("default_predict", "default_test"):
         assert png_decoder_choice(load_config(name)) == "host"
@@ -669,12 +669,12 @@ def test_malformed_files_beside_good_ones():
     assert d3.st.tolist() == [0, 0] and all(np.array_equal(im, img) for im in d3.images)
 
 
-# ------------------------------------------------------------------------------------------------------- data.PngDecoder
+# ------------------------------------------------------------------------------------------------------- decode.ImageDecoder
 @pytest.mark.gpu
 def test_png_decoder_class_groups_falls_back_and_raises(tmp_path):
     from PIL import Image
 
-    from crossscore_amd.data import PngDecoder, read_image_u8, read_metric_map_u16
+    from crossscore_amd.decode import ImageDecoder, read_image_u8, read_metric_map_u16
 
     rng = np.random.default_rng(90)
     paths, kinds = [], []
@@ -698,7 +698,7 @@ def test_png_decoder_class_groups_falls_back_and_raises(tmp_path):
     put("g_photo.jpg", buf.getvalue())
     put("h_interlaced.png", _interlaced_png(image_of(rng, 6, 5, "rgb")))
     put("i_rgb_20x30.png", pil_png(image_of(rng, 20, 30, "rgb"), optimize=True))
-    dec = PngDecoder("cuda")
+    dec = ImageDecoder("cuda")
     handle = dec.decode(paths, kinds)
     handle.wait()
     handle.check()
@@ -737,9 +737,41 @@ def _interlaced_png(img: np.ndarray) -> bytes:
 
 
 @pytest.mark.gpu
+def test_a_request_without_any_device_group(tmp_path):
+    """No path at all, and a request whose every file goes to PIL: the group loop runs zero times and the handle is complete all the same."""
+    from PIL import Image
+
+    from crossscore_amd.decode import ImageDecoder, read_image_u8
+
+    dec = ImageDecoder("cuda")
+    handle = dec.decode([])
+    assert handle.tensors == [] and handle.paths == [] and handle.host_paths == []
+    handle.wait()
+    handle.check()
+    rng = np.random.default_rng(93)
+    buf = io.BytesIO()
+    Image.fromarray(image_of(rng, 8, 8, "rgb")).save(buf, format="JPEG")
+    paths = [str(tmp_path / "interlaced_5x7.png"), str(tmp_path / "photo_8x8.jpg")]
+    for p, data in zip(paths, (_interlaced_png(image_of(rng, 5, 7, "rgb")), buf.getvalue())):
+        with open(p, "wb") as f:
+            f.write(data)
+    handle = dec.decode(paths)
+    handle.wait()
+    handle.check()
+    assert handle.host_paths == paths
+    assert dec.stats() == {"png_decoded_gpu": 0, "png_decoded_host": 2}
+    assert dec.jpeg_stats() == {"jpeg_decoded_gpu": 0, "jpeg_decoded_host": 0}
+    assert dec.progressive_stats() == {"jpeg_progressive_gpu": 0, "jpeg_progressive_host": 0}
+    for p, t in zip(paths, handle.tensors):
+        want = read_image_u8(p)
+        assert t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == want.shape, p
+        assert np.array_equal(t.cpu().numpy(), want), p
+
+
+@pytest.mark.gpu
 def test_png_decoder_does_not_wait_for_the_stream(tmp_path):
     """decode() returns while its stream is still busy with work queued before it (pinned, non-blocking uploads; status words behind the event)."""
-    from crossscore_amd.data import PngDecoder, read_image_u8
+    from crossscore_amd.decode import ImageDecoder, read_image_u8
 
     if not hasattr(torch.cuda, "_sleep"):
         pytest.skip("torch.cuda._sleep is not available")
@@ -749,7 +781,7 @@ def test_png_decoder_does_not_wait_for_the_stream(tmp_path):
         p = str(tmp_path / f"q{k}.png")
         open(p, "wb").write(pil_png(image_of(rng, 20, 30, "rgb")))
         paths.append(p)
-    dec = PngDecoder("cuda")
+    dec = ImageDecoder("cuda")
     dec.decode(paths).check()  # kernels, pinned blocks and allocator pools exist from here on
     torch.cuda.synchronize()
     with torch.cuda.stream(dec.stream):

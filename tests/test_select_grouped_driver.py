@@ -128,7 +128,8 @@ def test_every_query_chooses_inside_its_own_candidate_list(scene):
 
 
 def test_the_scores_are_forward_cached_on_the_chosen_files(scene):
-    from crossscore_amd.data import InputStage, read_image_u8
+    from crossscore_amd.data import InputStage
+    from crossscore_amd.decode import read_image_u8
     from crossscore_amd.model import CrossScoreNet
 
     tree, _, sd, base, cap = scene

@@ -13,7 +13,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.ins
 from PIL import Image
 from crossscore_amd import _lib, synth
 from crossscore_amd.config import load_config, model_config
-from crossscore_amd.data import InputStage, read_metric_map_u16
+from crossscore_amd.data import InputStage
+from crossscore_amd.decode import read_metric_map_u16
 from crossscore_amd.evaluate import evaluate
 from crossscore_amd.metric_maps import generate
 from crossscore_amd.model import CrossScoreNet

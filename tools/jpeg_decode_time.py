@@ -3,7 +3,7 @@
 Two sets of 540x720 photo-like images (smooth + sigma 8 noise) written by PIL at quality 90, 4:2:0: without restart markers (one wave decodes a
 file) and with one MCU row per restart interval (the four waves of a file's workgroup share its intervals).  Per set one JSON line: ms per call,
 microseconds per image and compressed bytes per second for the whole window and for I = 8 (what the window buys), PIL's ms per image on one
-thread and images/s on an 8-thread pool, and the host's own cost per file (read + probe + pinned copy + launch) through data.PngDecoder.
+thread and images/s on an 8-thread pool, and the host's own cost per file (read + probe + pinned copy + launch) through decode.ImageDecoder.
 usage: python tools/jpeg_decode_time.py [--window 64] [--reps 5]"""
 import argparse, ctypes as C, io, json, os, sys, tempfile, time
 from concurrent.futures import ThreadPoolExecutor
@@ -11,7 +11,7 @@ import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
 from PIL import Image
 from crossscore_amd import _lib
-from crossscore_amd.data import PngDecoder, probe_jpeg, read_image_u8
+from crossscore_amd.decode import ImageDecoder, probe_jpeg, read_image_u8
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--window", type=int, default=64)
@@ -61,7 +61,7 @@ for name, files in sets:
     for i, f in enumerate(files):
         paths.append(os.path.join(tmp, f"{name}_{i}.jpg")); open(paths[-1], "wb").write(f)
     with ThreadPoolExecutor(8) as pool:
-        dec = PngDecoder("cuda", pool, jpeg=True)
+        dec = ImageDecoder("cuda", pool, jpeg=True)
         dec.decode(paths).check()
         torch.cuda.synchronize(); t = time.perf_counter(); hd = dec.decode(paths); host_ms = (time.perf_counter() - t) * 1e3; hd.check()
         assert not hd.host_paths and dec.jpeg_stats()["jpeg_decoded_gpu"] == 2 * len(files)

@@ -14,7 +14,7 @@ import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
 from PIL import Image
 from crossscore_amd import _lib
-from crossscore_amd.data import probe_jpeg, read_image_u8
+from crossscore_amd.decode import probe_jpeg, read_image_u8
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--window", type=int, default=64)

@@ -3,7 +3,7 @@
 Three sets: 540x720 RGB photos (smooth + sigma 8 noise) written by PIL, the same images written by the device encoder (cs_op_png_encode: fixed
 Huffman / stored blocks, one IDAT chunk per 16 KiB), and 518x518 gray16 maps.  Per set one JSON line: ms per call, microseconds per image and
 literals + match bytes per second for the whole window and for I = 8 (what the window buys), PIL's ms per image on one thread and images/s on an
-8-thread pool, and the host's own cost per file (read + probe + pinned copy) through data.PngDecoder.
+8-thread pool, and the host's own cost per file (read + probe + pinned copy) through decode.ImageDecoder.
 usage: python tools/png_decode_time.py [--window 64] [--maps 8] [--reps 5]"""
 import argparse, ctypes as C, io, json, os, sys, tempfile, time
 from concurrent.futures import ThreadPoolExecutor
@@ -11,7 +11,7 @@ import numpy as np, torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, REPO)
 from PIL import Image
 from crossscore_amd import _lib
-from crossscore_amd.data import PngDecoder, probe_png, read_image_u8, read_metric_map_u16
+from crossscore_amd.decode import ImageDecoder, probe_png, read_image_u8, read_metric_map_u16
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--window", type=int, default=64)
@@ -81,7 +81,7 @@ for name, files, kind, h, w in sets:
     for i, f in enumerate(files):
         paths.append(os.path.join(tmp, f"{name}_{i}.png")); open(paths[-1], "wb").write(f)
     with ThreadPoolExecutor(8) as pool:
-        dec = PngDecoder("cuda", pool)
+        dec = ImageDecoder("cuda", pool)
         dec.decode(paths, kind == _lib.PNG_GRAY16).check()
         torch.cuda.synchronize(); t = time.perf_counter(); hd = dec.decode(paths, kind == _lib.PNG_GRAY16); host_ms = (time.perf_counter() - t) * 1e3; hd.check()
     line = {"set": name, "files": len(files), "mean_file_bytes": int(np.mean([len(f) for f in files])), "pil_ms_per_image_one_thread": round(pil_ms, 2),
