@@ -110,6 +110,8 @@ SYMBOLS = {
     "cs_op_head_score": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "cs_op_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "cs_op_attention_weights": (_i, [_vp, _vp, _i, _i, _ll, _ll, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp]),
+    "cs_op_reference_use": (_i, [_vp, _vp, _i, _i, _ll, _ll, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cs_request_reference_use": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "cs_op_layernorm": (_i, [_vp, _i, _i, _vp, _vp, _f, _vp, _vp, _vp]),
     "cs_op_ln_finalize": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp]),
     "cs_op_silu_mul": (_i, [_vp, _i, _i, _i, _vp]),

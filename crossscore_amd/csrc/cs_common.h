@@ -204,6 +204,19 @@ struct CsAttnParams {
   int bf16;                                            // operand type of Q, K, V, P and O: 0 IEEE half, 1 bfloat16
 };
 
+// Reference use (refuse.hip): Q / K / lse as the last decoder layer's cross-attention saw and wrote them; keys are N segments
+// of Np rows.  Outputs (any may be null): share, peak_prob, peak_index (batch, N, Lq), entropy (batch, Lq).
+struct CsRefUseParams {
+  const h16_t* Q; const h16_t* K;
+  int ldq, ldk;                                        // row strides (elements)
+  long long q_bs, k_bs;                                // batch strides (elements)
+  int Lq, N, Np, heads, nbatch;
+  float scale_log2e;                                   // as CsAttnParams::scale_log2e
+  const float* lse;                                    // [batch][heads][Lq], base 2, from cs_attn_kernel
+  float* share; float* peak_prob; int32_t* peak_index; float* entropy;
+  int bf16;                                            // operand type of Q and K
+};
+
 // One-pass input stage (SURVEY.md 8f-4 as worded: uint8 in, tokens out).  Filter tables of one resize geometry (preprocess.hip) and the per-image
 // descriptor the patch kernel reads (patch.hip); images of one launch may differ in source size and geometry, not in the H x W window they produce.
 struct CsU8Tables {
@@ -282,6 +295,9 @@ extern int g_gemm_grid;  // cs_debug_gemm_grid: > 0 replaces the CU-derived bloc
 // attention.hip
 const char* cs_attn_check(const CsAttnParams* p, int dh, int batch);
 hipError_t cs_attn_launch(const CsAttnParams* p, int dh, int batch, hipStream_t stream);
+// refuse.hip
+const char* cs_refuse_check(const CsRefUseParams* p, int dh);
+hipError_t cs_refuse_launch(const CsRefUseParams* p, int dh, hipStream_t stream);
 // elementwise.hip
 hipError_t cs_im2col_launch(const float* q, const float* refs, int N, int img0, h16_t* out, int I, int H, int W, int P, int Kp,
                             float* pmean, int bf, hipStream_t st);

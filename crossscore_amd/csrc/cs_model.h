@@ -117,6 +117,12 @@ struct cs_model {
   hipStream_t last_stream = nullptr; hipEvent_t ev_done = nullptr;  // ordering of calls that arrive on different streams
   hipEvent_t ev_kv0 = nullptr, ev_kv1 = nullptr;                    // decoder: K/V projection on a side stream
   hipEvent_t ev_fork = nullptr, ev_join[CS_MAX_LANES] = {}, ev_stag[CS_MAX_LANES] = {};
+  // cs_request_reference_use: armed for the next cs_forward* call on this handle, which takes it and clears it whether it succeeds or fails
+  struct RefUse {
+    float* share = nullptr; float* peak_prob = nullptr; int32_t* peak_index = nullptr; float* entropy = nullptr;
+    bool any() const { return share || peak_prob || peak_index || entropy; }
+  };
+  RefUse ref_use;
   unsigned* nonfinite = nullptr;  // device counter: non-finite score-map values seen since the last cs_nonfinite_count
   // profiling
   bool prof = false;

@@ -265,6 +265,7 @@ struct Fwd {
   int bf = 0;        // 16-bit operand type of every activation buffer and packed weight: 0 IEEE half, 1 bfloat16
   int N_enc = 0;     // reference views that go through the encoder with their query
   int S_sel = 0;     // (grouped selection) rows of the longest group
+  cs_model::RefUse use{};  // cs_request_reference_use, taken off the handle by forward_impl
   Plan p{};          // (workspace)
   int u8_span = 0;   // (uint8 descriptors) source rows one patch row reaches, at most
   int NL = 1;        // (lanes) lanes of this call, and their streams: the caller's when there is one lane
@@ -711,6 +712,17 @@ struct Fwd {
     return false;
   }
 
+  // Behind the last layer's cross-attention, on its stream: the four reference-use outputs from its Q, K and lse (refuse.hip)
+  void reference_use(Launcher& L, const CsAttnParams& a, int dh) {
+    CsRefUseParams r{};
+    r.Q = a.Q; r.K = a.K; r.ldq = a.ldq; r.ldk = a.ldk; r.q_bs = a.q_bs; r.k_bs = a.k_bs; r.Lq = a.Lq; r.N = N; r.Np = p.Np; r.heads = a.heads; r.nbatch = B;
+    r.scale_log2e = a.scale_log2e; r.lse = a.lse; r.bf16 = bf;
+    r.share = use.share; r.peak_prob = use.peak_prob; r.peak_index = use.peak_index; r.entropy = use.entropy;
+    if (L.rc) return;
+    if (const char* e = cs_refuse_check(&r, dh)) { L.rc = fail(CS_ERR_BAD_ARG, "%s", e); return; }
+    L.small("ref_use", [&] { return cs_refuse_launch(&r, dh, L.st); });
+  }
+
   // The decoder runs as ONE group on the caller's stream, after the join: its kernels are small, and splitting the batch over streams only
   // makes them smaller (cfg-2, tools/dec_lanes.py: 1 group 8.77 ms, 2 groups 8.80, 3 groups 8.79, 4 groups 9.31).  Decoding each chunk's
   // items on its lane right after encoding them (no global join) was measured SLOWER too (833 vs 875 query-images/s on cfg-2): it doubles the
@@ -754,9 +766,11 @@ struct Fwd {
       if (kv_side && l == 0 && !L.rc && hipStreamWaitEvent(s, h->ev_kv1, 0) != hipSuccess) L.rc = CS_ERR_HIP;
       if (!have_q) L.gemm(gp(p.q_bf, C, D.ca_Wq, C, M, C, C, D.ca_bq, p.dq, C), CS_EPI_BIAS_F16);
       const bool want_w = attn_out && last_l;  // only the last layer's weights are returned (transformer.py:266-268)
-      const CsAttnParams a = attn_params(p.dq, C, p.kv + (size_t)l * 2 * C, p.kv + (size_t)l * 2 * C + C, KV, p.dob, p.Np, N * p.Np, c.dec_heads, want_w ? p.lse : nullptr);
+      const bool want_use = last_l && use.any();  // reference use: the same layer, the same lse
+      const CsAttnParams a = attn_params(p.dq, C, p.kv + (size_t)l * 2 * C, p.kv + (size_t)l * 2 * C + C, KV, p.dob, p.Np, N * p.Np, c.dec_heads, want_w || want_use ? p.lse : nullptr);
       L.attn(a, dec_dh, B);
       if (want_w) L.small("attn_weights", [&] { return cs_attn_weights_launch(&a, dec_dh, B, head_id, attn_out, s); });
+      if (want_use) reference_use(L, a, dec_dh);
       if (!dec_close(L, p.dob, D.ca_Wo, D.ca_bo, shortcut, D.n2g, D.n2b, "norm2", next_of(D.l1W, D.l1b, p.dhid, 1)))
         L.gemm(gp(p.q_bf, C, D.l1W, C, M, C, C, D.l1b, p.dhid, C), CS_EPI_BIAS_RELU_F16);
       // behind norm3: the head's first linear (its hidden rows replace linear1's in dhid: a workgroup writes exactly the 64 rows it staged into
@@ -826,6 +840,7 @@ int forward_impl(Fwd f) {
   // one to finish (calls on one stream are ordered anyway).
   cs_model* h = f.h;
   if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
+  if (f.mode != 2) { f.use = h->ref_use; h->ref_use = cs_model::RefUse{}; }  // one-shot: gone whatever this call returns
   if (h->ev_done && h->last_stream != f.st) HIPCHK(hipStreamWaitEvent(f.st, h->ev_done, 0));
   h->census.clear();
   const auto t0 = std::chrono::steady_clock::now();
@@ -859,6 +874,12 @@ size_t cs_workspace_bytes(cs_handle h, int B, int N, int H, int W) {
 int cs_forward(cs_handle h, const float* query, const float* refs, int B, int N, int H, int W, float* score_out, float* attn_out,
                int head_id, float* mean_out, cs_stream stream) {
   return forward_impl(Fwd{h, 0, query, refs, nullptr, nullptr, B, N, H, W, score_out, attn_out, head_id, mean_out, (hipStream_t)stream, nullptr});
+}
+
+int cs_request_reference_use(cs_handle h, float* share, float* peak_prob, int32_t* peak_index, float* entropy) {
+  if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
+  h->ref_use = cs_model::RefUse{share, peak_prob, peak_index, entropy};
+  return 0;
 }
 
 int cs_encode_references(cs_handle h, const float* imgs, int R, int H, int W, uint16_t* tokens_out, cs_stream stream) {

@@ -93,6 +93,22 @@ int cs_op_attention_weights(const uint16_t* Q, const uint16_t* K, int ldq, int l
   return 0;
 }
 
+int cs_op_reference_use(const uint16_t* Q, const uint16_t* K, int ldq, int ldk, long long q_bs, long long k_bs, int batch, int heads, int Lq, int N,
+                        int Np, int dh, float q_scale, const float* lse, float* share, float* peak_prob, int32_t* peak_index, float* entropy,
+                        cs_stream stream) {
+  if (!supported_dh(dh)) return fail(CS_ERR_UNSUPPORTED, "reference_use: head dim %d is none of 16, 48, 64, 96, 128, 192", dh);
+  if (!(q_scale >= 0.f)) return fail(CS_ERR_BAD_ARG, "reference_use: q_scale must be >= 0 (0 = log2(e)/sqrt(dh))");
+  CsRefUseParams a{};
+  a.Q = Q; a.K = K; a.ldq = ldq; a.ldk = ldk; a.q_bs = q_bs; a.k_bs = k_bs; a.Lq = Lq; a.N = N; a.Np = Np; a.heads = heads; a.nbatch = batch;
+  a.scale_log2e = q_scale == 0.f ? LOG2E / std::sqrt((float)dh) : q_scale; a.lse = lse;
+  a.share = share; a.peak_prob = peak_prob; a.peak_index = peak_index; a.entropy = entropy;
+  a.bf16 = g_op_bf16;
+  if (const char* e = cs_refuse_check(&a, dh)) return fail(CS_ERR_BAD_ARG, "%s", e);
+  if (!share && !peak_prob && !peak_index && !entropy) return 0;  // nothing asked for
+  HIPCHK(cs_refuse_launch(&a, dh, (hipStream_t)stream));
+  return 0;
+}
+
 int cs_op_layernorm(const float* x, int M, int C, const float* gamma, const float* beta, float eps, float* out_f32,
                     uint16_t* out_f16, cs_stream stream) {
   if (!x || !gamma || !beta || M <= 0 || C <= 0 || C % 4 || C > 2048) return fail(CS_ERR_BAD_ARG, "layernorm: C must be a multiple of 4 and <= 2048");

@@ -335,23 +335,42 @@ class CrossScoreNet(torch.nn.Module):
             results["score_mean_ref_cross"] = mean_out  # key does not start with "score_map": writers ignore it
         return results
 
-    def _score(self, call, B, N, H, W, dev, need_attn_weights, head_id, return_mean):
+    def _score(self, call, B, N, H, W, dev, need_attn_weights, head_id, return_mean, need_reference_use=False):
         """The plumbing every forward call shares: the outputs, the sub-batches (_sub_batches) and the result dict.  call(b0, b1, tail) makes
-        the C call for the items b0 .. b1 - 1 and returns its code; tail = (score, attn | None, head id, mean | None, stream) of those items."""
+        the C call for the items b0 .. b1 - 1 and returns its code; tail = (score, attn | None, head id, mean | None, stream) of those items.
+        need_reference_use arms cs_request_reference_use in front of every sub-batch's call, with that sub-batch's rows of the four outputs."""
         P = self.arch.patch
         with torch.cuda.device(dev):
             score, attn, mean_out = self._alloc_outputs(B, N, H, W, dev, need_attn_weights, return_mean)
+            use = self._alloc_reference_use(B, N, H, W, dev) if need_reference_use else None
             stream = torch.cuda.current_stream(dev).cuda_stream
             for b0, b1 in self._sub_batches(B, N, (H // P) * (W // P)):
+                if use is not None:
+                    _lib.check(_lib.load().cs_request_reference_use(self._handle, *(C.c_void_p(t[b0:b1].data_ptr()) for t in use.values())))
                 _lib.check(call(b0, b1, (C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
                                          int(head_id), C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None,
                                          C.c_void_p(stream))))
-        return self._results(score, attn, mean_out)
+        results = self._results(score, attn, mean_out)
+        if use is not None:
+            results.update(use)
+        return results
+
+    def _alloc_reference_use(self, B, N, H, W, dev):
+        """The four outputs of need_reference_use under their result keys, in cs_request_reference_use's argument order.
+        None of the keys starts with "score_map": the writers iterate over that prefix."""
+        h, w = H // self.arch.patch, W // self.arch.patch
+        return {"ref_use_share": torch.empty((B, N, h, w), dtype=torch.float32, device=dev),
+                "ref_use_peak_prob": torch.empty((B, N, h, w), dtype=torch.float32, device=dev),
+                "ref_use_peak_index": torch.empty((B, N, h, w), dtype=torch.int32, device=dev),
+                "ref_use_entropy": torch.empty((B, h, w), dtype=torch.float32, device=dev)}
 
     @torch.no_grad()
     def forward(self, query_img, ref_cross_imgs, need_attn_weights=False, need_attn_weights_head_id=0, norm_img=False,
-                return_mean=False):
+                return_mean=False, need_reference_use=False):
         """
+        :param need_reference_use: also return ref_use_share / ref_use_peak_prob / ref_use_peak_index (B, N, h, w) and ref_use_entropy (B, h, w):
+                                which reference each query patch's last-layer cross-attention went to, where it looked, how spread it was
+                                (mean over the heads).  Every forward* method takes it; the other outputs keep their bits.
         :param query_img:       (B, 3, H, W) fp32, ImageNet-normalised
         :param ref_cross_imgs:  (B, N_ref_cross, 3, H, W)
         :param norm_img:        reference flag (task/core.py:76-81), bug-for-bug: the std used is the mean.
@@ -387,7 +406,7 @@ class CrossScoreNet(torch.nn.Module):
         handle = self._ensure_handle(dev)
         return self._score(lambda b0, b1, tail: lib.cs_forward(handle, C.c_void_p(q[b0:b1].data_ptr()), C.c_void_p(r[b0:b1].data_ptr()),
                                                                b1 - b0, N, H, W, *tail),
-                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean)
+                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean, need_reference_use)
 
     def _sub_batches(self, B: int, N: int, Np: int):
         """Items are independent, so a batch whose decoder buffers would overflow the kernels' 32-bit element offsets
@@ -417,7 +436,8 @@ class CrossScoreNet(torch.nn.Module):
         return tok
 
     @torch.no_grad()
-    def forward_cached(self, query_img, ref_tokens, need_attn_weights=False, need_attn_weights_head_id=0, return_mean=False):
+    def forward_cached(self, query_img, ref_tokens, need_attn_weights=False, need_attn_weights_head_id=0, return_mean=False,
+                       need_reference_use=False):
         """forward() with the reference views given as cached tokens (B, N, h*w, C) fp16 from encode_references."""
         if query_img.dim() != 4 or ref_tokens.dim() != 4 or ref_tokens.shape[0] != query_img.shape[0]:
             raise ValueError("expected query_img (B,3,H,W) and ref_tokens (B,N,h*w,C)")
@@ -439,7 +459,7 @@ class CrossScoreNet(torch.nn.Module):
         lib = _lib.load()
         return self._score(lambda b0, b1, tail: lib.cs_forward_cached(handle, C.c_void_p(q[b0:b1].data_ptr()), C.c_void_p(t[b0:b1].data_ptr()),
                                                                       b1 - b0, N, H, W, *tail),
-                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean)
+                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean, need_reference_use)
 
     # -- the same three calls fed from decoded uint8 images (SURVEY.md 8f-4 as worded: uint8 in, tokens out) --------------------------------
     def u8_input_supported(self, img: U8Image, size, device=None) -> bool:
@@ -451,7 +471,8 @@ class CrossScoreNet(torch.nn.Module):
         return bool(_lib.load().cs_u8_input_supported(self._ensure_handle(dev), C.byref(st), int(size[0]), int(size[1])))
 
     @torch.no_grad()
-    def forward_u8(self, query: U8Batch, refs: U8Batch, need_attn_weights=False, need_attn_weights_head_id=0, return_mean=False):
+    def forward_u8(self, query: U8Batch, refs: U8Batch, need_attn_weights=False, need_attn_weights_head_id=0, return_mean=False,
+                   need_reference_use=False):
         """forward() from decoded uint8 images: query = B images, refs = B * N images (item-major).  The resize / crop / normalise of the input
         stage happens inside the patch-embedding launch; results are bit-identical to InputStage + forward()."""
         B = len(query)
@@ -467,7 +488,7 @@ class CrossScoreNet(torch.nn.Module):
         handle = self._ensure_handle(dev)
         return self._score(lambda b0, b1, tail: lib.cs_forward_u8(handle, query.c_array(b0, b1), refs.c_array(b0 * N, b1 * N),
                                                                   b1 - b0, N, H, W, query.mean, query.std, *tail),
-                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean)
+                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean, need_reference_use)
 
     @torch.no_grad()
     def encode_references_u8(self, imgs: U8Batch):
@@ -487,7 +508,8 @@ class CrossScoreNet(torch.nn.Module):
         return tok
 
     @torch.no_grad()
-    def forward_cached_u8(self, query: U8Batch, ref_tokens, need_attn_weights=False, need_attn_weights_head_id=0, return_mean=False):
+    def forward_cached_u8(self, query: U8Batch, ref_tokens, need_attn_weights=False, need_attn_weights_head_id=0, return_mean=False,
+                          need_reference_use=False):
         """forward_cached() with the query images as decoded uint8."""
         B = len(query)
         H, W = query.size
@@ -504,7 +526,7 @@ class CrossScoreNet(torch.nn.Module):
         handle = self._ensure_handle(dev)
         return self._score(lambda b0, b1, tail: lib.cs_forward_cached_u8(handle, query.c_array(b0, b1), C.c_void_p(t[b0:b1].data_ptr()),
                                                                          b1 - b0, N, H, W, query.mean, query.std, *tail),
-                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean)
+                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean, need_reference_use)
 
     # -- reference selection by similarity: the choice of each query's views is made on the device ----------------------
     @torch.no_grad()
@@ -537,7 +559,8 @@ class CrossScoreNet(torch.nn.Module):
                 _lib.check(lib.cs_op_descriptor_unit(C.c_void_p(mean.data_ptr()), R, Cc, C.c_void_p(centre.data_ptr()), C.c_void_p(unit.data_ptr()), st))
         return mean, centre, unit
 
-    def _forward_select(self, query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, u8, group=None):
+    def _forward_select(self, query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, u8, group=None,
+                        need_reference_use=False):
         N = int(bank.n_references if n_references is None else n_references)
         t = bank.tokens
         dev = t.device
@@ -594,7 +617,7 @@ class CrossScoreNet(torch.nn.Module):
                           C.c_void_p(ex[b0:b1].data_ptr()) if ex is not None else None, b1 - b0, N, H, W, *((query.mean, query.std) if u8 else ()),
                           *tail[:4], C.c_void_p(index[b0:b1].data_ptr()), C.c_void_p(sim[b0:b1].data_ptr()), tail[4])
 
-            results = self._score(call, B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean)
+            results = self._score(call, B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean, need_reference_use)
             results["reference_index"] = index
             # the similarities of the chosen entries, in the order chosen (an index of -1, a query that ran out of candidates, reads entry 0)
             if grouped:  # a column of sim is a place in the query's group; a padded place (-1) is NaN
@@ -606,20 +629,20 @@ class CrossScoreNet(torch.nn.Module):
 
     @torch.no_grad()
     def forward_select(self, query_img, bank: "SelectionBank", exclude=None, need_attn_weights=False, need_attn_weights_head_id=0,
-                       return_mean=False, n_references=None, group=None):
+                       return_mean=False, n_references=None, group=None, need_reference_use=False):
         """forward_cached() with each query's N = bank.n_references views chosen on the device: the bank entries most similar to the query's own
         pooled descriptor, descending, ties to the lower index, exclude[b] (int32 (B), -1 = none) left out.  The result also holds
         "reference_index" (B, N) int32 and "reference_similarity" (B, N) fp32; the score map, mean and attention weights are bit-identical to
         forward_cached(query_img, bank.tokens[reference_index]).  A grouped bank needs `group`, one group id per query (host integers): the
         query chooses among that group's rows only, a group shorter than N leaves -1 in reference_index and NaN in reference_similarity, and
         those places are fed bank.blank_row's tokens (zeros when it is -1)."""
-        return self._forward_select(query_img, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, False, group)
+        return self._forward_select(query_img, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, False, group, need_reference_use)
 
     @torch.no_grad()
     def forward_select_u8(self, query: U8Batch, bank: "SelectionBank", exclude=None, need_attn_weights=False, need_attn_weights_head_id=0,
-                          return_mean=False, n_references=None, group=None):
+                          return_mean=False, n_references=None, group=None, need_reference_use=False):
         """forward_select() with the query images as decoded uint8."""
-        return self._forward_select(query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, True, group)
+        return self._forward_select(query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, True, group, need_reference_use)
 
     def calibrate_lanes(self, query_img, ref_cross_imgs, tries: int = 3, steps: int = 4, min_gain: float = 0.08) -> Dict[str, Any]:
         """Checks that this module's multi-lane forward really overlaps its lanes, and repairs it if not.  The lanes' streams are probed

@@ -47,7 +47,7 @@ def resolve_out_dir(cfg, now: Optional[str] = None) -> str:
 
 def predict(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None) -> Dict[str, object]:
     """Runs the predict loop; returns {"out_dir", "files", "rows", "input_stage", "png_encoder", "png_compression", "png_files", "png_decoder", "png_decoded",
-    "jpeg_decoder", "jpeg_decoded", "jpeg_progressive", "jpeg_progressive_decoded", "query_images_per_sec"}."""
+    "jpeg_decoder", "jpeg_decoded", "jpeg_progressive", "jpeg_progressive_decoded", "reference_strategy", "reference_use", "query_images_per_sec"}."""
     opts = scoring.options(cfg, "predict")
     scoring.start(cfg, opts)
     device = opts.device

@@ -92,6 +92,16 @@ def options(cfg, phase: str) -> SimpleNamespace:
             raise ValueError("data.neighbour_config.strategy=similar needs data.neighbour_config.cross >= 1")
     elif o.strategy not in STRATEGIES:
         raise NotImplementedError(f"neighbour strategy {o.strategy} (sampler.py:60-66 knows 'random'; this build adds 'similar')")
+    # this_main.reference_use (default off): every batch is scored with need_reference_use and the run writes
+    # reference_use.csv -- per query the references it was scored against, the share of its patches' last-layer cross-attention each one took,
+    # the mean peak probability inside it, and how focused the attention was.  this_main.reference_use_images (default off) also writes the
+    # share maps and the focus map of every query as PNG files under batch/reference_use; it needs reference_use and the batch writer.
+    o.reference_use = bool(cfg.this_main.get("reference_use", False))
+    o.reference_use_images = bool(cfg.this_main.get("reference_use_images", False))
+    if o.reference_use and int(cfg.data.neighbour_config.cross) < 1:
+        raise ValueError("this_main.reference_use=True needs data.neighbour_config.cross >= 1: without reference views there is nothing to report")
+    if o.reference_use_images and not (o.reference_use and bool(cfg.logger[phase].write.flag.batch)):
+        raise ValueError(f"this_main.reference_use_images=True needs this_main.reference_use=True and logger.{phase}.write.flag.batch=True")
     return o
 
 
@@ -123,6 +133,41 @@ def write_reference_selection(out_dir: str, selection, path_parts: int = 1) -> s
         w.writerow(["query"] + [f"reference_{k}" for k in range(n)] + [f"similarity_{k}" for k in range(n)])
         for query, refs, sims in selection:
             w.writerow([name(query)] + [name(p) for p in refs] + ["" if p == EMPTY else "%.4f" % v for p, v in zip(refs, sims)])
+    return path
+
+
+USE_KEYS = ("ref_use_share", "ref_use_peak_prob", "ref_use_peak_index", "ref_use_entropy")
+
+
+def reference_use_row(share, peak_prob, entropy):
+    """One query's line of reference_use.csv from its outputs (share, peak_prob (N, h, w), entropy (h, w); host tensors), formed in fp64:
+    -> (mean share per reference, mean peak probability per reference, focus = 1 - mean(entropy) / log2(N h w))"""
+    N, h, w = (int(v) for v in share.shape)
+    shares = share.double().mean(dim=(1, 2)).tolist()
+    peaks = peak_prob.double().mean(dim=(1, 2)).tolist()
+    bits = float(np.log2(float(N * h * w)))
+    focus = 1.0 - float(entropy.double().mean()) / bits if bits > 0 else 1.0  # (one key in all: nothing to spread over)
+    return shares, peaks, focus
+
+
+def write_reference_use(out_dir: str, rows, path_parts: int = 1) -> str:
+    """reference_use.csv of a run with this_main.reference_use: per query its file name, the file names of the references it was scored against
+    (formed as write_reference_selection forms them: path_parts, empty_image for a padded place), then per reference share_k and peak_k, then
+    focus, all as %.4f.  rows: (query path, reference paths, shares, peaks, focus)."""
+    import csv
+    import os
+    from pathlib import Path
+
+    def name(p):
+        return EMPTY if p == EMPTY else "/".join(Path(p).parts[-path_parts:])
+
+    path = os.path.join(str(out_dir), "reference_use.csv")
+    n = len(rows[0][1]) if rows else 0
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["query"] + [f"reference_{k}" for k in range(n)] + [f"share_{k}" for k in range(n)] + [f"peak_{k}" for k in range(n)] + ["focus"])
+        for query, refs, shares, peaks, focus in rows:
+            w.writerow([name(query)] + [name(p) for p in refs] + ["%.4f" % v for v in shares] + ["%.4f" % v for v in peaks] + ["%.4f" % focus])
     return path
 
 
@@ -195,6 +240,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     # ... from the candidate lists THIS rank's batches name, in their order: bank_group maps an item's "reference/cross/group" to the bank's
     bank_group = {g: k for k, g in enumerate(sorted({it["reference/cross/group"] for its in batches for it in its}))} if grouped else None
     selection = []  # ... and per query (path, chosen reference paths, their similarities), in consumption order
+    use_rows = []   # this_main.reference_use: per query (path, reference paths, shares, peaks, focus), in consumption order
     decoder = ImageDecoder(device, pool, png=o.png_decoder == "gpu", jpeg=o.jpeg_decoder == "gpu",
                          progressive=o.jpeg_progressive == "gpu") if "gpu" in (o.png_decoder, o.jpeg_decoder) else None
     window = DecodeWindow(decoder, plan_decodes(batches, zero_ref, cache is not None, extra_files), o.decode_window) if decoder is not None else None
@@ -216,10 +262,24 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
         return prefetch.submit(decode, i, {k[0] for k in cache.tokens} if cache is not None else ())  # (skip: the paths cached by now)
 
     need_w, head_id = bool(cfg.model.need_attn_weights), int(cfg.model.need_attn_weights_head_id)
+    use_kw = {"need_reference_use": True} if o.reference_use else {}
     files, n_done = [], 0
 
+    def stage_reference_use(ticket):
+        """the four reference-use outputs on their way to pinned memory, queued behind the batch's forward on its stream: read in consume"""
+        if not o.reference_use:
+            return None
+        s = ticket.stream if ticket.stream is not None else torch.cuda.current_stream(device)
+        with torch.cuda.stream(s):
+            host = {k: torch.empty(ticket.out[k].shape, dtype=ticket.out[k].dtype, pin_memory=True) for k in USE_KEYS}
+            for k in USE_KEYS:
+                host[k].copy_(ticket.out[k], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(s)
+        return host, ev
+
     def consume(entry):
-        ticket, batch, idx, state = entry
+        ticket, batch, idx, state, use = entry
         out = pipe.result(ticket)
         if window is not None:
             window.check(idx)  # the status words of the files this batch read: a rejected file raises here, naming its path
@@ -235,11 +295,20 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
                 rows = index.to(device=device, dtype=torch.int64)
                 batch["reference/cross/imgs"] = bank.images[torch.where(rows < 0, bank.bank.blank_row, rows) if grouped else rows]
             selection.extend(zip(batch["item_paths"]["query/img"], chosen, sims.tolist()))
+        if use is not None:
+            host, ev = use
+            ev.synchronize()
+            ref_lists = batch["item_paths"]["reference/cross/imgs"]  # N lists of B paths
+            for b, query in enumerate(batch["item_paths"]["query/img"]):
+                use_rows.append((query, [ref_lists[n][b] for n in range(len(ref_lists))]) +
+                                reference_use_row(host["ref_use_share"][b], host["ref_use_peak_prob"][b], host["ref_use_entropy"][b]))
         if on_consume is not None:
             on_consume(idx, batch, out, state)
         summariser.update(batch, out, means=out.get("score_mean_ref_cross"))  # the per-image means the head launch left (score_summariser.py:180-192)
         if writer is not None:
             files.extend(writer.write_out(batch, out, o.local_rank, idx))
+            if o.reference_use_images:
+                files.extend(writer.write_reference_use(batch, out, o.local_rank, idx))
 
     long_run = calibrate and len(batches) >= 16
     pending = submit_decode(0)
@@ -268,7 +337,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
                 if any(e >= 0 for e in ex):  # (an array makes every query of the call count as carrying an exclusion: cs_forward_select)
                     exclude = torch.tensor(ex, dtype=torch.int32).to(device)
             group = np.array([bank_group[it["reference/cross/group"]] for it in its], dtype=np.int32) if grouped else None
-            ticket = (pipe.submit_select_u8 if fused_in else pipe.submit_select)(batch["query/img"], bank.bank, exclude, need_w, head_id, True, group=group)
+            ticket = (pipe.submit_select_u8 if fused_in else pipe.submit_select)(batch["query/img"], bank.bank, exclude, need_w, head_id, True, group=group, **use_kw)
         elif cache is None:
             pending = submit_decode(batch_idx + 1)
             batch, size = load_batch(its, stage, decoded, fused_in, zero_reference=zero_ref)
@@ -280,9 +349,9 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
                 if pipe.depth == 1 and not fused_in:  # one batch at a time: then it is the forward's two lanes that have to overlap (model.py)
                     net.calibrate_lanes(batch["query/img"], refs)
             if fused_in:
-                ticket = pipe.submit_u8(batch["query/img"], refs, need_w, head_id, True)
+                ticket = pipe.submit_u8(batch["query/img"], refs, need_w, head_id, True, **use_kw)
             else:
-                ticket = pipe.submit(batch["query/img"], refs, need_w, head_id, False, return_mean=True)
+                ticket = pipe.submit(batch["query/img"], refs, need_w, head_id, False, return_mean=True, **use_kw)
         else:
             batch, size = load_batch(its, stage, decoded, fused_in, references=False)
             if check_size is not None:
@@ -292,10 +361,10 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
             pending = submit_decode(batch_idx + 1)
             if batch_idx == 0 and long_run:  # the same check for the (default) cached mode
                 pipe.calibrate(batch["query/img"], tokens, cached=True, u8=fused_in)
-            ticket = (pipe.submit_cached_u8 if fused_in else pipe.submit_cached)(batch["query/img"], tokens, need_w, head_id, True)
+            ticket = (pipe.submit_cached_u8 if fused_in else pipe.submit_cached)(batch["query/img"], tokens, need_w, head_id, True, **use_kw)
         state = after_submit(ticket, its, decoded, extras, tuple(size), batch) if after_submit is not None else None
         n_done += len(its)
-        queued.append((ticket, batch, batch_idx, state))
+        queued.append((ticket, batch, batch_idx, state, stage_reference_use(ticket)))
         while len(queued) >= pipe.depth:
             consume(queued.pop(0))
     while queued:
@@ -312,6 +381,8 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
         files += summariser.summarise()
         if similar:
             files.append(write_reference_selection(log.out_dir, selection, 5 if grouped else 1))
+        if o.reference_use:
+            files.append(write_reference_use(log.out_dir, use_rows, 5 if phase == "test" else 1))
     except BaseException as exc:  # noqa: BLE001 -- re-raised by the driver, behind its collective
         failure = exc
     finally:
@@ -324,6 +395,6 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
               "jpeg_decoder": o.jpeg_decoder, "jpeg_decoded": decoder.jpeg_stats() if o.jpeg_decoder == "gpu" else {"jpeg_decoded_gpu": 0, "jpeg_decoded_host": 0},
               "jpeg_progressive": o.jpeg_progressive,
               "jpeg_progressive_decoded": decoder.progressive_stats() if o.jpeg_progressive == "gpu" else {"jpeg_progressive_gpu": 0, "jpeg_progressive_host": 0},
-              "reference_strategy": o.strategy,
+              "reference_strategy": o.strategy, "reference_use": o.reference_use,
               "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}  # the whole scoring loop: input stage, forwards, output stage
     return Scored(result, files, summariser.rows, failure, pipe.nonfinite_count(), net.operand_dtype)

@@ -14,7 +14,8 @@ PCIe instead of 4).  PNG compression has two forms, chosen by `this_main.png_enc
                    the device, queued behind the forward; finished files cross PCIe into pinned memory and the pool threads only write them.
                    Pixel-exact, valid PNGs, not byte-equal to PIL's (independent 16-KiB segments).  `this_main.png_compression`: fast =
                    Sub filter, fixed-Huffman / stored blocks (larger files); compact = per-row adaptive filter, dynamic-Huffman blocks.
-Attention-weight images and the item-path JSON always take the host path.  The composite matplotlib "vis" figure (task/core.py:422-434)
+Attention-weight images and the item-path JSON always take the host path.  The reference-use images (this_main.reference_use_images; DESIGN.md 6,
+f12) are coloured on the device for both encoders (cs_op_score_to_rgb on [0, 1]) and then take the chosen one, so the two give equal pixels.  The composite matplotlib "vis" figure (task/core.py:422-434)
 is not reproduced.
 """
 from __future__ import annotations
@@ -66,6 +67,25 @@ def attn2rgb(attn_map: np.ndarray, table: np.ndarray) -> np.ndarray:
     idx[~(x >= 0)] = 0
     idx[x > 256] = 255
     return table[np.clip(idx, 0, 255)]
+
+
+def focus_map(entropy: torch.Tensor, n_ref: int) -> torch.Tensor:
+    """entropy (B, h, w) in bits of an attention over n_ref * h * w keys -> 1 - entropy / log2(n_ref h w) in fp32: 1 where a patch looked at one
+    key, 0 where it spread evenly over all of them.  (Formed as 1 - entropy * fp32(1 / log2(..)): two roundings, the same on host and device.)"""
+    bits = float(np.log2(float(n_ref * entropy.shape[-2] * entropy.shape[-1])))
+    if not bits > 0:
+        return torch.ones_like(entropy, dtype=torch.float32)
+    return 1.0 - entropy.float() * float(np.float32(1.0 / bits))
+
+
+def unit_to_rgb8(values: torch.Tensor, lut: torch.Tensor) -> torch.Tensor:
+    """(I, H, W) fp32 CUDA values -> (I, H, W, 3) uint8 through the 256-entry table `lut` on [0, 1] (cs_op_score_to_rgb: index trunc(256 x),
+    below 0 the first entry, from 1 on the last)"""
+    values = values.contiguous()
+    out = torch.empty(tuple(values.shape) + (3,), dtype=torch.uint8, device=values.device)
+    _lib.check(_lib.load().cs_op_score_to_rgb(C.c_void_p(values.data_ptr()), values.numel(), 0.0, 1.0, C.c_void_p(lut.data_ptr()), C.c_void_p(out.data_ptr()),
+                                              C.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)))
+    return out
 
 
 def name_stem(path: str) -> str:
@@ -336,6 +356,32 @@ class BatchWriter:
                 self._save(path, attn2rgb(m, table))
                 written.append(str(path))
         return written
+
+    def write_reference_use(self, batch_input, batch_output, local_rank: int, batch_idx: int) -> List[str]:
+        """this_main.reference_use_images: per query, under batch/reference_use/<the attention images' directory name>/cross, ref<k>_<name>.png =
+        the (h, w) map of the share of each query patch's attention that reference k took, and focus.png = focus_map of the entropy; both
+        through the turbo table on [0, 1], at the size the attention images have."""
+        share, entropy = batch_output["ref_use_share"], batch_output["ref_use_entropy"]  # (B, N_ref, h, w), (B, h, w) on the device
+        B, n_ref, h, w = (int(v) for v in share.shape)
+        if getattr(self, "_turbo", None) is None or self._turbo.device != share.device:
+            self._turbo = torch.from_numpy(colormap_table("turbo").reshape(-1)).to(share.device)
+        rgb = unit_to_rgb8(torch.cat([share.reshape(B * n_ref, h, w), focus_map(entropy, n_ref)], dim=0), self._turbo)
+        stems = [name_stem(p) for p in batch_input["item_paths"]["query/img"]]
+        ref_paths = np.array(batch_input["item_paths"]["reference/cross/imgs"]).T  # (B, N_ref)
+        paths = []
+        for b, stem in enumerate(stems):
+            d = self.out_dir_dict["batch"] / "reference_use" / f"r{local_rank}_B{batch_idx:04}_b{b:03}_{stem}" / "cross"
+            d.mkdir(parents=True, exist_ok=True)
+            paths += [d / f"ref{k:02}_{name_stem(rp)}.png" for k, rp in enumerate(ref_paths[b])]
+        paths += [self.out_dir_dict["batch"] / "reference_use" / f"r{local_rank}_B{batch_idx:04}_b{b:03}_{stem}" / "cross" / "focus.png"
+                  for b, stem in enumerate(stems)]
+        if self._png is not None:
+            self._save_gpu(paths, rgb)
+        else:
+            host = rgb.cpu().numpy()
+            for i, path in enumerate(paths):
+                self._save(path, host[i])
+        return [str(p) for p in paths]
 
     def _save(self, path, arr: np.ndarray) -> None:
         self._stats["png_host_files"] += 1

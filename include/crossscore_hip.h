@@ -217,6 +217,12 @@ int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const ui
                                  int R, const int32_t* offsets, int G, const int32_t* query_group, int blank_row, const int32_t* exclude, int B,
                                  int N, int H, int W, const float* mean3, const float* std3, float* score_out, float* attn_out, int head_id,
                                  float* mean_out, int32_t* index_out, float* sim_out, cs_stream stream);
+/* Reference use of the next forward: the four outputs of cs_op_reference_use for the LAST decoder layer's cross-attention --
+ * the one attn_out reports -- with Lq = Np = (H / patch)(W / patch): share, peak_prob, peak_index (B, N, h, w), entropy (B, h, w), device memory,
+ * any of them NULL.  One-shot: the next cs_forward* call of any kind on this handle (plain, _u8, cached, select, grouped) takes the request, sizes it
+ * by its own B, N, H, W, adds one launch ("ref_use" in cs_forward_stats) behind that cross-attention on the call's stream, and clears it whether
+ * it succeeds or fails; cs_encode_references* leaves it armed.  All four NULL cancels.  Every other output of the forward keeps its bits. */
+int cs_request_reference_use(cs_handle h, float* share, float* peak_prob, int32_t* peak_index, float* entropy);
 /* Overflow report.  With fp16 operands an activation beyond 65504 becomes inf and reaches the score map as NaN (nothing clamps in
  * the hot kernels); every forward counts the non-finite values of its score map on the device.  This call waits for the handle's last
  * forward, returns the count since the previous call in *count and resets it: > 0 means "switch to operand_dtype = 1 (bf16)". */
@@ -296,6 +302,18 @@ int cs_op_attention(const uint16_t* Q, const uint16_t* K, const uint16_t* V, uin
 int cs_op_attention_weights(const uint16_t* Q, const uint16_t* K, int ldq, int ldk, long long q_bs, long long k_bs,
                             int batch, int heads, int Lq, int Lk, int dh, float q_scale, const float* lse, int head,
                             float* out, cs_stream stream);
+/* Reference use: what a cross-attention over N references of Np keys each (key k = n Np + j) did with them, all heads, one
+ * launch, no attention matrix in memory.  With s = q_scale * q.k (base 2, as cs_op_attention), e = s - lse[b][hd][q], p = 2^e and
+ * pm[b][q][k] = (1 / heads) sum_hd p:
+ *   share      (batch, N, Lq) fp32   sum_j pm[b][q][n Np + j]          peak_prob  (batch, N, Lq) fp32   max_j pm[b][q][n Np + j]
+ *   peak_index (batch, N, Lq) int32  the j of that maximum, the lowest on equal values
+ *   entropy    (batch, Lq) fp32      (1 / heads) sum_hd sum_k -p e, in bits
+ * lse is cs_op_attention's, used as written.  Any output may be NULL (all NULL: nothing is launched).  Q and K as for cs_op_attention_weights
+ * (CS_ERR_BAD_ARG before any launch otherwise), K rows hold the heads side by side (column hd * dh); a dh outside 16, 48, 64, 96, 128, 192 is
+ * CS_ERR_UNSUPPORTED.  Operand type: cs_debug_set_op_operand_dtype. */
+int cs_op_reference_use(const uint16_t* Q, const uint16_t* K, int ldq, int ldk, long long q_bs, long long k_bs, int batch, int heads, int Lq, int N,
+                        int Np, int dh, float q_scale, const float* lse, float* share, float* peak_prob, int32_t* peak_index, float* entropy,
+                        cs_stream stream);
 int cs_op_layernorm(const float* x, int M, int C, const float* gamma, const float* beta, float eps, float* out_f32,
                     uint16_t* out_f16, cs_stream stream);
 /* Row statistics of the LayerNorm folded into the 256-tile GEMM (cs_config.ln_fold = 0 on hidden 768 / 1024): part (M, sp, 2) partial (sum,

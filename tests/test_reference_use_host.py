@@ -1,0 +1,171 @@
+"""Reference use without a GPU: the fp64 oracle's own properties (tests/reference_use_oracle.py), the four tiling mistakes it can restate -- each
+moves more than half of the values it concerns, beyond the caps the GPU tests hold the kernel to -- and the drivers' option handling."""
+import os
+
+import numpy as np
+import pytest
+
+import reference_use_oracle as oracle
+
+
+def _rng(seed):
+    return np.random.Generator(np.random.PCG64(seed))
+
+
+def _case(seed, B, heads, Lq, N, Np, dh, q_amp=0.3):
+    g = _rng(seed)
+    Q = q_amp * g.standard_normal((B, Lq, heads * dh))
+    K = g.standard_normal((B, N * Np, heads * dh))
+    s = oracle.logits(Q, K, heads, dh)
+    return s, oracle.lse_of(s)
+
+
+SHAPES = [(2, 8, 33, 3, 65, 48), (1, 3, 17, 5, 17, 16), (2, 1, 16, 2, 100, 96), (1, 8, 5, 1, 63, 48)]
+
+
+@pytest.mark.parametrize("B,heads,Lq,N,Np,dh", SHAPES)
+def test_shares_sum_to_one_and_shapes(B, heads, Lq, N, Np, dh):
+    s, lse = _case(1, B, heads, Lq, N, Np, dh)
+    r = oracle.reference_use(s, lse, N, Np)
+    assert r["share"].shape == r["peak_prob"].shape == r["peak_index"].shape == (B, N, Lq) and r["entropy"].shape == (B, Lq)
+    assert np.abs(r["share"].sum(axis=1) - 1.0).max() < 1e-12
+    assert (r["peak_prob"] <= r["share"] + 1e-15).all() and (r["peak_prob"] >= r["share"] / Np - 1e-15).all()
+    assert (r["entropy"] > 0).all() and (r["entropy"] <= np.log2(N * Np) + 1e-12).all()
+    # the values themselves, from the definition written out per element
+    b, q, n = B - 1, Lq // 2, N - 1
+    p = np.exp2(s[b, :, q, :] - lse[b, :, q, None])
+    pm = p.mean(axis=0)[n * Np:(n + 1) * Np]
+    assert abs(r["share"][b, n, q] - pm.sum()) < 1e-14 and abs(r["peak_prob"][b, n, q] - pm.max()) < 1e-16
+    assert r["peak_index"][b, n, q] == int(pm.argmax())
+    assert abs(r["entropy"][b, q] - (-(p * np.log2(p)).sum(axis=1)).mean()) < 1e-10
+
+
+def test_zero_queries_give_uniform_use():
+    B, heads, Lq, N, Np, dh = 2, 3, 9, 3, 17, 16
+    s, lse = _case(2, B, heads, Lq, N, Np, dh, q_amp=0.0)
+    r = oracle.reference_use(s, lse, N, Np)
+    assert np.abs(r["share"] - 1.0 / N).max() < 1e-14
+    assert np.abs(r["entropy"] - np.log2(N * Np)).max() < 1e-12
+    assert (r["peak_index"] == 0).all()
+    assert np.abs(r["peak_prob"] - 1.0 / (N * Np)).max() < 1e-16
+
+
+def test_one_hot_rows_name_their_reference_and_patch():
+    B, heads, Lq, N, Np = 1, 2, 12, 3, 17
+    s = np.zeros((B, heads, Lq, N * Np))
+    q = np.arange(Lq)
+    n = (q // 2) % (N - 1)
+    ref = np.where(q % 2 == 1, n, n + 1)
+    j = np.where(q % 2 == 1, Np - 1, 0)
+    s[0, :, q, ref * Np + j] = 40.0
+    r = oracle.reference_use(s, oracle.lse_of(s), N, Np)
+    assert (r["share"][0, ref, q] > 0.999).all() and (r["peak_index"][0, ref, q] == j).all()
+    other = np.ones((N, Lq), dtype=bool)
+    other[ref, q] = False
+    assert (r["peak_index"][0][other] == 0).all() and (r["share"][0][other] < 1e-9).all()
+
+
+def _moved(a, b, cap):
+    return float((np.abs(a - b) > cap).mean())
+
+
+@pytest.mark.parametrize("B,heads,Lq,N,Np,dh", SHAPES)
+def test_counting_padded_keys_moves_the_shares(B, heads, Lq, N, Np, dh):
+    s, lse = _case(3, B, heads, Lq, N, Np, dh)
+    good, bad = oracle.reference_use(s, lse, N, Np), oracle.reference_use(s, lse, N, Np, count_padded=True)
+    assert _moved(good["share"], bad["share"], oracle.REL * good["share"] + 1e-6) > 0.5
+    assert np.abs(bad["share"].sum(axis=1) - 1.0).min() > oracle.REL
+
+
+@pytest.mark.parametrize("B,heads,Lq,N,Np,dh", [s for s in SHAPES if s[3] > 1])
+def test_a_tail_key_in_the_next_reference_moves_the_shares(B, heads, Lq, N, Np, dh):
+    s, lse = _case(4, B, heads, Lq, N, Np, dh)
+    good, bad = oracle.reference_use(s, lse, N, Np), oracle.reference_use(s, lse, N, Np, tail_to_next=True)
+    assert _moved(good["share"], bad["share"], oracle.REL * good["share"] + 1e-6) > 0.5
+
+
+@pytest.mark.parametrize("B,heads,Lq,N,Np,dh", [s for s in SHAPES if s[1] > 1])
+def test_the_head_mean_behind_the_maximum_moves_the_peaks(B, heads, Lq, N, Np, dh):
+    s, lse = _case(5, B, heads, Lq, N, Np, dh)
+    good, bad = oracle.reference_use(s, lse, N, Np), oracle.reference_use(s, lse, N, Np, max_before_mean=True)
+    assert _moved(good["peak_prob"], bad["peak_prob"], oracle.REL * good["peak_prob"] + 1e-6) > 0.5
+
+
+def test_ties_to_the_highest_index_move_every_index():
+    B, heads, Lq, N, Np, dh = 1, 3, 9, 3, 17, 16
+    s, lse = _case(6, B, heads, Lq, N, Np, dh, q_amp=0.0)
+    good, bad = oracle.reference_use(s, lse, N, Np), oracle.reference_use(s, lse, N, Np, ties_high=True)
+    assert (good["peak_index"] == 0).all() and (bad["peak_index"] == Np - 1).all()
+
+
+@pytest.mark.parametrize("B,heads,Lq,N,Np,dh", [(1, 8, 130, 3, 65, 48), (1, 8, 65, 5, 17, 16), (1, 8, 33, 3, 63, 48)])
+def test_the_peak_margin_leaves_few_cases_undecided(B, heads, Lq, N, Np, dh):
+    """On the GPU tests' data the oracle alone leaves well under 3 % of the (b, q, n) cases within 2e-3 of a tie, and checks itself."""
+    s, lse = _case(7, B, heads, Lq, N, Np, dh)
+    r = oracle.reference_use(s, lse, N, Np)
+    inside, total = oracle.check_peak_index(r["peak_index"], r, Np)
+    assert total == B * N * Lq and inside <= oracle.MAX_INSIDE * total
+    oracle.check_values(r, r)
+
+
+# ------------------------------------------------------------------------------------------------------------------- the drivers' options
+def _cfg(tmp_path, *over, name="default_predict"):
+    from crossscore_amd.config import load_config
+
+    return load_config(name, [f"data.dataset.query_dir={tmp_path / 'q'}", f"data.dataset.reference_dir={tmp_path / 'r'}", *over])
+
+
+def test_options_of_a_reference_use_run(tmp_path, monkeypatch):
+    import torch
+
+    from crossscore_amd import scoring
+
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)  # options() only reads the configuration behind this check
+    o = scoring.options(_cfg(tmp_path), "predict")
+    assert o.reference_use is False and o.reference_use_images is False  # the YAML files do not name the keys
+    o = scoring.options(_cfg(tmp_path, "this_main.reference_use=True"), "predict")
+    assert o.reference_use is True and o.reference_use_images is False
+    o = scoring.options(_cfg(tmp_path, "this_main.reference_use=True", "this_main.reference_use_images=True"), "predict")
+    assert o.reference_use_images is True
+    with pytest.raises(ValueError, match="reference_use_images"):  # the images need the request ...
+        scoring.options(_cfg(tmp_path, "this_main.reference_use_images=True"), "predict")
+    with pytest.raises(ValueError, match="reference_use_images"):  # ... and the batch writer
+        scoring.options(_cfg(tmp_path, "this_main.reference_use=True", "this_main.reference_use_images=True", "logger.predict.write.flag.batch=False"), "predict")
+    with pytest.raises(ValueError, match="cross"):
+        scoring.options(_cfg(tmp_path, "this_main.reference_use=True", "data.neighbour_config.cross=0"), "predict")
+    for strategy in ("random", "similar"):
+        assert scoring.options(_cfg(tmp_path, "this_main.reference_use=True", f"data.neighbour_config.strategy={strategy}"), "predict").reference_use
+
+
+def test_reference_use_csv_and_rows(tmp_path):
+    import torch
+
+    from crossscore_amd import scoring
+
+    share = torch.tensor([[[0.25, 0.75], [0.5, 0.5]], [[0.75, 0.25], [0.5, 0.5]]])       # (N = 2, h = 2, w = 2)
+    peak = share / 2
+    ent = torch.full((2, 2), 1.5)
+    shares, peaks, focus = scoring.reference_use_row(share, peak, ent)
+    assert shares == [0.5, 0.5] and peaks == [0.25, 0.25] and abs(focus - (1 - 1.5 / 3.0)) < 1e-15
+    rows = [("/d/a/b/c/renders/q0.png", ["/d/a/b/c/gt/r0.png", "empty_image"], shares, peaks, focus)]
+    path = scoring.write_reference_use(str(tmp_path), rows, 1)
+    assert open(path).read().splitlines() == ["query,reference_0,reference_1,share_0,share_1,peak_0,peak_1,focus",
+                                              "q0.png,r0.png,empty_image,0.5000,0.5000,0.2500,0.2500,0.5000"]
+    scoring.write_reference_use(str(tmp_path), rows, 5)
+    assert open(path).read().splitlines()[1].startswith("a/b/c/renders/q0.png,a/b/c/gt/r0.png,empty_image,")
+    # the names are formed as reference_selection.csv forms them
+    scoring.write_reference_selection(str(tmp_path), [(rows[0][0], rows[0][1], [0.5, 0.0])], 5)
+    sel = open(os.path.join(str(tmp_path), "reference_selection.csv")).read().splitlines()[1].split(",")
+    assert sel[:3] == open(path).read().splitlines()[1].split(",")[:3]
+
+
+def test_focus_map_is_one_minus_the_normalised_entropy():
+    import torch
+
+    from crossscore_amd.writers import focus_map
+
+    ent = torch.tensor([[[0.0, 3.0], [1.5, 0.75]]])  # (1, 2, 2), N = 2: log2(8) = 3 bits
+    want = np.float32(1.0) - ent.numpy() * np.float32(1.0 / 3.0)  # fp32 throughout: a product and a difference, each rounded once
+    assert want.dtype == np.float32 and np.array_equal(focus_map(ent, 2).numpy(), want)
+    assert np.abs(want - np.array([[[1.0, 0.0], [0.5, 0.75]]])).max() < 1e-6
+    assert torch.equal(focus_map(torch.zeros((1, 1, 1)), 1), torch.ones((1, 1, 1)))  # one key in all

@@ -1,0 +1,306 @@
+"""cs_op_reference_use (csrc/refuse.hip) against the fp64 oracle of tests/reference_use_oracle.py, in fp16 and bf16.
+
+Both sides see the same 16-bit Q and K (Q carries the softmax scale: q_scale = 1) and the lse cs_op_attention wrote for them, so what is compared
+is the kernel's own arithmetic: the MFMA dot products in fp32, v_exp_f32, the fp32 sums over heads and keys.  The bounds are the caps of DESIGN.md 6
+(f12), stated in reference_use_oracle.check_values / check_peak_index.
+
+Geometry.  A workgroup is 4 waves of 16 query rows of one batch item; it walks the references, each reference's 64-key tiles, each tile's heads.  Lane
+(li, g) owns query li and keys 16 kt + 4 g .. + 3 of the tile.  What this makes possible to get wrong: a ragged tile's clamped rows counted, a tile
+that runs into the next reference, dead waves that must still stage and meet the barriers (Lq = 1, 15, 16, 17, 33, 65, 130), dead 16-key tiles
+(Np = 1, 15, 16, 17), both LDS buffers used again (Np = 65, 100 or several heads / references), the zero columns of dh = 16 / 48, the reduction
+over a row's four lanes with the lowest-index rule, and the reset between references."""
+import ctypes as C
+import itertools
+
+import numpy as np
+import pytest
+import torch
+
+from crossscore_amd import _lib  # noqa: E402
+import guard  # noqa: E402
+import hip_helpers as hh  # noqa: E402
+import reference_use_oracle as oracle  # noqa: E402
+from test_hip_attention_tiles import _OpDtype, _fl, _rd, _rng, _t  # noqa: E402
+
+DEV = "cuda"
+NPS = (1, 15, 16, 17, 63, 64, 65, 100)
+LQS = (1, 15, 16, 17, 33, 64, 65, 130)
+NS = (1, 2, 3, 5)
+HEADS = (1, 3, 8)
+DHS = (16, 48, 64, 96, 128, 192)
+NAMES = ("share", "peak_prob", "peak_index", "entropy")
+
+
+def operand(x, ld, extra_rows=3):
+    """x (B, L, C) 16-bit -> a view of the same values with rows ld apart and items (L + extra_rows) rows apart; the row padding, the rows between
+    the items and the bands around everything hold NaN / Inf / 65504"""
+    B, L, Cc = x.shape
+    full = torch.full((B, L + extra_rows, Cc), float("nan"), dtype=torch.float16, device=x.device)
+    full[:, :L] = x
+    return guard.poisoned_in(full, ld)[:, :L]
+
+
+def outputs(B, N, Lq):
+    """the four outputs inside guard bands -> ({name: view}, [check, ...])"""
+    views, checks = {}, []
+    for name in NAMES:
+        shape = (B, Lq) if name == "entropy" else (B, N, Lq)
+        v, chk = guard.guarded_out(shape, torch.int32 if name == "peak_index" else torch.float32, guard_rows=64)
+        views[name] = v
+        checks.append(chk)
+    return views, checks
+
+
+def reference_use(Q, K, lse, heads, dh, N, Np, out, q_scale=1.0, rc_only=False, ldq=None, ldk=None):
+    """Q (B, Lq, .), K (B, N Np, .) strided views; out: {name: tensor or None}"""
+    lib = _lib.load()
+    B, Lq, _ = Q.shape
+    for t in out.values():
+        assert t is None or t.is_contiguous()
+    rc = lib.cs_op_reference_use(hh._p(Q), hh._p(K), ldq or Q.stride(1), ldk or K.stride(1), Q.stride(0), K.stride(0), B, heads, Lq, N, Np, dh, q_scale,
+                                 hh._p(lse), *(hh._p(out.get(n)) for n in NAMES), hh._stream())
+    if rc_only:
+        return rc
+    _lib.check(rc)
+    return out
+
+
+def random_case(g, B, Lq, N, Np, heads, dh, bf16):
+    """Q = 0.3 N(0, 1), K = N(0, 1) rounded to the operand type, in strided poisoned buffers (ldk = 4 heads dh as in the forward's kv buffer);
+    lse from cs_op_attention on them -> (Q, K, lse, oracle result)"""
+    rd, fl = _rd(bf16), _fl(bf16)
+    Cc = heads * dh
+    Q = operand(rd(_t(0.3 * g.standard_normal((B, Lq, Cc), dtype=np.float32))), Cc + 8)
+    K = operand(rd(_t(g.standard_normal((B, N * Np, Cc), dtype=np.float32))), 4 * Cc)
+    V = rd(_t(g.standard_normal((B, N * Np, Cc), dtype=np.float32)))
+    _, lse = hh.attention(Q, K, V, heads, dh, lse=True, q_scale=1.0)
+    want = oracle.reference_use(oracle.logits(fl(Q).cpu().numpy(), fl(K).cpu().numpy(), heads, dh), lse.cpu().numpy(), N, Np)
+    return Q, K, lse, want
+
+
+def run_and_check(Q, K, lse, want, heads, dh, N, Np, what):
+    B, Lq, _ = Q.shape
+    out, checks = outputs(B, N, Lq)
+    reference_use(Q, K, lse, heads, dh, N, Np, out)
+    for chk in checks:
+        chk(what)
+    got = {k: v.cpu().numpy() for k, v in out.items()}
+    assert all(np.isfinite(got[k]).all() for k in ("share", "peak_prob", "entropy")), what
+    fig = oracle.check_values(got, want, what)
+    inside = oracle.check_peak_index(got["peak_index"], want, Np, what)
+    return fig, inside, got
+
+
+def _sweep(shapes, heads, dh, bf16, seed):
+    worst, inside, total = {}, 0, 0
+    with _OpDtype(bf16):
+        for i, (Lq, N, Np) in enumerate(shapes):
+            B = 1 + i % 3
+            g = _rng(seed + 7919 * i)
+            Q, K, lse, want = random_case(g, B, Lq, N, Np, heads, dh, bf16)
+            fig, (a, b), _ = run_and_check(Q, K, lse, want, heads, dh, N, Np, f"dh {dh} heads {heads} Lq {Lq} N {N} Np {Np} B {B}")
+            inside, total = inside + a, total + b
+            for k, v in fig.items():
+                worst[k] = max(worst.get(k, 0.0), v)
+    print(f"dh {dh} heads {heads} {'bf16' if bf16 else 'fp16'}: share {worst['share']:.3f} peak {worst['peak_prob']:.3f} entropy {worst['entropy']:.3f} "
+          f"of their caps, |sum - 1| {worst['sum']:.2e}; {inside} of {total} peak cases inside the margin")
+    return inside, total
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("heads", HEADS)
+@pytest.mark.parametrize("N", NS)
+@pytest.mark.parametrize("dh", [16, 48])
+def test_full_grid_against_the_oracle(dh, N, heads, bf16):
+    """Every Lq x Np of the grid for this (dh, N, heads, type), batch 1 - 3 in turn, strides wider than tight, poison around Q and K."""
+    shapes = [(Lq, N, Np) for Lq, Np in itertools.product(LQS, NPS)]
+    inside, total = _sweep(shapes, heads, dh, bf16, 1000 * dh + 100 * N + heads)
+    assert inside <= oracle.MAX_INSIDE * total, (inside, total)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("dh", DHS)
+def test_every_head_dim_against_the_oracle(dh, bf16):
+    """Every head dim the attention kernel takes at (Lq 65, N 3, Np 65) and (17, 2, 17), every number of heads."""
+    inside = total = 0
+    for heads in HEADS:
+        a, b = _sweep([(65, 3, 65), (17, 2, 17)], heads, dh, bf16, 77 * dh + heads)
+        inside, total = inside + a, total + b
+    assert inside <= oracle.MAX_INSIDE * total, (inside, total)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("dh", [16, 48, 96])
+def test_zero_queries_tie_to_index_zero_and_equal_shares(dh, bf16):
+    """Q = 0: every logit is 0, every p of a row the same.  peak_index is 0 everywhere (the tie rule, through the lane-local scan and the
+    four-lane reduction), every (b, q, n) share has the same bits, the entropy is log2(N Np) within its cap."""
+    rd = _rd(bf16)
+    heads = 3
+    with _OpDtype(bf16):
+        for Lq, N, Np in ((33, 3, 65), (130, 5, 17), (17, 2, 100), (16, 1, 64)):
+            g = _rng(dh + Np)
+            Cc = heads * dh
+            Q = operand(rd(torch.zeros((2, Lq, Cc), device=DEV)), Cc + 8)
+            K = operand(rd(_t(g.standard_normal((2, N * Np, Cc), dtype=np.float32))), 4 * Cc)
+            _, lse = hh.attention(Q, K, K.contiguous(), heads, dh, lse=True, q_scale=1.0)
+            out, checks = outputs(2, N, Lq)
+            reference_use(Q, K, lse, heads, dh, N, Np, out)
+            for chk in checks:
+                chk()
+            assert int(out["peak_index"].abs().max()) == 0
+            bits = out["share"].view(torch.int32)
+            assert int(bits.min()) == int(bits.max()), "shares of equal logits differ in their bits"
+            assert abs(float(out["share"][0, 0, 0]) - 1.0 / N) <= 5e-4 / N + 1e-6
+            ent = np.log2(N * Np)
+            assert float((out["entropy"].double() - ent).abs().max()) <= 5e-4 * (1 + ent) + 1e-5
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("dh", [16, 48])
+def test_one_hot_rows_on_both_sides_of_a_reference_boundary(dh, bf16):
+    """Query q looks at ONE key with logit 40 against 0: for odd q the last patch (j = Np - 1) of reference n, for even q the first patch of
+    reference n + 1, n = (q // 2) mod (N - 1) -- the two keys on either side of a boundary between references.  The share of the right reference is
+    above 0.999, its peak_index exact; every other reference holds equal values only, so its index is 0."""
+    rd = _rd(bf16)
+    heads = 3
+    with _OpDtype(bf16):
+        for Lq, N, Np in ((33, 2, 1), (33, 3, 17), (65, 5, 64), (33, 3, 65), (17, 2, 100)):
+            Cc = heads * dh
+            q = torch.arange(Lq, device=DEV)
+            n = (q // 2) % (N - 1)
+            ref = torch.where(q % 2 == 1, n, n + 1)
+            j = torch.where(q % 2 == 1, torch.full_like(q, Np - 1), torch.zeros_like(q))
+            chan = 2 * n + (q % 2 == 0).long()  # one channel per designated key: at most 2 (N - 1) <= 8
+            Qd = torch.zeros((1, Lq, heads, dh), device=DEV)
+            Qd[0, q, :, chan] = 5.0
+            Kd = torch.zeros((1, N * Np, heads, dh), device=DEV)
+            Kd[0, ref * Np + j, :, chan] = 8.0
+            Q = operand(rd(Qd.view(1, Lq, Cc)), Cc + 8)
+            K = operand(rd(Kd.view(1, N * Np, Cc)), 4 * Cc)
+            _, lse = hh.attention(Q, K, K.contiguous(), heads, dh, lse=True, q_scale=1.0)
+            out, checks = outputs(1, N, Lq)
+            reference_use(Q, K, lse, heads, dh, N, Np, out)
+            for chk in checks:
+                chk()
+            want_idx = torch.zeros((N, Lq), dtype=torch.int32, device=DEV)
+            want_idx[ref, q] = j.int()
+            assert torch.equal(out["peak_index"][0], want_idx), (Lq, N, Np)
+            assert float(out["share"][0, ref, q].min()) > 0.999, (Lq, N, Np)
+            assert float((out["share"][0].sum(0) - 1).abs().max()) <= 5e-4
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("Np", [17, 65])
+def test_negative_logits_show_a_counted_padded_key(Np, bf16):
+    """All real logits near -20 (K along -Q's common direction): a zero-filled key of the ragged tile, s = 0, would carry 2^20 times a real key's
+    weight.  The shares still sum to 1 and everything meets the oracle."""
+    rd, fl = _rd(bf16), _fl(bf16)
+    heads, dh, Lq, N, B = 3, 48, 33, 3, 2
+    Cc = heads * dh
+    g = _rng(Np)
+    a = np.sqrt(20.0 / dh)
+    with _OpDtype(bf16):
+        Q = operand(rd(_t((a + 0.05 * g.standard_normal((B, Lq, Cc))).astype(np.float32))), Cc + 8)
+        K = operand(rd(_t((-a + 0.05 * g.standard_normal((B, N * Np, Cc))).astype(np.float32))), 4 * Cc)
+        _, lse = hh.attention(Q, K, K.contiguous(), heads, dh, lse=True, q_scale=1.0)
+        s = oracle.logits(fl(Q).cpu().numpy(), fl(K).cpu().numpy(), heads, dh)
+        assert s.max() < -15 and s.min() > -25
+        want = oracle.reference_use(s, lse.cpu().numpy(), N, Np)
+        fig, _, got = run_and_check(Q, K, lse, want, heads, dh, N, Np, f"Np {Np}")
+        wrong = oracle.reference_use(s, lse.cpu().numpy(), N, Np, count_padded=True)
+        assert wrong["share"].sum(axis=1).min() > 100.0  # what the mistake would give here
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+def test_items_are_independent_of_their_batch(bf16):
+    """Every output of an item has the same bits alone and at any position of a batch of 3; a call on the middle item of a guarded buffer of three
+    leaves the other two items' outputs and the bands untouched."""
+    heads, dh, Lq, N, Np = 8, 48, 65, 3, 65
+    with _OpDtype(bf16):
+        Q, K, lse, _ = random_case(_rng(5), 3, Lq, N, Np, heads, dh, bf16)
+        out, checks = outputs(3, N, Lq)
+        reference_use(Q, K, lse, heads, dh, N, Np, out)
+        for b in range(3):
+            one, chk1 = outputs(3, N, Lq)
+            reference_use(Q[b:b + 1], K[b:b + 1], lse[b:b + 1].contiguous(), heads, dh, N, Np, {k: v[1:2] for k, v in one.items()})
+            for chk in chk1:
+                chk()
+            torch.cuda.synchronize()
+            for name in NAMES:
+                assert torch.equal(one[name][1].view(torch.int32), out[name][b].view(torch.int32)), (name, b)
+                ib = one[name].view(torch.int32)
+                sentinel = guard._signed(guard.SENTINEL[one[name].dtype], 4)
+                assert bool((ib[0] == sentinel).all()) and bool((ib[2] == sentinel).all()), f"{name}: a call on one item wrote into another's output"
+
+
+@pytest.mark.gpu
+def test_null_outputs_in_every_combination():
+    """Any output pointer may be null: the others keep the bits of the full call; all four null launches nothing and returns 0."""
+    heads, dh, Lq, N, Np = 3, 16, 33, 2, 17
+    Q, K, lse, _ = random_case(_rng(9), 2, Lq, N, Np, heads, dh, False)
+    full, _ = outputs(2, N, Lq)
+    reference_use(Q, K, lse, heads, dh, N, Np, full)
+    for mask in range(16):
+        out, checks = outputs(2, N, Lq)
+        reference_use(Q, K, lse, heads, dh, N, Np, {n: (out[n] if mask >> i & 1 else None) for i, n in enumerate(NAMES)})
+        for chk in checks:
+            chk()
+        for i, n in enumerate(NAMES):
+            if mask >> i & 1:
+                assert torch.equal(out[n].view(torch.int32), full[n].view(torch.int32)), (mask, n)
+            else:
+                assert bool((out[n].view(torch.int32) == guard._signed(guard.SENTINEL[out[n].dtype], 4)).all()), (mask, n)
+
+
+@pytest.mark.gpu
+def test_bad_strides_and_head_dims_are_refused_before_any_launch():
+    """cs_attn_check's rules for Q and K: row and batch strides multiples of 8 elements, N Np ldk below 2^30; an unbuilt head dim is
+    CS_ERR_UNSUPPORTED.  Nothing is written."""
+    heads, dh, Lq, N, Np = 2, 16, 17, 2, 17
+    Q, K, lse, _ = random_case(_rng(3), 1, Lq, N, Np, heads, dh, False)
+    out, checks = outputs(1, N, Lq)
+    lib = _lib.load()
+
+    def call(ldq=Q.stride(1), ldk=K.stride(1), q_bs=Q.stride(0), k_bs=K.stride(0), dh_=dh, N_=N, lse_=lse, q_scale=1.0):
+        return lib.cs_op_reference_use(hh._p(Q), hh._p(K), ldq, ldk, q_bs, k_bs, 1, heads, Lq, N_, Np, dh_, q_scale, hh._p(lse_),
+                                       *(hh._p(out[n]) for n in NAMES), hh._stream())
+
+    assert call(ldq=Q.stride(1) + 4) == _lib.CS_ERR_BAD_ARG
+    assert call(ldk=K.stride(1) + 4) == _lib.CS_ERR_BAD_ARG
+    assert call(q_bs=Q.stride(0) + 4) == _lib.CS_ERR_BAD_ARG
+    assert call(k_bs=K.stride(0) + 4) == _lib.CS_ERR_BAD_ARG
+    assert call(ldk=(1 << 30) // (N * Np) // 8 * 8 + 8) == _lib.CS_ERR_BAD_ARG
+    assert call(N_=0) == _lib.CS_ERR_BAD_ARG
+    assert call(lse_=None) == _lib.CS_ERR_BAD_ARG
+    assert call(q_scale=-1.0) == _lib.CS_ERR_BAD_ARG
+    for bad_dh in (8, 32, 80, 256):
+        assert call(dh_=bad_dh) == _lib.CS_ERR_UNSUPPORTED, bad_dh
+    for chk in checks:
+        chk()
+    for n in NAMES:
+        assert bool((out[n].view(torch.int32) == guard._signed(guard.SENTINEL[out[n].dtype], 4)).all()), n
+    assert call() == 0  # and the same arguments unchanged are taken
+
+
+@pytest.mark.gpu
+def test_raw_queries_are_scaled_and_rounded_like_the_attention_kernel():
+    """q_scale = 0: log2(e) / sqrt(dh) is applied to raw Q inside both kernels with one more rounding to the operand type."""
+    heads, dh, Lq, N, Np, B = 3, 48, 33, 2, 65, 2
+    g = _rng(11)
+    Cc = heads * dh
+    Q = operand(_t(2.0 * g.standard_normal((B, Lq, Cc), dtype=np.float32)).half(), Cc + 8)
+    K = operand(_t(g.standard_normal((B, N * Np, Cc), dtype=np.float32)).half(), 4 * Cc)
+    _, lse = hh.attention(Q, K, K.contiguous(), heads, dh, lse=True, q_scale=0.0)
+    Qs = (Q.float() * float(np.float32(1.4426950408889634) / np.sqrt(np.float32(dh)))).half()  # the factor in fp32, as the library forms it
+    want = oracle.reference_use(oracle.logits(Qs.float().cpu().numpy(), K.float().cpu().numpy(), heads, dh), lse.cpu().numpy(), N, Np)
+    out, checks = outputs(B, N, Lq)
+    reference_use(Q, K, lse, heads, dh, N, Np, out, q_scale=0.0)
+    for chk in checks:
+        chk()
+    oracle.check_values({k: v.cpu().numpy() for k, v in out.items()}, want)

@@ -21,6 +21,7 @@ ap.add_argument("--images-per-split", type=int, default=16)
 ap.add_argument("--rounds", type=int, default=2)
 ap.add_argument("--size", default="540x720", help="render size HxW (518x518: cfg-2's geometry, no resize)")
 ap.add_argument("--png-decoders", default="host", help="comma-separated this_main.png_decoder values, one leg each per phase")
+ap.add_argument("--reference-use", action="store_true", help="predict legs only, without and with this_main.reference_use=True (DESIGN.md 6, f12), alternating")
 args = ap.parse_args()
 root = tempfile.mkdtemp(prefix="eval_e2e_")
 base = os.path.join(root, "tree", "res_540")
@@ -65,7 +66,10 @@ def _maps_timed(self, *a, **k):
 data_mod.InputStage.metric_maps = _maps_timed
 
 for rnd in range(args.rounds):  # (the first round pays table builds, stream probes and page-ins)
-    for phase, dec in [(ph, d) for ph in ("evaluate", "predict") for d in args.png_decoders.split(",")]:
+    legs = [(ph, d, False) for ph in ("evaluate", "predict") for d in args.png_decoders.split(",")]
+    if args.reference_use:
+        legs = [("predict", d, use) for d in args.png_decoders.split(",") for use in (False, True)]
+    for phase, dec, use in legs:
         spans.clear()
         gt_host.clear()
         t0 = time.perf_counter()
@@ -79,15 +83,15 @@ for rnd in range(args.rounds):  # (the first round pays table builds, stream pro
             for split, other in (("train", "test"), ("test", "train")):
                 d = os.path.join(base, "s00000")
                 over = [f"data.dataset.query_dir={d}/{split}/ours_1000/renders", f"data.dataset.reference_dir={d}/{other}/ours_1000/gt",
-                        f"logger.predict.out_dir={root}/out_{rnd}_{split}_pred_{dec}", "logger.predict.write.config.score_map_colour_mode=gray",
-                        f"this_main.png_decoder={dec}"]
+                        f"logger.predict.out_dir={root}/out_{rnd}_{split}_pred_{dec}_{use}", "logger.predict.write.config.score_map_colour_mode=gray",
+                        f"this_main.png_decoder={dec}", f"this_main.reference_use={use}"]
                 r = predict(load_config("default_predict", over + [c.format("predict") for c in common]), state_dict=sd, now="T")
                 rates.append(r["query_images_per_sec"])
             loop = n / sum(args.images_per_split / x for x in rates)
         dt = time.perf_counter() - t0
         fr = [p.in_flight_fractions() for p in spans]
         busy = sum(f["window_ms"] * (1 - f["fraction_idle"]) for f in fr if f) / max(sum(f["window_ms"] for f in fr if f), 1e-9)
-        print(json.dumps({"round": rnd, "phase": phase, "png_decoder": dec, "size": args.size, "query_images": n, "query_images_per_sec_loop": round(loop, 1),
+        print(json.dumps({"round": rnd, "phase": phase, "png_decoder": dec, **({"reference_use": use} if args.reference_use else {}), "size": args.size, "query_images": n, "query_images_per_sec_loop": round(loop, 1),
                           "query_images_per_sec_wall": round(n / dt, 1), "gpu_busy_fraction_of_forward_window": round(busy, 3),
                           **({"gt_stage_host_ms_per_batch_median": round(1e3 * sorted(gt_host)[len(gt_host) // 2], 3),
                               "gt_stage_host_ms_per_batch_max": round(1e3 * max(gt_host), 3)} if gt_host else {})}), flush=True)
