@@ -1,6 +1,8 @@
 """Tile-level tests of the encoder token-panel kernel (csrc/panel.hip) on its 16x16x32 MFMA tiles: a wave pair's 32 rows are two row tiles of
 16, a weight fragment is 16 output features x 32 contraction slots, a D tile hands lane (li, g) token li and features 4g .. 4g+3.
 Same op entry points as test_hip_panel.py (cs_op_panel_pack / cs_op_encoder_panel); every case is one or a few launches of at most 257 rows.
+The 8-wave kernel (the default) throughout; the four-wave form (csrc/panel4.hip: 32-row blocks, column-split waves, its own weight image) has
+its own module, test_hip_panel4_tiles.py, which shares the reference, the operand helpers and the bounds below.
 
 Parent kernel (32x32x16 tiles) on the inputs of test_ragged_rows_at_tile_granularity, measured once with the parent library; the bounds of the
 test are the ones test_hip_panel.py carries (fp16: test_panel_vs_torch; bf16: the concurrent-streams test), not these figures:
@@ -20,7 +22,8 @@ DEV = "cuda:0"
 
 
 class _mode:
-    """cs_debug_set_op_operand_dtype for the duration of a block, restored in any case; the 8-wave kernel (the default) throughout"""
+    """cs_debug_set_op_operand_dtype for the duration of a block, restored in any case; the 8-wave kernel (the default) throughout (the four-wave
+    kernel: _mode4 of test_hip_panel4_tiles.py)"""
 
     def __init__(self, bf16):
         self.bf16 = bf16
