@@ -1,10 +1,33 @@
 """torch-tensor wrappers over the single-op C-ABI entry points (tests only).  Outputs are allocated here unless the caller passes them (views into
 guarded buffers: tests/guard.py); every row pitch passed to the library is the tensor's own stride, so strided views go through unchanged."""
+import contextlib
 import ctypes as C
 
 import torch
 
 from crossscore_amd import _lib
+
+# the library's process-wide debug switches: keyword of switches() -> (setter, the library's default).  The ABI has no getters.
+SWITCHES = {"bf16": ("cs_debug_set_op_operand_dtype", 0), "gemm256": ("cs_debug_gemm256_enable", 1), "panel_impl": ("cs_debug_panel_impl", 0),
+            "rowln": ("cs_debug_rowln_enable", 1), "grid": ("cs_debug_gemm_grid", 0)}
+
+
+@contextlib.contextmanager
+def switches(lib=None, **given):
+    """Sets exactly the switches it is given (bf16=, gemm256=, panel_impl=, rowln=, grid=; None: not given) for the duration of a block and puts
+    exactly those back to the library's defaults on every way out, a refused operand type during entry included.  Managers over different
+    switches nest; `lib` is the loaded library unless a test passes a stand-in."""
+    given = {k: int(v) for k, v in given.items() if v is not None}
+    assert set(given) <= set(SWITCHES), sorted(set(given) - set(SWITCHES))
+    lib = lib or _lib.load()
+    try:
+        for name, v in given.items():
+            rc = getattr(lib, SWITCHES[name][0])(v)
+            assert name != "bf16" or rc == 0, rc
+        yield
+    finally:
+        for name in given:
+            getattr(lib, SWITCHES[name][0])(SWITCHES[name][1])
 
 
 def _p(t):

@@ -17,7 +17,7 @@ from crossscore_amd import synth  # noqa: E402
 from crossscore_amd.config import load_config, model_config  # noqa: E402
 from crossscore_amd.model import CrossScoreNet  # noqa: E402
 from oracle import crossscore_oracle as orc  # noqa: E402
-from test_hip_forward import MAE_TARGET, MAE_TOL, MAX_TOL, _check_compact, _net  # noqa: E402
+from nets import MAE_TARGET, MAE_TOL, MAX_TOL, check_compact, make_net  # noqa: E402
 
 VITS, VITB = "facebook/dinov2-small", "facebook/dinov2-base"
 
@@ -43,7 +43,7 @@ def test_cfg2_bf16_operands_at_batch8(seed):
     default is fp16) -- on two seeds: every item of the batch is bit-identical to the same item scored alone (batch invariance in this operand
     mode too), and items 0, 3 and 7 are held to north_star's MAE < 1e-3 against the fp32 oracle on the host.  The measured MAEs are printed:
     DESIGN.md 2 states the margin to the bound (r5 measured 7.6e-4 on seed 1, item 0)."""
-    net, arch, sd = _net(VITS, seed)
+    net, arch, sd = make_net(VITS, seed)
     net.operand_dtype = "bf16"
     q, r = synth.make_inputs_shard(0, 8, 5, 518, 518, seed)
     score = _run(net, q, r)
@@ -65,11 +65,11 @@ def test_cfg3_vitb_10refs_batch8(golden_dir):
     """BASELINE configs[2]: ViT-B/14, 518x518, 10 refs, bs=8 (I = 88 images, cross-attention Lk = 13 690, decoder dh = 96)."""
     g = np.load(os.path.join(golden_dir, "g2_vitb_518_n10.npz"))
     seed = int(g["seed"])
-    net, arch, sd = _net(VITB, seed)
+    net, arch, sd = make_net(VITB, seed)
     q, r = synth.make_inputs_shard(0, 8, 10, 518, 518, seed)
     score = _run(net, q, r)
     assert score.shape == (8, 518, 518)
-    mae_rows, mae_grid, dmean = _check_compact(g, score[:1])  # item 0 = the reference's own golden
+    mae_rows, mae_grid, dmean = check_compact(g, score[:1])  # item 0 = the reference's own golden
     assert mae_rows < MAE_TARGET and mae_grid < MAE_TARGET and dmean < 1e-4, (mae_rows, mae_grid, dmean)
     one = _run(net, q[:1], r[:1])
     assert torch.equal(one[0], score[0])  # the same item alone: bitwise
@@ -82,12 +82,12 @@ def test_cfg3_shape_vitb_bf16_operands_vs_reference_golden(golden_dir):
     golden g2, inside north_star's 1e-3 (VERDICT r3 weak #2)."""
     g = np.load(os.path.join(golden_dir, "g2_vitb_518_n10.npz"))
     seed = int(g["seed"])
-    net, arch, sd = _net(VITB, seed)
+    net, arch, sd = make_net(VITB, seed)
     net.operand_dtype = "bf16"
     q, r = synth.make_inputs_shard(0, 1, 10, 518, 518, seed)
     score = _run(net, q, r)
     assert net.nonfinite_count() == 0
-    mae_rows, mae_grid, dmean = _check_compact(g, score)
+    mae_rows, mae_grid, dmean = check_compact(g, score)
     print(f"cfg-3 shape, bf16 operands vs g2: MAE rows {mae_rows:.2e} grid {mae_grid:.2e} mean diff {dmean:.2e}")
     assert mae_rows < MAE_TOL and mae_grid < MAE_TOL and dmean < 1e-3, (mae_rows, mae_grid, dmean)
 
@@ -97,7 +97,7 @@ def test_cfg4_vitb_5refs_vs_oracle_and_16_per_gpu():
     then one rank's 16 items: the first two must be bit-identical to the B=2 forward (shard-equivalence: concatenated shard outputs
     == single-GPU output), and the batch is permutation-equivariant."""
     seed = 4
-    net, arch, sd = _net(VITB, seed)
+    net, arch, sd = make_net(VITB, seed)
     q, r = synth.make_inputs_shard(0, 16, 5, 518, 518, seed)
     s2 = _run(net, q[:2], r[:2])
     torch.set_num_threads(min(os.cpu_count() or 1, 32))
@@ -118,11 +118,11 @@ def test_cfg5_1036_batch2(golden_dir):
     """BASELINE configs[4]: 1036x1036 query, 5 refs, bs=2 (T = 5477 encoder tokens per image, cross-attention 5476 x 27 380)."""
     g = np.load(os.path.join(golden_dir, "g3_vits_1036_n5.npz"))
     seed = int(g["seed"])
-    net, arch, sd = _net(VITS, seed)
+    net, arch, sd = make_net(VITS, seed)
     q, r = synth.make_inputs_shard(0, 2, 5, 1036, 1036, seed)
     score = _run(net, q, r)
     assert score.shape == (2, 1036, 1036)
-    mae_rows, mae_grid, dmean = _check_compact(g, score[:1])
+    mae_rows, mae_grid, dmean = check_compact(g, score[:1])
     assert mae_rows < MAE_TARGET and mae_grid < MAE_TARGET and dmean < 1e-4, (mae_rows, mae_grid, dmean)
     assert torch.equal(_run(net, q[1:], r[1:])[0], score[1])
     _properties(net, q, r, score)
@@ -180,7 +180,7 @@ def test_dinov2_giant_vs_oracle_and_batch_invariance():
     """facebook/dinov2-giant (C = 1536, 40 layers, 24 heads, SwiGLU MLP with 4096 hidden features; decoder heads of 192 channels) -- the backbone
     task/core.py:39-40 would load for model.backbone.from_pretrained=facebook/dinov2-giant.  The real depth at 224 x 224 (256 patches; the fp32
     oracle on the host takes the two images through 40 layers), B=1, N=1 against the oracle, then B=3, N=2: item-wise bitwise invariance."""
-    net, arch, sd = _net("facebook/dinov2-giant", 11)
+    net, arch, sd = make_net("facebook/dinov2-giant", 11)
     assert arch.swiglu and arch.ffn_hidden == 4096 and arch.hidden // arch.dec_heads == 192
     q, r = synth.make_inputs_shard(0, 1, 1, 224, 224, 11)
     score = _run(net, q, r)
@@ -199,7 +199,7 @@ def test_dinov2_giant_vs_oracle_and_batch_invariance():
 def test_dinov2_large_518_vs_oracle_and_batch_invariance():
     """Beyond BASELINE's two backbones: facebook/dinov2-large (C = 1024, 24 layers, 16 heads; decoder heads of 128 channels) at 518x518.
     B=1, N=1 against the fp32 oracle on the host (two images through 24 layers: ~20 s), then B=3, N=2: item-wise bitwise invariance."""
-    net, arch, sd = _net("facebook/dinov2-large", 9)
+    net, arch, sd = make_net("facebook/dinov2-large", 9)
     q, r = synth.make_inputs_shard(0, 1, 1, 518, 518, 9)
     score = _run(net, q, r)
     assert net.nonfinite_count() == 0
@@ -235,5 +235,5 @@ def test_bench_plain_run_dumps_the_last_step(tmp_path, golden_dir):
     s = np.load(out / "score_map_ref_cross.npy")
     assert s.dtype == np.float32 and s.shape == (8, 518, 518) and np.isfinite(s).all()
     g = np.load(os.path.join(golden_dir, "g1_vits_518_n5.npz"))
-    mae_rows, mae_grid, dmean = _check_compact(g, torch.from_numpy(s[:1]))
+    mae_rows, mae_grid, dmean = check_compact(g, torch.from_numpy(s[:1]))
     assert mae_rows < MAE_TARGET and mae_grid < MAE_TARGET and dmean < 1e-4, (mae_rows, mae_grid, dmean)

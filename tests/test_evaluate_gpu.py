@@ -1,6 +1,5 @@
 """Test phase on the GPU: the GT input stage (cs_op_metric_map_u16) against the reference's goldens, the score-vs-GT sums
 (cs_op_score_gt_stats) against numpy fp64, and crossscore_amd.evaluate end to end on the tree of tests/nvs_tree.py."""
-import csv
 import ctypes as C
 import os
 import sys
@@ -14,11 +13,11 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
 
 from nvs_tree import make_tree  # noqa: E402
+from scenes import read_csv_dicts, run_evaluate  # noqa: E402
 
 torch = pytest.importorskip("torch")
 MAPS = os.path.join(HERE, "golden", "n0_nvs_maps.npz")
 MODES = {"ssim_-1_1": 0, "ssim_0_1": 1, "mae": 2, "mse": 3}
-TINY = "synthetic/dinov2-tiny"
 
 
 @pytest.fixture(autouse=True)
@@ -188,29 +187,6 @@ def test_score_gt_stats_kernel():
                                     None) == _lib.CS_ERR_BAD_ARG
 
 
-def _run(tree, tmp_path, name, extra, back=TINY, seed=7):
-    from crossscore_amd import synth
-    from crossscore_amd.config import load_config, model_config
-    from crossscore_amd.evaluate import evaluate
-    from crossscore_amd.model import CrossScoreNet
-
-    arch = CrossScoreNet(model_config(**{"backbone.from_pretrained": back})).arch
-    sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, seed).items()}
-    cfg = load_config("default_test", [f"data.dataset.path={tree}", f"model.backbone.from_pretrained={back}", "this_main.resize_short_side=56",
-                                       "data.dataset.num_gaussians_iters=2", "data.loader.validation.batch_size=4",
-                                       "data.loader.validation.num_workers=2", "data.neighbour_config.deterministic=True",
-                                       f"logger.test.out_dir={tmp_path}/{name}"] + list(extra))
-    cap = []
-    np.random.seed(0)
-    with torch.no_grad():
-        res = evaluate(cfg, state_dict=sd, now="NOW", capture=cap)
-    return res, cap, sd, arch
-
-
-def _read_csv(path):
-    return list(csv.DictReader(open(path)))
-
-
 @pytest.mark.gpu
 def test_evaluate_end_to_end(tree, tmp_path):
     from PIL import Image
@@ -221,7 +197,7 @@ def test_evaluate_end_to_end(tree, tmp_path):
     from crossscore_amd.writers import ScoreMapEncoder
     from oracle import crossscore_oracle as orc
 
-    res, cap, sd, arch = _run(tree, tmp_path, "out", ["logger.test.write.flag.score_map_gt=True"])
+    res, cap, sd, arch = run_evaluate(tree, tmp_path, "out", ["logger.test.write.flag.score_map_gt=True"])
     assert res["version_dir"] == os.path.join("log", "NOW", "test_empty_ckpt", "version_0")
     assert len(cap) == 3 and sum(c["gt"].shape[0] for c in cap) == 12  # 12 items in batches of 4
     # per-batch metrics from the kernel's sums = an fp64 recomputation from the run's own score and GT maps
@@ -233,8 +209,8 @@ def test_evaluate_end_to_end(tree, tmp_path):
         assert row["psnr"] == pytest.approx(-10 * np.log10(np.abs(s - g).mean() ** 2), rel=1e-9)
         assert all(row[k] == pytest.approx(want[k], rel=1e-12) for k in ("loss", "corr", "psnr"))
     # metrics.csv = the batch-size-weighted mean of test_batches.csv
-    m = _read_csv(os.path.join(res["version_dir"], "metrics.csv"))[0]
-    rows = _read_csv(os.path.join(res["out_dir"], "test_batches.csv"))
+    m = read_csv_dicts(os.path.join(res["version_dir"], "metrics.csv"))[0]
+    rows = read_csv_dicts(os.path.join(res["out_dir"], "test_batches.csv"))
     w = np.array([float(r["batch_size"]) for r in rows])
     for col, key in (("loss", "test/loss"), ("corr", "test/corr_cross"), ("psnr", "test/psnr_cross")):
         assert float(m[key]) == pytest.approx((w * np.array([float(r[col]) for r in rows])).sum() / w.sum(), rel=1e-12)
@@ -272,8 +248,8 @@ def test_evaluate_input_paths_give_identical_metrics(tree, tmp_path):
     got = {}
     for cache in (True, False):
         for fused in (True, False):
-            res, cap, _, _ = _run(tree, tmp_path, f"o_{cache}_{fused}", [f"this_main.cache_reference_tokens={cache}",
-                                                                         f"this_main.fused_input_stage={fused}"], back=back)
+            res, cap, _, _ = run_evaluate(tree, tmp_path, f"o_{cache}_{fused}", [f"this_main.cache_reference_tokens={cache}",
+                                                                                 f"this_main.fused_input_stage={fused}"], back=back)
             assert res["input_stage"].startswith("one-pass" if fused else "two-launch")
             got[(cache, fused)] = (res["metrics"], [r for r in res["batches"]], [c["score"] for c in cap])
     base = got[(True, True)]
@@ -285,9 +261,9 @@ def test_evaluate_input_paths_give_identical_metrics(tree, tmp_path):
 @pytest.mark.gpu
 def test_evaluate_nan_gt_and_crop_errors(tree, tmp_path):
     # mae: scene_b has no metric maps -> NaN placeholders -> that batch's values and the epoch values are NaN (not filtered)
-    res, cap, _, _ = _run(tree, tmp_path, "mae", ["model.predict.metric.type=mae", "data.loader.validation.shuffle=False"])
+    res, cap, _, _ = run_evaluate(tree, tmp_path, "mae", ["model.predict.metric.type=mae", "data.loader.validation.shuffle=False"])
     assert np.isnan(res["batches"][-1]["loss"]) and np.isfinite(res["batches"][0]["loss"])
     assert all(np.isnan(v) for v in res["metrics"].values())
     # crop_mode null with sides that are not whole patches: ValueError, as the reference fails in the L1 broadcast
     with pytest.raises(ValueError, match="crop_mode null"):
-        _run(tree, tmp_path, "nocrop", ["this_main.crop_mode=null"])
+        run_evaluate(tree, tmp_path, "nocrop", ["this_main.crop_mode=null"])

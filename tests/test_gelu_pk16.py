@@ -5,37 +5,17 @@ The GPU side of the same claim is tests/test_hip_activations.py: the kernels' ow
 finite 16-bit input and at every hidden position (tests/test_hip_panel.py and tests/test_hip_stages.py see the GELU only through fc2, on
 Gaussian inputs).  The same file holds the expected-value side of the fp32 GELU of the GEMM epilogues (cs_common.h gelu_erf4), modelled here
 in numpy and checked on every finite half and bfloat16 input."""
-import importlib.util
 import os
 import re
 
 import numpy as np
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _tool():
-    spec = importlib.util.spec_from_file_location("gelu_pk16_fit", os.path.join(REPO, "tools", "gelu_pk16_fit.py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
-
-def _kernel_constants():
-    """{name: half value} of pk_gelu_consts() in panel_shared.h (both halves of every packed constant must be equal)."""
-    src = open(os.path.join(REPO, "crossscore_amd", "csrc", "panel_shared.h")).read()  # (shared by panel.hip and panel4.hip since round 6)
-    out = {}
-    for name, hexv in re.findall(r'asm volatile\("[sv]_mov_b32 %0, 0x([0-9a-f]{8})" : "=[sv]"\(k\.(\w+)\)\)', src):
-        name, hexv = hexv, name
-        lo, hi = int(hexv[4:], 16), int(hexv[:4], 16)
-        assert lo == hi, (name, hexv)
-        out[name] = float(np.array([lo], dtype=np.uint16).view(np.float16)[0])
-    return out
+from kernel_data import REPO, gelu_compiled, gelu_kernel_constants, gelu_tool
 
 
 def test_kernel_constants_are_the_fitted_ones_and_the_error_figures_hold():
-    t = _tool()
-    k = _kernel_constants()
+    t = gelu_tool()
+    k = gelu_kernel_constants()
     assert set(k) == {"nk", "c5", "c4", "c3", "c2", "c1", "c0", "vc6"} and k["nk"] == -0.25  # -1 / R, R = 4
     c, fit_err = t.fit()
     assert fit_err < 1.0e-4  # 8.2e-5: minimax fit of -|x| Phi(-|x|) in z on |x| <= 4
@@ -65,7 +45,7 @@ def test_kernel_constants_are_the_fitted_ones_and_the_error_figures_hold():
 
 def test_the_horner_form_of_phi_does_not_survive_half_precision():
     """Why the kernel does not evaluate Phi(x) = 0.5 + x Q(x^2) in halves (the form of the fp32 epilogues, cs_common.h gelu_erf4)."""
-    t = _tool()
+    t = gelu_tool()
     rng = np.random.default_rng(1)
     x = (rng.standard_normal(100000) * 2.0).astype(np.float32).astype(np.float64)
     c, _ = t.fit()
@@ -86,17 +66,13 @@ def _all_finite_bf16():
     return b[np.isfinite(b)]
 
 
-def _compiled(k):
-    return np.asarray([k["c0"], k["c1"], k["c2"], k["c3"], k["c4"], k["c5"], k["vc6"]])
-
-
 def test_packed_half_gelu_on_every_finite_half_input():
     """fp16 operand mode: the eleven instructions on ALL finite half inputs (the linspace above never reaches the denormals, the values beyond
     8 or the largest ones).  Measured: max |e| 1.09e-3 on [-4, 4], 1.22e-4 for x <= -4, relative 3.2e-5 for x >= 4."""
-    t = _tool()
+    t = gelu_tool()
     x = _all_finite_half()
     assert x.size == 63488
-    y = t.kernel_gelu(x, _compiled(_kernel_constants()))
+    y = t.kernel_gelu(x, gelu_compiled(gelu_kernel_constants()))
     e = np.abs(y - t.gelu(x))
     print(f"packed-half GELU, every finite half: max |e| {e[np.abs(x) <= 8].max():.3e} on |x| <= 8, {e[x <= -4].max():.3e} for x <= -4, "
           f"relative {(e[x >= 4] / x[x >= 4]).max():.3e} for x >= 4")
@@ -111,10 +87,10 @@ def test_packed_half_gelu_bf16_mode_on_every_finite_bf16_input():
     """bf16 operand mode (tools/gelu_pk16_fit.py kernel_gelu_bf16: correction term in halves on the half-rounded input, relu and the sum in fp32,
     one bf16 rounding): the fit figure of the fp16 form plus half a bf16 ulp of the result, on ALL finite bfloat16 inputs -- fp32's range is what
     that mode is for, so +-3.4e38 must behave as relu."""
-    t = _tool()
+    t = gelu_tool()
     a = _all_finite_bf16()
     assert a.size == 65280
-    y = t.kernel_gelu_bf16(a, _compiled(_kernel_constants()))
+    y = t.kernel_gelu_bf16(a, gelu_compiled(gelu_kernel_constants()))
     g = t.gelu(a.astype(np.float64))
     e = np.abs(y - g)
     slack = e - (2.5e-3 + 2.0 ** -8 * np.abs(g))
@@ -159,7 +135,7 @@ def test_fp32_gelu_of_the_gemm_epilogues_on_every_finite_16_bit_input():
         |y - gelu(x)| <= 2.1e-4 + 3.1e-5 |gelu(x)|
     2.1e-4 is the header's figure for the fit as evaluated in fp32, 3.1e-5 = 1 - Phi_fit(4.2) the relative slope above the clamp (3.01e-5).
     On all 63 488 finite half and all 65 280 finite bfloat16 inputs (the factor in front of Phi has to be max(x, -4.2), not x, for that)."""
-    t = _tool()
+    t = gelu_tool()
     k = _gelu_erf4_constants()
     for name, x in (("half", _all_finite_half().astype(np.float32)), ("bf16", _all_finite_bf16())):
         g = t.gelu(x.astype(np.float64))

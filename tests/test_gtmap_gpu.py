@@ -29,7 +29,7 @@ sys.path.insert(0, HERE)
 import gtmap_oracle as orc  # noqa: E402
 from guard import guarded_out, poisoned_in  # noqa: E402
 from nvs_tree import make_tree  # noqa: E402
-from test_evaluate_gpu import _read_csv, _run  # noqa: E402
+from scenes import read_csv_dicts, run_evaluate  # noqa: E402
 
 torch = pytest.importorskip("torch")
 SSIM, MAE = 0, 1
@@ -315,8 +315,8 @@ def _pair(trees, tmp_path, tag, extra, back="synthetic/dinov2-small-2l"):
     """evaluate in compute mode on the bare tree and in files mode on the filled one, same weights -> (compute, files) results and captures"""
     bare, filled, _ = trees
     extra = list(extra) + ["logger.test.write.flag.score_map_gt=True"]
-    comp = _run(bare, tmp_path, f"{tag}_compute", extra + ["this_main.gt_metric_maps=compute"], back=back)
-    files = _run(filled, tmp_path, f"{tag}_files", extra + ["this_main.gt_metric_maps=files"], back=back)
+    comp = run_evaluate(bare, tmp_path, f"{tag}_compute", extra + ["this_main.gt_metric_maps=compute"], back=back)
+    files = run_evaluate(filled, tmp_path, f"{tag}_files", extra + ["this_main.gt_metric_maps=files"], back=back)
     assert comp[0]["gt_metric_maps"] == "compute" and files[0]["gt_metric_maps"] == "files"
     return comp, files
 
@@ -331,7 +331,7 @@ def _assert_same_run(comp, files):
         assert np.array_equal(x["score"], y["score"])
         assert np.isfinite(x["gt"]).all()
     assert open(os.path.join(rc["version_dir"], "metrics.csv")).read() == open(os.path.join(rf["version_dir"], "metrics.csv")).read()
-    assert _read_csv(os.path.join(rc["out_dir"], "test_batches.csv")) == _read_csv(os.path.join(rf["out_dir"], "test_batches.csv"))
+    assert read_csv_dicts(os.path.join(rc["out_dir"], "test_batches.csv")) == read_csv_dicts(os.path.join(rf["out_dir"], "test_batches.csv"))
     rel = lambda r: sorted(os.path.relpath(f, r["out_dir"]) for f in r["files"] if f.startswith(r["out_dir"]))  # noqa: E731
     assert rel(rc) == rel(rf) and any(f.startswith(os.path.join("batch", "score_map_gt")) for f in rel(rc))
     for f in rel(rc):
@@ -365,15 +365,15 @@ def test_evaluate_compute_equals_files_for_every_metric_type_at_540x720(trees, t
 def test_compute_mode_scores_a_scene_without_metric_maps(tmp_path):
     """scene_b has no metric_map/: files mode scores it against the placeholder (a zero map: no correlation), compute mode for real."""
     tree = make_tree(tmp_path / "t", scenes=["scene_b"])
-    files, _, _, _ = _run(tree, tmp_path, "files", [])
-    comp, cap, _, _ = _run(tree, tmp_path, "compute", ["this_main.gt_metric_maps=compute"])
+    files, _, _, _ = run_evaluate(tree, tmp_path, "files", [])
+    comp, cap, _, _ = run_evaluate(tree, tmp_path, "compute", ["this_main.gt_metric_maps=compute"])
     assert not np.isfinite(files["metrics"]["test/corr_cross"])
     assert all(np.isfinite(v) for v in comp["metrics"].values())
     assert all(c["gt"].std() > 0 for c in cap)
     assert not os.path.exists(os.path.join(tree, "res_540", "scene_b", "test", "ours_1000", "metric_map"))
     # mae: the placeholder is NaN in files mode
-    files, _, _, _ = _run(tree, tmp_path, "files_mae", ["model.predict.metric.type=mae"])
-    comp, _, _, _ = _run(tree, tmp_path, "compute_mae", ["model.predict.metric.type=mae", "this_main.gt_metric_maps=compute"])
+    files, _, _, _ = run_evaluate(tree, tmp_path, "files_mae", ["model.predict.metric.type=mae"])
+    comp, _, _, _ = run_evaluate(tree, tmp_path, "compute_mae", ["model.predict.metric.type=mae", "this_main.gt_metric_maps=compute"])
     assert all(np.isnan(v) for v in files["metrics"].values()) and all(np.isfinite(v) for v in comp["metrics"].values())
 
 
@@ -388,8 +388,8 @@ def test_a_render_and_a_captured_image_of_different_sizes_raise(tmp_path):
     g = os.path.join(tree, "res_540", "scene_b", "test", "ours_1000", "gt", "frame_00000.png")
     Image.fromarray(np.zeros((60, 80, 3), np.uint8)).save(g)
     with pytest.raises(ValueError, match=r"renders/frame_00000\.png is 60x84 and .*gt/frame_00000\.png is 60x80"):
-        _run(tree, tmp_path, "bad", ["this_main.gt_metric_maps=compute"])
+        run_evaluate(tree, tmp_path, "bad", ["this_main.gt_metric_maps=compute"])
     with pytest.raises(ValueError, match=r"renders/frame_00000\.png is 60x84 and .*gt/frame_00000\.png is 60x80"):
         generate(load_config("default_test", [f"data.dataset.path={tree}"]))
     with pytest.raises(ValueError, match="gt_metric_maps"):
-        _run(tree, tmp_path, "bad2", ["this_main.gt_metric_maps=both"])
+        run_evaluate(tree, tmp_path, "bad2", ["this_main.gt_metric_maps=both"])

@@ -14,9 +14,9 @@ REPO = os.path.dirname(HERE)
 sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
 
+from gt_summary_golden import GOLDEN, golden_rows, read_rows  # noqa: E402
 from nvs_tree import make_tree  # noqa: E402
-from test_evaluate_gpu import _run  # noqa: E402
-from test_gtsum_host import GOLDEN, golden_rows, read_rows  # noqa: E402
+from scenes import run_evaluate  # noqa: E402
 
 torch = pytest.importorskip("torch")
 
@@ -94,7 +94,7 @@ def test_ground_truth_and_predicted_summaries_join(tree, tmp_path, capsys):
     from crossscore_amd import summary as sm
 
     _, path = tree
-    res, _, _, _ = _run(path, tmp_path, "eval", [])
+    res, _, _, _ = run_evaluate(path, tmp_path, "eval", [])
     pred_dir = os.path.join(res["out_dir"], "score_summary")
     assert os.path.exists(os.path.join(pred_dir, "mfr", "gaussian.csv"))
     sg.summarise(os.path.join(path, "res_540"), tmp_path / "gt", num_workers=2)

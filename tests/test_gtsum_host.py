@@ -3,7 +3,6 @@ sums of a frame are formed here with numpy int64 and handed to rows_from_sums.  
 SummaryWriterGroundTruth wrote for the same tree (tests/golden/s0_gt_summary.json, made by tests/golden/make_golden_summary.py), and the reader
 what the reference's SummaryReader returned."""
 import csv
-import json
 import math
 import os
 import re
@@ -18,13 +17,11 @@ REPO = os.path.dirname(HERE)
 sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
 
+from gt_summary_golden import GOLDEN, TOKEN, golden_rows, read_rows  # noqa: E402
 from nvs_tree import make_tree  # noqa: E402
 
 from crossscore_amd import summarise_gt as sg  # noqa: E402
 from crossscore_amd import summary as sm  # noqa: E402
-
-GOLDEN = json.load(open(os.path.join(HERE, "golden", "s0_gt_summary.json")))
-TOKEN = GOLDEN["root_token"]
 
 
 def numpy_sums(ssim_u16, mae_u16):
@@ -41,16 +38,6 @@ def sums_of_files(frames):
         sums.append(numpy_sums(a, b))
         sizes.append(a.shape)
     return sums, sizes
-
-
-def read_rows(path):
-    with open(path, newline="") as f:
-        rows = list(csv.reader(f))
-    return rows[0], rows[1:]
-
-
-def golden_rows(key, root):
-    return [[c.replace(TOKEN, root.lstrip("/")) for c in r] for r in GOLDEN[key]]
 
 
 @pytest.fixture(scope="module")

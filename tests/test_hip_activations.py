@@ -19,12 +19,12 @@ pytestmark = pytest.mark.gpu
 from crossscore_amd import _lib  # noqa: E402
 from oracle import crossscore_oracle as orc  # noqa: E402
 import hip_helpers as hh  # noqa: E402
-from test_gelu_pk16 import _compiled, _kernel_constants, _tool  # noqa: E402
+from bits16 import MODES, bits  # noqa: E402
+from kernel_data import gelu_compiled, gelu_kernel_constants, gelu_tool  # noqa: E402
 
 DEV = "cuda"
 F16, BF16 = torch.float16, torch.bfloat16
 EPIS = {"bias": _lib.EPI_BIAS_F16, "gelu": _lib.EPI_BIAS_GELU_F16, "relu": _lib.EPI_BIAS_RELU_F16, "leaky": _lib.EPI_BIAS_LEAKY_F16}
-DT = pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
 
 
 def _dt(bf16):
@@ -42,32 +42,11 @@ def _finite_sweep(bf16):
     return torch.where(torch.isfinite(v), v, torch.zeros_like(v))
 
 
-def _bits(t):
-    return t.contiguous().view(torch.int16)
-
-
 def _gelu64(x):
     """exact erf GELU in float64 (HF ACT2FN["gelu"]); -inf gives the limit -0"""
     x = x.double()
     g = 0.5 * x * torch.special.erfc(-x / math.sqrt(2.0))
     return torch.where(torch.isinf(x) & (x < 0), torch.zeros_like(x), g)
-
-
-class _Mode:
-    """operand type / GEMM routing of the single-op entry points for a block, put back in any case"""
-
-    def __init__(self, bf16=False, g256=True):
-        self.bf16, self.g256 = bf16, g256
-
-    def __enter__(self):
-        lib = _lib.load()
-        assert lib.cs_debug_set_op_operand_dtype(1 if self.bf16 else 0) == 0
-        lib.cs_debug_gemm256_enable(1 if self.g256 else 0)
-
-    def __exit__(self, *exc):
-        lib = _lib.load()
-        lib.cs_debug_set_op_operand_dtype(0)
-        lib.cs_debug_gemm256_enable(1)
 
 
 # ================================================================================================ a. GEMM epilogues
@@ -100,13 +79,13 @@ def gemm_sweep():
         xs[bf16] = x
         zero = torch.zeros((GN,), device=DEV)
         for g256 in (True, False):
-            with _Mode(bf16, g256):
+            with hh.switches(bf16=bf16, gemm256=g256):
                 for name, epi in EPIS.items():
                     outs[(bf16, g256, name)] = _gemm_run(A, W, zero, epi, bf16)
     return outs, xs
 
 
-@DT
+@MODES
 def test_gemm_bias_relu_leaky_are_exact_on_every_finite_input(gemm_sweep, bf16):
     """bias 0: BIAS returns its input, ReLU max(x, 0), LeakyReLU the operand-type rounding of the fp32 product 0.01f * x below 0 -- bit for bit,
     both kernels.  (-0 comes back as +0: it enters an fp32 sum that starts at the bias +0 and holds the +0 products of the padding columns.)"""
@@ -119,14 +98,14 @@ def test_gemm_bias_relu_leaky_are_exact_on_every_finite_input(gemm_sweep, bf16):
     for g256 in (True, False):
         for name, w in want.items():
             got = outs[(bf16, g256, name)]
-            bad = _bits(got) != _bits(w)
+            bad = bits(got) != bits(w)
             n = int(bad.sum())
             first = [(hex(int(i)), float(got.flatten()[i]), float(w.flatten()[i])) for i in bad.flatten().nonzero().flatten()[:6]]
             print(f"gemm{'256' if g256 else '128'} {name} {'bf16' if bf16 else 'fp16'}: {n} of 65536 patterns differ {first}")
             assert n == 0, (g256, name, n, first)
 
 
-@DT
+@MODES
 @pytest.mark.parametrize("g256", [True, False], ids=["gemm256", "gemm128"])
 def test_gemm_gelu_on_every_finite_input(gemm_sweep, bf16, g256):
     """BIAS_GELU (cs_common.h gelu_erf4) against the float64 erf GELU of the exact input:
@@ -148,12 +127,12 @@ def test_gemm_gelu_on_every_finite_input(gemm_sweep, bf16, g256):
     assert float(y[x < 0].max()) <= 0.0
 
 
-@DT
+@MODES
 def test_gemm_kernels_agree_bit_for_bit_on_every_epilogue(gemm_sweep, bf16):
     """the two GEMM kernels share their epilogue functions and start their accumulators at the bias: the same bits (the header's standing claim)"""
     outs, _ = gemm_sweep
     for name in EPIS:
-        assert torch.equal(_bits(outs[(bf16, True, name)]), _bits(outs[(bf16, False, name)])), name
+        assert torch.equal(bits(outs[(bf16, True, name)]), bits(outs[(bf16, False, name)])), name
 
 
 # fractions of one ulp of the 16-bit type: exact ties, quarter / three-quarter points, near-ties one fp32-representable step to either side
@@ -170,7 +149,7 @@ def _row_ulp(n, bf16):
     return 2.0 ** (max(e, 1) - 15 - 10)
 
 
-@DT
+@MODES
 def test_gemm_bias_rounds_to_nearest_even_at_ties_and_near_ties(bf16):
     """BIAS with fp32 offsets that put W + bias on and next to the rounding ties of the output type: bias[n] = f * ulp(row n), f through
     +-1/2, +-1/4, +-3/4, +-3/8, +-(1/2 +- 2^-13), +-3/2, +-(1/2 + 2^-6); 16 launches rotate the fractions over the rows, so that every binade
@@ -180,13 +159,13 @@ def test_gemm_bias_rounds_to_nearest_even_at_ties_and_near_ties(bf16):
     x32 = x.float()
     worst = 0
     for g256 in (True, False):
-        with _Mode(bf16, g256):
+        with hh.switches(bf16=bf16, gemm256=g256):
             for t in range(16):
                 b64 = torch.tensor([_TIE_FRACTIONS[(n + t) % 16] * _row_ulp(n, bf16) for n in range(GN)], dtype=torch.float64)
                 bias = b64.float() + 0.0   # (an offset that underflows becomes +0, never -0: the sum of the padding columns holds +0)
                 got = _gemm_run(A, W, bias.to(DEV), _lib.EPI_BIAS_F16, bf16)
                 want = (x32 + bias[:, None]).to(x.dtype)
-                bad = _bits(got) != _bits(want)
+                bad = bits(got) != bits(want)
                 worst = max(worst, int(bad.sum()))
                 first = [(hex(int(i)), float(bias[int(i) // 256]), float(got.flatten()[i]), float(want.flatten()[i])) for i in bad.flatten().nonzero().flatten()[:6]]
                 assert not bad.any(), (g256, t, int(bad.sum()), first)
@@ -203,7 +182,7 @@ def test_gemm_ln_gelu_is_the_same_function(gemm_sweep, g256):
     c = xs[False].flatten()[idx].float()
     A = torch.zeros((M, Cc), dtype=F16, device=DEV)
     W = torch.zeros((N, Cc), dtype=F16, device=DEV)
-    with _Mode(False, g256):
+    with hh.switches(bf16=False, gemm256=g256):
         if g256:   # finalised (mean, rstd) rows, padded to whole 256-row tiles
             ln = torch.zeros((512, 1, 2), device=DEV)
             ln[:, 0, 1] = 1.0
@@ -215,7 +194,7 @@ def test_gemm_ln_gelu_is_the_same_function(gemm_sweep, g256):
         torch.cuda.synchronize()
     want = outs[(False, g256, "gelu")].flatten()[idx]
     out = out.cpu()
-    assert torch.equal(_bits(out), _bits(want[None, :].expand(M, N)))
+    assert torch.equal(bits(out), bits(want[None, :].expand(M, N)))
 
 
 # ================================================================================================ b. the token-panel kernels' packed-half GELU
@@ -228,7 +207,7 @@ def _hi_lo(v, bf16):
     """What panel4.hip makes of an fc1 bias: it enters through the matrix pipe as hi + lo, two values of the operand type (hi = the rounded
     bias, lo = the rounded rest: 22 significant bits in fp16 mode, 16 in bf16 mode); panel.hip starts its accumulators at the fp32 bias itself."""
     v = np.asarray(v, dtype=_f)
-    t = _tool()
+    t = gelu_tool()
     rd = (lambda a: t.rbf16(a).astype(_f)) if bf16 else (lambda a: a.astype(np.float16).astype(_f))
     hi = rd(v)
     return (hi + rd((v - hi).astype(_f))).astype(_f)
@@ -309,16 +288,11 @@ def _panel_run(b1_rows):
 def panel_gelu(request):
     """both coverage sets through one kernel and operand mode: (impl, bf16, b1 rows, kernel outputs of row 0, rows-all-equal flag, emulation)"""
     impl, bf16 = request.param
-    lib = _lib.load()
     rows = np.concatenate([_panel_values(bf16), _panel_edges(bf16)])
-    lib.cs_debug_panel_impl(impl)
-    try:
-        with _Mode(bf16):
-            out = _panel_run(rows)
-    finally:
-        lib.cs_debug_panel_impl(0)
-    t = _tool()
-    c = _compiled(_kernel_constants())
+    with hh.switches(bf16=bf16, gemm256=True, panel_impl=impl):
+        out = _panel_run(rows)
+    t = gelu_tool()
+    c = gelu_compiled(gelu_kernel_constants())
     with np.errstate(over="ignore"):
         emu = t.kernel_gelu_bf16(rows, c) if bf16 else t.kernel_gelu(rows.astype(np.float64), c)
     return impl, bf16, rows, out, emu
@@ -389,7 +363,7 @@ def test_head_activation_on_every_finite_half(act, powp):
     W = sweep[(torch.arange(N * K) % 65536)].view(N, K)
     A = torch.zeros((Np, K), dtype=F16)
     A[torch.arange(Np), torch.arange(Np)] = 1.0
-    with _Mode(False):
+    with hh.switches(bf16=False, gemm256=True):
         score, mean, cnt = hh.head_score(A.to(DEV), W.to(DEV), torch.zeros((N,), device=DEV), 1, gh, gw, P, act=act, powp=powp)
         torch.cuda.synchronize()
     x = W.double().t().contiguous()                      # (patch m, column n)
@@ -418,7 +392,7 @@ def test_head_activation_on_every_finite_half(act, powp):
 
 
 # ================================================================================================ d. the SwiGLU gate
-@DT
+@MODES
 def test_silu_mul_on_every_finite_input(bf16):
     """cs_op_silu_mul with x1 through every finite pattern of the operand type and x2 = 1, -1, 0.5: test_silu_mul's tolerance (one rounding of an
     fp32 evaluation + half an ulp of the 16-bit output), finite everywhere (the exp overflows for x1 < -88), exactly 0 from -100 downwards"""
@@ -429,11 +403,11 @@ def test_silu_mul_on_every_finite_input(bf16):
     for m, v in enumerate((1.0, -1.0, 0.5)):
         x[m, F:] = v
     buf = x.view(F16).to(DEV)
-    with _Mode(bf16):
+    with hh.switches(bf16=bf16, gemm256=True):
         hh.silu_mul(buf)
         torch.cuda.synchronize()
     out = buf.cpu().view(dt)
-    assert torch.equal(_bits(out[:, F:]), _bits(x[:, F:]))
+    assert torch.equal(bits(out[:, F:]), bits(x[:, F:]))
     x1, x2 = x[:, :F].double(), x[:, F:].double()
     ref = x1 / (1.0 + torch.exp(-x1)) * x2
     o = out[:, :F].double()

@@ -12,8 +12,10 @@ import numpy as np
 import pytest
 import torch
 
-from crossscore_amd import _lib  # noqa: E402
 import hip_helpers as hh  # noqa: E402
+import bits16 as b16  # noqa: E402
+from bits16 import rng, to_dev  # noqa: E402
+from kernel_data import attn_code, attn_ref  # noqa: E402
 
 DEV = "cuda"
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,52 +26,6 @@ LKS = (1, 15, 16, 17, 26, 31, 32, 33, 47, 48, 49, 63, 64, 65, 1370)
 LQS = (1, 16, 17, 90, 112, 113, 128, 129, 1370)
 
 
-class _OpDtype:
-    """cs_debug_set_op_operand_dtype for the duration of a block, restored in any case"""
-
-    def __init__(self, bf16):
-        self.bf16 = bf16
-
-    def __enter__(self):
-        assert _lib.load().cs_debug_set_op_operand_dtype(1 if self.bf16 else 0) == 0
-
-    def __exit__(self, *exc):
-        _lib.load().cs_debug_set_op_operand_dtype(0)
-
-
-def _rd(bf16):
-    return (lambda t: t.to(torch.bfloat16).view(F16)) if bf16 else (lambda t: t.to(F16))
-
-
-def _fl(bf16):
-    return (lambda t: t.view(torch.bfloat16).float()) if bf16 else (lambda t: t.float())
-
-
-def _rng(seed):
-    return np.random.Generator(np.random.PCG64(seed))
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
-
-
-def _attn_ref(Q, K, V, heads, dh):
-    """fp32 reference for a Q that carries log2(e)/sqrt(dh) already (hip_helpers.prescale_q): natural-log logits are q.k * ln 2"""
-    B, Lq, _ = Q.shape
-    Lk = K.shape[1]
-    q = Q.float().view(B, Lq, heads, dh).transpose(1, 2)
-    k = K.float().view(B, Lk, heads, dh).transpose(1, 2)
-    v = V.float().view(B, Lk, heads, dh).transpose(1, 2)
-    s = (q @ k.transpose(-1, -2)) * math.log(2.0)
-    p = torch.softmax(s, dim=-1)
-    return (p @ v).transpose(1, 2).reshape(B, Lq, heads * dh), torch.logsumexp(s, dim=-1)
-
-
-def _code(i, nbits=11):
-    """11-bit codes in +-16: q.k is maximal (11 * 256) for the matching key only, 512 less for the nearest other one"""
-    return (((i[..., None] >> torch.arange(nbits, device=DEV)) & 1).float() * 2 - 1) * 16
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
 @pytest.mark.parametrize("dh", [64, 48])
@@ -77,18 +33,18 @@ def test_one_hot_layout_every_position_and_every_ragged_shape(dh, bf16):
     """One-hot softmax: O[q] == V[key(q)] exactly.  Batch item b selects key (37 q + 11 + b) mod Lk for query q, and there are min(64, Lk) batch
     items, so EVERY query row (both query tiles of a wave, all four waves, every block) hits 64 consecutive keys = every position of a 64-key tile,
     for each Lq x Lk of the grid.  The losing keys are at least 2^-92 down: nothing of them survives the fp32 sums."""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     bad = []
-    with _OpDtype(bf16):
+    with hh.switches(bf16=bf16):
         for Lk in LKS:
             B = min(64, Lk)
             K = torch.zeros((B, Lk, dh), device=DEV)
-            K[:, :, :11] = _code(torch.arange(Lk, device=DEV))[None]
+            K[:, :, :11] = attn_code(torch.arange(Lk, device=DEV))[None]
             V = (torch.arange(Lk * dh, device=DEV).float().view(1, Lk, dh) * 7 % 251 - 125).expand(B, Lk, dh).contiguous()  # exact in 16 bits
             for Lq in LQS:
                 sel = (torch.arange(Lq, device=DEV)[None, :] * 37 + 11 + torch.arange(B, device=DEV)[:, None]) % Lk  # (B, Lq)
                 Q = torch.zeros((B, Lq, dh), device=DEV)
-                Q[:, :, :11] = _code(sel)
+                Q[:, :, :11] = attn_code(sel)
                 O = hh.attention(rd(Q), rd(K), rd(V), 1, dh)  # raw Q: the kernel applies log2(e)/sqrt(dh) itself
                 want = torch.gather(V, 1, sel[:, :, None].expand(B, Lq, dh))
                 err = float((fl(O) - want).abs().max())
@@ -109,16 +65,16 @@ def test_ragged_grid_matches_fp32_with_poison_behind_keys_and_columns(dh, heads)
     poison = torch.tensor([float("nan"), float("inf"), -float("inf"), 65504.0], device=DEV).to(F16)
     bad, worst = [], [0.0, 0.0, 0.0]
     for Lk in LKS:
-        g = _rng(dh * 100 + heads * 10000 + Lk)
+        g = rng(dh * 100 + heads * 10000 + Lk)
         kb = poison[torch.arange(B * (Lk + pad) * (Cc + 16), device=DEV) % 4].view(B, Lk + pad, Cc + 16).clone()
         vb = kb.clone()
-        kb[:, :Lk, :Cc] = _t(1.5 * g.standard_normal((B, Lk, Cc), dtype=np.float32)).to(F16)
-        vb[:, :Lk, :Cc] = _t(g.standard_normal((B, Lk, Cc), dtype=np.float32)).to(F16)
+        kb[:, :Lk, :Cc] = to_dev(1.5 * g.standard_normal((B, Lk, Cc), dtype=np.float32)).to(F16)
+        vb[:, :Lk, :Cc] = to_dev(g.standard_normal((B, Lk, Cc), dtype=np.float32)).to(F16)
         K, V = kb[:, :Lk, :Cc], vb[:, :Lk, :Cc]
         for Lq in LQS:
-            Q = hh.prescale_q(_t(1.5 * g.standard_normal((B, Lq, Cc), dtype=np.float32)).to(F16), dh)
+            Q = hh.prescale_q(to_dev(1.5 * g.standard_normal((B, Lq, Cc), dtype=np.float32)).to(F16), dh)
             O, lse = hh.attention(Q, K, V, heads, dh, lse=True, q_scale=1.0)
-            ref, lse_ref = _attn_ref(Q, K.contiguous(), V.contiguous(), heads, dh)
+            ref, lse_ref = attn_ref(Q, K.contiguous(), V.contiguous(), heads, dh)
             err = (O.float() - ref).abs()
             fig = (float(err.max()), float(err.mean()), float((lse * math.log(2.0) - lse_ref).abs().max()))
             worst = [max(a, b) if b == b else float("nan") for a, b in zip(worst, fig)]
@@ -136,14 +92,14 @@ def test_reference_move_needed_by_one_row_only(dh, bf16):
     """A spike on ONE key for ONE query, late in the key sequence, in each of the four lane groups that share a query row (keys 4 g .. 4 g + 3 of a
     16-key tile) and for a row of either query tile: the move is decided by one lane and must reach all four lanes of that row -- and every row
     of the wave -- by the same amount.  Only dimension 0 carries the spike, so no other (query, key) pair sees it."""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     heads, Lq, Lk = 1, 128, 640
     # fp16: the bounds of test_attention_matches_fp32.  bf16: P and O carry 8 bits instead of 11 (2^3 times the fp16 bound); the statistics are fp32 in both
     tol = (3.2e-2 if bf16 else 4e-3, 5e-4)
-    with _OpDtype(bf16):
+    with hh.switches(bf16=bf16):
         for g4 in range(4):
             for q in (5, 16 + 9, 64 + 3, 96 + 16 + 14):  # query tiles 0 / 1 of waves 0, 0, 2, 3
-                g = _rng(1000 * g4 + q + dh)
+                g = rng(1000 * g4 + q + dh)
                 Q = 0.5 * g.standard_normal((1, Lq, dh), dtype=np.float32)
                 K = 0.5 * g.standard_normal((1, Lk, dh), dtype=np.float32)
                 V = g.standard_normal((1, Lk, dh), dtype=np.float32)
@@ -152,9 +108,9 @@ def test_reference_move_needed_by_one_row_only(dh, bf16):
                 K[:, :, 0] = 0.0
                 Q[0, q, 0] = 4.0
                 K[0, key, 0] = 8.0  # +32 in base-2 units for (q, key) alone: far above kTau = 8
-                Qs, Kb, Vb = rd(_t(Q)), rd(_t(K)), rd(_t(V))  # Q taken as already scaled: q_scale = 1
+                Qs, Kb, Vb = rd(to_dev(Q)), rd(to_dev(K)), rd(to_dev(V))  # Q taken as already scaled: q_scale = 1
                 O, lse = hh.attention(Qs, Kb, Vb, heads, dh, lse=True, q_scale=1.0)
-                ref, lse_ref = _attn_ref(fl(Qs), fl(Kb), fl(Vb), heads, dh)
+                ref, lse_ref = attn_ref(fl(Qs), fl(Kb), fl(Vb), heads, dh)
                 err = float((fl(O) - ref).abs().max())
                 lerr = float((lse * math.log(2.0) - lse_ref).abs().max())
                 assert err < tol[0] and lerr < tol[1], (g4, q, key, err, lerr)
@@ -167,15 +123,15 @@ def test_reference_move_needed_by_one_row_only(dh, bf16):
 def test_rows_are_bitwise_independent_of_their_position(dh, Lk, bf16):
     """The same (Q row, K, V) gives the same bits in any lane, query tile, wave, block and batch item -- also in the wave whose second query tile
     is dead (rows 288..299 of Lq = 300) and which therefore runs the ragged instance of the tile body on every tile."""
-    rd = _rd(bf16)
+    rd = b16.rd(bf16)
     heads, Lq, B = 2, 300, 2
-    g = _rng(dh + Lk)
+    g = rng(dh + Lk)
     Cc = heads * dh
     q1 = 1.5 * g.standard_normal((1, 1, Cc), dtype=np.float32)
-    Q = hh.prescale_q(_t(np.tile(q1, (B, Lq, 1))), dh)
-    K = _t(np.tile(1.5 * g.standard_normal((1, Lk, Cc), dtype=np.float32), (B, 1, 1)))
-    V = _t(np.tile(g.standard_normal((1, Lk, Cc), dtype=np.float32), (B, 1, 1)))
-    with _OpDtype(bf16):
+    Q = hh.prescale_q(to_dev(np.tile(q1, (B, Lq, 1))), dh)
+    K = to_dev(np.tile(1.5 * g.standard_normal((1, Lk, Cc), dtype=np.float32), (B, 1, 1)))
+    V = to_dev(np.tile(g.standard_normal((1, Lk, Cc), dtype=np.float32), (B, 1, 1)))
+    with hh.switches(bf16=bf16):
         O, lse = hh.attention(rd(Q.float()), rd(K), rd(V), heads, dh, lse=True, q_scale=1.0)
     torch.cuda.synchronize()
     Oi = O.view(torch.int16)
@@ -189,8 +145,8 @@ def test_encoder_shape_is_bit_identical_from_run_to_run():
     """cfg-2's encoder launch (48 images x 6 heads, 1370 tokens, dh 64, read in place from the packed [T][3C] projection), twice."""
     dh, heads, T, B = 64, 6, 1370, 48
     Cc = heads * dh
-    g = _rng(2)
-    qkv = _t(g.standard_normal((B, T, 3 * Cc), dtype=np.float32)).to(F16)
+    g = rng(2)
+    qkv = to_dev(g.standard_normal((B, T, 3 * Cc), dtype=np.float32)).to(F16)
     qkv[:, :, :Cc] = hh.prescale_q(1.5 * qkv[:, :, :Cc].float(), dh)
     args = (qkv[:, :, :Cc], qkv[:, :, Cc:2 * Cc], qkv[:, :, 2 * Cc:], heads, dh)
     O1, l1 = hh.attention(*args, lse=True, q_scale=1.0)

@@ -33,7 +33,9 @@ import torch
 from crossscore_amd import _lib  # noqa: E402
 import guard  # noqa: E402
 import hip_helpers as hh  # noqa: E402
-from test_hip_attention_tiles import _OpDtype, _attn_ref, _code, _fl, _rd, _rng, _t  # noqa: E402
+import bits16 as b16  # noqa: E402
+from bits16 import rng, to_dev  # noqa: E402
+from kernel_data import attn_code, attn_ref  # noqa: E402
 
 DEV = "cuda"
 F16 = torch.float16
@@ -61,18 +63,18 @@ def test_one_hot_layout_every_position_and_every_ragged_shape(dh, bf16):
         dh = 16:  32 c = 11.542 -> qs = 11.539 (fp16), 11.5625 (bf16): gap >= 738, peak logit 11 * 32 * 11.5625 = 4070 (harmless in fp32)
     so all losing keys together carry less than 296 * 2^-213 of the weight: nothing of them survives the fp32 sums or shows in a 16-bit output of a
     zero V entry (at +-16 and dh = 192 the gap would be 53 and a bf16 zero would show ~1e-13 on a correct kernel)."""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     bad = []
-    with _OpDtype(bf16):
+    with hh.switches(bf16=bf16):
         for Lk in LKS32:
             B = min(64, Lk)
             K = torch.zeros((B, Lk, dh), device=DEV)
-            K[:, :, :11] = 2 * _code(torch.arange(Lk, device=DEV))[None]
+            K[:, :, :11] = 2 * attn_code(torch.arange(Lk, device=DEV))[None]
             V = (torch.arange(Lk * dh, device=DEV).float().view(1, Lk, dh) * 7 % 251 - 125).expand(B, Lk, dh).contiguous()  # exact in 16 bits
             for Lq in LQS32:
                 sel = (torch.arange(Lq, device=DEV)[None, :] * 37 + 11 + torch.arange(B, device=DEV)[:, None]) % Lk  # (B, Lq)
                 Q = torch.zeros((B, Lq, dh), device=DEV)
-                Q[:, :, :11] = 2 * _code(sel)
+                Q[:, :, :11] = 2 * attn_code(sel)
                 O = hh.attention(rd(Q), rd(K), rd(V), 1, dh)  # raw Q: the kernel applies log2(e)/sqrt(dh) itself
                 want = torch.gather(V, 1, sel[:, :, None].expand(B, Lq, dh))
                 err = float((fl(O) - want).abs().max())
@@ -94,16 +96,16 @@ def test_ragged_grid_matches_fp32_with_poison_behind_keys_and_columns(dh, heads)
     poison = torch.tensor([float("nan"), float("inf"), -float("inf"), 65504.0], device=DEV).to(F16)
     bad, worst, at = [], [0.0, 0.0, 0.0], [None, None, None]
     for Lk in LKS32:
-        g = _rng(dh * 100 + heads * 10000 + Lk)
+        g = rng(dh * 100 + heads * 10000 + Lk)
         kb = poison[torch.arange(B * (Lk + pad) * (Cc + 16), device=DEV) % 4].view(B, Lk + pad, Cc + 16).clone()
         vb = kb.clone()
-        kb[:, :Lk, :Cc] = _t(1.5 * g.standard_normal((B, Lk, Cc), dtype=np.float32)).to(F16)
-        vb[:, :Lk, :Cc] = _t(g.standard_normal((B, Lk, Cc), dtype=np.float32)).to(F16)
+        kb[:, :Lk, :Cc] = to_dev(1.5 * g.standard_normal((B, Lk, Cc), dtype=np.float32)).to(F16)
+        vb[:, :Lk, :Cc] = to_dev(g.standard_normal((B, Lk, Cc), dtype=np.float32)).to(F16)
         K, V = kb[:, :Lk, :Cc], vb[:, :Lk, :Cc]
         for Lq in LQS32:
-            Q = hh.prescale_q(_t(1.5 * g.standard_normal((B, Lq, Cc), dtype=np.float32)).to(F16), dh)
+            Q = hh.prescale_q(to_dev(1.5 * g.standard_normal((B, Lq, Cc), dtype=np.float32)).to(F16), dh)
             O, lse = hh.attention(Q, K, V, heads, dh, lse=True, q_scale=1.0)
-            ref, lse_ref = _attn_ref(Q, K.contiguous(), V.contiguous(), heads, dh)
+            ref, lse_ref = attn_ref(Q, K.contiguous(), V.contiguous(), heads, dh)
             err = (O.float() - ref).abs()
             fig = (float(err.max()), float(err.mean()), float((lse * math.log(2.0) - lse_ref).abs().max()))
             for i in range(3):
@@ -127,18 +129,18 @@ def test_reference_move_needed_by_one_row_only(dh, bf16):
     with Lk = 8 * 64 + 20 and the spike in the live half of the last tile: the move then runs in the LAST instance of the body with two == false.
     Only dimension 0 carries the spike, so no other (query, key) pair sees it; the random part has a standard deviation of 2 base-2 units at every
     head dim (Q is drawn at 0.5 sqrt(64 / dh)), the sibling's."""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     heads, Lq = 1, 128
     # fp16: the bounds of test_attention_matches_fp32.  bf16: P and O carry 8 bits instead of 11 (2^3 times the fp16 bound); the statistics are fp32 in both
     tol = (3.2e-2 if bf16 else 4e-3, 5e-4)
     cases = [(640, 32 * half + off) for half in (0, 1) for off in (9, 22)] + [(8 * 64 + 20, off) for off in (9, 14)]  # off % 8 in {1, 6}
     worst = [0.0, 0.0]
-    with _OpDtype(bf16):
+    with hh.switches(bf16=bf16):
         for Lk, off in cases:
             key = 64 * 8 + off
             assert key % 8 in (1, 6) and key < Lk
             for q in (5, 32 + 30, 64 + 17, 96 + 31):  # one row of each wave
-                g = _rng(1000 * off + q + dh + Lk)
+                g = rng(1000 * off + q + dh + Lk)
                 Q = 0.5 * math.sqrt(64 / dh) * g.standard_normal((1, Lq, dh), dtype=np.float32)
                 K = 0.5 * g.standard_normal((1, Lk, dh), dtype=np.float32)
                 V = g.standard_normal((1, Lk, dh), dtype=np.float32)
@@ -146,9 +148,9 @@ def test_reference_move_needed_by_one_row_only(dh, bf16):
                 K[:, :, 0] = 0.0
                 Q[0, q, 0] = 4.0
                 K[0, key, 0] = 8.0  # +32 in base-2 units for (q, key) alone: far above kTau = 8
-                Qs, Kb, Vb = rd(_t(Q)), rd(_t(K)), rd(_t(V))  # Q taken as already scaled: q_scale = 1
+                Qs, Kb, Vb = rd(to_dev(Q)), rd(to_dev(K)), rd(to_dev(V))  # Q taken as already scaled: q_scale = 1
                 O, lse = hh.attention(Qs, Kb, Vb, heads, dh, lse=True, q_scale=1.0)
-                ref, lse_ref = _attn_ref(fl(Qs), fl(Kb), fl(Vb), heads, dh)
+                ref, lse_ref = attn_ref(fl(Qs), fl(Kb), fl(Vb), heads, dh)
                 err = float((fl(O) - ref).abs().max())
                 lerr = float((lse * math.log(2.0) - lse_ref).abs().max())
                 worst = [max(worst[0], err) if err == err else err, max(worst[1], lerr) if lerr == lerr else lerr]
@@ -166,16 +168,16 @@ def test_lazy_reference_point(dh, step, tiles):
     logits do not depend on dh), same bounds."""
     heads, Lq = 1, 64
     Lk = 64 * tiles
-    g = _rng(int(10 * abs(step)) + tiles + dh)
+    g = rng(int(10 * abs(step)) + tiles + dh)
     u = g.standard_normal(dh).astype(np.float32)
     u /= np.linalg.norm(u)
-    Q = _t(np.tile(u[None, None, :], (1, Lq, 1)) * (1 + 0.05 * g.standard_normal((1, Lq, 1)).astype(np.float32)))  # q.u ~ 1 in base-2 units
+    Q = to_dev(np.tile(u[None, None, :], (1, Lq, 1)) * (1 + 0.05 * g.standard_normal((1, Lq, 1)).astype(np.float32)))  # q.u ~ 1 in base-2 units
     ramp = (np.arange(Lk) // 64).astype(np.float32) * step
-    K = _t(ramp[None, :, None] * u[None, None, :] + 0.3 * g.standard_normal((1, Lk, dh)).astype(np.float32))
-    V = _t(g.standard_normal((1, Lk, dh), dtype=np.float32))
+    K = to_dev(ramp[None, :, None] * u[None, None, :] + 0.3 * g.standard_normal((1, Lk, dh)).astype(np.float32))
+    V = to_dev(g.standard_normal((1, Lk, dh), dtype=np.float32))
     Qs, Kb, Vb = Q.to(F16), K.to(F16), V.to(F16)  # Q taken as already scaled: q_scale = 1
     O, lse = hh.attention(Qs, Kb, Vb, heads, dh, lse=True, q_scale=1.0)
-    ref, lse_ref = _attn_ref(Qs, Kb, Vb, heads, dh)
+    ref, lse_ref = attn_ref(Qs, Kb, Vb, heads, dh)
     torch.cuda.synchronize()
     err, lerr = float((O.float() - ref).abs().max()), float((lse * math.log(2.0) - lse_ref).abs().max())
     print(f"dh {dh} step {step} tiles {tiles}: max {err:.2e} lse {lerr:.2e}")
@@ -189,15 +191,15 @@ def test_lazy_reference_point(dh, step, tiles):
 def test_rows_are_bitwise_independent_of_their_position(dh, Lk, bf16):
     """The same (Q row, K, V) gives the same bits in any lane of either half, wave, block, head-of-grid position and batch item -- also in the wave
     with 12 live rows (288..299 of Lq = 300) beside two dead ones."""
-    rd = _rd(bf16)
+    rd = b16.rd(bf16)
     heads, Lq, B = 2, 300, 2
-    g = _rng(dh + Lk)
+    g = rng(dh + Lk)
     Cc = heads * dh
     q1 = 1.5 * g.standard_normal((1, 1, Cc), dtype=np.float32)
-    Q = hh.prescale_q(_t(np.tile(q1, (B, Lq, 1))), dh)
-    K = _t(np.tile(1.5 * g.standard_normal((1, Lk, Cc), dtype=np.float32), (B, 1, 1)))
-    V = _t(np.tile(g.standard_normal((1, Lk, Cc), dtype=np.float32), (B, 1, 1)))
-    with _OpDtype(bf16):
+    Q = hh.prescale_q(to_dev(np.tile(q1, (B, Lq, 1))), dh)
+    K = to_dev(np.tile(1.5 * g.standard_normal((1, Lk, Cc), dtype=np.float32), (B, 1, 1)))
+    V = to_dev(np.tile(g.standard_normal((1, Lk, Cc), dtype=np.float32), (B, 1, 1)))
+    with hh.switches(bf16=bf16):
         O, lse = hh.attention(rd(Q.float()), rd(K), rd(V), heads, dh, lse=True, q_scale=1.0)
     torch.cuda.synchronize()
     Oi = O.view(torch.int16)
@@ -214,19 +216,19 @@ def test_attention_weights_one_middle_head(dh, bf16):
     ragged shape (Lk = 210: the fourth wave of the only key block has 18 live lanes).  Rows sum to 1 and match the fp32 softmax within 1e-4, the
     bounds of test_attention_weights_one_head; in bf16 too, because the kernel's dot product and the fused kernel's statistics are fp32 on the
     same 16-bit operands.  K is a view with poison rows behind key Lk - 1, which lanes beyond Lk must not read into the output."""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     heads, head, Lq, Lk, B, pad = 3, 1, 70, 210, 2, 70
-    g = _rng(8 + dh)
+    g = rng(8 + dh)
     Cc = heads * dh
-    Q = rd(hh.prescale_q(_t(1.5 * g.standard_normal((B, Lq, Cc), dtype=np.float32)), dh).float())
+    Q = rd(hh.prescale_q(to_dev(1.5 * g.standard_normal((B, Lq, Cc), dtype=np.float32)), dh).float())
     poison = torch.tensor([float("nan"), float("inf"), -float("inf"), 65504.0], device=DEV)
     kb = poison[torch.arange(B * (Lk + pad) * Cc, device=DEV) % 4].view(B, Lk + pad, Cc).clone()
-    kb[:, :Lk] = _t(1.5 * g.standard_normal((B, Lk, Cc), dtype=np.float32))
+    kb[:, :Lk] = to_dev(1.5 * g.standard_normal((B, Lk, Cc), dtype=np.float32))
     kb = rd(kb)
     assert bool(torch.isnan(fl(kb[:, Lk:])).any())
     K = kb[:, :Lk]
-    V = rd(_t(g.standard_normal((B, Lk, Cc), dtype=np.float32)))
-    with _OpDtype(bf16):
+    V = rd(to_dev(g.standard_normal((B, Lk, Cc), dtype=np.float32)))
+    with hh.switches(bf16=bf16):
         _, lse = hh.attention(Q, K, V, heads, dh, lse=True, q_scale=1.0)
         Pw = hh.attention_weights(Q, K, heads, dh, lse, head=head, q_scale=1.0)
     torch.cuda.synchronize()

@@ -4,8 +4,8 @@ values are compared with a high-precision reference of the same operation on the
 kernel's own tiling (see the ids): rows and columns around tile edges, K around the GEMM's residual-prefetch threshold, persistent grids one
 tile short of / at / one past a full round, query and key counts around the attention's 128-query blocks and 64-key tiles."""
 import ctypes as C
+import functools
 import math
-import time
 
 import numpy as np
 import pytest
@@ -17,19 +17,25 @@ from crossscore_amd import _lib  # noqa: E402
 from oracle import crossscore_oracle as orc  # noqa: E402
 import guard  # noqa: E402
 import hip_helpers as hh  # noqa: E402
+import bits16 as b16  # noqa: E402
 from guard import guarded_out, poisoned_in  # noqa: E402
+from kernel_data import row_partials  # noqa: E402
+from nets import make_net  # noqa: E402
+from panel_data import make as panel_make  # noqa: E402
+from panel_data import reference as panel_reference  # noqa: E402
 
 DEV = "cuda"
 F16, F32 = torch.float16, torch.float32
-
+_same = functools.partial(b16.same_bits, by_value=True)  # 16-bit outputs by their bits, fp32 outputs by value (+0 equals -0)
+_wall = b16.Worst("test_hip_bounds")
 
 
 def setup_module(module):
-    module._T0 = time.time()
+    _wall.start()
 
 
 def teardown_module(module):
-    print(f"\ntest_hip_bounds wall time: {time.time() - module._T0:.1f} s")
+    _wall.report()
 
 
 def _ints(rows, cols, a, b, m, off):
@@ -37,44 +43,11 @@ def _ints(rows, cols, a, b, m, off):
     return ((torch.arange(rows, device=DEV)[:, None] * a + torch.arange(cols, device=DEV)[None, :] * b) % m - off).float()
 
 
-def _rd(bf16):
-    return (lambda t: t.to(torch.bfloat16).view(F16)) if bf16 else (lambda t: t.to(F16))
-
-
-def _fl(bf16):
-    return (lambda t: t.view(torch.bfloat16).float()) if bf16 else (lambda t: t.float())
-
-
-class _OpDtype:
-    """cs_debug_set_op_operand_dtype / cs_debug_gemm256_enable for the duration of a block, restored in any case"""
-
-    def __init__(self, bf16=False, gemm256=True):
-        self.bf16, self.g256 = bf16, gemm256
-
-    def __enter__(self):
-        lib = _lib.load()
-        assert lib.cs_debug_set_op_operand_dtype(1 if self.bf16 else 0) == 0
-        lib.cs_debug_gemm256_enable(1 if self.g256 else 0)
-
-    def __exit__(self, *exc):
-        lib = _lib.load()
-        lib.cs_debug_set_op_operand_dtype(0)
-        lib.cs_debug_gemm256_enable(1)
-
-
-def _same(out, ref, what=""):
-    """bit for bit; 16-bit tensors through their integer view (they may carry bfloat16 bits under a half dtype)"""
-    if out.element_size() == 2:
-        assert torch.equal(out.contiguous().view(torch.int16), ref.contiguous().view(torch.int16)), what
-    else:
-        assert torch.equal(out, ref), (what, float((out.double() - ref.double()).abs().max()))
-
-
 # ================================================================================================ GEMM (both kernels)
 def _gemm_case(M, N, K, epi, pad=0, inplace=False, bf16=False, g256=False, random=False):
     """one cs_op_gemm call with poisoned operands (rows K + pad apart), a guarded output (rows N + pad apart) and, for RESID_F32, a poisoned or
     in-place residual; integer operands: compared bit for bit; random ones: against the stated rounding bound"""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     if random:
         g = np.random.Generator(np.random.PCG64(M * 7 + N * 3 + K))
         A0 = rd(torch.from_numpy(g.standard_normal((M, K), dtype=np.float32)).to(DEV))
@@ -90,7 +63,7 @@ def _gemm_case(M, N, K, epi, pad=0, inplace=False, bf16=False, g256=False, rando
     S = fl(A0).double().abs() @ fl(W0).double().abs().t()
     f32 = epi == _lib.EPI_RESID_F32
     resid = None
-    with _OpDtype(bf16, g256):
+    with hh.switches(bf16=bf16, gemm256=g256):
         if f32:
             if inplace:
                 out, chk = guarded_out((M, N), F32, ld=N + pad, init=r)
@@ -190,21 +163,6 @@ def test_gemm256_extents(M, N, K, epi, bf16):
     _gemm_case(M, N, K, _E[epi], 8, epi == "resid" and M % 2 == 1, bf16=bf16, g256=True)
 
 
-def _row_partials(x, sp):
-    """(sum, sumsq) of each row of x over the column ranges the 128-row kernel's (column tile, wave) pairs own"""
-    M, Cc = x.shape
-    tiles = sp // 4
-    bn = Cc // tiles if Cc % 192 == 0 else 128
-    wn = bn // 4
-    out = torch.zeros((M, sp, 2), device=x.device)
-    for t in range(tiles):
-        for w in range(4):
-            seg = x[:, t * bn + w * wn:min(t * bn + w * wn + wn, Cc)]
-            out[:, t * 4 + w, 0] = seg.sum(1)
-            out[:, t * 4 + w, 1] = (seg * seg).sum(1)
-    return out
-
-
 @pytest.mark.parametrize("M,Cc,K,g256", [(1, 384, 256, False), (129, 128, 256, False), (127, 384, 576, False), (257, 768, 384, True),
                                          (513, 512, 512, True)], ids=lambda v: str(v))
 def test_gemm_resid_layernorm_producer_extents(M, Cc, K, g256):
@@ -217,7 +175,7 @@ def test_gemm_resid_layernorm_producer_extents(M, Cc, K, g256):
     x, cx = guarded_out((M, Cc), F32, ld=Cc, init=r)
     x16, c16 = guarded_out((M, Cc), F16)
     st, cst = guarded_out((M, sp, 2), F32)
-    with _OpDtype(False, g256):
+    with hh.switches(bf16=False, gemm256=g256):
         hh.gemm(poisoned_in(A0, ld=K + 8), poisoned_in(W0, ld=K + 8), b, _lib.EPI_RESID_F32_LN, resid=x, out=x, out_f16=x16, stats_out=st)
     cx("x")
     c16("x16")
@@ -225,7 +183,7 @@ def test_gemm_resid_layernorm_producer_extents(M, Cc, K, g256):
     ref = A0.double() @ W0.double().t() + b.double() + r.double()
     _same(x, ref.float(), "x")
     _same(x16, x.half(), "x16")
-    want = _row_partials(x, sp) if not g256 else torch.stack([x.view(M, sp, 64).sum(2), (x * x).view(M, sp, 64).sum(2)], dim=2)
+    want = row_partials(x, sp) if not g256 else torch.stack([x.view(M, sp, 64).sum(2), (x * x).view(M, sp, 64).sum(2)], dim=2)
     assert (st - want).abs().max() <= 2e-5 * float(want.abs().max()), float((st - want).abs().max())  # fp32 sums in another order
 
 
@@ -243,7 +201,7 @@ def test_gemm_layernorm_consumer_extents(M, Cc, N, epi, g256):
     Wp = (Wf * gam[None, :]).half()
     s, c = Wp.float().sum(1), bb + Wf @ bet
     e = _lib.EPI_LN_F16 if epi == "ln" else _lib.EPI_LN_GELU_F16
-    with _OpDtype(False, g256):
+    with hh.switches(bf16=False, gemm256=g256):
         if g256:
             part = torch.stack([x.view(M, Cc // 64, 64).sum(2), (x * x).view(M, Cc // 64, 64).sum(2)], dim=2)
             Mpad = (M + 255) // 256 * 256
@@ -253,7 +211,7 @@ def test_gemm_layernorm_consumer_extents(M, Cc, N, epi, g256):
             assert (stat[M:] == 0).all()
             ln = stat
         else:
-            ln = _row_partials(x, 4 * hh.column_tiles(Cc))
+            ln = row_partials(x, 4 * hh.column_tiles(Cc))
         out, chk = guarded_out((M, N), F16, ld=N + 8)
         hh.gemm(poisoned_in(x.half(), ld=Cc + 8), poisoned_in(Wp, ld=Cc + 8), c, e, out=out, ln_part=ln, col_s=s, ln_eps=1e-6)
         chk("LN consumer out")
@@ -273,7 +231,7 @@ def test_gemm_patch_epilogue_extents(I, gh, gw, pad):
     b = torch.arange(Cc, device=DEV) % 11 - 5.0
     pos = _ints(1 + Np, Cc, 2, 1, 13, 6)
     g = guard.guarded((I * (1 + Np), Cc), F32, ld=Cc + pad)
-    with _OpDtype(False, False):
+    with hh.switches(bf16=False, gemm256=False):
         hh.gemm(poisoned_in(A0, ld=K + pad), poisoned_in(W0, ld=K + pad), b, _lib.EPI_PATCH_F32, out=g.view, pos=pos, Np=Np, K=K)
     g.check("patch out")
     o3 = g.view.unflatten(0, (I, 1 + Np))
@@ -296,7 +254,7 @@ def test_head_score_extents(gh, gw, B):
     part, cp = guarded_out((M, hh.head_sp(P)), F32)
     cnt, cc = guarded_out((B,), torch.int32, init=torch.zeros(B, dtype=torch.int32, device=DEV))
     mean, cm = guarded_out((B,), F32)
-    with _OpDtype(False, False):
+    with hh.switches(bf16=False, gemm256=False):
         hh.head_score(A, W, b, B, gh, gw, P, cnt=cnt, score=score, part=part, mean=mean)
     for chk, what in ((cs, "score"), (cp, "mean_part"), (cc, "counters"), (cm, "mean")):
         chk(what)
@@ -315,7 +273,7 @@ ATTN = [  # (dh, heads, B, Lq, Lk): every head dim, Lq around the 128-query bloc
 
 
 def _attn_case(dh, heads, B, Lq, Lk, bf16):
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     g = np.random.Generator(np.random.PCG64(dh * 1000 + Lq * 7 + Lk))
     Cc = heads * dh
     gap = 3  # rows of poison between batch items
@@ -336,7 +294,7 @@ def _attn_case(dh, heads, B, Lq, Lk, bf16):
     O = og.view[:, :Lq]
     L, cl = guarded_out((B, heads, Lq), F32)
     Pw, cw = guarded_out((B, Lq, Lk), F32)
-    with _OpDtype(bf16):
+    with hh.switches(bf16=bf16, gemm256=True):
         hh.attention(Q, K, V, heads, dh, q_scale=1.0, O=O, L=L)
         hh.attention_weights(Q, K, heads, dh, L, heads - 1, q_scale=1.0, out=Pw)
     og.check("O")
@@ -384,7 +342,7 @@ def test_layernorm_extents(Cc, M, mode):
     want32, want16 = mode in ("both", "f32", "bf16"), mode in ("both", "f16", "bf16")
     of, c32 = guarded_out((M, Cc), F32) if want32 else (None, None)
     ob, c16 = guarded_out((M, Cc), F16) if want16 else (None, None)
-    with _OpDtype(bf16):
+    with hh.switches(bf16=bf16, gemm256=True):
         hh.layernorm(x, gam, bet, 1e-6, want32, want16, of=of, ob=ob)
     ref = torch.nn.functional.layer_norm(x.double(), (Cc,), gam.double(), bet.double(), 1e-6)
     if want32:
@@ -392,11 +350,11 @@ def test_layernorm_extents(Cc, M, mode):
         assert (of.double() - ref).abs().max() < 2e-5
     if want16:
         c16("out_f16")
-        o16 = _fl(bf16)(ob).double()
+        o16 = b16.fl(bf16)(ob).double()
         half = 2.0 ** -8 if bf16 else 2.0 ** -11
         assert ((o16 - ref).abs() <= half * ref.abs() + 2e-5).all()
         if want32:
-            _same(ob, _rd(bf16)(of), "16-bit out = the fp32 out rounded once")
+            _same(ob, b16.rd(bf16)(of), "16-bit out = the fp32 out rounded once")
 
 
 @pytest.mark.parametrize("M,with_resid,inplace", [(1, True, True), (63, False, False), (64, True, False), (65, True, True)], ids=lambda v: str(v))
@@ -438,11 +396,9 @@ def test_linear_layernorm_extents(M, with_resid, inplace):
 @pytest.mark.parametrize("M", [1, 127, 128, 129])
 def test_encoder_panel_extents(M, impl):
     """128 rows per workgroup: x (in place) and u guarded past row M; the packed weight image guarded with both byte sentinels"""
-    from test_hip_panel import _make, _reference
     lib = _lib.load()
-    lib.cs_debug_panel_impl(impl)
-    try:
-        x, o, w = _make(M, 40 + M, torch.device(DEV))
+    with hh.switches(panel_impl=impl):
+        x, o, w = panel_make(M, 40 + M, torch.device(DEV))
         n = lib.cs_panel_image_bytes(1)
         imgs = []
         for s in (guard.SENTINEL[torch.uint8], guard.ALT_SENTINEL[torch.uint8]):
@@ -456,9 +412,7 @@ def test_encoder_panel_extents(M, impl):
         hh.encoder_panel(xk, o, imgs[0], w["bo"], w["b1"], w["b2"], u=u)
         cx("x")
         cu("u")
-    finally:
-        lib.cs_debug_panel_impl(0)
-    ref_x, ref_u = _reference(x, o, w, True, emulate=True)
+    ref_x, ref_u = panel_reference(x, o, w, True, emulate=True)
     assert (xk - ref_x).abs().max() < 4e-3
     assert (u.float() - ref_u).abs().max() < 6e-3
 
@@ -469,7 +423,7 @@ def test_encoder_panel_extents(M, impl):
 def test_silu_mul(F, M, pad, bf16):
     """cs_op_silu_mul against fp64 silu(x1) * x2 rounded once, in place on rows ld >= 2 F apart: the second half of each row and the padding
     are unchanged; x1 far negative (the exp overflow side), +-0 and x2 = 0 included"""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     g = np.random.Generator(np.random.PCG64(F + M))
     x = torch.from_numpy(3.0 * g.standard_normal((M, 2 * F), dtype=np.float32)).to(DEV)
     x[0, :4] = torch.tensor([-100.0, -20000.0, 0.0, -0.0])
@@ -478,7 +432,7 @@ def test_silu_mul(F, M, pad, bf16):
     x[0, F + 6] = -0.0
     x0 = rd(x)
     gbuf = guard.guarded((M, 2 * F), F16, ld=2 * F + pad, init=x0)
-    with _OpDtype(bf16):
+    with hh.switches(bf16=bf16, gemm256=True):
         hh.silu_mul(gbuf.view)
     gbuf.check("silu_mul rows")  # the ld padding of every row and the guards
     out = gbuf.view
@@ -663,13 +617,6 @@ def test_position_tables_extents(gh, gw):
 
 
 # ================================================================================================ forward-level extents and the all-placeholder batch
-def _net(back, seed=3):
-    from crossscore_amd import synth
-    from crossscore_amd.config import model_config
-    from crossscore_amd.model import CrossScoreNet
-    net = CrossScoreNet(model_config(**{"backbone.from_pretrained": back}))
-    net.load_numpy_state_dict(synth.make_state_dict(net.arch, seed))
-    return net.to(DEV)
 
 
 def _vp(t):
@@ -682,7 +629,7 @@ def test_forward_outputs_stay_inside_their_buffers(back):
     guarded buffers; odd B and N, H and W not multiples of 14; the same bits as the unguarded call"""
     from crossscore_amd import synth
     from crossscore_amd.model import U8Batch, U8Image
-    net = _net(back)
+    net = make_net(back, 3, device=DEV)[0]
     lib = _lib.load()
     B, N, H, W, P = 3, 3, 75, 90, 14
     h, w = H // P, W // P
@@ -759,7 +706,7 @@ def test_encode_references_u8_all_placeholders():
     """every image of the batch a placeholder (data NULL; U8Batch.device then comes from the stage): the same bits as cs_encode_references on
     images that hold zero_image_value; ReferenceTokenCache.gather with zero_reference gives the same tokens with from_u8 on and off"""
     from crossscore_amd.data import InputStage, ReferenceTokenCache
-    net = _net("synthetic/dinov2-small-2l")
+    net = make_net("synthetic/dinov2-small-2l", 3, device=DEV)[0]
     stage = InputStage(torch.device(DEV), resize_short_side=56)
     H, W, R = 56, 70, 3
     batch = stage.batch([stage.placeholder((H, W)) for _ in range(R)], (H, W))
@@ -784,13 +731,12 @@ def test_predict_and_evaluate_with_zero_reference_on_the_one_pass_stage(tmp_path
     from crossscore_amd.config import load_config
     from crossscore_amd.predict import predict
     from nvs_tree import make_tree
-    from test_evaluate_gpu import _run
-    from test_predict_driver import _make_scene
+    from scenes import make_scene, run_evaluate
 
     back = "synthetic/dinov2-small-2l"
-    net = _net(back, 6)
+    net = make_net(back, 6, device=DEV)[0]
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(net.arch, 6).items()}
-    qd, rd = _make_scene(str(tmp_path / "data"), n_query=3, n_ref=4, h=70, w=90)
+    qd, rd = make_scene(str(tmp_path / "data"), n_query=3, n_ref=4, h=70, w=90)
     common = [f"data.dataset.query_dir={qd}", f"data.dataset.reference_dir={rd}", f"model.backbone.from_pretrained={back}",
               "this_main.resize_short_side=56", "data.neighbour_config.cross=3", "data.loader.validation.batch_size=2",
               "this_main.cache_reference_tokens=True", "data.dataset.zero_reference=True", "logger.predict.write.config.score_map_colour_mode=gray",
@@ -812,8 +758,8 @@ def test_predict_and_evaluate_with_zero_reference_on_the_one_pass_stage(tmp_path
     tree = make_tree(tmp_path / "nvs")
     got = {}
     for fused in (True, False):
-        res, cap, _, _ = _run(tree, tmp_path, f"z_{fused}", ["this_main.cache_reference_tokens=True", f"this_main.fused_input_stage={fused}",
-                                                            "data.dataset.zero_reference=True"], back=back)
+        res, cap, _, _ = run_evaluate(tree, tmp_path, f"z_{fused}", ["this_main.cache_reference_tokens=True", f"this_main.fused_input_stage={fused}",
+                                                                     "data.dataset.zero_reference=True"], back=back)
         assert res["input_stage"].startswith("one-pass" if fused else "two-launch")
         got[fused] = (res["metrics"], [c["score"] for c in cap])
     assert got[True][0] == got[False][0]

@@ -14,8 +14,8 @@ same rounded operands, and every output under the hook is bit-equal to the defau
 
 The ids name the hand-overs a case contains with 8 blocks: FF / FR / RF / RR = a full (F) or ragged (R) tile followed by a full or ragged one,
 lastF / lastR = what a block's last tile is."""
+import functools
 import math
-import time
 
 import numpy as np
 import pytest
@@ -25,46 +25,34 @@ pytestmark = pytest.mark.gpu
 
 from crossscore_amd import _lib  # noqa: E402
 from oracle import crossscore_oracle as orc  # noqa: E402
+import bits16 as b16  # noqa: E402
 import gemm_walk_data as wd  # noqa: E402
 import hip_helpers as hh  # noqa: E402
+from bits16 import to_dev  # noqa: E402
 from guard import guarded, guarded_out, poisoned_in  # noqa: E402
-from test_hip_bounds import _OpDtype, _fl, _rd, _row_partials, _same  # noqa: E402
+from kernel_data import row_partials  # noqa: E402
+from nets import make_net  # noqa: E402
 
 DEV = "cuda"
 F16, F32 = torch.float16, torch.float32
 GRIDS = (0, 8, 16)  # 0: the default grid (one tile per block at these shapes)
+_same = functools.partial(b16.same_bits, by_value=True)  # 16-bit outputs by their bits, fp32 outputs by value (+0 equals -0)
+_wall = b16.Worst("test_hip_gemm_walk")
 
 
 def setup_module(module):
-    module._T0 = time.time()
+    _wall.start()
 
 
 def teardown_module(module):
-    print(f"\ntest_hip_gemm_walk wall time: {time.time() - module._T0:.1f} s")
-
-
-class _Grid:
-    """cs_debug_gemm_grid for the duration of a block, back to 0 in any case"""
-
-    def __init__(self, blocks):
-        self.blocks = blocks
-
-    def __enter__(self):
-        _lib.load().cs_debug_gemm_grid(self.blocks)
-
-    def __exit__(self, *exc):
-        _lib.load().cs_debug_gemm_grid(0)
-
-
-def _to(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    _wall.report()
 
 
 def _per_grid(run, grids=GRIDS):
     """run() (fresh outputs each time) under each grid -> {blocks: tuple of outputs}"""
     outs = {}
     for blocks in grids:
-        with _Grid(blocks):
+        with hh.switches(grid=blocks):
             outs[blocks] = run()
     torch.cuda.synchronize()
     return outs
@@ -96,16 +84,16 @@ HALF128 = wd.HALF128
 
 
 def _half_case(M, N, K, epi, bf16=False):
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     d = wd.operands(M, N, K)
-    A0, W0, b = rd(_to(d["A"])), rd(_to(d["W"])), _to(d["b"])
+    A0, W0, b = rd(to_dev(d["A"])), rd(to_dev(d["W"])), to_dev(d["b"])
     A, W = poisoned_in(A0, ld=K + 8), poisoned_in(W0, ld=K + 8)
     y = fl(A0).double() @ fl(W0).double().t() + b.double()
     _exact_16bit(y, bf16)
 
     def run():
         out, chk = guarded_out((M, N), F16, ld=N + 8)
-        with _OpDtype(bf16, False):
+        with hh.switches(bf16=bf16, gemm256=False):
             hh.gemm(A, W, b, _E16[epi], out=out)
         chk(f"{epi} out")
         return (out,)
@@ -139,9 +127,9 @@ RESID128 = wd.RESID128
 
 
 def _resid_case(M, N, K, mode, bf16=False, grids=GRIDS):
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     d = wd.operands(M, N, K)
-    A0, W0, b, r = rd(_to(d["A"])), rd(_to(d["W"])), _to(d["b"]), _to(d["r"])
+    A0, W0, b, r = rd(to_dev(d["A"])), rd(to_dev(d["W"])), to_dev(d["b"]), to_dev(d["r"])
     A, W = poisoned_in(A0, ld=K + 8), poisoned_in(W0, ld=K + 8)
     ref = fl(A0).double() @ fl(W0).double().t() + b.double() + (r.double() if mode != "none" else 0.0)
     assert float(ref.abs().max()) < 2 ** 24
@@ -154,7 +142,7 @@ def _resid_case(M, N, K, mode, bf16=False, grids=GRIDS):
         else:
             out, chk = guarded_out((M, N), F32, ld=N + 8)
             resid = rsep
-        with _OpDtype(bf16, False):
+        with hh.switches(bf16=bf16, gemm256=False):
             hh.gemm(A, W, b, _lib.EPI_RESID_F32, resid=resid, out=out)
         chk("resid out")
         return (out,)
@@ -184,9 +172,9 @@ RESID_LN128 = wd.RESID_LN128
 
 
 def _resid_ln_case(M, Cc, K, bf16=False):
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     d = wd.operands(M, Cc, K)
-    A0, W0, b, r = rd(_to(d["A"])), rd(_to(d["W"])), _to(d["b"]), _to(d["r"])
+    A0, W0, b, r = rd(to_dev(d["A"])), rd(to_dev(d["W"])), to_dev(d["b"]), to_dev(d["r"])
     A, W = poisoned_in(A0, ld=K + 8), poisoned_in(W0, ld=K + 8)
     ref = fl(A0).double() @ fl(W0).double().t() + b.double() + r.double()
     sp = 4 * hh.column_tiles(Cc)
@@ -195,7 +183,7 @@ def _resid_ln_case(M, Cc, K, bf16=False):
         x, cx = guarded_out((M, Cc), F32, init=r)
         x16, c16 = guarded_out((M, Cc), F16)
         st, cst = guarded_out((M, sp, 2), F32)
-        with _OpDtype(bf16, False):
+        with hh.switches(bf16=bf16, gemm256=False):
             hh.gemm(A, W, b, _lib.EPI_RESID_F32_LN, resid=x, out=x, out_f16=x16, stats_out=st)
         for c, what in ((cx, "x"), (c16, "x16"), (cst, "stats")):
             c(what)
@@ -205,7 +193,7 @@ def _resid_ln_case(M, Cc, K, bf16=False):
     for blocks, (x, x16, st) in outs.items():
         _same(x, ref.float(), f"x, {blocks} blocks")
         _same(x16, rd(x), f"x16, {blocks} blocks")
-        want = _row_partials(x, sp)
+        want = row_partials(x, sp)
         assert (st - want).abs().max() <= 2e-5 * float(want.abs().max()), (blocks, float((st - want).abs().max()))  # fp32 sums in another order
     _grid_invariant(outs, ("x", "x16", "stats"))
 
@@ -239,15 +227,15 @@ def test_gemm128_walk_layernorm_consumers(M, Cc, N, epi):
     Wp_, s_, c_ = wd.ln_weights(N, Cc)
     part_ = wd.row_partials128(x, wd.bn128(Cc, "wide")).astype(np.float32)  # integers: exact
     assert part_.shape[1] == 4 * hh.column_tiles(Cc) == {128: 4, 384: 8, 768: 16}[Cc]
-    x16, Wp, s, c, part = _to(x).half(), _to(Wp_).half(), _to(s_), _to(c_), _to(part_)
-    assert torch.equal(x16.float(), _to(x)) and torch.equal(Wp.float(), _to(Wp_))
+    x16, Wp, s, c, part = to_dev(x).half(), to_dev(Wp_).half(), to_dev(s_), to_dev(c_), to_dev(part_)
+    assert torch.equal(x16.float(), to_dev(x)) and torch.equal(Wp.float(), to_dev(Wp_))
     A, W = poisoned_in(x16, ld=Cc + 8), poisoned_in(Wp, ld=Cc + 8)
     e = _lib.EPI_LN_F16 if epi == "ln" else _lib.EPI_LN_GELU_F16
     eps = 1e-6
 
     def run():
         out, chk = guarded_out((M, N), F16, ld=N + 8)
-        with _OpDtype(False, False):
+        with hh.switches(bf16=False, gemm256=False):
             hh.gemm(A, W, c, e, out=out, ln_part=part, col_s=s, ln_eps=eps)
         chk("LN consumer out")
         return (out,)
@@ -266,7 +254,7 @@ def test_gemm128_walk_layernorm_consumers(M, Cc, N, epi):
         ref = orc.gelu_erf(pre.float().cpu()).double().to(DEV)
         tail = torch.where(pre.abs() > 4.2, 1.3e-4 * pre.abs(), torch.zeros_like(pre))
         tol = 1.13 * bound + 3e-4 + tail + 2.0 ** -11 * ref.abs() + 2.0 ** -25
-    true = torch.nn.functional.layer_norm(_to(x).double(), (Cc,), None, None, eps) @ Wp.double().t() + c.double()
+    true = torch.nn.functional.layer_norm(to_dev(x).double(), (Cc,), None, None, eps) @ Wp.double().t() + c.double()
     if epi != "ln":
         true = orc.gelu_erf(true.float().cpu()).double().to(DEV)
     for blocks, (out,) in outs.items():
@@ -282,11 +270,11 @@ def test_gemm128_walk_layernorm_consumers(M, Cc, N, epi):
 def _patch_case(pc, with_stats, bf16=False):
     """19 images of 63 patches (M = 1197: 10 row panels, image boundaries inside tiles); N = 384 (192-column tiles), K = 640, and N = 136
     (128 + 8 columns: ragged tiles followed by full ones), K = 128"""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     I, Np, Cc, K = (pc[k] for k in ("I", "Np", "Cc", "K"))
     M, T = I * Np, 1 + Np
     d = wd.operands(M, Cc, K)
-    A0, W0, b, pos = rd(_to(d["A"])), rd(_to(d["W"])), _to(d["b"]), _to(wd.pos_rows(Np, Cc))
+    A0, W0, b, pos = rd(to_dev(d["A"])), rd(to_dev(d["W"])), to_dev(d["b"]), to_dev(wd.pos_rows(Np, Cc))
     A, W = poisoned_in(A0, ld=K + 8), poisoned_in(W0, ld=K + 8)
     ref = (fl(A0).double() @ fl(W0).double().t() + b.double()).reshape(I, Np, Cc) + pos[None, 1:].double()
     sp = 4 * hh.column_tiles(Cc)
@@ -295,7 +283,7 @@ def _patch_case(pc, with_stats, bf16=False):
         g = guarded((I * T, Cc), F32)
         g16 = guarded((I * T, Cc), F16) if with_stats else None
         gst = guarded((I * T, sp, 2), F32) if with_stats else None
-        with _OpDtype(bf16, False):
+        with hh.switches(bf16=bf16, gemm256=False):
             hh.gemm(A, W, b, _lib.EPI_PATCH_F32, out=g.view, pos=pos, Np=Np, K=K, out_f16=g16.view if with_stats else None,
                     stats_out=gst.view if with_stats else None)
         g.check("patch out")
@@ -314,7 +302,7 @@ def _patch_case(pc, with_stats, bf16=False):
         _same(o[0], ref.float(), f"patch rows, {blocks} blocks")
         if with_stats:
             _same(o[1], rd(o[0]), f"patch x16, {blocks} blocks")
-            want = _row_partials(o[0].reshape(M, Cc), sp)
+            want = row_partials(o[0].reshape(M, Cc), sp)
             got = o[2].reshape(M, sp, 2)
             assert (got - want).abs().max() <= 2e-5 * float(want.abs().max()), (blocks, float((got - want).abs().max()))
     _grid_invariant(outs, ("out", "x16", "stats"))
@@ -332,15 +320,15 @@ def test_gemm128_walk_patch_embed_centred():
     I, H, W, P, Cc = 19, 98, 126, 14, 384
     Np = (H // P) * (W // P)
     g = np.random.Generator(np.random.PCG64(19))
-    x = _to(g.standard_normal((I, 3, H, W), dtype=np.float32) + 0.5)
-    wconv = _to(g.standard_normal((Cc, 3, P, P), dtype=np.float32) / math.sqrt(588))
-    b = _to(g.standard_normal((Cc,), dtype=np.float32))
-    pos = _to(g.standard_normal((1 + Np, Cc), dtype=np.float32))
+    x = to_dev(g.standard_normal((I, 3, H, W), dtype=np.float32) + 0.5)
+    wconv = to_dev(g.standard_normal((Cc, 3, P, P), dtype=np.float32) / math.sqrt(588))
+    b = to_dev(g.standard_normal((Cc,), dtype=np.float32))
+    pos = to_dev(g.standard_normal((1 + Np, Cc), dtype=np.float32))
     ref = torch.nn.functional.conv2d(x.double(), wconv.double(), b.double(), stride=P).flatten(2).transpose(1, 2) + pos[None, 1:].double()
 
     def run():
         gg = guarded((I * (1 + Np), Cc), F32)
-        with _OpDtype(False, False):
+        with hh.switches(bf16=False, gemm256=False):
             hh.patch_embed(x, wconv, b, pos, P, 1, out=gg.view)
         gg.check("patch_embed centred")
         o3 = gg.view.reshape(I, 1 + Np, Cc)
@@ -356,14 +344,14 @@ def test_gemm128_walk_patch_embed_centred():
 # ================================================================================================ 128-row kernel: HEAD_SCORE
 def _head_case(P, act, powp, bf16=False):
     """19 images of 7 x 9 patch rows (M = 1197: images straddle the 128-row tiles, 10 panels); P = 14: column tiles 128 + 68, P = 8: one of 64"""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     gh, gw, B, Cc = (wd.HEAD128[k] for k in ("gh", "gw", "B", "Cc"))
     Np = gh * gw
     M = B * Np
     g = np.random.Generator(np.random.PCG64(P * 10 + act))
-    A0 = rd(_to(g.standard_normal((M, Cc), dtype=np.float32)))
-    W0 = rd(_to(g.standard_normal((P * P, Cc), dtype=np.float32) / math.sqrt(Cc)))
-    b = _to(g.standard_normal((P * P,), dtype=np.float32))
+    A0 = rd(to_dev(g.standard_normal((M, Cc), dtype=np.float32)))
+    W0 = rd(to_dev(g.standard_normal((P * P, Cc), dtype=np.float32) / math.sqrt(Cc)))
+    b = to_dev(g.standard_normal((P * P,), dtype=np.float32))
     A, W = poisoned_in(A0, ld=Cc + 8), poisoned_in(W0, ld=Cc + 8)
     y = fl(A0).double() @ fl(W0).double().t() + b.double()
     y = torch.sigmoid(y) if act == 0 else torch.tanh(y)
@@ -377,7 +365,7 @@ def _head_case(P, act, powp, bf16=False):
         cnt, cc = guarded_out((B,), torch.int32, init=torch.zeros(B, dtype=torch.int32, device=DEV))
         mean, cm = guarded_out((B,), F32)
         mean2, cm2 = guarded_out((B,), F32)
-        with _OpDtype(bf16, False):
+        with hh.switches(bf16=bf16, gemm256=False):
             hh.head_score(A, W, b, B, gh, gw, P, act=act, powp=powp, cnt=cnt, score=score, part=part, mean=mean)
             for chk, what in ((cs, "score"), (cp, "mean_part"), (cc, "counters"), (cm, "mean")):
                 chk(what)
@@ -434,16 +422,16 @@ G256 = wd.G256
 def test_gemm256_walk(M, N, K, epi, bf16):
     """bias / GELU / RESID_F32 (in place, separate) / RESID_F32_LN + cs_op_ln_finalize under 8 and 16 blocks: exact (GELU: the bound of
     test_hip_bounds), bit-equal to the default grid and, for the bias and residual epilogues, to the 128-row kernel"""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     d = wd.operands(M, N, K)
-    A0, W0, b, r = rd(_to(d["A"])), rd(_to(d["W"])), _to(d["b"]), _to(d["r"])
+    A0, W0, b, r = rd(to_dev(d["A"])), rd(to_dev(d["W"])), to_dev(d["b"]), to_dev(d["r"])
     A, W = poisoned_in(A0, ld=K + 8), poisoned_in(W0, ld=K + 8)
     y = fl(A0).double() @ fl(W0).double().t() + b.double()
     rsep = poisoned_in(r, ld=N + 8)
     sp = N // 64
 
     def run(g256=True):
-        with _OpDtype(bf16, g256):
+        with hh.switches(bf16=bf16, gemm256=g256):
             if epi in ("bias", "gelu"):
                 out, chk = guarded_out((M, N), F16, ld=N + 8)
                 hh.gemm(A, W, b, _lib.EPI_BIAS_F16 if epi == "bias" else _lib.EPI_BIAS_GELU_F16, out=out)
@@ -501,17 +489,17 @@ LN256 = wd.LN256
 def test_gemm256_walk_layernorm_consumers(M, Cc, N, epi, bf16):
     """the two LayerNorm-folded consumers of the 256-tile kernel from finalised rows (cs_op_ln_finalize), checked as
     test_gemm256_layernorm_folded_chain checks them, on rows whose statistics differ from row panel to row panel and from row to row"""
-    rd, fl = _rd(bf16), _fl(bf16)
-    x = _to(wd.ln_rows(M, Cc, 256))
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
+    x = to_dev(wd.ln_rows(M, Cc, 256))
     Wp_, s_, c_ = wd.ln_weights(N, Cc)
-    x16, Wp, s, c = rd(x), rd(_to(Wp_)), _to(s_), _to(c_)
-    assert torch.equal(fl(x16), x) and torch.equal(fl(Wp), _to(Wp_))
+    x16, Wp, s, c = rd(x), rd(to_dev(Wp_)), to_dev(s_), to_dev(c_)
+    assert torch.equal(fl(x16), x) and torch.equal(fl(Wp), to_dev(Wp_))
     part = torch.stack([x.view(M, Cc // 64, 64).sum(2), (x * x).view(M, Cc // 64, 64).sum(2)], dim=2)
     A, W = poisoned_in(x16, ld=Cc + 8), poisoned_in(Wp, ld=Cc + 8)
     e = _lib.EPI_LN_F16 if epi == "ln" else _lib.EPI_LN_GELU_F16
 
     def run():
-        with _OpDtype(bf16, True):
+        with hh.switches(bf16=bf16, gemm256=True):
             stat, cstat = guarded_out(((M + 255) // 256 * 256, 1, 2), F32)
             hh.ln_finalize(part, Cc, stat=stat)
             out, chk = guarded_out((M, N), F16, ld=N + 8)
@@ -543,12 +531,12 @@ def test_forward_is_bit_equal_under_the_grid_hook(back):
     """every production epilogue combination through a walk in context: 20 images of 63 patches (10 row panels of 128) with 8 blocks per GEMM
     launch against the default grid, on the same handle (launches are issued live and read the hook each time)"""
     from crossscore_amd import synth
-    from test_hip_bounds import _net
-    net = _net(back)
+
+    net = make_net(back, 3, device=DEV)[0]
     q, r = (torch.from_numpy(a).to(DEV) for a in synth.make_inputs(5, 3, 98, 126, 5))
     outs = {}
     for blocks in (0, 8):
-        with _Grid(blocks):
+        with hh.switches(grid=blocks):
             o = net(q, r, False, 0, False, return_mean=True)
             torch.cuda.synchronize()
             outs[blocks] = (o["score_map_ref_cross"].clone(), o["score_mean_ref_cross"].clone())

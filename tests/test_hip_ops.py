@@ -10,17 +10,15 @@ pytestmark = pytest.mark.gpu
 
 from crossscore_amd import _lib  # noqa: E402
 from oracle import crossscore_oracle as orc  # noqa: E402
+import bits16 as b16  # noqa: E402
 import hip_helpers as hh  # noqa: E402
+from bits16 import rng  # noqa: E402
 
 DEV = "cuda"
 
 
-def _rng(seed):
-    return np.random.Generator(np.random.PCG64(seed))
-
-
 def _t(a, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV).to(dtype)
+    return b16.to_dev(a, dtype)
 
 
 def _bf(x):
@@ -38,7 +36,7 @@ def _same_f16(a, b):
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (300, 384, 384), (1370, 1152, 384), (257, 196 + 60, 128), (65, 1536, 384),
                                    (1000, 384, 1536), (2740, 2304, 768), (65760, 1152, 384), (5000, 136, 256), (16440, 384, 128)])
 def test_gemm_bias_f16(M, N, K):
-    g = _rng(M + N + K)
+    g = rng(M + N + K)
     A = _bf(_t(g.standard_normal((M, K), dtype=np.float32)))
     W = _bf(_t(g.standard_normal((N, K), dtype=np.float32) / math.sqrt(K)))
     b = _t(g.standard_normal((N,), dtype=np.float32))
@@ -65,7 +63,7 @@ def test_gemm_exact_integer_layout():
 @pytest.mark.parametrize("epi", [_lib.EPI_BIAS_GELU_F16, _lib.EPI_BIAS_RELU_F16, _lib.EPI_BIAS_LEAKY_F16])
 def test_gemm_activations(epi):
     M, N, K = 513, 384, 384
-    g = _rng(epi)
+    g = rng(epi)
     A = _bf(_t(g.standard_normal((M, K), dtype=np.float32)))
     W = _bf(_t(g.standard_normal((N, K), dtype=np.float32) / math.sqrt(K)))
     b = _t(g.standard_normal((N,), dtype=np.float32))
@@ -84,7 +82,7 @@ def test_gemm_resid_f32(M, with_scale, with_resid):
     """x += lambda * (A Wo^T + b): LayerScale is folded into the packed rows of W and into the bias (as cs_finalize does),
     the epilogue is a plain in-place residual add (full-tile fast path and ragged last row panel)."""
     N, K = 384, 1536
-    g = _rng(11 + M)
+    g = rng(11 + M)
     A = _bf(_t(g.standard_normal((M, K), dtype=np.float32)))
     Wf = _t(g.standard_normal((N, K), dtype=np.float32) / math.sqrt(K))
     b = _t(g.standard_normal((N,), dtype=np.float32))
@@ -102,8 +100,6 @@ def test_gemm_resid_f32(M, with_scale, with_resid):
 
 
 # ---- the 256 x 256 x 64-tile kernel (csrc/gemm256.hip): shapes with K >= 384 (six K tiles: ViT-S QKV / decoder K/V), N % 256 == 0, M >= 256 ----
-def _gemm256(on):
-    _lib.load().cs_debug_gemm256_enable(1 if on else 0)
 
 
 def test_gemm256_exact_integer_layout():
@@ -133,23 +129,20 @@ def _gemm256_integer_layout(M, N, K):
                                    (2740, 768, 1536), (513, 256, 640), (700, 4096, 1024),  # (N > 3072: bias read from memory per tile)
                                    (1370, 1280, 384), (10952, 1536, 384), (32880, 1280, 384)])  # K = 384: ViT-S QKV (padded) and decoder K/V
 def test_gemm256_matches_reference_and_small_tile_kernel(M, N, K):
-    g = _rng(M + N + K + 1)
+    g = rng(M + N + K + 1)
     A = _bf(_t(g.standard_normal((M, K), dtype=np.float32)))
     W = _bf(_t(g.standard_normal((N, K), dtype=np.float32) / math.sqrt(K)))
     b = _t(g.standard_normal((N,), dtype=np.float32))
     r = _t(g.standard_normal((M, N), dtype=np.float32))
-    try:
-        outs = {}
-        for on in (True, False):
-            _gemm256(on)
+    outs = {}
+    for on in (True, False):
+        with hh.switches(gemm256=on):
             o16 = hh.gemm(A, W, b, _lib.EPI_BIAS_F16)
             og = hh.gemm(A, W, b, _lib.EPI_BIAS_GELU_F16)
             x = r.clone()
             o32 = hh.gemm(A, W, b, _lib.EPI_RESID_F32, resid=x, out=x)
             torch.cuda.synchronize()
             outs[on] = (o16, og, o32)
-    finally:
-        _gemm256(True)
     y = A.float() @ W.float().t() + b
     for on in (True, False):
         o16, og, o32 = outs[on]
@@ -167,9 +160,7 @@ def test_gemm256_matches_reference_and_small_tile_kernel(M, N, K):
 def test_ops_in_bf16_operand_mode():
     """The single-op entry points with bfloat16 operands (cs_debug_set_op_operand_dtype(1)): both GEMM kernels exact on small integers (which
     bf16 holds exactly), bias + GELU / residual epilogues and attention against fp32 references at bf16 tolerances."""
-    lib = _lib.load()
-    assert lib.cs_debug_set_op_operand_dtype(1) == 0
-    try:
+    with hh.switches(bf16=True):
         for (M, N, K) in ((300, 384, 256), (700, 512, 1024)):  # 128-row kernel / 256 x 256 x 64-tile kernel
             A = ((torch.arange(M, device=DEV)[:, None] * 5 + torch.arange(K, device=DEV)[None, :] * 3) % 7 - 3.0)
             W = ((torch.arange(N, device=DEV)[:, None] * 3 + torch.arange(K, device=DEV)[None, :] * 7) % 5 - 2.0)
@@ -177,7 +168,7 @@ def test_ops_in_bf16_operand_mode():
             out = hh.gemm(A.to(torch.bfloat16).view(torch.float16), W.to(torch.bfloat16).view(torch.float16), b, _lib.EPI_RESID_F32)
             torch.cuda.synchronize()
             assert torch.equal(out, A @ W.t() + b), (M, N, K)
-        g = _rng(77)
+        g = rng(77)
         M, N, K = 1370, 768, 768
         A = _t(g.standard_normal((M, K), dtype=np.float32)).to(torch.bfloat16)
         W = _t(g.standard_normal((N, K), dtype=np.float32) / math.sqrt(K)).to(torch.bfloat16)
@@ -212,8 +203,6 @@ def test_ops_in_bf16_operand_mode():
             torch.cuda.synchronize()
             d = (O.float() - ref).abs()
             assert float(d.max()) < 3e-2 and float(d.mean()) < 3e-3, (dh, float(d.max()), float(d.mean()))
-    finally:
-        lib.cs_debug_set_op_operand_dtype(0)
 
 
 def _row_partials(x, sp):
@@ -237,7 +226,7 @@ def _row_partials(x, sp):
 def test_gemm_layernorm_folded_consumer(M, Cc, N, epi):
     """LN(x) W^T + b computed as rstd*(fp16(x) W'^T - mu*s) + c from the producer's per-row partial sums
     (HF modeling_dinov2.py:365,373 LayerNorm -> query/key/value / fc1)."""
-    g = _rng(M + N)
+    g = rng(M + N)
     x = _t(2.0 * g.standard_normal((M, Cc), dtype=np.float32) + 0.7)           # non-zero row means
     gam = _t(1 + 0.2 * g.standard_normal((Cc,), dtype=np.float32))
     bet = _t(0.1 * g.standard_normal((Cc,), dtype=np.float32))
@@ -263,7 +252,7 @@ def test_gemm_layernorm_folded_consumer(M, Cc, N, epi):
 def test_gemm_resid_producer_emits_bf16_rows_and_partials(M, Cc):
     """RESID_F32_LN: x += A Wo^T + b, plus the fp16 copy of the new rows and their per-(tile, wave) partial sums."""
     K = 256
-    g = _rng(M * 3 + Cc)
+    g = rng(M * 3 + Cc)
     A = _bf(_t(g.standard_normal((M, K), dtype=np.float32)))
     W = _bf(_t(g.standard_normal((Cc, K), dtype=np.float32) / math.sqrt(K)))
     b = _t(g.standard_normal((Cc,), dtype=np.float32))
@@ -289,12 +278,9 @@ def test_gemm256_layernorm_folded_chain(M, Cc, K, bf16):
     """The ViT-B encoder's LayerNorm fold on the 256-tile GEMM (gemm256.hip LN = 2 / 1; HF modeling_dinov2.py:361-380): the residual epilogue
     (x += A Wo^T + b) also emits 16-bit(x) and per-row partial sums over its 64-column wave slices, cs_op_ln_finalize turns them into
     (mean, rstd), and the consuming projection computes LN(x) W^T + b as rstd * (16-bit(x) W'^T - mean * s) + c [+ GELU]."""
-    lib = _lib.load()
-    assert lib.cs_debug_set_op_operand_dtype(1 if bf16 else 0) == 0
-    try:
-        rd = (lambda t: t.to(torch.bfloat16).view(torch.float16)) if bf16 else _bf       # fp32 -> the operand type's bits (carried as uint16 / half)
-        fl = (lambda t: t.view(torch.bfloat16).float()) if bf16 else (lambda t: t.float())
-        g = _rng(M + Cc + K + (7 if bf16 else 0))
+    with hh.switches(bf16=bf16):
+        rd, fl = b16.rd(bf16), b16.fl(bf16)  # fp32 -> the operand type's bits (carried as uint16 / half), and back
+        g = rng(M + Cc + K + (7 if bf16 else 0))
         A = rd(_t(g.standard_normal((M, K), dtype=np.float32)))
         W = rd(_t(g.standard_normal((Cc, K), dtype=np.float32) / math.sqrt(K)))
         b = _t(g.standard_normal((Cc,), dtype=np.float32))
@@ -342,8 +328,6 @@ def test_gemm256_layernorm_folded_chain(M, Cc, K, bf16):
             assert (err <= rel * same.abs() + (4e-3 if bf16 else 1.5e-3)).all(), float((err - rel * same.abs()).max())
             err = (o - true).abs()
             assert err.mean() < (8e-3 if bf16 else 1.2e-3) and err.max() < (0.2 if bf16 else 3e-2), (float(err.mean()), float(err.max()))
-    finally:
-        lib.cs_debug_set_op_operand_dtype(0)
 
 
 @pytest.mark.parametrize("offset", [8.0, 30.0])
@@ -356,7 +340,7 @@ def test_gemm256_layernorm_fold_with_a_row_offset(offset):
         error; beyond it ln_fold = 2 (LayerNorm launches on the fp32 stream) is the setting.  A DINOv2 residual row has |mu| << sigma (sigma is set
         by its outlier channels), which the +-300 channels of test_gemm256_layernorm_folded_chain model."""
     M, Cc, K = 512, 768, 768
-    g = _rng(int(offset) + 901)
+    g = rng(int(offset) + 901)
     A = _bf(_t(g.standard_normal((M, K), dtype=np.float32)))
     W = _bf(_t(g.standard_normal((Cc, K), dtype=np.float32) / math.sqrt(K) * 0.5))
     b = _t(0.1 * g.standard_normal((Cc,), dtype=np.float32))
@@ -392,7 +376,7 @@ def test_gemm_patch_epilogue_and_im2col():
     I, H, W, P, Cc = 3, 75, 90, 14, 128
     gh, gw = H // P, W // P
     Np, T = gh * gw, gh * gw + 1
-    g = _rng(5)
+    g = rng(5)
     x = _t(g.standard_normal((I, 3, H, W), dtype=np.float32))
     wconv = _t(g.standard_normal((Cc, 3, P, P), dtype=np.float32) / math.sqrt(588))
     b = _t(g.standard_normal((Cc,), dtype=np.float32))
@@ -420,7 +404,7 @@ def test_patch_embed_mean_centred_vs_fp32_conv():
     I, H, W, P, Cc = 2, 98, 112, 14, 128
     gh, gw = H // P, W // P
     Np = gh * gw
-    g = _rng(17)
+    g = rng(17)
     yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
     smooth = np.stack([[1.8 * np.sin(xx / (19.0 + 3 * c) + i) + 1.2 * np.cos(yy / (23.0 + c)) + 0.7 * (c - 1) for c in range(3)] for i in range(I)]).astype(np.float32)
     smooth += 0.05 * g.standard_normal(smooth.shape, dtype=np.float32)
@@ -458,7 +442,7 @@ def test_patch_embed_one_launch_matches_two_kernel_path_and_conv(I, H, W, Cc):
     P = 14
     gh, gw = H // P, W // P
     Np = gh * gw
-    g = _rng(1000 + H + W + Cc)
+    g = rng(1000 + H + W + Cc)
     yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
     img = np.stack([[1.8 * np.sin(xx / (19.0 + 3 * c) + i) + 1.2 * np.cos(yy / (23.0 + c)) + 0.7 * (c - 1) for c in range(3)] for i in range(I)]).astype(np.float32)
     img += 0.3 * g.standard_normal(img.shape, dtype=np.float32)
@@ -486,7 +470,7 @@ def test_im2col_cuts_wide_patch_rows_into_runs(gw):
     the cut falls; two patch rows and two images, so a run's offset into the output is checked in both directions."""
     I, H, P, Kp = 2, 28, 14, 640
     W = gw * P + 3  # (trailing pixels past the last whole patch are ignored)
-    x = _t(_rng(gw).standard_normal((I, 3, H, W), dtype=np.float32))
+    x = _t(rng(gw).standard_normal((I, 3, H, W), dtype=np.float32))
     A = hh.im2col(x, P, Kp)
     torch.cuda.synchronize()
     want = x[:, :, :, :gw * P].reshape(I, 3, H // P, P, gw, P).permute(0, 2, 4, 1, 3, 5).reshape(I * (H // P) * gw, 588).half()
@@ -496,7 +480,7 @@ def test_im2col_cuts_wide_patch_rows_into_runs(gw):
 
 def test_patch_embed_one_launch_refuses_what_it_does_not_take():
     """odd row pitch (8-byte loads), C not a multiple of 384, other patch sizes: CS_ERR_BAD_ARG from the op; cs_forward falls back to im2col + GEMM"""
-    g = _rng(5)
+    g = rng(5)
     for (H, W, Cc, P) in ((70, 91, 384, 14), (70, 84, 256, 14)):
         x = _t(g.standard_normal((1, 3, H, W), dtype=np.float32))
         w = _t(g.standard_normal((Cc, 3, P, P), dtype=np.float32))
@@ -509,19 +493,15 @@ def test_patch_embed_one_launch_refuses_what_it_does_not_take():
 def test_patch_embed_one_launch_bf16_operands():
     I, H, W, Cc, P = 2, 518, 518, 384, 14
     Np = (H // P) * (W // P)
-    g = _rng(77)
+    g = rng(77)
     x = _t(g.standard_normal((I, 3, H, W), dtype=np.float32))
     wconv = _t(g.standard_normal((Cc, 3, P, P), dtype=np.float32) / math.sqrt(588))
     b = _t(g.standard_normal((Cc,), dtype=np.float32))
     pos = _t(g.standard_normal((1 + Np, Cc), dtype=np.float32))
-    lib = _lib.load()
-    lib.cs_debug_set_op_operand_dtype(1)
-    try:
+    with hh.switches(bf16=True):
         one = hh.patch_embed_fused(x, wconv, b, pos, P).reshape(I, 1 + Np, Cc)
         two = hh.patch_embed(x, wconv, b, pos, P, 1).reshape(I, 1 + Np, Cc)
         torch.cuda.synchronize()
-    finally:
-        lib.cs_debug_set_op_operand_dtype(0)
     assert (one[:, 1:] - two[:, 1:]).abs().max() < 2e-5
     ref = torch.nn.functional.conv2d(x.double(), wconv.double(), b.double(), stride=P).flatten(2).transpose(1, 2) + pos[None, 1:].double()
     assert (one[:, 1:].double() - ref).abs().mean() < 4e-3  # bfloat16 operands: 8 significant bits
@@ -530,7 +510,7 @@ def test_patch_embed_one_launch_bf16_operands():
 def test_attention_dh96_long_keys():
     """Decoder cross-attention at ViT-B size: dh = 96, Lk = 13 690 (cfg-3: 10 references of 1369 patches), ragged in both directions."""
     dh, heads, Lq, Lk = 96, 8, 300, 13690
-    g = _rng(96)
+    g = rng(96)
     Q = _bf(_t(1.5 * g.standard_normal((1, Lq, heads * dh), dtype=np.float32)))
     K = _bf(_t(1.5 * g.standard_normal((1, Lk, heads * dh), dtype=np.float32)))
     V = _bf(_t(g.standard_normal((1, Lk, heads * dh), dtype=np.float32)))
@@ -551,7 +531,7 @@ def test_head_score_mean_from_the_same_launch(gh, gw, B):
     finisher waves put the arrival counters back to zero), and a launch that finds a counter not at zero is what the contract says it is: wrong."""
     P, Cc = 14, 384
     Np = gh * gw
-    g = _rng(90 + gh)
+    g = rng(90 + gh)
     one = g.standard_normal((Np, Cc), dtype=np.float32)
     rows = np.concatenate([one if b in (0, B - 1) else g.standard_normal((Np, Cc), dtype=np.float32) for b in range(B)])
     A = _bf(_t(rows))
@@ -580,7 +560,7 @@ def test_gemm_head_score_jigsaw(act, powp):
     """sigmoid/tanh (+pow) + jigsaw store (regression_layer.py:26-62, utils/misc/image.py:8-21)."""
     B, gh, gw, P, Cc = 2, 5, 6, 14, 128
     Np = gh * gw
-    g = _rng(9)
+    g = rng(9)
     A = _bf(_t(g.standard_normal((B * Np, Cc), dtype=np.float32)))
     W = _bf(_t(g.standard_normal((P * P, Cc), dtype=np.float32) / math.sqrt(Cc)))
     b = _t(g.standard_normal((P * P,), dtype=np.float32))
@@ -624,7 +604,7 @@ def _attn_ref(Q, K, V, heads, dh, prescaled=True):
     (192, 8, 257, 700, 1), (192, 2, 64, 129, 2),  # dinov2-giant's decoder heads (C = 1536 / 8)
 ])
 def test_attention_matches_fp32(dh, heads, Lq, Lk, B):
-    g = _rng(dh * 1000 + Lq + Lk)
+    g = rng(dh * 1000 + Lq + Lk)
     Cc = heads * dh
     Q = _bf(_t(1.5 * g.standard_normal((B, Lq, Cc), dtype=np.float32)))
     K = _bf(_t(1.5 * g.standard_normal((B, Lk, Cc), dtype=np.float32)))
@@ -643,7 +623,7 @@ def test_attention_raw_q_scaled_in_kernel():
     """q_scale = 0: raw Q, multiplied by log2(e)/sqrt(dh) and rounded to fp16 once more inside the kernel (rel 4.9e-4 of the logits);
     the weights entry rounds the same way, so its rows still sum to one."""
     dh, heads, Lq, Lk, B = 64, 3, 200, 700, 2
-    g = _rng(123)
+    g = rng(123)
     Cc = heads * dh
     Q = _bf(_t(1.5 * g.standard_normal((B, Lq, Cc), dtype=np.float32)))
     K = _bf(_t(1.5 * g.standard_normal((B, Lk, Cc), dtype=np.float32)))
@@ -682,7 +662,7 @@ def test_attention_forces_rescale_branch():
     """Spike in a LATE key tile: the running max jumps there, so the online-softmax rescale of O and l is exercised
     against a full fp32 reference (cdna guide rule 26)."""
     dh, heads, Lq, Lk = 64, 2, 96, 640
-    g = _rng(77)
+    g = rng(77)
     Q = _t(g.standard_normal((1, Lq, heads * dh), dtype=np.float32))
     K = _t(g.standard_normal((1, Lk, heads * dh), dtype=np.float32))
     V = _t(g.standard_normal((1, Lk, heads * dh), dtype=np.float32))
@@ -702,7 +682,7 @@ def test_attention_lazy_reference_point(step, tiles):
     cross it; falling logits never move it.  All three must match the fp32 softmax."""
     dh, heads, Lq = 64, 1, 64
     Lk = 64 * tiles
-    g = _rng(int(10 * abs(step)) + tiles)
+    g = rng(int(10 * abs(step)) + tiles)
     u = g.standard_normal(dh).astype(np.float32)
     u /= np.linalg.norm(u)
     Q = _t(np.tile(u[None, None, :], (1, Lq, 1)) * (1 + 0.05 * g.standard_normal((1, Lq, 1)).astype(np.float32)))  # q.u ~ 1 in base-2 units
@@ -721,7 +701,7 @@ def test_attention_strided_packed_qkv():
     """Reads Q/K/V in place from a packed [tokens][3C] projection, as the encoder does."""
     dh, heads, T, B = 64, 2, 150, 2
     Cc = heads * dh
-    g = _rng(3)
+    g = rng(3)
     qkv = _bf(_t(g.standard_normal((B, T, 3 * Cc), dtype=np.float32)))
     qkv[:, :, :Cc] = hh.prescale_q(qkv[:, :, :Cc], dh)
     O = hh.attention(qkv[:, :, :Cc], qkv[:, :, Cc:2 * Cc], qkv[:, :, 2 * Cc:], heads, dh, q_scale=1.0)
@@ -735,7 +715,7 @@ def test_attention_strided_packed_qkv():
 def test_attention_ignores_poison_behind_the_last_key(dh, heads, Lq, Lk, packed):
     """K / V are views into a larger buffer whose rows behind key Lk-1 hold NaN / Inf bit patterns: the ragged last tile must not
     read them -- a masked key has p = 0, and 0 * NaN would reach O.  Encoder shape (packed [T][3C] projection, 1370 keys) and decoder shapes."""
-    g = _rng(dh + Lk)
+    g = rng(dh + Lk)
     Cc = heads * dh
     pad = 130  # more than one 64-key tile of poison rows
     poison = torch.tensor([float("nan"), float("inf"), -float("inf"), 65504.0], device=DEV).to(torch.float16)
@@ -762,7 +742,7 @@ def test_attention_ignores_poison_behind_the_last_key(dh, heads, Lq, Lk, packed)
 
 def test_attention_weights_one_head():
     dh, heads, Lq, Lk, B = 48, 8, 70, 210, 2
-    g = _rng(8)
+    g = rng(8)
     Cc = heads * dh
     Q = hh.prescale_q(_t(1.5 * g.standard_normal((B, Lq, Cc), dtype=np.float32)), dh)
     K = _bf(_t(1.5 * g.standard_normal((B, Lk, Cc), dtype=np.float32)))
@@ -787,7 +767,7 @@ def test_linear_layernorm_one_launch(M, with_resid):
     """csrc/rowln.hip: LN(x + y W^T + b) as the post-norm decoder layer closes its sub-blocks (transformer.py:157-173; without x when
     decoder_do_short_cut is off), against fp32 torch on the same fp16 operands, and against the two-launch form of the forward (GEMM with the
     fp32 residual epilogue, then the LayerNorm kernel): same operands, fp32 accumulation in another order."""
-    g = _rng(M + 3)
+    g = rng(M + 3)
     Cc = 384
     A = _bf(_t(g.standard_normal((M, Cc), dtype=np.float32)))
     W = _bf(_t(g.standard_normal((Cc, Cc), dtype=np.float32) / math.sqrt(Cc)))
@@ -826,7 +806,7 @@ def test_linear_layernorm_linear_one_launch(M, n2, act2):
     transformer.py:157-210, cross_reference.py:45-50).  Its input is the normalised rows rounded to fp16 -- exactly what the separate GEMM
     reads -- so the reference is built from the one-launch LayerNorm's own fp16 rows: fp32 torch on those and, as the forward's other form,
     the GEMM kernel with the matching epilogue."""
-    g = _rng(M + n2 + act2)
+    g = rng(M + n2 + act2)
     Cc = 384
     A = _bf(_t(g.standard_normal((M, Cc), dtype=np.float32)))
     W = _bf(_t(g.standard_normal((Cc, Cc), dtype=np.float32) / math.sqrt(Cc)))
@@ -865,7 +845,7 @@ def test_linear_layernorm_linear_one_launch(M, n2, act2):
 # ------------------------------------------------------------------------------- LayerNorm & position tables
 @pytest.mark.parametrize("M,Cc,eps", [(1370, 384, 1e-6), (77, 768, 1e-5), (5, 128, 1e-6)])
 def test_layernorm(M, Cc, eps):
-    g = _rng(M)
+    g = rng(M)
     x = _t(3.0 * g.standard_normal((M, Cc), dtype=np.float32) + 1.0)
     gam = _t(1 + 0.2 * g.standard_normal((Cc,), dtype=np.float32))
     bet = _t(0.1 * g.standard_normal((Cc,), dtype=np.float32))
@@ -879,7 +859,7 @@ def test_layernorm(M, Cc, eps):
 @pytest.mark.parametrize("G,gh,gw", [(5, 5, 6), (37, 74, 74), (37, 37, 49), (37, 20, 11)])
 def test_pos_bicubic(G, gh, gw):
     Cc = 64
-    g = _rng(G + gh)
+    g = rng(G + gh)
     pos = _t(g.standard_normal((1 + G * G, Cc), dtype=np.float32))
     out = hh.pos_bicubic(pos, G, gh, gw)
     ref = torch.cat([pos[:1].cpu(), orc.bicubic_resize_grid(pos[1:].cpu().reshape(G, G, Cc), gh, gw).reshape(gh * gw, Cc)])
@@ -908,7 +888,7 @@ def test_pos_bicubic_legacy_matches_torch_scale_factor_golden(tag, backbone, h, 
 @pytest.mark.parametrize("gh,gw", [(37, 37), (5, 6), (74, 74), (37, 49)])
 def test_pe_bilinear(gh, gw):
     Cc = 64
-    g = _rng(gh * gw)
+    g = rng(gh * gw)
     pe = _t(g.standard_normal((40, 40, Cc), dtype=np.float32))
     out = hh.pe_bilinear(pe, gh, gw)
     ref = orc.bilinear_resize_grid_align_corners(pe.cpu(), gh, gw).reshape(gh * gw, Cc)
@@ -920,7 +900,7 @@ def test_pe_bilinear(gh, gw):
 def test_pe_bicubic_mode(gh, gw):
     """model.pos_enc.multi_view.interpolate_mode=bicubic (positional_encoding.py:61-69 with align_corners=True): kernel vs the oracle's
     restatement (itself pinned against torch's F.interpolate in tests/test_oracle_golden.py); mode 0 is the bilinear kernel."""
-    g = _rng(gh * 50 + gw)
+    g = rng(gh * 50 + gw)
     pe = _t(g.standard_normal((40, 40, 96), dtype=np.float32))
     out = hh.pe_interp(pe, gh, gw, 1)
     ref = orc.multiview_pe({"pos_enc_fn.PE": pe.cpu()[None]}, gh, gw, "bicubic")

@@ -4,9 +4,11 @@ LayerScale + residual, and the next layer's norm1 (without gamma / beta)."""
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+import hip_helpers as hh
+from bits16 import bits16, r16, vals16
+from panel_data import C, make, norm, reference
 
-C, F = 384, 1536
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(params=[0, 1], ids=["panel8", "panel4"], autouse=True)
@@ -14,57 +16,22 @@ def panel_impl(request):
     """Both token-panel kernels through every test of this file: csrc/panel.hip (8 waves in role-split pairs) and csrc/panel4.hip (4 waves, one per
     SIMD, column-split residual products).  cs_debug_panel_impl selects the weight image cs_op_panel_pack builds and the kernel
     cs_op_encoder_panel launches."""
-    from crossscore_amd import _lib
-    lib = _lib.load()
-    lib.cs_debug_panel_impl(request.param)
-    yield request.param
-    lib.cs_debug_panel_impl(0)
-
-
-def _bf(t):
-    return t.to(torch.float16).to(torch.float32)
-
-
-def _norm(x, eps=1e-6):
-    mu = x.mean(-1, keepdim=True)
-    var = ((x - mu) ** 2).mean(-1, keepdim=True)
-    return (x - mu) / torch.sqrt(var + eps)
-
-
-def _make(M, seed, dev):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    rn = lambda *s, sc=1.0: (torch.randn(*s, generator=g) * sc).to(dev)
-    x = rn(M, C, sc=2.0)
-    x[:, 7] += 3.0  # a feature with a large mean, as DINOv2 residual streams have
-    o = rn(M, C).to(torch.float16)
-    w = dict(wo=rn(C, C, sc=C ** -0.5), ls1=rn(C, sc=0.3) + 1.0, bo=rn(C, sc=0.1), w1=rn(F, C, sc=C ** -0.5), g2=rn(C, sc=0.2) + 1.0,
-             b1=rn(F, sc=0.5), w2=rn(C, F, sc=F ** -0.5), ls2=rn(C, sc=0.3) + 1.0, b2=rn(C, sc=0.1))
-    return x, o, w
-
-
-def _reference(x, o, w, outproj, emulate):
-    r = _bf if emulate else (lambda t: t)
-    x1 = x.clone()
-    if outproj:
-        x1 = x1 + o.float() @ r(w["wo"] * w["ls1"][:, None]).T + w["bo"]
-    h = torch.nn.functional.gelu(r(_norm(x1)) @ r(w["w1"] * w["g2"][None, :]).T + w["b1"])
-    x2 = x1 + r(h) @ r(w["w2"] * w["ls2"][:, None]).T + w["b2"]
-    return x2, _norm(x2)
+    with hh.switches(panel_impl=request.param):
+        yield request.param
 
 
 @pytest.mark.parametrize("M,outproj", [(128, True), (128, False), (1370, True), (77, True), (4 * 1370 + 5, False), (33, False)])
 def test_panel_vs_torch(M, outproj):
     from crossscore_amd import _lib
-    import hip_helpers as hh
 
     assert _lib.load().cs_panel_supported(C, 4) == 1
     dev = torch.device("cuda:0")
-    x, o, w = _make(M, 10 + M, dev)
+    x, o, w = make(M, 10 + M, dev)
     img = hh.panel_pack(w["wo"] if outproj else None, w["ls1"] if outproj else None, w["w1"], w["g2"], w["w2"], w["ls2"])
     xk = x.clone()
     u = hh.encoder_panel(xk, o if outproj else None, img, w["bo"] if outproj else None, w["b1"], w["b2"])
     torch.cuda.synchronize()
-    ref_x, ref_u = _reference(x, o, w, outproj, emulate=True)
+    ref_x, ref_u = reference(x, o, w, outproj, emulate=True)
     # same fp16 operand roundings as the kernel: what is left is fp32 summation order and the GELU.  Since round 5 the kernel rounds the fc1
     # output to half BEFORE the activation and evaluates GELU's correction term in packed half arithmetic (panel.hip, tools/gelu_pk16_fit.py):
     # per hidden value rms 2.6e-4 / worst 2.1e-3 against the exact GELU (the reference's own 16-mixed arithmetic: rms 2.1e-4), where the fp32
@@ -79,17 +46,15 @@ def test_panel_vs_torch(M, outproj):
     u_err = (u.float() - ref_u).abs().max().item()
     assert u_err < 6e-3, u_err  # fp16 output of O(1..4) values: half an ulp is up to 2e-3
     # against exact fp32 arithmetic the fp16 operand rounding dominates
-    ex_x, _ = _reference(x, o, w, outproj, emulate=False)
+    ex_x, _ = reference(x, o, w, outproj, emulate=False)
     ex_err = (xk - ex_x).abs().mean().item()
     assert ex_err < 1.2e-3, ex_err
 
 
 def test_panel_rows_are_independent():
     """A row's result must not depend on which panel / wave / lane it lands in (bitwise)."""
-    import hip_helpers as hh
-
     dev = torch.device("cuda:0")
-    x, o, w = _make(300, 5, dev)
+    x, o, w = make(300, 5, dev)
     img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
     xa = x.clone()
     ua = hh.encoder_panel(xa, o, img, w["bo"], w["b1"], w["b2"])
@@ -101,10 +66,8 @@ def test_panel_rows_are_independent():
 
 
 def test_panel_bad_arguments():
-    import hip_helpers as hh
-
     dev = torch.device("cuda:0")
-    x, o, w = _make(16, 1, dev)
+    x, o, w = make(16, 1, dev)
     img = hh.panel_pack(None, None, w["w1"], w["g2"], w["w2"], w["ls2"])
     with pytest.raises(ValueError):
         hh.encoder_panel(x, o, img, None, w["b1"], w["b2"])  # out-projection without its bias
@@ -116,17 +79,12 @@ def test_panel_full_chip_launches_repeat_bit_identically_under_concurrent_stream
     forward's lanes and batches in flight run it: every run bit-identical to a launch that had the chip to itself.  The hand-offs between the
     wave pairs (inline-asm LDS writes behind MFMA results, counted waits, unit barriers: ADVICE r4) are timing-sensitive by construction;
     a hazard shows up as a run that differs.  Both operand modes (their GELU hand-offs differ: packed halves / fp32 accumulators)."""
-    from crossscore_amd import _lib
-    import hip_helpers as hh
-
-    lib = _lib.load()
     dev = torch.device("cuda:0")
     M = 48 * 1370
-    x, o, w = _make(M, 21, dev)
-    assert lib.cs_debug_set_op_operand_dtype(1 if bf16 else 0) == 0
-    try:
+    x, o, w = make(M, 21, dev)
+    with hh.switches(bf16=bf16):
         img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
-        ob = o.float().to(torch.bfloat16).view(torch.float16) if bf16 else o
+        ob = bits16(o.float(), bf16)
         x0 = x.clone()
         u0 = hh.encoder_panel(x0, ob, img, w["bo"], w["b1"], w["b2"])
         torch.cuda.synchronize()
@@ -142,11 +100,9 @@ def test_panel_full_chip_launches_repeat_bit_identically_under_concurrent_stream
         for xr, ur in runs:
             assert torch.equal(xr, x0) and torch.equal(ur, u0)
         # and the result is right (fp32 restatement with the same operand roundings; bf16: 8 significant bits)
-        r = (lambda t: t.to(torch.bfloat16).float()) if bf16 else _bf
-        x1 = x[:4096] + ob[:4096].view(torch.bfloat16 if bf16 else torch.float16).float() @ r(w["wo"] * w["ls1"][:, None]).T + w["bo"]
-        hdn = torch.nn.functional.gelu(r(_norm(x1)) @ r(w["w1"] * w["g2"][None, :]).T + w["b1"])
+        r = lambda t: r16(t, bf16)
+        x1 = x[:4096] + vals16(ob[:4096], bf16) @ r(w["wo"] * w["ls1"][:, None]).T + w["bo"]
+        hdn = torch.nn.functional.gelu(r(norm(x1)) @ r(w["w1"] * w["g2"][None, :]).T + w["b1"])
         ref = x1 + r(hdn) @ r(w["w2"] * w["ls2"][:, None]).T + w["b2"]
         err = (x0[:4096] - ref).abs()
         assert float(err.mean()) < (2.4e-3 if bf16 else 3e-4) and float(err.max()) < (3.2e-2 if bf16 else 4e-3), (float(err.mean()), float(err.max()))
-    finally:
-        lib.cs_debug_set_op_operand_dtype(0)

@@ -6,8 +6,8 @@ buffers; b1 and b2 enter through the matrix pipe, split hi + lo; the bf16 instan
 last ticks are instantiations of their own.  Same op entry points (cs_op_panel_pack / cs_op_encoder_panel) behind cs_debug_panel_impl(1); every
 case is one or a few launches of at most 257 rows; every test runs with fp16 and with bf16 operands.
 
-Measured against the fp64 reference on the same rounded operands (_reference64), worst over the cases of the test:
-  test_ragged_rows_at_row_block_granularity (all M, both out-projection settings; bounds: _BOUNDS of test_hip_panel_tiles.py)
+Measured against the fp64 reference on the same rounded operands (panel_data.reference64), worst over the cases of the test:
+  test_ragged_rows_at_row_block_granularity (all M, both out-projection settings; bounds: panel_data.BOUNDS)
     fp16: max |dx| 2.36e-3, mean |dx| 2.83e-4, max |du| 1.96e-3
     bf16: max |dx| 4.85e-3, mean |dx| 3.70e-4, max |du| 1.56e-2
   (the 8-wave kernel's figures on its own row counts, test_hip_panel_tiles.py: 2.36e-3 / 2.83e-4 / 1.95e-3 and 4.63e-3 / 3.69e-4 / 1.56e-2)
@@ -21,36 +21,16 @@ import numpy as np
 import pytest
 import torch
 
-from test_hip_panel_tiles import _BOUNDS, _bits16, _r16, _reference64, _vals16, _zero_weights
+import hip_helpers as hh
+from bits16 import MODES, bits16, r16, vals16
+from guard import guarded_out
+from kernel_data import gelu_compiled, gelu_kernel_constants, gelu_tool
+from panel_data import BOUNDS, C, F, make, reference64, zero_weights
 
 pytestmark = pytest.mark.gpu
 
-C, F = 384, 1536
 HT, NTICK = 64, 24  # hidden units per tick of the MLP loop, ticks
 DEV = "cuda:0"
-BOTH = pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
-
-
-class _mode4:
-    """the four-wave kernel and the operand type for the duration of a block; the 8-wave kernel and fp16 restored in any case"""
-
-    def __init__(self, bf16):
-        self.bf16 = bf16
-
-    def __enter__(self):
-        from crossscore_amd import _lib
-        lib = _lib.load()
-        lib.cs_debug_panel_impl(1)
-        rc = lib.cs_debug_set_op_operand_dtype(1 if self.bf16 else 0)
-        if rc != 0:
-            self.__exit__()
-            raise AssertionError(rc)
-
-    def __exit__(self, *a):
-        from crossscore_amd import _lib
-        lib = _lib.load()
-        lib.cs_debug_panel_impl(0)
-        lib.cs_debug_set_op_operand_dtype(0)
 
 
 def _perm4(i):
@@ -71,17 +51,13 @@ def _nan_backed16(t16, extra=128):
 
 
 def _ragged_case(M, outproj, bf16, want_u=True):
-    """-> (max |dx|, mean |dx|, max |du| or None) of one launch against _reference64.  x and u lie between guard bands of NaN bits (x's rows
+    """-> (max |dx|, mean |dx|, max |du| or None) of one launch against panel_data.reference64.  x and u lie between guard bands of NaN bits (x's rows
     behind M are therefore NaN, as are the attention output's): the kernel clamps its reads to row M - 1 and must neither let those rows in nor
     write to them."""
-    import hip_helpers as hh
-    from guard import guarded_out
-    from test_hip_panel import _make
-
     dev = torch.device(DEV)
-    x, o, w = _make(M, 900 + M, dev)
-    with _mode4(bf16):
-        o16 = _nan_backed16(_bits16(o.float(), bf16))
+    x, o, w = make(M, 900 + M, dev)
+    with hh.switches(bf16=bf16, panel_impl=1):
+        o16 = _nan_backed16(bits16(o.float(), bf16))
         img = hh.panel_pack(w["wo"] if outproj else None, w["ls1"] if outproj else None, w["w1"], w["g2"], w["w2"], w["ls2"])
         xk, cx = guarded_out((M, C), torch.float32, init=x)
         u, cu = guarded_out((M, C), torch.float16) if want_u else (None, None)
@@ -90,10 +66,10 @@ def _ragged_case(M, outproj, bf16, want_u=True):
     cx("x")
     if want_u:
         cu("u")
-    ref_x, ref_u = _reference64(x, _vals16(o16, bf16), w, outproj, bf16)
+    ref_x, ref_u = reference64(x, vals16(o16, bf16), w, outproj, bf16)
     assert torch.isfinite(xk).all()
     dx = (xk.double() - ref_x).abs()
-    du = (_vals16(u, bf16).double() - ref_u).abs() if want_u else None
+    du = (vals16(u, bf16).double() - ref_u).abs() if want_u else None
     if want_u:
         assert torch.isfinite(du).all()
     return float(dx.max()), float(dx.mean()), (float(du.max()) if want_u else None)
@@ -102,7 +78,7 @@ def _ragged_case(M, outproj, bf16, want_u=True):
 RAGGED_M = [1, 31, 32, 33, 63, 64, 65, 95, 96, 97, 127, 128, 129, 161, 257]
 
 
-@BOTH
+@MODES
 @pytest.mark.parametrize("outproj", [True, False], ids=["outproj", "mlp"])
 @pytest.mark.parametrize("M", RAGGED_M)
 def test_ragged_rows_at_row_block_granularity(M, outproj, bf16):
@@ -110,16 +86,16 @@ def test_ragged_rows_at_row_block_granularity(M, outproj, bf16):
     behind M neither read into a result nor written."""
     mx, mean, mu = _ragged_case(M, outproj, bf16)
     print(f"panel4 tiles M={M} outproj={outproj} bf16={bf16}: max |dx| {mx:.2e} mean |dx| {mean:.2e} max |du| {mu:.2e}")
-    bx, bm, bu = _BOUNDS[bf16]
+    bx, bm, bu = BOUNDS[bf16]
     assert mx < bx and mean < bm and mu < bu, (mx, mean, mu)
 
 
-@BOTH
+@MODES
 def test_ragged_rows_without_the_normalised_output(bf16):
     """u_out = null: the same x, no second statistics pass, nothing else written (M = 97: three full row blocks and one row of the fourth)."""
     mx, mean, _ = _ragged_case(97, True, bf16, want_u=False)
     print(f"panel4 tiles M=97 outproj=True bf16={bf16} want_u=False: max |dx| {mx:.2e} mean |dx| {mean:.2e}")
-    bx, bm, _ = _BOUNDS[bf16]
+    bx, bm, _ = BOUNDS[bf16]
     assert mx < bx and mean < bm, (mx, mean)
 
 
@@ -160,7 +136,7 @@ def _positions():
 _POSITIONS = _positions()  # (at import: a wrong set fails at collection, without a GPU)
 
 
-@BOTH
+@MODES
 @pytest.mark.parametrize("stage", ["wo", "w1", "w2"])
 def test_one_hot_weight_layouts(stage, bf16):
     """A single nonzero in Wo, in W1 (observed through one nonzero of W2 on the same hidden unit) or in W2, everything else zero: the output is
@@ -177,15 +153,13 @@ def test_one_hot_weight_layouts(stage, bf16):
           GELU is no longer the identity in 16 bits.  The constant that moves is therefore W1[hid, k] = 4 (not 1): the folded weight is
           exactly 1, the pre-activation 13.859375 / 13.875 as in the 8-wave test, and a g2 from another column gives 12 times that
           ->  column n is x + 2 x that value."""
-    import hip_helpers as hh
-
     dev = torch.device(DEV)
     M = 129
     rows = torch.arange(M, device=dev)
     o = ((rows[:, None] * 7 + torch.arange(C, device=dev)[None, :] * 3) % 17 - 8).float()
-    with _mode4(bf16):
-        o16 = _bits16(o, bf16)
-        w = _zero_weights(dev)
+    with hh.switches(bf16=bf16, panel_impl=1):
+        o16 = bits16(o, bf16)
+        w = zero_weights(dev)
         for n, k, hid in _POSITIONS:
             for name, idx, v in (("ls1", n, 0.5), ("g2", k, 0.25), ("ls2", n, 2.0)):
                 w[name].fill_(3.0)
@@ -216,19 +190,16 @@ def test_one_hot_weight_layouts(stage, bf16):
 
 
 # ---- 3. rows across row blocks and waves --------------------------------------------------------------------------------------------------
-@BOTH
+@MODES
 def test_rows_are_independent_across_row_blocks_and_waves(bf16):
     """Rows meet in LDS three times: the LayerNorm exchange red[wave][row], fc1 by row block (wave w runs rows 32 w .. 32 w + 31 for everybody)
     and the hand-off buffers every wave reads all sixteen fragments of.  With different data in every row, perturbing one row (its residual and
     its attention output) changes that row's x and u and no other bit: first and last row of every row block, and of a second workgroup."""
-    import hip_helpers as hh
-    from test_hip_panel import _make
-
     dev = torch.device(DEV)
     M = 160
-    x, o, w = _make(M, 77, dev)
-    with _mode4(bf16):
-        o16 = _bits16(o.float(), bf16)
+    x, o, w = make(M, 77, dev)
+    with hh.switches(bf16=bf16, panel_impl=1):
+        o16 = bits16(o.float(), bf16)
         img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
         x0 = x.clone()
         u0 = hh.encoder_panel(x0, o16, img, w["bo"], w["b1"], w["b2"])
@@ -254,7 +225,7 @@ def _extreme_units():
 _EXTREME_UNITS = _extreme_units()
 
 
-@BOTH
+@MODES
 def test_gelu_hand_off_reaches_every_branch_on_all_four_row_blocks(bf16):
     """The fc1 pre-activations are a ramp over the hidden units (b1 = -6 .. 6 in steps of 1/128, plus +-8, +-1000, +-60000 on even and odd ticks,
     both hidden tiles, the first and the last tick: the fitted range, both clamps, the sign of the relu, values whose half is far from their
@@ -266,11 +237,8 @@ def test_gelu_hand_off_reaches_every_branch_on_all_four_row_blocks(bf16):
     Every hidden unit has a bias of its own, so the test also pins the b1 lookup (b1g + (t + 1) * HT * 4, offset 128 for the second tile,
     panel4_perm).  Not observable here: the hi + lo split of b1 -- the pre-activation is rounded to the operand type before the GELU, and every
     bias of this test is hi + lo exactly (the fp32 sums the MFMA forms are exact in any order)."""
-    import hip_helpers as hh
-    from test_gelu_pk16 import _compiled, _kernel_constants, _tool
-
-    t = _tool()
-    consts = _compiled(_kernel_constants())
+    t = gelu_tool()
+    consts = gelu_compiled(gelu_kernel_constants())
     dev = torch.device(DEV)
     M = 128
     k0, hid0 = 37, HT * 7 + 32 + 21
@@ -284,9 +252,9 @@ def test_gelu_hand_off_reaches_every_branch_on_all_four_row_blocks(bf16):
     with np.errstate(over="ignore"):
         h = t.kernel_gelu_bf16(pre, consts) if bf16 else t.kernel_gelu(pre, consts)
     h = torch.from_numpy(np.asarray(h, dtype=np.float64)).to(dev)
-    with _mode4(bf16):
+    with hh.switches(bf16=bf16, panel_impl=1):
         for j in range(4):
-            w = _zero_weights(dev)
+            w = zero_weights(dev)
             w["b1"] = b1.to(dev)
             w["w1"][hid0, k0] = 1.0
             for n in range(C):
@@ -313,8 +281,8 @@ def test_gelu_hand_off_reaches_every_branch_on_all_four_row_blocks(bf16):
 # ---- 5. b2 through the matrix pipe --------------------------------------------------------------------------------------------------------
 def _split16(b, bf16):
     """the kernel's split of an fp32 bias: hi = rnd16(b), lo = rnd16(b - hi) -> (hi, lo) as fp32 values"""
-    hi = _r16(b, bf16)
-    lo = _r16(b - hi, bf16)
+    hi = r16(b, bf16)
+    lo = r16(b - hi, bf16)
     return hi, lo
 
 
@@ -332,7 +300,7 @@ def _exact_b2(bf16):
         lo = torch.clamp(lo, min=2.0 ** -14)
     lo = lo * (1.0 - 2.0 * ((n // 7) % 2))
     assert len(set(hi.tolist())) == C and float(hi.abs().min()) >= 0.125 and float(hi.abs().max()) < 4.0
-    assert torch.equal(_r16(hi, bf16), hi) and torch.equal(_r16(lo, bf16), lo)
+    assert torch.equal(r16(hi, bf16), hi) and torch.equal(r16(lo, bf16), lo)
     assert bool((lo.abs() <= ulp / 2).all()) and float(lo.abs().min()) >= (2.0 ** -126 if bf16 else 2.0 ** -14)
     b = hi + lo
     assert torch.equal(b.float().double(), b)          # exactly an fp32 value
@@ -346,12 +314,10 @@ _EXACT_B2 = {bf: _exact_b2(bf) for bf in (False, True)}  # (at import, on the CP
 
 def _b2_launch(x, b2, outproj, bf16):
     """all weights zero, b1 = 0 -> x after one launch"""
-    import hip_helpers as hh
-
     dev = x.device
-    w = _zero_weights(dev)
+    w = zero_weights(dev)
     w["b2"] = b2.to(dev)
-    with _mode4(bf16):
+    with hh.switches(bf16=bf16, panel_impl=1):
         img = hh.panel_pack(w["wo"] if outproj else None, w["ls1"] if outproj else None, w["w1"], w["g2"], w["w2"], w["ls2"])
         o16 = torch.zeros(x.shape[0], C, dtype=torch.float16, device=dev) if outproj else None
         xk = x.clone()
@@ -371,7 +337,7 @@ def _claim(b2, bf16):
     return b2.double().abs() * (2.0 ** -16 if bf16 else 2.0 ** -22) + (0.0 if bf16 else 2.0 ** -25)
 
 
-@BOTH
+@MODES
 @pytest.mark.parametrize("outproj", [True, False], ids=["outproj", "mlp"])
 def test_b2_exactly_representable_as_hi_plus_lo(outproj, bf16):
     """(a) x = 0, all weights zero: x_out[:, n] = b2[n] bit for bit in every row of both workgroups.  Distinct values per feature pin the permuted
@@ -384,7 +350,7 @@ def test_b2_exactly_representable_as_hi_plus_lo(outproj, bf16):
     assert torch.equal(xk, expect), torch.nonzero(xk != expect)[:4].tolist()
 
 
-@BOTH
+@MODES
 def test_random_b2_is_its_hi_plus_lo(bf16):
     """(b) random fp32 b2 in +-4 (about a dozen of magnitude below 2^-3, whose fp16 lo is subnormal): x_out is float(hi) + float(lo) of the host
     split exactly -- the MFMA adds the two products to a zero accumulator without a rounding and takes a subnormal half operand as it is -- and
@@ -411,17 +377,15 @@ def _ulp32(v):
     return 2.0 ** (torch.floor(torch.log2(torch.clamp(v.abs(), min=2.0 ** -126))) - 23)
 
 
-@BOTH
+@MODES
 @pytest.mark.parametrize("outproj", [True, False], ids=["outproj", "mlp"])
 def test_b2_on_random_residual(outproj, bf16):
-    """(c) the random b2 of (b) on the random residual of test_hip_panel._make, all weights zero: against fp64 x + b2 the error is the split's own
+    """(c) the random b2 of (b) on the random residual of panel_data.make, all weights zero: against fp64 x + b2 the error is the split's own
     (|hi + lo - b2| per feature, known exactly) plus two fp32 ulps of the largest of |x|, |b2|, |x + b2| -- the accumulator takes two products,
     with two roundings at most."""
-    from test_hip_panel import _make
-
     dev = torch.device(DEV)
     M = 129
-    x, _, _ = _make(M, 31, dev)
+    x, _, _ = make(M, 31, dev)
     b2 = _random_b2()
     hi, lo = _split16(b2, bf16)
     split_err = ((hi.double() + lo.double()) - b2.double()).abs().to(dev)

@@ -2,7 +2,7 @@
 16, a weight fragment is 16 output features x 32 contraction slots, a D tile hands lane (li, g) token li and features 4g .. 4g+3.
 Same op entry points as test_hip_panel.py (cs_op_panel_pack / cs_op_encoder_panel); every case is one or a few launches of at most 257 rows.
 The 8-wave kernel (the default) throughout; the four-wave form (csrc/panel4.hip: 32-row blocks, column-split waves, its own weight image) has
-its own module, test_hip_panel4_tiles.py, which shares the reference, the operand helpers and the bounds below.
+its own module, test_hip_panel4_tiles.py; the reference, the operand helpers and the bounds are shared (tests/panel_data.py, tests/bits16.py).
 
 Parent kernel (32x32x16 tiles) on the inputs of test_ragged_rows_at_tile_granularity, measured once with the parent library; the bounds of the
 test are the ones test_hip_panel.py carries (fp16: test_panel_vs_torch; bf16: the concurrent-streams test), not these figures:
@@ -15,73 +15,23 @@ import numpy as np
 import pytest
 import torch
 
+import hip_helpers as hh
+from bits16 import MODES, bits16, vals16
+from guard import guarded_out
+from kernel_data import gelu_compiled, gelu_kernel_constants, gelu_tool
+from panel_data import BOUNDS, C, F, make, reference64, zero_weights
+
 pytestmark = pytest.mark.gpu
 
-C, F = 384, 1536
 DEV = "cuda:0"
 
 
-class _mode:
-    """cs_debug_set_op_operand_dtype for the duration of a block, restored in any case; the 8-wave kernel (the default) throughout (the four-wave
-    kernel: _mode4 of test_hip_panel4_tiles.py)"""
-
-    def __init__(self, bf16):
-        self.bf16 = bf16
-
-    def __enter__(self):
-        from crossscore_amd import _lib
-        lib = _lib.load()
-        lib.cs_debug_panel_impl(0)
-        assert lib.cs_debug_set_op_operand_dtype(1 if self.bf16 else 0) == 0
-
-    def __exit__(self, *a):
-        from crossscore_amd import _lib
-        _lib.load().cs_debug_set_op_operand_dtype(0)
-
-
-def _r16(t, bf16):
-    """round to the operand type, back in the input's dtype"""
-    return t.to(torch.bfloat16 if bf16 else torch.float16).to(t.dtype)
-
-
-def _bits16(t, bf16):
-    """fp32 values as the 16-bit operand tensor the ops take (raw bits in a float16 tensor in both modes)"""
-    return t.to(torch.bfloat16).view(torch.float16) if bf16 else t.to(torch.float16)
-
-
-def _vals16(t, bf16):
-    """the values of a 16-bit tensor the ops wrote"""
-    return (t.view(torch.bfloat16) if bf16 else t).float()
-
-
-def _norm64(x, eps=1e-6):
-    mu = x.mean(-1, keepdim=True)
-    var = ((x - mu) ** 2).mean(-1, keepdim=True)
-    return (x - mu) / torch.sqrt(var + eps)
-
-
-def _reference64(x, o16, w, outproj, bf16):
-    """the layer tail in fp64 on the same 16-bit-rounded operands (weights with LayerScale / gamma folded, norm2(x), the hidden slice), exact GELU"""
-    d = torch.float64
-    r = lambda t: _r16(t.float(), bf16).to(d)
-    x1 = x.to(d)
-    if outproj:
-        x1 = x1 + o16.to(d) @ r(w["wo"] * w["ls1"][:, None]).T + w["bo"].to(d)
-    h = torch.nn.functional.gelu(r(_norm64(x1)) @ r(w["w1"] * w["g2"][None, :]).T + w["b1"].to(d))
-    x2 = x1 + r(h) @ r(w["w2"] * w["ls2"][:, None]).T + w["b2"].to(d)
-    return x2, _norm64(x2)
-
-
 def _ragged_case(M, outproj, bf16, guarded=True):
-    """-> (max |dx|, mean |dx|, max |du|) of one launch against _reference64; guard bands around x and u checked"""
-    import hip_helpers as hh
-    from guard import guarded_out
-    from test_hip_panel import _make
-
+    """-> (max |dx|, mean |dx|, max |du|) of one launch against panel_data.reference64; guard bands around x and u checked"""
     dev = torch.device(DEV)
-    x, o, w = _make(M, 900 + M, dev)
-    with _mode(bf16):
-        o16 = _bits16(o.float(), bf16)
+    x, o, w = make(M, 900 + M, dev)
+    with hh.switches(bf16=bf16, panel_impl=0):
+        o16 = bits16(o.float(), bf16)
         img = hh.panel_pack(w["wo"] if outproj else None, w["ls1"] if outproj else None, w["w1"], w["g2"], w["w2"], w["ls2"])
         xk, cx = guarded_out((M, C), torch.float32, init=x)
         u, cu = guarded_out((M, C), torch.float16)
@@ -90,26 +40,23 @@ def _ragged_case(M, outproj, bf16, guarded=True):
     if guarded:
         cx("x")
         cu("u")
-    ref_x, ref_u = _reference64(x, _vals16(o16, bf16), w, outproj, bf16)
+    ref_x, ref_u = reference64(x, vals16(o16, bf16), w, outproj, bf16)
     assert torch.isfinite(xk).all()
     dx = (xk.double() - ref_x).abs()
-    du = (_vals16(u, bf16).double() - ref_u).abs()
+    du = (vals16(u, bf16).double() - ref_u).abs()
     return float(dx.max()), float(dx.mean()), float(du.max())
 
 
-# fp16: the bounds of test_hip_panel.py::test_panel_vs_torch.  bf16: max / mean of its concurrent-streams test (8 significant bits); u is a
-# bf16 value of magnitude up to 4 (half an ulp 7.8e-3) of rows whose x carries up to 3.2e-2 of error at rstd ~ 0.45: 7.8e-3 + 1.5e-2, rounded up.
-_BOUNDS = {False: (4e-3, 4e-4, 6e-3), True: (3.2e-2, 2.4e-3, 3e-2)}
 
 
-@pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+@MODES
 @pytest.mark.parametrize("outproj", [True, False], ids=["outproj", "mlp"])
 @pytest.mark.parametrize("M", [1, 15, 16, 17, 31, 32, 33, 127, 128, 129, 257])
 def test_ragged_rows_at_tile_granularity(M, outproj, bf16):
     """Row counts around the 16-row tile, the 32-row pair and the 128-row panel: every row right, nothing written past row M."""
     mx, mean, mu = _ragged_case(M, outproj, bf16)
     print(f"panel tiles M={M} outproj={outproj} bf16={bf16}: max |dx| {mx:.2e} mean |dx| {mean:.2e} max |du| {mu:.2e}")
-    bx, bm, bu = _BOUNDS[bf16]
+    bx, bm, bu = BOUNDS[bf16]
     assert mx < bx and mean < bm and mu < bu, (mx, mean, mu)
 
 
@@ -130,13 +77,7 @@ def _positions():
     return out
 
 
-def _zero_weights(dev):
-    z = lambda *s: torch.zeros(*s, device=dev)
-    one = lambda *s: torch.ones(*s, device=dev)
-    return dict(wo=z(C, C), ls1=one(C), bo=z(C), w1=z(F, C), g2=one(C), b1=z(F), w2=z(C, F), ls2=one(C), b2=z(C))
-
-
-@pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+@MODES
 @pytest.mark.parametrize("stage", ["wo", "w1", "w2"])
 def test_one_hot_weight_layouts(stage, bf16):
     """A single nonzero in Wo, in W1 (observed through one nonzero of W2 on the same hidden unit) or in W2, everything else zero, LayerScale and
@@ -146,14 +87,12 @@ def test_one_hot_weight_layouts(stage, bf16):
       w2: b1[hid] = 8, GELU(8) = 8 in both modes (8 - 1.3e-4 rounds to 8)          ->  column n of x is 8 in every row
       w1: rows (+4 at column k, -4 at column k + 192, else 0) have mean 0 and norm2 = +-sqrt(192) = 13.8564 there, far from a rounding
           boundary of either type (13.859375 half, 13.875 bfloat16), and GELU leaves that value as it is  ->  column n is x + that value."""
-    import hip_helpers as hh
-
     dev = torch.device(DEV)
     M = 33  # both row tiles of a pair and a second pair
     rows = torch.arange(M, device=dev)
-    with _mode(bf16):
+    with hh.switches(bf16=bf16, panel_impl=0):
         for n, k, hid in _positions():
-            w = _zero_weights(dev)
+            w = zero_weights(dev)
             x = torch.zeros(M, C, device=dev)
             o = None
             if stage == "wo":
@@ -174,24 +113,21 @@ def test_one_hot_weight_layouts(stage, bf16):
                 expect = x.clone()
                 expect[:, n] += 13.875 if bf16 else 13.859375
             img = hh.panel_pack(w["wo"] if o is not None else None, w["ls1"] if o is not None else None, w["w1"], w["g2"], w["w2"], w["ls2"])
-            hh.encoder_panel(x, _bits16(o, bf16) if o is not None else None, img, w["bo"] if o is not None else None, w["b1"], w["b2"], want_u=False)
+            hh.encoder_panel(x, bits16(o, bf16) if o is not None else None, img, w["bo"] if o is not None else None, w["b1"], w["b2"], want_u=False)
             torch.cuda.synchronize()
             assert torch.equal(x, expect), (stage, n, k, hid, torch.nonzero(x != expect)[:4].tolist())
 
 
 # ---- row tiles ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+@MODES
 def test_row_tiles_are_independent(bf16):
     """Rows 0-15 and 16-31 of a pair are two MFMA row tiles that share every weight fragment.  With different data in every row, perturbing one
     row (its residual and its attention output) changes that row's outputs and no other bit."""
-    import hip_helpers as hh
-    from test_hip_panel import _make
-
     dev = torch.device(DEV)
     M = 64
-    x, o, w = _make(M, 77, dev)
-    with _mode(bf16):
-        o16 = _bits16(o.float(), bf16)
+    x, o, w = make(M, 77, dev)
+    with hh.switches(bf16=bf16, panel_impl=0):
+        o16 = bits16(o.float(), bf16)
         img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
         x0 = x.clone()
         u0 = hh.encoder_panel(x0, o16, img, w["bo"], w["b1"], w["b2"])
@@ -207,7 +143,7 @@ def test_row_tiles_are_independent(bf16):
 
 
 # ---- GELU hand-off ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+@MODES
 def test_gelu_hand_off_reaches_every_branch_on_both_row_tiles(bf16):
     """The fc1 pre-activations are a ramp over the hidden units (b1 = -6 .. 6 in steps of 1/128, plus +-8, +-1000, +-60000: the fitted range, both
     clamps, the sign of the relu, values whose half is far from their fp32), one of them moved by a one-hot W1 on rows whose norm2 is +-13.86.
@@ -215,11 +151,8 @@ def test_gelu_hand_off_reaches_every_branch_on_both_row_tiles(bf16):
     hand-off); even and odd slices use different hand-off slots.  W2 routes hidden unit 4 n + j to output feature n (j = 0 .. 3: four
     launches), so x[:, n] is the activated value itself: compared with panel_shared.h's GELU evaluated on the host (tools/gelu_pk16_fit.py,
     the model test_gelu_pk16.py checks against the compiled constants) -- exactly in fp16 mode, to the one final bfloat16 rounding in bf16 mode."""
-    import hip_helpers as hh
-    from test_gelu_pk16 import _compiled, _kernel_constants, _tool
-
-    t = _tool()
-    consts = _compiled(_kernel_constants())
+    t = gelu_tool()
+    consts = gelu_compiled(gelu_kernel_constants())
     dev = torch.device(DEV)
     M = 32
     k0, hid0 = 37, 32 * 5 + 21
@@ -233,9 +166,9 @@ def test_gelu_hand_off_reaches_every_branch_on_both_row_tiles(bf16):
     with np.errstate(over="ignore"):
         h = t.kernel_gelu_bf16(pre, consts) if bf16 else t.kernel_gelu(pre, consts)
     h = torch.from_numpy(np.asarray(h, dtype=np.float64)).to(dev)
-    with _mode(bf16):
+    with hh.switches(bf16=bf16, panel_impl=0):
         for j in range(4):
-            w = _zero_weights(dev)
+            w = zero_weights(dev)
             w["b1"] = b1.to(dev)
             w["w1"][hid0, k0] = 1.0
             for n in range(C):

@@ -33,80 +33,38 @@ fp32 bit patterns); 3 the one stated fp32 bound.  Figures printed by the tests (
 run against this file: EXPERIMENTS.md.
 """
 import functools
-import time
 
 import numpy as np
 import pytest
 import torch
 
+import hip_helpers as hh
 import patch_tile_data as ptd
+from bits16 import MODES, Worst, bits, same_bits, to_dev
 
 gpu = pytest.mark.gpu
 
 DEV = "cuda"
 F32 = torch.float32
 P = 14
-MODES = pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
 FORMS = pytest.mark.parametrize("form", ["fused", "two"])
 
-_WORST = {}
+_worst = Worst("test_hip_patch_tiles", "patch tiles")
 
 
 def setup_module(module):
-    module._T0 = time.time()
+    _worst.start()
 
 
 def teardown_module(module):
-    print()
-    for (name, bf16), figs in sorted(_WORST.items()):
-        print(f"patch tiles worst, {name}, {'bf16' if bf16 else 'fp16'}: " + ", ".join(f"{k} {v:.3e}" for k, v in figs.items()))
-    print(f"test_hip_patch_tiles wall time: {time.time() - module._T0:.1f} s")
-
-
-def _note(name, bf16, **figs):
-    w = _WORST.setdefault((name, bf16), {})
-    for k, v in figs.items():
-        w[k] = max(w.get(k, 0.0), float(v))
-
-
-class _mode:
-    """cs_debug_set_op_operand_dtype for the duration of a block, restored in any case"""
-
-    def __init__(self, bf16):
-        self.bf16 = bf16
-
-    def __enter__(self):
-        from crossscore_amd import _lib
-        assert _lib.load().cs_debug_set_op_operand_dtype(1 if self.bf16 else 0) == 0
-
-    def __exit__(self, *a):
-        from crossscore_amd import _lib
-        _lib.load().cs_debug_set_op_operand_dtype(0)
-
-
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    _worst.report()
 
 
 def _run(form, x, w, b, pos, out=None):
     """(I, 3, H, W) images -> (I, 1 + Np, C) fp32 token rows; the CLS rows are not written"""
-    import hip_helpers as hh
-
     o = hh.patch_embed_fused(x, w, b, pos, P, out=out) if form == "fused" else hh.patch_embed(x, w, b, pos, P, 1, out=out)
     torch.cuda.synchronize()
     return o.reshape(x.shape[0], -1, w.shape[0])
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _same_bits(got, want, what):
-    g, w = _bits(got), _bits(want)
-    if not torch.equal(g, w):
-        bad = torch.nonzero(g != w)
-        raise AssertionError(f"{what}: {bad.shape[0]} of {g.numel()} elements differ in their bits; the first at {bad[0].tolist()}: "
-                             f"{float(got[tuple(bad[0])])!r} against {float(want[tuple(bad[0])])!r}")
 
 
 # ---- 1. exact integers --------------------------------------------------------------------------------------------------------------------
@@ -139,10 +97,10 @@ def test_exact_integers(gw, C, form, bf16):
     x, w, b, pos, ref32 = _integer_case(gw, C)
     Np = gh * gw
     gg = guard.guarded((I * (1 + Np), C), F32)
-    with _mode(bf16):
-        out = _run(form, guard.poisoned_in(_t(x)), _t(w), _t(b), _t(pos), out=gg.view)
+    with hh.switches(bf16=bf16):
+        out = _run(form, guard.poisoned_in(to_dev(x)), to_dev(w), to_dev(b), to_dev(pos), out=gg.view)
     gg.check(f"{form} gw={gw} C={C}")
-    assert bool((_bits(out[:, 0]) == gg.sentinel).all()), "a CLS row was written"
+    assert bool((bits(out[:, 0]) == gg.sentinel).all()), "a CLS row was written"
     got = out[:, 1:].cpu()
     if not torch.equal(got, ref32):
         bad = torch.nonzero(got != ref32)
@@ -171,13 +129,13 @@ def test_one_hot_weights_single_rounding(gw, C, form, bf16):
     in about half of the elements."""
     I, gh = 2, 2
     x = _generic_images(gw)
-    xd = _t(x)
+    xd = to_dev(x)
     zb, zpos = torch.zeros(C, device=DEV), torch.zeros(1 + gh * gw, C, device=DEV)
-    with _mode(bf16):
+    with hh.switches(bf16=bf16):
         for b in ptd.ONEHOT_B[C]:
-            out = _run(form, xd, _t(ptd.onehot_weights(C, b)), zb, zpos)
+            out = _run(form, xd, to_dev(ptd.onehot_weights(C, b)), zb, zpos)
             want = torch.from_numpy(ptd.onehot_expected(x, gh, gw, ptd.onehot_k(C, b), bf16))
-            _same_bits(out[:, 1:].cpu(), want, f"{form} gw={gw} C={C} b={b} bf16={bf16}")
+            same_bits(out[:, 1:].cpu(), want, f"{form} gw={gw} C={C} b={b} bf16={bf16}")
             assert bool((out[:, 0] == 7.0).all())
 
 
@@ -194,14 +152,14 @@ def test_constant_patches_mean_term(form, bf16):
     x, c = ptd.constant_images(I, gh, gw, 31)
     w, b, pos = ptd.random_operands(C, 1 + gh * gw, 32)
     ref, bound = ptd.conv64(x, w, b, pos, gh, gw), ptd.constant_bound(c, w, b, pos)
-    with _mode(bf16):
-        out = _run(form, _t(x), _t(w), _t(b), _t(pos))
+    with hh.switches(bf16=bf16):
+        out = _run(form, to_dev(x), to_dev(w), to_dev(b), to_dev(pos))
     got = out[:, 1:].cpu().numpy()
     assert np.isfinite(got).all()
     err = np.abs(got.astype(np.float64) - ref)
     ratio = float((err / bound).max())
     print(f"patch tiles constant patches {form} bf16={bf16}: max |out - fp64| {err.max():.3e}, worst error / bound {ratio:.3e}")
-    _note(f"constant_patches {form}", bf16, err=err.max(), over_bound=ratio)
+    _worst.note(f"constant_patches {form}", bf16, err=err.max(), over_bound=ratio)
     assert (err <= bound).all(), ratio
 
 
@@ -220,10 +178,10 @@ def test_a_patch_reaches_its_own_row_only(gw, where, form, bf16):
     means are indexed per patch, the row sums stay with their patch, a 16-row MFMA tile never mixes rows); the row itself is NaN in every
     column for NaN and Inf (the mean term alone sees to that) and finite again after the finite replacement."""
     I, gh, C = 2, 2, 384
-    x = _t(ptd.normal_images(I, gh, gw, 4000 + gw))
-    w, b, pos = (_t(a) for a in ptd.random_operands(C, 1 + gh * gw, 4100 + gw))
-    fresh = _t(np.random.Generator(np.random.PCG64(4200)).standard_normal((3, P, P)).astype(np.float32) * 1.5 + 0.25)
-    with _mode(bf16):
+    x = to_dev(ptd.normal_images(I, gh, gw, 4000 + gw))
+    w, b, pos = (to_dev(a) for a in ptd.random_operands(C, 1 + gh * gw, 4100 + gw))
+    fresh = to_dev(np.random.Generator(np.random.PCG64(4200)).standard_normal((3, P, P)).astype(np.float32) * 1.5 + 0.25)
+    with hh.switches(bf16=bf16):
         base = _run(form, x, w, b, pos).clone()
         assert torch.isfinite(base[:, 1:]).all()
         for img, pi, pj in where:
@@ -234,7 +192,7 @@ def test_a_patch_reaches_its_own_row_only(gw, where, form, bf16):
                 xv = x.clone()
                 xv[img, :, pi * P:(pi + 1) * P, pj * P:(pj + 1) * P] = val
                 got = _run(form, xv, w, b, pos)
-                same = (_bits(got) == _bits(base)).all(-1)
+                same = (bits(got) == bits(base)).all(-1)
                 assert bool(same[others].all()), (form, gw, (img, pi, pj), name, "rows changed (image, token):", torch.nonzero(~same & others)[:8].tolist())
                 row = got[img, tok]
                 if name == "finite":
@@ -251,12 +209,12 @@ def test_two_passes_equal_two_one_pass_launches(bf16):
     (Wb, bb, posb): pass 1 restarts its accumulators and reads its own weight pieces, bias, wsum and position columns.  gw = 38: the 48-row
     layout with ten dead rows."""
     I, gh, gw = 2, 2, 38
-    x = _t(ptd.normal_images(I, gh, gw, 5000))
+    x = to_dev(ptd.normal_images(I, gh, gw, 5000))
     w, b, pos = ptd.random_operands(768, 1 + gh * gw, 5001)
-    with _mode(bf16):
-        wide = _run("fused", x, _t(w), _t(b), _t(pos))
+    with hh.switches(bf16=bf16):
+        wide = _run("fused", x, to_dev(w), to_dev(b), to_dev(pos))
         for h in (0, 1):
             s = slice(384 * h, 384 * h + 384)
-            half = _run("fused", x, _t(w[s]), _t(b[s]), _t(pos[:, s]))
-            _same_bits(wide[:, 1:, s], half[:, 1:], f"columns {s.start}..{s.stop - 1} bf16={bf16}")
+            half = _run("fused", x, to_dev(w[s]), to_dev(b[s]), to_dev(pos[:, s]))
+            same_bits(wide[:, 1:, s], half[:, 1:], f"columns {s.start}..{s.stop - 1} bf16={bf16}")
     assert torch.isfinite(wide[:, 1:]).all()

@@ -27,82 +27,30 @@ Shape -> branch of the kernel:
 Figures printed by the tests (worst per test and mode) and the record of the kernel mutations run against this file: EXPERIMENTS.md.
 """
 import math
-import time
 
 import numpy as np
 import pytest
 import torch
 
+import hip_helpers as hh
+from bits16 import MODES, Worst, bits16, ordered16, same_bits, spacing16, vals16
+
 gpu = pytest.mark.gpu
 
 C = 384
 DEV = "cuda"
-F16, F32 = torch.float16, torch.float32
-MODES = pytest.mark.parametrize("bf16", [False, True], ids=["fp16", "bf16"])
+F16, F32, F64 = torch.float16, torch.float32, torch.float64
 TOL32 = 2e-4  # out_f32 against fp64: the bound of test_hip_ops.py::test_linear_layernorm_one_launch
 
-_WORST = {}
+_worst = Worst("test_hip_rowln_tiles", "rowln tiles")
 
 
 def setup_module(module):
-    module._T0 = time.time()
+    _worst.start()
 
 
 def teardown_module(module):
-    print()
-    for (name, bf16), figs in sorted(_WORST.items()):
-        print(f"rowln tiles worst, {name}, {'bf16' if bf16 else 'fp16'}: " + ", ".join(f"{k} {v:.3e}" for k, v in figs.items()))
-    print(f"test_hip_rowln_tiles wall time: {time.time() - module._T0:.1f} s")
-
-
-def _note(name, bf16, **figs):
-    w = _WORST.setdefault((name, bf16), {})
-    for k, v in figs.items():
-        w[k] = max(w.get(k, 0.0), float(v))
-
-
-class _mode:
-    """cs_debug_set_op_operand_dtype for the duration of a block, restored in any case"""
-
-    def __init__(self, bf16):
-        self.bf16 = bf16
-
-    def __enter__(self):
-        from crossscore_amd import _lib
-        assert _lib.load().cs_debug_set_op_operand_dtype(1 if self.bf16 else 0) == 0
-
-    def __exit__(self, *a):
-        from crossscore_amd import _lib
-        _lib.load().cs_debug_set_op_operand_dtype(0)
-
-
-def _bits16(t, bf16):
-    """fp32 values as the 16-bit operand tensor the ops take (raw bits in a float16 tensor in both modes), rounded to nearest even once"""
-    return t.to(torch.bfloat16).view(F16) if bf16 else t.to(F16)
-
-
-def _vals16(t, bf16):
-    """the values of a 16-bit tensor, in fp64"""
-    return (t.view(torch.bfloat16) if bf16 else t).double()
-
-
-def _same16(a, b, what=""):
-    a, b = a.contiguous().view(torch.int16), b.contiguous().view(torch.int16)
-    assert torch.equal(a, b), (what, int((a != b).sum()), torch.nonzero(a != b)[:4].tolist())
-
-
-def _ordered16(t):
-    """16-bit patterns as integers in the order of their values: neighbours differ by 1 (+0 and -0 by 0)"""
-    b = t.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
-    return torch.where(b >= 0x8000, -(b & 0x7FFF), b & 0x7FFF)
-
-
-def _spacing16(x, bf16):
-    """the spacing of the operand type's values around |x| (fp64 tensor): 2^(floor(log2 |x|) - 10) in fp16 from its smallest normal 2^-14 up,
-    2^(floor(log2 |x|) - 7) in bf16 from 2^-126"""
-    e = torch.frexp(x.abs())[1].double() - 1.0
-    e = torch.where(x == 0, torch.full_like(e, -1000.0), e)
-    return torch.exp2(torch.clamp(e, min=-126.0 if bf16 else -14.0) - (7.0 if bf16 else 10.0))
+    _worst.report()
 
 
 def _ln64(pre, gam, bet, eps):
@@ -122,15 +70,15 @@ def _rand_case(M, seed, bf16, with_resid=True, n2=0, offset=0.0, dev=None):
     """random operands, PCG64(seed), generated on the host: A, W, W2 rounded to the operand type; resid = offset + N(0, sigma)"""
     g = np.random.Generator(np.random.PCG64(seed))
     n = lambda *s: torch.from_numpy(g.standard_normal(s, dtype=np.float32))
-    d = dict(A=_bits16(n(M, C), bf16), W=_bits16(n(C, C) / math.sqrt(C), bf16), b=n(C),
+    d = dict(A=bits16(n(M, C), bf16), W=bits16(n(C, C) / math.sqrt(C), bf16), b=n(C),
              res=(offset + (1.0 if offset else 2.0) * n(M, C)) if with_resid else None, gam=1.0 + 0.3 * n(C), bet=0.2 * n(C))
     if n2:
-        d["W2"], d["b2"] = _bits16(n(n2, C) / math.sqrt(C), bf16), 0.5 * n(n2)
+        d["W2"], d["b2"] = bits16(n(n2, C) / math.sqrt(C), bf16), 0.5 * n(n2)
     return {k: (v.to(dev or DEV) if v is not None else None) for k, v in d.items()}
 
 
 def _pre64(d, bf16):
-    pre = _vals16(d["A"], bf16) @ _vals16(d["W"], bf16).t() + d["b"].double()
+    pre = vals16(d["A"], bf16, F64) @ vals16(d["W"], bf16, F64).t() + d["b"].double()
     return pre + d["res"].double() if d["res"] is not None else pre
 
 
@@ -230,7 +178,7 @@ def _check_margin_of_eight(bf16):
     rounding boundary; a value that rounds UP to a power of two cannot have more than that in fp16 (half an ulp of the binade below, 2^-9, over
     8), and 7.99999 has 0.995 of it (2.429e-4; bf16: 1.95e-3), so the assertion stands at 0.99 x 2^-12: about 4000 fp32 ulps either way."""
     x = _normalised_pm(16.0, 1e-5)
-    assert float(_vals16(_bits16(torch.tensor([x], dtype=torch.float64).float(), bf16), bf16)[0]) == 8.0
+    assert float(vals16(bits16(torch.tensor([x], dtype=torch.float64).float(), bf16), bf16, F64)[0]) == 8.0
     margin = _boundary_margin(x, bf16)
     assert margin >= 0.99 * 2.0 ** -12, margin
     assert 8.0 - x < 0.01 * 2.0 ** -9  # and it sits within 1 % of half an fp16 ulp of the value it rounds to
@@ -293,7 +241,6 @@ def test_ragged_rows_on_random_data(M, with_resid, n2, act2, bf16):
     """Row counts around the 32-row block and the 64-row workgroup.  A and the residual are exactly M rows inside poison, all outputs inside
     guard bands.  out_f32 against fp64 on the same rounded operands; out_f16 = out_f32 rounded once, bit for bit; out2 against fp64 on the
     kernel's own 16-bit rows, within half an ulp of the operand type plus the fp32 accumulation bound of test_hip_bounds.py::_gemm_case."""
-    import hip_helpers as hh
     from guard import guarded_out, poisoned_in
 
     d = _rand_case(M, 1000 + 7 * M + n2 + act2 + int(with_resid), bf16, with_resid, n2)
@@ -301,7 +248,7 @@ def test_ragged_rows_on_random_data(M, with_resid, n2, act2, bf16):
     res = poisoned_in(d["res"]) if with_resid else None
     of, cf = guarded_out((M, C), F32)
     oh, ch = guarded_out((M, C), F16)
-    with _mode(bf16):
+    with hh.switches(bf16=bf16):
         if n2:
             o2, c2 = guarded_out((M, n2), F16)
             hh.linear_layernorm_linear(A, d["W"], d["b"], res, d["gam"], d["bet"], 1e-5, d["W2"], d["b2"], act2, of=of, oh=oh, out2=o2)
@@ -313,21 +260,21 @@ def test_ragged_rows_on_random_data(M, with_resid, n2, act2, bf16):
     ref = _ln64(_pre64(d, bf16), d["gam"], d["bet"], 1e-5)
     e1 = float((of.double() - ref).abs().max())
     print(f"rowln tiles M={M} resid={with_resid} n2={n2} act2={act2} bf16={bf16}: max |out_f32 - ref| {e1:.2e}", end="")
-    _note("ragged", bf16, out_f32=e1)
+    _worst.note("ragged", bf16, out_f32=e1)
     assert torch.isfinite(of).all() and e1 < TOL32, e1
-    _same16(oh, _bits16(of, bf16), "out_f16 = out_f32 rounded once")
+    same_bits(oh, bits16(of, bf16), "out_f16 = out_f32 rounded once")
     if n2:
         c2("out2")
-        rows, W2 = _vals16(oh, bf16), _vals16(d["W2"], bf16)
+        rows, W2 = vals16(oh, bf16, F64), vals16(d["W2"], bf16, F64)
         r2 = _act64(rows @ W2.t() + d["b2"].double(), act2)
         S = rows.abs() @ W2.abs().t()
         half = 2.0 ** -8 if bf16 else 2.0 ** -11
         bound = half * r2.abs() + 1.001 * C * 2.0 ** -24 * S + 2.0 ** -24
         if act2 == 2:
             bound = bound + 2.0 ** -24 * r2.abs()  # the product with 0.01 is one more fp32 rounding
-        e2 = (_vals16(o2, bf16) - r2).abs()
+        e2 = (vals16(o2, bf16, F64) - r2).abs()
         print(f", max |out2 - ref| {float(e2.max()):.2e} (worst error / bound {float((e2 / bound).max()):.3f})", end="")
-        _note("ragged", bf16, out2=e2.max(), out2_over_bound=(e2 / bound).max())
+        _worst.note("ragged", bf16, out2=e2.max(), out2_over_bound=(e2 / bound).max())
         assert (e2 <= bound).all(), (float(e2.max()), float((e2 / bound).max()))
     print()
 
@@ -340,27 +287,25 @@ def test_one_hot_weight_first_stage(bf16):
     column k of A and everything else 0.  The normalised signal is +-19.6 at column n and -+0.05 elsewhere: a weight element in a wrong
     feature slot is off by O(1) at two columns, one in a wrong contraction slot by 39 in the rows where the two columns of A differ in sign.
     M = 65: both row blocks, a second workgroup."""
-    import hip_helpers as hh
-
     M = 65
     a = _signed_ints(M).to(DEV)
-    A = _bits16(a, bf16)
+    A = bits16(a, bf16)
     zero, one = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
     worst = 0.0
-    with _mode(bf16):
+    with hh.switches(bf16=bf16):
         for n, k in _positions():
             wf = torch.zeros(C, C, device=DEV)
             wf[n, k] = 1.0
-            of, oh = hh.linear_layernorm(A, _bits16(wf, bf16), zero, None, one, zero, 1e-6)
+            of, oh = hh.linear_layernorm(A, bits16(wf, bf16), zero, None, one, zero, 1e-6)
             torch.cuda.synchronize()
             pre = torch.zeros(M, C, dtype=torch.float64, device=DEV)
             pre[:, n] = a[:, k].double()
             err = float((of.double() - _ln64(pre, one, zero, 1e-6)).abs().max())
             worst = max(worst, err)
             assert err < TOL32, (n, k, err)
-            _same16(oh, _bits16(of, bf16), (n, k))
+            same_bits(oh, bits16(of, bf16), (n, k))
     print(f"rowln tiles one-hot W bf16={bf16}: max |out_f32 - ref| {worst:.2e} over {len(_positions())} positions")
-    _note("one_hot_w", bf16, out_f32=worst)
+    _worst.note("one_hot_w", bf16, out_f32=worst)
 
 
 # ---- 3. one-hot W2 ----------------------------------------------------------------------------------------------------------------------
@@ -381,8 +326,6 @@ def test_one_hot_weight_second_stage_exact(n2, bf16):
     +-7.99999 = +-8 in both operand types (margin asserted on the host), every other column 0.  With a single 1 at W2[n, k] and integer b2,
     out2 = round16(act2(b2 + (+-8 or 0 at column n))) bit for bit: the hand-off of the normalised rows through LDS, the slice and buffer a weight
     element travels through, the group its result lands in, and the accumulator reset of each group (a nonzero of group 0 stays out of 1, 2)."""
-    import hip_helpers as hh
-
     _check_margin_of_eight(bf16)
     M = 65
     rows, sign = _pm_rows(M, 16.0)
@@ -390,17 +333,17 @@ def test_one_hot_weight_second_stage_exact(n2, bf16):
     A, W = torch.zeros(M, C, dtype=F16, device=DEV), torch.zeros(C, C, dtype=F16, device=DEV)
     zero, one = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
     b2 = ((torch.arange(n2, device=DEV) * 7) % 11 - 5).float()
-    with _mode(bf16):
+    with hh.switches(bf16=bf16):
         for i, (n, k, act2) in enumerate(_positions2(n2)):
             w2 = torch.zeros(n2, C, device=DEV)
             w2[n, k] = 1.0
-            _, oh, o2 = hh.linear_layernorm_linear(A, W, zero, rows, one, zero, 1e-5, _bits16(w2, bf16), b2, act2, want_f32=False, want_f16=(i == 0))
+            _, oh, o2 = hh.linear_layernorm_linear(A, W, zero, rows, one, zero, 1e-5, bits16(w2, bf16), b2, act2, want_f32=False, want_f16=(i == 0))
             torch.cuda.synchronize()
             y = b2[None, :].repeat(M, 1)
             y[:, n] += norm[:, k]
-            _same16(o2, _bits16(_act32(y, act2), bf16), (n, k, act2))
+            same_bits(o2, bits16(_act32(y, act2), bf16), (n, k, act2))
             if i == 0:
-                _same16(oh, _bits16(norm, bf16), "normalised rows")
+                same_bits(oh, bits16(norm, bf16), "normalised rows")
 
 
 # ---- 4. eps -----------------------------------------------------------------------------------------------------------------------------
@@ -410,24 +353,22 @@ def test_one_hot_weight_second_stage_exact(n2, bf16):
 def test_eps_is_observable(eps, bf16):
     """Rows of +-2^-6 at six columns: variance 3.8e-6, so eps = 1e-3 / 1e-5 / 1e-6 dominates, matches or is below it and the result at the +v
     columns is 0.4932 / 4.2039 / 7.1209: any fixed eps fails two of the three cases by more than 100 tolerances (asserted by _eps_refs)."""
-    import hip_helpers as hh
-
     ref_v = _eps_refs()[EPS_SET.index(eps)]
     M = 65
     rows, sign = _pm_rows(M, 2.0 ** -6)
     rows = rows.to(DEV)
     A, W = torch.zeros(M, C, dtype=F16, device=DEV), torch.zeros(C, C, dtype=F16, device=DEV)
     zero, one = torch.zeros(C, device=DEV), torch.ones(C, device=DEV)
-    with _mode(bf16):
+    with hh.switches(bf16=bf16):
         of, oh = hh.linear_layernorm(A, W, zero, rows, one, zero, eps)
         torch.cuda.synchronize()
     ref = _ln64(rows, one, zero, eps)
     assert float((ref - sign.to(DEV).double() * ref_v).abs().max()) < 1e-12
     err = float((of.double() - ref).abs().max())
     print(f"rowln tiles eps={eps} bf16={bf16}: max |out_f32 - ref| {err:.2e} at |ref| {ref_v:.4f}")
-    _note("eps", bf16, out_f32=err)
+    _worst.note("eps", bf16, out_f32=err)
     assert err < TOL32, err
-    _same16(oh, _bits16(of, bf16))
+    same_bits(oh, bits16(of, bf16))
 
 
 # ---- 5. zero variance -------------------------------------------------------------------------------------------------------------------
@@ -438,8 +379,6 @@ def test_zero_variance_rows(eps, bf16):
     """Every row a constant c in {0, 1, 7.3, 30, 1000} (through the residual, W = 0), random gamma and beta.  c = 0: exactly beta.  Otherwise the
     centred value is the rounding error of the mean -- mean = s * fl(1 / C): one rounding in fl(1 / C), one in the product, and the sum s of
     384 equal fp32 values -- at most |c| 2^-23, and the variance is its square, far below eps: |out - beta| <= |gamma| |c| 2^-23 / sqrt(eps)."""
-    import hip_helpers as hh
-
     M = 65
     g = np.random.Generator(np.random.PCG64(55))
     gam = torch.from_numpy(1.0 + 0.3 * g.standard_normal(C, dtype=np.float32)).to(DEV)
@@ -447,7 +386,7 @@ def test_zero_variance_rows(eps, bf16):
     c = torch.tensor([0.0, 1.0, 7.3, 30.0, 1000.0], device=DEV)[torch.arange(M, device=DEV) % 5]
     rows = c[:, None].repeat(1, C)
     A, W = torch.zeros(M, C, dtype=F16, device=DEV), torch.zeros(C, C, dtype=F16, device=DEV)
-    with _mode(bf16):
+    with hh.switches(bf16=bf16):
         of, oh = hh.linear_layernorm(A, W, torch.zeros(C, device=DEV), rows, gam, bet, eps)
         torch.cuda.synchronize()
     assert torch.isfinite(of).all()
@@ -456,12 +395,12 @@ def test_zero_variance_rows(eps, bf16):
     for j, cv in enumerate((0.0, 1.0, 7.3, 30.0, 1000.0)):
         print(f"rowln tiles constant rows c={cv} eps={eps} bf16={bf16}: max |out - beta| {float(dev_[j::5].max()):.2e} (bound at gamma = 1: "
               f"{cv * 2.0 ** -23 / math.sqrt(eps):.2e})")
-    _note("zero_variance", bf16, out_minus_beta=dev_.max(), over_bound=(dev_[c != 0] / bound[c != 0]).max())
+    _worst.note("zero_variance", bf16, out_minus_beta=dev_.max(), over_bound=(dev_[c != 0] / bound[c != 0]).max())
     assert (dev_ <= bound).all(), float((dev_ - bound).max())
     zr = c == 0
     assert torch.equal(of[zr], bet[None, :].expand(int(zr.sum()), C))
-    _same16(oh[zr], _bits16(bet, bf16)[None, :].expand(int(zr.sum()), C), "beta rounded once")
-    _same16(oh, _bits16(of, bf16))
+    same_bits(oh[zr], bits16(bet, bf16)[None, :].expand(int(zr.sum()), C), "beta rounded once")
+    same_bits(oh, bits16(of, bf16))
 
 
 # ---- 6. large common mean ---------------------------------------------------------------------------------------------------------------
@@ -473,19 +412,17 @@ def test_large_common_mean(offset, bf16):
     error is the fp32 rounding of values of size |offset| and of their mean.  E[x^2] - mean^2 in fp32 on the same rows misses this bound at
     offset -1000 (checked on the host with the same seed, here and in test_host_side_constructions: the variance of about 3 is the difference of
     two numbers of 1e6 whose fp32 spacing is 0.06)."""
-    import hip_helpers as hh
-
     d, _, ref, bound = _mean_case(offset, bf16, DEV)
     if offset == -1000.0:
         assert _single_pass_misses(offset, bf16) > 0.5
-    with _mode(bf16):
+    with hh.switches(bf16=bf16):
         of, oh = hh.linear_layernorm(d["A"], d["W"], d["b"], d["res"], d["gam"], d["bet"], 1e-5)
         torch.cuda.synchronize()
     err = (of.double() - ref).abs()
     print(f"rowln tiles offset={offset} bf16={bf16}: max |out_f32 - ref| {float(err.max()):.2e} (worst error / bound {float((err / bound).max()):.3f})")
-    _note("common_mean", bf16, out_f32=err.max(), over_bound=(err / bound).max())
+    _worst.note("common_mean", bf16, out_f32=err.max(), over_bound=(err / bound).max())
     assert torch.isfinite(of).all() and (err <= bound).all(), float(err.max())
-    _same16(oh, _bits16(of, bf16))
+    same_bits(oh, bits16(of, bf16))
 
 
 # ---- 7. row independence ----------------------------------------------------------------------------------------------------------------
@@ -496,11 +433,9 @@ def test_rows_are_independent_bit_for_bit(M, rs, bf16):
     """A lane holds 48 values of ONE row per row block and the row sums meet other rows only as neighbours in the LDS exchange: perturbing row r
     (activations and residual) changes row r of out_f32, out_f16 and out2 (n2 = 3 C) and not one bit of any other row.  M = 65, r = 64: the
     workgroup's 63 rows past M re-read row 64 (min(row, M - 1)); they are computed and dropped."""
-    import hip_helpers as hh
-
     d = _rand_case(M, 4242 + M, bf16, True, 3 * C)
     run = lambda A, res: hh.linear_layernorm_linear(A, d["W"], d["b"], res, d["gam"], d["bet"], 1e-5, d["W2"], d["b2"], 2, want_f32=True, want_f16=True)
-    with _mode(bf16):
+    with hh.switches(bf16=bf16):
         base = run(d["A"], d["res"])
         for r in rs:
             A, res = d["A"].clone(), d["res"].clone()
@@ -525,28 +460,27 @@ def test_same_answer_as_the_two_launch_form(bf16):
     rounding boundary, plus one more per whole spacing that fits into d).  d is a few fp32 ulps of the row's largest values, so the second
     term is 0 -- a single step at most -- everywhere but at values so close to zero that the 16-bit grid is finer than d (fp16 keeps 2^-24
     there); the spacing is taken at the smaller of the two magnitudes, halved for a binade edge between them."""
-    import hip_helpers as hh
     from crossscore_amd import _lib
 
     M = 129
     d = _rand_case(M, 808, bf16, True, 0)
-    with _mode(bf16):
+    with hh.switches(bf16=bf16):
         of, oh = hh.linear_layernorm(d["A"], d["W"], d["b"], d["res"], d["gam"], d["bet"], 1e-5)
         y = hh.gemm(d["A"], d["W"], d["b"], _lib.EPI_RESID_F32, resid=d["res"])
         of2, oh2 = hh.layernorm(y, d["gam"], d["bet"], 1e-5)
         torch.cuda.synchronize()
     e = float((of - of2).abs().max())
-    ulps = (_ordered16(oh) - _ordered16(oh2)).abs()
+    ulps = (ordered16(oh) - ordered16(oh2)).abs()
     dd = (of.double() - of2.double()).abs()
-    small = torch.minimum(_vals16(oh, bf16).abs(), _vals16(oh2, bf16).abs())
-    allowed = 1 + torch.floor(dd / (0.5 * _spacing16(small, bf16)))
+    small = torch.minimum(vals16(oh, bf16, F64).abs(), vals16(oh2, bf16, F64).abs())
+    allowed = 1 + torch.floor(dd / (0.5 * spacing16(small, bf16)))
     multi = ulps > 1
     print(f"rowln tiles two-launch form bf16={bf16}: max |out_f32 difference| {e:.2e}, 16-bit rows differ in {float((ulps > 0).float().mean()):.2%} "
           f"of the elements; more than one step apart: {int(multi.sum())} element(s), at most {int(ulps.max())} steps, the largest of them "
           f"|{float(small[multi].max()) if bool(multi.any()) else 0.0:.2e}|")
-    _note("two_launch", bf16, out_f32=e, steps=ulps.max(), largest_multi_step_value=small[multi].max() if bool(multi.any()) else 0.0)
+    _worst.note("two_launch", bf16, out_f32=e, steps=ulps.max(), largest_multi_step_value=small[multi].max() if bool(multi.any()) else 0.0)
     assert e < TOL32 and bool((ulps <= allowed).all()), (e, int(ulps.max()))
-    assert bool((ulps[dd < 0.5 * _spacing16(small, bf16)] <= 1).all())
+    assert bool((ulps[dd < 0.5 * spacing16(small, bf16)] <= 1).all())
 
 
 # ---- 9. refusals ------------------------------------------------------------------------------------------------------------------------
@@ -583,7 +517,7 @@ def test_refusals_leave_outputs_untouched(bf16):
         "out2 + 4 bytes": dict(o2=ptr["o2"] + 4), "M = 0": dict(M=0), "M = -1": dict(M=-1), "n2 = 2 C": dict(n2=2 * C),
         "no output, n2 = 0": dict(n2=0, of=None, oh=None), "W2 null": dict(W2=None),
     }
-    with _mode(bf16):
+    with hh.switches(bf16=bf16):
         for what, over in refused.items():
             with pytest.raises(ValueError):
                 _lib.check(call(**over))

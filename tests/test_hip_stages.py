@@ -20,11 +20,10 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from crossscore_amd import synth  # noqa: E402
-from crossscore_amd.config import model_config  # noqa: E402
-from crossscore_amd.model import CrossScoreNet  # noqa: E402
 from oracle import crossscore_oracle as orc  # noqa: E402
+import hip_helpers as hh  # noqa: E402
+from nets import SMALL, TINY, make_net  # noqa: E402
 
-TINY = "synthetic/dinov2-tiny"
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 # stage -> (mean |d| / rms(ref), max |d| / rms(ref)) bounds, fp16 operand mode
@@ -39,10 +38,8 @@ STAGE_TOL = {                                # measured on MI355X (r4), fp16 ope
 
 
 def _net(seed, **over):
-    net = CrossScoreNet(model_config(**{"backbone.from_pretrained": TINY, **over}))
-    sd = synth.make_state_dict(net.arch, seed)
-    net.load_numpy_state_dict(sd)
-    return net.cuda(), sd
+    net, _, sd = make_net(TINY, seed, **over)
+    return net, sd
 
 
 def _rel(got: torch.Tensor, ref: np.ndarray):
@@ -160,7 +157,6 @@ def test_bf16_stages_stay_within_the_bf16_budget():
 #      embedding, attention at dh 48 / 96 -- start at C = 384 / 768.  g8 holds the reference's module outputs at the ViT-S width (two encoder
 #      layers, 8 images x 57 tokens = 456 rows in one chunk: every routing condition of the full-size forward holds); at the ViT-B width the
 #      same taps are compared with the oracle's (pinned by g0 / g8 / g2). ----
-SMALL2 = "synthetic/dinov2-small-2l"
 BASE2 = "synthetic/dinov2-base-2l"
 # mean / max of |d| over the stage's RMS, fp16 operands; ~3x the values MI355X measured in r5 (stated per stage; the tests print theirs):
 WIDE_TOL = {                                  # measured, C = 384 (g8) / C = 768 (oracle), fp16: mean / max
@@ -181,14 +177,10 @@ def _check_wide(stage, key, got, ref, scale=1.0):
 
 
 def _wide_net(name, seed, dtype, lanes=1, **attrs):
-    net = CrossScoreNet(model_config(**{"backbone.from_pretrained": name}))
-    sd = synth.make_state_dict(net.arch, seed)
-    net.load_numpy_state_dict(sd)
-    net.operand_dtype = dtype
+    net, _, sd = make_net(name, seed, dtype)
     net.lanes = lanes
     for k, v in attrs.items():
         setattr(net, k, v)
-    net = net.cuda()
     net.debug_capture(True)
     return net, sd
 
@@ -210,23 +202,14 @@ def test_vits_width_stages_match_the_references_intermediates(dtype, variant):
     """g8 against the kernels of the ViT-S forward.  default: one chunk of 456 rows -> 256-tile GEMM (QKV, decoder K/V), cs_panel_kernel, cs_rowln_kernel,
     cs_patch_fused_kernel, attention dh 64 / 48.  two_lanes: chunks of 228 rows -> the 128-row GEMM at K = 384.  gemm128: cs_debug_gemm256_enable(0).
     unfused: enc_fused = 1 and cs_debug_rowln_enable(0) -> LayerNorm / GEMM / GELU-epilogue launches instead of the panel and row-complete kernels."""
-    from crossscore_amd import _lib
-    lib = _lib.load()
     g = np.load(os.path.join(GOLD, "g8_vits_width_all.npz"))
     B, N, H, W = int(g["B"]), int(g["N"]), int(g["H"]), int(g["W"])
     attrs = dict(enc_fused=1) if variant == "unfused" else {}
-    net, sd = _wide_net(SMALL2, int(g["seed"]), dtype, lanes=2 if variant == "two_lanes" else 1, **attrs)
+    net, sd = _wide_net(SMALL, int(g["seed"]), dtype, lanes=2 if variant == "two_lanes" else 1, **attrs)
     q, r = synth.make_inputs(B, N, H, W, int(g["seed"]))
-    try:
-        if variant == "gemm128":
-            lib.cs_debug_gemm256_enable(0)
-        if variant == "unfused":
-            lib.cs_debug_rowln_enable(0)
+    with hh.switches(gemm256=False if variant == "gemm128" else None, rowln=0 if variant == "unfused" else None):
         out = net(torch.from_numpy(q).cuda(), torch.from_numpy(r).cuda(), True, 3, False)
         torch.cuda.synchronize()
-    finally:
-        lib.cs_debug_gemm256_enable(1)
-        lib.cs_debug_rowln_enable(1)
     # which kernels ran (cs_forward_stats): the point of this test is that they are the ones the full-size forward runs
     k = net.forward_stats()["kernels"]
     print("kernels:", k)
@@ -260,19 +243,14 @@ def test_vitb_width_stages_match_the_oracle_taps(dtype, routing):
       ln_launches  (ln_fold = 2) LayerNorm kernels + the 256-tile GEMM's plain epilogues
       gemm256_off  (cs_debug_gemm256_enable(0) on a folded handle) the chunk must fall to LayerNorm launches + the 128-row kernel, whose
                    folded statistics layouts differ (ADVICE r5 #1: this used to fail inside cs_gemm_check)."""
-    from crossscore_amd import _lib
-    lib = _lib.load()
     over = {"ln_fold": 2} if routing == "ln_launches" else {}
     net, sd = _wide_net(BASE2, 9, dtype, **over)
     q, r = synth.make_inputs(2, 3, 98, 112, 9)
     taps = {}
     ref = orc.forward(orc.to_torch(sd), dict(enc_heads=net.arch.enc_heads), torch.from_numpy(q), torch.from_numpy(r), taps=taps)
-    lib.cs_debug_gemm256_enable(0 if routing == "gemm256_off" else 1)
-    try:
+    with hh.switches(gemm256=routing != "gemm256_off"):
         out = net(torch.from_numpy(q).cuda(), torch.from_numpy(r).cuda(), False, 0, False)
         torch.cuda.synchronize()
-    finally:
-        lib.cs_debug_gemm256_enable(1)
     k = net.forward_stats()["kernels"]
     print("kernels:", k)
     assert "panel" not in k and "rowln" not in k and k.get("attn64") == 2 and k.get("attn96") == 4, k

@@ -14,9 +14,9 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
 
 from nvs_tree import make_tree  # noqa: E402
-from test_jpeg_host import content, jpeg_bytes, probe  # noqa: E402
-from test_png_decode_driver import SMALL, _tiny_weights, _tree_bytes  # noqa: E402
-from test_predict_driver import TINY, _make_scene  # noqa: E402
+from jpeg_files import content, jpeg_bytes, probe  # noqa: E402
+from nets import SMALL, TINY, state_dict_for  # noqa: E402
+from scenes import make_scene, tree_bytes  # noqa: E402
 
 torch = pytest.importorskip("torch")
 
@@ -32,7 +32,7 @@ def scene(tmp_path_factory):
     (the host fallback inside a gpu run)."""
     from PIL import Image
 
-    qd, rd = _make_scene(str(tmp_path_factory.mktemp("scene")), n_query=5, n_ref=4, h=70, w=90)
+    qd, rd = make_scene(str(tmp_path_factory.mktemp("scene")), n_query=5, n_ref=4, h=70, w=90)
     for f in os.listdir(rd):
         os.remove(os.path.join(rd, f))
     buf = io.BytesIO()
@@ -58,7 +58,7 @@ def test_predict_is_the_same_with_either_jpeg_decoder(tmp_path, scene, cache):
     from crossscore_amd.predict import predict
 
     qd, rd = scene
-    sd = _tiny_weights(5, SMALL)
+    sd = state_dict_for(SMALL, 5)
     common = _common(qd, rd, SMALL, cache)
     runs = {}
     for name, extra in (("host", ["this_main.jpeg_decoder=host"]), ("absent", None), ("gpu", ["this_main.jpeg_decoder=gpu"]),
@@ -69,10 +69,10 @@ def test_predict_is_the_same_with_either_jpeg_decoder(tmp_path, scene, cache):
             del cfg.this_main["jpeg_decoder"]  # a config file written before the key existed
         with torch.no_grad():
             runs[name] = predict(cfg, state_dict=sd, now="T")
-    host = _tree_bytes(runs["host"]["out_dir"])
+    host = tree_bytes(runs["host"]["out_dir"])
     assert len(host) > 5 and any(k.endswith(".png") for k in host) and any(k.endswith(".csv") for k in host)
     for name in ("absent", "gpu", "both", "gpu1"):
-        got = _tree_bytes(runs[name]["out_dir"])
+        got = tree_bytes(runs[name]["out_dir"])
         assert sorted(got) == sorted(host), name
         for rel in host:
             assert got[rel] == host[rel], (name, rel)  # score-map PNGs, processed images, CSVs: byte for byte
@@ -95,7 +95,7 @@ def test_predict_rejects_an_unknown_value_and_a_corrupt_jpeg(tmp_path, scene):
     from crossscore_amd.predict import predict
 
     qd, rd = scene
-    sd = _tiny_weights(5)
+    sd = state_dict_for(TINY, 5)
     common = _common(qd, rd, TINY)
     with pytest.raises(ValueError, match="jpeg_decoder"):
         predict(load_config("default_predict", common + ["this_main.jpeg_decoder=pil", f"logger.predict.out_dir={tmp_path}/x"]), state_dict=sd, now="T")
@@ -133,7 +133,7 @@ def test_evaluate_is_the_same_with_either_jpeg_decoder(tmp_path, tmp_path_factor
                 out.write(jpeg_bytes(img, (2, 0, 1)[n % 3], quality=90, **(dict(restart_marker_rows=1) if n % 2 else {})))
             n += 1
     assert n > 4
-    sd = _tiny_weights(7)
+    sd = state_dict_for(TINY, 7)
     common = [f"data.dataset.path={tree}", f"model.backbone.from_pretrained={TINY}", "this_main.resize_short_side=56",
               "data.dataset.num_gaussians_iters=2", "data.loader.validation.batch_size=4", "data.loader.validation.num_workers=2",
               "data.neighbour_config.deterministic=True", "logger.test.write.flag.score_map_gt=True", "this_main.gt_metric_maps=compute"]
@@ -144,7 +144,7 @@ def test_evaluate_is_the_same_with_either_jpeg_decoder(tmp_path, tmp_path_factor
         with torch.no_grad():
             runs[name] = evaluate(load_config("default_test", common + [f"this_main.jpeg_decoder={name}", f"logger.test.out_dir={tmp_path}/out_{name}"]),
                                   state_dict=sd, now=f"NOW_{name}", capture=caps[name])
-    host, got = _tree_bytes(runs["host"]["out_dir"]), _tree_bytes(runs["gpu"]["out_dir"])
+    host, got = tree_bytes(runs["host"]["out_dir"]), tree_bytes(runs["gpu"]["out_dir"])
     assert "test_batches.csv" in host and sorted(got) == sorted(host)
     for rel in host:
         assert got[rel] == host[rel], rel

@@ -17,7 +17,7 @@ sys.path.insert(0, HERE)
 import jpeg_oracle  # noqa: E402
 from crossscore_amd import _lib  # noqa: E402
 from guard import guarded  # noqa: E402
-from test_jpeg_host import SAMPLINGS, content, grid_files, jpeg_bytes, probe  # noqa: E402
+from jpeg_files import SAMPLINGS, content, grid_files, jpeg_bytes, probe  # noqa: E402
 
 
 def expected(data: bytes) -> np.ndarray:

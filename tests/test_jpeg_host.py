@@ -17,84 +17,9 @@ sys.path.insert(0, HERE)
 import jpeg_oracle  # noqa: E402
 from crossscore_amd import _lib  # noqa: E402
 from crossscore_amd.config import load_config  # noqa: E402
+from jpeg_files import SAMPLING_CODE, SAMPLINGS, adobe_spliced, as_440, content, grid_files, jpeg_bytes, pil_array, probe  # noqa: E402
 
-SAMPLINGS = (0, 1, 2, "gray")  # PIL's subsampling 0 (4:4:4), 1 (4:2:2), 2 (4:2:0); a one-component file
-SAMPLING_CODE = {"gray": _lib.JPEG_GRAY, 0: _lib.JPEG_444, 1: _lib.JPEG_422, 2: _lib.JPEG_420}
-SIZES = [(8, 8), (16, 16), (17, 23), (9, 31), (33, 50), (1, 1)]  # (H, W); 1 x 1 for 4:4:4 and gray only (subsampled files need W >= 5)
-CONTENTS = ("smooth", "noise", "mix")
-QUALITY = [dict(quality=30), dict(quality=90), dict(quality=100), dict(quality=90, optimize=True)]
-RESTARTS = [dict(), dict(restart_marker_blocks=1), dict(restart_marker_blocks=3), dict(restart_marker_rows=1)]
 NEW_SYMBOLS = ("cs_jpeg_probe", "cs_jpeg_decode_workspace_bytes", "cs_op_jpeg_decode")
-
-
-def content(kind: str, h: int, w: int, seed: int = 0) -> np.ndarray:
-    """(h, w, 3) uint8: smooth waves, uniform noise, or waves under Gaussian noise"""
-    rng = np.random.default_rng(seed * 1000 + h * 37 + w)
-    y, x = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    waves = np.stack([128 + 100 * np.sin(y / 7 + c) * np.cos(x / 9 - c) for c in range(3)], axis=-1)
-    if kind == "smooth":
-        a = waves
-    elif kind == "noise":
-        a = rng.integers(0, 256, size=(h, w, 3))
-    else:
-        a = waves + rng.normal(0, 20, size=(h, w, 3))
-    return np.clip(a, 0, 255).astype(np.uint8)
-
-
-def jpeg_bytes(img: np.ndarray, sampling=2, **kw) -> bytes:
-    """img (h, w, 3) written by PIL: sampling 0 / 1 / 2 as PIL's subsampling, "gray" as a one-component file of channel 0"""
-    from PIL import Image
-
-    buf = io.BytesIO()
-    if sampling == "gray":
-        Image.fromarray(img[:, :, 0]).save(buf, format="JPEG", **kw)
-    else:
-        Image.fromarray(img).save(buf, format="JPEG", subsampling=sampling, **kw)
-    return buf.getvalue()
-
-
-def pil_array(data: bytes) -> np.ndarray:
-    from PIL import Image
-
-    return np.array(Image.open(io.BytesIO(data)))
-
-
-def grid_files(sizes=SIZES, samplings=SAMPLINGS, contents=CONTENTS, quality=QUALITY, restarts=RESTARTS):
-    """(name, bytes) over the grid: every quality form without restart markers, every restart form at quality 90, and quality 30 / 100 with
-    optimised tables under restart_marker_blocks=3"""
-    forms = [dict(q) for q in quality] + [dict(quality=90, **r) for r in restarts if r]
-    if any(r for r in restarts):
-        forms += [dict(quality=30, optimize=True, restart_marker_blocks=3), dict(quality=100, optimize=True, restart_marker_rows=1)]
-    for h, w in sizes:
-        for s in samplings:
-            if s in (1, 2) and w < 5:
-                continue
-            for kind in contents:
-                img = content(kind, h, w)
-                for form in forms:
-                    yield f"{h}x{w} {s} {kind} {form}", jpeg_bytes(img, s, **form)
-
-
-def probe(data: bytes, n=None):
-    lib = _lib.load()
-    info = _lib.CsJpegInfo()
-    rc = lib.cs_jpeg_probe(data, len(data) if n is None else n, C.byref(info))
-    return rc, info
-
-
-def adobe_spliced(data: bytes) -> bytes:
-    """a 12-byte Adobe APP14 segment (transform 1) behind SOI"""
-    return data[:2] + b"\xff\xee\x00\x0eAdobe\x00\x64\x00\x00\x00\x00\x01" + data[2:]
-
-
-def as_440(data_422: bytes) -> bytes:
-    """The header of a 4:4:0 frame: luma 1 x 2 in the SOF of a file PIL wrote as 4:2:2 (this PIL's writer takes 0 / 1 / 2 only, so the file is
-    made here; the probe reads headers)."""
-    d = bytearray(data_422)
-    k = d.find(b"\xff\xc0")
-    assert d[k + 11] == 0x21
-    d[k + 11] = 0x12
-    return bytes(d)
 
 
 def test_new_symbols_declared_listed_and_exported():

@@ -13,9 +13,9 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
 
 from nvs_tree import make_tree  # noqa: E402
-from test_jpeg_host import content, jpeg_bytes  # noqa: E402
-from test_png_decode_driver import SMALL, _tiny_weights, _tree_bytes  # noqa: E402
-from test_predict_driver import TINY, _make_scene  # noqa: E402
+from jpeg_files import content, jpeg_bytes  # noqa: E402
+from nets import SMALL, TINY, state_dict_for  # noqa: E402
+from scenes import make_scene, tree_bytes  # noqa: E402
 
 torch = pytest.importorskip("torch")
 GPU = ["this_main.jpeg_decoder=gpu", "this_main.jpeg_progressive=gpu"]
@@ -31,7 +31,7 @@ def _in_tmp(tmp_path, monkeypatch):
 def scene(tmp_path_factory):
     """5 PNG queries and 4 JPEG references of 70 x 90 (-> 56 x 72), half of them progressive: 4:2:0 baseline, 4:4:4 progressive with restart
     markers, 4:2:2 baseline under a .png name, 4:2:0 progressive"""
-    qd, rd = _make_scene(str(tmp_path_factory.mktemp("scene")), n_query=5, n_ref=4, h=70, w=90)
+    qd, rd = make_scene(str(tmp_path_factory.mktemp("scene")), n_query=5, n_ref=4, h=70, w=90)
     for f in os.listdir(rd):
         os.remove(os.path.join(rd, f))
     refs = {"ref_0.jpg": jpeg_bytes(content("mix", 70, 90, seed=11), 2, quality=90),
@@ -56,16 +56,16 @@ def test_predict_is_the_same_with_progressive_files_on_the_device(tmp_path, scen
     from crossscore_amd.predict import predict
 
     qd, rd = scene
-    sd = _tiny_weights(5, SMALL)
+    sd = state_dict_for(SMALL, 5)
     common = _common(qd, rd, SMALL, cache, fused)
     runs = {}
     for name, extra in (("host", []), ("jpeg", ["this_main.jpeg_decoder=gpu"]), ("gpu", GPU)):
         with torch.no_grad():
             runs[name] = predict(load_config("default_predict", common + extra + [f"logger.predict.out_dir={tmp_path}/out_{name}"]), state_dict=sd, now="T")
-    host = _tree_bytes(runs["host"]["out_dir"])
+    host = tree_bytes(runs["host"]["out_dir"])
     assert len(host) > 5 and any(k.endswith(".png") for k in host) and any(k.endswith(".csv") for k in host)
     for name in ("jpeg", "gpu"):
-        got = _tree_bytes(runs[name]["out_dir"])
+        got = tree_bytes(runs[name]["out_dir"])
         assert sorted(got) == sorted(host), name
         for rel in host:
             assert got[rel] == host[rel], (name, rel)  # score-map PNGs, processed images, CSVs: byte for byte
@@ -89,7 +89,7 @@ def test_the_new_key_alone_raises(tmp_path, scene):
     from crossscore_amd.predict import predict
 
     qd, rd = scene
-    sd = _tiny_weights(5)
+    sd = state_dict_for(TINY, 5)
     for extra in (["this_main.jpeg_progressive=gpu"], ["this_main.jpeg_decoder=gpu", "this_main.jpeg_progressive=pil"]):
         with pytest.raises(ValueError, match="jpeg_progressive"):
             predict(load_config("default_predict", _common(qd, rd, TINY) + extra + [f"logger.predict.out_dir={tmp_path}/x"]), state_dict=sd, now="T")
@@ -124,7 +124,7 @@ def test_evaluate_is_the_same_with_progressive_files_on_the_device(tmp_path, tmp
 
     tree = make_tree(tmp_path_factory.mktemp("nvs"))
     assert _jpeg_gt(tree) > 4
-    sd = _tiny_weights(7)
+    sd = state_dict_for(TINY, 7)
     common = [f"data.dataset.path={tree}", f"model.backbone.from_pretrained={TINY}", "this_main.resize_short_side=56",
               "data.dataset.num_gaussians_iters=2", "data.loader.validation.batch_size=4", "data.loader.validation.num_workers=2",
               "data.neighbour_config.deterministic=True", "logger.test.write.flag.score_map_gt=True", "this_main.gt_metric_maps=compute"]
@@ -135,7 +135,7 @@ def test_evaluate_is_the_same_with_progressive_files_on_the_device(tmp_path, tmp
         with torch.no_grad():
             runs[name] = evaluate(load_config("default_test", common + extra + [f"logger.test.out_dir={tmp_path}/out_{name}"]),
                                   state_dict=sd, now=f"NOW_{name}", capture=caps[name])
-    host, got = _tree_bytes(runs["host"]["out_dir"]), _tree_bytes(runs["gpu"]["out_dir"])
+    host, got = tree_bytes(runs["host"]["out_dir"]), tree_bytes(runs["gpu"]["out_dir"])
     assert "test_batches.csv" in host and sorted(got) == sorted(host)
     for rel in host:
         assert got[rel] == host[rel], rel

@@ -19,8 +19,7 @@ import jpeg_oracle  # noqa: E402
 import jpeg_progressive_oracle as prog  # noqa: E402
 from crossscore_amd import _lib  # noqa: E402
 from guard import guarded  # noqa: E402
-from test_jpeg_host import content, jpeg_bytes, pil_array  # noqa: E402
-from test_jpeg_progressive_host import PIL_SCRIPT, SCRIPTS, patch_sos, probe_ex, progressive_grid, recoded  # noqa: E402
+from jpeg_files import PIL_SCRIPT, SCRIPTS, content, jpeg_bytes, patch_sos, pil_array, probe_ex, progressive_grid, recoded  # noqa: E402
 
 P = _lib.JPEG_PROGRESSIVE
 

@@ -18,68 +18,14 @@ import jpeg_oracle  # noqa: E402
 import jpeg_progressive_oracle as prog  # noqa: E402
 from crossscore_amd import _lib  # noqa: E402
 from crossscore_amd.config import load_config  # noqa: E402
-from test_jpeg_host import SAMPLING_CODE, SAMPLINGS, adobe_spliced, content, jpeg_bytes, pil_array, probe  # noqa: E402
+from jpeg_files import (GRID_FORMS, PIL_SCRIPT, SAMPLING_CODE, SCRIPTS, adobe_spliced, content, jpeg_bytes, patch_sos, pil_array, probe, probe_ex,  # noqa: E402
+                        progressive_grid, recoded)
 
 NEW_SYMBOLS = ("cs_jpeg_probe_ex", "cs_jpeg_decode_workspace_bytes_ex", "cs_op_jpeg_decode_ex", "cs_debug_jpeg_scan_levels")
-# (H, W, samplings): 5 x 5 is the smallest subsampled file, 1 x 1 gray the smallest of all
-GRID_SIZES = [(8, 8, SAMPLINGS), (9, 11, SAMPLINGS), (17, 23, SAMPLINGS), (33, 47, SAMPLINGS), (5, 5, (2,)), (1, 1, ("gray",))]
-GRID_FORMS = [dict(quality=30), dict(quality=75, optimize=True), dict(quality=95), dict(quality=100),
-              dict(quality=75, restart_marker_blocks=1), dict(quality=95, restart_marker_blocks=3), dict(quality=30, optimize=True, restart_marker_blocks=3)]
-
-# the scan script of libjpeg's jpeg_simple_progression for three components: what PIL writes
-PIL_SCRIPT = [((0, 1, 2), 0, 0, 0, 1), ((0,), 1, 5, 0, 2), ((2,), 1, 63, 0, 1), ((1,), 1, 63, 0, 1), ((0,), 6, 63, 0, 2), ((0,), 1, 63, 2, 1),
-              ((0, 1, 2), 0, 0, 1, 0), ((2,), 1, 63, 1, 0), ((1,), 1, 63, 1, 0), ((0,), 1, 63, 1, 0)]
-# scripts PIL never writes, each legal and complete, none above 32 scans
-SCRIPTS = {
-    "spectral selection only": [((0, 1, 2), 0, 0, 0, 0), ((0,), 1, 5, 0, 0), ((1,), 1, 63, 0, 0), ((2,), 1, 63, 0, 0), ((0,), 6, 63, 0, 0)],
-    "non-interleaved DC": [((0,), 0, 0, 0, 1), ((1,), 0, 0, 0, 0), ((2,), 0, 0, 0, 0), ((0,), 0, 0, 1, 0), ((0,), 1, 63, 0, 0), ((1,), 1, 63, 0, 0),
-                           ((2,), 1, 63, 0, 0)],
-    "chain 3 2 1 0": ([((0, 1, 2), 0, 0, 0, 3), ((0, 1, 2), 0, 0, 3, 2), ((0, 1, 2), 0, 0, 2, 1), ((0, 1, 2), 0, 0, 1, 0)] +
-                      [((c,), 1, 63, 0, 3) for c in range(3)] + [((c,), 1, 63, a + 1, a) for a in (2, 1, 0) for c in range(3)]),
-    "single-coefficient bands": ([((0, 1, 2), 0, 0, 0, 0)] + [((0,), k, k, 0, 0) for k in range(1, 25)] +
-                                 [((0,), 25, 63, 0, 0), ((1,), 1, 63, 0, 0), ((2,), 1, 63, 0, 0)]),
-    "chroma AC before luma AC": [((0, 1, 2), 0, 0, 0, 0), ((1,), 1, 63, 0, 1), ((2,), 1, 63, 0, 1), ((1,), 1, 63, 1, 0), ((2,), 1, 63, 1, 0),
-                                 ((0,), 1, 63, 0, 1), ((0,), 1, 63, 1, 0)],
-}
-
-
-def progressive_grid(sizes=GRID_SIZES, forms=GRID_FORMS):
-    """(name, progressive file, its baseline twin: the same image and settings) over sampling x quality x optimize x restart x sizes"""
-    for h, w, samplings in sizes:
-        for s in samplings:
-            img = content("mix", h, w, seed=h)
-            for form in forms:
-                yield f"{h}x{w} {s} {form}", jpeg_bytes(img, s, progressive=True, **form), jpeg_bytes(img, s, **form)
-
-
-def recoded(script, sampling=2, h=33, w=47, restart=0, quality=90, seed=3):
-    """(file under `script`, its baseline twin); the PIL condition is asserted here: PIL opens the file and returns the twin's pixels exactly"""
-    twin = jpeg_bytes(content("mix", h, w, seed=seed), sampling, quality=quality)
-    hdr = jpeg_oracle.parse(twin)
-    data = prog.write_progressive(jpeg_oracle.coefficients(twin, hdr), hdr, script, restart=restart)
-    assert np.array_equal(pil_array(data), pil_array(twin)), "the re-coder's file is not what PIL makes of the twin"
-    return data, twin
-
-
-def probe_ex(data: bytes, flags=_lib.JPEG_PROGRESSIVE, n=None):
-    lib = _lib.load()
-    info, scans = _lib.CsJpegInfo(), _lib.CsJpegScanInfo()
-    rc = lib.cs_jpeg_probe_ex(data, len(data) if n is None else n, flags, C.byref(info), C.byref(scans))
-    return rc, info, scans
 
 
 def fields(info):
     return tuple(getattr(info, name) for name, _ in info._fields_)
-
-
-def patch_sos(data: bytes, scan: int, **kw) -> bytes:
-    """scan `scan` (from 0) with Ss / Se / Ah / Al replaced"""
-    sc = prog.parse(data)["scans"][scan]
-    at = sc["start"] - 3
-    ss, se, ahal = data[at], data[at + 1], data[at + 2]
-    ss, se = kw.get("ss", ss), kw.get("se", se)
-    ah, al = kw.get("ah", ahal >> 4), kw.get("al", ahal & 15)
-    return data[:at] + bytes([ss, se, ah << 4 | al]) + data[at + 3:]
 
 
 def drop_scan(data: bytes, scan: int) -> bytes:

@@ -1,7 +1,7 @@
 """cs_op_png_encode_ex: the device PNG encoder's opt-in forms (CS_PNG_DYNAMIC: dynamic-Huffman blocks chosen per segment among four exactly
 priced forms; CS_PNG_ADAPTIVE_FILTER: the per-row minimum-sum-of-absolute-differences filter).  Host-side contract on the CPU, files on the GPU.
 
-Every file goes through test_png_encoder's validator: its own chunk parser with CRCs, zlib.decompress over the concatenated IDAT payloads
+Every file goes through the validator of tests/png_files.py: its own chunk parser with CRCs, zlib.decompress over the concatenated IDAT payloads
 (Adler-32 and every code table), the un-filter, and PIL's pixels."""
 import ctypes as C
 import functools
@@ -21,7 +21,7 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
 from crossscore_amd import _lib  # noqa: E402
 from crossscore_amd.config import load_config  # noqa: E402
-from test_png_encoder import GRAY16, RGB8, _contents, check_png, filtered_size, parse_chunks, row_bytes  # noqa: E402
+from png_files import GRAY16, RGB8, check_png, contents, encode_raw, filtered_size, parse_chunks, row_bytes  # noqa: E402
 
 DYNAMIC, ADAPTIVE = 1, 2
 SEG = 16384
@@ -138,7 +138,7 @@ def _first_btype(data: bytes) -> int:
 
 @functools.lru_cache(maxsize=None)
 def _images(kind, h, w):
-    return _contents(kind, h, w)
+    return contents(kind, h, w)
 
 
 @functools.lru_cache(maxsize=None)
@@ -153,10 +153,8 @@ def _plain_lengths(kind, h, w):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind", [GRAY16, RGB8])
 def test_flags_zero_is_the_old_encoder_byte_for_byte(kind):
-    from test_png_encoder import _encode_raw
-
     imgs = _images(kind, 75, 91)
-    old, _, _ = _encode_raw(_to_dev(imgs, kind), kind)
+    old, _, _ = encode_raw(_to_dev(imgs, kind), kind)
     new, _, _, _ = _encode_ex(imgs, kind, 0)
     assert old == new
 

@@ -13,8 +13,9 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
 
 from nvs_tree import make_tree  # noqa: E402
-from test_png_encoder import parse_chunks  # noqa: E402
-from test_predict_driver import TINY, _make_scene  # noqa: E402
+from png_files import parse_chunks  # noqa: E402
+from scenes import make_scene, tree_bytes  # noqa: E402
+from nets import TINY  # noqa: E402
 
 torch = pytest.importorskip("torch")
 
@@ -22,10 +23,6 @@ torch = pytest.importorskip("torch")
 @pytest.fixture(autouse=True)
 def _in_tmp(tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)  # evaluate's log/<now>/... directories land here
-
-
-def _tree(root):
-    return {os.path.relpath(os.path.join(d, f), root): open(os.path.join(d, f), "rb").read() for d, _, fs in os.walk(root) for f in fs}
 
 
 def _compare_trees(fast, compact, host=None, host_compact=None):
@@ -63,7 +60,7 @@ def test_predict_fast_and_compact(tmp_path):
     from crossscore_amd.model import CrossScoreNet
     from crossscore_amd.predict import predict
 
-    qd, rd = _make_scene(str(tmp_path / "data"), n_query=5, n_ref=4)
+    qd, rd = make_scene(str(tmp_path / "data"), n_query=5, n_ref=4)
     arch = CrossScoreNet(model_config(**{"backbone.from_pretrained": TINY})).arch
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, 5).items()}
     common = [f"data.dataset.query_dir={qd}", f"data.dataset.reference_dir={rd}", f"model.backbone.from_pretrained={TINY}",
@@ -76,7 +73,7 @@ def test_predict_fast_and_compact(tmp_path):
         np.random.seed(0)
         with torch.no_grad():
             runs[name] = predict(load_config("default_predict", common + extra + [f"logger.predict.out_dir={tmp_path}/out_{name}"]), state_dict=sd, now="T")
-    trees = {k: _tree(r["out_dir"]) for k, r in runs.items()}
+    trees = {k: tree_bytes(r["out_dir"]) for k, r in runs.items()}
     _compare_trees(trees["fast"], trees["compact"], trees["host"], trees["host_compact"])
     assert runs["fast"]["rows"] == runs["compact"]["rows"] == runs["host"]["rows"]
     assert runs["fast"]["png_compression"] == "fast" and runs["compact"]["png_compression"] == "compact" and runs["host"]["png_compression"] == "fast"
@@ -106,7 +103,7 @@ def test_evaluate_fast_and_compact(tmp_path, tmp_path_factory):
         np.random.seed(0)
         with torch.no_grad():
             runs[name] = evaluate(load_config("default_test", common + extra + [f"logger.test.out_dir={tmp_path}/out_{name}"]), state_dict=sd, now=f"NOW_{name}")
-    trees = {k: _tree(r["out_dir"]) for k, r in runs.items()}
+    trees = {k: tree_bytes(r["out_dir"]) for k, r in runs.items()}
     _compare_trees(trees["fast"], trees["compact"], trees["host"], trees["host_compact"])
     assert repr(runs["fast"]["metrics"]) == repr(runs["compact"]["metrics"]) == repr(runs["host"]["metrics"])
     assert [runs[k]["png_compression"] for k in ("fast", "compact", "host", "host_compact")] == ["fast", "compact", "fast", "compact"]
@@ -121,9 +118,9 @@ def test_metric_maps_fast_and_compact(tmp_path):
     res, trees = {}, {}
     for name, extra in (("fast", []), ("compact", ["this_main.png_compression=compact"])):
         root = make_tree(tmp_path / name, scenes=["scene_b"])  # the smallest scene: 60 x 84, no metric_map directory yet
-        before = set(_tree(root))
+        before = set(tree_bytes(root))
         res[name] = generate(load_config("default_test", [f"data.dataset.path={root}", "data.dataset.num_gaussians_iters=-1"] + extra))
-        trees[name] = {k: v for k, v in _tree(root).items() if k not in before}
+        trees[name] = {k: v for k, v in tree_bytes(root).items() if k not in before}
         assert len(trees[name]) == len(res[name]["written"]) == res[name]["png_gpu_files"] >= 2 and all(k.endswith(".png") for k in trees[name])
     assert res["fast"]["png_compression"] == "fast" and res["compact"]["png_compression"] == "compact"
     _compare_trees(trees["fast"], trees["compact"])

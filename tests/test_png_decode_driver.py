@@ -12,9 +12,10 @@ REPO = os.path.dirname(HERE)
 sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
 
+from nets import SMALL, TINY, state_dict_for  # noqa: E402
 from nvs_tree import make_tree  # noqa: E402
-from test_png_decoder import _interlaced_png, image_of, pil_png  # noqa: E402
-from test_predict_driver import TINY, _make_scene  # noqa: E402
+from png_files import image_of, interlaced_png, pil_png  # noqa: E402
+from scenes import make_scene, tree_bytes  # noqa: E402
 
 torch = pytest.importorskip("torch")
 
@@ -24,37 +25,16 @@ def _in_tmp(tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)  # evaluate's log/<now>/... directories land here
 
 
-def _tree_bytes(out_dir):
-    files = {}
-    for d, _, fs in os.walk(out_dir):
-        for f in fs:
-            p = os.path.join(d, f)
-            files[os.path.relpath(p, out_dir)] = open(p, "rb").read()
-    return files
-
-
-SMALL = "synthetic/dinov2-small-2l"  # the ViT-S width: what the one-pass input stage takes (tests/test_predict_driver.py)
-
-
-def _tiny_weights(seed, back=TINY):
-    from crossscore_amd import synth
-    from crossscore_amd.config import model_config
-    from crossscore_amd.model import CrossScoreNet
-
-    arch = CrossScoreNet(model_config(**{"backbone.from_pretrained": back})).arch
-    return {k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, seed).items()}
-
-
 @pytest.fixture(scope="module")
 def scene(tmp_path_factory):
     """5 queries, 4 references of 70 x 90 (-> 56 x 72: the one-launch patch embedding takes even widths); query 1 is an RGBA file (alpha dropped on the device), query 2 an interlaced one (the host fallback inside
     a gpu run)."""
-    qd, rd = _make_scene(str(tmp_path_factory.mktemp("scene")), n_query=5, n_ref=4, h=70, w=90)
+    qd, rd = make_scene(str(tmp_path_factory.mktemp("scene")), n_query=5, n_ref=4, h=70, w=90)
     rng = np.random.default_rng(3)
     with open(os.path.join(qd, "frame_00001.png"), "wb") as f:
         f.write(pil_png(image_of(rng, 70, 90, "rgba")))
     with open(os.path.join(qd, "frame_00002.png"), "wb") as f:
-        f.write(_interlaced_png(image_of(rng, 70, 90, "rgb")))
+        f.write(interlaced_png(image_of(rng, 70, 90, "rgb")))
     return qd, rd
 
 
@@ -66,7 +46,7 @@ def test_predict_is_the_same_with_either_decoder(tmp_path, scene, cache, one_pas
     from crossscore_amd.predict import predict
 
     qd, rd = scene
-    sd = _tiny_weights(5, SMALL)
+    sd = state_dict_for(SMALL, 5)
     common = [f"data.dataset.query_dir={qd}", f"data.dataset.reference_dir={rd}", f"model.backbone.from_pretrained={SMALL}",
               "this_main.resize_short_side=56", "data.neighbour_config.cross=3", "data.neighbour_config.deterministic=False",
               "data.loader.validation.batch_size=2", f"this_main.cache_reference_tokens={cache}", f"this_main.fused_input_stage={one_pass}"]
@@ -78,10 +58,10 @@ def test_predict_is_the_same_with_either_decoder(tmp_path, scene, cache, one_pas
                         ("gpu", ["this_main.png_decoder=gpu"]), ("gpu1000", ["this_main.png_decoder=gpu", "this_main.png_decode_window=1000"])):
         with torch.no_grad():
             runs[name] = predict(load_config("default_predict", common + extra + [f"logger.predict.out_dir={tmp_path}/out_{name}"]), state_dict=sd, now="T")
-    host = _tree_bytes(runs["host"]["out_dir"])
+    host = tree_bytes(runs["host"]["out_dir"])
     assert len(host) > 5 and any(k.endswith(".png") for k in host) and any(k.endswith(".csv") for k in host)
     for name in ("plain", "gpu1", "gpu", "gpu1000"):
-        got = _tree_bytes(runs[name]["out_dir"])
+        got = tree_bytes(runs[name]["out_dir"])
         assert sorted(got) == sorted(host), name
         for rel in host:
             assert got[rel] == host[rel], (name, rel)  # score-map PNGs, processed images, CSVs: byte for byte
@@ -103,7 +83,7 @@ def test_predict_rejects_an_unknown_decoder_and_a_damaged_file(tmp_path, scene):
     from crossscore_amd.predict import predict
 
     qd, rd = scene
-    sd = _tiny_weights(5)
+    sd = state_dict_for(TINY, 5)
     common = [f"data.dataset.query_dir={qd}", f"data.dataset.reference_dir={rd}", f"model.backbone.from_pretrained={TINY}",
               "this_main.resize_short_side=56", "data.neighbour_config.cross=3", "data.loader.validation.batch_size=2"]
     with pytest.raises(ValueError, match="png_decoder"):
@@ -132,7 +112,7 @@ def test_evaluate_is_the_same_with_either_decoder(tmp_path, tmp_path_factory, gt
     from crossscore_amd.evaluate import evaluate
 
     tree = make_tree(tmp_path_factory.mktemp("nvs"))
-    sd = _tiny_weights(7)
+    sd = state_dict_for(TINY, 7)
     common = [f"data.dataset.path={tree}", f"model.backbone.from_pretrained={TINY}", "this_main.resize_short_side=56",
               "data.dataset.num_gaussians_iters=2", "data.loader.validation.batch_size=4", "data.loader.validation.num_workers=2",
               "data.neighbour_config.deterministic=True", "logger.test.write.flag.score_map_gt=True", f"this_main.gt_metric_maps={gt_metric_maps}"]
@@ -144,11 +124,11 @@ def test_evaluate_is_the_same_with_either_decoder(tmp_path, tmp_path_factory, gt
         with torch.no_grad():
             runs[name] = evaluate(load_config("default_test", common + extra + [f"logger.test.out_dir={tmp_path}/out_{name}"]), state_dict=sd, now=f"NOW_{name}",
                                   capture=caps[name])
-    host = _tree_bytes(runs["host"]["out_dir"])
+    host = tree_bytes(runs["host"]["out_dir"])
     assert "test_batches.csv" in host and any(k.endswith(".png") for k in host)
     metrics = open(os.path.join(runs["host"]["version_dir"], "metrics.csv"), "rb").read()
     for name in ("gpu", "gpu3"):
-        got = _tree_bytes(runs[name]["out_dir"])
+        got = tree_bytes(runs[name]["out_dir"])
         assert sorted(got) == sorted(host)
         for rel in host:
             assert got[rel] == host[rel], (name, rel)

@@ -1,6 +1,6 @@
 """The device PNG decoder (csrc/pngdec.hip, cs_png_probe / cs_op_png_decode, decode.ImageDecoder): every decoded image equals, bit for bit, what
 read_image_u8 / read_metric_map_u16 make of PIL's array for the same bytes; hand-made streams are checked against zlib.decompress plus the
-un-filter of tests/test_png_encoder.py.  No tolerances.  Malformed files end with their documented status beside good files that still decode."""
+un-filter of tests/png_files.py.  No tolerances.  Malformed files end with their documented status beside good files that still decode."""
 import ctypes as C
 import io
 import os
@@ -20,10 +20,8 @@ sys.path.insert(0, HERE)
 from crossscore_amd import _lib  # noqa: E402
 from crossscore_amd.config import load_config  # noqa: E402
 from guard import guarded  # noqa: E402
-from test_png_encoder import unfilter  # noqa: E402
+from png_files import GRAY16, RGB8, SIGNATURE, chunk, encode_raw, ihdr, image_of, interlaced_png, pil_png, unfilter  # noqa: E402
 
-GRAY16, RGB8 = 0, 1
-SIGNATURE = b"\x89PNG\r\n\x1a\n"
 NEW_SYMBOLS = ("cs_png_probe", "cs_png_decode_workspace_bytes", "cs_op_png_decode")
 # (colour type, bit depth) -> (bytes per pixel, output kind)
 FORMS = {"gray8": (0, 8, 1, RGB8), "gray16": (0, 16, 2, GRAY16), "rgb": (2, 8, 3, RGB8), "rgba": (6, 8, 4, RGB8)}
@@ -31,14 +29,6 @@ SIZES = [(1, 1), (1, 7), (7, 1), (14, 14), (75, 91)]
 
 
 # ------------------------------------------------------------------------------------------------------------ a PNG writer
-def chunk(typ: bytes, payload: bytes, crc=None) -> bytes:
-    return struct.pack(">I", len(payload)) + typ + payload + struct.pack(">I", zlib.crc32(typ + payload) if crc is None else crc)
-
-
-def ihdr(h, w, ct, depth, interlace=0) -> bytes:
-    return chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, depth, ct, 0, 0, interlace))
-
-
 def split_at(data: bytes, cuts):
     """data cut at the byte positions `cuts` (sorted; repeated positions give empty pieces)"""
     pieces, a = [], 0
@@ -104,28 +94,11 @@ def write_png(img, form, ftypes=None, level=6, strategy=zlib.Z_DEFAULT_STRATEGY,
     return png_file(h, w, form, deflate(apply_filters(raw, FORMS[form][2], ftypes), level, strategy), cuts, front)
 
 
-def pil_png(img, **kw) -> bytes:
-    from PIL import Image
-
-    buf = io.BytesIO()
-    Image.fromarray(img).save(buf, format="PNG", **kw)
-    return buf.getvalue()
-
-
 def expected(data: bytes, kind: int) -> np.ndarray:
     """the host readers' array for a file's bytes (they take anything PIL opens)"""
     from crossscore_amd.decode import read_image_u8, read_metric_map_u16
 
     return (read_metric_map_u16 if kind == GRAY16 else read_image_u8)(io.BytesIO(data))
-
-
-def image_of(rng, h, w, form):
-    if form == "gray16":
-        return rng.integers(0, 65536, size=(h, w)).astype(np.uint16)
-    c = {"gray8": (), "rgb": (3,), "rgba": (4,)}[form]
-    base = rng.integers(0, 256, size=(h, w) + c).astype(np.int64)
-    ramp = (np.arange(h)[:, None] * 5 + np.arange(w)[None, :] * 3).reshape((h, w) + (1,) * len(c))
-    return ((base // 8 + ramp) % 256).astype(np.uint8)  # locally smooth: every filter type and real matches
 
 
 def smooth_noise(rng, h, w):
@@ -474,7 +447,6 @@ def test_pil_written_content(optimize):
 @pytest.mark.parametrize("h,w", [(75, 91), (518, 686)])
 def test_round_trip_with_the_device_encoder(kind, h, w):
     """cs_op_png_encode -> cs_op_png_decode: one IDAT chunk per 16-KiB segment, so this is also the many-chunk case."""
-    from test_png_encoder import _encode_raw
 
     rng = np.random.default_rng(30)
     if kind == GRAY16:
@@ -483,7 +455,7 @@ def test_round_trip_with_the_device_encoder(kind, h, w):
     else:
         imgs = np.stack([smooth_noise(rng, h, w), np.full((h, w, 3), 200, np.uint8)])
         px = torch.from_numpy(imgs).cuda()
-    files, _, _ = _encode_raw(px, kind)
+    files, _, _ = encode_raw(px, kind)
     assert probe(files[0])[1].num_idat >= (h * w * (2 if kind == GRAY16 else 3)) // 16384
     check_files(files, kind, h, w, want=[imgs[0], imgs[1]])
 
@@ -696,7 +668,7 @@ def test_png_decoder_class_groups_falls_back_and_raises(tmp_path):
     buf = io.BytesIO()
     Image.fromarray(image_of(rng, 20, 30, "rgb")).save(buf, format="JPEG")
     put("g_photo.jpg", buf.getvalue())
-    put("h_interlaced.png", _interlaced_png(image_of(rng, 6, 5, "rgb")))
+    put("h_interlaced.png", interlaced_png(image_of(rng, 6, 5, "rgb")))
     put("i_rgb_20x30.png", pil_png(image_of(rng, 20, 30, "rgb"), optimize=True))
     dec = ImageDecoder("cuda")
     handle = dec.decode(paths, kinds)
@@ -725,17 +697,6 @@ def test_png_decoder_class_groups_falls_back_and_raises(tmp_path):
         dec.decode([paths[1]], False)
 
 
-def _interlaced_png(img: np.ndarray) -> bytes:
-    """An Adam7 file written by hand (PIL reads them and writes none): filter type 0 on every pass row."""
-    h, w = img.shape[:2]
-    rows = []
-    for y0, x0, dy, dx in ((0, 0, 8, 8), (0, 4, 8, 8), (4, 0, 8, 4), (0, 2, 4, 4), (2, 0, 4, 2), (0, 1, 2, 2), (1, 0, 2, 1)):
-        sub = img[y0::dy, x0::dx]
-        if sub.shape[0] and sub.shape[1]:
-            rows += [b"\0" + sub[y].tobytes() for y in range(sub.shape[0])]
-    return SIGNATURE + ihdr(h, w, 2, 8, interlace=1) + chunk(b"IDAT", zlib.compress(b"".join(rows))) + chunk(b"IEND", b"")
-
-
 @pytest.mark.gpu
 def test_a_request_without_any_device_group(tmp_path):
     """No path at all, and a request whose every file goes to PIL: the group loop runs zero times and the handle is complete all the same."""
@@ -752,7 +713,7 @@ def test_a_request_without_any_device_group(tmp_path):
     buf = io.BytesIO()
     Image.fromarray(image_of(rng, 8, 8, "rgb")).save(buf, format="JPEG")
     paths = [str(tmp_path / "interlaced_5x7.png"), str(tmp_path / "photo_8x8.jpg")]
-    for p, data in zip(paths, (_interlaced_png(image_of(rng, 5, 7, "rgb")), buf.getvalue())):
+    for p, data in zip(paths, (interlaced_png(image_of(rng, 5, 7, "rgb")), buf.getvalue())):
         with open(p, "wb") as f:
             f.write(data)
     handle = dec.decode(paths)

@@ -13,8 +13,9 @@ sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
 
 from nvs_tree import make_tree  # noqa: E402
-from test_png_encoder import parse_chunks  # noqa: E402
-from test_predict_driver import TINY, _make_scene  # noqa: E402
+from png_files import parse_chunks  # noqa: E402
+from scenes import make_scene  # noqa: E402
+from nets import TINY  # noqa: E402
 
 torch = pytest.importorskip("torch")
 
@@ -80,7 +81,7 @@ def test_predict_writes_the_same_tree_with_either_encoder(tmp_path, colour_mode)
     from crossscore_amd.model import CrossScoreNet
     from crossscore_amd.predict import predict
 
-    qd, rd = _make_scene(str(tmp_path / "data"), n_query=5, n_ref=4)
+    qd, rd = make_scene(str(tmp_path / "data"), n_query=5, n_ref=4)
     arch = CrossScoreNet(model_config(**{"backbone.from_pretrained": TINY})).arch
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, 5).items()}
     common = [f"data.dataset.query_dir={qd}", f"data.dataset.reference_dir={rd}", f"model.backbone.from_pretrained={TINY}",

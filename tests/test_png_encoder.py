@@ -1,13 +1,12 @@
 """Device PNG encoder (cs_op_png_encode, cs_op_denorm_to_rgb8, writers.PngEncoder): host-side contract on the CPU, files on the GPU.
 
-PIL alone is not a sufficient validator (it decodes files whose Adler-32 or last chunk CRC are wrong), so the files go through a chunk
-parser of this module (signature, every chunk's length / type / CRC, chunk order) and through zlib.decompress over the concatenated
+PIL alone is not a sufficient validator (it decodes files whose Adler-32 or last chunk CRC are wrong), so the files go through the chunk
+parser of tests/png_files.py (signature, every chunk's length / type / CRC, chunk order) and through zlib.decompress over the concatenated
 IDAT payloads (which verifies Adler-32), before PIL's pixels are compared."""
 import ctypes as C
 import io
 import os
 import re
-import struct
 import sys
 import zlib
 
@@ -20,93 +19,9 @@ REPO = os.path.dirname(HERE)
 sys.path.insert(0, REPO)
 from crossscore_amd import _lib  # noqa: E402
 from crossscore_amd.config import load_config  # noqa: E402
+from png_files import GRAY16, RGB8, check_png, contents, encode_raw, filtered_size, parse_chunks, row_bytes  # noqa: E402
 
-GRAY16, RGB8 = _lib.PNG_GRAY16, _lib.PNG_RGB8
 NEW_SYMBOLS = ("cs_png_bound", "cs_png_workspace_bytes", "cs_op_png_encode", "cs_op_denorm_to_rgb8")
-SIGNATURE = b"\x89PNG\r\n\x1a\n"
-
-
-def row_bytes(kind, w):
-    return w * (2 if kind == GRAY16 else 3)
-
-
-def filtered_size(kind, h, w):
-    return h * (1 + row_bytes(kind, w))
-
-
-# ----------------------------------------------------------------------------------------------------------- the validator
-def parse_chunks(data: bytes):
-    """[(type, payload)] of a PNG file; asserts the signature, every chunk's CRC, the order IHDR, IDAT..., IEND and that nothing follows."""
-    assert data[:8] == SIGNATURE, data[:8]
-    pos, chunks = 8, []
-    while pos < len(data):
-        assert pos + 12 <= len(data), "truncated chunk"
-        (n,) = struct.unpack(">I", data[pos:pos + 4])
-        typ = data[pos + 4:pos + 8]
-        assert pos + 12 + n <= len(data), (typ, n, "chunk runs past the end of the file")
-        payload = data[pos + 8:pos + 8 + n]
-        (crc,) = struct.unpack(">I", data[pos + 8 + n:pos + 12 + n])
-        assert crc == zlib.crc32(typ + payload), (typ, len(chunks), hex(crc), hex(zlib.crc32(typ + payload)))
-        chunks.append((typ, payload))
-        pos += 12 + n
-        if typ == b"IEND":
-            break
-    assert pos == len(data), "bytes after IEND"
-    types = [t for t, _ in chunks]
-    assert types[0] == b"IHDR" and types[-1] == b"IEND" and len(types) >= 3 and all(t == b"IDAT" for t in types[1:-1]), types
-    assert len(chunks[0][1]) == 13 and len(chunks[-1][1]) == 0
-    return chunks
-
-
-def unfilter(stream: bytes, h: int, rb: int, bpp: int) -> np.ndarray:
-    """PNG filter types 0-4 undone: (h, rb) uint8 raw row bytes."""
-    a = np.frombuffer(stream, np.uint8).reshape(h, 1 + rb)
-    assert a[:, 0].max() <= 4, "illegal filter type"
-    out = np.zeros((h, rb), np.uint8)
-    for y in range(h):
-        ft, line = int(a[y, 0]), a[y, 1:]
-        prev = out[y - 1] if y else np.zeros(rb, np.uint8)
-        if ft == 0:
-            out[y] = line
-        elif ft == 1:  # Sub: a running sum per byte lane of the pixel
-            for c in range(min(bpp, rb)):
-                out[y, c::bpp] = np.cumsum(line[c::bpp].astype(np.uint64)).astype(np.uint8)
-        elif ft == 2:
-            out[y] = line + prev
-        else:
-            cur = np.zeros(rb, np.int64)
-            for x in range(rb):
-                left = cur[x - bpp] if x >= bpp else 0
-                up = int(prev[x])
-                ul = int(prev[x - bpp]) if x >= bpp else 0
-                if ft == 3:
-                    pred = (left + up) // 2
-                else:
-                    p = left + up - ul
-                    pa, pb, pc = abs(p - left), abs(p - up), abs(p - ul)
-                    pred = left if pa <= pb and pa <= pc else (up if pb <= pc else ul)
-                cur[x] = (int(line[x]) + pred) & 255
-            out[y] = cur
-    return out
-
-
-def check_png(data: bytes, img: np.ndarray, kind: int):
-    """Every condition of a valid, pixel-exact file."""
-    from PIL import Image
-
-    h, w = img.shape[:2]
-    rb, bpp = row_bytes(kind, w), 2 if kind == GRAY16 else 3
-    chunks = parse_chunks(data)
-    ihdr = struct.unpack(">IIBBBBB", chunks[0][1])
-    assert ihdr == (w, h, 16 if kind == GRAY16 else 8, 0 if kind == GRAY16 else 2, 0, 0, 0), ihdr
-    stream = zlib.decompress(b"".join(p for t, p in chunks if t == b"IDAT"))  # raises on a wrong Adler-32
-    assert len(stream) == h * (1 + rb)
-    raw = unfilter(stream, h, rb, bpp)
-    want = img.astype(">u2").view(np.uint8).reshape(h, rb) if kind == GRAY16 else img.reshape(h, rb)
-    assert np.array_equal(raw, want)
-    pil = Image.open(io.BytesIO(data))
-    assert pil.mode == ("I;16" if kind == GRAY16 else "RGB"), pil.mode
-    assert np.array_equal(np.array(pil), img)
 
 
 def test_validator_rejects_what_pil_accepts():
@@ -195,50 +110,6 @@ def test_png_encoder_key_is_validated():
 
 
 # ----------------------------------------------------------------------------------------------------------------- GPU
-def _encode_raw(pixels: torch.Tensor, kind: int, slot=None):
-    """cs_op_png_encode itself: (files, lengths, bound)."""
-    lib = _lib.load()
-    I, H, W = (int(v) for v in pixels.shape[:3])
-    bound = lib.cs_png_bound(kind, H, W)
-    slot = bound if slot is None else slot
-    out = torch.zeros((I, slot), dtype=torch.uint8, device="cuda")
-    lengths = torch.zeros((I,), dtype=torch.int32, device="cuda")
-    work = torch.empty((lib.cs_png_workspace_bytes(kind, I, H, W),), dtype=torch.uint8, device="cuda")
-    _lib.check(lib.cs_op_png_encode(C.c_void_p(pixels.data_ptr()), kind, I, H, W, H * row_bytes(kind, W), C.c_void_p(out.data_ptr()), slot,
-                                    C.c_void_p(lengths.data_ptr()), C.c_void_p(work.data_ptr()), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    ln = lengths.cpu().numpy()
-    o = out.cpu().numpy()
-    return [o[i, :ln[i]].tobytes() for i in range(I)], ln, bound
-
-
-def _score_map(h, w, seed):
-    """A score map as the model leaves it: smooth structure at the patch scale plus pixel noise, values over [0, 1] and slightly beyond."""
-    rng = np.random.Generator(np.random.PCG64(seed))
-    yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
-    s = 0.55 + 0.3 * np.sin(xx / 23.0 + 0.3) * np.cos(yy / 17.0) + 0.15 * np.sin((xx + yy) / 7.0)
-    s += rng.normal(0, 0.01, size=s.shape)
-    return (np.round(s * 64) / 64).astype(np.float32) if seed % 2 else s.astype(np.float32)
-
-
-def _contents(kind, h, w):
-    """constant, horizontal ramp, uniform noise, a score map converted by cs_op_score_to_gray16 / cs_op_score_to_rgb -> (4, ...) device tensor."""
-    from crossscore_amd.writers import ScoreMapEncoder
-
-    rng = np.random.Generator(np.random.PCG64(h * 4099 + w))
-    dev = torch.device("cuda")
-    score = torch.from_numpy(_score_map(h, w, h + w)).to(dev)[None]
-    if kind == GRAY16:
-        const = np.full((h, w), 0xA1B2, np.uint16)
-        ramp = np.broadcast_to((np.arange(w, dtype=np.uint32) * 257 % 65536).astype(np.uint16), (h, w))
-        noise = rng.integers(0, 65536, size=(h, w), dtype=np.uint16)
-        real = ScoreMapEncoder("ssim", 0, 1, "gray", dev).device_image(score).cpu().numpy().view(np.uint16)[0]
-    else:
-        const = np.broadcast_to(np.array([200, 17, 96], np.uint8), (h, w, 3))
-        ramp = np.broadcast_to(np.stack([np.arange(w) % 256, (np.arange(w) // 2) % 256, 255 - np.arange(w) % 256], 1).astype(np.uint8), (h, w, 3))
-        noise = rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
-        real = ScoreMapEncoder("ssim", 0, 1, "rgb", dev).device_image(score).cpu().numpy()[0]
-    return np.stack([const, ramp, noise, real])
 
 
 SIZES = [(1, 1), (1, 7), (14, 14), (75, 91), (518, 518), (518, 686), (1036, 1036)]
@@ -248,9 +119,9 @@ SIZES = [(1, 1), (1, 7), (14, 14), (75, 91), (518, 518), (518, 686), (1036, 1036
 @pytest.mark.parametrize("kind", [GRAY16, RGB8])
 @pytest.mark.parametrize("h,w", SIZES)
 def test_files_are_valid_and_pixel_exact(kind, h, w):
-    imgs = _contents(kind, h, w)
+    imgs = contents(kind, h, w)
     dev_imgs = torch.from_numpy(imgs.view(np.int16) if kind == GRAY16 else imgs).cuda()
-    files, ln, bound = _encode_raw(dev_imgs, kind)
+    files, ln, bound = encode_raw(dev_imgs, kind)
     raw = h * row_bytes(kind, w)
     print(f"kind {kind} {h}x{w}: bound {bound}, raw {raw}, lengths const/ramp/noise/map {ln.tolist()}")
     for i, name in enumerate(("constant", "ramp", "noise", "score map")):
@@ -264,11 +135,11 @@ def test_files_are_valid_and_pixel_exact(kind, h, w):
 @pytest.mark.parametrize("kind", [GRAY16, RGB8])
 def test_slot_larger_than_the_bound_and_untouched_tail(kind):
     h, w = 75, 91
-    imgs = _contents(kind, h, w)
+    imgs = contents(kind, h, w)
     dev_imgs = torch.from_numpy(imgs.view(np.int16) if kind == GRAY16 else imgs).cuda()
     lib = _lib.load()
     slot = lib.cs_png_bound(kind, h, w) + 37  # odd slot size: files start at any byte alignment
-    files, ln, _ = _encode_raw(dev_imgs, kind, slot=slot)
+    files, ln, _ = encode_raw(dev_imgs, kind, slot=slot)
     for i in range(4):
         check_png(files[i], imgs[i], kind)
 
@@ -277,17 +148,17 @@ def test_slot_larger_than_the_bound_and_untouched_tail(kind):
 @pytest.mark.parametrize("kind,h,w", [(GRAY16, 75, 91), (RGB8, 518, 518)])
 def test_bytes_do_not_depend_on_the_batch(kind, h, w):
     """Image k of a batch of 8 = the same image alone = the same image at another position among other images."""
-    parts = [_contents(kind, h, w), _contents(kind, h, w)[::-1].copy()]
+    parts = [contents(kind, h, w), contents(kind, h, w)[::-1].copy()]
     parts[1][0] = np.roll(parts[1][0], 5, axis=1)  # eight different images
     parts[1][3] = np.roll(parts[1][3], 3, axis=0)
     imgs = np.concatenate(parts)
     as_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int16) if kind == GRAY16 else np.ascontiguousarray(a)).cuda()  # noqa: E731
-    batch, _, _ = _encode_raw(as_dev(imgs), kind)
+    batch, _, _ = encode_raw(as_dev(imgs), kind)
     assert len(batch) == 8
     perm = [5, 2, 7, 0, 3, 6, 1, 4]
-    shuffled, _, _ = _encode_raw(as_dev(imgs[perm]), kind)
+    shuffled, _, _ = encode_raw(as_dev(imgs[perm]), kind)
     for k in range(8):
-        alone, _, _ = _encode_raw(as_dev(imgs[k:k + 1]), kind)
+        alone, _, _ = encode_raw(as_dev(imgs[k:k + 1]), kind)
         assert alone[0] == batch[k], k
         assert shuffled[perm.index(k)] == batch[k], k
 
@@ -336,10 +207,10 @@ def test_png_encoder_class_sync_and_async():
 
     enc = PngEncoder()
     for kind, (h, w) in ((GRAY16, (75, 91)), (RGB8, (14, 14))):
-        imgs = _contents(kind, h, w)
+        imgs = contents(kind, h, w)
         dev = torch.from_numpy(imgs.view(np.int16) if kind == GRAY16 else imgs).cuda()
         files = enc.encode(dev)
-        raw, _, _ = _encode_raw(dev, kind)
+        raw, _, _ = encode_raw(dev, kind)
         assert files == raw
         for i in range(4):
             check_png(files[i], imgs[i], kind)
@@ -357,7 +228,7 @@ def test_async_encode_does_not_wait_for_the_stream():
     from crossscore_amd.writers import PngEncoder
 
     enc = PngEncoder()
-    imgs = _contents(RGB8, 75, 91)
+    imgs = contents(RGB8, 75, 91)
     dev = torch.from_numpy(imgs).cuda()
     want = enc.encode(dev)  # kernels, pinned blocks and allocator pools exist from here on
     # device time ahead of the encode on the current stream, from the project's own op: 16 encodes of 8 noise images of 1036 x 1036

@@ -12,29 +12,10 @@ sys.path.insert(0, os.path.dirname(HERE))
 from crossscore_amd import data as csdata  # noqa: E402
 from crossscore_amd import synth  # noqa: E402
 from crossscore_amd.config import load_config  # noqa: E402
+from nets import TINY  # noqa: E402
 from oracle import preprocess_oracle as po  # noqa: E402
 from oracle import writers_oracle as wo  # noqa: E402
-
-TINY = "synthetic/dinov2-tiny"
-
-
-def _make_scene(root, n_query=3, n_ref=4, h=70, w=84, seed=7):
-    """<root>/<method>/<dataset>/<res>/<scene>/test/ours_1000/{renders,gt}/frame_XXXXX.png, the depth the reference's CSV
-    grouping indexes into (score_summariser.py:180-212)."""
-    from PIL import Image
-
-    rng = np.random.Generator(np.random.PCG64(seed))
-    base = os.path.join(root, "gaussian", "mfr", "res_540", "s00001", "test", "ours_1000")
-    qd, rd = os.path.join(base, "renders"), os.path.join(base, "gt")
-    os.makedirs(qd)
-    os.makedirs(rd)
-    yy, xx = np.mgrid[0:h, 0:w]
-    for d, n, off in ((qd, n_query, 0), (rd, n_ref, 100)):
-        for i in range(n):
-            img = np.stack([(xx * 3 + i * 17 + off) % 256, (yy * 2 + i * 29) % 256, (xx + yy + i * 11) % 256], axis=2).astype(np.uint8)
-            img = (img.astype(np.int32) + rng.integers(-20, 21, size=img.shape)).clip(0, 255).astype(np.uint8)
-            Image.fromarray(img).save(os.path.join(d, f"frame_{i:05}.png"))
-    return qd, rd
+from scenes import make_scene  # noqa: E402
 
 
 # ------------------------------------------------------------------------------------------------------------------- CPU
@@ -50,7 +31,7 @@ def test_resize_rule_and_geometry():
 
 
 def test_reference_sampling_rules(tmp_path):
-    qd, rd = _make_scene(str(tmp_path), n_query=2, n_ref=4)
+    qd, rd = make_scene(str(tmp_path), n_query=2, n_ref=4)
     items = csdata.SimpleReferenceItems(qd, rd, {"strategy": "random", "cross": 3, "deterministic": True})
     assert len(items) == 2 and items.query_paths == sorted(items.query_paths)
     it = items[1]
@@ -135,7 +116,7 @@ def test_predict_run_matches_oracle_pipeline(tmp_path, colour_mode):
     from crossscore_amd.predict import predict
     from oracle import crossscore_oracle as orc
 
-    qd, rd = _make_scene(str(tmp_path / "data"), n_query=3, n_ref=4)
+    qd, rd = make_scene(str(tmp_path / "data"), n_query=3, n_ref=4)
     arch = CrossScoreNet(model_config(**{"backbone.from_pretrained": TINY})).arch
     sd = synth.make_state_dict(arch, 5)
     ckpt = tmp_path / "run" / "ckpt" / "last.ckpt"
@@ -200,7 +181,7 @@ def test_reference_token_cache_gives_identical_outputs(tmp_path):
     from crossscore_amd.model import CrossScoreNet
     from crossscore_amd.predict import predict
 
-    qd, rd = _make_scene(str(tmp_path / "data"), n_query=5, n_ref=4)
+    qd, rd = make_scene(str(tmp_path / "data"), n_query=5, n_ref=4)
     arch = CrossScoreNet(model_config(**{"backbone.from_pretrained": TINY})).arch
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, 6).items()}
     outs = {}
@@ -232,7 +213,7 @@ def test_fused_input_stage_gives_identical_outputs(tmp_path, use_cache):
     from crossscore_amd.predict import predict
 
     back = "synthetic/dinov2-small-2l"
-    qd, rd = _make_scene(str(tmp_path / "data"), n_query=5, n_ref=4, h=70, w=90)  # -> 56 x 72 (the one-launch patch embedding takes even widths)
+    qd, rd = make_scene(str(tmp_path / "data"), n_query=5, n_ref=4, h=70, w=90)  # -> 56 x 72 (the one-launch patch embedding takes even widths)
     from crossscore_amd.config import model_config
     from crossscore_amd.model import CrossScoreNet
     arch = CrossScoreNet(model_config(**{"backbone.from_pretrained": back})).arch
@@ -289,7 +270,7 @@ def test_calibration_of_a_long_run_leaves_the_outputs_unchanged(tmp_path, cache,
     from crossscore_amd.predict import predict
 
     back = "synthetic/dinov2-small-2l" if fused == "auto" else TINY
-    qd, rd = _make_scene(str(tmp_path / "data"), n_query=16, n_ref=4, h=70, w=90)
+    qd, rd = make_scene(str(tmp_path / "data"), n_query=16, n_ref=4, h=70, w=90)
     arch = CrossScoreNet(model_config(**{"backbone.from_pretrained": back})).arch
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, 6).items()}
     common = [f"data.dataset.query_dir={qd}", f"data.dataset.reference_dir={rd}", f"model.backbone.from_pretrained={back}",

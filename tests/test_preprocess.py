@@ -206,7 +206,6 @@ def _one_pass_against_two_launches(h, w, rs, crop, pad, bf16=False, Cc=384):
     """tokens of cs_op_patch_embed_fused_u8 == tokens of cs_op_preprocess_u8 + cs_op_patch_embed_fused, two images, bit for bit"""
     import torch
     import hip_helpers as hh
-    from crossscore_amd import _lib
 
     P = 14
     rng = np.random.Generator(np.random.PCG64(h * 7 + w))
@@ -219,14 +218,10 @@ def _one_pass_against_two_launches(h, w, rs, crop, pad, bf16=False, Cc=384):
     pos = torch.from_numpy(rng.standard_normal((1 + (H // P) * (W // P), Cc)).astype(np.float32)).cuda()
     buf = np.zeros((2, h, w * 3 + pad), np.uint8)
     buf[:, :, : w * 3] = imgs.reshape(2, h, w * 3)
-    lib = _lib.load()
-    lib.cs_debug_set_op_operand_dtype(1 if bf16 else 0)
-    try:
+    with hh.switches(bf16=bf16):
         ref = hh.patch_embed_fused(torch.from_numpy(two).cuda(), wgt, bias, pos, P)
         got = hh.patch_embed_fused_u8(torch.from_numpy(buf).cuda(), rs, (y0, x0, H, W, w), po.IMAGENET_MEAN, po.IMAGENET_STD, wgt, bias, pos, P)
         torch.cuda.synchronize()
-    finally:
-        lib.cs_debug_set_op_operand_dtype(0)
     assert torch.isfinite(got[1:1 + (H // P) * (W // P)]).all()
     assert torch.equal(got, ref)
 

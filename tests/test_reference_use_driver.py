@@ -16,7 +16,8 @@ sys.path.insert(0, HERE)
 from crossscore_amd import scoring  # noqa: E402
 from crossscore_amd.config import load_config  # noqa: E402
 from nvs_tree import make_tree  # noqa: E402
-from test_select_driver import SMALL, _make_scene, _tree, _weights  # noqa: E402
+from nets import SMALL, state_dict_for  # noqa: E402
+from scenes import make_scene_with_copies, tree_bytes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -56,8 +57,8 @@ class _Recorder:
 @pytest.fixture(scope="module")
 def scene(tmp_path_factory):
     root = tmp_path_factory.mktemp("ref_use")
-    qd, rd = _make_scene(str(root / "data"))
-    return root, qd, rd, _weights(SMALL)
+    qd, rd = make_scene_with_copies(str(root / "data"))
+    return root, qd, rd, state_dict_for(SMALL, 6)
 
 
 @pytest.mark.parametrize("strategy", ["similar", "random"])
@@ -94,7 +95,7 @@ def test_the_csv_holds_the_means_of_the_modules_outputs_however_the_tokens_are_m
     off = _predict(str(root / f"{strategy}_off"), qd, rd, sd, f"data.neighbour_config.strategy={strategy}", "this_main.fused_input_stage=False",
                    "this_main.batches_in_flight=3")
     assert off["reference_use"] is False
-    a, b = _tree(off["out_dir"]), _tree(base["out_dir"])
+    a, b = tree_bytes(off["out_dir"]), tree_bytes(base["out_dir"])
     assert sorted(a) == sorted(k for k in b if k != "reference_use.csv") and "reference_use.csv" in b
     for rel in a:
         assert a[rel] == b[rel], rel
@@ -148,10 +149,9 @@ def test_options_are_checked_before_the_run(scene):
 
 def test_evaluate_names_padded_places_as_the_selection_does(tmp_path_factory):
     from crossscore_amd.evaluate import evaluate
-    from test_select_driver import _weights as weights
 
     tree = make_tree(tmp_path_factory.mktemp("ref_use_nvs") / "nvs" / "tree")
-    sd = weights(SMALL)
+    sd = state_dict_for(SMALL, 6)
     outs = []
     cwd = os.getcwd()
     for name, fused, depth in (("a", False, 3), ("b", "auto", 1)):

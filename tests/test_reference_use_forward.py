@@ -12,16 +12,14 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from crossscore_amd import _lib, synth  # noqa: E402
-from crossscore_amd.config import model_config  # noqa: E402
-from crossscore_amd.model import CrossScoreNet, SelectionBank  # noqa: E402
+from crossscore_amd.model import SelectionBank  # noqa: E402
 from crossscore_amd.pipeline import ForwardPipeline  # noqa: E402
+from nets import SMALL, TINY, make_net  # noqa: E402
 import guard  # noqa: E402
 import reference_use_oracle as oracle  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-TINY = "synthetic/dinov2-tiny"       # C = 128, 8 decoder heads of 16 (golden g0's net)
-SMALL = "synthetic/dinov2-small-2l"  # the ViT-S width, 8 decoder heads of 48 (golden g8's net)
 USE = ("ref_use_share", "ref_use_peak_prob", "ref_use_peak_index", "ref_use_entropy")
 # The forward's outputs against the fp64 recomputation from the eight fp32 maps of need_attn_weights_head_id = 0 .. 7.  Both sides use the same
 # lse and operand values; they differ by the order of the fp32 dot products (MFMA against a scalar chain) and the fp32 sums.  Bounds: 4 x the
@@ -33,13 +31,6 @@ BOUND_OF_CAP = {k: min(1.0, 4 * v) for k, v in MEASURED_OF_CAP.items()}
 
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _net(backbone, dtype, seed=3):
-    net = CrossScoreNet(model_config(**{"backbone.from_pretrained": backbone}))
-    net.load_numpy_state_dict(synth.make_state_dict(net.arch, seed))
-    net.operand_dtype = dtype
-    return net.cuda()
 
 
 def _inputs(B, N, H, W, seed):
@@ -56,7 +47,7 @@ def _same(a, b, keys):
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])
 @pytest.mark.parametrize("backbone,H,W,B,N", [(TINY, 70, 98, 3, 2), (TINY, 42, 42, 2, 3), (SMALL, 70, 84, 2, 3)])
 def test_outputs_equal_what_the_eight_attention_maps_give(backbone, H, W, B, N, dtype):
-    net = _net(backbone, dtype)
+    net = make_net(backbone, 3, dtype)[0]
     q, r = _inputs(B, N, H, W, 5)
     got = net(q, r, need_reference_use=True)
     P = net.arch.patch
@@ -85,7 +76,7 @@ def test_outputs_equal_what_the_eight_attention_maps_give(backbone, H, W, B, N, 
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])
 @pytest.mark.parametrize("backbone,H,W", [(TINY, 70, 98), (SMALL, 70, 84)])
 def test_other_outputs_keep_their_bits_and_the_census_gains_one_launch(backbone, H, W, dtype):
-    net = _net(backbone, dtype)
+    net = make_net(backbone, 3, dtype)[0]
     q, r = _inputs(2, 2, H, W, 6)
     keys = ("score_map_ref_cross", "score_mean_ref_cross", "attn_weights_map_ref_cross")
     plain = net(q, r, False, 0, False, True)
@@ -128,7 +119,7 @@ def _untouched(views):
 
 def test_the_request_is_one_shot_and_a_failing_forward_clears_it():
     H, W, B, N = 70, 98, 2, 2
-    net = _net(TINY, "fp16")
+    net = make_net(TINY, 3, "fp16")[0]
     q, r = _inputs(B, N, H, W, 7)
     want = net(q, r, need_reference_use=True)
     # armed through the C ABI: the next forward fills the buffers and nothing around them ...
@@ -171,7 +162,7 @@ def test_the_request_is_one_shot_and_a_failing_forward_clears_it():
 
 
 def test_no_reference_views_with_a_request_is_an_error():
-    net = _net(TINY, "fp16")
+    net = make_net(TINY, 3, "fp16")[0]
     q, r = _inputs(2, 1, 42, 42, 8)
     with pytest.raises(ValueError):
         net(q, r[:, :0], need_reference_use=True)
@@ -184,7 +175,7 @@ def test_every_entry_point_and_any_depth_give_the_same_bits(dtype):
     """plain, cached, uint8, cached uint8 and select on the same references; one batch at a time and three in flight"""
     from crossscore_amd.data import InputStage
 
-    net = _net(SMALL, dtype)
+    net = make_net(SMALL, 3, dtype)[0]
     dev = torch.device("cuda:0")
     stage = InputStage(dev, resize_short_side=70, integer_patches=True)
     rng = np.random.Generator(np.random.PCG64(19))

@@ -6,14 +6,11 @@ import numpy as np
 import pytest
 
 import reference_use_oracle as oracle
-
-
-def _rng(seed):
-    return np.random.Generator(np.random.PCG64(seed))
+from bits16 import rng
 
 
 def _case(seed, B, heads, Lq, N, Np, dh, q_amp=0.3):
-    g = _rng(seed)
+    g = rng(seed)
     Q = q_amp * g.standard_normal((B, Lq, heads * dh))
     K = g.standard_normal((B, N * Np, heads * dh))
     s = oracle.logits(Q, K, heads, dh)

@@ -20,7 +20,8 @@ from crossscore_amd import _lib  # noqa: E402
 import guard  # noqa: E402
 import hip_helpers as hh  # noqa: E402
 import reference_use_oracle as oracle  # noqa: E402
-from test_hip_attention_tiles import _OpDtype, _fl, _rd, _rng, _t  # noqa: E402
+import bits16 as b16  # noqa: E402
+from bits16 import rng, to_dev  # noqa: E402
 
 DEV = "cuda"
 NPS = (1, 15, 16, 17, 63, 64, 65, 100)
@@ -68,11 +69,11 @@ def reference_use(Q, K, lse, heads, dh, N, Np, out, q_scale=1.0, rc_only=False, 
 def random_case(g, B, Lq, N, Np, heads, dh, bf16):
     """Q = 0.3 N(0, 1), K = N(0, 1) rounded to the operand type, in strided poisoned buffers (ldk = 4 heads dh as in the forward's kv buffer);
     lse from cs_op_attention on them -> (Q, K, lse, oracle result)"""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     Cc = heads * dh
-    Q = operand(rd(_t(0.3 * g.standard_normal((B, Lq, Cc), dtype=np.float32))), Cc + 8)
-    K = operand(rd(_t(g.standard_normal((B, N * Np, Cc), dtype=np.float32))), 4 * Cc)
-    V = rd(_t(g.standard_normal((B, N * Np, Cc), dtype=np.float32)))
+    Q = operand(rd(to_dev(0.3 * g.standard_normal((B, Lq, Cc), dtype=np.float32))), Cc + 8)
+    K = operand(rd(to_dev(g.standard_normal((B, N * Np, Cc), dtype=np.float32))), 4 * Cc)
+    V = rd(to_dev(g.standard_normal((B, N * Np, Cc), dtype=np.float32)))
     _, lse = hh.attention(Q, K, V, heads, dh, lse=True, q_scale=1.0)
     want = oracle.reference_use(oracle.logits(fl(Q).cpu().numpy(), fl(K).cpu().numpy(), heads, dh), lse.cpu().numpy(), N, Np)
     return Q, K, lse, want
@@ -93,10 +94,10 @@ def run_and_check(Q, K, lse, want, heads, dh, N, Np, what):
 
 def _sweep(shapes, heads, dh, bf16, seed):
     worst, inside, total = {}, 0, 0
-    with _OpDtype(bf16):
+    with hh.switches(bf16=bf16):
         for i, (Lq, N, Np) in enumerate(shapes):
             B = 1 + i % 3
-            g = _rng(seed + 7919 * i)
+            g = rng(seed + 7919 * i)
             Q, K, lse, want = random_case(g, B, Lq, N, Np, heads, dh, bf16)
             fig, (a, b), _ = run_and_check(Q, K, lse, want, heads, dh, N, Np, f"dh {dh} heads {heads} Lq {Lq} N {N} Np {Np} B {B}")
             inside, total = inside + a, total + b
@@ -137,14 +138,14 @@ def test_every_head_dim_against_the_oracle(dh, bf16):
 def test_zero_queries_tie_to_index_zero_and_equal_shares(dh, bf16):
     """Q = 0: every logit is 0, every p of a row the same.  peak_index is 0 everywhere (the tie rule, through the lane-local scan and the
     four-lane reduction), every (b, q, n) share has the same bits, the entropy is log2(N Np) within its cap."""
-    rd = _rd(bf16)
+    rd = b16.rd(bf16)
     heads = 3
-    with _OpDtype(bf16):
+    with hh.switches(bf16=bf16):
         for Lq, N, Np in ((33, 3, 65), (130, 5, 17), (17, 2, 100), (16, 1, 64)):
-            g = _rng(dh + Np)
+            g = rng(dh + Np)
             Cc = heads * dh
             Q = operand(rd(torch.zeros((2, Lq, Cc), device=DEV)), Cc + 8)
-            K = operand(rd(_t(g.standard_normal((2, N * Np, Cc), dtype=np.float32))), 4 * Cc)
+            K = operand(rd(to_dev(g.standard_normal((2, N * Np, Cc), dtype=np.float32))), 4 * Cc)
             _, lse = hh.attention(Q, K, K.contiguous(), heads, dh, lse=True, q_scale=1.0)
             out, checks = outputs(2, N, Lq)
             reference_use(Q, K, lse, heads, dh, N, Np, out)
@@ -165,9 +166,9 @@ def test_one_hot_rows_on_both_sides_of_a_reference_boundary(dh, bf16):
     """Query q looks at ONE key with logit 40 against 0: for odd q the last patch (j = Np - 1) of reference n, for even q the first patch of
     reference n + 1, n = (q // 2) mod (N - 1) -- the two keys on either side of a boundary between references.  The share of the right reference is
     above 0.999, its peak_index exact; every other reference holds equal values only, so its index is 0."""
-    rd = _rd(bf16)
+    rd = b16.rd(bf16)
     heads = 3
-    with _OpDtype(bf16):
+    with hh.switches(bf16=bf16):
         for Lq, N, Np in ((33, 2, 1), (33, 3, 17), (65, 5, 64), (33, 3, 65), (17, 2, 100)):
             Cc = heads * dh
             q = torch.arange(Lq, device=DEV)
@@ -199,14 +200,14 @@ def test_one_hot_rows_on_both_sides_of_a_reference_boundary(dh, bf16):
 def test_negative_logits_show_a_counted_padded_key(Np, bf16):
     """All real logits near -20 (K along -Q's common direction): a zero-filled key of the ragged tile, s = 0, would carry 2^20 times a real key's
     weight.  The shares still sum to 1 and everything meets the oracle."""
-    rd, fl = _rd(bf16), _fl(bf16)
+    rd, fl = b16.rd(bf16), b16.fl(bf16)
     heads, dh, Lq, N, B = 3, 48, 33, 3, 2
     Cc = heads * dh
-    g = _rng(Np)
+    g = rng(Np)
     a = np.sqrt(20.0 / dh)
-    with _OpDtype(bf16):
-        Q = operand(rd(_t((a + 0.05 * g.standard_normal((B, Lq, Cc))).astype(np.float32))), Cc + 8)
-        K = operand(rd(_t((-a + 0.05 * g.standard_normal((B, N * Np, Cc))).astype(np.float32))), 4 * Cc)
+    with hh.switches(bf16=bf16):
+        Q = operand(rd(to_dev((a + 0.05 * g.standard_normal((B, Lq, Cc))).astype(np.float32))), Cc + 8)
+        K = operand(rd(to_dev((-a + 0.05 * g.standard_normal((B, N * Np, Cc))).astype(np.float32))), 4 * Cc)
         _, lse = hh.attention(Q, K, K.contiguous(), heads, dh, lse=True, q_scale=1.0)
         s = oracle.logits(fl(Q).cpu().numpy(), fl(K).cpu().numpy(), heads, dh)
         assert s.max() < -15 and s.min() > -25
@@ -222,8 +223,8 @@ def test_items_are_independent_of_their_batch(bf16):
     """Every output of an item has the same bits alone and at any position of a batch of 3; a call on the middle item of a guarded buffer of three
     leaves the other two items' outputs and the bands untouched."""
     heads, dh, Lq, N, Np = 8, 48, 65, 3, 65
-    with _OpDtype(bf16):
-        Q, K, lse, _ = random_case(_rng(5), 3, Lq, N, Np, heads, dh, bf16)
+    with hh.switches(bf16=bf16):
+        Q, K, lse, _ = random_case(rng(5), 3, Lq, N, Np, heads, dh, bf16)
         out, checks = outputs(3, N, Lq)
         reference_use(Q, K, lse, heads, dh, N, Np, out)
         for b in range(3):
@@ -243,7 +244,7 @@ def test_items_are_independent_of_their_batch(bf16):
 def test_null_outputs_in_every_combination():
     """Any output pointer may be null: the others keep the bits of the full call; all four null launches nothing and returns 0."""
     heads, dh, Lq, N, Np = 3, 16, 33, 2, 17
-    Q, K, lse, _ = random_case(_rng(9), 2, Lq, N, Np, heads, dh, False)
+    Q, K, lse, _ = random_case(rng(9), 2, Lq, N, Np, heads, dh, False)
     full, _ = outputs(2, N, Lq)
     reference_use(Q, K, lse, heads, dh, N, Np, full)
     for mask in range(16):
@@ -263,7 +264,7 @@ def test_bad_strides_and_head_dims_are_refused_before_any_launch():
     """cs_attn_check's rules for Q and K: row and batch strides multiples of 8 elements, N Np ldk below 2^30; an unbuilt head dim is
     CS_ERR_UNSUPPORTED.  Nothing is written."""
     heads, dh, Lq, N, Np = 2, 16, 17, 2, 17
-    Q, K, lse, _ = random_case(_rng(3), 1, Lq, N, Np, heads, dh, False)
+    Q, K, lse, _ = random_case(rng(3), 1, Lq, N, Np, heads, dh, False)
     out, checks = outputs(1, N, Lq)
     lib = _lib.load()
 
@@ -292,10 +293,10 @@ def test_bad_strides_and_head_dims_are_refused_before_any_launch():
 def test_raw_queries_are_scaled_and_rounded_like_the_attention_kernel():
     """q_scale = 0: log2(e) / sqrt(dh) is applied to raw Q inside both kernels with one more rounding to the operand type."""
     heads, dh, Lq, N, Np, B = 3, 48, 33, 2, 65, 2
-    g = _rng(11)
+    g = rng(11)
     Cc = heads * dh
-    Q = operand(_t(2.0 * g.standard_normal((B, Lq, Cc), dtype=np.float32)).half(), Cc + 8)
-    K = operand(_t(g.standard_normal((B, N * Np, Cc), dtype=np.float32)).half(), 4 * Cc)
+    Q = operand(to_dev(2.0 * g.standard_normal((B, Lq, Cc), dtype=np.float32)).half(), Cc + 8)
+    K = operand(to_dev(g.standard_normal((B, N * Np, Cc), dtype=np.float32)).half(), 4 * Cc)
     _, lse = hh.attention(Q, K, K.contiguous(), heads, dh, lse=True, q_scale=0.0)
     Qs = (Q.float() * float(np.float32(1.4426950408889634) / np.sqrt(np.float32(dh)))).half()  # the factor in fp32, as the library forms it
     want = oracle.reference_use(oracle.logits(Qs.float().cpu().numpy(), K.float().cpu().numpy(), heads, dh), lse.cpu().numpy(), N, Np)

@@ -12,26 +12,17 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from crossscore_amd import _lib, synth  # noqa: E402
-from crossscore_amd.config import model_config  # noqa: E402
-from crossscore_amd.model import CrossScoreNet, SelectionBank  # noqa: E402
+from crossscore_amd.model import SelectionBank  # noqa: E402
 from crossscore_amd.pipeline import ForwardPipeline  # noqa: E402
+from nets import SMALL, TINY, make_net  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-TINY = "synthetic/dinov2-tiny"
-SMALL = "synthetic/dinov2-small-2l"  # the ViT-S width: what the one-pass (uint8) input stage takes
 KEYS = ("score_map_ref_cross", "score_mean_ref_cross", "attn_weights_map_ref_cross")
 
 
 def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
-
-
-def _net(backbone, dtype, seed=3):
-    net = CrossScoreNet(model_config(**{"backbone.from_pretrained": backbone}))
-    net.load_numpy_state_dict(synth.make_state_dict(net.arch, seed))
-    net.operand_dtype = dtype
-    return net.cuda()
 
 
 def _bank(net, imgs, N):
@@ -64,7 +55,7 @@ def _ops_selection(net, q, bank, N, exclude):
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])
 @pytest.mark.parametrize("H,W,B,N,R", [(70, 98, 1, 1, 4), (70, 98, 3, 2, 9), (42, 42, 3, 1, 9), (42, 42, 1, 2, 4)])
 def test_forward_select_is_forward_cached_on_the_chosen_rows(H, W, B, N, R, dtype):
-    net = _net(TINY, dtype)
+    net = make_net(TINY, 3, dtype)[0]
     bank = _bank(net, _images(R, H, W, 21), N)
     q = _images(B, H, W, 22)
     for exclude in (None, torch.tensor([(2 * b + 1) % R if b != 1 else -1 for b in range(B)], dtype=torch.int32).cuda()):
@@ -96,7 +87,7 @@ def test_forward_select_is_forward_cached_on_the_chosen_rows(H, W, B, N, R, dtyp
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])
 def test_a_query_that_is_a_bank_image_picks_itself(dtype):
     H, W, R, N, j = 70, 98, 9, 2, 5
-    net = _net(TINY, dtype)
+    net = make_net(TINY, 3, dtype)[0]
     imgs = _images(R, H, W, 31)
     bank = _bank(net, imgs, N)
     q = torch.stack([imgs[j], _images(1, H, W, 32)[0]])
@@ -120,7 +111,7 @@ def test_entry_points_and_batches_in_flight_give_the_same_bits(dtype):
     """fp32 and uint8 queries, one batch at a time and three in flight through ForwardPipeline: the same choice and the same maps"""
     from crossscore_amd.data import InputStage
 
-    net = _net(SMALL, dtype)
+    net = make_net(SMALL, 3, dtype)[0]
     dev = torch.device("cuda:0")
     stage = InputStage(dev, resize_short_side=70, integer_patches=True)
     rng = np.random.Generator(np.random.PCG64(17))
@@ -158,7 +149,7 @@ def test_entry_points_and_batches_in_flight_give_the_same_bits(dtype):
 
 def test_bad_arguments_raise_and_leave_the_handle_usable():
     H, W, R = 42, 42, 4
-    net = _net(TINY, "fp16")
+    net = make_net(TINY, 3, "fp16")[0]
     bank = _bank(net, _images(R, H, W, 41), 2)
     q = _images(2, H, W, 42)
     good = net.forward_select(q, bank, None, False, 0, True)

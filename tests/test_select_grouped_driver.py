@@ -14,21 +14,14 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
-from crossscore_amd import synth  # noqa: E402
-from crossscore_amd.config import load_config, model_config  # noqa: E402
+from crossscore_amd.config import load_config  # noqa: E402
+from nets import SMALL, state_dict_for  # noqa: E402
 from nvs_tree import make_tree  # noqa: E402
+from scenes import tree_bytes  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-SMALL = "synthetic/dinov2-small-2l"  # the ViT-S width: what the one-pass input stage takes
 EMPTY = "empty_image"
-
-
-def _weights(backbone):
-    from crossscore_amd.model import CrossScoreNet
-
-    arch = CrossScoreNet(model_config(**{"backbone.from_pretrained": backbone})).arch
-    return {k: torch.from_numpy(v) for k, v in synth.make_state_dict(arch, 6).items()}
 
 
 def _config(tree, *over):
@@ -58,15 +51,6 @@ def _run(tree, root, name, sd, *over):
         os.chdir(cwd)
 
 
-def _tree(work):
-    files = {}
-    for d, _, fs in os.walk(work):
-        for f in fs:
-            p = os.path.join(d, f)
-            files[os.path.relpath(p, work)] = open(p, "rb").read()
-    return files
-
-
 @pytest.fixture(scope="module")
 def scene(tmp_path_factory):
     """the tree with metric_map/ written by the project's own generator (so that files and compute read the same ground truth), and the base run"""
@@ -79,7 +63,7 @@ def scene(tmp_path_factory):
             dirs.remove("metric_map")
     generate(load_config("default_test", [f"data.dataset.path={tree}"]))
     root = tmp_path_factory.mktemp("grouped_runs")
-    sd = _weights(SMALL)
+    sd = state_dict_for(SMALL, 6)
     base, cap = _run(tree, root, "base", sd, "this_main.fused_input_stage=False", "this_main.png_decoder=host", "this_main.batches_in_flight=3",
                      "this_main.gt_metric_maps=files")
     return tree, root, sd, base, cap
@@ -170,7 +154,7 @@ def test_the_run_does_not_depend_on_how_it_is_fed(scene, fused, decoder, depth, 
     assert res["input_stage"].startswith("one-pass" if fused == "auto" else "two-launch") and res["gt_metric_maps"] == gt
     if decoder == "gpu":
         assert res["png_decoded"]["png_decoded_gpu"] > 0 and res["png_decoded"]["png_decoded_host"] == 0
-    a, b = _tree(base["work"]), _tree(res["work"])
+    a, b = tree_bytes(base["work"]), tree_bytes(res["work"])
     assert sorted(a) == sorted(b) and len(a) > 8
     assert os.path.join("out", "reference_selection.csv") in a and any(k.endswith("metrics.csv") for k in a) and os.path.join("out", "test_batches.csv") in a
     for rel in a:

@@ -13,14 +13,12 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 from crossscore_amd import _lib, synth  # noqa: E402
-from crossscore_amd.config import model_config  # noqa: E402
-from crossscore_amd.model import CrossScoreNet, SelectionBank  # noqa: E402
+from crossscore_amd.model import SelectionBank  # noqa: E402
 from crossscore_amd.pipeline import ForwardPipeline  # noqa: E402
+from nets import SMALL, TINY, make_net  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-TINY = "synthetic/dinov2-tiny"
-SMALL = "synthetic/dinov2-small-2l"  # the ViT-S width: what the one-pass (uint8) input stage takes
 KEYS = ("score_map_ref_cross", "score_mean_ref_cross", "attn_weights_map_ref_cross")
 SIZES = (1, 4, 4)  # a group of one (padding with N = 2) and two that leave a choice; the blank row follows them
 OFFSETS = np.array([0, 1, 5, 9], dtype=np.int32)
@@ -34,13 +32,6 @@ def _p(t):
 
 def _h(a):
     return a.ctypes.data_as(C.c_void_p)
-
-
-def _net(backbone, dtype, seed=3):
-    net = CrossScoreNet(model_config(**{"backbone.from_pretrained": backbone}))
-    net.load_numpy_state_dict(synth.make_state_dict(net.arch, seed))
-    net.operand_dtype = dtype
-    return net.cuda()
 
 
 def _images(n, H, W, seed):
@@ -83,7 +74,7 @@ def _ops_selection(net, q, bank, groups, exclude):
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])
 @pytest.mark.parametrize("H,W", [(70, 98), (42, 42)])
 def test_grouped_forward_is_forward_cached_on_the_chosen_rows(H, W, dtype):
-    net = _net(TINY, dtype)
+    net = make_net(TINY, 3, dtype)[0]
     bank = _grouped_bank(net, _bank_images(H, W, 21))
     q = _images(B, H, W, 22)
     for exclude in (None, torch.tensor([3, -1, 0], dtype=torch.int32).cuda()):  # a row of the query's group; none; a row of another group
@@ -127,7 +118,7 @@ def test_grouped_forward_is_forward_cached_on_the_chosen_rows(H, W, dtype):
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])
 def test_one_group_over_every_row_is_todays_forward_select(dtype):
     H, W = 70, 98
-    net = _net(TINY, dtype)
+    net = make_net(TINY, 3, dtype)[0]
     imgs = _images(R, H, W, 51)
     tokens = net.encode_references(imgs)
     mean, centre, unit = net.reference_descriptors(tokens)
@@ -150,7 +141,7 @@ def test_entry_points_and_batches_in_flight_give_the_same_bits(dtype):
     """fp32 and uint8 queries, one batch at a time and three in flight through ForwardPipeline: the same choice and the same maps"""
     from crossscore_amd.data import InputStage
 
-    net = _net(SMALL, dtype)
+    net = make_net(SMALL, 3, dtype)[0]
     dev = torch.device("cuda:0")
     stage = InputStage(dev, resize_short_side=70, integer_patches=True)
     rng = np.random.Generator(np.random.PCG64(17))
@@ -190,7 +181,7 @@ def test_entry_points_and_batches_in_flight_give_the_same_bits(dtype):
 
 def test_bad_arguments_raise_and_leave_the_handle_usable():
     H, W = 42, 42
-    net = _net(TINY, "fp16")
+    net = make_net(TINY, 3, "fp16")[0]
     imgs = _bank_images(H, W, 41)
     bank = _grouped_bank(net, imgs)
     q = _images(B, H, W, 42)

@@ -5,12 +5,12 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import hip_helpers as hh
 from crossscore_amd import _lib
-from test_hip_panel import _make, _reference
+from panel_data import make, reference
 lib = _lib.load()
 dev = torch.device("cuda:0")
 M = int(os.environ.get("CS_PANEL_M", 48 * 1370))
 bf = int(os.environ.get("CS_PANEL_BF16", "0"))
-x, o, w = _make(M, 21, dev)
+x, o, w = make(M, 21, dev)
 lib.cs_debug_set_op_operand_dtype(bf)
 ob = o.float().to(torch.bfloat16).view(torch.float16) if bf else o
 imgs = {}
@@ -21,7 +21,7 @@ for impl in (0, 1):
     u = hh.encoder_panel(xk, ob, imgs[impl], w["bo"], w["b1"], w["b2"])
     torch.cuda.synchronize()
     if not bf:
-        ref_x, ref_u = _reference(x[:8192], o[:8192], w, True, emulate=True)
+        ref_x, ref_u = reference(x[:8192], o[:8192], w, True, emulate=True)
         d = (xk[:8192] - ref_x).abs()
         du = (u[:8192].float() - ref_u).abs()
         print(f"impl {impl}: x mean |d| {float(d.mean()):.2e} max {float(d.max()):.2e}; u max {float(du.max()):.2e}; finite {bool(torch.isfinite(xk).all())}", flush=True)

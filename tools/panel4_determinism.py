@@ -5,11 +5,11 @@ sys.path.insert(0,R); sys.path.insert(0,R+"/tests")
 if v!="-": sys.path.insert(0,R+"/tools/_var/"+v)
 import torch, hip_helpers as hh
 from crossscore_amd import _lib
-from test_hip_panel import _make
+from panel_data import make
 lib=_lib.load(); lib.cs_debug_panel_impl(1)
 dev=torch.device("cuda:0")
 for M in (300, 65760):
-    x,o,w=_make(M,5,dev)
+    x,o,w=make(M,5,dev)
     img=hh.panel_pack(w["wo"],w["ls1"],w["w1"],w["g2"],w["w2"],w["ls2"])
     outs=[]
     for r in range(5):

@@ -10,11 +10,11 @@ import crossscore_amd
 assert "_var" in crossscore_amd.__file__, crossscore_amd.__file__
 import hip_helpers as hh
 from crossscore_amd import _lib
-from test_hip_panel import _make
+from panel_data import make
 lib = _lib.load(); lib.cs_debug_panel_impl(1)
 dev = torch.device("cuda:0")
 M = int(os.environ.get("CS_PANEL_M", 48 * 1370))
-x, o, w = _make(M, 21, dev)
+x, o, w = make(M, 21, dev)
 img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
 for _ in range(5): hh.encoder_panel(x, o, img, w["bo"], w["b1"], w["b2"])
 torch.cuda.synchronize()

@@ -9,15 +9,15 @@ if os.environ.get("CS_P4_CHILD"):
     import torch
     import hip_helpers as hh
     from crossscore_amd import _lib
-    from test_hip_panel import _make, _reference
+    from panel_data import make, reference
     lib = _lib.load(); lib.cs_debug_panel_impl(int(os.environ.get("CS_PANEL_IMPL", "1")))
     dev = torch.device("cuda:0")
     out = []
     for M in (48 * 1370, 256 * 128):
-        x, o, w = _make(M, 21, dev)
+        x, o, w = make(M, 21, dev)
         img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
         xk = x.clone(); u = hh.encoder_panel(xk, o, img, w["bo"], w["b1"], w["b2"])
-        ref_x, _ = _reference(x[:1024], o[:1024], w, True, emulate=True)
+        ref_x, _ = reference(x[:1024], o[:1024], w, True, emulate=True)
         err = float((xk[:1024] - ref_x).abs().max())
         xs = x.clone()
         for _ in range(5): hh.encoder_panel(xs, o, img, w["bo"], w["b1"], w["b2"])

@@ -6,14 +6,14 @@ if os.environ.get("CS_PANEL_CHILD"):
     sys.path.insert(0, os.path.join(R, "tests")); sys.path.insert(0, os.environ["CS_PANEL_CHILD"])
     import torch
     import hip_helpers as hh
-    from test_hip_panel import _make, _reference
+    from panel_data import make, reference
     dev = torch.device("cuda:0")
     for M in (48 * 1370, 24 * 1370):
-        x, o, w = _make(M, 1, dev)
+        x, o, w = make(M, 1, dev)
         img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
         xk = x.clone()
         hh.encoder_panel(xk, o, img, w["bo"], w["b1"], w["b2"])
-        ref, _ = _reference(x[:512], o[:512], w, True, emulate=True)
+        ref, _ = reference(x[:512], o[:512], w, True, emulate=True)
         err = (xk[:512] - ref).abs().max().item()
         for _ in range(3): hh.encoder_panel(x, o, img, w["bo"], w["b1"], w["b2"])
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -9,15 +9,15 @@ sys.path.insert(0, %r); sys.path.insert(0, %r + "/tests")
 from crossscore_amd import _lib
 _lib.LIB_PATH = sys.argv[1]
 import hip_helpers as hh
-from test_hip_panel import _make, _reference
+from panel_data import make, reference
 N = int(sys.argv[2])
 dev = torch.device("cuda:0")
 M = 48 * 1370
-x, o, w = _make(M, 1, dev)
+x, o, w = make(M, 1, dev)
 img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
 xk = x.clone()
 hh.encoder_panel(xk, o, img, w["bo"], w["b1"], w["b2"])
-ref, _ = _reference(x[:512], o[:512], w, True, emulate=True)
+ref, _ = reference(x[:512], o[:512], w, True, emulate=True)
 err = (xk[:512] - ref).abs().max().item()
 assert err < 4e-3, err
 for _ in range(5): hh.encoder_panel(x, o, img, w["bo"], w["b1"], w["b2"])

@@ -8,10 +8,10 @@ if os.environ.get("CS_ABL_PKG"):  # child: crossscore_amd comes from the scratch
     sys.path.insert(0, os.path.join(R, "tests")); sys.path.insert(0, os.environ["CS_ABL_PKG"])
     import torch
     import hip_helpers as hh
-    from test_hip_panel import _make
+    from panel_data import make
     dev = torch.device("cuda:0")
     M = 256 * 128
-    x, o, w = _make(M, 1, dev)
+    x, o, w = make(M, 1, dev)
     img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
     res = {}
     for rnd in range(3):
@@ -37,7 +37,7 @@ if os.environ.get("CS_ABL_PKG"):  # child: crossscore_amd comes from the scratch
     from crossscore_amd import _lib
     os.environ["CS_PANEL_ABL"] = "0"
     for Mrows in (M, 129 * 128):
-        xs, os_, ws = _make(Mrows, 1, dev)
+        xs, os_, ws = make(Mrows, 1, dev)
         for _ in range(3):
             hh.encoder_panel(xs, os_, img, w["bo"], w["b1"], w["b2"])
         torch.cuda.synchronize()
@@ -54,7 +54,7 @@ if os.environ.get("CS_ABL_PKG"):  # child: crossscore_amd comes from the scratch
     # who is late at the MLP phase's unit boundaries (units 40 .. 55 of blocks 0 .. 3): arrival relative to the first arriver, and the release
     if hasattr(lib, "cs_panel_bar_read"):
         os.environ["CS_PANEL_ABL"] = "0"
-        xs, os_, ws = _make(M, 1, dev)
+        xs, os_, ws = make(M, 1, dev)
         for _ in range(3):
             hh.encoder_panel(xs, os_, img, w["bo"], w["b1"], w["b2"])
         torch.cuda.synchronize()
@@ -71,7 +71,7 @@ if os.environ.get("CS_ABL_PKG"):  # child: crossscore_amd comes from the scratch
                 prev = rel.min()
     # where the transitions' time goes (ABL = 64: s_memtime around the LDS drain, the vmcnt wait and the barrier of every transition)
     os.environ["CS_PANEL_ABL"] = "64"
-    xs, os_, ws = _make(M, 1, dev)
+    xs, os_, ws = make(M, 1, dev)
     for _ in range(3):
         hh.encoder_panel(xs, os_, img, w["bo"], w["b1"], w["b2"])
     torch.cuda.synchronize()

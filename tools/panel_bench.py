@@ -4,11 +4,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import torch
 import hip_helpers as hh
-from test_hip_panel import _make
+from panel_data import make
 
 dev = torch.device("cuda:0")
 for M in (48 * 1370, 24 * 1370, 12 * 1370):
-    x, o, w = _make(M, 1, dev)
+    x, o, w = make(M, 1, dev)
     img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
     for outproj in (True, False):
         im = img if outproj else hh.panel_pack(None, None, w["w1"], w["g2"], w["w2"], w["ls2"])

@@ -5,15 +5,15 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import torch
 import hip_helpers as hh
-from test_hip_panel import _make, _reference
+from panel_data import make, reference
 dev = torch.device("cuda:0")
 M = int(sys.argv[1]) if len(sys.argv) > 1 else 384
-x, o, w = _make(M, 1, dev)
+x, o, w = make(M, 1, dev)
 img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
 xk = x.clone()
 u = hh.encoder_panel(xk, o, img, w["bo"], w["b1"], w["b2"])
 torch.cuda.synchronize()
-ref, uref = _reference(x, o, w, True, emulate=True)
+ref, uref = reference(x, o, w, True, emulate=True)
 d = (xk - ref).abs()
 print("max err", float(d.max()), "mean", float(d.mean()))
 rows = torch.arange(M, device=dev)

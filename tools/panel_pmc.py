@@ -6,9 +6,9 @@ sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import torch
 import hip_helpers as hh
 from crossscore_amd import _lib
-from test_hip_panel import _make
+from panel_data import make
 dev = torch.device("cuda:0")
-x, o, w = _make(48 * 1370, 1, dev)
+x, o, w = make(48 * 1370, 1, dev)
 img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
 for _ in range(6):
     hh.encoder_panel(x, o, img, w["bo"], w["b1"], w["b2"])

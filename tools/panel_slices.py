@@ -5,16 +5,16 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import torch
 import hip_helpers as hh
-from test_hip_panel import _make, _reference
+from panel_data import make, reference
 dev = torch.device("cuda:0")
 M = 128
-x, o, w = _make(M, 1, dev)
+x, o, w = make(M, 1, dev)
 def run(w):
     img = hh.panel_pack(w["wo"], w["ls1"], w["w1"], w["g2"], w["w2"], w["ls2"])
     xk = x.clone()
     hh.encoder_panel(xk, o, img, w["bo"], w["b1"], w["b2"])
     torch.cuda.synchronize()
-    ref, _ = _reference(x, o, w, True, emulate=True)
+    ref, _ = reference(x, o, w, True, emulate=True)
     return (xk - ref).abs()
 errs = []
 for s in range(48):

@@ -6,11 +6,11 @@ R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R); sys.path.insert(0, os.path.join(R, "tests"))
 import hip_helpers as hh
 from crossscore_amd import _lib
-from test_hip_panel import _make
+from panel_data import make
 lib = _lib.load()
 dev = torch.device("cuda:0")
 M = 48 * 1370
-x, o, w = _make(M, 21, dev)
+x, o, w = make(M, 21, dev)
 def run(impl, zero, n=20):
     lib.cs_debug_panel_impl(impl)
     ww = {k: (torch.zeros_like(v) if zero else v) for k, v in w.items()}
