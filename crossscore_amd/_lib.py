@@ -150,6 +150,9 @@ SYMBOLS = {
     "cs_op_gt_metric_sums_u8": (_i, [_vp, _vp, _i, _i, _i, _ll, _vp, _vp]),
     "cs_score_gt_workspace_bytes": (_sz, [_i, _i, _i]),
     "cs_op_score_gt_stats": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "cs_score_pool_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "cs_op_score_pool_f32": (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cs_op_score_pool_u16": (_i, [_vp, _i, _i, _i, _i, _ll, C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cs_op_preprocess_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),
     "cs_op_pack_f16": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "cs_op_streams_overlap": (_i, [_vp, _vp, _vp]),

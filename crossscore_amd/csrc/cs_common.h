@@ -31,6 +31,15 @@ __device__ __forceinline__ uint32_t pack_h16x2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
+// fp32 score -> the 16-bit code the gray writer stores (metric_map_write, utils/io/images.py:49-63): m*65535 for the [0,1] intrinsic range,
+// (m+1)*32767 for [-1,1], truncated toward zero like astype(int32) (the conversion saturates, NaN gives 0), clipped to [0, 65535].  The one
+// definition behind score_gray16_kernel (preprocess.hip) and the pooling kernels (scorepool.hip).
+__device__ __forceinline__ uint32_t cs_score_code(float m, int signed_range) {
+  const float v = signed_range ? (m + 1.0f) * 32767.0f : m * 65535.0f;
+  const int q = (int)v;
+  return (uint32_t)(q < 0 ? 0 : (q > 65535 ? 65535 : q));
+}
+
 // ---- operand type of the MFMA kernels: IEEE half (default) or bfloat16 (cs_config.operand_dtype).  Both are 16 bits in memory (h16_t holds
 //      the raw bits either way), both MFMA forms take the same cycles; half carries 11 significant bits and is finite to 65504, bfloat16
 //      8 bits with fp32's range.  Kernels with MFMAs take the choice as a template parameter, the memory-bound ones as an argument. ----
@@ -380,4 +389,9 @@ hipError_t cs_gather_tokens_launch(const h16_t* bank, int R, int Np, int C, cons
 // gtsum.hip
 hipError_t cs_metric_map_sums_launch(const uint16_t* ssim, const uint16_t* mae, int B, int H, int W, int row_elems, long long image_stride,
                                      uint64_t* sums, hipStream_t st);
+// scorepool.hip
+size_t cs_scorepool_workspace(int B, int H, int W);
+hipError_t cs_scorepool_launch(const void* map, int is_f32, int B, int H, int W, int row_elems, long long image_stride, int signed_range,
+                               const uint32_t* ranks, int Q, int S, uint64_t* sum, uint32_t* quant, uint64_t* tail, uint64_t* window,
+                               void* scratch, hipStream_t st);
 }

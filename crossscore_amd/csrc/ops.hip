@@ -302,6 +302,54 @@ int cs_op_score_gt_stats(const float* score, const float* gt, int B, int H, int 
   return 0;
 }
 
+size_t cs_score_pool_workspace_bytes(int B, int H, int W, int Q) {
+  if (B <= 0 || B > 1024 || H <= 0 || W <= 0 || H > 4096 || W > 4096 || Q < 1 || Q > 16) return 0;
+  return cs_scorepool_workspace(B, H, W);
+}
+
+// the checks and rank arithmetic both entries share; map: fp32 scores (is_f32) or 16-bit codes
+static int score_pool_op(const char* who, const void* map, int is_f32, int B, int H, int W, int row_elems, long long image_stride, int signed_range,
+                         const int32_t* permille, int Q, int S, uint64_t* sum, uint32_t* quant, uint64_t* tail, uint64_t* window, void* scratch,
+                         cs_stream stream) {
+  if (B <= 0 || H <= 0 || W <= 0) return fail(CS_ERR_BAD_ARG, "%s: bad sizes (B %d, H %d, W %d)", who, B, H, W);
+  if (B > 1024 || H > 4096 || W > 4096)
+    return fail(CS_ERR_UNSUPPORTED, "%s: B %d, %d x %d is above 1024 images of 4096 x 4096", who, B, H, W);
+  if (signed_range != 0 && signed_range != 1) return fail(CS_ERR_BAD_ARG, "%s: signed_range %d is neither 0 nor 1", who, signed_range);
+  if (Q < 1 || Q > 16) return fail(CS_ERR_BAD_ARG, "%s: %d permille values (1 .. 16)", who, Q);
+  if (!map || !permille || !sum || !quant || !tail || !scratch) return fail(CS_ERR_BAD_ARG, "%s: null pointer", who);
+  for (int j = 0; j < Q; ++j)
+    if (permille[j] < 0 || permille[j] > 1000) return fail(CS_ERR_BAD_ARG, "%s: permille[%d] = %d is outside 0 .. 1000", who, j, (int)permille[j]);
+  if (S < 0 || S > 255 || S > H || S > W)
+    return fail(CS_ERR_BAD_ARG, "%s: a window of %d does not lie inside %d x %d (1 .. min(H, W, 255); 0: none)", who, S, H, W);
+  if (row_elems < W) return fail(CS_ERR_BAD_ARG, "%s: row of %d samples is below the width %d", who, row_elems, W);
+  if (image_stride < (long long)(H - 1) * row_elems + W)
+    return fail(CS_ERR_BAD_ARG, "%s: map stride %lld is below the map's %lld samples", who, image_stride, (long long)(H - 1) * row_elems + W);
+  if ((uintptr_t)map & (is_f32 ? 3 : 1)) return fail(CS_ERR_BAD_ARG, "%s: the map is not aligned to its samples", who);
+  if (((uintptr_t)sum | (uintptr_t)tail | (uintptr_t)window) & 7) return fail(CS_ERR_BAD_ARG, "%s: sum, tail and window must be 8-byte aligned", who);
+  if ((uintptr_t)quant & 3) return fail(CS_ERR_BAD_ARG, "%s: quant must be 4-byte aligned", who);
+  if ((uintptr_t)scratch & 15) return fail(CS_ERR_BAD_ARG, "%s: the scratch must be 16-byte aligned", who);
+  const long long n = (long long)H * W;
+  uint32_t ranks[32];
+  for (int j = 0; j < Q; ++j) {
+    const long long q = permille[j], k = q * n / 1000;
+    ranks[j] = (uint32_t)(q * (n - 1) / 1000);       // the quantile's index into the sorted codes
+    ranks[Q + j] = (uint32_t)((k < 1 ? 1 : k) - 1);  // the index of the last of the k smallest codes
+  }
+  HIPCHK(cs_scorepool_launch(map, is_f32, B, H, W, row_elems, image_stride, signed_range, ranks, Q, S, sum, quant, tail, window, scratch,
+                             (hipStream_t)stream));
+  return 0;
+}
+
+int cs_op_score_pool_f32(const float* score, int B, int H, int W, int signed_range, const int32_t* permille, int Q, int S, uint64_t* sum,
+                         uint32_t* quant, uint64_t* tail, uint64_t* window, void* scratch, cs_stream stream) {
+  return score_pool_op("score_pool_f32", score, 1, B, H, W, W, (long long)H * W, signed_range, permille, Q, S, sum, quant, tail, window, scratch, stream);
+}
+
+int cs_op_score_pool_u16(const uint16_t* codes, int B, int H, int W, int row_elems, long long image_stride_elems, const int32_t* permille, int Q,
+                         int S, uint64_t* sum, uint32_t* quant, uint64_t* tail, uint64_t* window, void* scratch, cs_stream stream) {
+  return score_pool_op("score_pool_u16", codes, 0, B, H, W, row_elems, image_stride_elems, 0, permille, Q, S, sum, quant, tail, window, scratch, stream);
+}
+
 int cs_op_score_to_rgb(const float* score, long long n, float vmin, float vmax, const uint8_t* lut256x3, uint8_t* out, cs_stream stream) {
   if (!score || !out || !lut256x3 || n <= 0 || !(vmax > vmin)) return fail(CS_ERR_BAD_ARG, "score_to_rgb: bad arguments");
   HIPCHK(cs_score_rgb_launch(score, (size_t)n, vmin, vmax, lut256x3, out, (hipStream_t)stream));

@@ -183,10 +183,7 @@ __global__ void resize_h_norm_kernel(const float* __restrict__ tmp, int rs_w, in
 __global__ void score_gray16_kernel(const float* __restrict__ score, size_t n, int signed_range, uint16_t* __restrict__ out) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float m = score[i];
-  const float v = signed_range ? (m + 1.0f) * 32767.0f : m * 65535.0f;
-  const int q = (int)v;  // truncation toward zero, like astype(int32)
-  out[i] = (uint16_t)(q < 0 ? 0 : (q > 65535 ? 65535 : q));
+  out[i] = (uint16_t)cs_score_code(score[i], signed_range);
 }
 
 // rgb: gray2rgb (utils/misc/image.py:37-52) = matplotlib Normalize(vmin, vmax) in fp32, colormap lookup with N = 256 entries

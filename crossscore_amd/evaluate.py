@@ -44,7 +44,7 @@ from typing import Dict, Iterable, List, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib, parallel, scoring
+from . import _lib, parallel, pooling, scoring
 from .config import load_config, this_main_choice
 from .data import EMPTY, InputStage, decode_items, metric_mode
 from .decode import read_image_u8, read_metric_map_u16
@@ -175,7 +175,9 @@ def decode_eval(items, zero_ref: bool, pool, skip=(), compute_gt: bool = False):
 def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None,
              capture: Optional[list] = None) -> Dict[str, object]:
     """Runs the test loop; returns {"version_dir", "out_dir", "metrics", "batches", "files", "query_images_per_sec", "input_stage", "png_encoder", "png_compression",
-    "png_files", "gt_metric_maps", "png_decoder", "png_decoded", "jpeg_decoder", "jpeg_decoded", "jpeg_progressive", "jpeg_progressive_decoded"}.
+    "png_files", "gt_metric_maps", "png_decoder", "png_decoded", "jpeg_decoder", "jpeg_decoded", "jpeg_progressive", "jpeg_progressive_decoded",
+    "score_pool"} and, with this_main.score_pool, "score_pool_correlation": per pooled value the Pearson coefficient of its pred_ column against
+    its gt_ column over this rank's rows whose ground truth is no placeholder.
     capture (tests, tools): a list that receives per batch {"batch_idx", "item_paths", "score", "gt", "stats"} (host copies)."""
     opts = scoring.options(cfg, "test")
     compute_gt = gt_metric_maps_choice(cfg) == "compute"  # this_main.gt_metric_maps: files (default) | compute
@@ -208,6 +210,9 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     batches = batches[:limit_batches(len(batches), cfg.trainer.limit_test_batches)]
     lib = _lib.load()
     rows: List[Dict[str, float]] = []
+    gt_pool: list = []  # this_main.score_pool: the pooling.ScorePool of the ground-truth maps, built with the first batch
+    pool_names = pooling.value_names(pooling.PERMILLE, opts.score_pool_window)
+    pool_signed = pooling.signed_range_of(cfg.model.predict.metric.type)  # cs_op_score_gt_stats' tensor, the range the writer stores it over
 
     def gt_files(it):
         if compute_gt:
@@ -221,7 +226,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
         return [None if it["query/score_map"] == EMPTY else d[it["query/score_map"]] for it in its]
 
     def gt_and_stats(ticket, its, decoded, maps, size, batch):
-        """GT stage + statistics kernel on the forward's stream, behind its score map; returns (gt, stats, event)."""
+        """GT stage + statistics kernel on the forward's stream, behind its score map; returns (gt, stats, event, the score pool's ticket)."""
         s = ticket.stream if ticket.stream is not None else torch.cuda.current_stream(device)
         oh, ow = size
         B = len(its)
@@ -248,7 +253,13 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
                                                 C.c_void_p(scratch.data_ptr()), C.c_void_p(s.cuda_stream)))
             ev = torch.cuda.Event()
             ev.record(s)
-        return gt, stats, ev
+        pooled = None
+        if opts.score_pool:  # the ground-truth maps pooled as the score maps are (pooling.py), behind the statistics kernel on the same stream
+            if not gt_pool:
+                gt_pool.append(pooling.ScorePool(device, opts.depth, pooling.PERMILLE, opts.score_pool_window))
+            placeholder = [not compute_gt and it["query/score_map"] == EMPTY for it in its]
+            pooled = (gt_pool[0].queue(gt, s, pool_signed), placeholder)
+        return gt, stats, ev, pooled
 
     def check_size(size):
         if crop_mode is None and (size[0] % patch or size[1] % patch):
@@ -256,7 +267,10 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
                              "fails in the L1 loss' broadcast); use crop_mode=integer_patches")
 
     def batch_stats(idx, batch, out, state):
-        gt, stats, ev = state
+        gt, stats, ev, pooled = state
+        if pooled is not None:  # the gt_ fields of the batch's score-pool rows; a placeholder ground truth reads nan in every one
+            values = gt_pool[0].rows(pooled[0])
+            batch["score_pool/extra"] = [pooling.format_fields(None if ph else v, pool_names) for v, ph in zip(values, pooled[1])]
         cur = torch.cuda.current_stream(device)
         cur.wait_event(ev)
         gt.record_stream(cur)
@@ -292,7 +306,8 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
         files.append(write_metrics_csv(version_dir, metrics))
         files.append(write_batches_csv(out_dir, all_rows))
     return {"version_dir": version_dir, "out_dir": out_dir, "metrics": metrics, "batches": sorted(rows, key=lambda r: r["batch_idx"]),
-            "files": files, "gt_metric_maps": "compute" if compute_gt else "files", **run.result}
+            "files": files, "gt_metric_maps": "compute" if compute_gt else "files", **run.result,
+            **({"score_pool_correlation": pooling.pool_correlation(run.pool_rows, run.pool_columns)} if opts.score_pool else {})}
 
 
 def main(argv: Optional[Iterable[str]] = None) -> int:

@@ -22,7 +22,7 @@ from typing import Dict, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import parallel, synth
+from . import parallel, pooling, synth
 from .data import EMPTY, STRATEGIES, ReferenceBank, ReferenceTokenCache, decode_items, load_batch, plan_decodes
 from .decode import DecodeWindow, ImageDecoder, jpeg_decoder_choice, jpeg_progressive_choice, png_decode_window_choice, png_decoder_choice, read_image_u8
 from .model import CrossScoreNet, U8Image, load_lightning_checkpoint
@@ -102,6 +102,11 @@ def options(cfg, phase: str) -> SimpleNamespace:
         raise ValueError("this_main.reference_use=True needs data.neighbour_config.cross >= 1: without reference views there is nothing to report")
     if o.reference_use_images and not (o.reference_use and bool(cfg.logger[phase].write.flag.batch)):
         raise ValueError(f"this_main.reference_use_images=True needs this_main.reference_use=True and logger.{phase}.write.flag.batch=True")
+    # this_main.score_pool (default off): behind every batch's forward the device pools its score maps -- per image the 16-bit
+    # mean, the 1 / 5 / 10 / 25 / 50 % quantiles, the means of the worst 1 / 5 / 10 / 25 / 50 % of the pixels and the worst window of
+    # this_main.score_pool_window pixels a side (default 56; 0: no window; only given with score_pool) -- and the run writes
+    # score_pool/<dataset>/<method>.csv beside the score summary (pooling.py).  evaluate pools the ground-truth maps the same way (gt_ columns).
+    o.score_pool, o.score_pool_window = pooling.pool_options(cfg)
     return o
 
 
@@ -178,6 +183,8 @@ class Scored(NamedTuple):
     failure: Optional[BaseException]  # what this rank's output stage raised: the driver re-raises it behind its collective
     nonfinite: int             # non-finite score-map values over the replicas
     operand_dtype: str
+    pool_rows: list = []       # this_main.score_pool: per image [scene_name, rendered_dir, image_name, fields ...] as the CSV holds them
+    pool_columns: list = []    # ... and the names of the fields
 
 
 def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: Optional[str] = None, *, calibrate: bool = False,
@@ -193,7 +200,8 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     check_size(size) may refuse a batch's processed size before anything of it is queued.
     reference_paths: the files of reference_dir, in the driver's order: the candidates of neighbour strategy similar.
     reference_groups (instead): candidate lists, of which each item names its own by "reference/cross/group" (nvs.NvsItems.groups).
-    after_submit(ticket, items, decoded, extras, size, batch) -> state; on_consume(idx, batch, out, state) runs before the summariser and writer."""
+    after_submit(ticket, items, decoded, extras, size, batch) -> state; on_consume(idx, batch, out, state) runs before the summariser and writer;
+    with this_main.score_pool it may leave per image the fields of its own score-pool columns in batch["score_pool/extra"] (evaluate: gt_*)."""
     phase, device = o.phase, o.device
     log = cfg.logger[phase]
     net = CrossScoreNet(cfg)
@@ -241,6 +249,11 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     bank_group = {g: k for k, g in enumerate(sorted({it["reference/cross/group"] for its in batches for it in its}))} if grouped else None
     selection = []  # ... and per query (path, chosen reference paths, their similarities), in consumption order
     use_rows = []   # this_main.reference_use: per query (path, reference paths, shares, peaks, focus), in consumption order
+    pool_rows = []  # this_main.score_pool: per query its key columns and fields, in consumption order
+    pool_names = pooling.value_names(pooling.PERMILLE, o.score_pool_window)
+    pool_columns = [f"pred_{k}" for k in pool_names] + ([f"gt_{k}" for k in pool_names] if phase == "test" else [])
+    pool_signed = pooling.signed_range_of(cfg.model.predict.metric.type)  # the range the gray16 writer stores this metric over
+    score_pool = None  # pooling.ScorePool, built with the first batch
     decoder = ImageDecoder(device, pool, png=o.png_decoder == "gpu", jpeg=o.jpeg_decoder == "gpu",
                          progressive=o.jpeg_progressive == "gpu") if "gpu" in (o.png_decoder, o.jpeg_decoder) else None
     window = DecodeWindow(decoder, plan_decodes(batches, zero_ref, cache is not None, extra_files), o.decode_window) if decoder is not None else None
@@ -278,8 +291,23 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
             ev.record(s)
         return host, ev
 
+    def stage_score_pool(ticket):
+        """the pooling of the batch's score maps and the copy of its words to pinned memory, queued behind the forward on its stream: read in consume"""
+        nonlocal score_pool
+        if not o.score_pool:
+            return None
+        if score_pool is None:
+            score_pool = pooling.ScorePool(device, pipe.depth, pooling.PERMILLE, o.score_pool_window)
+        return score_pool.queue(ticket.out["score_map_ref_cross"], ticket.stream, pool_signed)
+
+    def check(size):
+        if check_size is not None:
+            check_size(size)
+        if o.score_pool:
+            pooling.check_window(o.score_pool_window, size)
+
     def consume(entry):
-        ticket, batch, idx, state, use = entry
+        ticket, batch, idx, state, use, pooled = entry
         out = pipe.result(ticket)
         if window is not None:
             window.check(idx)  # the status words of the files this batch read: a rejected file raises here, naming its path
@@ -305,6 +333,11 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
         if on_consume is not None:
             on_consume(idx, batch, out, state)
         summariser.update(batch, out, means=out.get("score_mean_ref_cross"))  # the per-image means the head launch left (score_summariser.py:180-192)
+        if pooled is not None:
+            values = score_pool.rows(pooled)  # waits for the pool's event: its words are in pinned memory
+            extra = batch.get("score_pool/extra")
+            for b, (key, v) in enumerate(zip(summariser.rows[-len(values):], values)):  # (the summariser's key columns of the same images)
+                pool_rows.append(list(key[:3]) + pooling.format_fields(v, pool_names) + (list(extra[b]) if extra is not None else []))
         if writer is not None:
             files.extend(writer.write_out(batch, out, o.local_rank, idx))
             if o.reference_use_images:
@@ -319,8 +352,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
         decoded, extras = pending.result()
         if similar:
             batch, size = load_batch(its, stage, decoded, fused_in, references=False)
-            if check_size is not None:
-                check_size(size)
+            check(size)
             if bank is None:
                 bank = ReferenceBank(pipe, stage, reference_paths, tuple(size), n_cross, keep_images=keep_ref_images, max_images=o.cache_max_images,
                                      from_u8=fused_in, decoder=decoder, pool=pool, window=o.decode_window,
@@ -341,8 +373,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
         elif cache is None:
             pending = submit_decode(batch_idx + 1)
             batch, size = load_batch(its, stage, decoded, fused_in, zero_reference=zero_ref)
-            if check_size is not None:
-                check_size(size)
+            check(size)
             refs = batch["reference/cross/imgs"]
             if batch_idx == 0 and long_run:  # make sure the batches in flight really overlap (pipeline.py)
                 pipe.calibrate(batch["query/img"], refs, u8=fused_in)
@@ -354,17 +385,17 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
                 ticket = pipe.submit(batch["query/img"], refs, need_w, head_id, False, return_mean=True, **use_kw)
         else:
             batch, size = load_batch(its, stage, decoded, fused_in, references=False)
-            if check_size is not None:
-                check_size(size)
+            check(size)
             tokens, batch["reference/cross/imgs"] = cache.gather([it["reference/cross/imgs"] for it in its], decoded, size, zero_ref)
             # (submitted after gather so that the set of cached paths is current; decoding overlaps the forward below)
             pending = submit_decode(batch_idx + 1)
             if batch_idx == 0 and long_run:  # the same check for the (default) cached mode
                 pipe.calibrate(batch["query/img"], tokens, cached=True, u8=fused_in)
             ticket = (pipe.submit_cached_u8 if fused_in else pipe.submit_cached)(batch["query/img"], tokens, need_w, head_id, True, **use_kw)
+        pooled = stage_score_pool(ticket)
         state = after_submit(ticket, its, decoded, extras, tuple(size), batch) if after_submit is not None else None
         n_done += len(its)
-        queued.append((ticket, batch, batch_idx, state, stage_reference_use(ticket)))
+        queued.append((ticket, batch, batch_idx, state, stage_reference_use(ticket), pooled))
         while len(queued) >= pipe.depth:
             consume(queued.pop(0))
     while queued:
@@ -383,6 +414,8 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
             files.append(write_reference_selection(log.out_dir, selection, 5 if grouped else 1))
         if o.reference_use:
             files.append(write_reference_use(log.out_dir, use_rows, 5 if phase == "test" else 1))
+        if o.score_pool:
+            files += pooling.write_pool_csvs(log.out_dir, pool_rows, pool_columns)
     except BaseException as exc:  # noqa: BLE001 -- re-raised by the driver, behind its collective
         failure = exc
     finally:
@@ -395,6 +428,6 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
               "jpeg_decoder": o.jpeg_decoder, "jpeg_decoded": decoder.jpeg_stats() if o.jpeg_decoder == "gpu" else {"jpeg_decoded_gpu": 0, "jpeg_decoded_host": 0},
               "jpeg_progressive": o.jpeg_progressive,
               "jpeg_progressive_decoded": decoder.progressive_stats() if o.jpeg_progressive == "gpu" else {"jpeg_progressive_gpu": 0, "jpeg_progressive_host": 0},
-              "reference_strategy": o.strategy, "reference_use": o.reference_use,
+              "reference_strategy": o.strategy, "reference_use": o.reference_use, "score_pool": o.score_pool,
               "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}  # the whole scoring loop: input stage, forwards, output stage
-    return Scored(result, files, summariser.rows, failure, pipe.nonfinite_count(), net.operand_dtype)
+    return Scored(result, files, summariser.rows, failure, pipe.nonfinite_count(), net.operand_dtype, pool_rows, pool_columns)

@@ -443,6 +443,26 @@ class BatchWriter:
         return [str(p) for p in paths]
 
 
+def group_summary_rows(rows):
+    """score_summariser.py:197-250: the per-image rows ([scene_name, rendered_dir, image_name, ...], in scoring order) of each
+    <dataset>/<method>.csv: (dataset, method, its rows sorted by the three key columns), datasets and methods in order of first appearance.
+    The score summary and the score-pool CSVs (pooling.py) both come through here, so they hold the same images in the same order."""
+    part = ScoreSummariser._part
+    methods, datasets = [], []
+    for r in rows:
+        parts = r[1].split("/")
+        m, d = part(parts, -6), part(parts, -5)
+        if m not in methods:
+            methods.append(m)
+        if d not in datasets:
+            datasets.append(d)
+    for d in datasets:
+        for m in methods:
+            group = [r for r in rows if (m in r[1] or m == "unknown") and (d in r[1] or d == "unknown")]
+            group.sort(key=lambda r: (r[0], r[1], r[2]))
+            yield d, m, group
+
+
 class ScoreSummariser:
     """SummaryWriterPredictedOnlineTestPrediction: per-image mean scores -> score_summary/<dataset_type>/<rendering_method>.csv."""
 
@@ -476,28 +496,17 @@ class ScoreSummariser:
 
     def summarise(self) -> List[str]:
         """score_summariser.py:197-250: group by rendered_dir components, sort, write with float_format "%.4f"."""
-        methods, datasets = [], []
-        for r in self.rows:
-            parts = r[1].split("/")
-            m, d = self._part(parts, -6), self._part(parts, -5)
-            if m not in methods:
-                methods.append(m)
-            if d not in datasets:
-                datasets.append(d)
         written = []
-        for d in datasets:
-            for m in methods:
-                rows = [r for r in self.rows if (m in r[1] or m == "unknown") and (d in r[1] or d == "unknown")]
-                rows.sort(key=lambda r: (r[0], r[1], r[2]))
-                out_dir = self.csv_dir / d
-                out_dir.mkdir(parents=True, exist_ok=True)
-                path = out_dir / f"{m}.csv"
-                with open(path, "w", newline="") as f:
-                    w = csv.writer(f, lineterminator="\n")
-                    w.writerow(self.columns)
-                    for r in rows:
-                        w.writerow([r[0], r[1], r[2], "%.4f" % r[3]])
-                written.append(str(path))
+        for d, m, rows in group_summary_rows(self.rows):
+            out_dir = self.csv_dir / d
+            out_dir.mkdir(parents=True, exist_ok=True)
+            path = out_dir / f"{m}.csv"
+            with open(path, "w", newline="") as f:
+                w = csv.writer(f, lineterminator="\n")
+                w.writerow(self.columns)
+                for r in rows:
+                    w.writerow([r[0], r[1], r[2], "%.4f" % r[3]])
+            written.append(str(path))
         return written
 
     def __len__(self) -> int:

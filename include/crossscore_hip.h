@@ -556,6 +556,32 @@ int cs_op_gt_metric_sums_u8(const uint8_t* render, const uint8_t* gt, int B, int
  * cs_score_gt_workspace_bytes(B, H, W) bytes. */
 size_t cs_score_gt_workspace_bytes(int B, int H, int W);
 int cs_op_score_gt_stats(const float* score, const float* gt, int B, int H, int W, double* stats, void* scratch, cs_stream stream);
+/* Score pooling: order statistics, worst-tail sums and the worst window of a batch of maps (crossscore_amd/pooling.py; DESIGN.md section 6, row
+ * f13).  A map is H x W codes c in [0, 65535], n = H * W.  cs_op_score_pool_u16: the codes are the samples of B uint16 maps [B][H][row_elems],
+ * row_elems >= W, maps image_stride_elems >= (H - 1) * row_elems + W samples apart; only [row, row + W) of a row is read.
+ * cs_op_score_pool_f32: B contiguous fp32 maps; a pixel's code is exactly what cs_op_score_to_gray16 stores for it with the same signed_range
+ * (m * 65535, or (m + 1) * 32767, truncated and clipped; NaN, +-Inf, -0.0 and values outside the range included: one device function).
+ * With s[0] <= ... <= s[n - 1] the sorted codes and `permille` a HOST array of Q values q_j in [0, 1000] (1 <= Q <= 16, any order, duplicates
+ * allowed), per map b:
+ *   sum[b]       = sum c                                                       (u64)
+ *   quant[b][j]  = s[(q_j * (n - 1)) / 1000]   integer division in 64 bits     (u32; q = 0 the minimum, 1000 the maximum, 500 the lower median)
+ *   tail[b][j]   = sum of s[i], i < k_j,  k_j = max(1, (q_j * n) / 1000)       (u64; the k_j worst pixels; q = 1000 gives sum)
+ *   window[b][0] = the smallest sum of codes over all S x S windows lying fully inside the map (1 <= S <= min(H, W, 255): below 2^32),
+ *   window[b][1], window[b][2] = the y, x of its top-left corner; ties go to the smallest y, then the smallest x          (u64 each)
+ * unsigned integers, exact; nothing is formed in floating point on the device.  The host forms values in the units of the written 16-bit map,
+ * v = c / 65535 (signed_range 0) or c / 32767 - 1 (signed_range 1): a quantile v(quant), a tail mean v(tail / k), the window mean
+ * v(window[0] / S^2), the 16-bit mean v(sum / n).  Integer addition and min on the packed (sum, y, x) key are associative: a map's words are the
+ * same alone and at any position of any batch, whatever the order of tiles and atomics.
+ * window == NULL or S == 0 skips the window launches.  Both ops initialise what they accumulate into on `stream` and queue their launches there;
+ * nothing is waited for or allocated.  1 <= B <= 1024, 1 <= H, W <= 4096 (CS_ERR_UNSUPPORTED above).  S > min(H, W), S > 255, Q outside
+ * [1, 16], a permille outside [0, 1000], a null required pointer and row_elems < W are CS_ERR_BAD_ARG, rejected before anything is queued.
+ * sum, tail, window: device, 8-byte aligned; quant: 4-byte aligned; scratch: device, 16-byte aligned, at least
+ * cs_score_pool_workspace_bytes(B, H, W, Q) bytes (host arithmetic; 0 for sizes the ops do not take). */
+size_t cs_score_pool_workspace_bytes(int B, int H, int W, int Q);
+int cs_op_score_pool_f32(const float* score, int B, int H, int W, int signed_range, const int32_t* permille, int Q, int S, uint64_t* sum,
+                         uint32_t* quant, uint64_t* tail, uint64_t* window, void* scratch, cs_stream stream);
+int cs_op_score_pool_u16(const uint16_t* codes, int B, int H, int W, int row_elems, long long image_stride_elems, const int32_t* permille, int Q,
+                         int S, uint64_t* sum, uint32_t* quant, uint64_t* tail, uint64_t* window, void* scratch, cs_stream stream);
 int cs_op_pos_bicubic(const float* pos, int G, int C, int gh, int gw, float* out, cs_stream stream);
 /* the same with the resize convention as an argument: legacy = 0 F.interpolate(size=(gh, gw)) (cs_op_pos_bicubic), 1 the reference's pinned
  * transformers 4.33.3 form scale_factor=((gh + 0.1) / G, (gw + 0.1) / G) (cs_config.pos_interp_legacy; golden tests/golden/g6_pos_legacy.npz) */
