@@ -64,6 +64,18 @@ class CsJpegScanInfo(C.Structure):
     _fields_ = [("process", C.c_int), ("scans", C.c_int), ("entropy_offset", C.c_ulonglong)]
 
 
+SHEET_FILL, SHEET_IMAGE, SHEET_BLEND, SHEET_RAMP, SHEET_FRAME, SHEET_TEXT = range(6)  # cs_sheet_panel.kind (CS_SHEET_*)
+SHEET_MAX_PANELS, SHEET_MAX_SIDE = 48, 4096  # CS_SHEET_MAX_*
+
+
+class CsSheetPanel(C.Structure):
+    """cs_sheet_panel: one panel of cs_op_sheet_compose."""
+    _fields_ = [("kind", C.c_int), ("dst_y", C.c_int), ("dst_x", C.c_int), ("dst_h", C.c_int), ("dst_w", C.c_int),
+                ("src", C.c_void_p), ("src_h", C.c_int), ("src_w", C.c_int), ("src_row_bytes", C.c_int),
+                ("src2", C.c_void_p), ("src2_h", C.c_int), ("src2_w", C.c_int), ("src2_row_bytes", C.c_int),
+                ("rgb", C.c_uint8 * 3), ("param", C.c_int), ("text", C.c_char * 16)]
+
+
 # every symbol include/crossscore_hip.h declares: name -> (restype, argtypes)
 _vp, _i, _f, _ll, _sz = C.c_void_p, C.c_int, C.c_float, C.c_longlong, C.c_size_t
 _fp = C.POINTER(C.c_float)
@@ -153,6 +165,7 @@ SYMBOLS = {
     "cs_score_pool_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "cs_op_score_pool_f32": (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cs_op_score_pool_u16": (_i, [_vp, _i, _i, _i, _i, _ll, C.POINTER(C.c_int32), _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cs_op_sheet_compose": (_i, [C.POINTER(CsSheetPanel), _i, _vp, _i, _i, _vp]),
     "cs_op_preprocess_u8": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _vp, _vp, _vp]),
     "cs_op_pack_f16": (_i, [_vp, _i, _i, _vp, _i, _vp, _vp, _vp]),
     "cs_op_streams_overlap": (_i, [_vp, _vp, _vp]),

@@ -243,6 +243,19 @@ struct CsU8Desc {
 // the (G, C) centres it is centred with.  Checked on the host, uploaded with the call, clamped again where the device reads it.
 struct CsSelTriple { int start, len, centre; };
 
+// Preview sheet (sheet.hip): a panel as the kernel takes it, checked and translated from the public cs_sheet_panel by
+// cs_op_sheet_compose (kind: the public CS_SHEET_* values), and the block of them that travels as one kernel argument.
+struct CsSheetPanel {
+  const uint8_t* src;         // IMAGE, BLEND: uint8 HWC RGB, rows row_bytes apart; RAMP: the 256 x 3 table
+  const uint8_t* src2;        // BLEND: the second image, sh x sw as the first, rows row_bytes2 apart
+  unsigned long long glyphs;  // TEXT: the glyph index of character i in bits [4 i, 4 i + 4)
+  int kind, y, x, h, w;       // the destination rectangle, inside the canvas
+  int sh, sw, row_bytes, row_bytes2;
+  uint32_t rgb;               // r | g << 8 | b << 16
+  int param;                  // FRAME: thickness; TEXT: scale
+};
+struct CsSheetPanels { CsSheetPanel p[48]; };  // (CS_SHEET_MAX_PANELS: 48 x 72 bytes, inside the 4 KiB a kernel's arguments may take)
+
 // Encoder "token panel" kernel (panel.hip): one launch per DINOv2 layer does, for 128-row panels of the residual stream,
 //   x += attn_o Wo'^T + bo'                 (attention output projection, LayerScale folded; HF modeling_dinov2.py:249-252,365-370)
 //   x += GELU(LN2(x) W1'^T + b1') W2'^T + b2'   (norm2 + MLP + LayerScale; HF:373-378, 293-297)
@@ -394,4 +407,6 @@ size_t cs_scorepool_workspace(int B, int H, int W);
 hipError_t cs_scorepool_launch(const void* map, int is_f32, int B, int H, int W, int row_elems, long long image_stride, int signed_range,
                                const uint32_t* ranks, int Q, int S, uint64_t* sum, uint32_t* quant, uint64_t* tail, uint64_t* window,
                                void* scratch, hipStream_t st);
+// sheet.hip
+hipError_t cs_sheet_launch(const CsSheetPanels* panels, int n, uint8_t* canvas, int ch, int cw, hipStream_t st);
 }

@@ -3,6 +3,7 @@
 #include "cs_model.h"
 #include "jpeg_probe.h"
 #include "png_probe.h"
+#include "sheet_font.h"
 
 #include <cmath>
 #include <cstring>
@@ -348,6 +349,62 @@ int cs_op_score_pool_f32(const float* score, int B, int H, int W, int signed_ran
 int cs_op_score_pool_u16(const uint16_t* codes, int B, int H, int W, int row_elems, long long image_stride_elems, const int32_t* permille, int Q,
                          int S, uint64_t* sum, uint32_t* quant, uint64_t* tail, uint64_t* window, void* scratch, cs_stream stream) {
   return score_pool_op("score_pool_u16", codes, 0, B, H, W, row_elems, image_stride_elems, 0, permille, Q, S, sum, quant, tail, window, scratch, stream);
+}
+
+// every check of the header's contract, then the panels in the kernel's form: one launch
+int cs_op_sheet_compose(const cs_sheet_panel* panels, int n_panels, uint8_t* canvas, int canvas_h, int canvas_w, cs_stream stream) {
+  static_assert(sizeof(CsSheetPanels) == CS_SHEET_MAX_PANELS * sizeof(CsSheetPanel) && sizeof(CsSheetPanels) + 64 <= 4096, "kernel arguments");
+  const int kMax = CS_SHEET_MAX_SIDE;
+  if (!canvas || canvas_h <= 0 || canvas_w <= 0 || n_panels < 0 || (n_panels > 0 && !panels))
+    return fail(CS_ERR_BAD_ARG, "sheet_compose: bad arguments (canvas %d x %d, %d panels)", canvas_h, canvas_w, n_panels);
+  if (n_panels > CS_SHEET_MAX_PANELS) return fail(CS_ERR_UNSUPPORTED, "sheet_compose: %d panels are more than %d", n_panels, CS_SHEET_MAX_PANELS);
+  if (canvas_h > kMax || canvas_w > kMax) return fail(CS_ERR_UNSUPPORTED, "sheet_compose: a %d x %d canvas is above %d a side", canvas_h, canvas_w, kMax);
+  CsSheetPanels dev{};
+  for (int i = 0; i < n_panels; ++i) {
+    const cs_sheet_panel& p = panels[i];
+    CsSheetPanel& q = dev.p[i];
+    if (p.kind < CS_SHEET_FILL || p.kind > CS_SHEET_TEXT) return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d has the unknown kind %d", i, p.kind);
+    const bool image = p.kind == CS_SHEET_IMAGE || p.kind == CS_SHEET_BLEND;
+    if (p.dst_h > kMax || p.dst_w > kMax || (image && (p.src_h > kMax || p.src_w > kMax)))
+      return fail(CS_ERR_UNSUPPORTED, "sheet_compose: panel %d (%d x %d from %d x %d) has a side above %d", i, p.dst_h, p.dst_w, p.src_h, p.src_w, kMax);
+    if (p.dst_h <= 0 || p.dst_w <= 0) return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d has the empty rectangle %d x %d", i, p.dst_h, p.dst_w);
+    if (p.dst_y < 0 || p.dst_x < 0 || p.dst_y > canvas_h - p.dst_h || p.dst_x > canvas_w - p.dst_w)
+      return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d (%d x %d at %d, %d) does not lie inside the %d x %d canvas", i, p.dst_h, p.dst_w, p.dst_y,
+                  p.dst_x, canvas_h, canvas_w);
+    q.kind = p.kind; q.y = p.dst_y; q.x = p.dst_x; q.h = p.dst_h; q.w = p.dst_w;
+    q.rgb = (uint32_t)p.rgb[0] | (uint32_t)p.rgb[1] << 8 | (uint32_t)p.rgb[2] << 16;
+    q.param = p.param;
+    if (image) {
+      if (!p.src || p.src_h <= 0 || p.src_w <= 0 || p.src_row_bytes < 3 * p.src_w)
+        return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d has no source, an empty one or rows of %d bytes below 3 x %d", i, p.src_row_bytes, p.src_w);
+      q.src = p.src; q.sh = p.src_h; q.sw = p.src_w; q.row_bytes = p.src_row_bytes;
+      if (p.kind == CS_SHEET_BLEND) {
+        if (!p.src2 || p.src2_row_bytes < 3 * p.src2_w) return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d has no second source or too short rows", i);
+        if (p.src2_h != p.src_h || p.src2_w != p.src_w)
+          return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d blends %d x %d with %d x %d", i, p.src_h, p.src_w, p.src2_h, p.src2_w);
+        q.src2 = p.src2; q.row_bytes2 = p.src2_row_bytes;
+      }
+    } else if (p.kind == CS_SHEET_RAMP) {
+      if (!p.src) return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d has no colour table", i);
+      q.src = p.src;
+    } else if (p.kind == CS_SHEET_FRAME) {
+      if (p.param < 1) return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d has the thickness %d", i, p.param);
+    } else if (p.kind == CS_SHEET_TEXT) {
+      int n = 0;
+      while (n < 16 && p.text[n]) ++n;
+      if (p.param < 1 || n < 1) return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d has the scale %d and %d characters", i, p.param, n);
+      for (int k = 0; k < n; ++k) {
+        const int g = sheet_glyph_index(p.text[k]);
+        if (g < 0) return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d has a character (code %d) outside \"%s\"", i, (int)p.text[k], CS_SHEET_CHARS);
+        q.glyphs |= (unsigned long long)g << (4 * k);
+      }
+      if (p.param > kMax || p.dst_h != 7 * p.param || p.dst_w != (6 * n - 1) * p.param)
+        return fail(CS_ERR_BAD_ARG, "sheet_compose: panel %d: %d characters at scale %d take %d x %d, not %d x %d", i, n, p.param, 7 * p.param,
+                    (6 * n - 1) * p.param, p.dst_h, p.dst_w);
+    }
+  }
+  HIPCHK(cs_sheet_launch(&dev, n_panels, canvas, canvas_h, canvas_w, (hipStream_t)stream));
+  return 0;
 }
 
 int cs_op_score_to_rgb(const float* score, long long n, float vmin, float vmax, const uint8_t* lut256x3, uint8_t* out, cs_stream stream) {

@@ -176,7 +176,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
              capture: Optional[list] = None) -> Dict[str, object]:
     """Runs the test loop; returns {"version_dir", "out_dir", "metrics", "batches", "files", "query_images_per_sec", "input_stage", "png_encoder", "png_compression",
     "png_files", "gt_metric_maps", "png_decoder", "png_decoded", "jpeg_decoder", "jpeg_decoded", "jpeg_progressive", "jpeg_progressive_decoded",
-    "score_pool"} and, with this_main.score_pool, "score_pool_correlation": per pooled value the Pearson coefficient of its pred_ column against
+    "score_pool", "vis_sheet", "vis_sheets"} and, with this_main.score_pool, "score_pool_correlation": per pooled value the Pearson coefficient of its pred_ column against
     its gt_ column over this rank's rows whose ground truth is no placeholder.
     capture (tests, tools): a list that receives per batch {"batch_idx", "item_paths", "score", "gt", "stats"} (host copies)."""
     opts = scoring.options(cfg, "test")
@@ -278,6 +278,9 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
         m = batch_metrics(st, gt.shape[1] * gt.shape[2])
         rows.append(dict(m, batch_idx=idx, rank=rank, batch_size=int(gt.shape[0])))
         batch["query/score_map"] = gt
+        if opts.vis_sheet:  # item 0's ground-truth mean and L1 for its preview sheet, from the sums read above
+            n = float(gt.shape[1] * gt.shape[2])
+            batch["vis_sheet/extra"] = (float(st[0][2]) / n, float(st[0][0]) / n)
         if capture is not None:
             capture.append({"batch_idx": idx, "item_paths": batch["item_paths"], "score": out["score_map_ref_cross"].cpu().numpy(),
                             "gt": gt.cpu().numpy(), "stats": st})

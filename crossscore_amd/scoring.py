@@ -22,7 +22,7 @@ from typing import Dict, NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import parallel, pooling, synth
+from . import parallel, pooling, synth, vis
 from .data import EMPTY, STRATEGIES, ReferenceBank, ReferenceTokenCache, decode_items, load_batch, plan_decodes
 from .decode import DecodeWindow, ImageDecoder, jpeg_decoder_choice, jpeg_progressive_choice, png_decode_window_choice, png_decoder_choice, read_image_u8
 from .model import CrossScoreNet, U8Image, load_lightning_checkpoint
@@ -107,6 +107,10 @@ def options(cfg, phase: str) -> SimpleNamespace:
     # this_main.score_pool_window pixels a side (default 56; 0: no window; only given with score_pool) -- and the run writes
     # score_pool/<dataset>/<method>.csv beside the score summary (pooling.py).  evaluate pools the ground-truth maps the same way (gt_ columns).
     o.score_pool, o.score_pool_window = pooling.pool_options(cfg)
+    # this_main.vis_sheet (default off): every logger.<phase>.write.config.vis_img_every_n_steps-th batch writes the preview
+    # sheet of its item 0 to vis/r<rank>_B<batch>_b0.png (vis.py), whatever write.flag.batch says, as in the reference.  The sheet is built from
+    # the processed images: like image_query it keeps fused_input_stage=auto on the two-launch stage and is refused with fused_input_stage=True.
+    o.vis_sheet, o.vis_every = vis.sheet_options(cfg, phase)
     return o
 
 
@@ -201,7 +205,8 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     reference_paths: the files of reference_dir, in the driver's order: the candidates of neighbour strategy similar.
     reference_groups (instead): candidate lists, of which each item names its own by "reference/cross/group" (nvs.NvsItems.groups).
     after_submit(ticket, items, decoded, extras, size, batch) -> state; on_consume(idx, batch, out, state) runs before the summariser and writer;
-    with this_main.score_pool it may leave per image the fields of its own score-pool columns in batch["score_pool/extra"] (evaluate: gt_*)."""
+    with this_main.score_pool it may leave per image the fields of its own score-pool columns in batch["score_pool/extra"] (evaluate: gt_*),
+    with this_main.vis_sheet item 0's ground-truth mean and L1 in batch["vis_sheet/extra"]."""
     phase, device = o.phase, o.device
     log = cfg.logger[phase]
     net = CrossScoreNet(cfg)
@@ -223,6 +228,8 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     writer = (BatchWriter(cfg, phase, net.img_mean_std, device, workers=max(1, int(cfg.data.loader.validation.num_workers) // 2),
                           png_encoder=o.png_encoder, png_compression=o.png_compression)
               if log.write.flag.batch else None)
+    sheets = (vis.SheetWriter(cfg, phase, net.img_mean_std, device, png_encoder=o.png_encoder, png_compression=o.png_compression)
+              if o.vis_sheet and o.vis_every > 0 else None)
     summariser = ScoreSummariser(cfg.model.predict.metric.type, cfg.model.predict.metric.min, log.out_dir)
     zero_ref = bool(cfg.data.dataset.zero_reference)
     # Host side of the loader: the file lists of all batches are fixed up front, images are decoded by `num_workers` threads, and the next
@@ -230,7 +237,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     pool = ThreadPoolExecutor(max_workers=max(1, int(cfg.data.loader.validation.num_workers)))
     prefetch = ThreadPoolExecutor(max_workers=1)
     pipe = ForwardPipeline(net, depth=o.depth)
-    want_imgs = writer is not None and bool(log.write.flag.image_query or log.write.flag.image_reference)
+    want_imgs = (writer is not None and bool(log.write.flag.image_query or log.write.flag.image_reference)) or sheets is not None
     fused_in = False
     if o.fused not in (False, "false", "False", 0) and probe_path is not None and not want_imgs:
         probe = read_image_u8(probe_path)
@@ -240,7 +247,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
         raise ValueError("this_main.fused_input_stage=True, but " + (f"the writers need the processed images (logger.{phase}.write.flag.image_query / "
                          "image_reference)" if want_imgs else "this backbone / image geometry is not taken by the one-pass input stage"))
     similar = o.strategy == "similar"
-    keep_ref_images = bool(writer is not None and log.write.flag.image_reference)
+    keep_ref_images = bool(writer is not None and log.write.flag.image_reference) or sheets is not None
     cache = ReferenceTokenCache(pipe, stage, keep_images=keep_ref_images,
                                 max_images=o.cache_max_images, from_u8=fused_in) if o.use_cache and not similar else None
     bank = None  # neighbour strategy similar: data.ReferenceBank, built when the first batch tells the processed size
@@ -333,11 +340,18 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
         if on_consume is not None:
             on_consume(idx, batch, out, state)
         summariser.update(batch, out, means=out.get("score_mean_ref_cross"))  # the per-image means the head launch left (score_summariser.py:180-192)
+        worst = None  # item 0's worst window (y, x, S), for its sheet
         if pooled is not None:
             values = score_pool.rows(pooled)  # waits for the pool's event: its words are in pinned memory
             extra = batch.get("score_pool/extra")
             for b, (key, v) in enumerate(zip(summariser.rows[-len(values):], values)):  # (the summariser's key columns of the same images)
                 pool_rows.append(list(key[:3]) + pooling.format_fields(v, pool_names) + (list(extra[b]) if extra is not None else []))
+            if o.score_pool_window:
+                worst = (values[0]["window_y"], values[0]["window_x"], o.score_pool_window)
+        if sheets is not None and vis.sheet_due(idx, o.vis_every):
+            # (the number on the sheet is the score summary's: the mean as its CSV holds it, four digits)
+            mean0 = float("%.4f" % summariser.rows[-len(batch["item_paths"]["query/img"])][3])
+            files.extend(sheets.write(batch, out, o.local_rank, idx, mean0, worst, batch.get("vis_sheet/extra")))
         if writer is not None:
             files.extend(writer.write_out(batch, out, o.local_rank, idx))
             if o.reference_use_images:
@@ -409,6 +423,8 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     try:
         if writer is not None:
             writer.finish()
+        if sheets is not None:
+            sheets.finish()
         files += summariser.summarise()
         if similar:
             files.append(write_reference_selection(log.out_dir, selection, 5 if grouped else 1))
@@ -429,5 +445,6 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
               "jpeg_progressive": o.jpeg_progressive,
               "jpeg_progressive_decoded": decoder.progressive_stats() if o.jpeg_progressive == "gpu" else {"jpeg_progressive_gpu": 0, "jpeg_progressive_host": 0},
               "reference_strategy": o.strategy, "reference_use": o.reference_use, "score_pool": o.score_pool,
+              "vis_sheet": o.vis_sheet, "vis_sheets": sheets.sheets if sheets is not None else 0,
               "query_images_per_sec": n_done / t_loop if t_loop > 0 else 0.0}  # the whole scoring loop: input stage, forwards, output stage
     return Scored(result, files, summariser.rows, failure, pipe.nonfinite_count(), net.operand_dtype, pool_rows, pool_columns)

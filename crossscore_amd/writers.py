@@ -15,8 +15,8 @@ PCIe instead of 4).  PNG compression has two forms, chosen by `this_main.png_enc
                    Pixel-exact, valid PNGs, not byte-equal to PIL's (independent 16-KiB segments).  `this_main.png_compression`: fast =
                    Sub filter, fixed-Huffman / stored blocks (larger files); compact = per-row adaptive filter, dynamic-Huffman blocks.
 Attention-weight images and the item-path JSON always take the host path.  The reference-use images (this_main.reference_use_images; DESIGN.md 6,
-f12) are coloured on the device for both encoders (cs_op_score_to_rgb on [0, 1]) and then take the chosen one, so the two give equal pixels.  The composite matplotlib "vis" figure (task/core.py:422-434)
-is not reproduced.
+f12) are coloured on the device for both encoders (cs_op_score_to_rgb on [0, 1]) and then take the chosen one, so the two give equal pixels.  The composite "vis" figure (task/core.py:422-434) has a form of this build's own, the preview sheet
+of vis.py (this_main.vis_sheet), composed on the device from the integer images formed here.
 """
 from __future__ import annotations
 

@@ -582,6 +582,41 @@ int cs_op_score_pool_f32(const float* score, int B, int H, int W, int signed_ran
                          uint32_t* quant, uint64_t* tail, uint64_t* window, void* scratch, cs_stream stream);
 int cs_op_score_pool_u16(const uint16_t* codes, int B, int H, int W, int row_elems, long long image_stride_elems, const int32_t* permille, int Q,
                          int S, uint64_t* sum, uint32_t* quant, uint64_t* tail, uint64_t* window, void* scratch, cs_stream stream);
+/* Preview sheet: up to CS_SHEET_MAX_PANELS panels painted into one (canvas_h, canvas_w, 3) uint8 canvas, in one launch (crossscore_amd/vis.py;
+ * DESIGN.md section 6, row f14).  `panels` is a HOST array: its entries travel as kernel arguments, nothing is uploaded, waited for or allocated.
+ * Panels are painted in array order, a later one covers an earlier one; a canvas pixel no panel covers is (0, 0, 0); every canvas byte is stored
+ * exactly once and nothing else is.  Integer arithmetic throughout.  A panel's rectangle (dst_y, dst_x, dst_h, dst_w) lies inside the canvas; r, c
+ * below are a pixel's row and column inside it.
+ *   CS_SHEET_FILL   the rectangle takes rgb.
+ *   CS_SHEET_IMAGE  exact area resampling of src (src_h x src_w uint8 HWC RGB, rows src_row_bytes >= 3 src_w apart) into dst_h x dst_w: with
+ *                   sh, sw, dh, dw the four sizes, wx[i][j] = max(0, min((i + 1) dw, (j + 1) sw) - max(i dw, j sw)) and wy likewise with the
+ *                   heights, per channel S = sum_iy sum_ix wy[iy][r] wx[ix][c] v[iy][ix] and out = (S + (sh sw) / 2) / (sh sw), integer
+ *                   division (S < 2^32).  Equal sizes copy, an integer factor gives the rounded box mean, enlarging is allowed.
+ *   CS_SHEET_BLEND  the same resampling of the image (a + b + 1) >> 1, formed per source pixel: a = src, b = src2 (src2_h x src2_w equal to
+ *                   src_h x src_w, rows src2_row_bytes apart).
+ *   CS_SHEET_RAMP   src is a 256 x 3 byte table; row r takes its entry 255 - (r 256) / dst_h.
+ *   CS_SHEET_FRAME  the pixels with r < param, r >= dst_h - param, c < param or c >= dst_w - param take rgb (param >= 1: the outline, param
+ *                   pixels thick on the inside); the others are untouched.
+ *   CS_SHEET_TEXT   text: n = 1 .. 16 characters of "0123456789.- " (up to the first NUL) in a 5 x 7 font scaled by param >= 1
+ *                   (csrc/sheet_font.h): the pixel takes rgb where bit 4 - gx of row gy of the glyph of character c / (6 param) is set, with
+ *                   gx = (c mod 6 param) / param < 5 and gy = r / param; the others are untouched.  The rectangle is 7 param x (6 n - 1) param.
+ * CS_ERR_BAD_ARG: a NULL canvas or panel array, an unknown kind, an empty rectangle or one outside the canvas, a NULL source where the kind reads
+ * one, src_row_bytes < 3 src_w, unequal BLEND sources, param < 1, a TEXT rectangle of another size, no or an unknown character.
+ * CS_ERR_UNSUPPORTED: more than CS_SHEET_MAX_PANELS panels, a canvas, rectangle or source side above CS_SHEET_MAX_SIDE.  Both before any launch. */
+enum { CS_SHEET_FILL = 0, CS_SHEET_IMAGE = 1, CS_SHEET_BLEND = 2, CS_SHEET_RAMP = 3, CS_SHEET_FRAME = 4, CS_SHEET_TEXT = 5 };
+enum { CS_SHEET_MAX_PANELS = 48, CS_SHEET_MAX_SIDE = 4096 };
+typedef struct {
+  int kind;
+  int dst_y, dst_x, dst_h, dst_w;
+  const uint8_t* src; /* device */
+  int src_h, src_w, src_row_bytes;
+  const uint8_t* src2; /* device */
+  int src2_h, src2_w, src2_row_bytes;
+  uint8_t rgb[3];
+  int param;
+  char text[16];
+} cs_sheet_panel;
+int cs_op_sheet_compose(const cs_sheet_panel* panels, int n_panels, uint8_t* canvas, int canvas_h, int canvas_w, cs_stream stream);
 int cs_op_pos_bicubic(const float* pos, int G, int C, int gh, int gw, float* out, cs_stream stream);
 /* the same with the resize convention as an argument: legacy = 0 F.interpolate(size=(gh, gw)) (cs_op_pos_bicubic), 1 the reference's pinned
  * transformers 4.33.3 form scale_factor=((gh + 0.1) / G, (gw + 0.1) / G) (cs_config.pos_interp_legacy; golden tests/golden/g6_pos_legacy.npz) */
