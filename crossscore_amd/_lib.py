@@ -182,6 +182,21 @@ SYMBOLS = {
     "cs_op_linear_layernorm_linear": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _vp, _i, _i, _vp]),
     "cs_debug_rowln_enable": (None, [_i]),
     "cs_op_encoder_panel": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _vp]),
+    # head fit (csrc/headfit.hip)
+    "cs_head_fit_supported": (_i, [_i, _i]),
+    "cs_head_fit_row_tile": (_i, []),
+    "cs_head_fit_row_chunk": (_i, []),
+    "cs_head_fit_g_columns": (_i, []),
+    "cs_head_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cs_gemm_tn_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cs_op_head_grad_z": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cs_debug_op_head_grad_z_tap": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cs_op_gemm_tn": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp]),
+    "cs_op_head_backward": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cs_head_backward": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cs_debug_head_inputs": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "cs_op_adamw": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _i, _vp, _vp]),
+    "cs_set_head_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

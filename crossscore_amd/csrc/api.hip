@@ -119,6 +119,7 @@ void cs_destroy(cs_handle h) {
   for (auto& t : h->tables) { if (t.pos_owned) hipFree(t.pos_tab); if (t.pe_owned) hipFree(t.pe_tab); }
   reap_retired(h, true);
   if (h->ws) hipFree(h->ws);
+  if (h->hfit_ws) hipFree(h->hfit_ws);
   if (h->ev_done) hipEventDestroy(h->ev_done);
   if (h->ev_kv0) hipEventDestroy(h->ev_kv0);
   if (h->ev_kv1) hipEventDestroy(h->ev_kv1);
@@ -473,6 +474,26 @@ int cs_nonfinite_count(cs_handle h, long long* count) {
 void cs_debug_stream_probe_log(int on) { g_debug_stream_log = on; }
 void cs_debug_rowln_enable(int on) { g_rowln_off = on == 0 ? 1 : 0; g_rowln_no_next = on == 2 ? 1 : 0; }
 void cs_debug_panel_impl(int impl) { g_panel_impl = impl ? 1 : 0; }
+
+// Head fit: changed head weights back into the finalised handle.  The four fp32 device arrays are re-packed into the buffers
+// cs_finalize allocated (Wh0 / Wh2 in the handle's operand type, the biases in fp32), on `stream`, behind the handle's last call.
+int cs_set_head_weights(cs_handle h, const float* w0, const float* b0, const float* w2, const float* b2, cs_stream stream) {
+  if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
+  if (!h->finalized) return fail(CS_ERR_STATE, "cs_set_head_weights before cs_finalize");
+  if (!w0 || !b0 || !w2 || !b2) return fail(CS_ERR_BAD_ARG, "cs_set_head_weights: null pointer");
+  if (((uintptr_t)w0 | (uintptr_t)b0 | (uintptr_t)w2 | (uintptr_t)b2) & 3) return fail(CS_ERR_BAD_ARG, "cs_set_head_weights: misaligned pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int C = h->cfg.hidden, PP = h->cfg.patch * h->cfg.patch;
+  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
+  HIPCHK(cs_pack_f16_launch(w0, C, C, h->Wh0, C, nullptr, nullptr, h->cfg.operand_dtype, st));
+  HIPCHK(cs_pack_f16_launch(w2, PP, C, h->Wh2, C, nullptr, nullptr, h->cfg.operand_dtype, st));
+  HIPCHK(hipMemcpyAsync(h->bh0, b0, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(h->bh2, b2, (size_t)PP * 4, hipMemcpyDeviceToDevice, st));
+  if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(h->ev_done, st));
+  h->last_stream = st;
+  return 0;
+}
 
 int cs_debug_set_op_operand_dtype(int dtype) {
   if (dtype != 0 && dtype != 1) return fail(CS_ERR_BAD_ARG, "operand dtype must be 0 (fp16) or 1 (bf16)");

@@ -291,6 +291,34 @@ struct CsRowLnParams {
   int n2, act2;                 // act2: 0 none, 1 ReLU, 2 LeakyReLU(0.01)
 };
 
+// Head fit (headfit.hip).  The tile sizes are here because the tests read them through cs_head_fit_row_tile / _row_chunk.
+#define CS_HEADFIT_ROW_TILE 64    // rows of one workgroup of head_grad_z / head_da
+#define CS_HEADFIT_ROW_CHUNK 512  // rows of one fp32 partial of gemm_tn
+#define CS_HEADFIT_NPAD 224       // columns of g: 196 padded to whole 32-deep k steps
+struct CsHeadGradZ {
+  const h16_t* A; int lda;      // [M][lda] hidden rows, M = B gh gw
+  const h16_t* Wb; int ldw;     // [P*P][ldw] the head's second linear (nn.Linear layout)
+  const float* bb;              // [P*P]
+  const float* gt;              // [B][gh P][gw P] fp32
+  int B, gh, gw, P, C, act; float powp;
+  h16_t* g; int ldg;            // [M][ldg], ldg >= CS_HEADFIT_NPAD: 224 columns are written, the last 28 as zeros
+  double* loss; double loss_scale; int loss_accumulate;  // *loss = (accumulate ? *loss : 0) + scale * sum |s - gt|
+  float* colsum_part;           // [row tiles][CS_HEADFIT_NPAD] per-workgroup column sums of the rounded g, or null
+  float* s_tap;                 // [M][P*P] fp32 s as the kernel formed it (cs_debug_op_head_grad_z_tap), or null
+};
+struct CsGemmTn {
+  const h16_t* G; int ldg;      // [M][ldg], N columns used
+  const h16_t* X; int ldx;      // [M][ldx], K columns used
+  int M, N, K; float scale; int accumulate;
+  float* out; int ldo;          // [N][ldo] fp32
+  float* colsum;                // [N] scale * column sums of G by the same rule, or null
+};
+struct CsHeadBackward {
+  const h16_t* X; int ldx; const h16_t* A; int lda; const h16_t* Wb; int ldw; const float* bb; const float* gt;
+  int B, gh, gw, P, C, act; float powp; double inv_count; int accumulate;
+  float *dWa, *dba, *dWb, *dbb; double* loss;
+};
+
 // ---- The launch surface between the kernel files and the host files (api.hip, forward.hip, ops.hip): every cs_*_launch / cs_*_check /
 // cs_*_supported / size helper that one .hip defines and another calls, declared ONCE.  Every defining file includes this header, so a changed
 // parameter list fails to compile there instead of linking (most of these are extern "C") and misbehaving at run time. ----
@@ -409,4 +437,14 @@ hipError_t cs_scorepool_launch(const void* map, int is_f32, int B, int H, int W,
                                void* scratch, hipStream_t st);
 // sheet.hip
 hipError_t cs_sheet_launch(const CsSheetPanels* panels, int n, uint8_t* canvas, int ch, int cw, hipStream_t st);
+// headfit.hip (workspaces: 256-byte aligned device memory of the size the matching helper reports)
+int cs_headfit_supported(int C, int P);
+size_t cs_head_grad_z_workspace(int M);
+size_t cs_gemm_tn_workspace(int M, int N, int K);
+size_t cs_head_backward_workspace(int M, int C);
+hipError_t cs_head_grad_z_launch(const CsHeadGradZ* p, void* ws, int bf, hipStream_t st);
+hipError_t cs_gemm_tn_launch(const CsGemmTn* p, void* ws, int bf, hipStream_t st);
+hipError_t cs_head_backward_launch(const CsHeadBackward* p, void* ws, int bf, hipStream_t st);
+hipError_t cs_adamw_launch(float* p, float* m, float* v, const float* g, long long n, float lr, float beta1, float beta2, float eps, float wd,
+                           int step, h16_t* p16, int bf, hipStream_t st);
 }

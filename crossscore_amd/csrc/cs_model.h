@@ -123,6 +123,10 @@ struct cs_model {
     bool any() const { return share || peak_prob || peak_index || entropy; }
   };
   RefUse ref_use;
+  // head fit (cs_head_backward): what the last forward-class call left behind, and the backward's own workspace
+  struct LastForward { bool ok = false; int mode = -1, B = 0, H = 0, W = 0; const float* xq = nullptr; const h16_t* dhid = nullptr; };
+  LastForward last_fwd;
+  void* hfit_ws = nullptr; size_t hfit_ws_bytes = 0;  // X in 16 bits (M, C), then cs_head_backward_workspace
   unsigned* nonfinite = nullptr;  // device counter: non-finite score-map values seen since the last cs_nonfinite_count
   // profiling
   bool prof = false;
@@ -189,6 +193,9 @@ inline void fill_triples(const int32_t* query_group, int B, const int32_t* offse
 }
 
 inline bool supported_dh(int dh) { return dh == 16 || dh == 48 || dh == 64 || dh == 96 || dh == 128 || dh == 192; }
+
+// ops.hip: the checks of a head backward, then its launches
+int head_backward_run(const char* op, const CsHeadBackward& q, void* ws, int bf, hipStream_t st);
 
 // forward.hip
 void reap_retired(cs_model* m, bool all);                        // frees retired workspaces whose last use has completed (never blocks unless `all`)

@@ -847,6 +847,8 @@ int forward_impl(Fwd f) {
   if (f.u8) cs_preprocess_tables_hold(1);  // (the filter tables its descriptors point at stay put until everything is queued: preprocess.hip)
   const int rc = f.body();
   if (f.u8) cs_preprocess_tables_hold(0);
+  // what cs_head_backward works on: the tokens behind the last norm3 and the head's hidden rows of THIS call (f.p: the plan body() carved)
+  h->last_fwd = cs_model::LastForward{rc == 0, f.mode, f.B, f.H, f.W, f.p.xq, f.p.dhid};
   h->host_enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
   HIPCHK(hipEventRecord(h->ev_done, f.st));
@@ -942,6 +944,86 @@ int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const ui
   const U8In u{query, nullptr, mean3, std3};
   const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out, offsets, G, query_group, blank_row};
   return forward_select(h, nullptr, &u, bank_tokens, s, B, N, H, W, score_out, attn_out, head_id, mean_out, stream);
+}
+
+// ---- head fit: the backward of the head over what the last forward left in the workspace ----
+// The closing launch of the decoder writes the normalised rows in fp32 (p.xq) and, where the head's first linear rides along (rowln.hip), no
+// 16-bit copy: X is rounded here from p.xq, the rounding the forward's own operand went through.  The workspace of the backward is the
+// handle's own allocation (X, then cs_head_backward_workspace), grown like the forward's.
+static int head_fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, const char* op, int* M_out, h16_t** X_out) {
+  if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
+  if (!h->finalized) return fail(CS_ERR_STATE, "%s before cs_finalize", op);
+  const cs_model::LastForward& lf = h->last_fwd;
+  if (!lf.ok || lf.mode < 0) return fail(CS_ERR_STATE, "%s: no successful cs_forward* call on this handle yet", op);
+  if (lf.mode == 2) return fail(CS_ERR_STATE, "%s: the last call on this handle only encoded references", op);
+  if (B > 0 && (lf.B != B || lf.H != H || lf.W != W))
+    return fail(CS_ERR_STATE, "%s: the last forward ran (B %d, H %d, W %d), this call names (%d, %d, %d)", op, lf.B, lf.H, lf.W, B, H, W);
+  const cs_config& c = h->cfg;
+  if (!cs_headfit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden a multiple of 64 and patch 14 (hidden %d, patch %d)", op, c.hidden, c.patch);
+  const int M = lf.B * (lf.H / c.patch) * (lf.W / c.patch), C = c.hidden;
+  const size_t xbytes = ((size_t)M * C * 2 + 255) & ~size_t(255), need = xbytes + cs_head_backward_workspace(M, C);
+  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
+  if (need > h->hfit_ws_bytes) {
+    if (h->hfit_ws) {
+      cs_model::Retired r{h->hfit_ws, nullptr};
+      HIPCHK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+      HIPCHK(hipEventRecord(r.ev, st));
+      h->retired.push_back(r);
+    }
+    h->hfit_ws = nullptr; h->hfit_ws_bytes = 0;
+    HIPCHK(hipMalloc(&h->hfit_ws, need));
+    h->hfit_ws_bytes = need;
+  }
+  h16_t* X = static_cast<h16_t*>(h->hfit_ws);
+  HIPCHK(cs_pack_f16_launch(lf.xq, M, C, X, C, nullptr, nullptr, c.operand_dtype, st));
+  *M_out = M; *X_out = X;
+  return 0;
+}
+
+static int head_fit_done(cs_model* h, hipStream_t st) {
+  if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(h->ev_done, st));
+  h->last_stream = st;
+  return 0;
+}
+
+int cs_head_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWa, float* dba, float* dWb,
+                     float* dbb, double* loss, cs_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (B <= 0) return fail(CS_ERR_BAD_ARG, "cs_head_backward: empty batch");
+  if (!gt || !dWa || !dba || !dWb || !dbb || !loss) return fail(CS_ERR_BAD_ARG, "cs_head_backward: null pointer");
+  // everything the caller can get wrong is refused here, before head_fit_inputs allocates or queues the rounding of X (head_backward_run checks
+  // again, with the handle's own operands)
+  if ((((uintptr_t)gt | (uintptr_t)dWa | (uintptr_t)dba | (uintptr_t)dWb | (uintptr_t)dbb) & 3) || ((uintptr_t)loss & 7))
+    return fail(CS_ERR_BAD_ARG, "cs_head_backward: misaligned pointer (fp32 4 bytes, the loss 8)");
+  if (!(inv_count > 0.0)) return fail(CS_ERR_BAD_ARG, "cs_head_backward: inv_count must be positive");
+  if (h && h->cfg.act == 1 && h->cfg.pow_p != 1.0f) return fail(CS_ERR_UNSUPPORTED, "cs_head_backward: tanh with a power factor other than 1 is not built");
+  int M = 0; h16_t* X = nullptr;
+  if (int r = head_fit_inputs(h, B, H, W, st, "cs_head_backward", &M, &X)) return r;
+  const cs_config& c = h->cfg;
+  const int C = c.hidden;
+  CsHeadBackward q{};
+  q.X = X; q.ldx = C; q.A = h->last_fwd.dhid; q.lda = C; q.Wb = h->Wh2; q.ldw = C; q.bb = h->bh2; q.gt = gt; q.B = B; q.gh = H / c.patch; q.gw = W / c.patch;
+  q.P = c.patch; q.C = C; q.act = c.act; q.powp = c.pow_p; q.inv_count = inv_count; q.accumulate = accumulate != 0;
+  q.dWa = dWa; q.dba = dba; q.dWb = dWb; q.dbb = dbb; q.loss = loss;
+  char* ws = static_cast<char*>(h->hfit_ws) + (((size_t)M * C * 2 + 255) & ~size_t(255));
+  const int rc = head_backward_run("cs_head_backward", q, ws, c.operand_dtype, st);
+  if (int r = head_fit_done(h, st)) return r;
+  return rc;
+}
+
+int cs_debug_head_inputs(cs_handle h, uint16_t* X_out, uint16_t* A_out, int rows, cs_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  int M = 0; h16_t* X = nullptr;
+  if (h && h->finalized && h->last_fwd.ok && h->last_fwd.mode != 2 &&
+      rows != h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch))
+    return fail(CS_ERR_BAD_ARG, "cs_debug_head_inputs: the last forward left %d rows, the caller names %d",
+                h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch), rows);
+  if (int r = head_fit_inputs(h, 0, 0, 0, st, "cs_debug_head_inputs", &M, &X)) return r;
+  const size_t bytes = (size_t)M * h->cfg.hidden * 2;
+  if (X_out) HIPCHK(hipMemcpyAsync(X_out, X, bytes, hipMemcpyDeviceToDevice, st));
+  if (A_out) HIPCHK(hipMemcpyAsync(A_out, h->last_fwd.dhid, bytes, hipMemcpyDeviceToDevice, st));
+  return head_fit_done(h, st);
 }
 
 int cs_u8_input_supported(cs_handle h, const cs_u8_image* im, int H, int W) {

@@ -716,4 +716,118 @@ int cs_op_select_references_grouped(const float* q_mean, int B, const int32_t* q
   return stage_done(sl, st);
 }
 
+// ---- head fit (headfit.hip): checks first, then the launches ----
+int cs_head_fit_supported(int hidden, int patch) { return cs_headfit_supported(hidden, patch); }
+int cs_head_fit_row_tile(void) { return CS_HEADFIT_ROW_TILE; }
+int cs_head_fit_row_chunk(void) { return CS_HEADFIT_ROW_CHUNK; }
+int cs_head_fit_g_columns(void) { return CS_HEADFIT_NPAD; }
+
+size_t cs_head_backward_workspace_bytes(int M, int C, int P) {
+  if (M <= 0 || !cs_headfit_supported(C, P)) return 0;
+  return cs_head_backward_workspace(M, C);
+}
+
+size_t cs_gemm_tn_workspace_bytes(int M, int N, int K) {
+  if (M <= 0 || N <= 0 || K <= 0) return 0;
+  return cs_gemm_tn_workspace(M, N, K);
+}
+
+static bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+
+// what every head-fit entry asks of the head's shape and of the 16-bit operands A (M, C) and Wb (P P, C)
+static int head_fit_shape_check(const char* op, const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B,
+                                int gh, int gw, int P, int C, int act, float powp, const void* ws) {
+  if (!A || !Wb || !bb || !gt || !ws) return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
+  if (B <= 0 || gh <= 0 || gw <= 0) return fail(CS_ERR_BAD_ARG, "%s: empty batch or patch grid", op);
+  if (!cs_headfit_supported(C, P)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden a multiple of 64 in [64, 4096] and patch 14 (hidden %d, patch %d)", op, C, P);
+  if (act != 0 && act != 1) return fail(CS_ERR_BAD_ARG, "%s: act must be 0 (sigmoid) or 1 (tanh)", op);
+  if (!(powp > 0.f)) return fail(CS_ERR_BAD_ARG, "%s: power factor must be positive", op);
+  // (the reference forces p = 1 with tanh, regression_layer.py:48-56: a power of a negative base has no gradient worth defining)
+  if (act == 1 && powp != 1.0f) return fail(CS_ERR_UNSUPPORTED, "%s: tanh with a power factor other than 1 is not built", op);
+  if ((long long)B * gh * gw > (1ll << 22)) return fail(CS_ERR_UNSUPPORTED, "%s: more than 2^22 token rows; split the batch", op);
+  if (lda < C || ldw < C || lda % 8 || ldw % 8) return fail(CS_ERR_BAD_ARG, "%s: row strides must be multiples of 8 elements and at least C", op);
+  if (misaligned(A, 16) || misaligned(Wb, 16) || misaligned(bb, 4) || misaligned(gt, 4) || misaligned(ws, 256))
+    return fail(CS_ERR_BAD_ARG, "%s: misaligned pointer (16-bit operands 16 bytes, fp32 4, workspace 256)", op);
+  return 0;
+}
+
+static int head_grad_z_op(const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P, int C,
+                          int act, float powp, uint16_t* g, int ldg, double* loss_sum, float* colsum_part, float* s_tap, void* ws, cs_stream stream) {
+  if (int r = head_fit_shape_check("head_grad_z", A, lda, Wb, ldw, bb, gt, B, gh, gw, P, C, act, powp, ws)) return r;
+  if (!g || !loss_sum) return fail(CS_ERR_BAD_ARG, "head_grad_z: null pointer");
+  if (ldg < CS_HEADFIT_NPAD || ldg % 8 || misaligned(g, 16) || misaligned(loss_sum, 8) || misaligned(colsum_part, 4))
+    return fail(CS_ERR_BAD_ARG, "head_grad_z: g needs rows of at least %d elements, a multiple of 8 apart, 16-byte aligned; the loss 8-byte aligned", CS_HEADFIT_NPAD);
+  CsHeadGradZ z{};
+  z.A = A; z.lda = lda; z.Wb = Wb; z.ldw = ldw; z.bb = bb; z.gt = gt; z.B = B; z.gh = gh; z.gw = gw; z.P = P; z.C = C; z.act = act; z.powp = powp;
+  z.g = g; z.ldg = ldg; z.loss = loss_sum; z.loss_scale = 1.0; z.loss_accumulate = 1; z.colsum_part = colsum_part; z.s_tap = s_tap;
+  HIPCHK(cs_head_grad_z_launch(&z, ws, g_op_bf16, (hipStream_t)stream));
+  return 0;
+}
+
+int cs_op_head_grad_z(const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P, int C,
+                      int act, float powp, uint16_t* g, int ldg, double* loss_sum, float* colsum_part, void* ws, cs_stream stream) {
+  return head_grad_z_op(A, lda, Wb, ldw, bb, gt, B, gh, gw, P, C, act, powp, g, ldg, loss_sum, colsum_part, nullptr, ws, stream);
+}
+
+// tests: the same call with s (M, P P) fp32 as the epilogue formed it
+int cs_debug_op_head_grad_z_tap(const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P,
+                                int C, int act, float powp, uint16_t* g, int ldg, double* loss_sum, float* colsum_part, float* s_out, void* ws,
+                                cs_stream stream) {
+  if (!s_out || misaligned(s_out, 4)) return fail(CS_ERR_BAD_ARG, "head_grad_z tap: s_out missing or misaligned");
+  return head_grad_z_op(A, lda, Wb, ldw, bb, gt, B, gh, gw, P, C, act, powp, g, ldg, loss_sum, colsum_part, s_out, ws, stream);
+}
+
+int cs_op_gemm_tn(const uint16_t* G, int ldg, const uint16_t* X, int ldx, int M, int N, int K, float scale, int accumulate, float* out, int ldo,
+                  float* colsum, void* ws, cs_stream stream) {
+  if (!G || !X || !out || !ws) return fail(CS_ERR_BAD_ARG, "gemm_tn: null pointer");
+  if (M <= 0 || N <= 0 || K <= 0) return fail(CS_ERR_BAD_ARG, "gemm_tn: empty shape");
+  if (K % 8 || N > 65535 * 64 || (long long)M > (1ll << 22) || (long long)N * K >= (1ll << 31))
+    return fail(CS_ERR_UNSUPPORTED, "gemm_tn: K must be a multiple of 8, M <= 2^22, N K < 2^31 (M %d, N %d, K %d)", M, N, K);
+  if (ldg < N || ldx < K || ldo < K || ldg % 8 || ldx % 8) return fail(CS_ERR_BAD_ARG, "gemm_tn: row strides must cover the rows; those of G and X must be multiples of 8 elements");
+  if (misaligned(G, 16) || misaligned(X, 16) || misaligned(out, 4) || misaligned(colsum, 4) || misaligned(ws, 256))
+    return fail(CS_ERR_BAD_ARG, "gemm_tn: misaligned pointer (16-bit operands 16 bytes, fp32 4, workspace 256)");
+  CsGemmTn t{};
+  t.G = G; t.ldg = ldg; t.X = X; t.ldx = ldx; t.M = M; t.N = N; t.K = K; t.scale = scale; t.accumulate = accumulate != 0; t.out = out; t.ldo = ldo;
+  t.colsum = colsum;
+  HIPCHK(cs_gemm_tn_launch(&t, ws, g_op_bf16, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"
+
+// cs_op_head_backward and cs_head_backward (forward.hip) come through here
+int cs_host::head_backward_run(const char* op, const CsHeadBackward& q, void* ws, int bf, hipStream_t st) {
+  if (int r = head_fit_shape_check(op, q.A, q.lda, q.Wb, q.ldw, q.bb, q.gt, q.B, q.gh, q.gw, q.P, q.C, q.act, q.powp, ws)) return r;
+  if (!q.X || !q.dWa || !q.dba || !q.dWb || !q.dbb || !q.loss) return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
+  if (q.ldx < q.C || q.ldx % 8 || misaligned(q.X, 16)) return fail(CS_ERR_BAD_ARG, "%s: X needs 16-byte aligned rows a multiple of 8 elements apart", op);
+  if (misaligned(q.dWa, 4) || misaligned(q.dba, 4) || misaligned(q.dWb, 4) || misaligned(q.dbb, 4) || misaligned(q.loss, 8))
+    return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
+  if (!(q.inv_count > 0.0)) return fail(CS_ERR_BAD_ARG, "%s: inv_count must be positive", op);
+  HIPCHK(cs_head_backward_launch(&q, ws, bf, st));
+  return 0;
+}
+
+extern "C" {
+
+int cs_op_head_backward(const uint16_t* X, int ldx, const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B,
+                        int gh, int gw, int P, int C, int act, float powp, double inv_count, int accumulate, float* dWa, float* dba, float* dWb,
+                        float* dbb, double* loss, void* ws, cs_stream stream) {
+  CsHeadBackward q{};
+  q.X = X; q.ldx = ldx; q.A = A; q.lda = lda; q.Wb = Wb; q.ldw = ldw; q.bb = bb; q.gt = gt; q.B = B; q.gh = gh; q.gw = gw; q.P = P; q.C = C;
+  q.act = act; q.powp = powp; q.inv_count = inv_count; q.accumulate = accumulate != 0; q.dWa = dWa; q.dba = dba; q.dWb = dWb; q.dbb = dbb; q.loss = loss;
+  return head_backward_run("head_backward", q, ws, g_op_bf16, (hipStream_t)stream);
+}
+
+int cs_op_adamw(float* p, float* m, float* v, const float* g, long long n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                int step, uint16_t* p16, cs_stream stream) {
+  if (!p || !m || !v || !g) return fail(CS_ERR_BAD_ARG, "adamw: null pointer");
+  if (n <= 0 || n > (1ll << 38)) return fail(CS_ERR_BAD_ARG, "adamw: n must be in [1, 2^38]");
+  if (step < 1) return fail(CS_ERR_BAD_ARG, "adamw: steps count from 1");
+  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) || !(weight_decay >= 0.f))
+    return fail(CS_ERR_BAD_ARG, "adamw: lr, eps, weight_decay must be >= 0 and the betas in [0, 1)");
+  if (misaligned(p, 4) || misaligned(m, 4) || misaligned(v, 4) || misaligned(g, 4) || misaligned(p16, 2)) return fail(CS_ERR_BAD_ARG, "adamw: misaligned pointer");
+  HIPCHK(cs_adamw_launch(p, m, v, g, n, lr, beta1, beta2, eps, weight_decay, step, p16, g_op_bf16, (hipStream_t)stream));
+  return 0;
+}
+
 }  // extern "C"

@@ -220,6 +220,7 @@ class CrossScoreNet(torch.nn.Module):
         self.operand_dtype = str(cfg.model.backbone.get("operand_dtype", "fp16"))
         self._capture = False      # debug taps (debug_capture / debug_read): stage-level parity tests only
         self.finite_check = True   # every forward counts the non-finite values of its score map on the device (~3 us)
+        self._after_sub_batch = None  # fit_head_step's hook behind each sub-batch's forward call (_score)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._mark_dirty())
 
     # -- weights ----------------------------------------------------------------------------------------------
@@ -350,6 +351,8 @@ class CrossScoreNet(torch.nn.Module):
                 _lib.check(call(b0, b1, (C.c_void_p(score[b0:b1].data_ptr()), C.c_void_p(attn[b0:b1].data_ptr()) if attn is not None else None,
                                          int(head_id), C.c_void_p(mean_out[b0:b1].data_ptr()) if mean_out is not None else None,
                                          C.c_void_p(stream))))
+                if self._after_sub_batch is not None:
+                    self._after_sub_batch(b0, b1)  # fit_head_step: the head's backward over what this sub-batch's forward left behind
         results = self._results(score, attn, mean_out)
         if use is not None:
             results.update(use)
@@ -684,6 +687,100 @@ class CrossScoreNet(torch.nn.Module):
                 break
         return {"one_lane_s": one, "lanes_s": seen}
 
+    # -- fitting the regression head ---------------------------------------------------------------
+    HEAD_KEYS = ("ref_cross.head.0.weight", "ref_cross.head.0.bias", "ref_cross.head.2.weight", "ref_cross.head.2.bias")
+
+    def head_parameters(self):
+        """The four tensors of the regression head, the one trainable unit of this build: head.0 weight (C, C) and bias (C), head.2 weight
+        (P P, C) and bias (P P)."""
+        if not self._do_reference_cross:
+            raise ValueError("model.do_reference_cross=False: this module has no regression head")
+        return [self.get_parameter(k) for k in self.HEAD_KEYS]
+
+    def head_fit_supported(self) -> bool:
+        return bool(_lib.load().cs_head_fit_supported(self.arch.hidden, self.arch.patch))
+
+    def head_inputs(self, rows: int):
+        """(X, A): the 16-bit tokens behind the last norm3 and the head's hidden rows of the last forward call, (rows, C) each; rows = its
+        B h w, checked by the library (tests)."""
+        if self._handle is None:
+            raise _lib.CrossScoreHipError("head_inputs before any forward")
+        dev = self._handle_device
+        with torch.cuda.device(dev):
+            X = torch.empty((int(rows), self.arch.hidden), dtype=self.token_dtype, device=dev)
+            A = torch.empty_like(X)
+            _lib.check(_lib.load().cs_debug_head_inputs(self._handle, C.c_void_p(X.data_ptr()), C.c_void_p(A.data_ptr()), int(rows),
+                                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return X, A
+
+    def head_backward(self, gt, inv_count=None, accumulate=False, out=None):
+        """cs_head_backward over the LAST forward call of this module (its last sub-batch): gt (B, h P, w P) fp32 on the device ->
+        (dWa, dba, dWb, dbb, loss): fp32 gradients and the fp64 device scalar loss, each scaled by inv_count (default 1 / gt.numel())."""
+        if self._handle is None:
+            raise _lib.CrossScoreHipError("head_backward before any forward")
+        dev = self._handle_device
+        if gt.dim() != 3 or gt.dtype != torch.float32 or gt.device != dev or not gt.is_contiguous():
+            raise ValueError("expected a contiguous fp32 gt (B, H, W) on the module's device")
+        B, H, W = gt.shape
+        Cc, PP = self.arch.hidden, self.arch.patch ** 2
+        if out is None:
+            out = (torch.zeros((Cc, Cc), device=dev), torch.zeros((Cc,), device=dev), torch.zeros((PP, Cc), device=dev),
+                   torch.zeros((PP,), device=dev), torch.zeros((), dtype=torch.float64, device=dev))
+        inv = 1.0 / gt.numel() if inv_count is None else float(inv_count)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().cs_head_backward(self._handle, C.c_void_p(gt.data_ptr()), B, H, W, inv, int(bool(accumulate)),
+                                                    *(C.c_void_p(t.data_ptr()) for t in out),
+                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
+    def fit_head_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
+        """One AdamW step of the regression head on one batch: the forward through the existing path (forward for tensors, forward_u8 for
+        U8Batch inputs, the cached forms with ref_tokens), cs_head_backward behind each sub-batch, cs_op_adamw on the four parameters in place,
+        cs_set_head_weights.  The module is not marked dirty: the handle keeps every other packed weight.  gt: (B, h P, w P) fp32 on the
+        device, the score map's shape.  Returns the loss of the batch BEFORE the step as a device fp64 scalar; nothing is waited for."""
+        if (refs is None) == (ref_tokens is None):
+            raise ValueError("fit_head_step takes the references either as images (refs) or as cached tokens (ref_tokens)")
+        if not self.head_fit_supported():
+            raise ValueError(f"head fit is built for hidden a multiple of 64 and patch 14 (hidden {self.arch.hidden}, patch {self.arch.patch})")
+        params = self.head_parameters()
+        dev = gt.device
+        for p in params:
+            if not p.is_cuda or p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("fit_head_step needs the module's fp32 parameters on the device of the batch (net.to(device))")
+        if gt.dim() != 3 or gt.dtype != torch.float32 or not gt.is_contiguous():
+            raise ValueError("expected a contiguous fp32 gt (B, h P, w P)")
+        state.prepare(params)
+        lib = _lib.load()
+        inv = 1.0 / gt.numel()
+        grads, loss = state.grads, torch.zeros((), dtype=torch.float64, device=dev)
+        H, W = gt.shape[1:]
+
+        def backward(b0, b1):
+            _lib.check(lib.cs_head_backward(self._handle, C.c_void_p(gt[b0:b1].data_ptr()), b1 - b0, H, W, inv, int(b0 > 0),
+                                            *(C.c_void_p(g.data_ptr()) for g in grads), C.c_void_p(loss.data_ptr()),
+                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+        u8 = isinstance(query, U8Batch)
+        self._after_sub_batch = backward
+        try:
+            if ref_tokens is not None:
+                res = self.forward_cached_u8(query, ref_tokens) if u8 else self.forward_cached(query, ref_tokens)
+            else:
+                res = self.forward_u8(query, refs) if u8 else self.forward(query, refs)
+        finally:
+            self._after_sub_batch = None
+        if tuple(res["score_map_ref_cross"].shape) != tuple(gt.shape):
+            raise ValueError(f"gt {tuple(gt.shape)} does not have the score map's shape {tuple(res['score_map_ref_cross'].shape)}")
+        state.step += 1
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            for p, m, v, g in zip(params, state.m, state.v, grads):
+                _lib.check(lib.cs_op_adamw(C.c_void_p(p.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(g.data_ptr()),
+                                           p.numel(), state.lr, state.betas[0], state.betas[1], state.eps, state.weight_decay, state.step, None,
+                                           stream))
+            _lib.check(lib.cs_set_head_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params), stream))
+        return loss
+
     # -- debug taps used by the stage-level parity tests (tests/test_hip_stages.py) ------------------------------------
     def debug_capture(self, on: bool = True) -> None:
         """Following forwards also keep their intermediate tensors (cs_debug_capture): not for timed runs."""
@@ -728,3 +825,26 @@ def load_lightning_checkpoint(path: str) -> Dict[str, torch.Tensor]:
     ckpt = torch.load(path, map_location="cpu", weights_only=False)
     sd = ckpt["state_dict"] if "state_dict" in ckpt else ckpt
     return {k[len("model."):]: v for k, v in sd.items() if k.startswith("model.")} or dict(sd)
+
+
+class HeadFitState:
+    """What fit_head_step keeps between steps: AdamW's moments of the four head parameters, the step count (from 1 at the first step), the
+    learning rate (the driver's StepLR writes it) and the gradient buffers.  Defaults are torch.optim.AdamW's."""
+
+    def __init__(self, lr: float = 5e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2):
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.step = 0
+        self.m = self.v = self.grads = None
+
+    def prepare(self, params) -> None:
+        if self.m is None or any(m.device != p.device for m, p in zip(self.m, params)):
+            self.m = [torch.zeros_like(p, requires_grad=False) for p in params]
+            self.v = [torch.zeros_like(p, requires_grad=False) for p in params]
+            self.grads = [torch.zeros_like(p, requires_grad=False) for p in params]
+
+
+def save_lightning_checkpoint(path: str, net: CrossScoreNet) -> None:
+    """The module's state dict in the layout load_lightning_checkpoint (and the reference's Lightning module) reads: {"state_dict":
+    {"model." + key: tensor}}, tensors on the CPU.  Optimiser state is not written."""
+    sd = {"model." + k: v.detach().to("cpu").clone() for k, v in net.state_dict().items()}
+    torch.save({"state_dict": sd}, path)

@@ -145,6 +145,11 @@ class NvsItems:
     def __len__(self) -> int:
         return len(self._index)
 
+    def ground_truth_files(self):
+        """(query path, ground-truth map path or "empty_image") of every item, in item order, without building the items: no reference is
+        sampled, so the seeded generator is left as it is."""
+        return [(entry[0], entry[1]) for entry in self._index]
+
     def __getitem__(self, idx: int) -> Dict[str, object]:
         query, score_map, cross = self._index[idx][:3]
         if self.candidates:  # no RNG is drawn

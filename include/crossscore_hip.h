@@ -684,6 +684,58 @@ void cs_debug_rowln_enable(int on);
 /* number of column tiles the GEMM launcher uses for N output columns (LayerNorm partial-sum slots per row = 4 x this) */
 int cs_gemm_column_tiles(int N);
 
+/* ---- Fitting the regression head on the device (csrc/headfit.hip) ----
+ * The head is ref_cross.head.{0,2}: Linear(C, C) "a" -> LeakyReLU(0.01) -> Linear(C, P P) "b" -> sigmoid | tanh -> pow -> jigsaw.  X (M, C) are
+ * the 16-bit tokens behind the last norm3, A (M, C) the 16-bit hidden rows, M = B gh gw.  Loss = inv_count * sum |s - gt|; the gradient g of
+ * the sum with respect to z = A Wb^T + bb is rounded once to the operand type, dpre = (g Wb) * (A > 0 ? 1 : 0.01) once more; the four
+ * gradients are fp32 and carry the factor inv_count, applied in fp32 behind each reduction (no loss scaling is needed).  Every sum over rows has
+ * a fixed order and there are no atomics: two runs give the same bits.  Operand type of the cs_op_* forms: cs_debug_set_op_operand_dtype.
+ * Every entry rejects null or misaligned pointers (16-bit operands: 16 bytes, row strides multiples of 8 elements; fp32: 4 bytes; the loss: 8)
+ * and unsupported shapes before any launch; workspaces are device memory, 256-byte aligned. */
+/* widths the kernels take: hidden a multiple of 64 in [64, 4096] (every width the forward's head GEMM takes), patch 14 */
+int cs_head_fit_supported(int hidden, int patch);
+/* tile sizes the tests place their edge cases by: rows per workgroup of cs_op_head_grad_z, rows per fp32 partial of cs_op_gemm_tn, and the columns
+ * of g (P P = 196 padded to whole 32-deep k steps) */
+int cs_head_fit_row_tile(void);
+int cs_head_fit_row_chunk(void);
+int cs_head_fit_g_columns(void);
+/* bytes of `ws` for cs_op_head_backward (and for cs_op_head_grad_z with the same M) */
+size_t cs_head_backward_workspace_bytes(int M, int C, int P);
+/* bytes of `ws` for cs_op_gemm_tn */
+size_t cs_gemm_tn_workspace_bytes(int M, int N, int K);
+/* g (M, ldg >= cs_head_fit_g_columns()) = sign(s - gt) ds/dz with zeros in columns 196 .. 223; *loss_sum += sum |s - gt| (fp32 terms, summed in
+ * fp64); colsum_part (may be NULL): (ceil(M / row tile), cs_head_fit_g_columns()) per-workgroup column sums of the rounded g.  act 0 sigmoid, 1 tanh
+ * (tanh with powp != 1 is CS_ERR_UNSUPPORTED in every head-fit entry: the reference forces p = 1 there). */
+int cs_op_head_grad_z(const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P, int C,
+                      int act, float powp, uint16_t* g, int ldg, double* loss_sum, float* colsum_part, void* ws, cs_stream stream);
+/* debug (tests): cs_op_head_grad_z that also stores s (M, P P) fp32 as its epilogue formed it into s_out (required); per call, no state */
+int cs_debug_op_head_grad_z_tap(const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P,
+                                int C, int act, float powp, uint16_t* g, int ldg, double* loss_sum, float* colsum_part, float* s_out, void* ws,
+                                cs_stream stream);
+/* out (N, K; rows ldo apart) = (accumulate ? out : 0) + scale * sum_m G[m][n] X[m][k]; colsum (NULL or N) the same for sum_m G[m][n].  K a multiple of 8. */
+int cs_op_gemm_tn(const uint16_t* G, int ldg, const uint16_t* X, int ldx, int M, int N, int K, float scale, int accumulate, float* out, int ldo,
+                  float* colsum, void* ws, cs_stream stream);
+/* the whole backward: dWa (C, C), dba (C), dWb (P P, C), dbb (P P), *loss (device), each = (accumulate ? itself : 0) + inv_count * its sum */
+int cs_op_head_backward(const uint16_t* X, int ldx, const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B,
+                        int gh, int gw, int P, int C, int act, float powp, double inv_count, int accumulate, float* dWa, float* dba, float* dWb,
+                        float* dbb, double* loss, void* ws, cs_stream stream);
+/* The same on the tokens and hidden rows the LAST cs_forward* call on this handle left in its workspace, with the handle's packed Wb, bias,
+ * activation and power; gt (B, H, W) fp32.  CS_ERR_STATE if no forward ran, if it failed, if its (B, H, W) differ or if it only encoded
+ * references.  inv_count and accumulate let sub-batches add up to one batch gradient.  Allocates its own workspace on first use. */
+int cs_head_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWa, float* dba, float* dWb,
+                     float* dbb, double* loss, cs_stream stream);
+/* debug: copies of the tokens X and hidden rows A (rows, C; 16 bit, contiguous) cs_head_backward would read; either may be NULL.  rows must be
+ * the last forward's B Np (CS_ERR_BAD_ARG otherwise: nothing is copied). */
+int cs_debug_head_inputs(cs_handle h, uint16_t* X, uint16_t* A, int rows, cs_stream stream);
+/* torch.optim.AdamW's single-tensor step (amsgrad off) in place on fp32 p, m, v from g; step counts from 1; p16 (NULL or n): the updated
+ * parameter rounded once to the operand type, in the same pass */
+int cs_op_adamw(float* p, float* m, float* v, const float* g, long long n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                int step, uint16_t* p16, cs_stream stream);
+/* Re-packs fp32 device weights (w0 (C, C), b0 (C), w2 (P P, C), b2 (P P)) into the finalised handle's existing head buffers, in stream order
+ * behind the handle's last call; the handle is not rebuilt.  A forward queued on ANOTHER stream at the same time races with it: that is the
+ * caller's to order. */
+int cs_set_head_weights(cs_handle h, const float* w0, const float* b0, const float* w2, const float* b2, cs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
