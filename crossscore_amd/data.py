@@ -264,8 +264,8 @@ class InputStage:
 
     # -- the one-pass form (SURVEY.md 8f-4 as worded): nothing is computed here, the patch-embedding launch does the pixel work --------------
     def describe(self, img_u8):
-        """The decoded image on the device with its geometry (model.U8Image) for CrossScoreNet.forward_u8 and its siblings.  img_u8: a host
-        array or a CUDA uint8 tensor (no copy)."""
+        """The decoded image on the device with its geometry (model.U8Image), an entry of the model.U8Batch CrossScoreNet.forward and its
+        siblings take.  img_u8: a host array or a CUDA uint8 tensor (no copy)."""
         from .model import U8Image
         h, w, _ = (int(v) for v in img_u8.shape)
         rs, crop = self.geometry(h, w)
@@ -279,6 +279,22 @@ class InputStage:
     def batch(self, images, size):
         from .model import U8Batch
         return U8Batch(images, size, self.mean_std, device=self.device)
+
+    def model_input(self, images, size, u8: bool, out: Optional[torch.Tensor] = None, lead: Optional[Tuple[int, ...]] = None):
+        """Decoded images (host arrays or CUDA uint8 tensors; None = the all-zero placeholder, zeros BEFORE T.Normalize: nvs_dataset.py:459-470)
+        of the processed size -> the form the model's methods take them in: a model.U8Batch (u8, the one-pass input stage: nothing is computed
+        here), else the processed (len(images), 3, oh, ow) fp32 tensor, written into `out` when the caller keeps the images and returned as
+        (*lead, 3, oh, ow) when the images are a batch's views, item-major: lead = (B, N)."""
+        if u8:
+            return self.batch([self.placeholder(size) if im is None else self.describe(im) for im in images], size)
+        if out is None:
+            out = torch.empty((len(images), 3, size[0], size[1]), dtype=torch.float32, device=self.device)
+        for i, im in enumerate(images):
+            if im is None:
+                out[i] = self.zero_image_value[:, None, None]
+            else:
+                self(im, out[i])
+        return out if lead is None else out.view(*lead, 3, size[0], size[1])
 
 
 STRATEGIES = ("random", "similar")  # data.neighbour_config.strategy: the reference's sampler, and this build's choice by DINOv2 similarity
@@ -305,13 +321,18 @@ class SimpleReferenceItems:
         return {"query/img": self.query_paths[idx], "query/score_map": EMPTY, "reference/cross/imgs": refs}
 
 
-def decode_items(items: List[Dict[str, object]], zero_reference: bool = False, pool=None, skip=()) -> Dict[str, np.ndarray]:
-    """path -> decoded uint8 image for every file the items name (host side; PIL releases the GIL while decoding, so a thread pool
-    plays the role of the reference's DataLoader workers, task/predict.py:110-117).  Reference paths in `skip` (already in the
-    token cache) are not decoded."""
-    uniq = list(dict.fromkeys(p for p, _ in batch_files(items, zero_reference, skip=skip)))
-    imgs = list(pool.map(read_image_u8, uniq)) if pool is not None else [read_image_u8(p) for p in uniq]
-    return dict(zip(uniq, imgs))
+def decode_items(items: List[Dict[str, object]], zero_reference: bool = False, pool=None, skip=(), extra=None) -> Dict[str, np.ndarray]:
+    """path -> decoded image for every file batch_files lists for the items, each path read once (host side; PIL releases the GIL while
+    decoding, so a thread pool plays the role of the reference's DataLoader workers, task/predict.py:110-117): a uint8 image, or the 16-bit
+    map of a gray16 entry of extra(item).  Reference paths in `skip` (already in the token cache) are not decoded; extras always are."""
+    gray16: Dict[str, bool] = {}  # in reading order; a path listed twice is read as its first entry says
+    for path, flag in batch_files(items, zero_reference, extra, skip):
+        gray16.setdefault(path, flag)
+
+    def read(path):
+        return (read_metric_map_u16 if gray16[path] else read_image_u8)(path)
+
+    return dict(zip(gray16, pool.map(read, gray16) if pool is not None else map(read, gray16)))
 
 
 def item_paths(items: List[Dict[str, object]]) -> Dict[str, list]:
@@ -338,32 +359,21 @@ def load_batch(items: List[Dict[str, object]], stage: InputStage, decoded: Optio
                references: bool = True, zero_reference: bool = False):
     """(batch, processed size): one batch dict with the keys `_core_step` reads (task/core.py:265-272) plus `item_paths`.  `decoded` holds
     images already read by decode_items (a reference image shared by several items of the batch is decoded once).
-    u8: the one-pass input stage -- "query/img" and "reference/cross/imgs" are model.U8Batch objects (decoded images on the device + geometry) for
-    CrossScoreNet.forward_u8 and no processed fp32 tensor exists; else (B, 3, oh, ow) and (B, N, 3, oh, ow) fp32 tensors.
+    u8: the one-pass input stage -- "query/img" and "reference/cross/imgs" are model.U8Batch objects (decoded images on the device + geometry)
+    and no processed fp32 tensor exists; else (B, 3, oh, ow) and (B, N, 3, oh, ow) fp32 tensors.
     references=False: the references come from a ReferenceTokenCache and "reference/cross/imgs" is None."""
     decoded = decoded if decoded is not None else {}
     q_imgs = [decoded[it["query/img"]] if it["query/img"] in decoded else read_image_u8(it["query/img"]) for it in items]
     geo = {stage.geometry(*im.shape[:2])[1][2:] for im in q_imgs}
     if len(geo) != 1:
         raise ValueError(f"query images of one batch must share the processed size, got {sorted(geo)}")
-    size = oh, ow = next(iter(geo))
+    size = next(iter(geo))
     ref_lists = [it["reference/cross/imgs"] if references else () for it in items]
     # nvs_dataset.py:459-470: placeholders and zero_reference are all-zero images BEFORE T.Normalize -> (0 - mean) / std
     blank = lambda p: p == EMPTY or zero_reference  # noqa: E731
-    if u8:
-        refs = stage.batch([stage.placeholder(size) if blank(p) else stage.describe(_reference_image(p, decoded, stage, size))
-                            for ps in ref_lists for p in ps], size) if references else None
-        query = stage.batch([stage.describe(qi) for qi in q_imgs], size)
-    else:
-        query = torch.empty((len(items), 3, oh, ow), dtype=torch.float32, device=stage.device)
-        refs = torch.empty((len(items), len(ref_lists[0]), 3, oh, ow), dtype=torch.float32, device=stage.device) if references else None
-        for b, (ps, qi) in enumerate(zip(ref_lists, q_imgs)):
-            stage(qi, query[b])
-            for n, p in enumerate(ps):
-                if blank(p):
-                    refs[b, n] = stage.zero_image_value[:, None, None]
-                else:
-                    stage(_reference_image(p, decoded, stage, size), refs[b, n])
+    query = stage.model_input(q_imgs, size, u8)
+    refs = stage.model_input([None if blank(p) else _reference_image(p, decoded, stage, size) for ps in ref_lists for p in ps], size, u8,
+                             lead=(len(items), len(ref_lists[0]))) if references else None
     return {"query/img": query, "reference/cross/imgs": refs, "item_paths": item_paths(items)}, size
 
 
@@ -392,17 +402,8 @@ class ReferenceTokenCache:
                 self.images.clear()
                 missing = list(dict.fromkeys(k for ks in keys for k in ks))
             imgs = [None if k[0] == EMPTY else _reference_image(k[0], decoded, self.stage, (oh, ow)) for k in missing]
-            if self.from_u8:
-                tok = self.net.encode_references_u8(self.stage.batch(
-                    [self.stage.placeholder((oh, ow)) if im is None else self.stage.describe(im) for im in imgs], (oh, ow)))
-            else:
-                buf = torch.empty((len(missing), 3, oh, ow), dtype=torch.float32, device=self.stage.device)
-                for i, im in enumerate(imgs):
-                    if im is None:
-                        buf[i] = self.stage.zero_image_value[:, None, None]
-                    else:
-                        self.stage(im, buf[i])
-                tok = self.net.encode_references(buf)
+            buf = self.stage.model_input(imgs, (oh, ow), self.from_u8)
+            tok = self.net.encode_references(buf)
             for i, k in enumerate(missing):
                 self.tokens[k] = tok[i]
                 if self.keep_images:
@@ -424,7 +425,8 @@ class ReferenceBank:
     group only (CrossScoreNet.forward_select(group=...)); a file that several groups list is held once per group.
 
     decoder: the run's ImageDecoder (this_main.png_decoder / jpeg_decoder = gpu): a chunk's files are decoded on the device, `window` files per
-    call; else PIL on `pool`.  from_u8: the one-pass input stage (encode_references_u8; no processed image exists, so not with keep_images)."""
+    call; else PIL on `pool`.  from_u8: the one-pass input stage (a U8Batch goes to encode_references; no processed image exists, so not
+    with keep_images)."""
 
     def __init__(self, net, stage: InputStage, paths: Sequence[str], size: Tuple[int, int], n_references: int, keep_images: bool = False,
                  max_images: int = 4096, from_u8: bool = False, decoder: Optional[decode.ImageDecoder] = None, pool=None, chunk: int = 32, window: int = 64,
@@ -471,23 +473,12 @@ class ReferenceBank:
                     raise ValueError(f"{p}: processed size differs from the query's {oh}x{ow}" +
                                      (": one bank has one patch grid; this_main.crop_mode=dataset_default gives the images of every scene one size"
                                       if groups is not None else ""))
-            if from_u8:
-                tok = net.encode_references_u8(stage.batch([stage.describe(im) for im in imgs], (oh, ow)))
-            else:
-                buf = self.images[r0:r0 + len(part)] if keep_images else torch.empty((len(part), 3, oh, ow), dtype=torch.float32, device=stage.device)
-                for i, im in enumerate(imgs):
-                    stage(im, buf[i])
-                tok = net.encode_references(buf)
+            tok = net.encode_references(stage.model_input(imgs, size, from_u8, out=self.images[r0:r0 + len(part)] if keep_images else None))
             if tokens is None:
                 tokens = torch.empty((R,) + tuple(tok.shape[1:]), dtype=tok.dtype, device=tok.device)
             tokens[r0:r0 + len(part)] = tok
         if groups is not None:  # the placeholder's row: zeros BEFORE T.Normalize, as load_batch and ReferenceTokenCache feed "empty_image"
-            if from_u8:
-                tokens[R - 1] = net.encode_references_u8(stage.batch([stage.placeholder((oh, ow))], (oh, ow)))[0]
-            else:
-                buf = self.images[R - 1:] if keep_images else torch.empty((1, 3, oh, ow), dtype=torch.float32, device=stage.device)
-                buf[0] = stage.zero_image_value[:, None, None]
-                tokens[R - 1] = net.encode_references(buf)[0]
+            tokens[R - 1] = net.encode_references(stage.model_input([None], size, from_u8, out=self.images[R - 1:] if keep_images else None))[0]
             mean, centre, unit = net.reference_descriptors(tokens, self.offsets)
             self.bank = SelectionBank(tokens, mean, centre, unit, n_references, self.offsets, R - 1)
         else:

@@ -35,6 +35,7 @@ from __future__ import annotations
 
 import csv
 import ctypes as C
+import functools
 import os
 import sys
 from datetime import datetime
@@ -46,8 +47,8 @@ import torch
 
 from . import _lib, parallel, pooling, scoring
 from .config import load_config, this_main_choice
-from .data import EMPTY, InputStage, decode_items, metric_mode
-from .decode import read_image_u8, read_metric_map_u16
+from .data import EMPTY, metric_mode
+from .model import U8Batch
 from .nvs import NvsItems, random_order
 
 METRIC_KEYS = ("test/loss", "test/loss_cross", "test/corr_cross", "test/psnr_cross")
@@ -162,14 +163,18 @@ def write_batches_csv(out_dir: str, rows: Sequence[Dict[str, float]]) -> str:
     return path
 
 
-def decode_eval(items, zero_ref: bool, pool, skip=(), compute_gt: bool = False):
-    """decode_items plus the GT maps of the queries (None for "empty_image"); in compute mode the captured images ("query/gt") instead."""
+def gt_file(item, compute_gt: bool):
+    """The [(path, gray16)] of an item's ground truth beside its images (scoring.score's extra_files): the 16-bit metric map (none for
+    "empty_image"), in compute mode the captured image ("query/gt")."""
     if compute_gt:
-        futs = [pool.submit(read_image_u8, it["query/gt"]) for it in items]
-    else:
-        futs = [None if it["query/score_map"] == EMPTY else pool.submit(read_metric_map_u16, it["query/score_map"]) for it in items]
-    decoded = decode_items(items, zero_ref, pool, skip)  # (the maps decode beside the images, on the same workers)
-    return decoded, [None if f is None else f.result() for f in futs]
+        return [(item["query/gt"], False)]
+    return [] if item["query/score_map"] == EMPTY else [(item["query/score_map"], True)]
+
+
+def gt_inputs(decoded, items, compute_gt: bool) -> list:
+    """Per item what gt_file named, out of the batch's decoded files (host arrays, or the decode window's device tensors); None for "empty_image"."""
+    files = [gt_file(it, compute_gt) for it in items]
+    return [decoded[f[0][0]] if f else None for f in files]
 
 
 def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None,
@@ -192,11 +197,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     cfg.logger.test.out_dir = out_dir
     Path(out_dir).mkdir(parents=True, exist_ok=True)
 
-    if crop_mode not in (None, "integer_patches", "dataset_default"):
-        raise ValueError(f"crop_mode {crop_mode} not supported (task/test.py:75-91 knows null, integer_patches and dataset_default)")
-    stage = InputStage(device, resize_short_side=int(cfg.this_main.resize_short_side),
-                       crop_size=int(cfg.data.transforms.crop_size) if crop_mode == "dataset_default" else None,
-                       integer_patches=crop_mode == "integer_patches")
+    stage = scoring.nvs_input_stage(cfg, device)
     mode = metric_mode(cfg.model.predict.metric.type, cfg.model.predict.metric.min)
     if cfg.model.loss.fn != "l1":
         raise NotImplementedError(f"loss fn {cfg.model.loss.fn} (task/core.py:183-187 knows l1)")
@@ -214,22 +215,12 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     pool_names = pooling.value_names(pooling.PERMILLE, opts.score_pool_window)
     pool_signed = pooling.signed_range_of(cfg.model.predict.metric.type)  # cs_op_score_gt_stats' tensor, the range the writer stores it over
 
-    def gt_files(it):
-        if compute_gt:
-            return [(it["query/gt"], False)]
-        return [] if it["query/score_map"] == EMPTY else [(it["query/score_map"], True)]
-
-    def fetch_eval(d, its):
-        """decode_eval's second value out of the decode window's tensors: device tensors for the maps / captured images"""
-        if compute_gt:
-            return [d[it["query/gt"]] for it in its]
-        return [None if it["query/score_map"] == EMPTY else d[it["query/score_map"]] for it in its]
-
-    def gt_and_stats(ticket, its, decoded, maps, size, batch):
+    def gt_and_stats(ticket, its, decoded, size, batch):
         """GT stage + statistics kernel on the forward's stream, behind its score map; returns (gt, stats, event, the score pool's ticket)."""
         s = ticket.stream if ticket.stream is not None else torch.cuda.current_stream(device)
         oh, ow = size
         B = len(its)
+        maps = gt_inputs(decoded, its, compute_gt)
         if compute_gt:  # `maps` holds the captured images
             for it, g in zip(its, maps):
                 r = decoded[it["query/img"]]
@@ -240,7 +231,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
             gt = torch.empty((B, oh, ow), dtype=torch.float32, device=device)
             if compute_gt:
                 # the render bytes the one-pass input stage already holds on the device, else the decoded host arrays
-                on_device = hasattr(batch["query/img"], "images")  # (a model.U8Batch)
+                on_device = isinstance(batch["query/img"], U8Batch)
                 renders = [im.data for im in batch["query/img"].images] if on_device else [decoded[it["query/img"]] for it in its]
                 maps = stage.gt_metric_maps(renders, maps, gt_kind)
             stage.metric_maps(maps, [decoded[it["query/img"]].shape[:2] for it in its], mode, gt)
@@ -287,8 +278,7 @@ def evaluate(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
 
     run = scoring.score(cfg, opts, stage, batches, state_dict, batches[0][0]["query/img"] if batches else None,
                         calibrate=False,  # inherited: the test loop has never calibrated its batches in flight
-                        extra_files=gt_files, decode_host=lambda its, zr, pool, skip: decode_eval(its, zr, pool, skip, compute_gt),
-                        from_window=fetch_eval,
+                        extra_files=functools.partial(gt_file, compute_gt=compute_gt),
                         check_size=check_size, after_submit=gt_and_stats, on_consume=batch_stats,
                         reference_groups=items.groups if items.candidates else None)  # neighbour strategy similar: each scene's candidate lists
     # one collective that carries the metrics and any failure of a rank's output stage (a rank that raised on its own before it would leave

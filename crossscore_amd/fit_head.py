@@ -14,6 +14,7 @@ image is encoded once per run and every step after that is a forward_cached."""
 from __future__ import annotations
 
 import csv
+import functools
 import os
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -23,13 +24,13 @@ from typing import Dict, Iterable, Optional
 
 import torch
 
-from . import synth
+from . import _lib
 from .config import load_config
-from .data import EMPTY, InputStage, ReferenceTokenCache, load_batch, metric_mode
-from .evaluate import decode_eval, gt_map_kind, gt_metric_maps_choice, limit_batches
-from .model import CrossScoreNet, HeadFitState, load_lightning_checkpoint, save_lightning_checkpoint
+from .data import EMPTY, ReferenceTokenCache, decode_items, load_batch, metric_mode
+from .evaluate import gt_file, gt_inputs, gt_map_kind, gt_metric_maps_choice, limit_batches
+from .model import HeadFitState, arch_from_cfg, save_lightning_checkpoint
 from .nvs import NvsItems, random_order
-from .scoring import seed_everything
+from .scoring import build_net, nvs_input_stage, seed_everything
 
 
 def step_lr(lr0: float, step_size: int, gamma: float, n: int) -> float:
@@ -64,19 +65,10 @@ def fit_head(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
     seed_everything(int(cfg.lightning.seed))
-    net = CrossScoreNet(cfg)
-    if "operand_dtype" not in cfg.model.backbone:
-        net.operand_dtype = "bf16" if str(cfg.trainer.precision).startswith("bf16") else "fp16"
-    if not net.head_fit_supported():
-        raise ValueError(f"the head fit is built for hidden a multiple of 64 and patch 14 (hidden {net.arch.hidden}, patch {net.arch.patch})")
-    if state_dict is None:
-        if cfg.trainer.ckpt_path_to_load is not None:
-            state_dict = load_lightning_checkpoint(cfg.trainer.ckpt_path_to_load)
-        else:
-            print("[crossscore_amd.fit_head] no checkpoint: seeded synthetic weights", file=sys.stderr)
-            state_dict = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(net.arch, int(cfg.lightning.seed)).items()}
-    net.load_state_dict(state_dict, strict=True)
-    net = net.to(device)
+    arch = arch_from_cfg(cfg)
+    if not _lib.load().cs_head_fit_supported(arch.hidden, arch.patch):  # (before the weights: they would not fit another patch size either)
+        raise ValueError(f"the head fit is built for hidden a multiple of 64 and patch 14 (hidden {arch.hidden}, patch {arch.patch})")
+    net = build_net(cfg, device, state_dict, "fit_head")
 
     out_dir = cfg.logger.train.out_dir
     if out_dir is None:
@@ -85,10 +77,7 @@ def fit_head(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
                                "fit_head_" + (Path(ckpt).stem if ckpt is not None else "empty_ckpt"))
     Path(out_dir, "checkpoints").mkdir(parents=True, exist_ok=True)
 
-    crop_mode = cfg.this_main.crop_mode
-    stage = InputStage(device, resize_short_side=int(cfg.this_main.resize_short_side),
-                       crop_size=int(cfg.data.transforms.crop_size) if crop_mode == "dataset_default" else None,
-                       integer_patches=crop_mode == "integer_patches")
+    stage = nvs_input_stage(cfg, device)
     mode = metric_mode(cfg.model.predict.metric.type, cfg.model.predict.metric.min)
     gt_kind = gt_map_kind(cfg.model.predict.metric.type)
     items = NvsItems.from_config(cfg, compute_gt)
@@ -108,6 +97,7 @@ def fit_head(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     cache = (ReferenceTokenCache(net, stage, keep_images=False, max_images=int(cfg.this_main.get("reference_cache_max_images", 4096)))
              if bool(cfg.this_main.get("cache_reference_tokens", True)) else None)
     pool = ThreadPoolExecutor(max_workers=max(1, int(loader.num_workers)))
+    gt_files = functools.partial(gt_file, compute_gt=compute_gt)
     rows, losses = [], []
     try:
         for epoch in range(max_epochs):
@@ -117,7 +107,8 @@ def fit_head(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
             for its in batches:
                 if 0 <= max_steps <= state.step:
                     break
-                decoded, maps = decode_eval(its, zero_ref, pool, {k[0] for k in cache.tokens} if cache is not None else (), compute_gt)
+                decoded = decode_items(its, zero_ref, pool, {k[0] for k in cache.tokens} if cache is not None else (), gt_files)
+                maps = gt_inputs(decoded, its, compute_gt)
                 batch, size = load_batch(its, stage, decoded, False, references=cache is None, zero_reference=zero_ref)
                 if size[0] % net.arch.patch or size[1] % net.arch.patch:
                     raise ValueError(f"a {size[0]}x{size[1]} image is no whole number of {net.arch.patch}-pixel patches; use crop_mode=integer_patches")

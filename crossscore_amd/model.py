@@ -85,8 +85,8 @@ class U8Image:
 
 
 class U8Batch:
-    """The images of a forward as decoded uint8 (CrossScoreNet.forward_u8 and its siblings): `images` in batch order (references item-major:
-    item 0's N views, item 1's, ...), all producing the same (H, W) window; mean_std = the six T.Normalize numbers (task/predict.py:68-74).
+    """The images of a forward as decoded uint8 (what CrossScoreNet.forward and its siblings take in place of fp32 tensors): `images` in batch
+    order (references item-major: item 0's N views, item 1's, ...), all producing the same (H, W) window; mean_std = the six T.Normalize numbers (task/predict.py:68-74).
     device: where the batch runs when every image is a placeholder (data None: nothing to take it from), e.g. zero_reference's reference keys."""
 
     def __init__(self, images, size, mean_std=synth.IMAGENET_MEAN_STD, device=None):
@@ -166,6 +166,24 @@ def _group_offsets(offsets, R: int) -> np.ndarray:
     if o.size < 2 or o[0] != 0 or np.any(np.diff(o) <= 0) or o[-1] > R:
         raise ValueError(f"group offsets must start at 0, increase strictly and end inside the bank's {R} rows: {o.tolist()[:8]}{'...' if o.size > 8 else ''}")
     return o.astype(np.int32)
+
+
+def _u8_form(*imgs) -> bool:
+    """Whether a call's image arguments are U8Batch objects (else fp32 tensors): this picks the C entry point.  One call takes one form."""
+    u8 = [isinstance(x, U8Batch) for x in imgs if x is not None]
+    if any(u8) and not all(u8):
+        raise ValueError("a call takes its images in one form: U8Batch objects or fp32 tensors, not both")
+    return any(u8)
+
+
+def _images(x, b0: int, b1: int, per_item: int = 1):
+    """The C argument for the images of the items b0 .. b1 - 1 in either form (a U8Batch of references holds per_item images an item)."""
+    return x.c_array(b0 * per_item, b1 * per_item) if isinstance(x, U8Batch) else C.c_void_p(x[b0:b1].data_ptr())
+
+
+def _norm(x) -> tuple:
+    """The (mean, std) pair a *_u8 entry point takes in front of its tail; the fp32 form is normalised already."""
+    return (x.mean, x.std) if isinstance(x, U8Batch) else ()
 
 
 class _Node(torch.nn.Module):
@@ -374,41 +392,55 @@ class CrossScoreNet(torch.nn.Module):
         :param need_reference_use: also return ref_use_share / ref_use_peak_prob / ref_use_peak_index (B, N, h, w) and ref_use_entropy (B, h, w):
                                 which reference each query patch's last-layer cross-attention went to, where it looked, how spread it was
                                 (mean over the heads).  Every forward* method takes it; the other outputs keep their bits.
-        :param query_img:       (B, 3, H, W) fp32, ImageNet-normalised
-        :param ref_cross_imgs:  (B, N_ref_cross, 3, H, W)
+        :param query_img:       (B, 3, H, W) fp32, ImageNet-normalised -- or a U8Batch of B decoded images
+        :param ref_cross_imgs:  (B, N_ref_cross, 3, H, W) -- or a U8Batch of B * N images; one call takes one form
         :param norm_img:        reference flag (task/core.py:76-81), bug-for-bug: the std used is the mean.
         """
-        if not self._do_reference_cross:
-            # task/core.py:84-117 with the flag off: features of the query (and of the references, when given) are computed and dropped, the
-            # result dict stays empty.  The input checks of get_featmaps (:119-138: a 4-D query, references that concatenate with it) still hold.
-            if query_img.dim() != 4 or query_img.shape[1] != 3:
-                raise ValueError("expected query_img (B,3,H,W)")
-            if ref_cross_imgs is not None and (ref_cross_imgs.dim() != 5 or ref_cross_imgs.shape[0] != query_img.shape[0] or
-                                               tuple(ref_cross_imgs.shape[2:]) != tuple(query_img.shape[1:])):
-                raise ValueError("expected ref_cross_imgs (B,N,3,H,W) matching query_img")
-            return {}
-        if ref_cross_imgs is None:
-            raise ValueError("ref_cross_imgs is required when model.do_reference_cross=True (task/core.py:90)")
-        if query_img.dim() != 4 or query_img.shape[1] != 3 or ref_cross_imgs.dim() != 5 or ref_cross_imgs.shape[2] != 3:
-            raise ValueError("expected query_img (B,3,H,W) and ref_cross_imgs (B,N,3,H,W)")
-        if ref_cross_imgs.shape[0] != query_img.shape[0] or ref_cross_imgs.shape[-2:] != query_img.shape[-2:]:
-            raise ValueError("query and reference batch / image sizes differ")
-        if not query_img.is_cuda:
-            raise _lib.CrossScoreHipError("CrossScoreNet.forward needs CUDA(HIP) tensors: the hot path has no CPU fallback")
-        dev = query_img.device
-        if norm_img:
-            mean = self.img_mean_std.to(dev)[None, :3, None, None]
-            query_img = (query_img - mean) / mean  # sic: task/core.py:77-79 divides by the mean
-            ref_cross_imgs = (ref_cross_imgs - mean[:, None]) / mean[:, None]
-        q = query_img.to(torch.float32).contiguous()
-        r = ref_cross_imgs.to(device=dev, dtype=torch.float32).contiguous()
-        B, _, H, W = q.shape
-        N = r.shape[1]
+        u8 = _u8_form(query_img, ref_cross_imgs)
+        if u8:
+            # decoded uint8 images: query = B images, refs = B * N images (item-major).  The resize / crop / normalise of the input stage
+            # happens inside the patch-embedding launch; results are bit-identical to InputStage + the fp32 form.
+            if norm_img:
+                raise ValueError("norm_img=True takes fp32 images: U8Batch inputs are normalised inside the patch-embedding launch")
+            q, r, B = query_img, ref_cross_imgs, len(query_img)
+            if B == 0 or len(r) % B or q.size != r.size:
+                raise ValueError("expected B query images and B * N reference images of one processed size")
+            N = len(r) // B
+            H, W = q.size
+            dev = q.device
+            if dev is None:
+                raise _lib.CrossScoreHipError("forward needs device images: the hot path has no CPU fallback")
+        else:
+            if not self._do_reference_cross:
+                # task/core.py:84-117 with the flag off: features of the query (and of the references, when given) are computed and dropped, the
+                # result dict stays empty.  The input checks of get_featmaps (:119-138: a 4-D query, references that concatenate with it) still hold.
+                if query_img.dim() != 4 or query_img.shape[1] != 3:
+                    raise ValueError("expected query_img (B,3,H,W)")
+                if ref_cross_imgs is not None and (ref_cross_imgs.dim() != 5 or ref_cross_imgs.shape[0] != query_img.shape[0] or
+                                                   tuple(ref_cross_imgs.shape[2:]) != tuple(query_img.shape[1:])):
+                    raise ValueError("expected ref_cross_imgs (B,N,3,H,W) matching query_img")
+                return {}
+            if ref_cross_imgs is None:
+                raise ValueError("ref_cross_imgs is required when model.do_reference_cross=True (task/core.py:90)")
+            if query_img.dim() != 4 or query_img.shape[1] != 3 or ref_cross_imgs.dim() != 5 or ref_cross_imgs.shape[2] != 3:
+                raise ValueError("expected query_img (B,3,H,W) and ref_cross_imgs (B,N,3,H,W)")
+            if ref_cross_imgs.shape[0] != query_img.shape[0] or ref_cross_imgs.shape[-2:] != query_img.shape[-2:]:
+                raise ValueError("query and reference batch / image sizes differ")
+            if not query_img.is_cuda:
+                raise _lib.CrossScoreHipError("CrossScoreNet.forward needs CUDA(HIP) tensors: the hot path has no CPU fallback")
+            dev = query_img.device
+            if norm_img:
+                mean = self.img_mean_std.to(dev)[None, :3, None, None]
+                query_img = (query_img - mean) / mean  # sic: task/core.py:77-79 divides by the mean
+                ref_cross_imgs = (ref_cross_imgs - mean[:, None]) / mean[:, None]
+            q = query_img.to(torch.float32).contiguous()
+            r = ref_cross_imgs.to(device=dev, dtype=torch.float32).contiguous()
+            B, _, H, W = q.shape
+            N = r.shape[1]
         self._check_pe_mode(H, W)
-        lib = _lib.load()
         handle = self._ensure_handle(dev)
-        return self._score(lambda b0, b1, tail: lib.cs_forward(handle, C.c_void_p(q[b0:b1].data_ptr()), C.c_void_p(r[b0:b1].data_ptr()),
-                                                               b1 - b0, N, H, W, *tail),
+        fn = _lib.load().cs_forward_u8 if u8 else _lib.load().cs_forward
+        return self._score(lambda b0, b1, tail: fn(handle, _images(q, b0, b1), _images(r, b0, b1, N), b1 - b0, N, H, W, *_norm(q), *tail),
                            B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean, need_reference_use)
 
     def _sub_batches(self, B: int, N: int, Np: int):
@@ -421,115 +453,67 @@ class CrossScoreNet(torch.nn.Module):
     # -- reference-feature cache: a separate mode, bit-identical results ---------------------------
     @torch.no_grad()
     def encode_references(self, ref_imgs):
-        """(R,3,H,W) normalised reference images -> (R, h*w, C) fp16 decoder-ready tokens (final LN + multi-view PE).
-        A reference's tokens depend neither on the query nor on its view slot, so they can be computed once per image of
+        """(R,3,H,W) normalised reference images, or a U8Batch of R decoded ones -> (R, h*w, C) fp16 decoder-ready tokens (final LN + multi-view
+        PE).  A reference's tokens depend neither on the query nor on its view slot, so they can be computed once per image of
         reference_dir and gathered per query."""
-        if ref_imgs.dim() != 4 or ref_imgs.shape[1] != 3 or not ref_imgs.is_cuda:
-            raise ValueError("expected CUDA ref_imgs (R,3,H,W)")
-        dev = ref_imgs.device
-        x = ref_imgs.to(torch.float32).contiguous()
-        R, _, H, W = x.shape
+        u8 = _u8_form(ref_imgs)
+        if u8:
+            x, R, (H, W), dev = ref_imgs, len(ref_imgs), ref_imgs.size, ref_imgs.device
+            if R == 0 or dev is None:
+                raise ValueError("expected at least one device image")
+        else:
+            if ref_imgs.dim() != 4 or ref_imgs.shape[1] != 3 or not ref_imgs.is_cuda:
+                raise ValueError("expected CUDA ref_imgs (R,3,H,W)")
+            dev = ref_imgs.device
+            x = ref_imgs.to(torch.float32).contiguous()
+            R, _, H, W = x.shape
         self._check_pe_mode(H, W)
         P = self.arch.patch
         handle = self._ensure_handle(dev)
+        fn = _lib.load().cs_encode_references_u8 if u8 else _lib.load().cs_encode_references
         with torch.cuda.device(dev):
             tok = torch.empty((R, (H // P) * (W // P), self.arch.hidden), dtype=self.token_dtype, device=dev)
-            _lib.check(_lib.load().cs_encode_references(handle, C.c_void_p(x.data_ptr()), R, H, W, C.c_void_p(tok.data_ptr()),
-                                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _lib.check(fn(handle, _images(x, 0, R), R, H, W, *_norm(x), C.c_void_p(tok.data_ptr()),
+                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return tok
 
     @torch.no_grad()
     def forward_cached(self, query_img, ref_tokens, need_attn_weights=False, need_attn_weights_head_id=0, return_mean=False,
                        need_reference_use=False):
         """forward() with the reference views given as cached tokens (B, N, h*w, C) fp16 from encode_references."""
-        if query_img.dim() != 4 or ref_tokens.dim() != 4 or ref_tokens.shape[0] != query_img.shape[0]:
-            raise ValueError("expected query_img (B,3,H,W) and ref_tokens (B,N,h*w,C)")
-        if not query_img.is_cuda or not ref_tokens.is_cuda or ref_tokens.device != query_img.device:
-            raise _lib.CrossScoreHipError("forward_cached needs CUDA(HIP) tensors on one device: the hot path has no CPU fallback")
-        dev = query_img.device
-        q = query_img.to(torch.float32).contiguous()
-        if ref_tokens.dtype != self.token_dtype:
-            raise ValueError(f"ref_tokens are {ref_tokens.dtype}, this module's operand type is {self.token_dtype}: encode them with the same module")
+        u8 = _u8_form(query_img)
+        if u8:
+            q, B, (H, W), dev = query_img, len(query_img), query_img.size, ref_tokens.device
+            if ref_tokens.dim() != 4 or ref_tokens.shape[0] != B or not ref_tokens.is_cuda or ref_tokens.dtype != self.token_dtype:
+                raise ValueError("expected CUDA ref_tokens (B,N,h*w,C) of this module's operand type")
+        else:
+            if query_img.dim() != 4 or ref_tokens.dim() != 4 or ref_tokens.shape[0] != query_img.shape[0]:
+                raise ValueError("expected query_img (B,3,H,W) and ref_tokens (B,N,h*w,C)")
+            if not query_img.is_cuda or not ref_tokens.is_cuda or ref_tokens.device != query_img.device:
+                raise _lib.CrossScoreHipError("forward_cached needs CUDA(HIP) tensors on one device: the hot path has no CPU fallback")
+            dev = query_img.device
+            q = query_img.to(torch.float32).contiguous()
+            if ref_tokens.dtype != self.token_dtype:
+                raise ValueError(f"ref_tokens are {ref_tokens.dtype}, this module's operand type is {self.token_dtype}: encode them with the same module")
+            B, _, H, W = q.shape
         t = ref_tokens.contiguous()
-        B, _, H, W = q.shape
         N = t.shape[1]
         P = self.arch.patch
-        h, w = H // P, W // P
         self._check_pe_mode(H, W)
-        if t.shape[2] != h * w or t.shape[3] != self.arch.hidden:
+        if t.shape[2] != (H // P) * (W // P) or t.shape[3] != self.arch.hidden:
             raise ValueError("ref_tokens do not match the query's patch grid / hidden size")
         handle = self._ensure_handle(dev)
-        lib = _lib.load()
-        return self._score(lambda b0, b1, tail: lib.cs_forward_cached(handle, C.c_void_p(q[b0:b1].data_ptr()), C.c_void_p(t[b0:b1].data_ptr()),
-                                                                      b1 - b0, N, H, W, *tail),
+        fn = _lib.load().cs_forward_cached_u8 if u8 else _lib.load().cs_forward_cached
+        return self._score(lambda b0, b1, tail: fn(handle, _images(q, b0, b1), C.c_void_p(t[b0:b1].data_ptr()), b1 - b0, N, H, W, *_norm(q), *tail),
                            B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean, need_reference_use)
 
-    # -- the same three calls fed from decoded uint8 images (SURVEY.md 8f-4 as worded: uint8 in, tokens out) --------------------------------
     def u8_input_supported(self, img: U8Image, size, device=None) -> bool:
-        """Whether forward_u8 / encode_references_u8 / forward_cached_u8 take this image geometry (else: InputStage + the fp32 calls)."""
+        """Whether forward / encode_references / forward_cached take this image geometry as a U8Batch (else: InputStage + the fp32 form)."""
         dev = device or (img.data.device if img.data is not None else None)
         if dev is None or not self._do_reference_cross:
             return False
         st = img.c_struct()
         return bool(_lib.load().cs_u8_input_supported(self._ensure_handle(dev), C.byref(st), int(size[0]), int(size[1])))
-
-    @torch.no_grad()
-    def forward_u8(self, query: U8Batch, refs: U8Batch, need_attn_weights=False, need_attn_weights_head_id=0, return_mean=False,
-                   need_reference_use=False):
-        """forward() from decoded uint8 images: query = B images, refs = B * N images (item-major).  The resize / crop / normalise of the input
-        stage happens inside the patch-embedding launch; results are bit-identical to InputStage + forward()."""
-        B = len(query)
-        if B == 0 or len(refs) % B or query.size != refs.size:
-            raise ValueError("expected B query images and B * N reference images of one processed size")
-        N = len(refs) // B
-        H, W = query.size
-        dev = query.device
-        if dev is None:
-            raise _lib.CrossScoreHipError("forward_u8 needs device images: the hot path has no CPU fallback")
-        self._check_pe_mode(H, W)
-        lib = _lib.load()
-        handle = self._ensure_handle(dev)
-        return self._score(lambda b0, b1, tail: lib.cs_forward_u8(handle, query.c_array(b0, b1), refs.c_array(b0 * N, b1 * N),
-                                                                  b1 - b0, N, H, W, query.mean, query.std, *tail),
-                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean, need_reference_use)
-
-    @torch.no_grad()
-    def encode_references_u8(self, imgs: U8Batch):
-        """encode_references() from decoded uint8 images."""
-        R = len(imgs)
-        H, W = imgs.size
-        dev = imgs.device
-        if R == 0 or dev is None:
-            raise ValueError("expected at least one device image")
-        self._check_pe_mode(H, W)
-        P = self.arch.patch
-        handle = self._ensure_handle(dev)
-        with torch.cuda.device(dev):
-            tok = torch.empty((R, (H // P) * (W // P), self.arch.hidden), dtype=self.token_dtype, device=dev)
-            _lib.check(_lib.load().cs_encode_references_u8(handle, imgs.c_array(0, R), R, H, W, imgs.mean, imgs.std, C.c_void_p(tok.data_ptr()),
-                                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        return tok
-
-    @torch.no_grad()
-    def forward_cached_u8(self, query: U8Batch, ref_tokens, need_attn_weights=False, need_attn_weights_head_id=0, return_mean=False,
-                          need_reference_use=False):
-        """forward_cached() with the query images as decoded uint8."""
-        B = len(query)
-        H, W = query.size
-        dev = ref_tokens.device
-        if ref_tokens.dim() != 4 or ref_tokens.shape[0] != B or not ref_tokens.is_cuda or ref_tokens.dtype != self.token_dtype:
-            raise ValueError("expected CUDA ref_tokens (B,N,h*w,C) of this module's operand type")
-        t = ref_tokens.contiguous()
-        N = t.shape[1]
-        P = self.arch.patch
-        if t.shape[2] != (H // P) * (W // P) or t.shape[3] != self.arch.hidden:
-            raise ValueError("ref_tokens do not match the query's patch grid / hidden size")
-        self._check_pe_mode(H, W)
-        lib = _lib.load()
-        handle = self._ensure_handle(dev)
-        return self._score(lambda b0, b1, tail: lib.cs_forward_cached_u8(handle, query.c_array(b0, b1), C.c_void_p(t[b0:b1].data_ptr()),
-                                                                         b1 - b0, N, H, W, query.mean, query.std, *tail),
-                           B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean, need_reference_use)
 
     # -- reference selection by similarity (DESIGN.md 6, f11): the choice of each query's views is made on the device ----------------------
     @torch.no_grad()
@@ -562,16 +546,16 @@ class CrossScoreNet(torch.nn.Module):
                 _lib.check(lib.cs_op_descriptor_unit(C.c_void_p(mean.data_ptr()), R, Cc, C.c_void_p(centre.data_ptr()), C.c_void_p(unit.data_ptr()), st))
         return mean, centre, unit
 
-    def _forward_select(self, query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, u8, group=None,
+    def _forward_select(self, query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, group=None,
                         need_reference_use=False):
+        u8 = _u8_form(query)
         N = int(bank.n_references if n_references is None else n_references)
         t = bank.tokens
         dev = t.device
         if t.dtype != self.token_dtype:
             raise ValueError(f"the bank's tokens are {t.dtype}, this module's operand type is {self.token_dtype}: encode them with the same module")
         if u8:
-            B = len(query)
-            H, W = query.size
+            q, B, (H, W) = query, len(query), query.size
             if B == 0:
                 raise ValueError("expected at least one query image")
         else:
@@ -616,8 +600,8 @@ class CrossScoreNet(torch.nn.Module):
                 # (a grouped bank's host arrays are copied into a pinned slot inside the call: they need not outlive it)
                 groups = (bank.offsets.ctypes.data_as(C.c_void_p), len(bank.offsets) - 1, grp[b0:b1].ctypes.data_as(C.c_void_p),
                           bank.blank_row) if grouped else ()
-                return fn(handle, query.c_array(b0, b1) if u8 else C.c_void_p(q[b0:b1].data_ptr()), *bank_args, *groups,
-                          C.c_void_p(ex[b0:b1].data_ptr()) if ex is not None else None, b1 - b0, N, H, W, *((query.mean, query.std) if u8 else ()),
+                return fn(handle, _images(q, b0, b1), *bank_args, *groups,
+                          C.c_void_p(ex[b0:b1].data_ptr()) if ex is not None else None, b1 - b0, N, H, W, *_norm(q),
                           *tail[:4], C.c_void_p(index[b0:b1].data_ptr()), C.c_void_p(sim[b0:b1].data_ptr()), tail[4])
 
             results = self._score(call, B, N, H, W, dev, need_attn_weights, need_attn_weights_head_id, return_mean, need_reference_use)
@@ -636,16 +620,10 @@ class CrossScoreNet(torch.nn.Module):
         """forward_cached() with each query's N = bank.n_references views chosen on the device: the bank entries most similar to the query's own
         pooled descriptor, descending, ties to the lower index, exclude[b] (int32 (B), -1 = none) left out.  The result also holds
         "reference_index" (B, N) int32 and "reference_similarity" (B, N) fp32; the score map, mean and attention weights are bit-identical to
-        forward_cached(query_img, bank.tokens[reference_index]).  A grouped bank needs `group`, one group id per query (host integers): the
-        query chooses among that group's rows only, a group shorter than N leaves -1 in reference_index and NaN in reference_similarity, and
+        forward_cached(query_img, bank.tokens[reference_index]).  query_img: fp32 (B, 3, H, W) or a U8Batch.  A grouped bank needs `group`, one
+        group id per query (host integers): the query chooses among that group's rows only, a group shorter than N leaves -1 in reference_index and NaN in reference_similarity, and
         those places are fed bank.blank_row's tokens (zeros when it is -1)."""
-        return self._forward_select(query_img, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, False, group, need_reference_use)
-
-    @torch.no_grad()
-    def forward_select_u8(self, query: U8Batch, bank: "SelectionBank", exclude=None, need_attn_weights=False, need_attn_weights_head_id=0,
-                          return_mean=False, n_references=None, group=None, need_reference_use=False):
-        """forward_select() with the query images as decoded uint8."""
-        return self._forward_select(query, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, True, group, need_reference_use)
+        return self._forward_select(query_img, bank, exclude, need_attn_weights, need_attn_weights_head_id, return_mean, n_references, group, need_reference_use)
 
     def calibrate_lanes(self, query_img, ref_cross_imgs, tries: int = 3, steps: int = 4, min_gain: float = 0.08) -> Dict[str, Any]:
         """Checks that this module's multi-lane forward really overlaps its lanes, and repairs it if not.  The lanes' streams are probed
@@ -734,8 +712,8 @@ class CrossScoreNet(torch.nn.Module):
         return out
 
     def fit_head_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
-        """One AdamW step of the regression head on one batch: the forward through the existing path (forward for tensors, forward_u8 for
-        U8Batch inputs, the cached forms with ref_tokens), cs_head_backward behind each sub-batch, cs_op_adamw on the four parameters in place,
+        """One AdamW step of the regression head on one batch: the forward through the existing path (forward, in either form of its
+        images; forward_cached with ref_tokens), cs_head_backward behind each sub-batch, cs_op_adamw on the four parameters in place,
         cs_set_head_weights.  The module is not marked dirty: the handle keeps every other packed weight.  gt: (B, h P, w P) fp32 on the
         device, the score map's shape.  Returns the loss of the batch BEFORE the step as a device fp64 scalar; nothing is waited for."""
         if (refs is None) == (ref_tokens is None):
@@ -760,13 +738,9 @@ class CrossScoreNet(torch.nn.Module):
                                             *(C.c_void_p(g.data_ptr()) for g in grads), C.c_void_p(loss.data_ptr()),
                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
 
-        u8 = isinstance(query, U8Batch)
         self._after_sub_batch = backward
         try:
-            if ref_tokens is not None:
-                res = self.forward_cached_u8(query, ref_tokens) if u8 else self.forward_cached(query, ref_tokens)
-            else:
-                res = self.forward_u8(query, refs) if u8 else self.forward(query, refs)
+            res = self.forward_cached(query, ref_tokens) if ref_tokens is not None else self.forward(query, refs)
         finally:
             self._after_sub_batch = None
         if tuple(res["score_map_ref_cross"].shape) != tuple(gt.shape):

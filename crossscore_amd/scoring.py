@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import parallel, pooling, synth, vis
-from .data import EMPTY, STRATEGIES, ReferenceBank, ReferenceTokenCache, decode_items, load_batch, plan_decodes
+from .data import EMPTY, STRATEGIES, InputStage, ReferenceBank, ReferenceTokenCache, decode_items, load_batch, plan_decodes
 from .decode import DecodeWindow, ImageDecoder, jpeg_decoder_choice, jpeg_progressive_choice, png_decode_window_choice, png_decoder_choice, read_image_u8
 from .model import CrossScoreNet, U8Image, load_lightning_checkpoint
 from .pipeline import ForwardPipeline
@@ -123,6 +123,36 @@ def start(cfg, o: SimpleNamespace) -> None:
     torch.cuda.set_device(o.device)
 
 
+def build_net(cfg, device, state_dict, who: str) -> CrossScoreNet:
+    """The run's module on `device` with its weights: state_dict, else the checkpoint of trainer.ckpt_path_to_load, else seeded synthetic
+    weights and a warning in the name of the driver `who`."""
+    net = CrossScoreNet(cfg)
+    # trainer.precision (config/default_predict.yaml:25, the reference's own key; Lightning names): "16-mixed" (default) / "16" -> IEEE
+    # half MFMA operands, "bf16-mixed" / "bf16" -> bfloat16 operands (fp32's range: for checkpoints whose activations leave the half
+    # range).  "32" / "32-true" have no counterpart here (the MFMA operands are 16 bits wide; everything else is fp32 already) and
+    # select the more accurate of the two, half.  An explicit model.backbone.operand_dtype wins.
+    if "operand_dtype" not in cfg.model.backbone:
+        net.operand_dtype = "bf16" if str(cfg.trainer.precision).startswith("bf16") else "fp16"
+    if state_dict is None:
+        if cfg.trainer.ckpt_path_to_load is not None:
+            state_dict = load_lightning_checkpoint(cfg.trainer.ckpt_path_to_load)
+        else:  # the reference would start from the hub's DINOv2 weights + a random decoder; there is no hub here
+            print(f"[crossscore_amd.{who}] no checkpoint: seeded synthetic weights (scores are meaningless)", file=sys.stderr)
+            state_dict = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(net.arch, int(cfg.lightning.seed)).items()}
+    net.load_state_dict(state_dict, strict=True)
+    return net.to(device)
+
+
+def nvs_input_stage(cfg, device) -> InputStage:
+    """The input stage of the drivers that walk an NvsDataset tree (evaluate, fit_head), from this_main.crop_mode."""
+    crop_mode = cfg.this_main.crop_mode
+    if crop_mode not in (None, "integer_patches", "dataset_default"):
+        raise ValueError(f"crop_mode {crop_mode} not supported (task/test.py:75-91 knows null, integer_patches and dataset_default)")
+    return InputStage(device, resize_short_side=int(cfg.this_main.resize_short_side),
+                      crop_size=int(cfg.data.transforms.crop_size) if crop_mode == "dataset_default" else None,
+                      integer_patches=crop_mode == "integer_patches")
+
+
 def write_reference_selection(out_dir: str, selection, path_parts: int = 1) -> str:
     """reference_selection.csv of a run with neighbour strategy similar: per query its file name, then the chosen references' file names in the
     order chosen, then their similarities as %.4f.  path_parts: how many trailing parts of a path name a file, joined with "/" -- 1 for predict's
@@ -192,38 +222,22 @@ class Scored(NamedTuple):
 
 
 def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: Optional[str] = None, *, calibrate: bool = False,
-          extra_files=None, decode_host=None, from_window=None, check_size=None, after_submit=None, on_consume=None,
+          extra_files=None, check_size=None, after_submit=None, on_consume=None,
           reference_paths=None, reference_groups=None) -> Scored:
     """Scores `batches` (lists of item dictionaries; cfg.logger.<phase>.out_dir exists) and finishes the outputs.
 
     probe_path: the first query of this rank, whose geometry decides about the one-pass input stage (None: no image to look at).
     calibrate: at batch 0 of a run of >= 16 batches, make sure the batches in flight (at depth 1 the forward's lanes) really overlap.
-    extra_files(item) -> [(path, gray16)]: files the decode window reads beside the item's images.
-    decode_host(items, zero_ref, pool, skip) -> (decoded, extras) replaces decode_items on the host path; from_window(decoded, items) -> extras
-    picks the same extras out of the window's tensors.
+    extra_files(item) -> [(path, gray16)]: files the loader reads beside the item's images, into the same `decoded`.
     check_size(size) may refuse a batch's processed size before anything of it is queued.
     reference_paths: the files of reference_dir, in the driver's order: the candidates of neighbour strategy similar.
     reference_groups (instead): candidate lists, of which each item names its own by "reference/cross/group" (nvs.NvsItems.groups).
-    after_submit(ticket, items, decoded, extras, size, batch) -> state; on_consume(idx, batch, out, state) runs before the summariser and writer;
+    after_submit(ticket, items, decoded, size, batch) -> state; on_consume(idx, batch, out, state) runs before the summariser and writer;
     with this_main.score_pool it may leave per image the fields of its own score-pool columns in batch["score_pool/extra"] (evaluate: gt_*),
     with this_main.vis_sheet item 0's ground-truth mean and L1 in batch["vis_sheet/extra"]."""
     phase, device = o.phase, o.device
     log = cfg.logger[phase]
-    net = CrossScoreNet(cfg)
-    # trainer.precision (config/default_predict.yaml:25, the reference's own key; Lightning names): "16-mixed" (default) / "16" -> IEEE
-    # half MFMA operands, "bf16-mixed" / "bf16" -> bfloat16 operands (fp32's range: for checkpoints whose activations leave the half
-    # range).  "32" / "32-true" have no counterpart here (the MFMA operands are 16 bits wide; everything else is fp32 already) and
-    # select the more accurate of the two, half.  An explicit model.backbone.operand_dtype wins.
-    if "operand_dtype" not in cfg.model.backbone:
-        net.operand_dtype = "bf16" if str(cfg.trainer.precision).startswith("bf16") else "fp16"
-    if state_dict is None:
-        if cfg.trainer.ckpt_path_to_load is not None:
-            state_dict = load_lightning_checkpoint(cfg.trainer.ckpt_path_to_load)
-        else:  # the reference would start from the hub's DINOv2 weights + a random decoder; there is no hub here
-            print(f"[crossscore_amd.{DRIVER[phase]}] no checkpoint: seeded synthetic weights (scores are meaningless)", file=sys.stderr)
-            state_dict = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(net.arch, int(cfg.lightning.seed)).items()}
-    net.load_state_dict(state_dict, strict=True)
-    net = net.to(device)
+    net = build_net(cfg, device, state_dict, DRIVER[phase])
 
     writer = (BatchWriter(cfg, phase, net.img_mean_std, device, workers=max(1, int(cfg.data.loader.validation.num_workers) // 2),
                           png_encoder=o.png_encoder, png_compression=o.png_compression)
@@ -267,14 +281,8 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     n_cross = int(cfg.data.neighbour_config.cross)
 
     def decode(i, skip):
-        """(decoded images of batch i, the driver's extras), on the loader's thread: {path: device tensor} from the decode window, else
-        {path: host array}"""
-        if window is not None:
-            d = window.fetch(i)
-            return d, from_window(d, batches[i]) if from_window is not None else None
-        if decode_host is not None:
-            return decode_host(batches[i], zero_ref, pool, skip)
-        return decode_items(batches[i], zero_ref, pool, skip), None
+        """the decoded files of batch i, on the loader's thread: {path: device tensor} from the decode window, else {path: host array}"""
+        return window.fetch(i) if window is not None else decode_items(batches[i], zero_ref, pool, skip, extra_files)
 
     def submit_decode(i):
         if i >= len(batches):
@@ -363,7 +371,7 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
     t0 = time.perf_counter()
     queued = []  # batches submitted and not yet consumed, oldest first: depth of them stay in flight
     for batch_idx, its in enumerate(batches):
-        decoded, extras = pending.result()
+        decoded = pending.result()
         if similar:
             batch, size = load_batch(its, stage, decoded, fused_in, references=False)
             check(size)
@@ -383,20 +391,17 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
                 if any(e >= 0 for e in ex):  # (an array makes every query of the call count as carrying an exclusion: cs_forward_select)
                     exclude = torch.tensor(ex, dtype=torch.int32).to(device)
             group = np.array([bank_group[it["reference/cross/group"]] for it in its], dtype=np.int32) if grouped else None
-            ticket = (pipe.submit_select_u8 if fused_in else pipe.submit_select)(batch["query/img"], bank.bank, exclude, need_w, head_id, True, group=group, **use_kw)
+            ticket = pipe.submit_select(batch["query/img"], bank.bank, exclude, need_w, head_id, True, group=group, **use_kw)
         elif cache is None:
             pending = submit_decode(batch_idx + 1)
             batch, size = load_batch(its, stage, decoded, fused_in, zero_reference=zero_ref)
             check(size)
             refs = batch["reference/cross/imgs"]
             if batch_idx == 0 and long_run:  # make sure the batches in flight really overlap (pipeline.py)
-                pipe.calibrate(batch["query/img"], refs, u8=fused_in)
+                pipe.calibrate(batch["query/img"], refs)
                 if pipe.depth == 1 and not fused_in:  # one batch at a time: then it is the forward's two lanes that have to overlap (model.py)
                     net.calibrate_lanes(batch["query/img"], refs)
-            if fused_in:
-                ticket = pipe.submit_u8(batch["query/img"], refs, need_w, head_id, True, **use_kw)
-            else:
-                ticket = pipe.submit(batch["query/img"], refs, need_w, head_id, False, return_mean=True, **use_kw)
+            ticket = pipe.submit(batch["query/img"], refs, need_w, head_id, return_mean=True, **use_kw)
         else:
             batch, size = load_batch(its, stage, decoded, fused_in, references=False)
             check(size)
@@ -404,10 +409,10 @@ def score(cfg, o: SimpleNamespace, stage, batches, state_dict=None, probe_path: 
             # (submitted after gather so that the set of cached paths is current; decoding overlaps the forward below)
             pending = submit_decode(batch_idx + 1)
             if batch_idx == 0 and long_run:  # the same check for the (default) cached mode
-                pipe.calibrate(batch["query/img"], tokens, cached=True, u8=fused_in)
-            ticket = (pipe.submit_cached_u8 if fused_in else pipe.submit_cached)(batch["query/img"], tokens, need_w, head_id, True, **use_kw)
+                pipe.calibrate(batch["query/img"], tokens, cached=True)
+            ticket = pipe.submit_cached(batch["query/img"], tokens, need_w, head_id, True, **use_kw)
         pooled = stage_score_pool(ticket)
-        state = after_submit(ticket, its, decoded, extras, tuple(size), batch) if after_submit is not None else None
+        state = after_submit(ticket, its, decoded, tuple(size), batch) if after_submit is not None else None
         n_done += len(its)
         queued.append((ticket, batch, batch_idx, state, stage_reference_use(ticket), pooled))
         while len(queued) >= pipe.depth:

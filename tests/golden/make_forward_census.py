@@ -119,10 +119,10 @@ def run_case(name, capture=False):
         q, r = (torch.from_numpy(a).to(dev) for a in synth.make_inputs(B, N, H, W, 8))
         if drive == "u8":
             q8, r8 = _u8_inputs(net, B, N, dev)
-            note("forward_u8", net.forward_u8(q8, r8, True, 3, True))
-            tok = net.encode_references_u8(r8)
+            note("forward_u8", net.forward(q8, r8, True, 3, return_mean=True))
+            tok = net.encode_references(r8)
             note("encode_references_u8", {"tokens": tok})
-            note("forward_cached_u8", net.forward_cached_u8(q8, tok.reshape((B, N) + tuple(tok.shape[1:])), False, 0, True))
+            note("forward_cached_u8", net.forward_cached(q8, tok.reshape((B, N) + tuple(tok.shape[1:])), False, 0, True))
         elif drive == "cached":
             tok = net.encode_references(r.reshape(B * N, 3, H, W))
             note("encode_references", {"tokens": tok})

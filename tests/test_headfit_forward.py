@@ -63,7 +63,7 @@ def test_backward_equals_op_on_the_forwards_tokens(backbone, B, N, how, dtype):
         tok = net.encode_references(r.reshape(B * N, 3, H, W)).reshape(B, N, -1, net.arch.hidden)
         score = net.forward_cached(q, tok)["score_map_ref_cross"]
     else:
-        score = net.forward_u8(_u8_batch(B, H, W, 1), _u8_batch(B * N, H, W, 2))["score_map_ref_cross"]
+        score = net.forward(_u8_batch(B, H, W, 1), _u8_batch(B * N, H, W, 2))["score_map_ref_cross"]
     gh, gw, Cc = H // P, W // P, net.arch.hidden
     M = B * gh * gw
     gt = _gt_near(score, 9)

@@ -711,7 +711,7 @@ def test_encode_references_u8_all_placeholders():
     H, W, R = 56, 70, 3
     batch = stage.batch([stage.placeholder((H, W)) for _ in range(R)], (H, W))
     assert batch.device == torch.device(DEV)
-    t_u8 = net.encode_references_u8(batch)
+    t_u8 = net.encode_references(batch)
     imgs = stage.zero_image_value[None, :, None, None].expand(R, 3, H, W).contiguous()
     t_f32 = net.encode_references(imgs)
     torch.cuda.synchronize()

@@ -413,3 +413,24 @@ def test_all_placeholder_u8_batch_keeps_its_device():
     ph = [U8Image(None, 56, 70, (56, 70)) for _ in range(3)]
     assert U8Batch(ph, (56, 70)).device is None
     assert U8Batch(ph, (56, 70), device="cuda:0").device == torch.device("cuda:0")
+
+
+def test_forward_refuses_mixed_forms_and_norm_img_with_u8():
+    """A call takes its images in one form, and norm_img belongs to the fp32 form (a U8Batch is normalised inside the patch-embedding launch):
+    both are refused with ValueError before the handle or the library is touched, so no GPU is needed to see it."""
+    from crossscore_amd.model import U8Batch, U8Image
+
+    net = CrossScoreNet(model_config(**{"backbone.from_pretrained": "synthetic/dinov2-tiny"}))
+    B, N, size = 2, 3, (56, 70)
+    q8 = U8Batch([U8Image(None, 56, 70, size) for _ in range(B)], size, device="cuda:0")
+    r8 = U8Batch([U8Image(None, 56, 70, size) for _ in range(B * N)], size, device="cuda:0")
+    q32, r32 = torch.zeros((B, 3) + size), torch.zeros((B, N, 3) + size)
+    with pytest.raises(ValueError, match="one form"):
+        net.forward(q8, r32)
+    with pytest.raises(ValueError, match="one form"):
+        net.forward(q32, r8)
+    with pytest.raises(ValueError, match="norm_img"):
+        net.forward(q8, r8, norm_img=True)
+    with pytest.raises(ValueError, match="norm_img"):
+        net(q8, r8, False, 0, True)  # the fifth positional argument of forward is norm_img, whatever the form
+    assert net._handle is None

@@ -157,14 +157,14 @@ def test_forwards_fed_from_uint8_are_bit_identical(backbone, dtype):
     r_u8 = stage.batch(refs_u8, size)
     assert net.u8_input_supported(q_u8.images[0], size)
     want = net(q32, r32, True, 3, False, return_mean=True)
-    got = net.forward_u8(q_u8, r_u8, True, 3, True)
+    got = net.forward(q_u8, r_u8, True, 3, return_mean=True)
     torch.cuda.synchronize()
     for k in ("score_map_ref_cross", "score_mean_ref_cross", "attn_weights_map_ref_cross"):
         assert torch.equal(got[k], want[k]), k
     tok32 = net.encode_references(r32.reshape((B * N, 3) + size))
-    tok_u8 = net.encode_references_u8(r_u8)
+    tok_u8 = net.encode_references(r_u8)
     assert torch.equal(tok_u8, tok32)
-    cached = net.forward_cached_u8(q_u8, tok_u8.reshape((B, N) + tuple(tok_u8.shape[1:])), False, 0, True)
+    cached = net.forward_cached(q_u8, tok_u8.reshape((B, N) + tuple(tok_u8.shape[1:])), False, 0, True)
     torch.cuda.synchronize()
     assert torch.equal(cached["score_map_ref_cross"], want["score_map_ref_cross"]) and torch.equal(cached["score_mean_ref_cross"], want["score_mean_ref_cross"])
     stats = net.forward_stats()
@@ -173,7 +173,7 @@ def test_forwards_fed_from_uint8_are_bit_identical(backbone, dtype):
     # later the same call rebuilds what it needs and gives the same bits
     for k in range(70):
         net.u8_input_supported(U8Image(None, 200 + k, 260, (70 + 14 * (k % 3), 98), 0, 0), (70, 98), dev)
-    again = net.forward_u8(q_u8, r_u8, True, 3, True)
+    again = net.forward(q_u8, r_u8, True, 3, return_mean=True)
     torch.cuda.synchronize()
     assert torch.equal(again["score_map_ref_cross"], want["score_map_ref_cross"])
     # a 114 x down-scale: 14 pixel rows reach 1 800 source rows, more than the launch holds for even one patch per run (1 170)

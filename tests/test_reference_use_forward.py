@@ -199,14 +199,14 @@ def test_every_entry_point_and_any_depth_give_the_same_bits(dtype):
     tokens = net.encode_references(r)
     _same(net.forward_cached(q, tokens.view(B, N, *tokens.shape[1:]), need_reference_use=True), want, keys)
     assert net.u8_input_supported(stage.describe(raw_q[0]), size)
-    _same(net.forward_u8(u8(raw_q), u8(raw_r), need_reference_use=True), want, keys)
-    _same(net.forward_cached_u8(u8(raw_q), tokens.view(B, N, *tokens.shape[1:]), need_reference_use=True), want, keys)
+    _same(net.forward(u8(raw_q), u8(raw_r), need_reference_use=True), want, keys)
+    _same(net.forward_cached(u8(raw_q), tokens.view(B, N, *tokens.shape[1:]), need_reference_use=True), want, keys)
     # select: whatever it chooses, the outputs are those of the cached forward on the chosen rows
     mean, centre, unit = net.reference_descriptors(tokens)
     bank = SelectionBank(tokens, mean, centre, unit, N)
     sel = net.forward_select(q, bank, need_reference_use=True)
     _same(sel, net.forward_cached(q, bank.tokens[sel["reference_index"].long()], need_reference_use=True), keys)
-    _same(net.forward_select_u8(u8(raw_q), bank, need_reference_use=True), sel, keys + ("reference_index",))
+    _same(net.forward_select(u8(raw_q), bank, need_reference_use=True), sel, keys + ("reference_index",))
     for depth in (1, 3):
         pipe = ForwardPipeline(net, depth=depth)
         tickets = [pipe.submit(q, r.view(B, N, 3, *size), need_reference_use=True) for _ in range(4)]

@@ -74,3 +74,28 @@ def test_item_paths_collates_references_slot_major():
     assert paths["query/img"] == ["q0", "q1"] and paths["query/score_map"] == ["m0", "m1"]
     assert paths["reference/cross/imgs"] == [["r0", "r3"], ["r1", E], ["r2", "r4"]]  # N lists of B paths, as default_collate gives
     assert csdata.item_paths([_item("q0", ())])["reference/cross/imgs"] == []
+
+
+def test_decode_items_reads_extras_with_their_reader(monkeypatch):
+    read8, read16 = [], []
+    monkeypatch.setattr(csdata, "read_image_u8", lambda p: read8.append(p) or ("img", p))
+    monkeypatch.setattr(csdata, "read_metric_map_u16", lambda p: read16.append(p) or ("map", p))
+
+    def extra(it):  # as in test_plan_decodes_extra_follows_its_item, and q3 names r2 -- one of its own references -- as an 8-bit extra
+        if it["query/img"] == "q1":
+            return []
+        return [(it["query/score_map"], True)] + ([("g2", False)] if it["query/img"] == "q2" else []) + ([("r2", False)] if it["query/img"] == "q3" else [])
+
+    decoded = csdata.decode_items(BATCHES[0], extra=extra)
+    assert read16 == ["m0"] and read8 == ["q0", "r0", "r1", "r2", "q1", "r3", "r4"]  # 16-bit entries to the map reader, the rest to the image reader
+    assert list(decoded) == ["q0", "r0", "r1", "r2", "m0", "q1", "r3", "r4"] and decoded["m0"] == ("map", "m0") and decoded["r2"] == ("img", "r2")
+    del read8[:], read16[:]
+    decoded = csdata.decode_items(BATCHES[1], extra=extra)
+    assert read16 == ["m2", "m3"] and read8 == ["q2", "r5", "r6", "r7", "g2", "q3", "r2", "r8", "r9"]  # r2: reference and extra, read once
+    assert len(decoded) == len(read8) + len(read16)
+    del read8[:], read16[:]
+    decoded = csdata.decode_items(BATCHES[1], skip={"r2", "r8"}, extra=extra)  # a skipped reference that is also an extra is still read
+    assert read16 == ["m2", "m3"] and read8 == ["q2", "r5", "r6", "r7", "g2", "q3", "r9", "r2"]
+    assert decoded["r2"] == ("img", "r2") and "r8" not in decoded
+    del read8[:], read16[:]
+    assert list(csdata.decode_items(BATCHES[0], zero_reference=True, extra=extra)) == ["q0", "m0", "q1"] and read16 == ["m0"] and read8 == ["q0", "q1"]

@@ -167,7 +167,7 @@ def test_entry_points_and_batches_in_flight_give_the_same_bits(dtype):
             tickets = []
             for b, g in list(zip(batches, groups)) * 2:
                 if u8:
-                    tickets.append(pipe.submit_select_u8(stage.batch([stage.describe(im) for im in b], size), bank, ex, True, 2, True, group=g))
+                    tickets.append(pipe.submit_select(stage.batch([stage.describe(im) for im in b], size), bank, ex, True, 2, True, group=g))
                 else:
                     tickets.append(pipe.submit_select(f32(b), bank, ex, True, 2, True, group=g))
             outs = [pipe.result(t) for t in tickets]

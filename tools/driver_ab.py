@@ -1,6 +1,6 @@
-"""A/B of the predict and evaluate drivers of two source trees, same box: do both trees write the same bytes and return the same results?
+"""A/B of the predict, evaluate and fit_head drivers of two source trees, same box: do both trees write the same bytes and return the same results?
 
-usage: driver_ab.py <parent tree> <new tree> [--jobs N] [--only predict|evaluate] [--match TEXT] [--drop-result-key KEY ...]
+usage: driver_ab.py <parent tree> <new tree> [--jobs N] [--only predict|evaluate|fit_head] [--match TEXT] [--drop-result-key KEY ...]
 
 Each tree is a checkout with its own built library (the parent e.g. as a `git worktree`).  The input trees are generated once (the geometry of the
 driver tests: 5 queries and 4 references of 70 x 90 -> 56 x 72, batch 2, ViT-S two-layer synthetic weights; tests/nvs_tree.py for evaluate).  One
@@ -10,7 +10,11 @@ case directory; the long values -- files, rows, batches, metrics -- as a count a
 
 predict:  cache on / off x fused_input_stage auto / False x png_decoder host / gpu x batches_in_flight 1 / 3; every writer flag on; JPEG queries
           with jpeg_decoder=gpu; neighbour strategy similar over input stage, decoder and batches in flight.
-evaluate: cache x fused x png_decoder x gt_metric_maps files / compute x shuffle on / off; limit_test_batches=2.
+          reference_use with its images, score_pool, vis_sheet: each over fused_input_stage auto / False.
+evaluate: cache x fused x png_decoder x gt_metric_maps files / compute x shuffle on / off; limit_test_batches=2; neighbour strategy similar,
+          score_pool, vis_sheet: each over fused_input_stage auto / False.
+fit_head: the overrides of tests/test_headfit_driver.py, two epochs; token cache on / off, gt_metric_maps files / compute.  Its digest is over
+          fit_head.csv, the tensors of checkpoints/last.ckpt (not the file: a pickle) and the result dictionary.
 
 --match keeps the cases whose name holds TEXT; --drop-result-key leaves a key out of both trees' result dictionaries (one that only the new
 tree reports, e.g. reference_strategy: profiles/r15_reference_selection.txt).
@@ -48,7 +52,14 @@ back = [o.split("=", 1)[1] for o in overrides if o.startswith("model.backbone.fr
 sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(CrossScoreNet(model_config(**{"backbone.from_pretrained": back})).arch, 6).items()}
 np.random.seed(0)
 with torch.no_grad():
-    if driver == "predict":
+    if driver == "fit_head":
+        from crossscore_amd.fit_head import fit_head
+        res = fit_head(load_config("default_fit_head", overrides + ["logger.train.out_dir=" + os.path.join(case_dir, "out")]), state_dict=sd, now="T")
+        ckpt = torch.load(res["checkpoint"], map_location="cpu", weights_only=False)["state_dict"]
+        with open(res["checkpoint"], "wb") as f:  # the digest below then covers the tensors, key by key
+            for k in sorted(ckpt):
+                f.write(k.encode() + b"\0" + str(ckpt[k].dtype).encode() + str(tuple(ckpt[k].shape)).encode() + ckpt[k].contiguous().numpy().tobytes())
+    elif driver == "predict":
         from crossscore_amd.predict import predict
         res = predict(load_config("default_predict", overrides + ["logger.predict.out_dir=" + os.path.join(case_dir, "out")]), state_dict=sd, now="T")
     else:
@@ -62,14 +73,15 @@ for d, ds, fs in os.walk(case_dir):
         h.update(os.path.relpath(p, case_dir).encode() + b"\0" + open(p, "rb").read() + b"\0")
         n += 1
 rel = lambda v: os.path.relpath(v, case_dir) if os.path.isabs(v) else v
-res.pop("query_images_per_sec")
+res.pop("query_images_per_sec", None)
 for k in drop:
     res.pop(k, None)
-res["files"] = sorted(rel(f) for f in res["files"])
-for k in ("out_dir", "version_dir"):
+if "files" in res:
+    res["files"] = sorted(rel(f) for f in res["files"])
+for k in ("out_dir", "version_dir", "csv", "checkpoint"):
     if k in res:
         res[k] = rel(res[k])
-for k in ("files", "rows", "batches", "metrics"):
+for k in ("files", "rows", "batches", "metrics", "losses"):
     if k in res:
         res[k] = "%d:%s" % (len(res[k]), hashlib.sha256(repr(res[k]).encode()).hexdigest()[:16])
 print("%d files %s %s" % (n, h.hexdigest()[:32], json.dumps(res, sort_keys=True)))
@@ -121,6 +133,20 @@ def cases(pred, ev, jpeg_dir):
         yield "evaluate", f"evaluate cache={c} fused={f} png_decoder={d} gt_metric_maps={gt} shuffle={shuffle}", \
             ev + knobs(c, f, d) + [f"this_main.gt_metric_maps={gt}", f"data.loader.validation.shuffle={shuffle}"]
     yield "evaluate", "evaluate limit_test_batches=2", ev + ["trainer.limit_test_batches=2"]
+    # what the scoring run has learnt since: each over both input stages (vis_sheet keeps auto on the two-launch stage)
+    ev_no_imgs = [o.replace(".predict.", ".test.") for o in no_imgs]
+    for f in ("auto", False):
+        fused = [f"this_main.fused_input_stage={f}"]
+        yield "predict", f"predict reference_use + images fused={f}", pred + no_imgs + fused + ["this_main.reference_use=True", "this_main.reference_use_images=True"]
+        for key in ("score_pool", "vis_sheet"):
+            yield "predict", f"predict {key} fused={f}", pred + no_imgs + fused + [f"this_main.{key}=True"]
+            yield "evaluate", f"evaluate {key} fused={f}", ev + ev_no_imgs + fused + [f"this_main.{key}=True"]
+        yield "evaluate", f"evaluate strategy=similar fused={f}", ev + ev_no_imgs + fused + \
+            ["data.neighbour_config.strategy=similar", "data.neighbour_config.cross=2", "logger.test.write.flag.item_path_json=True"]
+    fit = [o for o in ev if not o.startswith("data.loader.validation.")] + ["data.loader.train.batch_size=4", "data.loader.train.num_workers=2",
+                                                                         "trainer.max_epochs=2", "trainer.lr_scheduler.step_size=1", "trainer.lr_scheduler.gamma=0.5"]
+    for c, gt in ((True, "files"), (False, "files"), (True, "compute")):
+        yield "fit_head", f"fit_head cache={c} gt_metric_maps={gt}", fit + [f"this_main.cache_reference_tokens={c}", f"this_main.gt_metric_maps={gt}"]
 
 
 def main():
@@ -128,7 +154,7 @@ def main():
     ap.add_argument("parent")
     ap.add_argument("new")
     ap.add_argument("--jobs", type=int, default=1, help="children running side by side (each opens the GPU: keep it small)")
-    ap.add_argument("--only", choices=("predict", "evaluate"))
+    ap.add_argument("--only", choices=("predict", "evaluate", "fit_head"))
     ap.add_argument("--match", help="only the cases whose name holds this text")
     ap.add_argument("--drop-result-key", action="append", default=[], help="a result key to leave out of the comparison (reported by one tree only)")
     args = ap.parse_args()

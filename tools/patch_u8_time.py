@@ -36,7 +36,7 @@ for (h, w) in ((540, 720), (518, 518), (1080, 1440)):
                                            C.c_void_p(buf[i].data_ptr()), C.c_void_p(scratch.data_ptr()) if rs != (h, w) else None,
                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     def one():
-        return net.encode_references_u8(ub)
+        return net.encode_references(ub)
     assert torch.equal(two(), one())
     for name, f in (("two-launch stage + patch embedding", two), ("one-pass (uint8 in, tokens out)", one)) * 2:
         for _ in range(3): f()
