@@ -197,6 +197,18 @@ SYMBOLS = {
     "cs_debug_head_inputs": (_i, [_vp, _vp, _vp, _i, _vp]),
     "cs_op_adamw": (_i, [_vp, _vp, _vp, _vp, _ll, _f, _f, _f, _f, _f, _i, _vp, _vp]),
     "cs_set_head_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    # tail fit (csrc/tailfit.hip)
+    "cs_tail_fit_supported": (_i, [_i, _i]),
+    "cs_tail_fit_ln_row_tile": (_i, []),
+    "cs_ln_backward_workspace_bytes": (_sz, [_i, _i]),
+    "cs_tail_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "cs_op_ln_backward": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _f, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cs_op_tail_backward": (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f,
+                                 C.c_double, _i] + [_vp] * 13),
+    "cs_fit_tail_keep": (_i, [_vp, _i]),
+    "cs_tail_backward": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _i] + [_vp] * 12),
+    "cs_debug_tail_inputs": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "cs_set_tail_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -120,6 +120,7 @@ void cs_destroy(cs_handle h) {
   reap_retired(h, true);
   if (h->ws) hipFree(h->ws);
   if (h->hfit_ws) hipFree(h->hfit_ws);
+  if (h->tail_kept) hipFree(h->tail_kept);
   if (h->ev_done) hipEventDestroy(h->ev_done);
   if (h->ev_kv0) hipEventDestroy(h->ev_kv0);
   if (h->ev_kv1) hipEventDestroy(h->ev_kv1);
@@ -357,7 +358,7 @@ int cs_finalize(cs_handle h) {
 }
 
 // What the last forward-class call on this handle launched, and what it cost the host: `launches` = kernel launches (memcpy taps of capture
-// mode not counted), `host_ms` = wall time of the call on the calling thread (everything is enqueued, nothing waited for), `names` (optional,
+// mode not counted; the two copies of cs_fit_tail_keep counted as tail_keep=2), `host_ms` = wall time of the call on the calling thread (everything is enqueued, nothing waited for), `names` (optional,
 // `names_bytes` long) = "kernel=count kernel=count ..." by kernel: gemm256 / gemm128 (cs_gemm256_kernel / cs_gemm_kernel), attn<dh>, panel,
 // rowln, patch, im2col, ln1 / ln2 / ln (layernorm_kernel), cls, final_ln, score_check, ...
 int cs_forward_stats(cs_handle h, int* launches, double* host_ms, char* names, size_t names_bytes) {
@@ -489,6 +490,39 @@ int cs_set_head_weights(cs_handle h, const float* w0, const float* b0, const flo
   HIPCHK(cs_pack_f16_launch(w2, PP, C, h->Wh2, C, nullptr, nullptr, h->cfg.operand_dtype, st));
   HIPCHK(hipMemcpyAsync(h->bh0, b0, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(h->bh2, b2, (size_t)PP * 4, hipMemcpyDeviceToDevice, st));
+  if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(h->ev_done, st));
+  h->last_stream = st;
+  return 0;
+}
+
+// Tail fit: a persistent switch like cs_debug_capture, off by default.  With it on, every forward that runs the decoder
+// keeps the last layer's norm2 output and its ReLU rows (two stream-ordered copies) for cs_tail_backward; nothing else of the forward changes.
+int cs_fit_tail_keep(cs_handle h, int on) {
+  if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
+  h->tail_keep = on != 0;
+  return 0;
+}
+
+// The six changed tensors of the last decoder layer's feed-forward block and norm3 back into the finalised handle: w1 / w2 (C, C) re-packed into
+// the layer's existing operand buffers, the biases and norm3's weight and bias copied, on `stream`, behind the handle's last call.
+int cs_set_tail_weights(cs_handle h, const float* w1, const float* b1, const float* w2, const float* b2, const float* g3, const float* b3,
+                        cs_stream stream) {
+  if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
+  if (!h->finalized) return fail(CS_ERR_STATE, "cs_set_tail_weights before cs_finalize");
+  if (h->dec.empty()) return fail(CS_ERR_STATE, "cs_set_tail_weights: the handle has no decoder layer");
+  if (!w1 || !b1 || !w2 || !b2 || !g3 || !b3) return fail(CS_ERR_BAD_ARG, "cs_set_tail_weights: null pointer");
+  if (((uintptr_t)w1 | (uintptr_t)b1 | (uintptr_t)w2 | (uintptr_t)b2 | (uintptr_t)g3 | (uintptr_t)b3) & 3) return fail(CS_ERR_BAD_ARG, "cs_set_tail_weights: misaligned pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const int C = h->cfg.hidden;
+  const DecLayer& D = h->dec.back();
+  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
+  HIPCHK(cs_pack_f16_launch(w1, C, C, D.l1W, C, nullptr, nullptr, h->cfg.operand_dtype, st));
+  HIPCHK(cs_pack_f16_launch(w2, C, C, D.l2W, C, nullptr, nullptr, h->cfg.operand_dtype, st));
+  HIPCHK(hipMemcpyAsync(D.l1b, b1, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(D.l2b, b2, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(D.n3g, g3, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(D.n3b, b3, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
   if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
   HIPCHK(hipEventRecord(h->ev_done, st));
   h->last_stream = st;

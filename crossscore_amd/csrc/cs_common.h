@@ -319,6 +319,25 @@ struct CsHeadBackward {
   float *dWa, *dba, *dWb, *dbb; double* loss;
 };
 
+// Tail fit (tailfit.hip): the last decoder layer's linear1 -> ReLU -> linear2 -> + residual -> norm3 in front of the head.
+#define CS_TAILFIT_LN_ROW_TILE 32  // rows of one workgroup of ln_backward (8 waves x 4 rows, or 4 x 8 for C > 512) = rows of one fp32 partial of d gamma / d beta
+struct CsLnBackward {
+  const float* y; int ldy;      // [M][ldy] fp32 rows the LayerNorm normalised
+  const float* dx; int ldx;     // [M][ldx] fp32 gradient of the LayerNorm's output
+  const float* gamma; float eps;
+  int M, C; float scale; int accumulate;
+  h16_t* dyh; int ldd;          // [M][ldd] gradient of y, rounded once to the operand type
+  float *dgamma, *dbeta;        // [C] each: (accumulate ? old : 0) + scale * (sum_m dx * xhat | sum_m dx)
+};
+struct CsTailBackward {
+  const float* x2;              // [M][C] fp32, contiguous: the last layer's norm2 output
+  const h16_t* H; int ldh;      // [M][ldh] relu(linear1(x2)) as the forward stored it
+  const h16_t* W2; int ldw2; const float* b2; const float* gamma3; float eps;  // linear2 (packed) and norm3's weight
+  const h16_t* Wa; int ldwa;    // the head's first linear (packed)
+  CsHeadBackward head;          // X, A, Wb, bb, gt, shapes, inv_count, accumulate, the head's four gradients and the loss
+  float *dW1, *db1, *dW2, *db2, *dg3, *db3;
+};
+
 // ---- The launch surface between the kernel files and the host files (api.hip, forward.hip, ops.hip): every cs_*_launch / cs_*_check /
 // cs_*_supported / size helper that one .hip defines and another calls, declared ONCE.  Every defining file includes this header, so a changed
 // parameter list fails to compile there instead of linking (most of these are extern "C") and misbehaving at run time. ----
@@ -445,6 +464,14 @@ size_t cs_head_backward_workspace(int M, int C);
 hipError_t cs_head_grad_z_launch(const CsHeadGradZ* p, void* ws, int bf, hipStream_t st);
 hipError_t cs_gemm_tn_launch(const CsGemmTn* p, void* ws, int bf, hipStream_t st);
 hipError_t cs_head_backward_launch(const CsHeadBackward* p, void* ws, int bf, hipStream_t st);
+size_t cs_head_backward_dpre_offset(int M);  // where cs_head_backward_launch leaves dpre (M, C; 16 bit, rounded once) in its workspace
+// out (cols, ldo) = src (rows, lds)^T in 16 bits, zeros in the columns [rows, ldo)
+hipError_t cs_transpose16_launch(const h16_t* src, int lds, int rows, int cols, h16_t* out, int ldo, hipStream_t st);
+// tailfit.hip
+size_t cs_ln_backward_workspace(int M, int C);
+size_t cs_tail_backward_workspace(int M, int C);
+hipError_t cs_ln_backward_launch(const CsLnBackward* p, void* ws, int bf, hipStream_t st);
+hipError_t cs_tail_backward_launch(const CsTailBackward* p, void* ws, int bf, hipStream_t st);
 hipError_t cs_adamw_launch(float* p, float* m, float* v, const float* g, long long n, float lr, float beta1, float beta2, float eps, float wd,
                            int step, h16_t* p16, int bf, hipStream_t st);
 }

@@ -124,9 +124,13 @@ struct cs_model {
   };
   RefUse ref_use;
   // head fit (cs_head_backward): what the last forward-class call left behind, and the backward's own workspace
-  struct LastForward { bool ok = false; int mode = -1, B = 0, H = 0, W = 0; const float* xq = nullptr; const h16_t* dhid = nullptr; };
+  struct LastForward { bool ok = false; int mode = -1, B = 0, H = 0, W = 0; const float* xq = nullptr; const h16_t* dhid = nullptr; bool tail_kept = false; };
   LastForward last_fwd;
-  void* hfit_ws = nullptr; size_t hfit_ws_bytes = 0;  // X in 16 bits (M, C), then cs_head_backward_workspace
+  void* hfit_ws = nullptr; size_t hfit_ws_bytes = 0;  // X in 16 bits (M, C), then cs_head_backward_workspace (cs_tail_backward_workspace once the tail is fitted)
+  // tail fit (cs_fit_tail_keep): with the switch on every forward copies the last layer's norm2 output x2 (M, C) fp32 and H = relu(linear1(x2))
+  // (M, C) 16 bit into this region, between the two closings of that layer
+  bool tail_keep = false;
+  void* tail_kept = nullptr; size_t tail_kept_bytes = 0;
   unsigned* nonfinite = nullptr;  // device counter: non-finite score-map values seen since the last cs_nonfinite_count
   // profiling
   bool prof = false;
@@ -196,6 +200,8 @@ inline bool supported_dh(int dh) { return dh == 16 || dh == 48 || dh == 64 || dh
 
 // ops.hip: the checks of a head backward, then its launches
 int head_backward_run(const char* op, const CsHeadBackward& q, void* ws, int bf, hipStream_t st);
+// ops.hip: the same for the tail's backward (the head's is its first part)
+int tail_backward_run(const char* op, const CsTailBackward& q, void* ws, int bf, hipStream_t st);
 
 // forward.hip
 void reap_retired(cs_model* m, bool all);                        // frees retired workspaces whose last use has completed (never blocks unless `all`)

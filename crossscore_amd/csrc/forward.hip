@@ -273,6 +273,7 @@ struct Fwd {
   // (decoder) each sub-block closes with LN(x + Linear(.)): one launch where the row-complete kernel is built (C = 384), else GEMM + LayerNorm
   // ... and where it is, the sub-block's NEXT linear rides in the same launch when it is C wide (second stage of rowln.hip)
   bool fused_ln = false, fuse_next = false;
+  bool tail_kept = false;  // (cs_fit_tail_keep) this call has queued the two copies cs_tail_backward works on
 
   // ---- step 1: arguments ----
   int validate() {
@@ -723,6 +724,29 @@ struct Fwd {
     L.small("ref_use", [&] { return cs_refuse_launch(&r, dh, L.st); });
   }
 
+  // cs_fit_tail_keep: between the norm2 and the norm3 closing of the last layer p.xq holds x2 and p.dhid holds
+  // H = relu(linear1(x2)); both are overwritten by the time the forward returns, so they are copied into the handle's own region here
+  // (M C fp32, then M C 16 bit), which grows like the workspace does.
+  int keep_tail(hipStream_t s) {
+    const size_t M = (size_t)B * p.Np, xb = (M * p.C * 4 + 255) & ~size_t(255), need = xb + M * p.C * 2;
+    if (need > h->tail_kept_bytes) {
+      if (h->tail_kept) {
+        cs_model::Retired r{h->tail_kept, nullptr};
+        HIPCHK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(r.ev, s));
+        h->retired.push_back(r);
+      }
+      h->tail_kept = nullptr; h->tail_kept_bytes = 0;
+      HIPCHK(hipMalloc(&h->tail_kept, need));
+      h->tail_kept_bytes = need;
+    }
+    HIPCHK(hipMemcpyAsync(h->tail_kept, p.xq, M * p.C * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(static_cast<char*>(h->tail_kept) + xb, p.dhid, M * p.C * 2, hipMemcpyDeviceToDevice, s));
+    h->census["tail_keep"] += 2;
+    tail_kept = true;
+    return 0;
+  }
+
   // The decoder runs as ONE group on the caller's stream, after the join: its kernels are small, and splitting the batch over streams only
   // makes them smaller (cfg-2, tools/dec_lanes.py: 1 group 8.77 ms, 2 groups 8.80, 3 groups 8.79, 4 groups 9.31).  Decoding each chunk's
   // items on its lane right after encoding them (no global join) was measured SLOWER too (833 vs 875 query-images/s on cfg-2): it doubles the
@@ -773,6 +797,7 @@ struct Fwd {
       if (want_use) reference_use(L, a, dec_dh);
       if (!dec_close(L, p.dob, D.ca_Wo, D.ca_bo, shortcut, D.n2g, D.n2b, "norm2", next_of(D.l1W, D.l1b, p.dhid, 1)))
         L.gemm(gp(p.q_bf, C, D.l1W, C, M, C, C, D.l1b, p.dhid, C), CS_EPI_BIAS_RELU_F16);
+      if (last_l && h->tail_keep && !L.rc) L.rc = keep_tail(s);
       // behind norm3: the head's first linear (its hidden rows replace linear1's in dhid: a workgroup writes exactly the 64 rows it staged into
       // LDS at its start), or -- without self-attention -- the next layer's Q projection
       NextLinear next{};
@@ -848,7 +873,7 @@ int forward_impl(Fwd f) {
   const int rc = f.body();
   if (f.u8) cs_preprocess_tables_hold(0);
   // what cs_head_backward works on: the tokens behind the last norm3 and the head's hidden rows of THIS call (f.p: the plan body() carved)
-  h->last_fwd = cs_model::LastForward{rc == 0, f.mode, f.B, f.H, f.W, f.p.xq, f.p.dhid};
+  h->last_fwd = cs_model::LastForward{rc == 0, f.mode, f.B, f.H, f.W, f.p.xq, f.p.dhid, f.tail_kept};
   h->host_enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
   HIPCHK(hipEventRecord(h->ev_done, f.st));
@@ -950,7 +975,8 @@ int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const ui
 // The closing launch of the decoder writes the normalised rows in fp32 (p.xq) and, where the head's first linear rides along (rowln.hip), no
 // 16-bit copy: X is rounded here from p.xq, the rounding the forward's own operand went through.  The workspace of the backward is the
 // handle's own allocation (X, then cs_head_backward_workspace), grown like the forward's.
-static int head_fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, const char* op, int* M_out, h16_t** X_out) {
+// `tail`: the call is the tail's -- the last forward must have kept x2 and H, and the workspace is the tail backward's.
+static int head_fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, const char* op, int* M_out, h16_t** X_out, bool tail = false) {
   if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
   if (!h->finalized) return fail(CS_ERR_STATE, "%s before cs_finalize", op);
   const cs_model::LastForward& lf = h->last_fwd;
@@ -960,8 +986,11 @@ static int head_fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, con
     return fail(CS_ERR_STATE, "%s: the last forward ran (B %d, H %d, W %d), this call names (%d, %d, %d)", op, lf.B, lf.H, lf.W, B, H, W);
   const cs_config& c = h->cfg;
   if (!cs_headfit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden a multiple of 64 and patch 14 (hidden %d, patch %d)", op, c.hidden, c.patch);
+  if (tail && !cs_tail_fit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden <= 2048 (hidden %d)", op, c.hidden);
+  if (tail && !lf.tail_kept) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_tail_keep off", op);
   const int M = lf.B * (lf.H / c.patch) * (lf.W / c.patch), C = c.hidden;
-  const size_t xbytes = ((size_t)M * C * 2 + 255) & ~size_t(255), need = xbytes + cs_head_backward_workspace(M, C);
+  const size_t xbytes = ((size_t)M * C * 2 + 255) & ~size_t(255),
+               need = xbytes + (tail ? cs_tail_backward_workspace(M, C) : cs_head_backward_workspace(M, C));
   if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
   if (need > h->hfit_ws_bytes) {
     if (h->hfit_ws) {
@@ -1023,6 +1052,56 @@ int cs_debug_head_inputs(cs_handle h, uint16_t* X_out, uint16_t* A_out, int rows
   const size_t bytes = (size_t)M * h->cfg.hidden * 2;
   if (X_out) HIPCHK(hipMemcpyAsync(X_out, X, bytes, hipMemcpyDeviceToDevice, st));
   if (A_out) HIPCHK(hipMemcpyAsync(A_out, h->last_fwd.dhid, bytes, hipMemcpyDeviceToDevice, st));
+  return head_fit_done(h, st);
+}
+
+// ---- tail fit: the same over the last layer's feed-forward block, norm3 and the head, on what a forward with
+// cs_fit_tail_keep left behind ----
+int cs_tail_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dW1, float* db1, float* dW2,
+                     float* db2, float* dg3, float* db3, float* dWa, float* dba, float* dWb, float* dbb, double* loss, cs_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (B <= 0) return fail(CS_ERR_BAD_ARG, "cs_tail_backward: empty batch");
+  uintptr_t bits = (uintptr_t)gt;
+  for (const float* o : {dW1, db1, dW2, db2, dg3, db3, dWa, dba, dWb, dbb}) {
+    if (!o) return fail(CS_ERR_BAD_ARG, "cs_tail_backward: null pointer");
+    bits |= (uintptr_t)o;
+  }
+  if (!gt || !loss) return fail(CS_ERR_BAD_ARG, "cs_tail_backward: null pointer");
+  if ((bits & 3) || ((uintptr_t)loss & 7)) return fail(CS_ERR_BAD_ARG, "cs_tail_backward: misaligned pointer (fp32 4 bytes, the loss 8)");
+  if (!(inv_count > 0.0)) return fail(CS_ERR_BAD_ARG, "cs_tail_backward: inv_count must be positive");
+  if (h && h->cfg.act == 1 && h->cfg.pow_p != 1.0f) return fail(CS_ERR_UNSUPPORTED, "cs_tail_backward: tanh with a power factor other than 1 is not built");
+  int M = 0; h16_t* X = nullptr;
+  if (h && h->finalized && h->dec.empty()) return fail(CS_ERR_STATE, "cs_tail_backward: the handle has no decoder layer");
+  if (int r = head_fit_inputs(h, B, H, W, st, "cs_tail_backward", &M, &X, true)) return r;
+  const cs_config& c = h->cfg;
+  const int C = c.hidden;
+  const DecLayer& D = h->dec.back();
+  CsTailBackward q{};
+  q.x2 = static_cast<const float*>(h->tail_kept);
+  q.H = reinterpret_cast<const h16_t*>(static_cast<const char*>(h->tail_kept) + (((size_t)M * C * 4 + 255) & ~size_t(255))); q.ldh = C;
+  q.W2 = D.l2W; q.ldw2 = C; q.b2 = D.l2b; q.gamma3 = D.n3g; q.eps = 1e-5f; q.Wa = h->Wh0; q.ldwa = C;
+  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dg3; q.db3 = db3;
+  CsHeadBackward& hq = q.head;
+  hq.X = X; hq.ldx = C; hq.A = h->last_fwd.dhid; hq.lda = C; hq.Wb = h->Wh2; hq.ldw = C; hq.bb = h->bh2; hq.gt = gt; hq.B = B; hq.gh = H / c.patch;
+  hq.gw = W / c.patch; hq.P = c.patch; hq.C = C; hq.act = c.act; hq.powp = c.pow_p; hq.inv_count = inv_count; hq.accumulate = accumulate != 0;
+  hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb; hq.loss = loss;
+  char* ws = static_cast<char*>(h->hfit_ws) + (((size_t)M * C * 2 + 255) & ~size_t(255));
+  const int rc = tail_backward_run("cs_tail_backward", q, ws, c.operand_dtype, st);
+  if (int r = head_fit_done(h, st)) return r;
+  return rc;
+}
+
+int cs_debug_tail_inputs(cs_handle h, float* x2_out, uint16_t* H_out, int rows, cs_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  int M = 0; h16_t* X = nullptr;
+  if (h && h->finalized && h->last_fwd.ok && h->last_fwd.mode != 2 &&
+      rows != h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch))
+    return fail(CS_ERR_BAD_ARG, "cs_debug_tail_inputs: the last forward left %d rows, the caller names %d",
+                h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch), rows);
+  if (int r = head_fit_inputs(h, 0, 0, 0, st, "cs_debug_tail_inputs", &M, &X, true)) return r;
+  const size_t n = (size_t)M * h->cfg.hidden;
+  if (x2_out) HIPCHK(hipMemcpyAsync(x2_out, h->tail_kept, n * 4, hipMemcpyDeviceToDevice, st));
+  if (H_out) HIPCHK(hipMemcpyAsync(H_out, static_cast<const char*>(h->tail_kept) + ((n * 4 + 255) & ~size_t(255)), n * 2, hipMemcpyDeviceToDevice, st));
   return head_fit_done(h, st);
 }
 

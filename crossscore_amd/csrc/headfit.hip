@@ -105,12 +105,13 @@ __global__ __launch_bounds__(64) void hf_loss_finish_kernel(const double* part, 
   if (threadIdx.x == 0) *loss = (accumulate ? *loss : 0.0) + scale * s;
 }
 
-// WbT (C, HF_NP) = Wb (PP, ldw)^T, zero in the padding columns
-__global__ void hf_transpose_kernel(const h16_t* Wb, int ldw, int PP, int C, h16_t* out) {
+// out (cols, ldo) = src (rows, lds)^T, zero in the padding columns [rows, ldo): the head's WbT (C, HF_NP) from Wb (PP, ldw), and the square
+// weights of the tail's input gradients (tailfit.hip)
+__global__ void hf_transpose_kernel(const h16_t* src, int lds, int rows, int cols, h16_t* out, int ldo) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= C * HF_NP) return;
-  const int c = idx / HF_NP, n = idx - c * HF_NP;
-  out[idx] = n < PP ? Wb[(size_t)n * ldw + c] : (h16_t)0;
+  if (idx >= cols * ldo) return;
+  const int c = idx / ldo, n = idx - c * ldo;
+  out[idx] = n < rows ? src[(size_t)n * lds + c] : (h16_t)0;
 }
 
 // ---- dpre = (g WbT^T) * (A > 0 ? 1 : 0.01): 64 rows x 64 columns per workgroup ----
@@ -285,6 +286,13 @@ size_t cs_head_backward_workspace(int M, int C) {
          cs_gemm_tn_workspace(M, C > HF_NP ? C : HF_NP, C);
 }
 
+size_t cs_head_backward_dpre_offset(int M) { return up256((size_t)M * HF_NP * 2); }
+
+hipError_t cs_transpose16_launch(const h16_t* src, int lds, int rows, int cols, h16_t* out, int ldo, hipStream_t st) {
+  hf_transpose_kernel<<<(cols * ldo + 255) / 256, 256, 0, st>>>(src, lds, rows, cols, out, ldo);
+  return hipGetLastError();
+}
+
 hipError_t cs_head_backward_launch(const CsHeadBackward* q, void* ws, int bf, hipStream_t st) {
   const int M = q->B * q->gh * q->gw, C = q->C, PP = q->P * q->P;
   char* w = static_cast<char*>(ws);
@@ -298,7 +306,7 @@ hipError_t cs_head_backward_launch(const CsHeadBackward* q, void* ws, int bf, hi
   z.act = q->act; z.powp = q->powp; z.g = g; z.ldg = HF_NP; z.loss = q->loss; z.loss_scale = q->inv_count; z.loss_accumulate = q->accumulate;
   hipError_t e = cs_head_grad_z_launch(&z, zws, bf, st);
   if (e != hipSuccess) return e;
-  hf_transpose_kernel<<<(C * HF_NP + 255) / 256, 256, 0, st>>>(q->Wb, q->ldw, PP, C, WbT);
+  hf_transpose_kernel<<<(C * HF_NP + 255) / 256, 256, 0, st>>>(q->Wb, q->ldw, PP, C, WbT, HF_NP);
   const dim3 grid((M + HF_ROWS - 1) / HF_ROWS, C / 64);
   if (bf) head_da_kernel<true><<<grid, 256, 0, st>>>(g, HF_NP, WbT, q->A, q->lda, dpre, C, M, C);
   else head_da_kernel<false><<<grid, 256, 0, st>>>(g, HF_NP, WbT, q->A, q->lda, dpre, C, M, C);

@@ -818,6 +818,79 @@ int cs_op_head_backward(const uint16_t* X, int ldx, const uint16_t* A, int lda, 
   return head_backward_run("head_backward", q, ws, g_op_bf16, (hipStream_t)stream);
 }
 
+// ---- tail fit (tailfit.hip) ----
+// (the head's condition, inside the widths layernorm_kernel -- and with it the forward's decoder -- takes)
+int cs_tail_fit_supported(int hidden, int patch) { return cs_headfit_supported(hidden, patch) && hidden <= 2048; }
+int cs_tail_fit_ln_row_tile(void) { return CS_TAILFIT_LN_ROW_TILE; }
+
+size_t cs_ln_backward_workspace_bytes(int M, int C) {
+  if (M <= 0 || C < 64 || C % 64 || C > 2048) return 0;
+  return cs_ln_backward_workspace(M, C);
+}
+
+size_t cs_tail_backward_workspace_bytes(int M, int C, int P) {
+  if (M <= 0 || !cs_tail_fit_supported(C, P)) return 0;
+  return cs_tail_backward_workspace(M, C);
+}
+
+int cs_op_ln_backward(const float* y, int ldy, const float* dx, int ldx, const float* gamma, int M, int C, float eps, int bf16, float inv_count,
+                      int accumulate, uint16_t* dyh, int ldd, float* dgamma, float* dbeta, void* ws, cs_stream stream) {
+  if (!y || !dx || !gamma || !dyh || !dgamma || !dbeta || !ws) return fail(CS_ERR_BAD_ARG, "ln_backward: null pointer");
+  if (M <= 0) return fail(CS_ERR_BAD_ARG, "ln_backward: empty shape");
+  if (C < 64 || C % 64 || C > 2048 || M > (1 << 22)) return fail(CS_ERR_UNSUPPORTED, "ln_backward: built for C a multiple of 64 in [64, 2048] and M <= 2^22 (M %d, C %d)", M, C);
+  if (ldy < C || ldx < C || ldd < C || ldy % 4 || ldx % 4 || ldd % 4) return fail(CS_ERR_BAD_ARG, "ln_backward: row strides must be multiples of 4 elements and at least C");
+  if (!(eps >= 0.f) || !(inv_count > 0.f)) return fail(CS_ERR_BAD_ARG, "ln_backward: eps must be >= 0 and inv_count positive");
+  if (bf16 != 0 && bf16 != 1) return fail(CS_ERR_BAD_ARG, "ln_backward: bf16 must be 0 or 1");
+  if (misaligned(y, 16) || misaligned(dx, 16) || misaligned(gamma, 16) || misaligned(dyh, 8) || misaligned(dgamma, 4) || misaligned(dbeta, 4) || misaligned(ws, 256))
+    return fail(CS_ERR_BAD_ARG, "ln_backward: misaligned pointer (fp32 rows and gamma 16 bytes, dyh 8, the sums 4, workspace 256)");
+  CsLnBackward p{};
+  p.y = y; p.ldy = ldy; p.dx = dx; p.ldx = ldx; p.gamma = gamma; p.eps = eps; p.M = M; p.C = C; p.scale = inv_count; p.accumulate = accumulate != 0;
+  p.dyh = dyh; p.ldd = ldd; p.dgamma = dgamma; p.dbeta = dbeta;
+  HIPCHK(cs_ln_backward_launch(&p, ws, bf16, (hipStream_t)stream));
+  return 0;
+}
+
+}  // extern "C"
+
+// cs_op_tail_backward and cs_tail_backward (forward.hip) come through here: every check of both backwards first, then the launches
+int cs_host::tail_backward_run(const char* op, const CsTailBackward& q, void* ws, int bf, hipStream_t st) {
+  const CsHeadBackward& hq = q.head;
+  if (int r = head_fit_shape_check(op, hq.A, hq.lda, hq.Wb, hq.ldw, hq.bb, hq.gt, hq.B, hq.gh, hq.gw, hq.P, hq.C, hq.act, hq.powp, ws)) return r;
+  const int C = hq.C;
+  if (!cs_tail_fit_supported(C, hq.P) || (long long)hq.B * hq.gh * hq.gw * C >= (1ll << 31))
+    return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden <= 2048 and fewer than 2^31 token elements; split the batch", op);
+  if (!hq.X || !hq.dWa || !hq.dba || !hq.dWb || !hq.dbb || !hq.loss || !q.x2 || !q.H || !q.W2 || !q.b2 || !q.gamma3 || !q.Wa || !q.dW1 || !q.db1 ||
+      !q.dW2 || !q.db2 || !q.dg3 || !q.db3)
+    return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
+  for (int ld : {hq.ldx, q.ldh, q.ldw2, q.ldwa})
+    if (ld < C || ld % 8) return fail(CS_ERR_BAD_ARG, "%s: row strides must be multiples of 8 elements and at least C", op);
+  if (misaligned(hq.X, 16) || misaligned(q.x2, 16) || misaligned(q.H, 16) || misaligned(q.W2, 16) || misaligned(q.Wa, 16) || misaligned(q.b2, 16) || misaligned(q.gamma3, 16))
+    return fail(CS_ERR_BAD_ARG, "%s: misaligned input (16-bit operands, x2, b2 and gamma 16 bytes)", op);
+  for (const float* o : {hq.dWa, hq.dba, hq.dWb, hq.dbb, q.dW1, q.db1, q.dW2, q.db2, q.dg3, q.db3})
+    if (misaligned(o, 4)) return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
+  if (misaligned(hq.loss, 8)) return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
+  if (!(hq.inv_count > 0.0) || !(q.eps >= 0.f)) return fail(CS_ERR_BAD_ARG, "%s: inv_count must be positive and eps >= 0", op);
+  HIPCHK(cs_tail_backward_launch(&q, ws, bf, st));
+  return 0;
+}
+
+extern "C" {
+
+int cs_op_tail_backward(const float* x2, const uint16_t* H, int ldh, const uint16_t* X, int ldx, const uint16_t* A, int lda, const uint16_t* W2,
+                        int ldw2, const float* b2, const float* gamma3, float eps, const uint16_t* Wa, int ldwa, const uint16_t* Wb, int ldw,
+                        const float* bb, const float* gt, int B, int gh, int gw, int P, int C, int act, float powp, double inv_count,
+                        int accumulate, float* dW1, float* db1, float* dW2, float* db2, float* dg3, float* db3, float* dWa, float* dba,
+                        float* dWb, float* dbb, double* loss, void* ws, cs_stream stream) {
+  CsTailBackward q{};
+  q.x2 = x2; q.H = H; q.ldh = ldh; q.W2 = W2; q.ldw2 = ldw2; q.b2 = b2; q.gamma3 = gamma3; q.eps = eps; q.Wa = Wa; q.ldwa = ldwa;
+  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dg3; q.db3 = db3;
+  CsHeadBackward& hq = q.head;
+  hq.X = X; hq.ldx = ldx; hq.A = A; hq.lda = lda; hq.Wb = Wb; hq.ldw = ldw; hq.bb = bb; hq.gt = gt; hq.B = B; hq.gh = gh; hq.gw = gw; hq.P = P; hq.C = C;
+  hq.act = act; hq.powp = powp; hq.inv_count = inv_count; hq.accumulate = accumulate != 0; hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb;
+  hq.loss = loss;
+  return tail_backward_run("tail_backward", q, ws, g_op_bf16, (hipStream_t)stream);
+}
+
 int cs_op_adamw(float* p, float* m, float* v, const float* g, long long n, float lr, float beta1, float beta2, float eps, float weight_decay,
                 int step, uint16_t* p16, cs_stream stream) {
   if (!p || !m || !v || !g) return fail(CS_ERR_BAD_ARG, "adamw: null pointer");

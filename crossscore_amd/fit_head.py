@@ -1,4 +1,6 @@
-"""python -m crossscore_amd.fit_head: fits the regression head on the device.
+"""python -m crossscore_amd.fit_head: fits the regression head on the device, or with this_main.fit_scope=tail the decoder's
+tail: the last decoder layer's linear1, linear2 and norm3 together with the head, ten tensors (CrossScoreNet.fit_tail_step).
+The default scope is head; the gradient of the tail stops at the last layer's norm2 output, so everything below stays frozen in both scopes.
 
 Walks the nvs.NvsItems of this_main.data_split (default train) with the host loaders and the GT stage of crossscore_amd.evaluate
 (InputStage.metric_maps over the metric-map files, or this_main.gt_metric_maps=compute on a bare tree), geometry as evaluate's, one handle, one
@@ -7,7 +9,8 @@ the positional tables stay as the checkpoint has them (the encoder is frozen in 
 
 Hyperparameters are the reference's keys (config/default.yaml): trainer.optimizer.lr, trainer.lr_scheduler.{step_size, gamma, step_interval}
 (StepLR), trainer.max_epochs, max_steps, limit_train_batches, lightning.seed.  Outputs under logger.train.out_dir: fit_head.csv (epoch, step,
-lr, loss), checkpoints/last.ckpt (load_lightning_checkpoint and both drivers read it) and the returned run summary.  Not built: random crops and
+lr, loss), checkpoints/last.ckpt (the whole state dict; load_lightning_checkpoint and both drivers read it) and the returned run summary
+(with fit_scope).  Not built: random crops and
 augmentation, a validation loop, more than one device, and the one-pass (uint8) input stage and the device decoders in this driver: the queries
 take the fp32 input path; the references go through evaluate's token cache (this_main.cache_reference_tokens, default True), so each reference
 image is encoded once per run and every step after that is a forward_cached."""
@@ -38,7 +41,19 @@ def step_lr(lr0: float, step_size: int, gamma: float, n: int) -> float:
     return lr0 * gamma ** (n // step_size)
 
 
+FIT_SCOPES = ("head", "tail")
+
+
+def fit_scope(cfg) -> str:
+    """this_main.fit_scope: head (default; ref_cross.head.{0,2}) or tail (the last decoder layer's feed-forward block and norm3 as well)"""
+    scope = str(cfg.this_main.get("fit_scope", "head"))
+    if scope not in FIT_SCOPES:
+        raise ValueError(f"this_main.fit_scope={scope}: head | tail")
+    return scope
+
+
 def check_config(cfg) -> None:
+    fit_scope(cfg)
     devices = cfg.trainer.devices
     if (isinstance(devices, (list, tuple)) and len(devices) != 1) or (isinstance(devices, int) and devices != 1):
         raise ValueError(f"trainer.devices={devices}: the head fit runs on one device (gradients are not reduced across GPUs)")
@@ -57,7 +72,7 @@ def check_config(cfg) -> None:
 
 
 def fit_head(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Optional[str] = None) -> Dict[str, object]:
-    """Runs the fit; returns {"out_dir", "csv", "checkpoint", "steps", "epochs", "first_loss", "last_loss", "losses", "gt_metric_maps"}."""
+    """Runs the fit; returns {"out_dir", "csv", "checkpoint", "steps", "epochs", "first_loss", "last_loss", "losses", "gt_metric_maps", "fit_scope"}."""
     check_config(cfg)
     if not torch.cuda.is_available():
         raise RuntimeError("crossscore_amd.fit_head needs a GPU: the head fit has no CPU fallback")
@@ -68,7 +83,11 @@ def fit_head(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     arch = arch_from_cfg(cfg)
     if not _lib.load().cs_head_fit_supported(arch.hidden, arch.patch):  # (before the weights: they would not fit another patch size either)
         raise ValueError(f"the head fit is built for hidden a multiple of 64 and patch 14 (hidden {arch.hidden}, patch {arch.patch})")
+    scope = fit_scope(cfg)
+    if scope == "tail" and not _lib.load().cs_tail_fit_supported(arch.hidden, arch.patch):
+        raise ValueError(f"the tail fit is built for hidden a multiple of 64 up to 2048 and patch 14 (hidden {arch.hidden}, patch {arch.patch})")
     net = build_net(cfg, device, state_dict, "fit_head")
+    fit_step = net.fit_tail_step if scope == "tail" else net.fit_head_step
 
     out_dir = cfg.logger.train.out_dir
     if out_dir is None:
@@ -120,9 +139,9 @@ def fit_head(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
                 if cache is not None:
                     # the encoder is frozen, so a reference's tokens never change: each image of the split is encoded once per run
                     tokens, _ = cache.gather([it["reference/cross/imgs"] for it in its], decoded, size, zero_ref)
-                    losses.append(net.fit_head_step(batch["query/img"], None, gt, state, ref_tokens=tokens))
+                    losses.append(fit_step(batch["query/img"], None, gt, state, ref_tokens=tokens))
                 else:
-                    losses.append(net.fit_head_step(batch["query/img"], batch["reference/cross/imgs"], gt, state))
+                    losses.append(fit_step(batch["query/img"], batch["reference/cross/imgs"], gt, state))
                 rows.append((epoch, state.step, state.lr))
     finally:
         pool.shutdown()
@@ -140,7 +159,7 @@ def fit_head(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     save_lightning_checkpoint(ckpt_path, net)
     return {"out_dir": out_dir, "csv": csv_path, "checkpoint": ckpt_path, "steps": state.step, "epochs": max_epochs, "losses": host,
             "first_loss": host[0] if host else None, "last_loss": host[-1] if host else None, "gt_metric_maps": "compute" if compute_gt else "files",
-            "cache_reference_tokens": cache is not None}
+            "cache_reference_tokens": cache is not None, "fit_scope": scope}
 
 
 def main(argv: Optional[Iterable[str]] = None) -> int:

@@ -238,7 +238,8 @@ class CrossScoreNet(torch.nn.Module):
         self.operand_dtype = str(cfg.model.backbone.get("operand_dtype", "fp16"))
         self._capture = False      # debug taps (debug_capture / debug_read): stage-level parity tests only
         self.finite_check = True   # every forward counts the non-finite values of its score map on the device (~3 us)
-        self._after_sub_batch = None  # fit_head_step's hook behind each sub-batch's forward call (_score)
+        self._after_sub_batch = None  # fit_head_step's / fit_tail_step's hook behind each sub-batch's forward call (_score)
+        self._tail_keep = False    # fit_tail_keep: forwards keep what the tail's backward reads (fit_tail_step turns it on for its call)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._mark_dirty())
 
     # -- weights ----------------------------------------------------------------------------------------------
@@ -335,6 +336,8 @@ class CrossScoreNet(torch.nn.Module):
         self._handle, self._handle_device, self._dirty = h, device, False
         if self._capture:
             _lib.check(lib.cs_debug_capture(h, 1))
+        if self._tail_keep:
+            _lib.check(lib.cs_fit_tail_keep(h, 1))
         return h
 
     # -- forward ----------------------------------------------------------------------------------------------
@@ -753,6 +756,107 @@ class CrossScoreNet(torch.nn.Module):
                                            p.numel(), state.lr, state.betas[0], state.betas[1], state.eps, state.weight_decay, state.step, None,
                                            stream))
             _lib.check(lib.cs_set_head_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params), stream))
+        return loss
+
+    # -- fitting the decoder's tail with the head ----------------------------------------------------
+    @property
+    def TAIL_KEYS(self):
+        """The ten keys of the tail: the last decoder layer's linear1, linear2 and norm3, then the head (the order of cs_tail_backward's
+        gradients)."""
+        p = f"ref_cross.attn.layers.{self.arch.dec_layers - 1}."
+        return tuple(p + k for k in ("linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm3.weight", "norm3.bias")) + self.HEAD_KEYS
+
+    def tail_parameters(self):
+        if not self._do_reference_cross:
+            raise ValueError("model.do_reference_cross=False: this module has no decoder to fit")
+        return [self.get_parameter(k) for k in self.TAIL_KEYS]
+
+    def tail_fit_supported(self) -> bool:
+        return bool(_lib.load().cs_tail_fit_supported(self.arch.hidden, self.arch.patch))
+
+    def fit_tail_keep(self, on: bool = True) -> None:
+        """Following forwards also keep the last decoder layer's norm2 output and ReLU rows (cs_fit_tail_keep): what tail_backward reads."""
+        self._tail_keep = bool(on)
+        if self._handle is not None:
+            _lib.check(_lib.load().cs_fit_tail_keep(self._handle, int(self._tail_keep)))
+
+    def tail_inputs(self, rows: int):
+        """(x2, H): the fp32 output of the last layer's norm2 and the 16-bit rows relu(linear1(x2)) of the last forward call, (rows, C) each
+        (tests); that forward must have run with fit_tail_keep on."""
+        if self._handle is None:
+            raise _lib.CrossScoreHipError("tail_inputs before any forward")
+        dev = self._handle_device
+        with torch.cuda.device(dev):
+            x2 = torch.empty((int(rows), self.arch.hidden), dtype=torch.float32, device=dev)
+            H = torch.empty((int(rows), self.arch.hidden), dtype=self.token_dtype, device=dev)
+            _lib.check(_lib.load().cs_debug_tail_inputs(self._handle, C.c_void_p(x2.data_ptr()), C.c_void_p(H.data_ptr()), int(rows),
+                                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return x2, H
+
+    def tail_backward(self, gt, inv_count=None, accumulate=False, out=None):
+        """cs_tail_backward over the LAST forward call of this module (run with fit_tail_keep on): gt (B, h P, w P) fp32 on the device -> the ten
+        fp32 gradients in TAIL_KEYS order and the fp64 device scalar loss, each scaled by inv_count (default 1 / gt.numel())."""
+        if self._handle is None:
+            raise _lib.CrossScoreHipError("tail_backward before any forward")
+        dev = self._handle_device
+        if gt.dim() != 3 or gt.dtype != torch.float32 or gt.device != dev or not gt.is_contiguous():
+            raise ValueError("expected a contiguous fp32 gt (B, H, W) on the module's device")
+        B, H, W = gt.shape
+        if out is None:
+            out = tuple(torch.zeros(p.shape, device=dev) for p in self.tail_parameters()) + (torch.zeros((), dtype=torch.float64, device=dev),)
+        inv = 1.0 / gt.numel() if inv_count is None else float(inv_count)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().cs_tail_backward(self._handle, C.c_void_p(gt.data_ptr()), B, H, W, inv, int(bool(accumulate)),
+                                                    *(C.c_void_p(t.data_ptr()) for t in out),
+                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
+    def fit_tail_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
+        """fit_head_step over the ten tensors of the tail: the forward with fit_tail_keep on for the call, cs_tail_backward behind each
+        sub-batch, ten cs_op_adamw launches, cs_set_tail_weights and cs_set_head_weights.  Same contract: the module is not marked dirty, the
+        loss of the batch BEFORE the step comes back as a device fp64 scalar, nothing is waited for."""
+        if (refs is None) == (ref_tokens is None):
+            raise ValueError("fit_tail_step takes the references either as images (refs) or as cached tokens (ref_tokens)")
+        if not self.tail_fit_supported():
+            raise ValueError(f"tail fit is built for hidden a multiple of 64 up to 2048 and patch 14 (hidden {self.arch.hidden}, patch {self.arch.patch})")
+        params = self.tail_parameters()
+        dev = gt.device
+        for p in params:
+            if not p.is_cuda or p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("fit_tail_step needs the module's fp32 parameters on the device of the batch (net.to(device))")
+        if gt.dim() != 3 or gt.dtype != torch.float32 or not gt.is_contiguous():
+            raise ValueError("expected a contiguous fp32 gt (B, h P, w P)")
+        state.prepare(params)
+        lib = _lib.load()
+        inv = 1.0 / gt.numel()
+        grads, loss = state.grads, torch.zeros((), dtype=torch.float64, device=dev)
+        H, W = gt.shape[1:]
+
+        def backward(b0, b1):
+            _lib.check(lib.cs_tail_backward(self._handle, C.c_void_p(gt[b0:b1].data_ptr()), b1 - b0, H, W, inv, int(b0 > 0),
+                                            *(C.c_void_p(g.data_ptr()) for g in grads), C.c_void_p(loss.data_ptr()),
+                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+        kept = self._tail_keep
+        self._after_sub_batch = backward
+        try:
+            self._ensure_handle(dev)  # (the forward below finds it ready: the switch goes onto the handle it will use)
+            self.fit_tail_keep(True)
+            res = self.forward_cached(query, ref_tokens) if ref_tokens is not None else self.forward(query, refs)
+        finally:
+            self._after_sub_batch = None
+            self.fit_tail_keep(kept)
+        if tuple(res["score_map_ref_cross"].shape) != tuple(gt.shape):
+            raise ValueError(f"gt {tuple(gt.shape)} does not have the score map's shape {tuple(res['score_map_ref_cross'].shape)}")
+        state.step += 1
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            for p, m, v, g in zip(params, state.m, state.v, grads):
+                _lib.check(lib.cs_op_adamw(C.c_void_p(p.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(g.data_ptr()),
+                                           p.numel(), state.lr, state.betas[0], state.betas[1], state.eps, state.weight_decay, state.step, None,
+                                           stream))
+            _lib.check(lib.cs_set_tail_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[:6]), stream))
+            _lib.check(lib.cs_set_head_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[6:]), stream))
         return loss
 
     # -- debug taps used by the stage-level parity tests (tests/test_hip_stages.py) ------------------------------------

@@ -736,6 +736,47 @@ int cs_op_adamw(float* p, float* m, float* v, const float* g, long long n, float
  * caller's to order. */
 int cs_set_head_weights(cs_handle h, const float* w0, const float* b0, const float* w2, const float* b2, cs_stream stream);
 
+/* ---- Fitting the decoder's tail with the head (csrc/tailfit.hip) ----
+ * The tail is the last decoder layer's linear1 -> ReLU -> linear2 -> + residual -> norm3 and the head behind it: ten tensors.  x2 (M, C) fp32 is
+ * that layer's norm2 output, H (M, C) 16 bit = relu(linear1(x2)) as the forward stored it.  The backward recomputes y = x2 + H W2^T + b2 in fp32
+ * from the packed W2 (the forward never stores its pre-LayerNorm sum), takes mean, rstd and xhat from y two-pass in fp32, and forms
+ *   dX = dpre Wa (fp32; dpre is the head backward's, 16 bit),  dgamma = inv_count sum_m dX xhat,  dbeta = inv_count sum_m dX,
+ *   dy = rstd (gamma dX - mean_c(gamma dX) - xhat mean_c(gamma dX xhat)) rounded once to the operand type,  db2 = inv_count sum_m dy,
+ *   dW2 = inv_count dy^T H,  dH = (dy W2) [H > 0] rounded once,  db1 = inv_count sum_m dH,  dW1 = inv_count dH^T x2 (x2 rounded once).
+ * The gradient stops at x2.  W1, b1 and norm3's bias enter none of the ten gradients, so no entry takes them.  Sums over rows have a fixed order
+ * and there are no atomics; pointer, stride and workspace rules are the head fit's, fp32 ROWS (x2, y, dX) and gamma are 16-byte aligned. */
+/* the head's condition with hidden <= 2048, the widest LayerNorm the forward's decoder runs */
+int cs_tail_fit_supported(int hidden, int patch);
+/* rows per workgroup (= per fp32 partial of dgamma / dbeta) of cs_op_ln_backward, for the tests' edge cases */
+int cs_tail_fit_ln_row_tile(void);
+size_t cs_ln_backward_workspace_bytes(int M, int C);
+size_t cs_tail_backward_workspace_bytes(int M, int C, int P);
+/* LayerNorm backward on rows y (M, ldy) and dX (M, ldx) in fp32: dyh (M, ldd) 16 bit (bf16: 0 IEEE half, 1 bfloat16); dgamma, dbeta (C) =
+ * (accumulate ? itself : 0) + inv_count * its sum.  C a multiple of 64 in [64, 2048]; row strides multiples of 4 elements. */
+int cs_op_ln_backward(const float* y, int ldy, const float* dX, int ldx, const float* gamma, int M, int C, float eps, int bf16, float inv_count,
+                      int accumulate, uint16_t* dyh, int ldd, float* dgamma, float* dbeta, void* ws, cs_stream stream);
+/* the whole backward on caller-owned tensors: x2 contiguous; W2 (C, C), Wa (C, C), Wb (P P, C) packed 16 bit; the six tail gradients dW1 (C, C),
+ * db1, dW2 (C, C), db2, dgamma3, dbeta3 (C) and the head's four, which are bit for bit cs_op_head_backward's on the same X, A, Wb, bb, gt */
+int cs_op_tail_backward(const float* x2, const uint16_t* H, int ldh, const uint16_t* X, int ldx, const uint16_t* A, int lda, const uint16_t* W2,
+                        int ldw2, const float* b2, const float* gamma3, float eps, const uint16_t* Wa, int ldwa, const uint16_t* Wb, int ldw,
+                        const float* bb, const float* gt, int B, int gh, int gw, int P, int C, int act, float powp, double inv_count,
+                        int accumulate, float* dW1, float* db1, float* dW2, float* db2, float* dgamma3, float* dbeta3, float* dWa, float* dba,
+                        float* dWb, float* dbb, double* loss, void* ws, cs_stream stream);
+/* A persistent switch like cs_debug_capture, off by default.  On: every cs_forward* call that runs the decoder also queues two stream-ordered
+ * device-to-device copies (x2 and H, between the two closings of the last decoder layer) into a region the handle owns, allocated on first use;
+ * the score map, the mean and every tap keep their bits.  Off: no launch, copy, allocation or byte of the forward changes. */
+int cs_fit_tail_keep(cs_handle h, int on);
+/* cs_op_tail_backward on what the LAST cs_forward* call on this handle left (with cs_fit_tail_keep on), with the handle's packed weights.
+ * CS_ERR_STATE in the cases of cs_head_backward, and when that forward ran with the switch off. */
+int cs_tail_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dW1, float* db1, float* dW2,
+                     float* db2, float* dgamma3, float* dbeta3, float* dWa, float* dba, float* dWb, float* dbb, double* loss, cs_stream stream);
+/* debug: copies of x2 (rows, C) fp32 and H (rows, C) 16 bit cs_tail_backward would read; either may be NULL; rows as in cs_debug_head_inputs */
+int cs_debug_tail_inputs(cs_handle h, float* x2, uint16_t* H, int rows, cs_stream stream);
+/* Re-packs fp32 device weights of the LAST decoder layer (linear1 and linear2 weight (C, C) and bias (C), norm3 weight and bias (C)) into the
+ * finalised handle's existing buffers, in stream order behind the handle's last call; the race caveat of cs_set_head_weights holds. */
+int cs_set_tail_weights(cs_handle h, const float* w1, const float* b1, const float* w2, const float* b2, const float* g3, const float* b3,
+                        cs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
