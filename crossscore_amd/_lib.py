@@ -209,6 +209,20 @@ SYMBOLS = {
     "cs_tail_backward": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _i] + [_vp] * 12),
     "cs_debug_tail_inputs": (_i, [_vp, _vp, _vp, _i, _vp]),
     "cs_set_tail_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # attention backward (csrc/attnbwd.hip)
+    "cs_attention_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "cs_attention_backward_tiles": (_i, [_i, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "cs_op_attention_backward": (_i, [_vp] * 6 + [_i] * 5 + [_ll] * 5 + [_i] * 5 + [_f, _vp, _i, _ll, _vp, _i, _ll, _vp, _i, _ll, _vp, _vp]),
+    # cross-attention fit (csrc/crossfit.hip)
+    "cs_cross_fit_supported": (_i, [_i, _i, _i]),
+    "cs_cross_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "cs_op_cross_backward": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i,
+                                  _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f,
+                                  C.c_double, _i] + [_vp] * 19),
+    "cs_fit_cross_keep": (_i, [_vp, _i]),
+    "cs_cross_backward": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _i] + [_vp] * 18),
+    "cs_debug_cross_inputs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "cs_set_cross_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

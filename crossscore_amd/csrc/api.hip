@@ -121,6 +121,7 @@ void cs_destroy(cs_handle h) {
   if (h->ws) hipFree(h->ws);
   if (h->hfit_ws) hipFree(h->hfit_ws);
   if (h->tail_kept) hipFree(h->tail_kept);
+  if (h->cross_kept) hipFree(h->cross_kept);
   if (h->ev_done) hipEventDestroy(h->ev_done);
   if (h->ev_kv0) hipEventDestroy(h->ev_kv0);
   if (h->ev_kv1) hipEventDestroy(h->ev_kv1);
@@ -233,6 +234,7 @@ int cs_finalize(cs_handle h) {
     HIPCHK(hipMemcpy(qs_enc, hv.data(), (size_t)C * sizeof(float), hipMemcpyHostToDevice));
     std::fill(hv.begin(), hv.end(), LOG2E / std::sqrt((float)(C / c.dec_heads)));
     HIPCHK(hipMemcpy(qs_dec, hv.data(), (size_t)C * sizeof(float), hipMemcpyHostToDevice));
+    h->qs_dec = qs_dec;
   }
   h->enc.resize(c.enc_layers);
   for (int l = 0; l < c.enc_layers; ++l) {
@@ -358,7 +360,7 @@ int cs_finalize(cs_handle h) {
 }
 
 // What the last forward-class call on this handle launched, and what it cost the host: `launches` = kernel launches (memcpy taps of capture
-// mode not counted; the two copies of cs_fit_tail_keep counted as tail_keep=2), `host_ms` = wall time of the call on the calling thread (everything is enqueued, nothing waited for), `names` (optional,
+// mode not counted; the two copies of cs_fit_tail_keep counted as tail_keep=2, the one more of cs_fit_cross_keep as cross_keep=1), `host_ms` = wall time of the call on the calling thread (everything is enqueued, nothing waited for), `names` (optional,
 // `names_bytes` long) = "kernel=count kernel=count ..." by kernel: gemm256 / gemm128 (cs_gemm256_kernel / cs_gemm_kernel), attn<dh>, panel,
 // rowln, patch, im2col, ln1 / ln2 / ln (layernorm_kernel), cls, final_ln, score_check, ...
 int cs_forward_stats(cs_handle h, int* launches, double* host_ms, char* names, size_t names_bytes) {
@@ -523,6 +525,43 @@ int cs_set_tail_weights(cs_handle h, const float* w1, const float* b1, const flo
   HIPCHK(hipMemcpyAsync(D.l2b, b2, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(D.n3g, g3, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(D.n3b, b3, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
+  if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(h->ev_done, st));
+  h->last_stream = st;
+  return 0;
+}
+
+// Cross-attention fit: a persistent switch that implies cs_fit_tail_keep's copies; in addition the last layer's cross-attention
+// writes its lse and x1 is copied in front of the norm2 closing.  Nothing else of the forward changes.
+int cs_fit_cross_keep(cs_handle h, int on) {
+  if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
+  h->cross_keep = on != 0;
+  return 0;
+}
+
+// The six changed tensors of the last decoder layer's cross-attention block back into the finalised handle, exactly as cs_finalize packs them:
+// rows [0, C) of in_proj into ca_Wq / ca_bq with log2(e) / sqrt(dh) folded in, rows [C, 3C) into the layer's 2C rows of the fused K | V
+// projection, out_proj re-packed, its bias and norm2 copied; on `stream`, behind the handle's last call.
+int cs_set_cross_weights(cs_handle h, const float* in_w, const float* in_b, const float* out_w, const float* out_b, const float* g2, const float* b2,
+                         cs_stream stream) {
+  if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
+  if (!h->finalized) return fail(CS_ERR_STATE, "cs_set_cross_weights before cs_finalize");
+  if (h->dec.empty()) return fail(CS_ERR_STATE, "cs_set_cross_weights: the handle has no decoder layer");
+  if (!in_w || !in_b || !out_w || !out_b || !g2 || !b2) return fail(CS_ERR_BAD_ARG, "cs_set_cross_weights: null pointer");
+  if (((uintptr_t)in_w | (uintptr_t)in_b | (uintptr_t)out_w | (uintptr_t)out_b | (uintptr_t)g2 | (uintptr_t)b2) & 3) return fail(CS_ERR_BAD_ARG, "cs_set_cross_weights: misaligned pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t C = h->cfg.hidden, l = h->dec.size() - 1;
+  const int bf = h->cfg.operand_dtype;
+  const DecLayer& D = h->dec.back();
+  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
+  HIPCHK(cs_pack_f16_launch(in_w, (int)C, (int)C, D.ca_Wq, (int)C, h->qs_dec, nullptr, bf, st));
+  HIPCHK(cs_vec_mul_launch(in_b, h->qs_dec, D.ca_bq, (int)C, st));
+  HIPCHK(cs_pack_f16_launch(in_w + C * C, (int)(2 * C), (int)C, h->Wkv_all + l * 2 * C * C, (int)C, nullptr, nullptr, bf, st));
+  HIPCHK(hipMemcpyAsync(h->bkv_all + l * 2 * C, in_b + C, 2 * C * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(cs_pack_f16_launch(out_w, (int)C, (int)C, D.ca_Wo, (int)C, nullptr, nullptr, bf, st));
+  HIPCHK(hipMemcpyAsync(D.ca_bo, out_b, C * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(D.n2g, g2, C * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(D.n2b, b2, C * 4, hipMemcpyDeviceToDevice, st));
   if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
   HIPCHK(hipEventRecord(h->ev_done, st));
   h->last_stream = st;

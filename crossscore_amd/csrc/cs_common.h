@@ -213,6 +213,21 @@ struct CsAttnParams {
   int bf16;                                            // operand type of Q, K, V, P and O: 0 IEEE half, 1 bfloat16
 };
 
+// Attention backward (attnbwd.hip): the forward's operands, dO and the lse cs_attn_kernel wrote; dQ, dK, dV in the operand type.
+struct CsAttnBwdParams {
+  const h16_t* Q; const h16_t* K; const h16_t* V; const h16_t* O; const h16_t* dO;
+  const float* lse;                                    // [batch][heads][Lq], base 2
+  int ldq, ldk, ldv, ldo, lddo;                        // row strides (elements)
+  long long q_bs, k_bs, v_bs, o_bs, do_bs;             // batch strides (elements)
+  int nbatch, heads, Lq, Lk;
+  float scale_log2e;                                   // as CsAttnParams::scale_log2e
+  h16_t* dQ; int lddq; long long dq_bs;
+  h16_t* dK; int lddk; long long dk_bs;
+  h16_t* dV; int lddv; long long dv_bs;
+  float* D;                                            // workspace [batch][heads][Lq]: sum_d dO O per query row
+  int bf16;
+};
+
 // Reference use (refuse.hip): Q / K / lse as the last decoder layer's cross-attention saw and wrote them; keys are N segments
 // of Np rows.  Outputs (any may be null): share, peak_prob, peak_index (batch, N, Lq), entropy (batch, Lq).
 struct CsRefUseParams {
@@ -338,6 +353,20 @@ struct CsTailBackward {
   float *dW1, *db1, *dW2, *db2, *dg3, *db3;
 };
 
+// Cross-attention fit (crossfit.hip): the last decoder layer's in_proj -> attention -> out_proj -> + residual -> norm2 in front of the tail.
+struct CsCrossBackward {
+  CsTailBackward tail;          // x2, H, the tail's weights, the head's block (B, gh, gw, C, inv_count, accumulate), the ten gradients and the loss
+  const float* x1;              // [M][C] fp32, contiguous: the rows that entered the cross-attention block
+  const h16_t* Qp; int ldq;     // [M][ldq] the query projection as the forward stored it (log2(e) / sqrt(dh) folded in)
+  const h16_t* K; const h16_t* V; int ldkv;  // [Mk][ldkv] the layer's column blocks of the packed K | V rows, Mk = M N
+  const h16_t* O; int ldo;      // [M][ldo] the attention output
+  const float* lse;             // [B][heads][Np], base 2, as cs_attn_kernel wrote it
+  const h16_t* mem; int ldm;    // [Mk][ldm] the reference tokens the K / V projection read
+  const h16_t* W1; int ldw1; const h16_t* Wo; int ldwo; const float* bo; const float* gamma2;  // linear1 and out_proj (packed), norm2's weight
+  int N, heads, short_cut;
+  float *dWin, *dbin, *dWo, *dbo, *dg2, *db2;  // in_proj (3C, C) and (3C), out_proj (C, C) and (C), norm2 (C) each
+};
+
 // ---- The launch surface between the kernel files and the host files (api.hip, forward.hip, ops.hip): every cs_*_launch / cs_*_check /
 // cs_*_supported / size helper that one .hip defines and another calls, declared ONCE.  Every defining file includes this header, so a changed
 // parameter list fails to compile there instead of linking (most of these are extern "C") and misbehaving at run time. ----
@@ -364,6 +393,11 @@ extern int g_gemm_grid;  // cs_debug_gemm_grid: > 0 replaces the CU-derived bloc
 // attention.hip
 const char* cs_attn_check(const CsAttnParams* p, int dh, int batch);
 hipError_t cs_attn_launch(const CsAttnParams* p, int dh, int batch, hipStream_t stream);
+// attnbwd.hip
+int cs_attnbwd_supported(int dh);
+size_t cs_attnbwd_workspace(int batch, int heads, int Lq);
+const char* cs_attnbwd_check(const CsAttnBwdParams* p);
+hipError_t cs_attnbwd_launch(const CsAttnBwdParams* p, int dh, hipStream_t st);
 // refuse.hip
 const char* cs_refuse_check(const CsRefUseParams* p, int dh);
 hipError_t cs_refuse_launch(const CsRefUseParams* p, int dh, hipStream_t stream);
@@ -472,6 +506,12 @@ size_t cs_ln_backward_workspace(int M, int C);
 size_t cs_tail_backward_workspace(int M, int C);
 hipError_t cs_ln_backward_launch(const CsLnBackward* p, void* ws, int bf, hipStream_t st);
 hipError_t cs_tail_backward_launch(const CsTailBackward* p, void* ws, int bf, hipStream_t st);
+size_t cs_tail_backward_dyh_offset(int M, int C);  // where cs_tail_backward_launch leaves dyh and dHh (M, C; 16 bit) in its workspace
+size_t cs_tail_backward_dh_offset(int M, int C);
+// crossfit.hip
+size_t cs_cross_backward_workspace(int M, int Mk, int C, int batch, int heads);
+void cs_cross_backward_attn_params(const CsCrossBackward* p, void* ws, int bf, CsAttnBwdParams* out);  // the attention backward it queues
+hipError_t cs_cross_backward_launch(const CsCrossBackward* p, void* ws, int bf, hipStream_t st);
 hipError_t cs_adamw_launch(float* p, float* m, float* v, const float* g, long long n, float lr, float beta1, float beta2, float eps, float wd,
                            int step, h16_t* p16, int bf, hipStream_t st);
 }

@@ -124,13 +124,24 @@ struct cs_model {
   };
   RefUse ref_use;
   // head fit (cs_head_backward): what the last forward-class call left behind, and the backward's own workspace
-  struct LastForward { bool ok = false; int mode = -1, B = 0, H = 0, W = 0; const float* xq = nullptr; const h16_t* dhid = nullptr; bool tail_kept = false; };
+  struct LastForward {
+    bool ok = false; int mode = -1, B = 0, H = 0, W = 0; const float* xq = nullptr; const h16_t* dhid = nullptr; bool tail_kept = false;
+    // cs_fit_cross_keep: the last layer's cross-attention as the forward left it in the workspace -- Q' (M, C), the layer's K block of the packed
+    // K | V rows (Mk, ldkv; V is C columns further), O (M, C), lse (B, heads, Np) -- and the reference tokens its K / V projection read (Mk, C)
+    bool cross_kept = false; int N = 0; const h16_t* dq = nullptr; const h16_t* k = nullptr; int ldkv = 0; const h16_t* dob = nullptr;
+    const float* lse = nullptr; const h16_t* mem = nullptr;
+  };
   LastForward last_fwd;
   void* hfit_ws = nullptr; size_t hfit_ws_bytes = 0;  // X in 16 bits (M, C), then cs_head_backward_workspace (cs_tail_backward_workspace once the tail is fitted)
   // tail fit (cs_fit_tail_keep): with the switch on every forward copies the last layer's norm2 output x2 (M, C) fp32 and H = relu(linear1(x2))
   // (M, C) 16 bit into this region, between the two closings of that layer
   bool tail_keep = false;
   void* tail_kept = nullptr; size_t tail_kept_bytes = 0;
+  // cross-attention fit (cs_fit_cross_keep): implies tail_keep; in addition the last layer's cross-attention writes its lse and x1, the fp32 rows
+  // that enter that block, is copied into this region before the norm2 closing overwrites it
+  bool cross_keep = false;
+  void* cross_kept = nullptr; size_t cross_kept_bytes = 0;
+  float* qs_dec = nullptr;  // [C] log2(e) / sqrt(dh) of the decoder: the row scale of the packed query projections (cs_set_cross_weights packs with it again)
   unsigned* nonfinite = nullptr;  // device counter: non-finite score-map values seen since the last cs_nonfinite_count
   // profiling
   bool prof = false;
@@ -202,6 +213,8 @@ inline bool supported_dh(int dh) { return dh == 16 || dh == 48 || dh == 64 || dh
 int head_backward_run(const char* op, const CsHeadBackward& q, void* ws, int bf, hipStream_t st);
 // ops.hip: the same for the tail's backward (the head's is its first part)
 int tail_backward_run(const char* op, const CsTailBackward& q, void* ws, int bf, hipStream_t st);
+// ops.hip: the same for the cross-attention block's backward (the tail's is its first part)
+int cross_backward_run(const char* op, const CsCrossBackward& q, void* ws, int bf, hipStream_t st);
 
 // forward.hip
 void reap_retired(cs_model* m, bool all);                        // frees retired workspaces whose last use has completed (never blocks unless `all`)

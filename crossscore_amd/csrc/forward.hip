@@ -274,6 +274,7 @@ struct Fwd {
   // ... and where it is, the sub-block's NEXT linear rides in the same launch when it is C wide (second stage of rowln.hip)
   bool fused_ln = false, fuse_next = false;
   bool tail_kept = false;  // (cs_fit_tail_keep) this call has queued the two copies cs_tail_backward works on
+  bool cross_kept = false;  // (cs_fit_cross_keep) ... and the copy of x1, with lse written: what cs_cross_backward works on
 
   // ---- step 1: arguments ----
   int validate() {
@@ -747,6 +748,30 @@ struct Fwd {
     return 0;
   }
 
+  // cs_fit_cross_keep: in front of the last layer's norm2 closing p.xq holds x1, the rows that entered the cross-attention
+  // block (norm1's output, or the layer's input without self-attention); the closing overwrites it, so it is copied into the handle's own region.
+  // Q', the packed K | V rows, O and lse stay where they are: nothing behind the last layer's cross-attention writes p.dq (only a NOT-last layer's
+  // closing projects the next query into it), p.kv (written once, before the first layer), p.dob (the self-attention writes it, in front of the
+  // cross-attention) or p.lse, and mem is the caller's ref_tokens or p.mem_bf, which only the encoder / the gather write.
+  int keep_x1(hipStream_t s) {
+    const size_t need = (size_t)B * p.Np * p.C * 4;
+    if (need > h->cross_kept_bytes) {
+      if (h->cross_kept) {
+        cs_model::Retired r{h->cross_kept, nullptr};
+        HIPCHK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+        HIPCHK(hipEventRecord(r.ev, s));
+        h->retired.push_back(r);
+      }
+      h->cross_kept = nullptr; h->cross_kept_bytes = 0;
+      HIPCHK(hipMalloc(&h->cross_kept, need));
+      h->cross_kept_bytes = need;
+    }
+    HIPCHK(hipMemcpyAsync(h->cross_kept, p.xq, need, hipMemcpyDeviceToDevice, s));
+    h->census["cross_keep"] += 1;
+    cross_kept = true;
+    return 0;
+  }
+
   // The decoder runs as ONE group on the caller's stream, after the join: its kernels are small, and splitting the batch over streams only
   // makes them smaller (cfg-2, tools/dec_lanes.py: 1 group 8.77 ms, 2 groups 8.80, 3 groups 8.79, 4 groups 9.31).  Decoding each chunk's
   // items on its lane right after encoding them (no global join) was measured SLOWER too (833 vs 875 query-images/s on cfg-2): it doubles the
@@ -791,13 +816,15 @@ struct Fwd {
       if (!have_q) L.gemm(gp(p.q_bf, C, D.ca_Wq, C, M, C, C, D.ca_bq, p.dq, C), CS_EPI_BIAS_F16);
       const bool want_w = attn_out && last_l;  // only the last layer's weights are returned (transformer.py:266-268)
       const bool want_use = last_l && use.any();  // reference use: the same layer, the same lse
-      const CsAttnParams a = attn_params(p.dq, C, p.kv + (size_t)l * 2 * C, p.kv + (size_t)l * 2 * C + C, KV, p.dob, p.Np, N * p.Np, c.dec_heads, want_w || want_use ? p.lse : nullptr);
+      const bool want_fit = last_l && h->cross_keep;  // cross-attention fit: lse for the backward, x1 kept below
+      const CsAttnParams a = attn_params(p.dq, C, p.kv + (size_t)l * 2 * C, p.kv + (size_t)l * 2 * C + C, KV, p.dob, p.Np, N * p.Np, c.dec_heads, want_w || want_use || want_fit ? p.lse : nullptr);
       L.attn(a, dec_dh, B);
       if (want_w) L.small("attn_weights", [&] { return cs_attn_weights_launch(&a, dec_dh, B, head_id, attn_out, s); });
       if (want_use) reference_use(L, a, dec_dh);
+      if (want_fit && !L.rc) L.rc = keep_x1(s);
       if (!dec_close(L, p.dob, D.ca_Wo, D.ca_bo, shortcut, D.n2g, D.n2b, "norm2", next_of(D.l1W, D.l1b, p.dhid, 1)))
         L.gemm(gp(p.q_bf, C, D.l1W, C, M, C, C, D.l1b, p.dhid, C), CS_EPI_BIAS_RELU_F16);
-      if (last_l && h->tail_keep && !L.rc) L.rc = keep_tail(s);
+      if (last_l && (h->tail_keep || h->cross_keep) && !L.rc) L.rc = keep_tail(s);
       // behind norm3: the head's first linear (its hidden rows replace linear1's in dhid: a workgroup writes exactly the 64 rows it staged into
       // LDS at its start), or -- without self-attention -- the next layer's Q projection
       NextLinear next{};
@@ -874,6 +901,12 @@ int forward_impl(Fwd f) {
   if (f.u8) cs_preprocess_tables_hold(0);
   // what cs_head_backward works on: the tokens behind the last norm3 and the head's hidden rows of THIS call (f.p: the plan body() carved)
   h->last_fwd = cs_model::LastForward{rc == 0, f.mode, f.B, f.H, f.W, f.p.xq, f.p.dhid, f.tail_kept};
+  if (f.cross_kept) {  // (the decoder ran: the plan is carved and the handle has a last layer)
+    cs_model::LastForward& lf = h->last_fwd;
+    const int C = h->cfg.hidden, L = h->cfg.dec_layers;
+    lf.cross_kept = true; lf.N = f.N; lf.dq = f.p.dq; lf.k = f.p.kv + (size_t)(L - 1) * 2 * C; lf.ldkv = 2 * C * L; lf.dob = f.p.dob; lf.lse = f.p.lse;
+    lf.mem = f.mode == 1 ? f.ref_tokens : f.p.mem_bf;
+  }
   h->host_enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
   HIPCHK(hipEventRecord(h->ev_done, f.st));
@@ -976,7 +1009,10 @@ int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const ui
 // 16-bit copy: X is rounded here from p.xq, the rounding the forward's own operand went through.  The workspace of the backward is the
 // handle's own allocation (X, then cs_head_backward_workspace), grown like the forward's.
 // `tail`: the call is the tail's -- the last forward must have kept x2 and H, and the workspace is the tail backward's.
-static int head_fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, const char* op, int* M_out, h16_t** X_out, bool tail = false) {
+// `level` 2: the call is the cross-attention fit's -- x1 and lse kept as well, the workspace is that backward's.
+// the state a fit call needs, without touching the handle: the checks of head_fit_inputs (below), which calls this first
+static int fit_state_check(cs_model* h, int B, int H, int W, const char* op, int level) {
+  const bool tail = level >= 1, cross = level >= 2;
   if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
   if (!h->finalized) return fail(CS_ERR_STATE, "%s before cs_finalize", op);
   const cs_model::LastForward& lf = h->last_fwd;
@@ -987,10 +1023,22 @@ static int head_fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, con
   const cs_config& c = h->cfg;
   if (!cs_headfit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden a multiple of 64 and patch 14 (hidden %d, patch %d)", op, c.hidden, c.patch);
   if (tail && !cs_tail_fit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden <= 2048 (hidden %d)", op, c.hidden);
+  if (cross && !cs_cross_fit_supported(c.hidden, c.dec_heads, c.patch))
+    return fail(CS_ERR_UNSUPPORTED, "%s: the attention backward is built for head dims 16, 48 and 96 (hidden %d, %d heads)", op, c.hidden, c.dec_heads);
+  if (cross && !(lf.cross_kept && lf.tail_kept)) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_cross_keep off", op);
   if (tail && !lf.tail_kept) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_tail_keep off", op);
+  return 0;
+}
+
+static int head_fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, const char* op, int* M_out, h16_t** X_out, int level = 0) {
+  if (int r = fit_state_check(h, B, H, W, op, level)) return r;
+  const bool tail = level >= 1, cross = level >= 2;
+  const cs_model::LastForward& lf = h->last_fwd;
+  const cs_config& c = h->cfg;
   const int M = lf.B * (lf.H / c.patch) * (lf.W / c.patch), C = c.hidden;
   const size_t xbytes = ((size_t)M * C * 2 + 255) & ~size_t(255),
-               need = xbytes + (tail ? cs_tail_backward_workspace(M, C) : cs_head_backward_workspace(M, C));
+               need = xbytes + (cross ? cs_cross_backward_workspace(M, M * lf.N, C, lf.B, c.dec_heads)
+                                      : tail ? cs_tail_backward_workspace(M, C) : cs_head_backward_workspace(M, C));
   if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
   if (need > h->hfit_ws_bytes) {
     if (h->hfit_ws) {
@@ -1072,7 +1120,7 @@ int cs_tail_backward(cs_handle h, const float* gt, int B, int H, int W, double i
   if (h && h->cfg.act == 1 && h->cfg.pow_p != 1.0f) return fail(CS_ERR_UNSUPPORTED, "cs_tail_backward: tanh with a power factor other than 1 is not built");
   int M = 0; h16_t* X = nullptr;
   if (h && h->finalized && h->dec.empty()) return fail(CS_ERR_STATE, "cs_tail_backward: the handle has no decoder layer");
-  if (int r = head_fit_inputs(h, B, H, W, st, "cs_tail_backward", &M, &X, true)) return r;
+  if (int r = head_fit_inputs(h, B, H, W, st, "cs_tail_backward", &M, &X, 1)) return r;
   const cs_config& c = h->cfg;
   const int C = c.hidden;
   const DecLayer& D = h->dec.back();
@@ -1098,10 +1146,76 @@ int cs_debug_tail_inputs(cs_handle h, float* x2_out, uint16_t* H_out, int rows, 
       rows != h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch))
     return fail(CS_ERR_BAD_ARG, "cs_debug_tail_inputs: the last forward left %d rows, the caller names %d",
                 h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch), rows);
-  if (int r = head_fit_inputs(h, 0, 0, 0, st, "cs_debug_tail_inputs", &M, &X, true)) return r;
+  if (int r = head_fit_inputs(h, 0, 0, 0, st, "cs_debug_tail_inputs", &M, &X, 1)) return r;
   const size_t n = (size_t)M * h->cfg.hidden;
   if (x2_out) HIPCHK(hipMemcpyAsync(x2_out, h->tail_kept, n * 4, hipMemcpyDeviceToDevice, st));
   if (H_out) HIPCHK(hipMemcpyAsync(H_out, static_cast<const char*>(h->tail_kept) + ((n * 4 + 255) & ~size_t(255)), n * 2, hipMemcpyDeviceToDevice, st));
+  return head_fit_done(h, st);
+}
+
+// ---- cross-attention fit: the same over the last layer's cross-attention block as well, on what a forward with
+// cs_fit_cross_keep left behind ----
+int cs_cross_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWin, float* dbin, float* dWo,
+                      float* dbo, float* dgamma2, float* dbeta2, float* dW1, float* db1, float* dW2, float* db2, float* dg3, float* db3, float* dWa,
+                      float* dba, float* dWb, float* dbb, double* loss, cs_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (B <= 0) return fail(CS_ERR_BAD_ARG, "cs_cross_backward: empty batch");
+  uintptr_t bits = (uintptr_t)gt;
+  for (const float* o : {dWin, dbin, dWo, dbo, dgamma2, dbeta2, dW1, db1, dW2, db2, dg3, db3, dWa, dba, dWb, dbb}) {
+    if (!o) return fail(CS_ERR_BAD_ARG, "cs_cross_backward: null pointer");
+    bits |= (uintptr_t)o;
+  }
+  if (!gt || !loss) return fail(CS_ERR_BAD_ARG, "cs_cross_backward: null pointer");
+  if ((bits & 3) || ((uintptr_t)loss & 7)) return fail(CS_ERR_BAD_ARG, "cs_cross_backward: misaligned pointer (fp32 4 bytes, the loss 8)");
+  if (!(inv_count > 0.0)) return fail(CS_ERR_BAD_ARG, "cs_cross_backward: inv_count must be positive");
+  if (h && h->cfg.act == 1 && h->cfg.pow_p != 1.0f) return fail(CS_ERR_UNSUPPORTED, "cs_cross_backward: tanh with a power factor other than 1 is not built");
+  int M = 0; h16_t* X = nullptr;
+  if (h && h->finalized && h->dec.empty()) return fail(CS_ERR_STATE, "cs_cross_backward: the handle has no decoder layer");
+  if (int r = head_fit_inputs(h, B, H, W, st, "cs_cross_backward", &M, &X, 2)) return r;
+  const cs_config& c = h->cfg;
+  const int C = c.hidden;
+  const DecLayer& D = h->dec.back();
+  const cs_model::LastForward& lf = h->last_fwd;
+  CsCrossBackward x{};
+  x.x1 = static_cast<const float*>(h->cross_kept); x.Qp = lf.dq; x.ldq = C; x.K = lf.k; x.V = lf.k + C; x.ldkv = lf.ldkv; x.O = lf.dob; x.ldo = C;
+  x.lse = lf.lse; x.mem = lf.mem; x.ldm = C; x.W1 = D.l1W; x.ldw1 = C; x.Wo = D.ca_Wo; x.ldwo = C; x.bo = D.ca_bo; x.gamma2 = D.n2g;
+  x.N = lf.N; x.heads = c.dec_heads; x.short_cut = c.do_short_cut != 0;
+  x.dWin = dWin; x.dbin = dbin; x.dWo = dWo; x.dbo = dbo; x.dg2 = dgamma2; x.db2 = dbeta2;
+  CsTailBackward& q = x.tail;
+  q.x2 = static_cast<const float*>(h->tail_kept);
+  q.H = reinterpret_cast<const h16_t*>(static_cast<const char*>(h->tail_kept) + (((size_t)M * C * 4 + 255) & ~size_t(255))); q.ldh = C;
+  q.W2 = D.l2W; q.ldw2 = C; q.b2 = D.l2b; q.gamma3 = D.n3g; q.eps = 1e-5f; q.Wa = h->Wh0; q.ldwa = C;
+  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dg3; q.db3 = db3;
+  CsHeadBackward& hq = q.head;
+  hq.X = X; hq.ldx = C; hq.A = lf.dhid; hq.lda = C; hq.Wb = h->Wh2; hq.ldw = C; hq.bb = h->bh2; hq.gt = gt; hq.B = B; hq.gh = H / c.patch;
+  hq.gw = W / c.patch; hq.P = c.patch; hq.C = C; hq.act = c.act; hq.powp = c.pow_p; hq.inv_count = inv_count; hq.accumulate = accumulate != 0;
+  hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb; hq.loss = loss;
+  char* ws = static_cast<char*>(h->hfit_ws) + (((size_t)M * C * 2 + 255) & ~size_t(255));
+  const int rc = cross_backward_run("cs_cross_backward", x, ws, c.operand_dtype, st);
+  if (int r = head_fit_done(h, st)) return r;
+  return rc;
+}
+
+int cs_debug_cross_inputs(cs_handle h, float* x1_out, uint16_t* q_out, uint16_t* o_out, float* lse_out, uint16_t* k_out, uint16_t* v_out, int rows,
+                          cs_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  int M = 0;
+  if (h && h->finalized && h->last_fwd.ok && h->last_fwd.mode != 2 &&
+      rows != h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch))
+    return fail(CS_ERR_BAD_ARG, "cs_debug_cross_inputs: the last forward left %d rows, the caller names %d",
+                h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch), rows);
+  // (the state checks alone: six copies need neither X nor the backward's workspace, which head_fit_inputs would grow the handle's region to)
+  if (int r = fit_state_check(h, 0, 0, 0, "cs_debug_cross_inputs", 2)) return r;
+  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
+  const cs_model::LastForward& lf = h->last_fwd;
+  M = lf.B * (lf.H / h->cfg.patch) * (lf.W / h->cfg.patch);
+  const size_t C = h->cfg.hidden, n = (size_t)M * C, Mk = (size_t)M * lf.N;
+  if (x1_out) HIPCHK(hipMemcpyAsync(x1_out, h->cross_kept, n * 4, hipMemcpyDeviceToDevice, st));
+  if (q_out) HIPCHK(hipMemcpyAsync(q_out, lf.dq, n * 2, hipMemcpyDeviceToDevice, st));
+  if (o_out) HIPCHK(hipMemcpyAsync(o_out, lf.dob, n * 2, hipMemcpyDeviceToDevice, st));
+  if (lse_out) HIPCHK(hipMemcpyAsync(lse_out, lf.lse, (size_t)M * h->cfg.dec_heads * 4, hipMemcpyDeviceToDevice, st));
+  if (k_out) HIPCHK(hipMemcpy2DAsync(k_out, C * 2, lf.k, (size_t)lf.ldkv * 2, C * 2, Mk, hipMemcpyDeviceToDevice, st));
+  if (v_out) HIPCHK(hipMemcpy2DAsync(v_out, C * 2, lf.k + C, (size_t)lf.ldkv * 2, C * 2, Mk, hipMemcpyDeviceToDevice, st));
   return head_fit_done(h, st);
 }
 

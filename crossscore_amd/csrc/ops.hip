@@ -852,8 +852,8 @@ int cs_op_ln_backward(const float* y, int ldy, const float* dx, int ldx, const f
 
 }  // extern "C"
 
-// cs_op_tail_backward and cs_tail_backward (forward.hip) come through here: every check of both backwards first, then the launches
-int cs_host::tail_backward_run(const char* op, const CsTailBackward& q, void* ws, int bf, hipStream_t st) {
+// every check of the head's and the tail's backward (cs_op_tail_backward, cs_tail_backward and the cross-attention fit's come through here)
+static int tail_backward_check(const char* op, const CsTailBackward& q, void* ws) {
   const CsHeadBackward& hq = q.head;
   if (int r = head_fit_shape_check(op, hq.A, hq.lda, hq.Wb, hq.ldw, hq.bb, hq.gt, hq.B, hq.gh, hq.gw, hq.P, hq.C, hq.act, hq.powp, ws)) return r;
   const int C = hq.C;
@@ -870,7 +870,42 @@ int cs_host::tail_backward_run(const char* op, const CsTailBackward& q, void* ws
     if (misaligned(o, 4)) return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
   if (misaligned(hq.loss, 8)) return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
   if (!(hq.inv_count > 0.0) || !(q.eps >= 0.f)) return fail(CS_ERR_BAD_ARG, "%s: inv_count must be positive and eps >= 0", op);
+  return 0;
+}
+
+// cs_op_tail_backward and cs_tail_backward (forward.hip) come through here: every check of both backwards first, then the launches
+int cs_host::tail_backward_run(const char* op, const CsTailBackward& q, void* ws, int bf, hipStream_t st) {
+  if (int r = tail_backward_check(op, q, ws)) return r;
   HIPCHK(cs_tail_backward_launch(&q, ws, bf, st));
+  return 0;
+}
+
+// cs_op_cross_backward and cs_cross_backward (forward.hip): the tail's checks, the block's own, then the launches
+int cs_host::cross_backward_run(const char* op, const CsCrossBackward& q, void* ws, int bf, hipStream_t st) {
+  if (int r = tail_backward_check(op, q.tail, ws)) return r;
+  const CsHeadBackward& hq = q.tail.head;
+  const int C = hq.C;
+  if (q.heads <= 0 || C % q.heads || !cs_attnbwd_supported(C / q.heads))
+    return fail(CS_ERR_UNSUPPORTED, "%s: the attention backward is built for head dims 16, 48 and 96 (hidden %d, %d heads)", op, C, q.heads);
+  if (q.N <= 0) return fail(CS_ERR_BAD_ARG, "%s: N must be positive", op);
+  const long long Mk = (long long)hq.B * hq.gh * hq.gw * q.N;
+  if (Mk * 2 * C >= (1ll << 31)) return fail(CS_ERR_UNSUPPORTED, "%s: built for fewer than 2^31 K | V elements; split the batch", op);
+  if (!q.x1 || !q.Qp || !q.K || !q.V || !q.O || !q.lse || !q.mem || !q.W1 || !q.Wo || !q.bo || !q.gamma2 || !q.dWin || !q.dbin || !q.dWo || !q.dbo ||
+      !q.dg2 || !q.db2)
+    return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
+  for (int ld : {q.ldq, q.ldo, q.ldm, q.ldw1, q.ldwo})
+    if (ld < C || ld % 8) return fail(CS_ERR_BAD_ARG, "%s: row strides must be multiples of 8 elements and at least C", op);
+  if (q.ldkv < C || q.ldkv % 8 || (long long)hq.gh * hq.gw * q.N * q.ldkv >= (1ll << 30))
+    return fail(CS_ERR_BAD_ARG, "%s: the K | V row stride must be a multiple of 8 elements, at least C, and N Np times it below 2^30", op);
+  if (misaligned(q.x1, 16) || misaligned(q.Qp, 16) || misaligned(q.K, 16) || misaligned(q.V, 16) || misaligned(q.O, 16) || misaligned(q.mem, 16) ||
+      misaligned(q.W1, 16) || misaligned(q.Wo, 16) || misaligned(q.bo, 16) || misaligned(q.gamma2, 16) || misaligned(q.lse, 4))
+    return fail(CS_ERR_BAD_ARG, "%s: misaligned input (16-bit operands, x1, bo and gamma 16 bytes, lse 4)", op);
+  for (const float* o : {q.dWin, q.dbin, q.dWo, q.dbo, q.dg2, q.db2})
+    if (misaligned(o, 4)) return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
+  CsAttnBwdParams a{};
+  cs_cross_backward_attn_params(&q, ws, bf, &a);
+  if (const char* e = cs_attnbwd_check(&a)) return fail(CS_ERR_BAD_ARG, "%s: %s", op, e);
+  HIPCHK(cs_cross_backward_launch(&q, ws, bf, st));
   return 0;
 }
 
@@ -901,6 +936,69 @@ int cs_op_adamw(float* p, float* m, float* v, const float* g, long long n, float
   if (misaligned(p, 4) || misaligned(m, 4) || misaligned(v, 4) || misaligned(g, 4) || misaligned(p16, 2)) return fail(CS_ERR_BAD_ARG, "adamw: misaligned pointer");
   HIPCHK(cs_adamw_launch(p, m, v, g, n, lr, beta1, beta2, eps, weight_decay, step, p16, g_op_bf16, (hipStream_t)stream));
   return 0;
+}
+
+// ---- attention backward (attnbwd.hip) ----
+size_t cs_attention_backward_workspace_bytes(int batch, int heads, int Lq, int Lk, int dh) {
+  if (batch <= 0 || heads <= 0 || Lq <= 0 || Lk <= 0 || !cs_attnbwd_supported(dh)) return 0;
+  return cs_attnbwd_workspace(batch, heads, Lq);
+}
+
+int cs_attention_backward_tiles(int dh, int* q_tile, int* k_tile) {
+  if (!cs_attnbwd_supported(dh)) return fail(CS_ERR_UNSUPPORTED, "attention_backward: built for head dims 16, 48 and 96 (got %d)", dh);
+  if (q_tile) *q_tile = 64;
+  if (k_tile) *k_tile = 64;
+  return 0;
+}
+
+int cs_op_attention_backward(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* O, const uint16_t* dO, const float* lse,
+                             int ldq, int ldk, int ldv, int ldo, int lddo, long long q_bs, long long k_bs, long long v_bs, long long o_bs,
+                             long long do_bs, int batch, int heads, int Lq, int Lk, int dh, float q_scale, uint16_t* dQ, int lddq,
+                             long long dq_bs, uint16_t* dK, int lddk, long long dk_bs, uint16_t* dV, int lddv, long long dv_bs, void* ws,
+                             cs_stream stream) {
+  CsAttnBwdParams a{};
+  a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.lse = lse; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo;
+  a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs; a.do_bs = do_bs; a.nbatch = batch; a.heads = heads; a.Lq = Lq; a.Lk = Lk;
+  a.dQ = dQ; a.lddq = lddq; a.dq_bs = dq_bs; a.dK = dK; a.lddk = lddk; a.dk_bs = dk_bs; a.dV = dV; a.lddv = lddv; a.dv_bs = dv_bs;
+  a.D = static_cast<float*>(ws); a.bf16 = g_op_bf16;
+  if (!(q_scale >= 0.f)) return fail(CS_ERR_BAD_ARG, "attention_backward: q_scale must be >= 0 (0 = log2(e)/sqrt(dh))");
+  if (const char* e = cs_attnbwd_check(&a)) return fail(CS_ERR_BAD_ARG, "%s", e);
+  if (!cs_attnbwd_supported(dh)) return fail(CS_ERR_UNSUPPORTED, "attention_backward: built for head dims 16, 48 and 96 (got %d)", dh);
+  a.scale_log2e = q_scale == 0.f ? LOG2E / std::sqrt((float)dh) : q_scale;
+  HIPCHK(cs_attnbwd_launch(&a, dh, (hipStream_t)stream));
+  return 0;
+}
+
+// ---- cross-attention fit (crossfit.hip) ----
+int cs_cross_fit_supported(int hidden, int heads, int patch) {
+  return cs_tail_fit_supported(hidden, patch) && heads > 0 && hidden % heads == 0 && cs_attnbwd_supported(hidden / heads);
+}
+
+size_t cs_cross_backward_workspace_bytes(int B, int Np, int N, int C, int P, int heads) {
+  if (B <= 0 || Np <= 0 || N <= 0 || !cs_cross_fit_supported(C, heads, P) || (long long)B * Np * N * 2 * C >= (1ll << 31)) return 0;
+  return cs_cross_backward_workspace(B * Np, B * Np * N, C, B, heads);
+}
+
+int cs_op_cross_backward(const float* x1, const uint16_t* Qp, int ldq, const uint16_t* K, const uint16_t* V, int ldkv, const uint16_t* O, int ldo,
+                         const float* lse, const uint16_t* mem, int ldm, const uint16_t* W1, int ldw1, const uint16_t* Wo, int ldwo, const float* bo,
+                         const float* gamma2, int N, int heads, int short_cut, const float* x2, const uint16_t* H, int ldh, const uint16_t* X,
+                         int ldx, const uint16_t* A, int lda, const uint16_t* W2, int ldw2, const float* b2, const float* gamma3, float eps,
+                         const uint16_t* Wa, int ldwa, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P,
+                         int C, int act, float powp, double inv_count, int accumulate, float* dWin, float* dbin, float* dWo, float* dbo,
+                         float* dgamma2, float* dbeta2, float* dW1, float* db1, float* dW2, float* db2, float* dgamma3, float* dbeta3, float* dWa,
+                         float* dba, float* dWb, float* dbb, double* loss, void* ws, cs_stream stream) {
+  CsCrossBackward c{};
+  c.x1 = x1; c.Qp = Qp; c.ldq = ldq; c.K = K; c.V = V; c.ldkv = ldkv; c.O = O; c.ldo = ldo; c.lse = lse; c.mem = mem; c.ldm = ldm;
+  c.W1 = W1; c.ldw1 = ldw1; c.Wo = Wo; c.ldwo = ldwo; c.bo = bo; c.gamma2 = gamma2; c.N = N; c.heads = heads; c.short_cut = short_cut != 0;
+  c.dWin = dWin; c.dbin = dbin; c.dWo = dWo; c.dbo = dbo; c.dg2 = dgamma2; c.db2 = dbeta2;
+  CsTailBackward& q = c.tail;
+  q.x2 = x2; q.H = H; q.ldh = ldh; q.W2 = W2; q.ldw2 = ldw2; q.b2 = b2; q.gamma3 = gamma3; q.eps = eps; q.Wa = Wa; q.ldwa = ldwa;
+  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dgamma3; q.db3 = dbeta3;
+  CsHeadBackward& hq = q.head;
+  hq.X = X; hq.ldx = ldx; hq.A = A; hq.lda = lda; hq.Wb = Wb; hq.ldw = ldw; hq.bb = bb; hq.gt = gt; hq.B = B; hq.gh = gh; hq.gw = gw; hq.P = P; hq.C = C;
+  hq.act = act; hq.powp = powp; hq.inv_count = inv_count; hq.accumulate = accumulate != 0; hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb;
+  hq.loss = loss;
+  return cross_backward_run("cross_backward", c, ws, g_op_bf16, (hipStream_t)stream);
 }
 
 }  // extern "C"

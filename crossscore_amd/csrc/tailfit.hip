@@ -194,6 +194,13 @@ size_t cs_tail_backward_workspace(int M, int C) {
          cs_ln_backward_workspace(M, C) + cs_gemm_tn_workspace(M, C, C);
 }
 
+// where cs_tail_backward_launch leaves dyh and dHh (M, C; 16 bit, contiguous) in its workspace: the cross-attention fit continues from them
+size_t cs_tail_backward_dyh_offset(int M, int C) {
+  const size_t mc = (size_t)M * C;
+  return cs_head_backward_workspace(M, C) + up256((size_t)C * C * 2) + up256((size_t)C * 4) + 2 * up256(mc * 4);
+}
+size_t cs_tail_backward_dh_offset(int M, int C) { return cs_tail_backward_dyh_offset(M, C) + up256((size_t)M * C * 2); }
+
 hipError_t cs_tail_backward_launch(const CsTailBackward* q, void* ws, int bf, hipStream_t st) {
   const CsHeadBackward& hq = q->head;
   const int M = hq.B * hq.gh * hq.gw, C = hq.C;
@@ -205,8 +212,9 @@ hipError_t cs_tail_backward_launch(const CsTailBackward* q, void* ws, int bf, hi
   float* zb = reinterpret_cast<float*>(w); w += up256((size_t)C * 4);
   float* dX = reinterpret_cast<float*>(w); w += up256(mc * 4);
   float* y = reinterpret_cast<float*>(w); w += up256(mc * 4);
-  h16_t* dyh = reinterpret_cast<h16_t*>(w); w += up256(mc * 2);
-  h16_t* dH = reinterpret_cast<h16_t*>(w); w += up256(mc * 2);
+  // (dyh and dH through the helpers the cross-attention fit reads them back with: one place knows where they lie)
+  h16_t* dyh = reinterpret_cast<h16_t*>(static_cast<char*>(ws) + cs_tail_backward_dyh_offset(M, C)); w += up256(mc * 2);
+  h16_t* dH = reinterpret_cast<h16_t*>(static_cast<char*>(ws) + cs_tail_backward_dh_offset(M, C)); w += up256(mc * 2);
   h16_t* x2h = reinterpret_cast<h16_t*>(w); w += up256(mc * 2);
   void* lws = w; w += cs_ln_backward_workspace(M, C);
   void* tws = w;

@@ -1,6 +1,8 @@
 """python -m crossscore_amd.fit_head: fits the regression head on the device, or with this_main.fit_scope=tail the decoder's
-tail: the last decoder layer's linear1, linear2 and norm3 together with the head, ten tensors (CrossScoreNet.fit_tail_step).
-The default scope is head; the gradient of the tail stops at the last layer's norm2 output, so everything below stays frozen in both scopes.
+tail: the last decoder layer's linear1, linear2 and norm3 together with the head, ten tensors (CrossScoreNet.fit_tail_step),
+or with this_main.fit_scope=cross that layer's cross-attention as well: its in_proj, out_proj and norm2, sixteen tensors (DESIGN.md 6, f17;
+CrossScoreNet.fit_cross_step).  The default scope is head; the gradient of the tail stops at the last layer's norm2 output and that of the
+cross scope at the rows and the reference tokens that enter the cross-attention, so everything below stays frozen in every scope.
 
 Walks the nvs.NvsItems of this_main.data_split (default train) with the host loaders and the GT stage of crossscore_amd.evaluate
 (InputStage.metric_maps over the metric-map files, or this_main.gt_metric_maps=compute on a bare tree), geometry as evaluate's, one handle, one
@@ -41,14 +43,15 @@ def step_lr(lr0: float, step_size: int, gamma: float, n: int) -> float:
     return lr0 * gamma ** (n // step_size)
 
 
-FIT_SCOPES = ("head", "tail")
+FIT_SCOPES = ("head", "tail", "cross")
 
 
 def fit_scope(cfg) -> str:
-    """this_main.fit_scope: head (default; ref_cross.head.{0,2}) or tail (the last decoder layer's feed-forward block and norm3 as well)"""
+    """this_main.fit_scope: head (default; ref_cross.head.{0,2}), tail (the last decoder layer's feed-forward block and norm3 as well) or cross
+    (that layer's cross-attention and norm2 as well)"""
     scope = str(cfg.this_main.get("fit_scope", "head"))
     if scope not in FIT_SCOPES:
-        raise ValueError(f"this_main.fit_scope={scope}: head | tail")
+        raise ValueError(f"this_main.fit_scope={scope}: head | tail | cross")
     return scope
 
 
@@ -86,8 +89,11 @@ def fit_head(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     scope = fit_scope(cfg)
     if scope == "tail" and not _lib.load().cs_tail_fit_supported(arch.hidden, arch.patch):
         raise ValueError(f"the tail fit is built for hidden a multiple of 64 up to 2048 and patch 14 (hidden {arch.hidden}, patch {arch.patch})")
+    if scope == "cross" and not _lib.load().cs_cross_fit_supported(arch.hidden, arch.dec_heads, arch.patch):
+        raise NotImplementedError(f"the cross-attention fit is built for the tail's shapes and decoder head dims 16, 48 and 96 (hidden {arch.hidden}, "
+                                  f"{arch.dec_heads} heads, patch {arch.patch})")
     net = build_net(cfg, device, state_dict, "fit_head")
-    fit_step = net.fit_tail_step if scope == "tail" else net.fit_head_step
+    fit_step = {"head": net.fit_head_step, "tail": net.fit_tail_step, "cross": net.fit_cross_step}[scope]
 
     out_dir = cfg.logger.train.out_dir
     if out_dir is None:

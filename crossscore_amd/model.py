@@ -240,6 +240,7 @@ class CrossScoreNet(torch.nn.Module):
         self.finite_check = True   # every forward counts the non-finite values of its score map on the device (~3 us)
         self._after_sub_batch = None  # fit_head_step's / fit_tail_step's hook behind each sub-batch's forward call (_score)
         self._tail_keep = False    # fit_tail_keep: forwards keep what the tail's backward reads (fit_tail_step turns it on for its call)
+        self._cross_keep = False   # fit_cross_keep: ... and what the cross-attention block's backward reads (fit_cross_step, for its call)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._mark_dirty())
 
     # -- weights ----------------------------------------------------------------------------------------------
@@ -338,6 +339,8 @@ class CrossScoreNet(torch.nn.Module):
             _lib.check(lib.cs_debug_capture(h, 1))
         if self._tail_keep:
             _lib.check(lib.cs_fit_tail_keep(h, 1))
+        if self._cross_keep:
+            _lib.check(lib.cs_fit_cross_keep(h, 1))
         return h
 
     # -- forward ----------------------------------------------------------------------------------------------
@@ -857,6 +860,116 @@ class CrossScoreNet(torch.nn.Module):
                                            stream))
             _lib.check(lib.cs_set_tail_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[:6]), stream))
             _lib.check(lib.cs_set_head_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[6:]), stream))
+        return loss
+
+    # -- fitting the last decoder layer's cross-attention with the tail and the head ----------------------
+    @property
+    def CROSS_KEYS(self):
+        """The sixteen keys of the cross-attention fit: the last decoder layer's multihead_attn in_proj and out_proj and norm2, then TAIL_KEYS
+        (the order of cs_cross_backward's gradients)."""
+        p = f"ref_cross.attn.layers.{self.arch.dec_layers - 1}."
+        return tuple(p + k for k in ("multihead_attn.in_proj_weight", "multihead_attn.in_proj_bias", "multihead_attn.out_proj.weight",
+                                     "multihead_attn.out_proj.bias", "norm2.weight", "norm2.bias")) + self.TAIL_KEYS
+
+    def cross_parameters(self):
+        if not self._do_reference_cross:
+            raise ValueError("model.do_reference_cross=False: this module has no decoder to fit")
+        return [self.get_parameter(k) for k in self.CROSS_KEYS]
+
+    def cross_fit_supported(self) -> bool:
+        return bool(_lib.load().cs_cross_fit_supported(self.arch.hidden, self.arch.dec_heads, self.arch.patch))
+
+    def fit_cross_keep(self, on: bool = True) -> None:
+        """Following forwards also keep what cross_backward reads (cs_fit_cross_keep): fit_tail_keep's two copies, x1 and the last
+        cross-attention's lse."""
+        self._cross_keep = bool(on)
+        if self._handle is not None:
+            _lib.check(_lib.load().cs_fit_cross_keep(self._handle, int(self._cross_keep)))
+
+    def cross_inputs(self, rows: int, N: int):
+        """(x1, Q', O, lse, K, V) of the last forward call's last cross-attention (tests): x1 (rows, C) fp32, Q' and O (rows, C) 16 bit, lse
+        (rows heads) fp32 in (B, heads, Np) order, K and V (rows N, C) 16 bit; that forward must have run with fit_cross_keep on."""
+        if self._handle is None:
+            raise _lib.CrossScoreHipError("cross_inputs before any forward")
+        dev = self._handle_device
+        Cc = self.arch.hidden
+        with torch.cuda.device(dev):
+            x1 = torch.empty((int(rows), Cc), dtype=torch.float32, device=dev)
+            Qp = torch.empty((int(rows), Cc), dtype=self.token_dtype, device=dev)
+            O = torch.empty_like(Qp)
+            lse = torch.empty((int(rows) * self.arch.dec_heads,), dtype=torch.float32, device=dev)
+            K = torch.empty((int(rows) * int(N), Cc), dtype=self.token_dtype, device=dev)
+            V = torch.empty_like(K)
+            _lib.check(_lib.load().cs_debug_cross_inputs(self._handle, *(C.c_void_p(t.data_ptr()) for t in (x1, Qp, O, lse, K, V)), int(rows),
+                                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return x1, Qp, O, lse, K, V
+
+    def cross_backward(self, gt, inv_count=None, accumulate=False, out=None):
+        """cs_cross_backward over the LAST forward call of this module (run with fit_cross_keep on): gt (B, h P, w P) fp32 on the device -> the
+        sixteen fp32 gradients in CROSS_KEYS order and the fp64 device scalar loss, each scaled by inv_count (default 1 / gt.numel())."""
+        if self._handle is None:
+            raise _lib.CrossScoreHipError("cross_backward before any forward")
+        dev = self._handle_device
+        if gt.dim() != 3 or gt.dtype != torch.float32 or gt.device != dev or not gt.is_contiguous():
+            raise ValueError("expected a contiguous fp32 gt (B, H, W) on the module's device")
+        B, H, W = gt.shape
+        if out is None:
+            out = tuple(torch.zeros(p.shape, device=dev) for p in self.cross_parameters()) + (torch.zeros((), dtype=torch.float64, device=dev),)
+        inv = 1.0 / gt.numel() if inv_count is None else float(inv_count)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().cs_cross_backward(self._handle, C.c_void_p(gt.data_ptr()), B, H, W, inv, int(bool(accumulate)),
+                                                     *(C.c_void_p(t.data_ptr()) for t in out),
+                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
+    def fit_cross_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
+        """fit_tail_step over the sixteen tensors of the cross-attention fit: the forward with fit_cross_keep on for the call, cs_cross_backward
+        behind each sub-batch, sixteen cs_op_adamw launches, cs_set_cross_weights, cs_set_tail_weights and cs_set_head_weights.  Same contract:
+        the module is not marked dirty, the loss of the batch BEFORE the step comes back as a device fp64 scalar, nothing is waited for."""
+        if (refs is None) == (ref_tokens is None):
+            raise ValueError("fit_cross_step takes the references either as images (refs) or as cached tokens (ref_tokens)")
+        if not self.cross_fit_supported():
+            raise NotImplementedError(f"cross-attention fit is built for the tail's shapes and decoder head dims 16, 48 and 96 (hidden {self.arch.hidden}, "
+                                      f"{self.arch.dec_heads} heads, patch {self.arch.patch})")
+        params = self.cross_parameters()
+        dev = gt.device
+        for p in params:
+            if not p.is_cuda or p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
+                raise ValueError("fit_cross_step needs the module's fp32 parameters on the device of the batch (net.to(device))")
+        if gt.dim() != 3 or gt.dtype != torch.float32 or not gt.is_contiguous():
+            raise ValueError("expected a contiguous fp32 gt (B, h P, w P)")
+        state.prepare(params)
+        lib = _lib.load()
+        inv = 1.0 / gt.numel()
+        grads, loss = state.grads, torch.zeros((), dtype=torch.float64, device=dev)
+        H, W = gt.shape[1:]
+
+        def backward(b0, b1):
+            _lib.check(lib.cs_cross_backward(self._handle, C.c_void_p(gt[b0:b1].data_ptr()), b1 - b0, H, W, inv, int(b0 > 0),
+                                             *(C.c_void_p(g.data_ptr()) for g in grads), C.c_void_p(loss.data_ptr()),
+                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+        kept = self._cross_keep
+        self._after_sub_batch = backward
+        try:
+            self._ensure_handle(dev)  # (the forward below finds it ready: the switch goes onto the handle it will use)
+            self.fit_cross_keep(True)
+            res = self.forward_cached(query, ref_tokens) if ref_tokens is not None else self.forward(query, refs)
+        finally:
+            self._after_sub_batch = None
+            self.fit_cross_keep(kept)
+        if tuple(res["score_map_ref_cross"].shape) != tuple(gt.shape):
+            raise ValueError(f"gt {tuple(gt.shape)} does not have the score map's shape {tuple(res['score_map_ref_cross'].shape)}")
+        state.step += 1
+        with torch.cuda.device(dev):
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            for p, m, v, g in zip(params, state.m, state.v, grads):
+                _lib.check(lib.cs_op_adamw(C.c_void_p(p.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(g.data_ptr()),
+                                           p.numel(), state.lr, state.betas[0], state.betas[1], state.eps, state.weight_decay, state.step, None,
+                                           stream))
+            _lib.check(lib.cs_set_cross_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[:6]), stream))
+            _lib.check(lib.cs_set_tail_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[6:12]), stream))
+            _lib.check(lib.cs_set_head_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[12:]), stream))
         return loss
 
     # -- debug taps used by the stage-level parity tests (tests/test_hip_stages.py) ------------------------------------

@@ -777,6 +777,72 @@ int cs_debug_tail_inputs(cs_handle h, float* x2, uint16_t* H, int rows, cs_strea
 int cs_set_tail_weights(cs_handle h, const float* w1, const float* b1, const float* w2, const float* b2, const float* g3, const float* b3,
                         cs_stream stream);
 
+/* ---- Attention backward (csrc/attnbwd.hip) ----
+ * The backward of cs_op_attention on the same operands: Q, K, V, O and dO are 16 bit (cs_debug_set_op_operand_dtype), addressed as there (row
+ * stride, batch stride, head hd at column hd * dh), lse (batch, heads, Lq) is what cs_op_attention wrote with the same q_scale.  Per batch item
+ * and head, with Q' = Q (q_scale = 1: the producer folded the scale) or Q * q_scale rounded once (0 = log2(e)/sqrt(dh)), as the forward rounds it:
+ *   S2 = Q' K^T,  P = 2^(S2 - lse),  D[q] = sum_d dO[q][d] O[q][d],  dP = dO V^T,  dz = P (dP - D)                    (all fp32)
+ *   dV = Ph^T dO,  dK = dzh^T Q',  dQ = dzh K             (Ph, dzh: P and dz rounded once to the operand type; fp32 sums, rounded once on store)
+ * dK and dQ are UNSCALED: the gradient with respect to K is ln2 * dK, the one with respect to Q' is ln2 * dQ; a consumer puts the scalar into
+ * its own fp32 reduction.  P is recomputed and never stored; rows past Lq and keys past Lk are neither read nor written.  Three launches, no
+ * atomics, every sum in a fixed order: two identical calls give identical bits.  dK and dV may sit side by side in one buffer.
+ * CS_ERR_BAD_ARG before any launch: a null pointer, a 16-bit operand that is not 16-byte aligned, a workspace that is not 256-byte aligned, a row
+ * or batch stride that is not a multiple of 8 elements, Lk * ldk (or * ldv, Lq * ldq, Lq * lddo) at or above 2^30.  CS_ERR_UNSUPPORTED: dh other
+ * than 16, 48, 96.  ws: device memory of cs_attention_backward_workspace_bytes (0 for an unsupported shape). */
+size_t cs_attention_backward_workspace_bytes(int batch, int heads, int Lq, int Lk, int dh);
+/* the query rows a workgroup of the dQ kernel owns and the keys a workgroup of the dK / dV kernel owns (both also stream the other axis in tiles
+ * of that size), for the tests' edge cases; CS_ERR_UNSUPPORTED for a head dim the backward is not built for */
+int cs_attention_backward_tiles(int dh, int* q_tile, int* k_tile);
+int cs_op_attention_backward(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* O, const uint16_t* dO, const float* lse,
+                             int ldq, int ldk, int ldv, int ldo, int lddo, long long q_bs, long long k_bs, long long v_bs, long long o_bs,
+                             long long do_bs, int batch, int heads, int Lq, int Lk, int dh, float q_scale, uint16_t* dQ, int lddq,
+                             long long dq_bs, uint16_t* dK, int lddk, long long dk_bs, uint16_t* dV, int lddv, long long dv_bs, void* ws,
+                             cs_stream stream);
+
+/* ---- Fitting the last decoder layer's cross-attention with the tail and the head (csrc/crossfit.hip) ----
+ * Sixteen tensors: the layer's multihead_attn.in_proj_weight (3C, C) and in_proj_bias (3C), out_proj.weight (C, C) and bias (C), norm2 weight and
+ * bias (C), and the tail's ten.  M = B Np query rows, Mk = M N memory rows, dh = C / heads.  x1 (M, C) fp32 is the row set that entered the block
+ * (norm1's output, or the layer's input without self-attention); Q' (M, ldq) the 16-bit query projection as the forward stored it (log2(e)/sqrt(dh)
+ * folded in); K, V the layer's column blocks of the packed K | V rows (Mk, ldkv); O (M, ldo) the attention output; lse (B, heads, Np) the kernel's;
+ * mem (Mk, ldm) the reference tokens the K / V projection read.  The backward continues the tail's chain (whose ten gradients and loss come out
+ * bit for bit as cs_op_tail_backward's):
+ *   dx2 = f32(dyh) + dHh W1 (fp32),  y2 = (short_cut ? x1 : 0) + O Wo^T + bo recomputed in fp32,  (dgamma2, dbeta2, dy2h) = the LayerNorm backward
+ *   dbo = inv_count sum_m dy2h,  dWo = inv_count dy2h^T O,  dOh = dy2h Wo rounded once,  (dQu, dKu, dV) = cs_op_attention_backward
+ *   in_proj rows [0, C): inv_count / sqrt(dh) dQu^T x1h (x1 rounded once);  [C, 2C): inv_count ln2 dKu^T mem;  [2C, 3C): inv_count dV^T mem;
+ *   in_proj_bias: the matching column sums (rows [C, 2C) are zero in exact arithmetic and carry rounding residue).
+ * The gradient stops at x1 and at mem.  Fixed summation orders, no atomics.  Pointer, stride and workspace rules are the tail fit's. */
+/* the tail's condition and a head dim the attention backward is built for (16, 48, 96) */
+int cs_cross_fit_supported(int hidden, int heads, int patch);
+size_t cs_cross_backward_workspace_bytes(int B, int Np, int N, int C, int P, int heads);
+/* the whole backward on caller-owned tensors: x1 and x2 contiguous; W1, Wo, W2, Wa (C, C) and Wb (P P, C) packed 16 bit */
+int cs_op_cross_backward(const float* x1, const uint16_t* Qp, int ldq, const uint16_t* K, const uint16_t* V, int ldkv, const uint16_t* O, int ldo,
+                         const float* lse, const uint16_t* mem, int ldm, const uint16_t* W1, int ldw1, const uint16_t* Wo, int ldwo, const float* bo,
+                         const float* gamma2, int N, int heads, int short_cut, const float* x2, const uint16_t* H, int ldh, const uint16_t* X,
+                         int ldx, const uint16_t* A, int lda, const uint16_t* W2, int ldw2, const float* b2, const float* gamma3, float eps,
+                         const uint16_t* Wa, int ldwa, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P,
+                         int C, int act, float powp, double inv_count, int accumulate, float* dWin, float* dbin, float* dWo, float* dbo,
+                         float* dgamma2, float* dbeta2, float* dW1, float* db1, float* dW2, float* db2, float* dgamma3, float* dbeta3, float* dWa,
+                         float* dba, float* dWb, float* dbb, double* loss, void* ws, cs_stream stream);
+/* A persistent switch like cs_fit_tail_keep, off by default, and it implies that switch's two copies.  On: the last decoder layer's cross-attention
+ * also writes its lse, and x1 is copied device-to-device on the forward's stream, in front of the norm2 closing that overwrites it, into a region
+ * the handle owns (one more copy: cs_forward_stats counts cross_keep=1).  Q', the packed K | V rows and O are read from the workspace where the
+ * forward left them (nothing behind that attention writes them), the reference tokens from the caller's ref_tokens (cached mode: keep them alive
+ * until the backward has run) or from the workspace.  The score map, the mean and every tap keep their bits.  Off: nothing of the forward changes. */
+int cs_fit_cross_keep(cs_handle h, int on);
+/* cs_op_cross_backward on what the LAST cs_forward* call on this handle left (with cs_fit_cross_keep on), with the handle's packed weights.
+ * CS_ERR_STATE in the cases of cs_tail_backward, and when that forward ran with cs_fit_cross_keep off. */
+int cs_cross_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWin, float* dbin, float* dWo,
+                      float* dbo, float* dgamma2, float* dbeta2, float* dW1, float* db1, float* dW2, float* db2, float* dgamma3, float* dbeta3,
+                      float* dWa, float* dba, float* dWb, float* dbb, double* loss, cs_stream stream);
+/* debug: contiguous copies of x1 (rows, C) fp32, Q' and O (rows, C) 16 bit, lse (B, heads, Np) fp32 and the K and V rows (rows N, C) 16 bit that
+ * cs_cross_backward would read; any may be NULL; rows as in cs_debug_head_inputs */
+int cs_debug_cross_inputs(cs_handle h, float* x1, uint16_t* Qp, uint16_t* O, float* lse, uint16_t* K, uint16_t* V, int rows, cs_stream stream);
+/* Re-packs fp32 device weights of the LAST decoder layer's cross-attention block (multihead_attn.in_proj_weight (3C, C) and in_proj_bias (3C),
+ * out_proj weight (C, C) and bias (C), norm2 weight and bias (C)) into the finalised handle's existing buffers exactly as cs_finalize packs them
+ * (the query rows with log2(e)/sqrt(dh) folded in), in stream order behind the handle's last call; the race caveat of cs_set_head_weights holds. */
+int cs_set_cross_weights(cs_handle h, const float* in_proj_w, const float* in_proj_b, const float* out_w, const float* out_b, const float* g2,
+                         const float* b2, cs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
