@@ -397,7 +397,7 @@ int cs_debug_read(cs_handle h, const char* name, void* dst, size_t dst_bytes, in
   if (!dst) return 0;
   if (dst_bytes < t.bytes) return fail(CS_ERR_BAD_ARG, "tap '%s' holds %zu bytes, destination %zu", name, t.bytes, dst_bytes);
   hipStream_t st = (hipStream_t)stream;
-  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
+  if (int r = call_enter(h, st)) return r;
   HIPCHK(hipMemcpyAsync(dst, t.d, t.bytes, hipMemcpyDeviceToDevice, st));
   return 0;
 }
@@ -487,15 +487,12 @@ int cs_set_head_weights(cs_handle h, const float* w0, const float* b0, const flo
   if (((uintptr_t)w0 | (uintptr_t)b0 | (uintptr_t)w2 | (uintptr_t)b2) & 3) return fail(CS_ERR_BAD_ARG, "cs_set_head_weights: misaligned pointer");
   hipStream_t st = (hipStream_t)stream;
   const int C = h->cfg.hidden, PP = h->cfg.patch * h->cfg.patch;
-  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
+  if (int r = call_enter(h, st)) return r;
   HIPCHK(cs_pack_f16_launch(w0, C, C, h->Wh0, C, nullptr, nullptr, h->cfg.operand_dtype, st));
   HIPCHK(cs_pack_f16_launch(w2, PP, C, h->Wh2, C, nullptr, nullptr, h->cfg.operand_dtype, st));
   HIPCHK(hipMemcpyAsync(h->bh0, b0, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(h->bh2, b2, (size_t)PP * 4, hipMemcpyDeviceToDevice, st));
-  if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(h->ev_done, st));
-  h->last_stream = st;
-  return 0;
+  return call_leave(h, st);
 }
 
 // Tail fit: a persistent switch like cs_debug_capture, off by default.  With it on, every forward that runs the decoder
@@ -518,17 +515,14 @@ int cs_set_tail_weights(cs_handle h, const float* w1, const float* b1, const flo
   hipStream_t st = (hipStream_t)stream;
   const int C = h->cfg.hidden;
   const DecLayer& D = h->dec.back();
-  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
+  if (int r = call_enter(h, st)) return r;
   HIPCHK(cs_pack_f16_launch(w1, C, C, D.l1W, C, nullptr, nullptr, h->cfg.operand_dtype, st));
   HIPCHK(cs_pack_f16_launch(w2, C, C, D.l2W, C, nullptr, nullptr, h->cfg.operand_dtype, st));
   HIPCHK(hipMemcpyAsync(D.l1b, b1, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(D.l2b, b2, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(D.n3g, g3, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(D.n3b, b3, (size_t)C * 4, hipMemcpyDeviceToDevice, st));
-  if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(h->ev_done, st));
-  h->last_stream = st;
-  return 0;
+  return call_leave(h, st);
 }
 
 // Cross-attention fit: a persistent switch that implies cs_fit_tail_keep's copies; in addition the last layer's cross-attention
@@ -553,7 +547,7 @@ int cs_set_cross_weights(cs_handle h, const float* in_w, const float* in_b, cons
   const size_t C = h->cfg.hidden, l = h->dec.size() - 1;
   const int bf = h->cfg.operand_dtype;
   const DecLayer& D = h->dec.back();
-  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
+  if (int r = call_enter(h, st)) return r;
   HIPCHK(cs_pack_f16_launch(in_w, (int)C, (int)C, D.ca_Wq, (int)C, h->qs_dec, nullptr, bf, st));
   HIPCHK(cs_vec_mul_launch(in_b, h->qs_dec, D.ca_bq, (int)C, st));
   HIPCHK(cs_pack_f16_launch(in_w + C * C, (int)(2 * C), (int)C, h->Wkv_all + l * 2 * C * C, (int)C, nullptr, nullptr, bf, st));
@@ -562,10 +556,7 @@ int cs_set_cross_weights(cs_handle h, const float* in_w, const float* in_b, cons
   HIPCHK(hipMemcpyAsync(D.ca_bo, out_b, C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(D.n2g, g2, C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(D.n2b, b2, C * 4, hipMemcpyDeviceToDevice, st));
-  if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(h->ev_done, st));
-  h->last_stream = st;
-  return 0;
+  return call_leave(h, st);
 }
 
 int cs_debug_set_op_operand_dtype(int dtype) {

@@ -6,13 +6,13 @@
 //   dbo, dWo = gemm_tn(dy2h, O)      dOh = dy2h Wo (16 bit)      (dQu, dKu | dV) = attention backward
 //   in_proj rows [0, C): gemm_tn(dQu, x1h) scaled inv_count / sqrt(dh);  [C, 2C): gemm_tn(dKu, mem) scaled inv_count ln2;  [2C, 3C): gemm_tn(dV, mem)
 // Every sum has a fixed order; nothing is accumulated with atomics.
-#include "cs_common.h"
+#include "fit_shared.h"
 
 #include <cmath>
 
 namespace {
 
-size_t up256(size_t n) { return (n + 255) & ~size_t(255); }
+using namespace cs_fit;
 
 // out (n) fp32 = the values of the 16-bit elements, eight per thread (n a multiple of 8)
 __global__ void widen16_kernel(const h16_t* src, float* out, long long n8, int bf) {
@@ -27,59 +27,46 @@ __global__ void widen16_kernel(const h16_t* src, float* out, long long n8, int b
   reinterpret_cast<float4*>(out)[2 * i + 1] = hi;
 }
 
-CsGemmParams gemm_params(const h16_t* A, int lda, const h16_t* W, int ldw, int M, int C, const float* bias, void* out, int bf) {
-  CsGemmParams g{};
-  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = M; g.N = C; g.K = C; g.bias = bias; g.out = out; g.ldc = C; g.powp = 1.f; g.bf16 = bf;
-  return g;
+// The pieces of one whole backward's workspace, carved in ONE place for the launch, for the parameters its caller checks and for the size: the
+// tail's (tail_carve, which leaves dyh and dHh there), the transposed weight (C, C), a zero bias (C), f32(dyh), dx2 and y2 (M, C) fp32, dy2h, dOh,
+// x1h and dQu (M, C) 16 bit, dKu | dV (Mk, 2C) 16 bit, the attention backward's, ln_backward's partials, gemm_tn's partials for the longer of the
+// two row counts
+struct CrossWs {
+  const h16_t *dyh, *dHh; h16_t* WT; float *zb, *dyf, *dx2, *y2; h16_t *dy2h, *dOh, *x1h, *dQu, *dKV; void *aws, *lws, *tws; size_t end;
+};
+CrossWs cross_carve(void* base, int B, int Np, int N, int C, int heads) {
+  const int M = B * Np, Mk = M * N;
+  const size_t mc = (size_t)M * C;
+  const TailWs t = tail_carve(base, M, C);
+  Carver w(base, t.end);
+  CrossWs k{};
+  k.dyh = t.dyh; k.dHh = t.dH;
+  k.WT = w.take<h16_t>((size_t)C * C * 2);
+  k.zb = w.take<float>((size_t)C * 4);
+  k.dyf = w.take<float>(mc * 4);
+  k.dx2 = w.take<float>(mc * 4);
+  k.y2 = w.take<float>(mc * 4);
+  k.dy2h = w.take<h16_t>(mc * 2);
+  k.dOh = w.take<h16_t>(mc * 2);
+  k.x1h = w.take<h16_t>(mc * 2);
+  k.dQu = w.take<h16_t>(mc * 2);
+  k.dKV = w.take<h16_t>((size_t)Mk * 2 * C * 2);
+  k.aws = w.take<char>(cs_attnbwd_workspace(B, heads, Np));
+  k.lws = w.take<char>(cs_ln_backward_workspace(M, C));
+  k.tws = w.take<char>(cs_gemm_tn_workspace(Mk > M ? Mk : M, C, C));
+  k.end = w.end();
+  return k;
 }
-
-hipError_t gemm_go(const CsGemmParams& g, int epi, hipStream_t st) {
-  if (cs_gemm_check(&g, epi)) return hipErrorInvalidValue;
-  return cs_gemm_launch(&g, epi, st);
+CrossWs cross_carve(const CsCrossBackward* q, void* ws) {
+  const CsHeadBackward& hq = q->tail.head;
+  return cross_carve(ws, hq.B, hq.gh * hq.gw, q->N, hq.C, q->heads);
 }
 
 }  // namespace
 
 extern "C" {
 
-// the workspace of one whole backward, carved in this order: the tail's (cs_tail_backward_workspace), the transposed weight (C, C), a zero bias (C),
-// f32(dyh), dx2 and y2 (M, C) fp32, dy2h, dOh, x1h and dQu (M, C) 16 bit, dKu | dV (Mk, 2C) 16 bit, the attention backward's, ln_backward's
-// partials, gemm_tn's partials for the longer of the two row counts
-size_t cs_cross_backward_workspace(int M, int Mk, int C, int batch, int heads) {
-  const size_t mc = (size_t)M * C;
-  return cs_tail_backward_workspace(M, C) + up256((size_t)C * C * 2) + up256((size_t)C * 4) + 3 * up256(mc * 4) + 4 * up256(mc * 2) +
-         up256((size_t)Mk * 2 * C * 2) + cs_attnbwd_workspace(batch, heads, M / batch) + cs_ln_backward_workspace(M, C) +
-         cs_gemm_tn_workspace(Mk > M ? Mk : M, C, C);
-}
-
-// the pieces of that workspace, carved in ONE place for the launch and for the parameters its caller checks
-struct CrossWs {
-  const h16_t *dyh, *dHh; h16_t* WT; float *zb, *dyf, *dx2, *y2; h16_t *dy2h, *dOh, *x1h, *dQu, *dKV; void *aws, *lws, *tws;
-};
-static CrossWs cross_carve(const CsCrossBackward* q, void* ws) {
-  const CsHeadBackward& hq = q->tail.head;
-  const int B = hq.B, Np = hq.gh * hq.gw, M = B * Np, C = hq.C;
-  const size_t mc = (size_t)M * C, Mk = (size_t)M * q->N;
-  char* w = static_cast<char*>(ws);
-  CrossWs k{};
-  k.dyh = reinterpret_cast<const h16_t*>(w + cs_tail_backward_dyh_offset(M, C));
-  k.dHh = reinterpret_cast<const h16_t*>(w + cs_tail_backward_dh_offset(M, C));
-  w += cs_tail_backward_workspace(M, C);
-  k.WT = reinterpret_cast<h16_t*>(w); w += up256((size_t)C * C * 2);
-  k.zb = reinterpret_cast<float*>(w); w += up256((size_t)C * 4);
-  k.dyf = reinterpret_cast<float*>(w); w += up256(mc * 4);
-  k.dx2 = reinterpret_cast<float*>(w); w += up256(mc * 4);
-  k.y2 = reinterpret_cast<float*>(w); w += up256(mc * 4);
-  k.dy2h = reinterpret_cast<h16_t*>(w); w += up256(mc * 2);
-  k.dOh = reinterpret_cast<h16_t*>(w); w += up256(mc * 2);
-  k.x1h = reinterpret_cast<h16_t*>(w); w += up256(mc * 2);
-  k.dQu = reinterpret_cast<h16_t*>(w); w += up256(mc * 2);
-  k.dKV = reinterpret_cast<h16_t*>(w); w += up256(Mk * 2 * C * 2);
-  k.aws = w; w += cs_attnbwd_workspace(B, q->heads, Np);
-  k.lws = w; w += cs_ln_backward_workspace(M, C);
-  k.tws = w;
-  return k;
-}
+size_t cs_cross_backward_workspace(int B, int Np, int N, int C, int heads) { return cross_carve(nullptr, B, Np, N, C, heads).end; }
 
 // The attention backward of one cross backward, as the launch below queues it: K and V in place in their packed rows, dKu | dV side by side.
 // cross_backward_run (ops.hip) builds it too and puts it through cs_attnbwd_check with every other check, before the first launch.

@@ -490,7 +490,8 @@ hipError_t cs_scorepool_launch(const void* map, int is_f32, int B, int H, int W,
                                void* scratch, hipStream_t st);
 // sheet.hip
 hipError_t cs_sheet_launch(const CsSheetPanels* panels, int n, uint8_t* canvas, int ch, int cw, hipStream_t st);
-// headfit.hip (workspaces: 256-byte aligned device memory of the size the matching helper reports)
+// headfit.hip (workspaces: 256-byte aligned device memory of the size the matching helper reports; the three whole backwards' are carved in
+// fit_shared.h, each beginning with the one before: the launches leave dpre, dyh and dH there for the next scope)
 int cs_headfit_supported(int C, int P);
 size_t cs_head_grad_z_workspace(int M);
 size_t cs_gemm_tn_workspace(int M, int N, int K);
@@ -498,7 +499,6 @@ size_t cs_head_backward_workspace(int M, int C);
 hipError_t cs_head_grad_z_launch(const CsHeadGradZ* p, void* ws, int bf, hipStream_t st);
 hipError_t cs_gemm_tn_launch(const CsGemmTn* p, void* ws, int bf, hipStream_t st);
 hipError_t cs_head_backward_launch(const CsHeadBackward* p, void* ws, int bf, hipStream_t st);
-size_t cs_head_backward_dpre_offset(int M);  // where cs_head_backward_launch leaves dpre (M, C; 16 bit, rounded once) in its workspace
 // out (cols, ldo) = src (rows, lds)^T in 16 bits, zeros in the columns [rows, ldo)
 hipError_t cs_transpose16_launch(const h16_t* src, int lds, int rows, int cols, h16_t* out, int ldo, hipStream_t st);
 // tailfit.hip
@@ -506,10 +506,8 @@ size_t cs_ln_backward_workspace(int M, int C);
 size_t cs_tail_backward_workspace(int M, int C);
 hipError_t cs_ln_backward_launch(const CsLnBackward* p, void* ws, int bf, hipStream_t st);
 hipError_t cs_tail_backward_launch(const CsTailBackward* p, void* ws, int bf, hipStream_t st);
-size_t cs_tail_backward_dyh_offset(int M, int C);  // where cs_tail_backward_launch leaves dyh and dHh (M, C; 16 bit) in its workspace
-size_t cs_tail_backward_dh_offset(int M, int C);
 // crossfit.hip
-size_t cs_cross_backward_workspace(int M, int Mk, int C, int batch, int heads);
+size_t cs_cross_backward_workspace(int B, int Np, int N, int C, int heads);
 void cs_cross_backward_attn_params(const CsCrossBackward* p, void* ws, int bf, CsAttnBwdParams* out);  // the attention backward it queues
 hipError_t cs_cross_backward_launch(const CsCrossBackward* p, void* ws, int bf, hipStream_t st);
 hipError_t cs_adamw_launch(float* p, float* m, float* v, const float* g, long long n, float lr, float beta1, float beta2, float eps, float wd,

@@ -99,7 +99,7 @@ struct cs_model {
   std::vector<Tables> tables;
   float *pos_tab = nullptr, *pe_tab = nullptr;  // the current shape's (point into `tables` or at the parameters)
   // workspace; a workspace that had to grow is retired behind an event and freed once that event has completed
-  char* ws = nullptr; size_t ws_bytes = 0;
+  void* ws = nullptr; size_t ws_bytes = 0;
   struct Retired { void* p; hipEvent_t ev; };
   std::vector<Retired> retired;
   // lanes: internal streams that run independent image chunks / batch groups concurrently (forked from and joined to
@@ -218,6 +218,12 @@ int cross_backward_run(const char* op, const CsCrossBackward& q, void* ws, int b
 
 // forward.hip
 void reap_retired(cs_model* m, bool all);                        // frees retired workspaces whose last use has completed (never blocks unless `all`)
+// *buf holds at least `need` bytes afterwards: a smaller one is retired behind an event recorded on `st` (freed by reap_retired) and replaced
+int grow_retired(cs_model* m, void** buf, size_t* bytes, size_t need, hipStream_t st);
+// The bracket of a call that works on the handle's buffers on `st`: call_enter orders it behind the handle's last call (which may have come on
+// another stream; calls on one stream are ordered anyway), call_leave makes it the last call.
+int call_enter(cs_model* m, hipStream_t st);
+int call_leave(cs_model* m, hipStream_t st);
 int streams_overlap(hipStream_t a, hipStream_t b, bool* yes);  // do kernels queued on a and b run side by side? (waits for both)
 
 // The forward's workspace, carved 256-byte aligned: make_plan(h, ..., nullptr).total is what cs_workspace_bytes reports.

@@ -4,6 +4,7 @@
 // CrossReferenceNet.forward (model/cross_reference.py:52-94) and the post-norm decoder layer (transformer.py:157-173).
 // forward_body at the end of the file is the sequence; the functions before it are its steps, in order.
 #include "cs_model.h"
+#include "fit_shared.h"
 
 #include <chrono>
 #include <cstdio>
@@ -24,6 +25,34 @@ void reap_retired(cs_model* m, bool all) {
   }
 }
 
+// Grows one of the handle's buffers.  The old one may still be in use by work queued earlier (on this or another stream), so it is retired
+// behind an event recorded on `st` (which is ordered after every earlier call) and freed by a later call once that event has completed -- no
+// wait here.
+int grow_retired(cs_model* m, void** buf, size_t* bytes, size_t need, hipStream_t st) {
+  if (need <= *bytes) return 0;
+  if (*buf) {
+    cs_model::Retired r{*buf, nullptr};
+    HIPCHK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(r.ev, st));
+    m->retired.push_back(r);
+  }
+  *buf = nullptr; *bytes = 0;
+  HIPCHK(hipMalloc(buf, need));
+  *bytes = need;
+  return 0;
+}
+
+int call_enter(cs_model* m, hipStream_t st) {
+  if (m->ev_done && m->last_stream != st) HIPCHK(hipStreamWaitEvent(st, m->ev_done, 0));
+  return 0;
+}
+
+int call_leave(cs_model* m, hipStream_t st) {
+  if (!m->ev_done) HIPCHK(hipEventCreateWithFlags(&m->ev_done, hipEventDisableTiming));
+  HIPCHK(hipEventRecord(m->ev_done, st));
+  m->last_stream = st;
+  return 0;
+}
 
 // Do kernels queued on streams a and b run side by side?  The HIP runtime multiplexes streams onto GPU_MAX_HW_QUEUES hardware queues,
 // and hardware queues onto the pipes of the compute micro-engine.  Two streams on one queue serialise outright; two queues on one
@@ -107,6 +136,9 @@ struct Arena {  // carve 256-byte aligned pieces out of the workspace
     return p;
   }
 };
+
+// cs_model::tail_kept holds x2 (M, C) fp32 and, from the next 256 bytes on, H (M, C) 16 bit: x2's share (keep_tail writes, kept_H reads)
+size_t kept_x2_bytes(size_t M, size_t C) { return cs_fit::up256(M * C * 4); }
 
 Plan make_plan(const cs_model* m, int B, int N, int N_enc, int H, int W, char* base, int R_sel = 0, bool own_sim = false, bool grouped = false) {
   Plan p{};
@@ -317,20 +349,8 @@ struct Fwd {
     const bool own_sim = mode == 3 && !sel->sim_out;
     const size_t need = make_plan(h, B, N_plan, N_enc, H, W, nullptr, R_sel, own_sim, grouped).total;
     reap_retired(h, false);
-    if (need > h->ws_bytes) {
-      // grow: the old workspace may still be in use by work queued earlier (on this or another stream), so it is retired behind an
-      // event recorded on this call's stream (which is ordered after every earlier call) and freed by a later call once that event has completed -- no wait here
-      if (h->ws) {
-        cs_model::Retired r{h->ws, nullptr};
-        HIPCHK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(r.ev, st));  // st already waits for the previous call's stream (forward_impl)
-        h->retired.push_back(r);
-      }
-      h->ws = nullptr; h->ws_bytes = 0;
-      HIPCHK(hipMalloc(&h->ws, need));
-      h->ws_bytes = need;
-    }
-    p = make_plan(h, B, N_plan, N_enc, H, W, h->ws, R_sel, own_sim, grouped);
+    if (int r = grow_retired(h, &h->ws, &h->ws_bytes, need, st)) return r;  // st already waits for the previous call's stream (forward_impl)
+    p = make_plan(h, B, N_plan, N_enc, H, W, static_cast<char*>(h->ws), R_sel, own_sim, grouped);
     return 0;
   }
 
@@ -729,18 +749,8 @@ struct Fwd {
   // H = relu(linear1(x2)); both are overwritten by the time the forward returns, so they are copied into the handle's own region here
   // (M C fp32, then M C 16 bit), which grows like the workspace does.
   int keep_tail(hipStream_t s) {
-    const size_t M = (size_t)B * p.Np, xb = (M * p.C * 4 + 255) & ~size_t(255), need = xb + M * p.C * 2;
-    if (need > h->tail_kept_bytes) {
-      if (h->tail_kept) {
-        cs_model::Retired r{h->tail_kept, nullptr};
-        HIPCHK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(r.ev, s));
-        h->retired.push_back(r);
-      }
-      h->tail_kept = nullptr; h->tail_kept_bytes = 0;
-      HIPCHK(hipMalloc(&h->tail_kept, need));
-      h->tail_kept_bytes = need;
-    }
+    const size_t M = (size_t)B * p.Np, xb = kept_x2_bytes(M, p.C), need = xb + M * p.C * 2;
+    if (int r = grow_retired(h, &h->tail_kept, &h->tail_kept_bytes, need, s)) return r;
     HIPCHK(hipMemcpyAsync(h->tail_kept, p.xq, M * p.C * 4, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(static_cast<char*>(h->tail_kept) + xb, p.dhid, M * p.C * 2, hipMemcpyDeviceToDevice, s));
     h->census["tail_keep"] += 2;
@@ -755,17 +765,7 @@ struct Fwd {
   // cross-attention) or p.lse, and mem is the caller's ref_tokens or p.mem_bf, which only the encoder / the gather write.
   int keep_x1(hipStream_t s) {
     const size_t need = (size_t)B * p.Np * p.C * 4;
-    if (need > h->cross_kept_bytes) {
-      if (h->cross_kept) {
-        cs_model::Retired r{h->cross_kept, nullptr};
-        HIPCHK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(r.ev, s));
-        h->retired.push_back(r);
-      }
-      h->cross_kept = nullptr; h->cross_kept_bytes = 0;
-      HIPCHK(hipMalloc(&h->cross_kept, need));
-      h->cross_kept_bytes = need;
-    }
+    if (int r = grow_retired(h, &h->cross_kept, &h->cross_kept_bytes, need, s)) return r;
     HIPCHK(hipMemcpyAsync(h->cross_kept, p.xq, need, hipMemcpyDeviceToDevice, s));
     h->census["cross_keep"] += 1;
     cross_kept = true;
@@ -893,7 +893,7 @@ int forward_impl(Fwd f) {
   cs_model* h = f.h;
   if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
   if (f.mode != 2) { f.use = h->ref_use; h->ref_use = cs_model::RefUse{}; }  // one-shot: gone whatever this call returns
-  if (h->ev_done && h->last_stream != f.st) HIPCHK(hipStreamWaitEvent(f.st, h->ev_done, 0));
+  if (int r = call_enter(h, f.st)) return r;
   h->census.clear();
   const auto t0 = std::chrono::steady_clock::now();
   if (f.u8) cs_preprocess_tables_hold(1);  // (the filter tables its descriptors point at stay put until everything is queued: preprocess.hip)
@@ -908,9 +908,7 @@ int forward_impl(Fwd f) {
     lf.mem = f.mode == 1 ? f.ref_tokens : f.p.mem_bf;
   }
   h->host_enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(h->ev_done, f.st));
-  h->last_stream = f.st;
+  if (int r = call_leave(h, f.st)) return r;
   return rc;
 }
 
@@ -1004,15 +1002,42 @@ int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const ui
   return forward_select(h, nullptr, &u, bank_tokens, s, B, N, H, W, score_out, attn_out, head_id, mean_out, stream);
 }
 
-// ---- head fit: the backward of the head over what the last forward left in the workspace ----
-// The closing launch of the decoder writes the normalised rows in fp32 (p.xq) and, where the head's first linear rides along (rowln.hip), no
-// 16-bit copy: X is rounded here from p.xq, the rounding the forward's own operand went through.  The workspace of the backward is the
-// handle's own allocation (X, then cs_head_backward_workspace), grown like the forward's.
-// `tail`: the call is the tail's -- the last forward must have kept x2 and H, and the workspace is the tail backward's.
-// `level` 2: the call is the cross-attention fit's -- x1 and lse kept as well, the workspace is that backward's.
-// the state a fit call needs, without touching the handle: the checks of head_fit_inputs (below), which calls this first
-static int fit_state_check(cs_model* h, int B, int H, int W, const char* op, int level) {
-  const bool tail = level >= 1, cross = level >= 2;
+}  // extern "C"
+
+// ---- fitting on the device: the backward of a fit scope over what the last forward left behind ----
+// The scopes are nested.  FIT_HEAD (f15) is the regression head; the closing launch of the decoder writes the normalised rows in fp32 (p.xq) and,
+// where the head's first linear rides along (rowln.hip), no 16-bit copy, so X is rounded here from p.xq, the rounding the forward's own operand
+// went through.  FIT_TAIL (f16) adds the last layer's feed-forward block and norm3: the last forward must have kept x2 and H (cs_fit_tail_keep).
+// FIT_CROSS (f17) adds that layer's cross-attention and norm2: x1 and lse kept as well (cs_fit_cross_keep).  The workspace of a backward is the
+// handle's own allocation (X, then the scope's cs_*_backward_workspace, each of which begins with its parent's), grown like the forward's.
+namespace {
+
+enum FitScope { FIT_HEAD, FIT_TAIL, FIT_CROSS };
+
+int last_rows(const cs_model* h) { return h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch); }
+
+const h16_t* kept_H(const cs_model* h, size_t M) {
+  return reinterpret_cast<const h16_t*>(static_cast<const char*>(h->tail_kept) + kept_x2_bytes(M, h->cfg.hidden));
+}
+
+// what a caller of the three backwards can get wrong, refused before fit_inputs allocates or queues the rounding of X (the *_backward_run of
+// ops.hip check again, with the handle's own operands)
+int fit_args_check(const char* op, const cs_model* h, int B, const float* gt, std::initializer_list<const float*> outs, const double* loss,
+                   double inv_count, bool needs_decoder) {
+  if (B <= 0) return fail(CS_ERR_BAD_ARG, "%s: empty batch", op);
+  bool null = !gt || !loss;
+  uintptr_t bits = (uintptr_t)gt;
+  for (const float* o : outs) { null = null || !o; bits |= (uintptr_t)o; }
+  if (null) return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
+  if ((bits & 3) || ((uintptr_t)loss & 7)) return fail(CS_ERR_BAD_ARG, "%s: misaligned pointer (fp32 4 bytes, the loss 8)", op);
+  if (!(inv_count > 0.0)) return fail(CS_ERR_BAD_ARG, "%s: inv_count must be positive", op);
+  if (h && h->cfg.act == 1 && h->cfg.pow_p != 1.0f) return fail(CS_ERR_UNSUPPORTED, "%s: tanh with a power factor other than 1 is not built", op);
+  if (needs_decoder && h && h->finalized && h->dec.empty()) return fail(CS_ERR_STATE, "%s: the handle has no decoder layer", op);
+  return 0;
+}
+
+// the state a fit call of `scope` needs, without touching the handle; B > 0: the shape the caller names is the last forward's
+int fit_state_check(cs_model* h, int B, int H, int W, const char* op, FitScope scope) {
   if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
   if (!h->finalized) return fail(CS_ERR_STATE, "%s before cs_finalize", op);
   const cs_model::LastForward& lf = h->last_fwd;
@@ -1022,156 +1047,121 @@ static int fit_state_check(cs_model* h, int B, int H, int W, const char* op, int
     return fail(CS_ERR_STATE, "%s: the last forward ran (B %d, H %d, W %d), this call names (%d, %d, %d)", op, lf.B, lf.H, lf.W, B, H, W);
   const cs_config& c = h->cfg;
   if (!cs_headfit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden a multiple of 64 and patch 14 (hidden %d, patch %d)", op, c.hidden, c.patch);
-  if (tail && !cs_tail_fit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden <= 2048 (hidden %d)", op, c.hidden);
-  if (cross && !cs_cross_fit_supported(c.hidden, c.dec_heads, c.patch))
+  if (scope >= FIT_TAIL && !cs_tail_fit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden <= 2048 (hidden %d)", op, c.hidden);
+  if (scope >= FIT_CROSS && !cs_cross_fit_supported(c.hidden, c.dec_heads, c.patch))
     return fail(CS_ERR_UNSUPPORTED, "%s: the attention backward is built for head dims 16, 48 and 96 (hidden %d, %d heads)", op, c.hidden, c.dec_heads);
-  if (cross && !(lf.cross_kept && lf.tail_kept)) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_cross_keep off", op);
-  if (tail && !lf.tail_kept) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_tail_keep off", op);
+  if (scope >= FIT_CROSS && !(lf.cross_kept && lf.tail_kept)) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_cross_keep off", op);
+  if (scope >= FIT_TAIL && !lf.tail_kept) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_tail_keep off", op);
   return 0;
 }
 
-static int head_fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, const char* op, int* M_out, h16_t** X_out, int level = 0) {
-  if (int r = fit_state_check(h, B, H, W, op, level)) return r;
-  const bool tail = level >= 1, cross = level >= 2;
+// the three cs_debug_*_inputs: the caller's row count against the last forward's, where there is one (fit_state_check refuses the rest)
+int debug_rows_check(const cs_model* h, int rows, const char* op) {
+  if (h && h->finalized && h->last_fwd.ok && h->last_fwd.mode != 2 && rows != last_rows(h))
+    return fail(CS_ERR_BAD_ARG, "%s: the last forward left %d rows, the caller names %d", op, last_rows(h), rows);
+  return 0;
+}
+
+// What a backward of `scope` starts from: the last forward's rows M, X (M, C) rounded to 16 bits at the front of the handle's region, and the
+// scope's workspace behind it.  Enters the call (call_enter): the caller leaves it with call_leave.
+struct FitIn { int M = 0; h16_t* X = nullptr; void* ws = nullptr; };
+int fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, const char* op, FitScope scope, FitIn* in) {
+  if (int r = fit_state_check(h, B, H, W, op, scope)) return r;
   const cs_model::LastForward& lf = h->last_fwd;
   const cs_config& c = h->cfg;
-  const int M = lf.B * (lf.H / c.patch) * (lf.W / c.patch), C = c.hidden;
-  const size_t xbytes = ((size_t)M * C * 2 + 255) & ~size_t(255),
-               need = xbytes + (cross ? cs_cross_backward_workspace(M, M * lf.N, C, lf.B, c.dec_heads)
-                                      : tail ? cs_tail_backward_workspace(M, C) : cs_head_backward_workspace(M, C));
-  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
-  if (need > h->hfit_ws_bytes) {
-    if (h->hfit_ws) {
-      cs_model::Retired r{h->hfit_ws, nullptr};
-      HIPCHK(hipEventCreateWithFlags(&r.ev, hipEventDisableTiming));
-      HIPCHK(hipEventRecord(r.ev, st));
-      h->retired.push_back(r);
-    }
-    h->hfit_ws = nullptr; h->hfit_ws_bytes = 0;
-    HIPCHK(hipMalloc(&h->hfit_ws, need));
-    h->hfit_ws_bytes = need;
-  }
-  h16_t* X = static_cast<h16_t*>(h->hfit_ws);
-  HIPCHK(cs_pack_f16_launch(lf.xq, M, C, X, C, nullptr, nullptr, c.operand_dtype, st));
-  *M_out = M; *X_out = X;
+  const int M = last_rows(h), C = c.hidden;
+  const size_t xbytes = cs_fit::up256((size_t)M * C * 2),
+               need = xbytes + (scope == FIT_CROSS ? cs_cross_backward_workspace(lf.B, M / lf.B, lf.N, C, c.dec_heads)
+                                : scope == FIT_TAIL ? cs_tail_backward_workspace(M, C) : cs_head_backward_workspace(M, C));
+  if (int r = call_enter(h, st)) return r;
+  if (int r = grow_retired(h, &h->hfit_ws, &h->hfit_ws_bytes, need, st)) return r;
+  in->M = M; in->X = static_cast<h16_t*>(h->hfit_ws); in->ws = static_cast<char*>(h->hfit_ws) + xbytes;
+  HIPCHK(cs_pack_f16_launch(lf.xq, M, C, in->X, C, nullptr, nullptr, c.operand_dtype, st));
   return 0;
 }
 
-static int head_fit_done(cs_model* h, hipStream_t st) {
-  if (!h->ev_done) HIPCHK(hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming));
-  HIPCHK(hipEventRecord(h->ev_done, st));
-  h->last_stream = st;
-  return 0;
-}
-
-int cs_head_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWa, float* dba, float* dWb,
-                     float* dbb, double* loss, cs_stream stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (B <= 0) return fail(CS_ERR_BAD_ARG, "cs_head_backward: empty batch");
-  if (!gt || !dWa || !dba || !dWb || !dbb || !loss) return fail(CS_ERR_BAD_ARG, "cs_head_backward: null pointer");
-  // everything the caller can get wrong is refused here, before head_fit_inputs allocates or queues the rounding of X (head_backward_run checks
-  // again, with the handle's own operands)
-  if ((((uintptr_t)gt | (uintptr_t)dWa | (uintptr_t)dba | (uintptr_t)dWb | (uintptr_t)dbb) & 3) || ((uintptr_t)loss & 7))
-    return fail(CS_ERR_BAD_ARG, "cs_head_backward: misaligned pointer (fp32 4 bytes, the loss 8)");
-  if (!(inv_count > 0.0)) return fail(CS_ERR_BAD_ARG, "cs_head_backward: inv_count must be positive");
-  if (h && h->cfg.act == 1 && h->cfg.pow_p != 1.0f) return fail(CS_ERR_UNSUPPORTED, "cs_head_backward: tanh with a power factor other than 1 is not built");
-  int M = 0; h16_t* X = nullptr;
-  if (int r = head_fit_inputs(h, B, H, W, st, "cs_head_backward", &M, &X)) return r;
+CsHeadBackward fill_head_backward(const cs_model* h, const h16_t* X, const float* gt, int B, int H, int W, double inv_count, int accumulate,
+                                  float* dWa, float* dba, float* dWb, float* dbb, double* loss) {
   const cs_config& c = h->cfg;
   const int C = c.hidden;
   CsHeadBackward q{};
   q.X = X; q.ldx = C; q.A = h->last_fwd.dhid; q.lda = C; q.Wb = h->Wh2; q.ldw = C; q.bb = h->bh2; q.gt = gt; q.B = B; q.gh = H / c.patch; q.gw = W / c.patch;
   q.P = c.patch; q.C = C; q.act = c.act; q.powp = c.pow_p; q.inv_count = inv_count; q.accumulate = accumulate != 0;
   q.dWa = dWa; q.dba = dba; q.dWb = dWb; q.dbb = dbb; q.loss = loss;
-  char* ws = static_cast<char*>(h->hfit_ws) + (((size_t)M * C * 2 + 255) & ~size_t(255));
-  const int rc = head_backward_run("cs_head_backward", q, ws, c.operand_dtype, st);
-  if (int r = head_fit_done(h, st)) return r;
-  return rc;
+  return q;
+}
+
+// (everything but .head)
+CsTailBackward fill_tail_backward(const cs_model* h, int M, float* dW1, float* db1, float* dW2, float* db2, float* dg3, float* db3) {
+  const int C = h->cfg.hidden;
+  const DecLayer& D = h->dec.back();
+  CsTailBackward q{};
+  q.x2 = static_cast<const float*>(h->tail_kept); q.H = kept_H(h, M); q.ldh = C;
+  q.W2 = D.l2W; q.ldw2 = C; q.b2 = D.l2b; q.gamma3 = D.n3g; q.eps = 1e-5f; q.Wa = h->Wh0; q.ldwa = C;
+  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dg3; q.db3 = db3;
+  return q;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cs_head_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWa, float* dba, float* dWb,
+                     float* dbb, double* loss, cs_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int r = fit_args_check("cs_head_backward", h, B, gt, {dWa, dba, dWb, dbb}, loss, inv_count, false)) return r;
+  FitIn in;
+  if (int r = fit_inputs(h, B, H, W, st, "cs_head_backward", FIT_HEAD, &in)) return r;
+  const CsHeadBackward q = fill_head_backward(h, in.X, gt, B, H, W, inv_count, accumulate, dWa, dba, dWb, dbb, loss);
+  const int rc = head_backward_run("cs_head_backward", q, in.ws, h->cfg.operand_dtype, st);
+  const int r = call_leave(h, st);
+  return r ? r : rc;
 }
 
 int cs_debug_head_inputs(cs_handle h, uint16_t* X_out, uint16_t* A_out, int rows, cs_stream stream) {
   hipStream_t st = (hipStream_t)stream;
-  int M = 0; h16_t* X = nullptr;
-  if (h && h->finalized && h->last_fwd.ok && h->last_fwd.mode != 2 &&
-      rows != h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch))
-    return fail(CS_ERR_BAD_ARG, "cs_debug_head_inputs: the last forward left %d rows, the caller names %d",
-                h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch), rows);
-  if (int r = head_fit_inputs(h, 0, 0, 0, st, "cs_debug_head_inputs", &M, &X)) return r;
-  const size_t bytes = (size_t)M * h->cfg.hidden * 2;
-  if (X_out) HIPCHK(hipMemcpyAsync(X_out, X, bytes, hipMemcpyDeviceToDevice, st));
+  if (int r = debug_rows_check(h, rows, "cs_debug_head_inputs")) return r;
+  FitIn in;
+  if (int r = fit_inputs(h, 0, 0, 0, st, "cs_debug_head_inputs", FIT_HEAD, &in)) return r;
+  const size_t bytes = (size_t)in.M * h->cfg.hidden * 2;
+  if (X_out) HIPCHK(hipMemcpyAsync(X_out, in.X, bytes, hipMemcpyDeviceToDevice, st));
   if (A_out) HIPCHK(hipMemcpyAsync(A_out, h->last_fwd.dhid, bytes, hipMemcpyDeviceToDevice, st));
-  return head_fit_done(h, st);
+  return call_leave(h, st);
 }
 
-// ---- tail fit: the same over the last layer's feed-forward block, norm3 and the head, on what a forward with
-// cs_fit_tail_keep left behind ----
 int cs_tail_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dW1, float* db1, float* dW2,
                      float* db2, float* dg3, float* db3, float* dWa, float* dba, float* dWb, float* dbb, double* loss, cs_stream stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (B <= 0) return fail(CS_ERR_BAD_ARG, "cs_tail_backward: empty batch");
-  uintptr_t bits = (uintptr_t)gt;
-  for (const float* o : {dW1, db1, dW2, db2, dg3, db3, dWa, dba, dWb, dbb}) {
-    if (!o) return fail(CS_ERR_BAD_ARG, "cs_tail_backward: null pointer");
-    bits |= (uintptr_t)o;
-  }
-  if (!gt || !loss) return fail(CS_ERR_BAD_ARG, "cs_tail_backward: null pointer");
-  if ((bits & 3) || ((uintptr_t)loss & 7)) return fail(CS_ERR_BAD_ARG, "cs_tail_backward: misaligned pointer (fp32 4 bytes, the loss 8)");
-  if (!(inv_count > 0.0)) return fail(CS_ERR_BAD_ARG, "cs_tail_backward: inv_count must be positive");
-  if (h && h->cfg.act == 1 && h->cfg.pow_p != 1.0f) return fail(CS_ERR_UNSUPPORTED, "cs_tail_backward: tanh with a power factor other than 1 is not built");
-  int M = 0; h16_t* X = nullptr;
-  if (h && h->finalized && h->dec.empty()) return fail(CS_ERR_STATE, "cs_tail_backward: the handle has no decoder layer");
-  if (int r = head_fit_inputs(h, B, H, W, st, "cs_tail_backward", &M, &X, 1)) return r;
-  const cs_config& c = h->cfg;
-  const int C = c.hidden;
-  const DecLayer& D = h->dec.back();
-  CsTailBackward q{};
-  q.x2 = static_cast<const float*>(h->tail_kept);
-  q.H = reinterpret_cast<const h16_t*>(static_cast<const char*>(h->tail_kept) + (((size_t)M * C * 4 + 255) & ~size_t(255))); q.ldh = C;
-  q.W2 = D.l2W; q.ldw2 = C; q.b2 = D.l2b; q.gamma3 = D.n3g; q.eps = 1e-5f; q.Wa = h->Wh0; q.ldwa = C;
-  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dg3; q.db3 = db3;
-  CsHeadBackward& hq = q.head;
-  hq.X = X; hq.ldx = C; hq.A = h->last_fwd.dhid; hq.lda = C; hq.Wb = h->Wh2; hq.ldw = C; hq.bb = h->bh2; hq.gt = gt; hq.B = B; hq.gh = H / c.patch;
-  hq.gw = W / c.patch; hq.P = c.patch; hq.C = C; hq.act = c.act; hq.powp = c.pow_p; hq.inv_count = inv_count; hq.accumulate = accumulate != 0;
-  hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb; hq.loss = loss;
-  char* ws = static_cast<char*>(h->hfit_ws) + (((size_t)M * C * 2 + 255) & ~size_t(255));
-  const int rc = tail_backward_run("cs_tail_backward", q, ws, c.operand_dtype, st);
-  if (int r = head_fit_done(h, st)) return r;
-  return rc;
+  if (int r = fit_args_check("cs_tail_backward", h, B, gt, {dW1, db1, dW2, db2, dg3, db3, dWa, dba, dWb, dbb}, loss, inv_count, true)) return r;
+  FitIn in;
+  if (int r = fit_inputs(h, B, H, W, st, "cs_tail_backward", FIT_TAIL, &in)) return r;
+  CsTailBackward q = fill_tail_backward(h, in.M, dW1, db1, dW2, db2, dg3, db3);
+  q.head = fill_head_backward(h, in.X, gt, B, H, W, inv_count, accumulate, dWa, dba, dWb, dbb, loss);
+  const int rc = tail_backward_run("cs_tail_backward", q, in.ws, h->cfg.operand_dtype, st);
+  const int r = call_leave(h, st);
+  return r ? r : rc;
 }
 
 int cs_debug_tail_inputs(cs_handle h, float* x2_out, uint16_t* H_out, int rows, cs_stream stream) {
   hipStream_t st = (hipStream_t)stream;
-  int M = 0; h16_t* X = nullptr;
-  if (h && h->finalized && h->last_fwd.ok && h->last_fwd.mode != 2 &&
-      rows != h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch))
-    return fail(CS_ERR_BAD_ARG, "cs_debug_tail_inputs: the last forward left %d rows, the caller names %d",
-                h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch), rows);
-  if (int r = head_fit_inputs(h, 0, 0, 0, st, "cs_debug_tail_inputs", &M, &X, 1)) return r;
-  const size_t n = (size_t)M * h->cfg.hidden;
+  if (int r = debug_rows_check(h, rows, "cs_debug_tail_inputs")) return r;
+  FitIn in;
+  if (int r = fit_inputs(h, 0, 0, 0, st, "cs_debug_tail_inputs", FIT_TAIL, &in)) return r;
+  const size_t n = (size_t)in.M * h->cfg.hidden;
   if (x2_out) HIPCHK(hipMemcpyAsync(x2_out, h->tail_kept, n * 4, hipMemcpyDeviceToDevice, st));
-  if (H_out) HIPCHK(hipMemcpyAsync(H_out, static_cast<const char*>(h->tail_kept) + ((n * 4 + 255) & ~size_t(255)), n * 2, hipMemcpyDeviceToDevice, st));
-  return head_fit_done(h, st);
+  if (H_out) HIPCHK(hipMemcpyAsync(H_out, kept_H(h, in.M), n * 2, hipMemcpyDeviceToDevice, st));
+  return call_leave(h, st);
 }
 
-// ---- cross-attention fit: the same over the last layer's cross-attention block as well, on what a forward with
-// cs_fit_cross_keep left behind ----
 int cs_cross_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWin, float* dbin, float* dWo,
                       float* dbo, float* dgamma2, float* dbeta2, float* dW1, float* db1, float* dW2, float* db2, float* dg3, float* db3, float* dWa,
                       float* dba, float* dWb, float* dbb, double* loss, cs_stream stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (B <= 0) return fail(CS_ERR_BAD_ARG, "cs_cross_backward: empty batch");
-  uintptr_t bits = (uintptr_t)gt;
-  for (const float* o : {dWin, dbin, dWo, dbo, dgamma2, dbeta2, dW1, db1, dW2, db2, dg3, db3, dWa, dba, dWb, dbb}) {
-    if (!o) return fail(CS_ERR_BAD_ARG, "cs_cross_backward: null pointer");
-    bits |= (uintptr_t)o;
-  }
-  if (!gt || !loss) return fail(CS_ERR_BAD_ARG, "cs_cross_backward: null pointer");
-  if ((bits & 3) || ((uintptr_t)loss & 7)) return fail(CS_ERR_BAD_ARG, "cs_cross_backward: misaligned pointer (fp32 4 bytes, the loss 8)");
-  if (!(inv_count > 0.0)) return fail(CS_ERR_BAD_ARG, "cs_cross_backward: inv_count must be positive");
-  if (h && h->cfg.act == 1 && h->cfg.pow_p != 1.0f) return fail(CS_ERR_UNSUPPORTED, "cs_cross_backward: tanh with a power factor other than 1 is not built");
-  int M = 0; h16_t* X = nullptr;
-  if (h && h->finalized && h->dec.empty()) return fail(CS_ERR_STATE, "cs_cross_backward: the handle has no decoder layer");
-  if (int r = head_fit_inputs(h, B, H, W, st, "cs_cross_backward", &M, &X, 2)) return r;
+  if (int r = fit_args_check("cs_cross_backward", h, B, gt, {dWin, dbin, dWo, dbo, dgamma2, dbeta2, dW1, db1, dW2, db2, dg3, db3, dWa, dba, dWb, dbb},
+                             loss, inv_count, true))
+    return r;
+  FitIn in;
+  if (int r = fit_inputs(h, B, H, W, st, "cs_cross_backward", FIT_CROSS, &in)) return r;
   const cs_config& c = h->cfg;
   const int C = c.hidden;
   const DecLayer& D = h->dec.back();
@@ -1181,42 +1171,29 @@ int cs_cross_backward(cs_handle h, const float* gt, int B, int H, int W, double 
   x.lse = lf.lse; x.mem = lf.mem; x.ldm = C; x.W1 = D.l1W; x.ldw1 = C; x.Wo = D.ca_Wo; x.ldwo = C; x.bo = D.ca_bo; x.gamma2 = D.n2g;
   x.N = lf.N; x.heads = c.dec_heads; x.short_cut = c.do_short_cut != 0;
   x.dWin = dWin; x.dbin = dbin; x.dWo = dWo; x.dbo = dbo; x.dg2 = dgamma2; x.db2 = dbeta2;
-  CsTailBackward& q = x.tail;
-  q.x2 = static_cast<const float*>(h->tail_kept);
-  q.H = reinterpret_cast<const h16_t*>(static_cast<const char*>(h->tail_kept) + (((size_t)M * C * 4 + 255) & ~size_t(255))); q.ldh = C;
-  q.W2 = D.l2W; q.ldw2 = C; q.b2 = D.l2b; q.gamma3 = D.n3g; q.eps = 1e-5f; q.Wa = h->Wh0; q.ldwa = C;
-  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dg3; q.db3 = db3;
-  CsHeadBackward& hq = q.head;
-  hq.X = X; hq.ldx = C; hq.A = lf.dhid; hq.lda = C; hq.Wb = h->Wh2; hq.ldw = C; hq.bb = h->bh2; hq.gt = gt; hq.B = B; hq.gh = H / c.patch;
-  hq.gw = W / c.patch; hq.P = c.patch; hq.C = C; hq.act = c.act; hq.powp = c.pow_p; hq.inv_count = inv_count; hq.accumulate = accumulate != 0;
-  hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb; hq.loss = loss;
-  char* ws = static_cast<char*>(h->hfit_ws) + (((size_t)M * C * 2 + 255) & ~size_t(255));
-  const int rc = cross_backward_run("cs_cross_backward", x, ws, c.operand_dtype, st);
-  if (int r = head_fit_done(h, st)) return r;
-  return rc;
+  x.tail = fill_tail_backward(h, in.M, dW1, db1, dW2, db2, dg3, db3);
+  x.tail.head = fill_head_backward(h, in.X, gt, B, H, W, inv_count, accumulate, dWa, dba, dWb, dbb, loss);
+  const int rc = cross_backward_run("cs_cross_backward", x, in.ws, c.operand_dtype, st);
+  const int r = call_leave(h, st);
+  return r ? r : rc;
 }
 
 int cs_debug_cross_inputs(cs_handle h, float* x1_out, uint16_t* q_out, uint16_t* o_out, float* lse_out, uint16_t* k_out, uint16_t* v_out, int rows,
                           cs_stream stream) {
   hipStream_t st = (hipStream_t)stream;
-  int M = 0;
-  if (h && h->finalized && h->last_fwd.ok && h->last_fwd.mode != 2 &&
-      rows != h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch))
-    return fail(CS_ERR_BAD_ARG, "cs_debug_cross_inputs: the last forward left %d rows, the caller names %d",
-                h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch), rows);
-  // (the state checks alone: six copies need neither X nor the backward's workspace, which head_fit_inputs would grow the handle's region to)
-  if (int r = fit_state_check(h, 0, 0, 0, "cs_debug_cross_inputs", 2)) return r;
-  if (h->ev_done && h->last_stream != st) HIPCHK(hipStreamWaitEvent(st, h->ev_done, 0));
+  if (int r = debug_rows_check(h, rows, "cs_debug_cross_inputs")) return r;
+  // (the state checks alone: six copies need neither X nor the backward's workspace, which fit_inputs would grow the handle's region to)
+  if (int r = fit_state_check(h, 0, 0, 0, "cs_debug_cross_inputs", FIT_CROSS)) return r;
+  if (int r = call_enter(h, st)) return r;
   const cs_model::LastForward& lf = h->last_fwd;
-  M = lf.B * (lf.H / h->cfg.patch) * (lf.W / h->cfg.patch);
-  const size_t C = h->cfg.hidden, n = (size_t)M * C, Mk = (size_t)M * lf.N;
+  const size_t M = last_rows(h), C = h->cfg.hidden, n = M * C, Mk = M * lf.N;
   if (x1_out) HIPCHK(hipMemcpyAsync(x1_out, h->cross_kept, n * 4, hipMemcpyDeviceToDevice, st));
   if (q_out) HIPCHK(hipMemcpyAsync(q_out, lf.dq, n * 2, hipMemcpyDeviceToDevice, st));
   if (o_out) HIPCHK(hipMemcpyAsync(o_out, lf.dob, n * 2, hipMemcpyDeviceToDevice, st));
-  if (lse_out) HIPCHK(hipMemcpyAsync(lse_out, lf.lse, (size_t)M * h->cfg.dec_heads * 4, hipMemcpyDeviceToDevice, st));
+  if (lse_out) HIPCHK(hipMemcpyAsync(lse_out, lf.lse, M * h->cfg.dec_heads * 4, hipMemcpyDeviceToDevice, st));
   if (k_out) HIPCHK(hipMemcpy2DAsync(k_out, C * 2, lf.k, (size_t)lf.ldkv * 2, C * 2, Mk, hipMemcpyDeviceToDevice, st));
   if (v_out) HIPCHK(hipMemcpy2DAsync(v_out, C * 2, lf.k + C, (size_t)lf.ldkv * 2, C * 2, Mk, hipMemcpyDeviceToDevice, st));
-  return head_fit_done(h, st);
+  return call_leave(h, st);
 }
 
 int cs_u8_input_supported(cs_handle h, const cs_u8_image* im, int H, int W) {

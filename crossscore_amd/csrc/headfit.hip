@@ -12,10 +12,12 @@
 //                 chunk writes an fp32 partial and a second kernel adds the partials in chunk order.  The same pair of kernels sums G's columns
 //                 (the bias gradients).  No atomics anywhere: two runs give the same bits.
 //   adamw         torch.optim.AdamW's single-tensor step in fp32, optionally with the parameter's 16-bit operand copy in the same pass.
-#include "cs_common.h"
+#include "fit_shared.h"
 #include <cmath>
 
 namespace {
+
+using namespace cs_fit;
 
 constexpr int HF_ROWS = CS_HEADFIT_ROW_TILE;   // rows of one workgroup of head_grad_z / head_da: 4 waves x 16
 constexpr int HF_NP = CS_HEADFIT_NPAD;         // g's columns: P*P = 196 padded to whole 32-deep k steps
@@ -244,8 +246,6 @@ __global__ void adamw_kernel(float* p, float* m, float* v, const float* g, long 
   if (p16) p16[i] = f2o(pi, bf);
 }
 
-size_t up256(size_t n) { return (n + 255) & ~size_t(255); }
-
 }  // namespace
 
 extern "C" {
@@ -280,13 +280,8 @@ hipError_t cs_gemm_tn_launch(const CsGemmTn* p, void* ws, int bf, hipStream_t st
   return hipGetLastError();
 }
 
-// the workspace of one whole backward, carved in this order: g (M, 224), dpre (M, C), WbT (C, 224), the loss partials, gemm_tn's partials
-size_t cs_head_backward_workspace(int M, int C) {
-  return up256((size_t)M * HF_NP * 2) + up256((size_t)M * C * 2) + up256((size_t)C * HF_NP * 2) + cs_head_grad_z_workspace(M) +
-         cs_gemm_tn_workspace(M, C > HF_NP ? C : HF_NP, C);
-}
-
-size_t cs_head_backward_dpre_offset(int M) { return up256((size_t)M * HF_NP * 2); }
+// the workspace of one whole backward: head_carve (fit_shared.h), which the launch below takes its pointers from
+size_t cs_head_backward_workspace(int M, int C) { return head_carve(nullptr, M, C).end; }
 
 hipError_t cs_transpose16_launch(const h16_t* src, int lds, int rows, int cols, h16_t* out, int ldo, hipStream_t st) {
   hf_transpose_kernel<<<(cols * ldo + 255) / 256, 256, 0, st>>>(src, lds, rows, cols, out, ldo);
@@ -295,12 +290,9 @@ hipError_t cs_transpose16_launch(const h16_t* src, int lds, int rows, int cols, 
 
 hipError_t cs_head_backward_launch(const CsHeadBackward* q, void* ws, int bf, hipStream_t st) {
   const int M = q->B * q->gh * q->gw, C = q->C, PP = q->P * q->P;
-  char* w = static_cast<char*>(ws);
-  h16_t* g = reinterpret_cast<h16_t*>(w); w += up256((size_t)M * HF_NP * 2);
-  h16_t* dpre = reinterpret_cast<h16_t*>(w); w += up256((size_t)M * C * 2);
-  h16_t* WbT = reinterpret_cast<h16_t*>(w); w += up256((size_t)C * HF_NP * 2);
-  void* zws = w; w += cs_head_grad_z_workspace(M);
-  void* tws = w;
+  const HeadWs k = head_carve(ws, M, C);
+  h16_t *g = k.g, *dpre = k.dpre, *WbT = k.WbT;
+  void *zws = k.zws, *tws = k.tws;
   CsHeadGradZ z{};
   z.A = q->A; z.lda = q->lda; z.Wb = q->Wb; z.ldw = q->ldw; z.bb = q->bb; z.gt = q->gt; z.B = q->B; z.gh = q->gh; z.gw = q->gw; z.P = q->P; z.C = C;
   z.act = q->act; z.powp = q->powp; z.g = g; z.ldg = HF_NP; z.loss = q->loss; z.loss_scale = q->inv_count; z.loss_accumulate = q->accumulate;

@@ -976,7 +976,7 @@ int cs_cross_fit_supported(int hidden, int heads, int patch) {
 
 size_t cs_cross_backward_workspace_bytes(int B, int Np, int N, int C, int P, int heads) {
   if (B <= 0 || Np <= 0 || N <= 0 || !cs_cross_fit_supported(C, heads, P) || (long long)B * Np * N * 2 * C >= (1ll << 31)) return 0;
-  return cs_cross_backward_workspace(B * Np, B * Np * N, C, B, heads);
+  return cs_cross_backward_workspace(B, Np, N, C, heads);
 }
 
 int cs_op_cross_backward(const float* x1, const uint16_t* Qp, int ldq, const uint16_t* K, const uint16_t* V, int ldkv, const uint16_t* O, int ldo,

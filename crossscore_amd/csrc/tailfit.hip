@@ -11,13 +11,13 @@
 //                         partials in workgroup order.  No atomics: two runs give the same bits.
 //   dH = dyh W2           the same transposed-weight GEMM with a 16-bit store, then relu_mask: dH * [H > 0] in place
 //   dW2, db2, dW1, db1    gemm_tn (headfit.hip) over (dyh, H) and (dHh, x2 rounded to the operand type)
-#include "cs_common.h"
+#include "fit_shared.h"
 
 namespace {
 
-constexpr int LNB_ROWS = CS_TAILFIT_LN_ROW_TILE;  // rows of one workgroup
+using namespace cs_fit;
 
-size_t up256(size_t n) { return (n + 255) & ~size_t(255); }
+constexpr int LNB_ROWS = CS_TAILFIT_LN_ROW_TILE;  // rows of one workgroup
 
 __device__ __forceinline__ float sum4(const float4& v) { return (v.x + v.y) + (v.z + v.w); }
 
@@ -155,17 +155,6 @@ template <int V, int NW> hipError_t ln_backward_go(const CsLnBackward& p, float*
   return hipGetLastError();
 }
 
-CsGemmParams gemm_params(const h16_t* A, int lda, const h16_t* W, int ldw, int M, int C, const float* bias, void* out, int bf) {
-  CsGemmParams g{};
-  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = M; g.N = C; g.K = C; g.bias = bias; g.out = out; g.ldc = C; g.powp = 1.f; g.bf16 = bf;
-  return g;
-}
-
-hipError_t gemm_go(const CsGemmParams& g, int epi, hipStream_t st) {
-  if (cs_gemm_check(&g, epi)) return hipErrorInvalidValue;
-  return cs_gemm_launch(&g, epi, st);
-}
-
 }  // namespace
 
 extern "C" {
@@ -186,38 +175,18 @@ hipError_t cs_ln_backward_launch(const CsLnBackward* p, void* ws, int bf, hipStr
   return hipGetLastError();
 }
 
-// the workspace of one whole tail backward, carved in this order: the head's (cs_head_backward_workspace), the transposed weight (C, C), a zero
-// bias (C), dX and y (M, C) fp32, dyh, dH and x2h (M, C) 16 bit, ln_backward's partials, gemm_tn's partials
-size_t cs_tail_backward_workspace(int M, int C) {
-  const size_t mc = (size_t)M * C;
-  return cs_head_backward_workspace(M, C) + up256((size_t)C * C * 2) + up256((size_t)C * 4) + 2 * up256(mc * 4) + 3 * up256(mc * 2) +
-         cs_ln_backward_workspace(M, C) + cs_gemm_tn_workspace(M, C, C);
-}
-
-// where cs_tail_backward_launch leaves dyh and dHh (M, C; 16 bit, contiguous) in its workspace: the cross-attention fit continues from them
-size_t cs_tail_backward_dyh_offset(int M, int C) {
-  const size_t mc = (size_t)M * C;
-  return cs_head_backward_workspace(M, C) + up256((size_t)C * C * 2) + up256((size_t)C * 4) + 2 * up256(mc * 4);
-}
-size_t cs_tail_backward_dh_offset(int M, int C) { return cs_tail_backward_dyh_offset(M, C) + up256((size_t)M * C * 2); }
+// the workspace of one whole tail backward: tail_carve (fit_shared.h), which the launch below takes its pointers from.  dyh and dH (M, C; 16 bit,
+// contiguous) stay in it: the cross-attention fit continues from them
+size_t cs_tail_backward_workspace(int M, int C) { return tail_carve(nullptr, M, C).end; }
 
 hipError_t cs_tail_backward_launch(const CsTailBackward* q, void* ws, int bf, hipStream_t st) {
   const CsHeadBackward& hq = q->head;
   const int M = hq.B * hq.gh * hq.gw, C = hq.C;
-  const size_t mc = (size_t)M * C;
-  char* w = static_cast<char*>(ws);
-  const h16_t* dpre = reinterpret_cast<const h16_t*>(w + cs_head_backward_dpre_offset(M));
-  w += cs_head_backward_workspace(M, C);
-  h16_t* WT = reinterpret_cast<h16_t*>(w); w += up256((size_t)C * C * 2);
-  float* zb = reinterpret_cast<float*>(w); w += up256((size_t)C * 4);
-  float* dX = reinterpret_cast<float*>(w); w += up256(mc * 4);
-  float* y = reinterpret_cast<float*>(w); w += up256(mc * 4);
-  // (dyh and dH through the helpers the cross-attention fit reads them back with: one place knows where they lie)
-  h16_t* dyh = reinterpret_cast<h16_t*>(static_cast<char*>(ws) + cs_tail_backward_dyh_offset(M, C)); w += up256(mc * 2);
-  h16_t* dH = reinterpret_cast<h16_t*>(static_cast<char*>(ws) + cs_tail_backward_dh_offset(M, C)); w += up256(mc * 2);
-  h16_t* x2h = reinterpret_cast<h16_t*>(w); w += up256(mc * 2);
-  void* lws = w; w += cs_ln_backward_workspace(M, C);
-  void* tws = w;
+  const TailWs k = tail_carve(ws, M, C);
+  const h16_t* dpre = k.head.dpre;
+  h16_t *WT = k.WT, *dyh = k.dyh, *dH = k.dH, *x2h = k.x2h;
+  float *zb = k.zb, *dX = k.dX, *y = k.y;
+  void *lws = k.lws, *tws = k.tws;
   const float scale = (float)hq.inv_count;
   hipError_t e = cs_head_backward_launch(&hq, ws, bf, st);  // dWa, dba, dWb, dbb, the loss; dpre stays in the workspace
   if (e != hipSuccess) return e;

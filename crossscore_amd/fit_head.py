@@ -29,11 +29,10 @@ from typing import Dict, Iterable, Optional
 
 import torch
 
-from . import _lib
 from .config import load_config
 from .data import EMPTY, ReferenceTokenCache, decode_items, load_batch, metric_mode
 from .evaluate import gt_file, gt_inputs, gt_map_kind, gt_metric_maps_choice, limit_batches
-from .model import HeadFitState, arch_from_cfg, save_lightning_checkpoint
+from .model import FIT_SCOPES as SCOPE_TABLE, HeadFitState, arch_from_cfg, check_fit_supported, save_lightning_checkpoint
 from .nvs import NvsItems, random_order
 from .scoring import build_net, nvs_input_stage, seed_everything
 
@@ -43,7 +42,7 @@ def step_lr(lr0: float, step_size: int, gamma: float, n: int) -> float:
     return lr0 * gamma ** (n // step_size)
 
 
-FIT_SCOPES = ("head", "tail", "cross")
+FIT_SCOPES = tuple(SCOPE_TABLE)  # head, tail, cross: the names of model.FIT_SCOPES
 
 
 def fit_scope(cfg) -> str:
@@ -83,17 +82,10 @@ def fit_head(cfg, state_dict: Optional[Dict[str, torch.Tensor]] = None, now: Opt
     device = torch.device("cuda", 0)
     torch.cuda.set_device(device)
     seed_everything(int(cfg.lightning.seed))
-    arch = arch_from_cfg(cfg)
-    if not _lib.load().cs_head_fit_supported(arch.hidden, arch.patch):  # (before the weights: they would not fit another patch size either)
-        raise ValueError(f"the head fit is built for hidden a multiple of 64 and patch 14 (hidden {arch.hidden}, patch {arch.patch})")
     scope = fit_scope(cfg)
-    if scope == "tail" and not _lib.load().cs_tail_fit_supported(arch.hidden, arch.patch):
-        raise ValueError(f"the tail fit is built for hidden a multiple of 64 up to 2048 and patch 14 (hidden {arch.hidden}, patch {arch.patch})")
-    if scope == "cross" and not _lib.load().cs_cross_fit_supported(arch.hidden, arch.dec_heads, arch.patch):
-        raise NotImplementedError(f"the cross-attention fit is built for the tail's shapes and decoder head dims 16, 48 and 96 (hidden {arch.hidden}, "
-                                  f"{arch.dec_heads} heads, patch {arch.patch})")
+    check_fit_supported(arch_from_cfg(cfg), scope)  # (before the weights: they would not fit another patch size either)
     net = build_net(cfg, device, state_dict, "fit_head")
-    fit_step = {"head": net.fit_head_step, "tail": net.fit_tail_step, "cross": net.fit_cross_step}[scope]
+    fit_step = getattr(net, f"fit_{scope}_step")
 
     out_dir = cfg.logger.train.out_dir
     if out_dir is None:

@@ -67,6 +67,57 @@ def arch_from_cfg(cfg) -> ArchSpec:
                                do_self_attn=bool(m.decoder_do_self_attn))
 
 
+@dataclasses.dataclass(frozen=True)
+class FitScope:
+    """One scope of on-device fitting.  The scopes are nested through `parent`: a scope's tensors are its own, then its parent's
+    (the order of its backward's gradients); its keep switch implies its parent's; its backward's workspace begins with its parent's.  `own`:
+    the key suffixes of its own tensors behind `prefix` ({last} = the last decoder layer).  The rest are C names (include/crossscore_hip.h),
+    the arch fields cs_*_fit_supported takes, and what check_fit_supported raises for another architecture."""
+    name: str
+    parent: Optional["FitScope"]
+    prefix: str
+    own: tuple
+    supported: str
+    supported_args: tuple
+    keep: Optional[str]
+    backward: str
+    set_weights: str
+    error: type
+    built_for: str
+
+    def chain(self):
+        """this scope, its parent, ... down to the head"""
+        s = self
+        while s is not None:
+            yield s
+            s = s.parent
+
+    def keys(self, dec_layers: int) -> tuple:
+        return tuple(k for s in self.chain() for k in (s.prefix.format(last=dec_layers - 1) + o for o in s.own))
+
+
+_LAST_LAYER = "ref_cross.attn.layers.{last}."
+FIT_HEAD = FitScope("head", None, "ref_cross.head.", ("0.weight", "0.bias", "2.weight", "2.bias"), "cs_head_fit_supported", ("hidden", "patch"),
+                    None, "cs_head_backward", "cs_set_head_weights", ValueError,
+                    "head fit is built for hidden a multiple of 64 and patch 14 (hidden {a.hidden}, patch {a.patch})")
+FIT_TAIL = FitScope("tail", FIT_HEAD, _LAST_LAYER, ("linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm3.weight", "norm3.bias"),
+                    "cs_tail_fit_supported", ("hidden", "patch"), "cs_fit_tail_keep", "cs_tail_backward", "cs_set_tail_weights", ValueError,
+                    "tail fit is built for hidden a multiple of 64 up to 2048 and patch 14 (hidden {a.hidden}, patch {a.patch})")
+FIT_CROSS = FitScope("cross", FIT_TAIL, _LAST_LAYER, ("multihead_attn.in_proj_weight", "multihead_attn.in_proj_bias", "multihead_attn.out_proj.weight",
+                                                      "multihead_attn.out_proj.bias", "norm2.weight", "norm2.bias"),
+                     "cs_cross_fit_supported", ("hidden", "dec_heads", "patch"), "cs_fit_cross_keep", "cs_cross_backward", "cs_set_cross_weights",
+                     NotImplementedError, "cross-attention fit is built for the tail's shapes and decoder head dims 16, 48 and 96 "
+                                          "(hidden {a.hidden}, {a.dec_heads} heads, patch {a.patch})")
+FIT_SCOPES = {s.name: s for s in (FIT_HEAD, FIT_TAIL, FIT_CROSS)}
+
+
+def check_fit_supported(arch: ArchSpec, scope) -> None:
+    """Raises the scope's error unless its backward is built for `arch`; scope: a FitScope or its name."""
+    s = FIT_SCOPES[scope] if isinstance(scope, str) else scope
+    if not getattr(_lib.load(), s.supported)(*(getattr(arch, a) for a in s.supported_args)):
+        raise s.error("the " + s.built_for.format(a=arch))
+
+
 class U8Image:
     """One decoded image on the device with its input-stage geometry (cs_u8_image): data (h, w, 3) uint8 CUDA tensor (rows may be padded:
     row_bytes), rs = size after T.Resize, (crop_y, crop_x) = top-left corner of the processed window.  data None = the all-zero placeholder
@@ -671,66 +722,55 @@ class CrossScoreNet(torch.nn.Module):
                 break
         return {"one_lane_s": one, "lanes_s": seen}
 
-    # -- fitting the regression head ---------------------------------------------------------------
-    HEAD_KEYS = ("ref_cross.head.0.weight", "ref_cross.head.0.bias", "ref_cross.head.2.weight", "ref_cross.head.2.bias")
+    # -- fitting on the device: the scopes FIT_HEAD < FIT_TAIL < FIT_CROSS of the table above ---------------------
+    HEAD_KEYS = FIT_HEAD.keys(0)  # (the head's keys name no layer)
+    TAIL_KEYS = property(lambda self: FIT_TAIL.keys(self.arch.dec_layers), doc="the ten keys of the tail, in the order of cs_tail_backward's gradients")
+    CROSS_KEYS = property(lambda self: FIT_CROSS.keys(self.arch.dec_layers), doc="the sixteen keys of the cross-attention fit, in cs_cross_backward's order")
 
-    def head_parameters(self):
-        """The four tensors of the regression head, the one trainable unit of this build: head.0 weight (C, C) and bias (C), head.2 weight
-        (P P, C) and bias (P P)."""
+    def _fit_parameters(self, scope: FitScope):
         if not self._do_reference_cross:
-            raise ValueError("model.do_reference_cross=False: this module has no regression head")
-        return [self.get_parameter(k) for k in self.HEAD_KEYS]
+            raise ValueError("model.do_reference_cross=False: this module has no regression head and no decoder to fit")
+        return [self.get_parameter(k) for k in scope.keys(self.arch.dec_layers)]
 
-    def head_fit_supported(self) -> bool:
-        return bool(_lib.load().cs_head_fit_supported(self.arch.hidden, self.arch.patch))
+    def _fit_supported(self, scope: FitScope) -> bool:
+        return bool(getattr(_lib.load(), scope.supported)(*(getattr(self.arch, a) for a in scope.supported_args)))
 
-    def head_inputs(self, rows: int):
-        """(X, A): the 16-bit tokens behind the last norm3 and the head's hidden rows of the last forward call, (rows, C) each; rows = its
-        B h w, checked by the library (tests)."""
+    def _fit_keep(self, scope: FitScope, on: bool) -> None:
+        setattr(self, f"_{scope.name}_keep", bool(on))
+        if self._handle is not None:
+            _lib.check(getattr(_lib.load(), scope.keep)(self._handle, int(bool(on))))
+
+    def _fit_backward(self, scope: FitScope, gt, inv_count, accumulate, out):
         if self._handle is None:
-            raise _lib.CrossScoreHipError("head_inputs before any forward")
-        dev = self._handle_device
-        with torch.cuda.device(dev):
-            X = torch.empty((int(rows), self.arch.hidden), dtype=self.token_dtype, device=dev)
-            A = torch.empty_like(X)
-            _lib.check(_lib.load().cs_debug_head_inputs(self._handle, C.c_void_p(X.data_ptr()), C.c_void_p(A.data_ptr()), int(rows),
-                                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        return X, A
-
-    def head_backward(self, gt, inv_count=None, accumulate=False, out=None):
-        """cs_head_backward over the LAST forward call of this module (its last sub-batch): gt (B, h P, w P) fp32 on the device ->
-        (dWa, dba, dWb, dbb, loss): fp32 gradients and the fp64 device scalar loss, each scaled by inv_count (default 1 / gt.numel())."""
-        if self._handle is None:
-            raise _lib.CrossScoreHipError("head_backward before any forward")
+            raise _lib.CrossScoreHipError(f"{scope.name}_backward before any forward")
         dev = self._handle_device
         if gt.dim() != 3 or gt.dtype != torch.float32 or gt.device != dev or not gt.is_contiguous():
             raise ValueError("expected a contiguous fp32 gt (B, H, W) on the module's device")
         B, H, W = gt.shape
-        Cc, PP = self.arch.hidden, self.arch.patch ** 2
         if out is None:
-            out = (torch.zeros((Cc, Cc), device=dev), torch.zeros((Cc,), device=dev), torch.zeros((PP, Cc), device=dev),
-                   torch.zeros((PP,), device=dev), torch.zeros((), dtype=torch.float64, device=dev))
+            out = tuple(torch.zeros(p.shape, device=dev) for p in self._fit_parameters(scope)) + (torch.zeros((), dtype=torch.float64, device=dev),)
         inv = 1.0 / gt.numel() if inv_count is None else float(inv_count)
         with torch.cuda.device(dev):
-            _lib.check(_lib.load().cs_head_backward(self._handle, C.c_void_p(gt.data_ptr()), B, H, W, inv, int(bool(accumulate)),
-                                                    *(C.c_void_p(t.data_ptr()) for t in out),
-                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _lib.check(getattr(_lib.load(), scope.backward)(self._handle, C.c_void_p(gt.data_ptr()), B, H, W, inv, int(bool(accumulate)),
+                                                            *(C.c_void_p(t.data_ptr()) for t in out),
+                                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return out
 
-    def fit_head_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
-        """One AdamW step of the regression head on one batch: the forward through the existing path (forward, in either form of its
-        images; forward_cached with ref_tokens), cs_head_backward behind each sub-batch, cs_op_adamw on the four parameters in place,
-        cs_set_head_weights.  The module is not marked dirty: the handle keeps every other packed weight.  gt: (B, h P, w P) fp32 on the
-        device, the score map's shape.  Returns the loss of the batch BEFORE the step as a device fp64 scalar; nothing is waited for."""
+    def _fit_step(self, scope: FitScope, query, refs, gt, state: "HeadFitState", ref_tokens):
+        """One AdamW step of the scope's tensors on one batch: the forward through the existing path (forward, in either form of its images;
+        forward_cached with ref_tokens) with the scope's keep switch on for the call, the scope's backward behind each sub-batch, cs_op_adamw on
+        every tensor in place, then each scope of the chain hands its own tensors back (cs_set_*_weights).  The module is not marked dirty: the
+        handle keeps every other packed weight.  gt: (B, h P, w P) fp32 on the device, the score map's shape.  Returns the loss of the batch
+        BEFORE the step as a device fp64 scalar; nothing is waited for."""
+        name = f"fit_{scope.name}_step"
         if (refs is None) == (ref_tokens is None):
-            raise ValueError("fit_head_step takes the references either as images (refs) or as cached tokens (ref_tokens)")
-        if not self.head_fit_supported():
-            raise ValueError(f"head fit is built for hidden a multiple of 64 and patch 14 (hidden {self.arch.hidden}, patch {self.arch.patch})")
-        params = self.head_parameters()
+            raise ValueError(f"{name} takes the references either as images (refs) or as cached tokens (ref_tokens)")
+        check_fit_supported(self.arch, scope)
+        params = self._fit_parameters(scope)
         dev = gt.device
         for p in params:
             if not p.is_cuda or p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                raise ValueError("fit_head_step needs the module's fp32 parameters on the device of the batch (net.to(device))")
+                raise ValueError(f"{name} needs the module's fp32 parameters on the device of the batch (net.to(device))")
         if gt.dim() != 3 or gt.dtype != torch.float32 or not gt.is_contiguous():
             raise ValueError("expected a contiguous fp32 gt (B, h P, w P)")
         state.prepare(params)
@@ -738,17 +778,24 @@ class CrossScoreNet(torch.nn.Module):
         inv = 1.0 / gt.numel()
         grads, loss = state.grads, torch.zeros((), dtype=torch.float64, device=dev)
         H, W = gt.shape[1:]
+        c_backward = getattr(lib, scope.backward)
 
         def backward(b0, b1):
-            _lib.check(lib.cs_head_backward(self._handle, C.c_void_p(gt[b0:b1].data_ptr()), b1 - b0, H, W, inv, int(b0 > 0),
-                                            *(C.c_void_p(g.data_ptr()) for g in grads), C.c_void_p(loss.data_ptr()),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _lib.check(c_backward(self._handle, C.c_void_p(gt[b0:b1].data_ptr()), b1 - b0, H, W, inv, int(b0 > 0),
+                                  *(C.c_void_p(g.data_ptr()) for g in grads), C.c_void_p(loss.data_ptr()),
+                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
 
+        kept = getattr(self, f"_{scope.name}_keep") if scope.keep else None
         self._after_sub_batch = backward
         try:
+            if scope.keep:
+                self._ensure_handle(dev)  # (the forward below finds it ready: the switch goes onto the handle it will use)
+                self._fit_keep(scope, True)
             res = self.forward_cached(query, ref_tokens) if ref_tokens is not None else self.forward(query, refs)
         finally:
             self._after_sub_batch = None
+            if scope.keep:
+                self._fit_keep(scope, kept)
         if tuple(res["score_map_ref_cross"].shape) != tuple(gt.shape):
             raise ValueError(f"gt {tuple(gt.shape)} does not have the score map's shape {tuple(res['score_map_ref_cross'].shape)}")
         state.step += 1
@@ -758,219 +805,99 @@ class CrossScoreNet(torch.nn.Module):
                 _lib.check(lib.cs_op_adamw(C.c_void_p(p.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(g.data_ptr()),
                                            p.numel(), state.lr, state.betas[0], state.betas[1], state.eps, state.weight_decay, state.step, None,
                                            stream))
-            _lib.check(lib.cs_set_head_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params), stream))
+            at = 0
+            for s in scope.chain():  # cross, tail, head: each its own tensors
+                own = params[at:at + len(s.own)]
+                _lib.check(getattr(lib, s.set_weights)(self._handle, *(C.c_void_p(p.data_ptr()) for p in own), stream))
+                at += len(own)
         return loss
 
-    # -- fitting the decoder's tail with the head ----------------------------------------------------
-    @property
-    def TAIL_KEYS(self):
-        """The ten keys of the tail: the last decoder layer's linear1, linear2 and norm3, then the head (the order of cs_tail_backward's
-        gradients)."""
-        p = f"ref_cross.attn.layers.{self.arch.dec_layers - 1}."
-        return tuple(p + k for k in ("linear1.weight", "linear1.bias", "linear2.weight", "linear2.bias", "norm3.weight", "norm3.bias")) + self.HEAD_KEYS
+    def head_parameters(self):
+        """The four tensors of the regression head: head.0 weight (C, C) and bias (C), head.2 weight (P P, C) and bias (P P)."""
+        return self._fit_parameters(FIT_HEAD)
 
     def tail_parameters(self):
-        if not self._do_reference_cross:
-            raise ValueError("model.do_reference_cross=False: this module has no decoder to fit")
-        return [self.get_parameter(k) for k in self.TAIL_KEYS]
+        """The last decoder layer's linear1, linear2 and norm3, then the head: ten tensors in TAIL_KEYS order."""
+        return self._fit_parameters(FIT_TAIL)
+
+    def cross_parameters(self):
+        """The last decoder layer's multihead_attn in_proj and out_proj and norm2, then the tail: sixteen tensors in CROSS_KEYS order."""
+        return self._fit_parameters(FIT_CROSS)
+
+    def head_fit_supported(self) -> bool:
+        return self._fit_supported(FIT_HEAD)
 
     def tail_fit_supported(self) -> bool:
-        return bool(_lib.load().cs_tail_fit_supported(self.arch.hidden, self.arch.patch))
+        return self._fit_supported(FIT_TAIL)
+
+    def cross_fit_supported(self) -> bool:
+        return self._fit_supported(FIT_CROSS)
 
     def fit_tail_keep(self, on: bool = True) -> None:
         """Following forwards also keep the last decoder layer's norm2 output and ReLU rows (cs_fit_tail_keep): what tail_backward reads."""
-        self._tail_keep = bool(on)
-        if self._handle is not None:
-            _lib.check(_lib.load().cs_fit_tail_keep(self._handle, int(self._tail_keep)))
-
-    def tail_inputs(self, rows: int):
-        """(x2, H): the fp32 output of the last layer's norm2 and the 16-bit rows relu(linear1(x2)) of the last forward call, (rows, C) each
-        (tests); that forward must have run with fit_tail_keep on."""
-        if self._handle is None:
-            raise _lib.CrossScoreHipError("tail_inputs before any forward")
-        dev = self._handle_device
-        with torch.cuda.device(dev):
-            x2 = torch.empty((int(rows), self.arch.hidden), dtype=torch.float32, device=dev)
-            H = torch.empty((int(rows), self.arch.hidden), dtype=self.token_dtype, device=dev)
-            _lib.check(_lib.load().cs_debug_tail_inputs(self._handle, C.c_void_p(x2.data_ptr()), C.c_void_p(H.data_ptr()), int(rows),
-                                                        C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        return x2, H
-
-    def tail_backward(self, gt, inv_count=None, accumulate=False, out=None):
-        """cs_tail_backward over the LAST forward call of this module (run with fit_tail_keep on): gt (B, h P, w P) fp32 on the device -> the ten
-        fp32 gradients in TAIL_KEYS order and the fp64 device scalar loss, each scaled by inv_count (default 1 / gt.numel())."""
-        if self._handle is None:
-            raise _lib.CrossScoreHipError("tail_backward before any forward")
-        dev = self._handle_device
-        if gt.dim() != 3 or gt.dtype != torch.float32 or gt.device != dev or not gt.is_contiguous():
-            raise ValueError("expected a contiguous fp32 gt (B, H, W) on the module's device")
-        B, H, W = gt.shape
-        if out is None:
-            out = tuple(torch.zeros(p.shape, device=dev) for p in self.tail_parameters()) + (torch.zeros((), dtype=torch.float64, device=dev),)
-        inv = 1.0 / gt.numel() if inv_count is None else float(inv_count)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().cs_tail_backward(self._handle, C.c_void_p(gt.data_ptr()), B, H, W, inv, int(bool(accumulate)),
-                                                    *(C.c_void_p(t.data_ptr()) for t in out),
-                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        return out
-
-    def fit_tail_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
-        """fit_head_step over the ten tensors of the tail: the forward with fit_tail_keep on for the call, cs_tail_backward behind each
-        sub-batch, ten cs_op_adamw launches, cs_set_tail_weights and cs_set_head_weights.  Same contract: the module is not marked dirty, the
-        loss of the batch BEFORE the step comes back as a device fp64 scalar, nothing is waited for."""
-        if (refs is None) == (ref_tokens is None):
-            raise ValueError("fit_tail_step takes the references either as images (refs) or as cached tokens (ref_tokens)")
-        if not self.tail_fit_supported():
-            raise ValueError(f"tail fit is built for hidden a multiple of 64 up to 2048 and patch 14 (hidden {self.arch.hidden}, patch {self.arch.patch})")
-        params = self.tail_parameters()
-        dev = gt.device
-        for p in params:
-            if not p.is_cuda or p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                raise ValueError("fit_tail_step needs the module's fp32 parameters on the device of the batch (net.to(device))")
-        if gt.dim() != 3 or gt.dtype != torch.float32 or not gt.is_contiguous():
-            raise ValueError("expected a contiguous fp32 gt (B, h P, w P)")
-        state.prepare(params)
-        lib = _lib.load()
-        inv = 1.0 / gt.numel()
-        grads, loss = state.grads, torch.zeros((), dtype=torch.float64, device=dev)
-        H, W = gt.shape[1:]
-
-        def backward(b0, b1):
-            _lib.check(lib.cs_tail_backward(self._handle, C.c_void_p(gt[b0:b1].data_ptr()), b1 - b0, H, W, inv, int(b0 > 0),
-                                            *(C.c_void_p(g.data_ptr()) for g in grads), C.c_void_p(loss.data_ptr()),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-
-        kept = self._tail_keep
-        self._after_sub_batch = backward
-        try:
-            self._ensure_handle(dev)  # (the forward below finds it ready: the switch goes onto the handle it will use)
-            self.fit_tail_keep(True)
-            res = self.forward_cached(query, ref_tokens) if ref_tokens is not None else self.forward(query, refs)
-        finally:
-            self._after_sub_batch = None
-            self.fit_tail_keep(kept)
-        if tuple(res["score_map_ref_cross"].shape) != tuple(gt.shape):
-            raise ValueError(f"gt {tuple(gt.shape)} does not have the score map's shape {tuple(res['score_map_ref_cross'].shape)}")
-        state.step += 1
-        with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            for p, m, v, g in zip(params, state.m, state.v, grads):
-                _lib.check(lib.cs_op_adamw(C.c_void_p(p.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(g.data_ptr()),
-                                           p.numel(), state.lr, state.betas[0], state.betas[1], state.eps, state.weight_decay, state.step, None,
-                                           stream))
-            _lib.check(lib.cs_set_tail_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[:6]), stream))
-            _lib.check(lib.cs_set_head_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[6:]), stream))
-        return loss
-
-    # -- fitting the last decoder layer's cross-attention with the tail and the head (DESIGN.md 6, f17) ----------------------
-    @property
-    def CROSS_KEYS(self):
-        """The sixteen keys of the cross-attention fit: the last decoder layer's multihead_attn in_proj and out_proj and norm2, then TAIL_KEYS
-        (the order of cs_cross_backward's gradients)."""
-        p = f"ref_cross.attn.layers.{self.arch.dec_layers - 1}."
-        return tuple(p + k for k in ("multihead_attn.in_proj_weight", "multihead_attn.in_proj_bias", "multihead_attn.out_proj.weight",
-                                     "multihead_attn.out_proj.bias", "norm2.weight", "norm2.bias")) + self.TAIL_KEYS
-
-    def cross_parameters(self):
-        if not self._do_reference_cross:
-            raise ValueError("model.do_reference_cross=False: this module has no decoder to fit")
-        return [self.get_parameter(k) for k in self.CROSS_KEYS]
-
-    def cross_fit_supported(self) -> bool:
-        return bool(_lib.load().cs_cross_fit_supported(self.arch.hidden, self.arch.dec_heads, self.arch.patch))
+        self._fit_keep(FIT_TAIL, on)
 
     def fit_cross_keep(self, on: bool = True) -> None:
         """Following forwards also keep what cross_backward reads (cs_fit_cross_keep): fit_tail_keep's two copies, x1 and the last
         cross-attention's lse."""
-        self._cross_keep = bool(on)
-        if self._handle is not None:
-            _lib.check(_lib.load().cs_fit_cross_keep(self._handle, int(self._cross_keep)))
+        self._fit_keep(FIT_CROSS, on)
 
-    def cross_inputs(self, rows: int, N: int):
-        """(x1, Q', O, lse, K, V) of the last forward call's last cross-attention (tests): x1 (rows, C) fp32, Q' and O (rows, C) 16 bit, lse
-        (rows heads) fp32 in (B, heads, Np) order, K and V (rows N, C) 16 bit; that forward must have run with fit_cross_keep on."""
-        if self._handle is None:
-            raise _lib.CrossScoreHipError("cross_inputs before any forward")
-        dev = self._handle_device
-        Cc = self.arch.hidden
-        with torch.cuda.device(dev):
-            x1 = torch.empty((int(rows), Cc), dtype=torch.float32, device=dev)
-            Qp = torch.empty((int(rows), Cc), dtype=self.token_dtype, device=dev)
-            O = torch.empty_like(Qp)
-            lse = torch.empty((int(rows) * self.arch.dec_heads,), dtype=torch.float32, device=dev)
-            K = torch.empty((int(rows) * int(N), Cc), dtype=self.token_dtype, device=dev)
-            V = torch.empty_like(K)
-            _lib.check(_lib.load().cs_debug_cross_inputs(self._handle, *(C.c_void_p(t.data_ptr()) for t in (x1, Qp, O, lse, K, V)), int(rows),
-                                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        return x1, Qp, O, lse, K, V
+    def head_backward(self, gt, inv_count=None, accumulate=False, out=None):
+        """cs_head_backward over the LAST forward call of this module (its last sub-batch): gt (B, h P, w P) fp32 on the device ->
+        (dWa, dba, dWb, dbb, loss): fp32 gradients and the fp64 device scalar loss, each scaled by inv_count (default 1 / gt.numel())."""
+        return self._fit_backward(FIT_HEAD, gt, inv_count, accumulate, out)
+
+    def tail_backward(self, gt, inv_count=None, accumulate=False, out=None):
+        """The same through cs_tail_backward (that forward run with fit_tail_keep on): the ten gradients in TAIL_KEYS order and the loss."""
+        return self._fit_backward(FIT_TAIL, gt, inv_count, accumulate, out)
 
     def cross_backward(self, gt, inv_count=None, accumulate=False, out=None):
-        """cs_cross_backward over the LAST forward call of this module (run with fit_cross_keep on): gt (B, h P, w P) fp32 on the device -> the
-        sixteen fp32 gradients in CROSS_KEYS order and the fp64 device scalar loss, each scaled by inv_count (default 1 / gt.numel())."""
-        if self._handle is None:
-            raise _lib.CrossScoreHipError("cross_backward before any forward")
-        dev = self._handle_device
-        if gt.dim() != 3 or gt.dtype != torch.float32 or gt.device != dev or not gt.is_contiguous():
-            raise ValueError("expected a contiguous fp32 gt (B, H, W) on the module's device")
-        B, H, W = gt.shape
-        if out is None:
-            out = tuple(torch.zeros(p.shape, device=dev) for p in self.cross_parameters()) + (torch.zeros((), dtype=torch.float64, device=dev),)
-        inv = 1.0 / gt.numel() if inv_count is None else float(inv_count)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().cs_cross_backward(self._handle, C.c_void_p(gt.data_ptr()), B, H, W, inv, int(bool(accumulate)),
-                                                     *(C.c_void_p(t.data_ptr()) for t in out),
-                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        return out
+        """The same through cs_cross_backward (that forward run with fit_cross_keep on): the sixteen gradients in CROSS_KEYS order and the loss."""
+        return self._fit_backward(FIT_CROSS, gt, inv_count, accumulate, out)
+
+    def fit_head_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
+        """_fit_step over the four tensors of the head: cs_head_backward, four cs_op_adamw launches, cs_set_head_weights."""
+        return self._fit_step(FIT_HEAD, query, refs, gt, state, ref_tokens)
+
+    def fit_tail_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
+        """_fit_step over the ten tensors of the tail: cs_tail_backward on a forward with fit_tail_keep on, cs_set_tail_weights and the head's."""
+        return self._fit_step(FIT_TAIL, query, refs, gt, state, ref_tokens)
 
     def fit_cross_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
-        """fit_tail_step over the sixteen tensors of the cross-attention fit: the forward with fit_cross_keep on for the call, cs_cross_backward
-        behind each sub-batch, sixteen cs_op_adamw launches, cs_set_cross_weights, cs_set_tail_weights and cs_set_head_weights.  Same contract:
-        the module is not marked dirty, the loss of the batch BEFORE the step comes back as a device fp64 scalar, nothing is waited for."""
-        if (refs is None) == (ref_tokens is None):
-            raise ValueError("fit_cross_step takes the references either as images (refs) or as cached tokens (ref_tokens)")
-        if not self.cross_fit_supported():
-            raise NotImplementedError(f"cross-attention fit is built for the tail's shapes and decoder head dims 16, 48 and 96 (hidden {self.arch.hidden}, "
-                                      f"{self.arch.dec_heads} heads, patch {self.arch.patch})")
-        params = self.cross_parameters()
-        dev = gt.device
-        for p in params:
-            if not p.is_cuda or p.device != dev or p.dtype != torch.float32 or not p.is_contiguous():
-                raise ValueError("fit_cross_step needs the module's fp32 parameters on the device of the batch (net.to(device))")
-        if gt.dim() != 3 or gt.dtype != torch.float32 or not gt.is_contiguous():
-            raise ValueError("expected a contiguous fp32 gt (B, h P, w P)")
-        state.prepare(params)
-        lib = _lib.load()
-        inv = 1.0 / gt.numel()
-        grads, loss = state.grads, torch.zeros((), dtype=torch.float64, device=dev)
-        H, W = gt.shape[1:]
+        """_fit_step over the sixteen tensors of the cross-attention fit: cs_cross_backward on a forward with fit_cross_keep on,
+        cs_set_cross_weights, the tail's and the head's."""
+        return self._fit_step(FIT_CROSS, query, refs, gt, state, ref_tokens)
 
-        def backward(b0, b1):
-            _lib.check(lib.cs_cross_backward(self._handle, C.c_void_p(gt[b0:b1].data_ptr()), b1 - b0, H, W, inv, int(b0 > 0),
-                                             *(C.c_void_p(g.data_ptr()) for g in grads), C.c_void_p(loss.data_ptr()),
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-
-        kept = self._cross_keep
-        self._after_sub_batch = backward
-        try:
-            self._ensure_handle(dev)  # (the forward below finds it ready: the switch goes onto the handle it will use)
-            self.fit_cross_keep(True)
-            res = self.forward_cached(query, ref_tokens) if ref_tokens is not None else self.forward(query, refs)
-        finally:
-            self._after_sub_batch = None
-            self.fit_cross_keep(kept)
-        if tuple(res["score_map_ref_cross"].shape) != tuple(gt.shape):
-            raise ValueError(f"gt {tuple(gt.shape)} does not have the score map's shape {tuple(res['score_map_ref_cross'].shape)}")
-        state.step += 1
+    def _debug_inputs(self, c_name: str, rows: int, specs):
+        """Fresh tensors of specs' (shape, dtype) filled by the library's cs_debug_*_inputs `c_name` from the last forward call; rows = its B h w,
+        checked by the library (tests)."""
+        if self._handle is None:
+            raise _lib.CrossScoreHipError(f"{c_name[len('cs_debug_'):]} before any forward")
+        dev = self._handle_device
         with torch.cuda.device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            for p, m, v, g in zip(params, state.m, state.v, grads):
-                _lib.check(lib.cs_op_adamw(C.c_void_p(p.data_ptr()), C.c_void_p(m.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(g.data_ptr()),
-                                           p.numel(), state.lr, state.betas[0], state.betas[1], state.eps, state.weight_decay, state.step, None,
-                                           stream))
-            _lib.check(lib.cs_set_cross_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[:6]), stream))
-            _lib.check(lib.cs_set_tail_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[6:12]), stream))
-            _lib.check(lib.cs_set_head_weights(self._handle, *(C.c_void_p(p.data_ptr()) for p in params[12:]), stream))
-        return loss
+            out = tuple(torch.empty(shape, dtype=dtype, device=dev) for shape, dtype in specs)
+            _lib.check(getattr(_lib.load(), c_name)(self._handle, *(C.c_void_p(t.data_ptr()) for t in out), int(rows),
+                                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
+    def head_inputs(self, rows: int):
+        """(X, A): the 16-bit tokens behind the last norm3 and the head's hidden rows of the last forward call, (rows, C) each."""
+        rc = (int(rows), self.arch.hidden)
+        return self._debug_inputs("cs_debug_head_inputs", rows, [(rc, self.token_dtype)] * 2)
+
+    def tail_inputs(self, rows: int):
+        """(x2, H): the fp32 output of the last layer's norm2 and the 16-bit rows relu(linear1(x2)) of the last forward call, (rows, C) each;
+        that forward must have run with fit_tail_keep on."""
+        rc = (int(rows), self.arch.hidden)
+        return self._debug_inputs("cs_debug_tail_inputs", rows, [(rc, torch.float32), (rc, self.token_dtype)])
+
+    def cross_inputs(self, rows: int, N: int):
+        """(x1, Q', O, lse, K, V) of the last forward call's last cross-attention: x1 (rows, C) fp32, Q' and O (rows, C) 16 bit, lse (rows heads)
+        fp32 in (B, heads, Np) order, K and V (rows N, C) 16 bit; that forward must have run with fit_cross_keep on."""
+        Cc, t16 = self.arch.hidden, self.token_dtype
+        rc, kv = (int(rows), Cc), (int(rows) * int(N), Cc)
+        return self._debug_inputs("cs_debug_cross_inputs", rows, [(rc, torch.float32), (rc, t16), (rc, t16),
+                                                                  ((int(rows) * self.arch.dec_heads,), torch.float32), (kv, t16), (kv, t16)])
 
     # -- debug taps used by the stage-level parity tests (tests/test_hip_stages.py) ------------------------------------
     def debug_capture(self, on: bool = True) -> None:
@@ -1019,8 +946,8 @@ def load_lightning_checkpoint(path: str) -> Dict[str, torch.Tensor]:
 
 
 class HeadFitState:
-    """What fit_head_step keeps between steps: AdamW's moments of the four head parameters, the step count (from 1 at the first step), the
-    learning rate (the driver's StepLR writes it) and the gradient buffers.  Defaults are torch.optim.AdamW's."""
+    """What fit_head_step, fit_tail_step or fit_cross_step keeps between steps: AdamW's moments of the scope's parameters, the step count (from 1
+    at the first step), the learning rate (the driver's StepLR writes it) and the gradient buffers.  Defaults are torch.optim.AdamW's."""
 
     def __init__(self, lr: float = 5e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2):
         self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
