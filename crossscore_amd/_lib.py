@@ -223,6 +223,17 @@ SYMBOLS = {
     "cs_cross_backward": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _i] + [_vp] * 18),
     "cs_debug_cross_inputs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "cs_set_cross_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # whole-layer fit (csrc/layerfit.hip)
+    "cs_layer_fit_supported": (_i, [_i, _i, _i, _i]),
+    "cs_layer_backward_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
+    "cs_op_layer_backward": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp,
+                                  _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i,
+                                  _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _f, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f,
+                                  C.c_double, _i] + [_vp] * 25),
+    "cs_fit_layer_keep": (_i, [_vp, _i]),
+    "cs_layer_backward": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _i] + [_vp] * 24),
+    "cs_debug_layer_inputs": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "cs_set_layer_weights": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -122,6 +122,7 @@ void cs_destroy(cs_handle h) {
   if (h->hfit_ws) hipFree(h->hfit_ws);
   if (h->tail_kept) hipFree(h->tail_kept);
   if (h->cross_kept) hipFree(h->cross_kept);
+  if (h->layer_kept) hipFree(h->layer_kept);
   if (h->ev_done) hipEventDestroy(h->ev_done);
   if (h->ev_kv0) hipEventDestroy(h->ev_kv0);
   if (h->ev_kv1) hipEventDestroy(h->ev_kv1);
@@ -360,7 +361,7 @@ int cs_finalize(cs_handle h) {
 }
 
 // What the last forward-class call on this handle launched, and what it cost the host: `launches` = kernel launches (memcpy taps of capture
-// mode not counted; the two copies of cs_fit_tail_keep counted as tail_keep=2, the one more of cs_fit_cross_keep as cross_keep=1), `host_ms` = wall time of the call on the calling thread (everything is enqueued, nothing waited for), `names` (optional,
+// mode not counted; the two copies of cs_fit_tail_keep counted as tail_keep=2, the one more of cs_fit_cross_keep as cross_keep=1, the two more of cs_fit_layer_keep as layer_keep=2), `host_ms` = wall time of the call on the calling thread (everything is enqueued, nothing waited for), `names` (optional,
 // `names_bytes` long) = "kernel=count kernel=count ..." by kernel: gemm256 / gemm128 (cs_gemm256_kernel / cs_gemm_kernel), attn<dh>, panel,
 // rowln, patch, im2col, ln1 / ln2 / ln (layernorm_kernel), cls, final_ln, score_check, ...
 int cs_forward_stats(cs_handle h, int* launches, double* host_ms, char* names, size_t names_bytes) {
@@ -556,6 +557,42 @@ int cs_set_cross_weights(cs_handle h, const float* in_w, const float* in_b, cons
   HIPCHK(hipMemcpyAsync(D.ca_bo, out_b, C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(D.n2g, g2, C * 4, hipMemcpyDeviceToDevice, st));
   HIPCHK(hipMemcpyAsync(D.n2b, b2, C * 4, hipMemcpyDeviceToDevice, st));
+  return call_leave(h, st);
+}
+
+// Whole-layer fit: a persistent switch that implies cs_fit_cross_keep's (and with it cs_fit_tail_keep's) copies; in addition the
+// last layer's self-attention writes its lse into the handle's region, and x0 and Os are copied there in front of the launches that overwrite them.
+// Nothing else of the forward changes.
+int cs_fit_layer_keep(cs_handle h, int on) {
+  if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
+  h->layer_keep = on != 0;
+  return 0;
+}
+
+// The six changed tensors of the last decoder layer's self-attention block back into the finalised handle, exactly as cs_finalize packs them: rows
+// [0, C) of in_proj into sa_Win / sa_bin with log2(e) / sqrt(dh) folded in, rows [C, 3C) behind them unscaled, out_proj re-packed, its bias and
+// norm1 copied -- the buffers both the GEMM path and the row-complete kernel read; on `stream`, behind the handle's last call.
+int cs_set_layer_weights(cs_handle h, const float* in_w, const float* in_b, const float* out_w, const float* out_b, const float* g1, const float* b1,
+                         cs_stream stream) {
+  if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
+  if (!h->finalized) return fail(CS_ERR_STATE, "cs_set_layer_weights before cs_finalize");
+  if (h->dec.empty()) return fail(CS_ERR_STATE, "cs_set_layer_weights: the handle has no decoder layer");
+  if (!h->cfg.do_self_attn) return fail(CS_ERR_UNSUPPORTED, "cs_set_layer_weights: the decoder has no self-attention (decoder_do_self_attn = 0)");
+  if (!in_w || !in_b || !out_w || !out_b || !g1 || !b1) return fail(CS_ERR_BAD_ARG, "cs_set_layer_weights: null pointer");
+  if (((uintptr_t)in_w | (uintptr_t)in_b | (uintptr_t)out_w | (uintptr_t)out_b | (uintptr_t)g1 | (uintptr_t)b1) & 3) return fail(CS_ERR_BAD_ARG, "cs_set_layer_weights: misaligned pointer");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t C = h->cfg.hidden;
+  const int bf = h->cfg.operand_dtype;
+  const DecLayer& D = h->dec.back();
+  if (int r = call_enter(h, st)) return r;
+  HIPCHK(cs_pack_f16_launch(in_w, (int)C, (int)C, D.sa_Win, (int)C, h->qs_dec, nullptr, bf, st));
+  HIPCHK(cs_pack_f16_launch(in_w + C * C, (int)(2 * C), (int)C, D.sa_Win + C * C, (int)C, nullptr, nullptr, bf, st));
+  HIPCHK(cs_vec_mul_launch(in_b, h->qs_dec, D.sa_bin, (int)C, st));
+  HIPCHK(hipMemcpyAsync(D.sa_bin + C, in_b + C, 2 * C * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(cs_pack_f16_launch(out_w, (int)C, (int)C, D.sa_Wo, (int)C, nullptr, nullptr, bf, st));
+  HIPCHK(hipMemcpyAsync(D.sa_bo, out_b, C * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(D.n1g, g1, C * 4, hipMemcpyDeviceToDevice, st));
+  HIPCHK(hipMemcpyAsync(D.n1b, b1, C * 4, hipMemcpyDeviceToDevice, st));
   return call_leave(h, st);
 }
 

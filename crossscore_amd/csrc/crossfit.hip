@@ -27,46 +27,17 @@ __global__ void widen16_kernel(const h16_t* src, float* out, long long n8, int b
   reinterpret_cast<float4*>(out)[2 * i + 1] = hi;
 }
 
-// The pieces of one whole backward's workspace, carved in ONE place for the launch, for the parameters its caller checks and for the size: the
-// tail's (tail_carve, which leaves dyh and dHh there), the transposed weight (C, C), a zero bias (C), f32(dyh), dx2 and y2 (M, C) fp32, dy2h, dOh,
-// x1h and dQu (M, C) 16 bit, dKu | dV (Mk, 2C) 16 bit, the attention backward's, ln_backward's partials, gemm_tn's partials for the longer of the
-// two row counts
-struct CrossWs {
-  const h16_t *dyh, *dHh; h16_t* WT; float *zb, *dyf, *dx2, *y2; h16_t *dy2h, *dOh, *x1h, *dQu, *dKV; void *aws, *lws, *tws; size_t end;
-};
-CrossWs cross_carve(void* base, int B, int Np, int N, int C, int heads) {
-  const int M = B * Np, Mk = M * N;
-  const size_t mc = (size_t)M * C;
-  const TailWs t = tail_carve(base, M, C);
-  Carver w(base, t.end);
-  CrossWs k{};
-  k.dyh = t.dyh; k.dHh = t.dH;
-  k.WT = w.take<h16_t>((size_t)C * C * 2);
-  k.zb = w.take<float>((size_t)C * 4);
-  k.dyf = w.take<float>(mc * 4);
-  k.dx2 = w.take<float>(mc * 4);
-  k.y2 = w.take<float>(mc * 4);
-  k.dy2h = w.take<h16_t>(mc * 2);
-  k.dOh = w.take<h16_t>(mc * 2);
-  k.x1h = w.take<h16_t>(mc * 2);
-  k.dQu = w.take<h16_t>(mc * 2);
-  k.dKV = w.take<h16_t>((size_t)Mk * 2 * C * 2);
-  k.aws = w.take<char>(cs_attnbwd_workspace(B, heads, Np));
-  k.lws = w.take<char>(cs_ln_backward_workspace(M, C));
-  k.tws = w.take<char>(cs_gemm_tn_workspace(Mk > M ? Mk : M, C, C));
-  k.end = w.end();
-  return k;
-}
+// the pieces of one whole backward's workspace (cs_fit::cross_carve, fit_shared.h) for the launch, for the parameters its caller checks and for the size
 CrossWs cross_carve(const CsCrossBackward* q, void* ws) {
   const CsHeadBackward& hq = q->tail.head;
-  return cross_carve(ws, hq.B, hq.gh * hq.gw, q->N, hq.C, q->heads);
+  return cs_fit::cross_carve(ws, hq.B, hq.gh * hq.gw, q->N, hq.C, q->heads);
 }
 
 }  // namespace
 
 extern "C" {
 
-size_t cs_cross_backward_workspace(int B, int Np, int N, int C, int heads) { return cross_carve(nullptr, B, Np, N, C, heads).end; }
+size_t cs_cross_backward_workspace(int B, int Np, int N, int C, int heads) { return cs_fit::cross_carve(nullptr, B, Np, N, C, heads).end; }
 
 // The attention backward of one cross backward, as the launch below queues it: K and V in place in their packed rows, dKu | dV side by side.
 // cross_backward_run (ops.hip) builds it too and puts it through cs_attnbwd_check with every other check, before the first launch.

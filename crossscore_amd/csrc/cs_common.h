@@ -367,6 +367,18 @@ struct CsCrossBackward {
   float *dWin, *dbin, *dWo, *dbo, *dg2, *db2;  // in_proj (3C, C) and (3C), out_proj (C, C) and (C), norm2 (C) each
 };
 
+// Whole-layer fit (layerfit.hip): the last decoder layer's self-attention -> out_proj -> + residual -> norm1 in front of the cross-attention fit.
+struct CsLayerBackward {
+  CsCrossBackward cross;        // x1, the cross-attention's operands and weights, the tail's and the head's blocks, the sixteen gradients and the loss
+  const float* x0;              // [M][C] fp32, contiguous: the rows that entered the layer
+  const h16_t* Qs; const h16_t* Ks; const h16_t* Vs; int ldqkv;  // [M][ldqkv] the column blocks of the packed projection rows (Qs' has log2(e) / sqrt(dh) folded in)
+  const h16_t* Os; int ldos;    // [M][ldos] the self-attention's output
+  const float* lse_s;           // [B][heads][Np], base 2, as cs_attn_kernel wrote it
+  const h16_t* Wq; int ldwq;    // the cross-attention's packed query projection (log2(e) / sqrt(dh) folded in)
+  const h16_t* Wo_s; int ldwos; const float* bo_s; const float* gamma1;  // the self-attention's out_proj (packed), norm1's weight
+  float *dWin_s, *dbin_s, *dWo_s, *dbo_s, *dg1, *db1;  // in_proj (3C, C) and (3C), out_proj (C, C) and (C), norm1 (C) each
+};
+
 // ---- The launch surface between the kernel files and the host files (api.hip, forward.hip, ops.hip): every cs_*_launch / cs_*_check /
 // cs_*_supported / size helper that one .hip defines and another calls, declared ONCE.  Every defining file includes this header, so a changed
 // parameter list fails to compile there instead of linking (most of these are extern "C") and misbehaving at run time. ----
@@ -510,6 +522,10 @@ hipError_t cs_tail_backward_launch(const CsTailBackward* p, void* ws, int bf, hi
 size_t cs_cross_backward_workspace(int B, int Np, int N, int C, int heads);
 void cs_cross_backward_attn_params(const CsCrossBackward* p, void* ws, int bf, CsAttnBwdParams* out);  // the attention backward it queues
 hipError_t cs_cross_backward_launch(const CsCrossBackward* p, void* ws, int bf, hipStream_t st);
+// layerfit.hip
+size_t cs_layer_backward_workspace(int B, int Np, int N, int C, int heads);
+void cs_layer_backward_attn_params(const CsLayerBackward* p, void* ws, int bf, CsAttnBwdParams* out);  // the self-attention backward it queues
+hipError_t cs_layer_backward_launch(const CsLayerBackward* p, void* ws, int bf, hipStream_t st);
 hipError_t cs_adamw_launch(float* p, float* m, float* v, const float* g, long long n, float lr, float beta1, float beta2, float eps, float wd,
                            int step, h16_t* p16, int bf, hipStream_t st);
 }

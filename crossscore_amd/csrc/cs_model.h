@@ -130,6 +130,8 @@ struct cs_model {
     // K | V rows (Mk, ldkv; V is C columns further), O (M, C), lse (B, heads, Np) -- and the reference tokens its K / V projection read (Mk, C)
     bool cross_kept = false; int N = 0; const h16_t* dq = nullptr; const h16_t* k = nullptr; int ldkv = 0; const h16_t* dob = nullptr;
     const float* lse = nullptr; const h16_t* mem = nullptr;
+    // cs_fit_layer_keep: the last layer's packed self-attention projection rows Q' | K | V (M, 3C) where the forward left them
+    bool layer_kept = false; const h16_t* dqkv = nullptr;
   };
   LastForward last_fwd;
   void* hfit_ws = nullptr; size_t hfit_ws_bytes = 0;  // X in 16 bits (M, C), then cs_head_backward_workspace (cs_tail_backward_workspace once the tail is fitted)
@@ -141,7 +143,11 @@ struct cs_model {
   // that enter that block, is copied into this region before the norm2 closing overwrites it
   bool cross_keep = false;
   void* cross_kept = nullptr; size_t cross_kept_bytes = 0;
-  float* qs_dec = nullptr;  // [C] log2(e) / sqrt(dh) of the decoder: the row scale of the packed query projections (cs_set_cross_weights packs with it again)
+  // whole-layer fit (cs_fit_layer_keep): implies cross_keep; in addition the last layer's self-attention writes its lse, and x0 (the fp32 rows that
+  // enter the layer), Os (its 16-bit output) and that lse are copied into this region before the norm1 closing and the cross-attention overwrite them
+  bool layer_keep = false;
+  void* layer_kept = nullptr; size_t layer_kept_bytes = 0;
+  float* qs_dec = nullptr;  // [C] log2(e) / sqrt(dh) of the decoder: the row scale of the packed query projections (cs_set_cross_weights and cs_set_layer_weights pack with it again)
   unsigned* nonfinite = nullptr;  // device counter: non-finite score-map values seen since the last cs_nonfinite_count
   // profiling
   bool prof = false;
@@ -215,6 +221,8 @@ int head_backward_run(const char* op, const CsHeadBackward& q, void* ws, int bf,
 int tail_backward_run(const char* op, const CsTailBackward& q, void* ws, int bf, hipStream_t st);
 // ops.hip: the same for the cross-attention block's backward (the tail's is its first part)
 int cross_backward_run(const char* op, const CsCrossBackward& q, void* ws, int bf, hipStream_t st);
+// ops.hip: the same for the whole layer's backward (the cross-attention block's is its first part)
+int layer_backward_run(const char* op, const CsLayerBackward& q, void* ws, int bf, hipStream_t st);
 
 // forward.hip
 void reap_retired(cs_model* m, bool all);                        // frees retired workspaces whose last use has completed (never blocks unless `all`)

@@ -307,6 +307,7 @@ struct Fwd {
   bool fused_ln = false, fuse_next = false;
   bool tail_kept = false;  // (cs_fit_tail_keep) this call has queued the two copies cs_tail_backward works on
   bool cross_kept = false;  // (cs_fit_cross_keep) ... and the copy of x1, with lse written: what cs_cross_backward works on
+  bool layer_kept = false;  // (cs_fit_layer_keep) ... and the copies of x0 and Os, with the self-attention's lse written: what cs_layer_backward works on
 
   // ---- step 1: arguments ----
   int validate() {
@@ -772,6 +773,27 @@ struct Fwd {
     return 0;
   }
 
+  // cs_fit_layer_keep: in front of the last layer's self-attention p.xq holds x0, the rows that enter the layer; the norm1
+  // closing overwrites it.  The self-attention's output Os (p.dob) is overwritten by the cross-attention's, and p.lse by that attention's own lse.
+  // So the handle's own region takes x0 here (M C fp32), then Os (M C 16 bit) behind the attention (keep_Os), and the self-attention writes its
+  // lse (B heads Np fp32) straight into it.  The packed Q' | K | V rows stay where they are: nothing behind the last layer's self-attention
+  // writes p.dqkv (only a layer's own in_proj GEMM does, in front of its self-attention).
+  size_t layer_kept_x0_bytes() const { return cs_fit::up256((size_t)B * p.Np * p.C * 4); }
+  size_t layer_kept_Os_bytes() const { return cs_fit::up256((size_t)B * p.Np * p.C * 2); }
+  int keep_x0(hipStream_t s, float** lse_s) {
+    const size_t need = layer_kept_x0_bytes() + layer_kept_Os_bytes() + (size_t)B * h->cfg.dec_heads * p.Np * 4;
+    if (int r = grow_retired(h, &h->layer_kept, &h->layer_kept_bytes, need, s)) return r;
+    HIPCHK(hipMemcpyAsync(h->layer_kept, p.xq, (size_t)B * p.Np * p.C * 4, hipMemcpyDeviceToDevice, s));
+    *lse_s = reinterpret_cast<float*>(static_cast<char*>(h->layer_kept) + layer_kept_x0_bytes() + layer_kept_Os_bytes());
+    return 0;
+  }
+  int keep_Os(hipStream_t s) {
+    HIPCHK(hipMemcpyAsync(static_cast<char*>(h->layer_kept) + layer_kept_x0_bytes(), p.dob, (size_t)B * p.Np * p.C * 2, hipMemcpyDeviceToDevice, s));
+    h->census["layer_keep"] += 2;
+    layer_kept = true;
+    return 0;
+  }
+
   // The decoder runs as ONE group on the caller's stream, after the join: its kernels are small, and splitting the batch over streams only
   // makes them smaller (cfg-2, tools/dec_lanes.py: 1 group 8.77 ms, 2 groups 8.80, 3 groups 8.79, 4 groups 9.31).  Decoding each chunk's
   // items on its lane right after encoding them (no global join) was measured SLOWER too (833 vs 875 query-images/s on cfg-2): it doubles the
@@ -808,15 +830,19 @@ struct Fwd {
       const float* shortcut = c.do_short_cut ? p.xq : nullptr;
       if (c.do_self_attn) {
         L.gemm(gp(p.q_bf, C, D.sa_Win, C, M, 3 * C, C, D.sa_bin, p.dqkv, 3 * C), CS_EPI_BIAS_F16);
-        const CsAttnParams a = attn_params(p.dqkv, 3 * C, p.dqkv + C, p.dqkv + 2 * C, 3 * C, p.dob, p.Np, p.Np, c.dec_heads);
+        const bool keep_l = last_l && h->layer_keep;  // whole-layer fit: x0, Os and the self-attention's lse kept
+        float* lse_s = nullptr;
+        if (keep_l && !L.rc) L.rc = keep_x0(s, &lse_s);
+        const CsAttnParams a = attn_params(p.dqkv, 3 * C, p.dqkv + C, p.dqkv + 2 * C, 3 * C, p.dob, p.Np, p.Np, c.dec_heads, lse_s);
         L.attn(a, dec_dh, B);
+        if (keep_l && !L.rc) L.rc = keep_Os(s);
         have_q = dec_close(L, p.dob, D.sa_Wo, D.sa_bo, shortcut, D.n1g, D.n1b, "norm1", next_of(D.ca_Wq, D.ca_bq, p.dq, 0));
       }
       if (kv_side && l == 0 && !L.rc && hipStreamWaitEvent(s, h->ev_kv1, 0) != hipSuccess) L.rc = CS_ERR_HIP;
       if (!have_q) L.gemm(gp(p.q_bf, C, D.ca_Wq, C, M, C, C, D.ca_bq, p.dq, C), CS_EPI_BIAS_F16);
       const bool want_w = attn_out && last_l;  // only the last layer's weights are returned (transformer.py:266-268)
       const bool want_use = last_l && use.any();  // reference use: the same layer, the same lse
-      const bool want_fit = last_l && h->cross_keep;  // cross-attention fit: lse for the backward, x1 kept below
+      const bool want_fit = last_l && (h->cross_keep || h->layer_keep);  // cross-attention fit: lse for the backward, x1 kept below
       const CsAttnParams a = attn_params(p.dq, C, p.kv + (size_t)l * 2 * C, p.kv + (size_t)l * 2 * C + C, KV, p.dob, p.Np, N * p.Np, c.dec_heads, want_w || want_use || want_fit ? p.lse : nullptr);
       L.attn(a, dec_dh, B);
       if (want_w) L.small("attn_weights", [&] { return cs_attn_weights_launch(&a, dec_dh, B, head_id, attn_out, s); });
@@ -824,7 +850,7 @@ struct Fwd {
       if (want_fit && !L.rc) L.rc = keep_x1(s);
       if (!dec_close(L, p.dob, D.ca_Wo, D.ca_bo, shortcut, D.n2g, D.n2b, "norm2", next_of(D.l1W, D.l1b, p.dhid, 1)))
         L.gemm(gp(p.q_bf, C, D.l1W, C, M, C, C, D.l1b, p.dhid, C), CS_EPI_BIAS_RELU_F16);
-      if (last_l && (h->tail_keep || h->cross_keep) && !L.rc) L.rc = keep_tail(s);
+      if (last_l && (h->tail_keep || h->cross_keep || h->layer_keep) && !L.rc) L.rc = keep_tail(s);
       // behind norm3: the head's first linear (its hidden rows replace linear1's in dhid: a workgroup writes exactly the 64 rows it staged into
       // LDS at its start), or -- without self-attention -- the next layer's Q projection
       NextLinear next{};
@@ -906,6 +932,7 @@ int forward_impl(Fwd f) {
     const int C = h->cfg.hidden, L = h->cfg.dec_layers;
     lf.cross_kept = true; lf.N = f.N; lf.dq = f.p.dq; lf.k = f.p.kv + (size_t)(L - 1) * 2 * C; lf.ldkv = 2 * C * L; lf.dob = f.p.dob; lf.lse = f.p.lse;
     lf.mem = f.mode == 1 ? f.ref_tokens : f.p.mem_bf;
+    lf.layer_kept = f.layer_kept; lf.dqkv = f.p.dqkv;
   }
   h->host_enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (int r = call_leave(h, f.st)) return r;
@@ -1008,11 +1035,12 @@ int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const ui
 // The scopes are nested.  FIT_HEAD (f15) is the regression head; the closing launch of the decoder writes the normalised rows in fp32 (p.xq) and,
 // where the head's first linear rides along (rowln.hip), no 16-bit copy, so X is rounded here from p.xq, the rounding the forward's own operand
 // went through.  FIT_TAIL (f16) adds the last layer's feed-forward block and norm3: the last forward must have kept x2 and H (cs_fit_tail_keep).
-// FIT_CROSS (f17) adds that layer's cross-attention and norm2: x1 and lse kept as well (cs_fit_cross_keep).  The workspace of a backward is the
+// FIT_CROSS (f17) adds that layer's cross-attention and norm2: x1 and lse kept as well (cs_fit_cross_keep).  FIT_LAYER (f18) adds its self-attention
+// and norm1: x0, Os and the self-attention's lse kept as well (cs_fit_layer_keep).  The workspace of a backward is the
 // handle's own allocation (X, then the scope's cs_*_backward_workspace, each of which begins with its parent's), grown like the forward's.
 namespace {
 
-enum FitScope { FIT_HEAD, FIT_TAIL, FIT_CROSS };
+enum FitScope { FIT_HEAD, FIT_TAIL, FIT_CROSS, FIT_LAYER };
 
 int last_rows(const cs_model* h) { return h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch); }
 
@@ -1050,6 +1078,8 @@ int fit_state_check(cs_model* h, int B, int H, int W, const char* op, FitScope s
   if (scope >= FIT_TAIL && !cs_tail_fit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden <= 2048 (hidden %d)", op, c.hidden);
   if (scope >= FIT_CROSS && !cs_cross_fit_supported(c.hidden, c.dec_heads, c.patch))
     return fail(CS_ERR_UNSUPPORTED, "%s: the attention backward is built for head dims 16, 48 and 96 (hidden %d, %d heads)", op, c.hidden, c.dec_heads);
+  if (scope >= FIT_LAYER && !c.do_self_attn) return fail(CS_ERR_UNSUPPORTED, "%s: the decoder has no self-attention (decoder_do_self_attn = 0): nothing to fit", op);
+  if (scope >= FIT_LAYER && !(lf.layer_kept && lf.cross_kept && lf.tail_kept)) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_layer_keep off", op);
   if (scope >= FIT_CROSS && !(lf.cross_kept && lf.tail_kept)) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_cross_keep off", op);
   if (scope >= FIT_TAIL && !lf.tail_kept) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_tail_keep off", op);
   return 0;
@@ -1071,7 +1101,8 @@ int fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, const char* op,
   const cs_config& c = h->cfg;
   const int M = last_rows(h), C = c.hidden;
   const size_t xbytes = cs_fit::up256((size_t)M * C * 2),
-               need = xbytes + (scope == FIT_CROSS ? cs_cross_backward_workspace(lf.B, M / lf.B, lf.N, C, c.dec_heads)
+               need = xbytes + (scope == FIT_LAYER ? cs_layer_backward_workspace(lf.B, M / lf.B, lf.N, C, c.dec_heads)
+                                : scope == FIT_CROSS ? cs_cross_backward_workspace(lf.B, M / lf.B, lf.N, C, c.dec_heads)
                                 : scope == FIT_TAIL ? cs_tail_backward_workspace(M, C) : cs_head_backward_workspace(M, C));
   if (int r = call_enter(h, st)) return r;
   if (int r = grow_retired(h, &h->hfit_ws, &h->hfit_ws_bytes, need, st)) return r;
@@ -1100,6 +1131,29 @@ CsTailBackward fill_tail_backward(const cs_model* h, int M, float* dW1, float* d
   q.W2 = D.l2W; q.ldw2 = C; q.b2 = D.l2b; q.gamma3 = D.n3g; q.eps = 1e-5f; q.Wa = h->Wh0; q.ldwa = C;
   q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dg3; q.db3 = db3;
   return q;
+}
+
+// (everything but .tail)
+CsCrossBackward fill_cross_backward(const cs_model* h, float* dWin, float* dbin, float* dWo, float* dbo, float* dgamma2, float* dbeta2) {
+  const cs_config& c = h->cfg;
+  const int C = c.hidden;
+  const DecLayer& D = h->dec.back();
+  const cs_model::LastForward& lf = h->last_fwd;
+  CsCrossBackward x{};
+  x.x1 = static_cast<const float*>(h->cross_kept); x.Qp = lf.dq; x.ldq = C; x.K = lf.k; x.V = lf.k + C; x.ldkv = lf.ldkv; x.O = lf.dob; x.ldo = C;
+  x.lse = lf.lse; x.mem = lf.mem; x.ldm = C; x.W1 = D.l1W; x.ldw1 = C; x.Wo = D.ca_Wo; x.ldwo = C; x.bo = D.ca_bo; x.gamma2 = D.n2g;
+  x.N = lf.N; x.heads = c.dec_heads; x.short_cut = c.do_short_cut != 0;
+  x.dWin = dWin; x.dbin = dbin; x.dWo = dWo; x.dbo = dbo; x.dg2 = dgamma2; x.db2 = dbeta2;
+  return x;
+}
+
+// the pieces of cs_model::layer_kept (keep_x0 / keep_Os write them): x0 (M, C) fp32, Os (M, C) 16 bit, lse_s (B, heads, Np) fp32, each from a 256-byte boundary
+const float* kept_x0(const cs_model* h) { return static_cast<const float*>(h->layer_kept); }
+const h16_t* kept_Os(const cs_model* h, size_t M) {
+  return reinterpret_cast<const h16_t*>(static_cast<const char*>(h->layer_kept) + cs_fit::up256(M * h->cfg.hidden * 4));
+}
+const float* kept_lse_s(const cs_model* h, size_t M) {
+  return reinterpret_cast<const float*>(static_cast<const char*>(h->layer_kept) + cs_fit::up256(M * h->cfg.hidden * 4) + cs_fit::up256(M * h->cfg.hidden * 2));
 }
 
 }  // namespace
@@ -1162,18 +1216,10 @@ int cs_cross_backward(cs_handle h, const float* gt, int B, int H, int W, double 
     return r;
   FitIn in;
   if (int r = fit_inputs(h, B, H, W, st, "cs_cross_backward", FIT_CROSS, &in)) return r;
-  const cs_config& c = h->cfg;
-  const int C = c.hidden;
-  const DecLayer& D = h->dec.back();
-  const cs_model::LastForward& lf = h->last_fwd;
-  CsCrossBackward x{};
-  x.x1 = static_cast<const float*>(h->cross_kept); x.Qp = lf.dq; x.ldq = C; x.K = lf.k; x.V = lf.k + C; x.ldkv = lf.ldkv; x.O = lf.dob; x.ldo = C;
-  x.lse = lf.lse; x.mem = lf.mem; x.ldm = C; x.W1 = D.l1W; x.ldw1 = C; x.Wo = D.ca_Wo; x.ldwo = C; x.bo = D.ca_bo; x.gamma2 = D.n2g;
-  x.N = lf.N; x.heads = c.dec_heads; x.short_cut = c.do_short_cut != 0;
-  x.dWin = dWin; x.dbin = dbin; x.dWo = dWo; x.dbo = dbo; x.dg2 = dgamma2; x.db2 = dbeta2;
+  CsCrossBackward x = fill_cross_backward(h, dWin, dbin, dWo, dbo, dgamma2, dbeta2);
   x.tail = fill_tail_backward(h, in.M, dW1, db1, dW2, db2, dg3, db3);
   x.tail.head = fill_head_backward(h, in.X, gt, B, H, W, inv_count, accumulate, dWa, dba, dWb, dbb, loss);
-  const int rc = cross_backward_run("cs_cross_backward", x, in.ws, c.operand_dtype, st);
+  const int rc = cross_backward_run("cs_cross_backward", x, in.ws, h->cfg.operand_dtype, st);
   const int r = call_leave(h, st);
   return r ? r : rc;
 }
@@ -1193,6 +1239,49 @@ int cs_debug_cross_inputs(cs_handle h, float* x1_out, uint16_t* q_out, uint16_t*
   if (lse_out) HIPCHK(hipMemcpyAsync(lse_out, lf.lse, M * h->cfg.dec_heads * 4, hipMemcpyDeviceToDevice, st));
   if (k_out) HIPCHK(hipMemcpy2DAsync(k_out, C * 2, lf.k, (size_t)lf.ldkv * 2, C * 2, Mk, hipMemcpyDeviceToDevice, st));
   if (v_out) HIPCHK(hipMemcpy2DAsync(v_out, C * 2, lf.k + C, (size_t)lf.ldkv * 2, C * 2, Mk, hipMemcpyDeviceToDevice, st));
+  return call_leave(h, st);
+}
+
+int cs_layer_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWin_s, float* dbin_s, float* dWo_s,
+                      float* dbo_s, float* dgamma1, float* dbeta1, float* dWin, float* dbin, float* dWo, float* dbo, float* dgamma2, float* dbeta2,
+                      float* dW1, float* db1, float* dW2, float* db2, float* dg3, float* db3, float* dWa, float* dba, float* dWb, float* dbb, double* loss,
+                      cs_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int r = fit_args_check("cs_layer_backward", h, B, gt, {dWin_s, dbin_s, dWo_s, dbo_s, dgamma1, dbeta1, dWin, dbin, dWo, dbo, dgamma2, dbeta2, dW1, db1,
+                                                             dW2, db2, dg3, db3, dWa, dba, dWb, dbb},
+                             loss, inv_count, true))
+    return r;
+  FitIn in;
+  if (int r = fit_inputs(h, B, H, W, st, "cs_layer_backward", FIT_LAYER, &in)) return r;
+  const int C = h->cfg.hidden;
+  const DecLayer& D = h->dec.back();
+  const cs_model::LastForward& lf = h->last_fwd;
+  CsLayerBackward y{};
+  y.x0 = kept_x0(h); y.Qs = lf.dqkv; y.Ks = lf.dqkv + C; y.Vs = lf.dqkv + 2 * C; y.ldqkv = 3 * C; y.Os = kept_Os(h, in.M); y.ldos = C;
+  y.lse_s = kept_lse_s(h, in.M); y.Wq = D.ca_Wq; y.ldwq = C; y.Wo_s = D.sa_Wo; y.ldwos = C; y.bo_s = D.sa_bo; y.gamma1 = D.n1g;
+  y.dWin_s = dWin_s; y.dbin_s = dbin_s; y.dWo_s = dWo_s; y.dbo_s = dbo_s; y.dg1 = dgamma1; y.db1 = dbeta1;
+  y.cross = fill_cross_backward(h, dWin, dbin, dWo, dbo, dgamma2, dbeta2);
+  y.cross.tail = fill_tail_backward(h, in.M, dW1, db1, dW2, db2, dg3, db3);
+  y.cross.tail.head = fill_head_backward(h, in.X, gt, B, H, W, inv_count, accumulate, dWa, dba, dWb, dbb, loss);
+  const int rc = layer_backward_run("cs_layer_backward", y, in.ws, h->cfg.operand_dtype, st);
+  const int r = call_leave(h, st);
+  return r ? r : rc;
+}
+
+int cs_debug_layer_inputs(cs_handle h, float* x0_out, uint16_t* q_out, uint16_t* k_out, uint16_t* v_out, uint16_t* o_out, float* lse_out, int rows,
+                          cs_stream stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (int r = debug_rows_check(h, rows, "cs_debug_layer_inputs")) return r;
+  if (int r = fit_state_check(h, 0, 0, 0, "cs_debug_layer_inputs", FIT_LAYER)) return r;  // (the state checks alone, as cs_debug_cross_inputs)
+  if (int r = call_enter(h, st)) return r;
+  const cs_model::LastForward& lf = h->last_fwd;
+  const size_t M = last_rows(h), C = h->cfg.hidden, n = M * C;
+  if (x0_out) HIPCHK(hipMemcpyAsync(x0_out, kept_x0(h), n * 4, hipMemcpyDeviceToDevice, st));
+  uint16_t* const outs[3] = {q_out, k_out, v_out};
+  for (int j = 0; j < 3; ++j)
+    if (outs[j]) HIPCHK(hipMemcpy2DAsync(outs[j], C * 2, lf.dqkv + j * C, 3 * C * 2, C * 2, M, hipMemcpyDeviceToDevice, st));
+  if (o_out) HIPCHK(hipMemcpyAsync(o_out, kept_Os(h, M), n * 2, hipMemcpyDeviceToDevice, st));
+  if (lse_out) HIPCHK(hipMemcpyAsync(lse_out, kept_lse_s(h, M), M * h->cfg.dec_heads * 4, hipMemcpyDeviceToDevice, st));
   return call_leave(h, st);
 }
 

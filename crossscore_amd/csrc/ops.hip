@@ -880,8 +880,8 @@ int cs_host::tail_backward_run(const char* op, const CsTailBackward& q, void* ws
   return 0;
 }
 
-// cs_op_cross_backward and cs_cross_backward (forward.hip): the tail's checks, the block's own, then the launches
-int cs_host::cross_backward_run(const char* op, const CsCrossBackward& q, void* ws, int bf, hipStream_t st) {
+// every check of the cross-attention fit's backward: the tail's, then the block's own (its attention backward's parameters included)
+static int cross_backward_check(const char* op, const CsCrossBackward& q, void* ws, int bf) {
   if (int r = tail_backward_check(op, q.tail, ws)) return r;
   const CsHeadBackward& hq = q.tail.head;
   const int C = hq.C;
@@ -905,7 +905,36 @@ int cs_host::cross_backward_run(const char* op, const CsCrossBackward& q, void* 
   CsAttnBwdParams a{};
   cs_cross_backward_attn_params(&q, ws, bf, &a);
   if (const char* e = cs_attnbwd_check(&a)) return fail(CS_ERR_BAD_ARG, "%s: %s", op, e);
+  return 0;
+}
+
+// cs_op_cross_backward and cs_cross_backward (forward.hip): every check first, then the launches
+int cs_host::cross_backward_run(const char* op, const CsCrossBackward& q, void* ws, int bf, hipStream_t st) {
+  if (int r = cross_backward_check(op, q, ws, bf)) return r;
   HIPCHK(cs_cross_backward_launch(&q, ws, bf, st));
+  return 0;
+}
+
+// cs_op_layer_backward and cs_layer_backward (forward.hip): the cross-attention fit's checks, the self-attention block's own, then the launches
+int cs_host::layer_backward_run(const char* op, const CsLayerBackward& q, void* ws, int bf, hipStream_t st) {
+  if (int r = cross_backward_check(op, q.cross, ws, bf)) return r;
+  const CsHeadBackward& hq = q.cross.tail.head;
+  const int C = hq.C;
+  if ((long long)hq.B * hq.gh * hq.gw * 3 * C >= (1ll << 31)) return fail(CS_ERR_UNSUPPORTED, "%s: built for fewer than 2^31 Q | K | V elements; split the batch", op);
+  if (!q.x0 || !q.Qs || !q.Ks || !q.Vs || !q.Os || !q.lse_s || !q.Wq || !q.Wo_s || !q.bo_s || !q.gamma1 || !q.dWin_s || !q.dbin_s || !q.dWo_s || !q.dbo_s ||
+      !q.dg1 || !q.db1)
+    return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
+  for (int ld : {q.ldqkv, q.ldos, q.ldwq, q.ldwos})
+    if (ld < C || ld % 8) return fail(CS_ERR_BAD_ARG, "%s: row strides must be multiples of 8 elements and at least C", op);
+  if (misaligned(q.x0, 16) || misaligned(q.Qs, 16) || misaligned(q.Ks, 16) || misaligned(q.Vs, 16) || misaligned(q.Os, 16) || misaligned(q.Wq, 16) ||
+      misaligned(q.Wo_s, 16) || misaligned(q.bo_s, 16) || misaligned(q.gamma1, 16) || misaligned(q.lse_s, 4))
+    return fail(CS_ERR_BAD_ARG, "%s: misaligned input (16-bit operands, x0, bo and gamma 16 bytes, lse 4)", op);
+  for (const float* o : {q.dWin_s, q.dbin_s, q.dWo_s, q.dbo_s, q.dg1, q.db1})
+    if (misaligned(o, 4)) return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
+  CsAttnBwdParams a{};
+  cs_layer_backward_attn_params(&q, ws, bf, &a);
+  if (const char* e = cs_attnbwd_check(&a)) return fail(CS_ERR_BAD_ARG, "%s: %s", op, e);
+  HIPCHK(cs_layer_backward_launch(&q, ws, bf, st));
   return 0;
 }
 
@@ -999,6 +1028,43 @@ int cs_op_cross_backward(const float* x1, const uint16_t* Qp, int ldq, const uin
   hq.act = act; hq.powp = powp; hq.inv_count = inv_count; hq.accumulate = accumulate != 0; hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb;
   hq.loss = loss;
   return cross_backward_run("cross_backward", c, ws, g_op_bf16, (hipStream_t)stream);
+}
+
+// ---- whole-layer fit (layerfit.hip) ----
+int cs_layer_fit_supported(int hidden, int heads, int patch, int do_self_attn) { return do_self_attn != 0 && cs_cross_fit_supported(hidden, heads, patch); }
+
+size_t cs_layer_backward_workspace_bytes(int B, int Np, int N, int C, int P, int heads) {
+  if (!cs_cross_backward_workspace_bytes(B, Np, N, C, P, heads) || (long long)B * Np * 3 * C >= (1ll << 31)) return 0;
+  return cs_layer_backward_workspace(B, Np, N, C, heads);
+}
+
+int cs_op_layer_backward(const float* x0, const uint16_t* Qs, const uint16_t* Ks, const uint16_t* Vs, int ldqkv, const uint16_t* Os, int ldos,
+                         const float* lse_s, const uint16_t* Wq, int ldwq, const uint16_t* Wo_s, int ldwos, const float* bo_s, const float* gamma1,
+                         const float* x1, const uint16_t* Qp, int ldq, const uint16_t* K, const uint16_t* V, int ldkv, const uint16_t* O, int ldo,
+                         const float* lse, const uint16_t* mem, int ldm, const uint16_t* W1, int ldw1, const uint16_t* Wo, int ldwo, const float* bo,
+                         const float* gamma2, int N, int heads, int short_cut, const float* x2, const uint16_t* H, int ldh, const uint16_t* X,
+                         int ldx, const uint16_t* A, int lda, const uint16_t* W2, int ldw2, const float* b2, const float* gamma3, float eps,
+                         const uint16_t* Wa, int ldwa, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P,
+                         int C, int act, float powp, double inv_count, int accumulate, float* dWin_s, float* dbin_s, float* dWo_s, float* dbo_s,
+                         float* dgamma1, float* dbeta1, float* dWin, float* dbin, float* dWo, float* dbo, float* dgamma2, float* dbeta2, float* dW1,
+                         float* db1, float* dW2, float* db2, float* dgamma3, float* dbeta3, float* dWa, float* dba, float* dWb, float* dbb,
+                         double* loss, void* ws, cs_stream stream) {
+  CsLayerBackward y{};
+  y.x0 = x0; y.Qs = Qs; y.Ks = Ks; y.Vs = Vs; y.ldqkv = ldqkv; y.Os = Os; y.ldos = ldos; y.lse_s = lse_s; y.Wq = Wq; y.ldwq = ldwq;
+  y.Wo_s = Wo_s; y.ldwos = ldwos; y.bo_s = bo_s; y.gamma1 = gamma1;
+  y.dWin_s = dWin_s; y.dbin_s = dbin_s; y.dWo_s = dWo_s; y.dbo_s = dbo_s; y.dg1 = dgamma1; y.db1 = dbeta1;
+  CsCrossBackward& c = y.cross;
+  c.x1 = x1; c.Qp = Qp; c.ldq = ldq; c.K = K; c.V = V; c.ldkv = ldkv; c.O = O; c.ldo = ldo; c.lse = lse; c.mem = mem; c.ldm = ldm;
+  c.W1 = W1; c.ldw1 = ldw1; c.Wo = Wo; c.ldwo = ldwo; c.bo = bo; c.gamma2 = gamma2; c.N = N; c.heads = heads; c.short_cut = short_cut != 0;
+  c.dWin = dWin; c.dbin = dbin; c.dWo = dWo; c.dbo = dbo; c.dg2 = dgamma2; c.db2 = dbeta2;
+  CsTailBackward& q = c.tail;
+  q.x2 = x2; q.H = H; q.ldh = ldh; q.W2 = W2; q.ldw2 = ldw2; q.b2 = b2; q.gamma3 = gamma3; q.eps = eps; q.Wa = Wa; q.ldwa = ldwa;
+  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dgamma3; q.db3 = dbeta3;
+  CsHeadBackward& hq = q.head;
+  hq.X = X; hq.ldx = ldx; hq.A = A; hq.lda = lda; hq.Wb = Wb; hq.ldw = ldw; hq.bb = bb; hq.gt = gt; hq.B = B; hq.gh = gh; hq.gw = gw; hq.P = P; hq.C = C;
+  hq.act = act; hq.powp = powp; hq.inv_count = inv_count; hq.accumulate = accumulate != 0; hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb;
+  hq.loss = loss;
+  return layer_backward_run("layer_backward", y, ws, g_op_bf16, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,8 +1,10 @@
 """python -m crossscore_amd.fit_head: fits the regression head on the device, or with this_main.fit_scope=tail the decoder's
 tail: the last decoder layer's linear1, linear2 and norm3 together with the head, ten tensors (CrossScoreNet.fit_tail_step),
 or with this_main.fit_scope=cross that layer's cross-attention as well: its in_proj, out_proj and norm2, sixteen tensors (DESIGN.md 6, f17;
-CrossScoreNet.fit_cross_step).  The default scope is head; the gradient of the tail stops at the last layer's norm2 output and that of the
-cross scope at the rows and the reference tokens that enter the cross-attention, so everything below stays frozen in every scope.
+CrossScoreNet.fit_cross_step), or with this_main.fit_scope=layer the whole last decoder layer: its self-attention and norm1 too, twenty-two tensors
+(CrossScoreNet.fit_layer_step; needs model.decoder_do_self_attn=True).  The default scope is head; the gradient of the tail
+stops at the last layer's norm2 output, that of the cross scope at the rows and the reference tokens that enter the cross-attention and that of
+the layer scope at the rows that enter the layer, so everything below stays frozen in every scope.
 
 Walks the nvs.NvsItems of this_main.data_split (default train) with the host loaders and the GT stage of crossscore_amd.evaluate
 (InputStage.metric_maps over the metric-map files, or this_main.gt_metric_maps=compute on a bare tree), geometry as evaluate's, one handle, one
@@ -32,7 +34,7 @@ import torch
 from .config import load_config
 from .data import EMPTY, ReferenceTokenCache, decode_items, load_batch, metric_mode
 from .evaluate import gt_file, gt_inputs, gt_map_kind, gt_metric_maps_choice, limit_batches
-from .model import FIT_SCOPES as SCOPE_TABLE, HeadFitState, arch_from_cfg, check_fit_supported, save_lightning_checkpoint
+from .model import ALL_FIT_SCOPES, FIT_SCOPES as SCOPE_TABLE, HeadFitState, arch_from_cfg, check_fit_supported, save_lightning_checkpoint
 from .nvs import NvsItems, random_order
 from .scoring import build_net, nvs_input_stage, seed_everything
 
@@ -47,10 +49,10 @@ FIT_SCOPES = tuple(SCOPE_TABLE)  # head, tail, cross: the names of model.FIT_SCO
 
 def fit_scope(cfg) -> str:
     """this_main.fit_scope: head (default; ref_cross.head.{0,2}), tail (the last decoder layer's feed-forward block and norm3 as well) or cross
-    (that layer's cross-attention and norm2 as well)"""
+    (that layer's cross-attention and norm2 as well) or layer (its self-attention and norm1 as well: the whole last decoder layer)"""
     scope = str(cfg.this_main.get("fit_scope", "head"))
-    if scope not in FIT_SCOPES:
-        raise ValueError(f"this_main.fit_scope={scope}: head | tail | cross")
+    if scope not in ALL_FIT_SCOPES:  # (FIT_SCOPES above keeps the three names its tests pin; the names are resolved through model.ALL_FIT_SCOPES)
+        raise ValueError(f"this_main.fit_scope={scope}: " + " | ".join(ALL_FIT_SCOPES))
     return scope
 
 

@@ -108,12 +108,23 @@ FIT_CROSS = FitScope("cross", FIT_TAIL, _LAST_LAYER, ("multihead_attn.in_proj_we
                      "cs_cross_fit_supported", ("hidden", "dec_heads", "patch"), "cs_fit_cross_keep", "cs_cross_backward", "cs_set_cross_weights",
                      NotImplementedError, "cross-attention fit is built for the tail's shapes and decoder head dims 16, 48 and 96 "
                                           "(hidden {a.hidden}, {a.dec_heads} heads, patch {a.patch})")
+FIT_LAYER = FitScope("layer", FIT_CROSS, _LAST_LAYER, ("self_attn.in_proj_weight", "self_attn.in_proj_bias", "self_attn.out_proj.weight",
+                                                      "self_attn.out_proj.bias", "norm1.weight", "norm1.bias"),
+                     "cs_layer_fit_supported", ("hidden", "dec_heads", "patch", "do_self_attn"), "cs_fit_layer_keep", "cs_layer_backward",
+                     "cs_set_layer_weights", NotImplementedError, "whole-layer fit is built for the cross-attention fit's shapes "
+                                                                  "(hidden {a.hidden}, {a.dec_heads} heads, patch {a.patch})")
 FIT_SCOPES = {s.name: s for s in (FIT_HEAD, FIT_TAIL, FIT_CROSS)}
+# two tables: FIT_SCOPES keeps the three scopes its tests pin; every lookup by name goes through ALL_FIT_SCOPES, which has the whole-layer scope too
+ALL_FIT_SCOPES = {**FIT_SCOPES, "layer": FIT_LAYER}
 
 
 def check_fit_supported(arch: ArchSpec, scope) -> None:
-    """Raises the scope's error unless its backward is built for `arch`; scope: a FitScope or its name."""
-    s = FIT_SCOPES[scope] if isinstance(scope, str) else scope
+    """Raises the scope's error unless its backward is built for `arch`; scope: a FitScope or its name.  The whole-layer scope without a decoder
+    self-attention is a ValueError: there is nothing to fit."""
+    s = ALL_FIT_SCOPES[scope] if isinstance(scope, str) else scope
+    if s is FIT_LAYER and not arch.do_self_attn:
+        raise ValueError("fit_scope=layer needs model.decoder_do_self_attn=True: without the self-attention the layer scope has nothing to fit "
+                         "beyond fit_scope=cross")
     if not getattr(_lib.load(), s.supported)(*(getattr(arch, a) for a in s.supported_args)):
         raise s.error("the " + s.built_for.format(a=arch))
 
@@ -291,6 +302,7 @@ class CrossScoreNet(torch.nn.Module):
         self.finite_check = True   # every forward counts the non-finite values of its score map on the device (~3 us)
         self._after_sub_batch = None  # fit_head_step's / fit_tail_step's hook behind each sub-batch's forward call (_score)
         self._tail_keep = False    # fit_tail_keep: forwards keep what the tail's backward reads (fit_tail_step turns it on for its call)
+        self._layer_keep = False   # fit_layer_keep: ... and what the self-attention block's backward reads (fit_layer_step, for its call)
         self._cross_keep = False   # fit_cross_keep: ... and what the cross-attention block's backward reads (fit_cross_step, for its call)
         self.register_load_state_dict_post_hook(lambda module, incompatible: module._mark_dirty())
 
@@ -392,6 +404,8 @@ class CrossScoreNet(torch.nn.Module):
             _lib.check(lib.cs_fit_tail_keep(h, 1))
         if self._cross_keep:
             _lib.check(lib.cs_fit_cross_keep(h, 1))
+        if self._layer_keep:
+            _lib.check(lib.cs_fit_layer_keep(h, 1))
         return h
 
     # -- forward ----------------------------------------------------------------------------------------------
@@ -722,10 +736,12 @@ class CrossScoreNet(torch.nn.Module):
                 break
         return {"one_lane_s": one, "lanes_s": seen}
 
-    # -- fitting on the device: the scopes FIT_HEAD < FIT_TAIL < FIT_CROSS of the table above ---------------------
+    # -- fitting on the device: the scopes FIT_HEAD < FIT_TAIL < FIT_CROSS < FIT_LAYER of the table above --------
     HEAD_KEYS = FIT_HEAD.keys(0)  # (the head's keys name no layer)
     TAIL_KEYS = property(lambda self: FIT_TAIL.keys(self.arch.dec_layers), doc="the ten keys of the tail, in the order of cs_tail_backward's gradients")
     CROSS_KEYS = property(lambda self: FIT_CROSS.keys(self.arch.dec_layers), doc="the sixteen keys of the cross-attention fit, in cs_cross_backward's order")
+
+    LAYER_KEYS = property(lambda self: FIT_LAYER.keys(self.arch.dec_layers), doc="the twenty-two keys of the whole-layer fit, in cs_layer_backward's order")
 
     def _fit_parameters(self, scope: FitScope):
         if not self._do_reference_cross:
@@ -824,6 +840,10 @@ class CrossScoreNet(torch.nn.Module):
         """The last decoder layer's multihead_attn in_proj and out_proj and norm2, then the tail: sixteen tensors in CROSS_KEYS order."""
         return self._fit_parameters(FIT_CROSS)
 
+    def layer_parameters(self):
+        """The last decoder layer's self_attn in_proj and out_proj and norm1, then the cross-attention fit's: twenty-two tensors in LAYER_KEYS order."""
+        return self._fit_parameters(FIT_LAYER)
+
     def head_fit_supported(self) -> bool:
         return self._fit_supported(FIT_HEAD)
 
@@ -832,6 +852,14 @@ class CrossScoreNet(torch.nn.Module):
 
     def cross_fit_supported(self) -> bool:
         return self._fit_supported(FIT_CROSS)
+
+    def layer_fit_supported(self) -> bool:
+        return self._fit_supported(FIT_LAYER)
+
+    def fit_layer_keep(self, on: bool = True) -> None:
+        """Following forwards also keep what layer_backward reads (cs_fit_layer_keep): fit_cross_keep's copies, x0, and the last
+        self-attention's output and lse."""
+        self._fit_keep(FIT_LAYER, on)
 
     def fit_tail_keep(self, on: bool = True) -> None:
         """Following forwards also keep the last decoder layer's norm2 output and ReLU rows (cs_fit_tail_keep): what tail_backward reads."""
@@ -855,6 +883,10 @@ class CrossScoreNet(torch.nn.Module):
         """The same through cs_cross_backward (that forward run with fit_cross_keep on): the sixteen gradients in CROSS_KEYS order and the loss."""
         return self._fit_backward(FIT_CROSS, gt, inv_count, accumulate, out)
 
+    def layer_backward(self, gt, inv_count=None, accumulate=False, out=None):
+        """The same through cs_layer_backward (that forward run with fit_layer_keep on): the twenty-two gradients in LAYER_KEYS order and the loss."""
+        return self._fit_backward(FIT_LAYER, gt, inv_count, accumulate, out)
+
     def fit_head_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
         """_fit_step over the four tensors of the head: cs_head_backward, four cs_op_adamw launches, cs_set_head_weights."""
         return self._fit_step(FIT_HEAD, query, refs, gt, state, ref_tokens)
@@ -867,6 +899,11 @@ class CrossScoreNet(torch.nn.Module):
         """_fit_step over the sixteen tensors of the cross-attention fit: cs_cross_backward on a forward with fit_cross_keep on,
         cs_set_cross_weights, the tail's and the head's."""
         return self._fit_step(FIT_CROSS, query, refs, gt, state, ref_tokens)
+
+    def fit_layer_step(self, query, refs, gt, state: "HeadFitState", ref_tokens=None):
+        """_fit_step over the twenty-two tensors of the whole-layer fit: cs_layer_backward on a forward with fit_layer_keep on,
+        cs_set_layer_weights, the cross-attention fit's, the tail's and the head's."""
+        return self._fit_step(FIT_LAYER, query, refs, gt, state, ref_tokens)
 
     def _debug_inputs(self, c_name: str, rows: int, specs):
         """Fresh tensors of specs' (shape, dtype) filled by the library's cs_debug_*_inputs `c_name` from the last forward call; rows = its B h w,
@@ -898,6 +935,13 @@ class CrossScoreNet(torch.nn.Module):
         rc, kv = (int(rows), Cc), (int(rows) * int(N), Cc)
         return self._debug_inputs("cs_debug_cross_inputs", rows, [(rc, torch.float32), (rc, t16), (rc, t16),
                                                                   ((int(rows) * self.arch.dec_heads,), torch.float32), (kv, t16), (kv, t16)])
+
+    def layer_inputs(self, rows: int):
+        """(x0, Qs', Ks, Vs, Os, lse_s) of the last forward call's last self-attention: x0 (rows, C) fp32, the three blocks of the packed projection
+        and Os (rows, C) 16 bit, lse_s (rows heads) fp32 in (B, heads, Np) order; that forward must have run with fit_layer_keep on."""
+        rc, t16 = (int(rows), self.arch.hidden), self.token_dtype
+        return self._debug_inputs("cs_debug_layer_inputs", rows, [(rc, torch.float32), (rc, t16), (rc, t16), (rc, t16), (rc, t16),
+                                                                  ((int(rows) * self.arch.dec_heads,), torch.float32)])
 
     # -- debug taps used by the stage-level parity tests (tests/test_hip_stages.py) ------------------------------------
     def debug_capture(self, on: bool = True) -> None:
@@ -946,7 +990,7 @@ def load_lightning_checkpoint(path: str) -> Dict[str, torch.Tensor]:
 
 
 class HeadFitState:
-    """What fit_head_step, fit_tail_step or fit_cross_step keeps between steps: AdamW's moments of the scope's parameters, the step count (from 1
+    """What fit_head_step, fit_tail_step, fit_cross_step or fit_layer_step keeps between steps: AdamW's moments of the scope's parameters, the step count (from 1
     at the first step), the learning rate (the driver's StepLR writes it) and the gradient buffers.  Defaults are torch.optim.AdamW's."""
 
     def __init__(self, lr: float = 5e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2):

@@ -843,6 +843,55 @@ int cs_debug_cross_inputs(cs_handle h, float* x1, uint16_t* Qp, uint16_t* O, flo
 int cs_set_cross_weights(cs_handle h, const float* in_proj_w, const float* in_proj_b, const float* out_w, const float* out_b, const float* g2,
                          const float* b2, cs_stream stream);
 
+/* ---- Fitting the whole last decoder layer: its self-attention and norm1 with the cross-attention fit (csrc/layerfit.hip) ----
+ * Twenty-two tensors: the layer's self_attn.in_proj_weight (3C, C) and in_proj_bias (3C), self_attn.out_proj.weight (C, C) and bias (C), norm1
+ * weight and bias (C), and the cross-attention fit's sixteen.  x0 (M, C) fp32 is the row set that entered the layer; Qs', Ks, Vs the three C-wide
+ * column blocks of the 16-bit packed projection rows (M, ldqkv) as the forward stored them (log2(e)/sqrt(dh) folded into Qs'); Os (M, ldos) the
+ * self-attention's output and lse_s (B, heads, Np) its base-2 log-sum-exp; every batch item attends to its own Np rows.  Wq (C, C) is the
+ * cross-attention's packed query projection (the scale folded in), Wo_s the self-attention's packed out_proj.  The backward continues the cross
+ * fit's chain (whose sixteen gradients and loss come out bit for bit as cs_op_cross_backward's), with dQu that block's stored query gradient:
+ *   dx1 = (short_cut ? f32(dy2h) : 0) + ln2 dQu Wq (fp32; the ln2 applied in fp32),  y1 = (short_cut ? x0 : 0) + Os Wo_s^T + bo_s recomputed in fp32,
+ *   (dgamma1, dbeta1, dy1h) = the LayerNorm backward,  dbo_s = inv_count sum_m dy1h,  dWo_s = inv_count dy1h^T Os,  dOsh = dy1h Wo_s rounded once,
+ *   (dQu_s, dKu_s, dV_s) = cs_op_attention_backward with Lq = Lk = Np,
+ *   in_proj rows [0, C): inv_count / sqrt(dh) dQu_s^T x0h (x0 rounded once);  [C, 2C): inv_count ln2 dKu_s^T x0h;  [2C, 3C): inv_count dV_s^T x0h;
+ *   in_proj_bias: the matching column sums.
+ * The gradient stops at x0.  Fixed summation orders, no atomics.  Pointer, stride and workspace rules are the cross-attention fit's. */
+/* the cross-attention fit's condition, and a decoder with self-attention */
+int cs_layer_fit_supported(int hidden, int heads, int patch, int do_self_attn);
+size_t cs_layer_backward_workspace_bytes(int B, int Np, int N, int C, int P, int heads);
+/* the whole backward on caller-owned tensors: x0, x1 and x2 contiguous; Qs, Ks, Vs share the row pitch ldqkv; the weights packed 16 bit */
+int cs_op_layer_backward(const float* x0, const uint16_t* Qs, const uint16_t* Ks, const uint16_t* Vs, int ldqkv, const uint16_t* Os, int ldos,
+                         const float* lse_s, const uint16_t* Wq, int ldwq, const uint16_t* Wo_s, int ldwos, const float* bo_s, const float* gamma1,
+                         const float* x1, const uint16_t* Qp, int ldq, const uint16_t* K, const uint16_t* V, int ldkv, const uint16_t* O, int ldo,
+                         const float* lse, const uint16_t* mem, int ldm, const uint16_t* W1, int ldw1, const uint16_t* Wo, int ldwo, const float* bo,
+                         const float* gamma2, int N, int heads, int short_cut, const float* x2, const uint16_t* H, int ldh, const uint16_t* X,
+                         int ldx, const uint16_t* A, int lda, const uint16_t* W2, int ldw2, const float* b2, const float* gamma3, float eps,
+                         const uint16_t* Wa, int ldwa, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P,
+                         int C, int act, float powp, double inv_count, int accumulate, float* dWin_s, float* dbin_s, float* dWo_s, float* dbo_s,
+                         float* dgamma1, float* dbeta1, float* dWin, float* dbin, float* dWo, float* dbo, float* dgamma2, float* dbeta2, float* dW1,
+                         float* db1, float* dW2, float* db2, float* dgamma3, float* dbeta3, float* dWa, float* dba, float* dWb, float* dbb,
+                         double* loss, void* ws, cs_stream stream);
+/* A persistent switch like cs_fit_cross_keep, off by default, and it implies that switch's copies.  On: the last decoder layer's self-attention also
+ * writes its lse, straight into a region the handle owns, and x0 (in front of the norm1 closing that overwrites it) and Os (in front of the
+ * cross-attention that overwrites it) are copied there device-to-device on the forward's stream (two more copies: cs_forward_stats counts
+ * layer_keep=2).  The packed Q' | K | V rows are read from the workspace where the forward left them (nothing behind that attention writes them).
+ * The score map, the mean and every tap keep their bits.  Off: nothing of the forward changes. */
+int cs_fit_layer_keep(cs_handle h, int on);
+/* cs_op_layer_backward on what the LAST cs_forward* call on this handle left (with cs_fit_layer_keep on), with the handle's packed weights.
+ * CS_ERR_STATE in the cases of cs_cross_backward, and when that forward ran with cs_fit_layer_keep off; CS_ERR_UNSUPPORTED without self-attention. */
+int cs_layer_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWin_s, float* dbin_s, float* dWo_s,
+                      float* dbo_s, float* dgamma1, float* dbeta1, float* dWin, float* dbin, float* dWo, float* dbo, float* dgamma2, float* dbeta2,
+                      float* dW1, float* db1, float* dW2, float* db2, float* dgamma3, float* dbeta3, float* dWa, float* dba, float* dWb, float* dbb,
+                      double* loss, cs_stream stream);
+/* debug: contiguous copies of x0 (rows, C) fp32, Qs', Ks, Vs and Os (rows, C) 16 bit and lse_s (B, heads, Np) fp32 that cs_layer_backward would
+ * read; any may be NULL; rows as in cs_debug_head_inputs */
+int cs_debug_layer_inputs(cs_handle h, float* x0, uint16_t* Qs, uint16_t* Ks, uint16_t* Vs, uint16_t* Os, float* lse_s, int rows, cs_stream stream);
+/* Re-packs fp32 device weights of the LAST decoder layer's self-attention block (self_attn.in_proj_weight (3C, C) and in_proj_bias (3C), out_proj
+ * weight (C, C) and bias (C), norm1 weight and bias (C)) into the finalised handle's existing buffers exactly as cs_finalize packs them (the query
+ * rows with log2(e)/sqrt(dh) folded in), in stream order behind the handle's last call; the race caveat of cs_set_head_weights holds. */
+int cs_set_layer_weights(cs_handle h, const float* in_proj_w, const float* in_proj_b, const float* out_w, const float* out_b, const float* g1,
+                         const float* b1, cs_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
