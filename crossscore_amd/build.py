@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcrossscore_hip.so")
-SOURCES = ["api.hip", "forward.hip", "ops.hip", "gemm.hip", "gemm256.hip", "attention.hip", "refuse.hip", "elementwise.hip", "preprocess.hip", "panel.hip", "panel4.hip", "patch.hip", "rowln.hip", "png.hip", "pngdec.hip", "jpegdec.hip", "jpegprog.hip", "gtmap.hip", "gtsum.hip", "select.hip", "scorepool.hip", "sheet.hip", "headfit.hip", "tailfit.hip", "attnbwd.hip", "crossfit.hip", "layerfit.hip"]
+SOURCES = ["api.hip", "forward.hip", "ops.hip", "fit_host.hip", "gemm.hip", "gemm256.hip", "attention.hip", "refuse.hip", "elementwise.hip", "preprocess.hip", "panel.hip", "panel4.hip", "patch.hip", "rowln.hip", "png.hip", "pngdec.hip", "jpegdec.hip", "jpegprog.hip", "gtmap.hip", "gtsum.hip", "select.hip", "scorepool.hip", "sheet.hip", "headfit.hip", "tailfit.hip", "attnbwd.hip", "crossfit.hip", "layerfit.hip"]
 
 
 # panel.hip: its GELU arithmetic shares one wave's issue stream with the MFMAs; SLP-packed v_pk_fma_f32 (dependent-issue nops)

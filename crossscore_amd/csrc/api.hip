@@ -1,6 +1,6 @@
 // C ABI of the CrossScore gfx950 path (see include/crossscore_hip.h): the handle's life cycle, weight packing, and the stats / debug /
-// profile / lane accessors.  Host-side only.  The forward itself is forward.hip, the single-op entry points are ops.hip; what the three
-// share is cs_model.h.
+// profile / lane accessors.  Host-side only.  The forward itself is forward.hip, the single-op entry points are ops.hip, fitting is fit_host.hip;
+// what the four share is cs_model.h.
 #include "cs_model.h"
 
 #include <cmath>
@@ -120,9 +120,7 @@ void cs_destroy(cs_handle h) {
   reap_retired(h, true);
   if (h->ws) hipFree(h->ws);
   if (h->hfit_ws) hipFree(h->hfit_ws);
-  if (h->tail_kept) hipFree(h->tail_kept);
-  if (h->cross_kept) hipFree(h->cross_kept);
-  if (h->layer_kept) hipFree(h->layer_kept);
+  if (h->fit_kept) hipFree(h->fit_kept);
   if (h->ev_done) hipEventDestroy(h->ev_done);
   if (h->ev_kv0) hipEventDestroy(h->ev_kv0);
   if (h->ev_kv1) hipEventDestroy(h->ev_kv1);

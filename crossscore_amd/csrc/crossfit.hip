@@ -8,8 +8,6 @@
 // Every sum has a fixed order; nothing is accumulated with atomics.
 #include "fit_shared.h"
 
-#include <cmath>
-
 namespace {
 
 using namespace cs_fit;
@@ -40,72 +38,37 @@ extern "C" {
 size_t cs_cross_backward_workspace(int B, int Np, int N, int C, int heads) { return cs_fit::cross_carve(nullptr, B, Np, N, C, heads).end; }
 
 // The attention backward of one cross backward, as the launch below queues it: K and V in place in their packed rows, dKu | dV side by side.
-// cross_backward_run (ops.hip) builds it too and puts it through cs_attnbwd_check with every other check, before the first launch.
+// cross_backward_run (fit_host.hip) builds it too and puts it through cs_attnbwd_check with every other check, before the first launch.
 void cs_cross_backward_attn_params(const CsCrossBackward* q, void* ws, int bf, CsAttnBwdParams* out) {
   const CsHeadBackward& hq = q->tail.head;
   const int B = hq.B, Np = hq.gh * hq.gw, C = hq.C;
   const CrossWs k = cross_carve(q, ws);
-  CsAttnBwdParams a{};
-  a.Q = q->Qp; a.K = q->K; a.V = q->V; a.O = q->O; a.dO = k.dOh; a.lse = q->lse;
-  a.ldq = q->ldq; a.ldk = q->ldkv; a.ldv = q->ldkv; a.ldo = q->ldo; a.lddo = C;
-  a.q_bs = (long long)Np * q->ldq; a.k_bs = (long long)q->N * Np * q->ldkv; a.v_bs = a.k_bs; a.o_bs = (long long)Np * q->ldo; a.do_bs = (long long)Np * C;
-  a.nbatch = B; a.heads = q->heads; a.Lq = Np; a.Lk = q->N * Np; a.scale_log2e = 1.0f;
-  a.dQ = k.dQu; a.lddq = C; a.dq_bs = (long long)Np * C;
-  a.dK = k.dKV; a.lddk = 2 * C; a.dk_bs = (long long)q->N * Np * 2 * C;
-  a.dV = k.dKV + C; a.lddv = 2 * C; a.dv_bs = a.dk_bs;
-  a.D = static_cast<float*>(k.aws); a.bf16 = bf;
-  *out = a;
+  *out = attn_bwd_params(q->Qp, q->ldq, q->K, q->V, q->ldkv, q->O, q->ldo, q->lse, k.dOh, B, q->heads, Np, q->N * Np, C, k.dQu, C, k.dKV, k.dKV + C,
+                         2 * C, k.aws, bf);
 }
 
 hipError_t cs_cross_backward_launch(const CsCrossBackward* q, void* ws, int bf, hipStream_t st) {
   const CsHeadBackward& hq = q->tail.head;
-  const int B = hq.B, Np = hq.gh * hq.gw, M = B * Np, Mk = M * q->N, C = hq.C, dh = C / q->heads;
-  const size_t mc = (size_t)M * C;
+  const int M = hq.B * hq.gh * hq.gw, Mk = M * q->N, C = hq.C;
   const CrossWs k = cross_carve(q, ws);
-  const h16_t *dyh = k.dyh, *dHh = k.dHh;
-  h16_t *WT = k.WT, *dy2h = k.dy2h, *dOh = k.dOh, *x1h = k.x1h, *dQu = k.dQu, *dKV = k.dKV;
-  float *zb = k.zb, *dyf = k.dyf, *dx2 = k.dx2, *y2 = k.y2;
-  void *lws = k.lws, *tws = k.tws;
   const float scale = (float)hq.inv_count;
   hipError_t e = cs_tail_backward_launch(&q->tail, ws, bf, st);  // the ten gradients of the tail and the head, the loss; dyh and dHh stay in the workspace
   if (e != hipSuccess) return e;
-  if ((e = hipMemsetAsync(zb, 0, (size_t)C * 4, st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(k.zb, 0, (size_t)C * 4, st)) != hipSuccess) return e;
   // dx2 = f32(dyh) + dHh W1
-  const long long n8 = (long long)(mc / 8);
-  widen16_kernel<<<(unsigned)((n8 + 255) / 256), 256, 0, st>>>(dyh, dyf, n8, bf);
+  const long long n8 = (long long)((size_t)M * C / 8);
+  widen16_kernel<<<(unsigned)((n8 + 255) / 256), 256, 0, st>>>(k.dyh, k.dyf, n8, bf);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  if ((e = cs_transpose16_launch(q->W1, q->ldw1, C, C, WT, C, st)) != hipSuccess) return e;
-  CsGemmParams gx = gemm_params(dHh, C, WT, C, M, C, zb, dx2, bf);
-  gx.resid = dyf; gx.ldr = C;
-  if ((e = gemm_go(gx, CS_EPI_RESID_F32, st)) != hipSuccess) return e;
-  // y2 = (short cut ? x1 : 0) + O Wo^T + bo
-  CsGemmParams gy = gemm_params(q->O, q->ldo, q->Wo, q->ldwo, M, C, q->bo, y2, bf);
-  gy.resid = q->short_cut ? q->x1 : nullptr; gy.ldr = C;
-  if ((e = gemm_go(gy, CS_EPI_RESID_F32, st)) != hipSuccess) return e;
-  CsLnBackward ln{};
-  ln.y = y2; ln.ldy = C; ln.dx = dx2; ln.ldx = C; ln.gamma = q->gamma2; ln.eps = q->tail.eps; ln.M = M; ln.C = C; ln.scale = scale; ln.accumulate = hq.accumulate;
-  ln.dyh = dy2h; ln.ldd = C; ln.dgamma = q->dg2; ln.dbeta = q->db2;
-  if ((e = cs_ln_backward_launch(&ln, lws, bf, st)) != hipSuccess) return e;
-  // dWo, dbo
-  CsGemmTn t{};
-  t.G = dy2h; t.ldg = C; t.X = q->O; t.ldx = q->ldo; t.M = M; t.N = C; t.K = C; t.scale = scale; t.accumulate = hq.accumulate;
-  t.out = q->dWo; t.ldo = C; t.colsum = q->dbo;
-  if ((e = cs_gemm_tn_launch(&t, tws, bf, st)) != hipSuccess) return e;
-  // dOh = dy2h Wo
-  if ((e = cs_transpose16_launch(q->Wo, q->ldwo, C, C, WT, C, st)) != hipSuccess) return e;  // (stream order: dx2's GEMM has read WT)
-  if ((e = gemm_go(gemm_params(dy2h, C, WT, C, M, C, zb, dOh, bf), CS_EPI_BIAS_F16, st)) != hipSuccess) return e;
-  // the attention backward (its parameters: cs_cross_backward_attn_params above; checked by the caller with everything else)
+  if ((e = through_weight(k.dHh, q->W1, q->ldw1, M, C, k.WT, k.zb, k.dyf, k.dx2, CS_EPI_RESID_F32, bf, st)) != hipSuccess) return e;
+  // y2 = (short cut ? x1 : 0) + O Wo^T + bo and norm2: dg2, db2, dy2h; dWo, dbo; dOh = dy2h Wo
+  const Closing c{q->O, q->ldo, q->Wo, q->ldwo, q->bo, q->short_cut ? q->x1 : nullptr, q->gamma2, q->tail.eps};
+  if ((e = closing_backward(c, k.dx2, {k.y2, k.dy2h, k.WT, k.zb, k.lws, k.tws}, {q->dWo, q->dbo, q->dg2, q->db2, k.dOh}, M, C, scale, hq.accumulate, bf,
+                            st)) != hipSuccess)
+    return e;
+  // the attention backward (its parameters: cs_cross_backward_attn_params above) and in_proj: dQu against x1h, dKu | dV against the reference tokens
   CsAttnBwdParams a{};
   cs_cross_backward_attn_params(q, ws, bf, &a);
-  if ((e = cs_attnbwd_launch(&a, dh, st)) != hipSuccess) return e;
-  // in_proj: the 1 / sqrt(dh) of the folded query scale and the ln2 of the base-2 logits ride in the reductions' fp32 scale
-  if ((e = cs_pack_f16_launch(q->x1, M, C, x1h, C, nullptr, nullptr, bf, st)) != hipSuccess) return e;
-  t.G = dQu; t.ldg = C; t.X = x1h; t.ldx = C; t.M = M; t.scale = scale * (1.0f / std::sqrt((float)dh)); t.out = q->dWin; t.colsum = q->dbin;
-  if ((e = cs_gemm_tn_launch(&t, tws, bf, st)) != hipSuccess) return e;
-  t.G = dKV; t.ldg = 2 * C; t.X = q->mem; t.ldx = q->ldm; t.M = Mk; t.scale = scale * 0.69314718055994531f; t.out = q->dWin + (size_t)C * C; t.colsum = q->dbin + C;
-  if ((e = cs_gemm_tn_launch(&t, tws, bf, st)) != hipSuccess) return e;
-  t.G = dKV + C; t.scale = scale; t.out = q->dWin + (size_t)2 * C * C; t.colsum = q->dbin + 2 * C;
-  return cs_gemm_tn_launch(&t, tws, bf, st);
+  return attn_block_backward(a, q->x1, k.x1h, M, C, q->mem, q->ldm, Mk, scale, hq.accumulate, q->dWin, q->dbin, k.tws, bf, st);
 }
 
 }

@@ -379,7 +379,7 @@ struct CsLayerBackward {
   float *dWin_s, *dbin_s, *dWo_s, *dbo_s, *dg1, *db1;  // in_proj (3C, C) and (3C), out_proj (C, C) and (C), norm1 (C) each
 };
 
-// ---- The launch surface between the kernel files and the host files (api.hip, forward.hip, ops.hip): every cs_*_launch / cs_*_check /
+// ---- The launch surface between the kernel files and the host files (api.hip, forward.hip, ops.hip, fit_host.hip): every cs_*_launch / cs_*_check /
 // cs_*_supported / size helper that one .hip defines and another calls, declared ONCE.  Every defining file includes this header, so a changed
 // parameter list fails to compile there instead of linking (most of these are extern "C") and misbehaving at run time. ----
 

@@ -1,9 +1,11 @@
-// What the three host files share: api.hip (handle life cycle, weights, accessors), forward.hip (plan + the forward's steps) and ops.hip
-// (single-op entry points).  The handle, its packed layers, the workspace plan, the launch helper that keeps the census / profile records,
-// and the library's one error slot.  Host-side only; no kernel file includes this.
+// What the four host files share: api.hip (handle life cycle, weights, accessors), forward.hip (plan + the forward's steps), ops.hip
+// (single-op entry points) and fit_host.hip (the fit scopes' checks, operators and backwards on a handle).  The handle, its packed layers, the
+// workspace plan, the launch helper that keeps the census / profile records, and the library's one error slot.  Host-side only; no kernel file
+// includes this.
 #pragma once
 #include "../../include/crossscore_hip.h"
 #include "cs_common.h"
+#include "fit_shared.h"
 
 #include <algorithm>
 #include <map>
@@ -123,30 +125,24 @@ struct cs_model {
     bool any() const { return share || peak_prob || peak_index || entropy; }
   };
   RefUse ref_use;
-  // head fit (cs_head_backward): what the last forward-class call left behind, and the backward's own workspace
+  // fitting (fit_host.hip): what the last forward-class call left behind, and the backwards' own workspace
   struct LastForward {
-    bool ok = false; int mode = -1, B = 0, H = 0, W = 0; const float* xq = nullptr; const h16_t* dhid = nullptr; bool tail_kept = false;
-    // cs_fit_cross_keep: the last layer's cross-attention as the forward left it in the workspace -- Q' (M, C), the layer's K block of the packed
+    bool ok = false; int mode = -1, B = 0, H = 0, W = 0; const float* xq = nullptr; const h16_t* dhid = nullptr;
+    FitScope kept = FIT_HEAD;  // the deepest scope this forward kept for: fit_kept is carved at this level (cs_fit::kept_carve)
+    // kept >= FIT_CROSS: the last layer's cross-attention as the forward left it in the workspace -- Q' (M, C), the layer's K block of the packed
     // K | V rows (Mk, ldkv; V is C columns further), O (M, C), lse (B, heads, Np) -- and the reference tokens its K / V projection read (Mk, C)
-    bool cross_kept = false; int N = 0; const h16_t* dq = nullptr; const h16_t* k = nullptr; int ldkv = 0; const h16_t* dob = nullptr;
+    int N = 0; const h16_t* dq = nullptr; const h16_t* k = nullptr; int ldkv = 0; const h16_t* dob = nullptr;
     const float* lse = nullptr; const h16_t* mem = nullptr;
-    // cs_fit_layer_keep: the last layer's packed self-attention projection rows Q' | K | V (M, 3C) where the forward left them
-    bool layer_kept = false; const h16_t* dqkv = nullptr;
+    // kept >= FIT_LAYER: the last layer's packed self-attention projection rows Q' | K | V (M, 3C) where the forward left them
+    const h16_t* dqkv = nullptr;
   };
   LastForward last_fwd;
-  void* hfit_ws = nullptr; size_t hfit_ws_bytes = 0;  // X in 16 bits (M, C), then cs_head_backward_workspace (cs_tail_backward_workspace once the tail is fitted)
-  // tail fit (cs_fit_tail_keep): with the switch on every forward copies the last layer's norm2 output x2 (M, C) fp32 and H = relu(linear1(x2))
-  // (M, C) 16 bit into this region, between the two closings of that layer
-  bool tail_keep = false;
-  void* tail_kept = nullptr; size_t tail_kept_bytes = 0;
-  // cross-attention fit (cs_fit_cross_keep): implies tail_keep; in addition the last layer's cross-attention writes its lse and x1, the fp32 rows
-  // that enter that block, is copied into this region before the norm2 closing overwrites it
-  bool cross_keep = false;
-  void* cross_kept = nullptr; size_t cross_kept_bytes = 0;
-  // whole-layer fit (cs_fit_layer_keep): implies cross_keep; in addition the last layer's self-attention writes its lse, and x0 (the fp32 rows that
-  // enter the layer), Os (its 16-bit output) and that lse are copied into this region before the norm1 closing and the cross-attention overwrite them
-  bool layer_keep = false;
-  void* layer_kept = nullptr; size_t layer_kept_bytes = 0;
+  void* hfit_ws = nullptr; size_t hfit_ws_bytes = 0;  // X in 16 bits (M, C), then the workspace of the deepest scope a backward has run (cs_*_backward_workspace: each begins with its parent's)
+  // The keep switches (cs_fit_tail_keep, cs_fit_cross_keep, cs_fit_layer_keep), independent of one another: a forward keeps for the deepest scope
+  // whose switch is on, which implies its parents' pieces (what is copied, and when: Fwd::keep_rows in forward.hip).  All of it goes into ONE region,
+  // carved by cs_fit::kept_carve (fit_shared.h) and grown like the workspace.
+  bool tail_keep = false, cross_keep = false, layer_keep = false;
+  void* fit_kept = nullptr; size_t fit_kept_bytes = 0;
   float* qs_dec = nullptr;  // [C] log2(e) / sqrt(dh) of the decoder: the row scale of the packed query projections (cs_set_cross_weights and cs_set_layer_weights pack with it again)
   unsigned* nonfinite = nullptr;  // device counter: non-finite score-map values seen since the last cs_nonfinite_count
   // profiling
@@ -215,13 +211,10 @@ inline void fill_triples(const int32_t* query_group, int B, const int32_t* offse
 
 inline bool supported_dh(int dh) { return dh == 16 || dh == 48 || dh == 64 || dh == 96 || dh == 128 || dh == 192; }
 
-// ops.hip: the checks of a head backward, then its launches
+// fit_host.hip: every check of a scope's backward (its parent's is its first part), then its launches
 int head_backward_run(const char* op, const CsHeadBackward& q, void* ws, int bf, hipStream_t st);
-// ops.hip: the same for the tail's backward (the head's is its first part)
 int tail_backward_run(const char* op, const CsTailBackward& q, void* ws, int bf, hipStream_t st);
-// ops.hip: the same for the cross-attention block's backward (the tail's is its first part)
 int cross_backward_run(const char* op, const CsCrossBackward& q, void* ws, int bf, hipStream_t st);
-// ops.hip: the same for the whole layer's backward (the cross-attention block's is its first part)
 int layer_backward_run(const char* op, const CsLayerBackward& q, void* ws, int bf, hipStream_t st);
 
 // forward.hip

@@ -4,7 +4,6 @@
 // CrossReferenceNet.forward (model/cross_reference.py:52-94) and the post-norm decoder layer (transformer.py:157-173).
 // forward_body at the end of the file is the sequence; the functions before it are its steps, in order.
 #include "cs_model.h"
-#include "fit_shared.h"
 
 #include <chrono>
 #include <cstdio>
@@ -136,9 +135,6 @@ struct Arena {  // carve 256-byte aligned pieces out of the workspace
     return p;
   }
 };
-
-// cs_model::tail_kept holds x2 (M, C) fp32 and, from the next 256 bytes on, H (M, C) 16 bit: x2's share (keep_tail writes, kept_H reads)
-size_t kept_x2_bytes(size_t M, size_t C) { return cs_fit::up256(M * C * 4); }
 
 Plan make_plan(const cs_model* m, int B, int N, int N_enc, int H, int W, char* base, int R_sel = 0, bool own_sim = false, bool grouped = false) {
   Plan p{};
@@ -305,9 +301,10 @@ struct Fwd {
   // (decoder) each sub-block closes with LN(x + Linear(.)): one launch where the row-complete kernel is built (C = 384), else GEMM + LayerNorm
   // ... and where it is, the sub-block's NEXT linear rides in the same launch when it is C wide (second stage of rowln.hip)
   bool fused_ln = false, fuse_next = false;
-  bool tail_kept = false;  // (cs_fit_tail_keep) this call has queued the two copies cs_tail_backward works on
-  bool cross_kept = false;  // (cs_fit_cross_keep) ... and the copy of x1, with lse written: what cs_cross_backward works on
-  bool layer_kept = false;  // (cs_fit_layer_keep) ... and the copies of x0 and Os, with the self-attention's lse written: what cs_layer_backward works on
+  // (fit keeps) the deepest scope this call keeps for -- FIT_TAIL: the two copies cs_tail_backward works on; FIT_CROSS: the copy of x1 as well, with
+  // lse written; FIT_LAYER: the copies of x0 and Os as well, with the self-attention's lse written -- and the handle's kept region carved for it
+  FitScope kept = FIT_HEAD;
+  cs_fit::Kept kp{};
 
   // ---- step 1: arguments ----
   int validate() {
@@ -746,51 +743,36 @@ struct Fwd {
     L.small("ref_use", [&] { return cs_refuse_launch(&r, dh, L.st); });
   }
 
-  // cs_fit_tail_keep: between the norm2 and the norm3 closing of the last layer p.xq holds x2 and p.dhid holds
-  // H = relu(linear1(x2)); both are overwritten by the time the forward returns, so they are copied into the handle's own region here
-  // (M C fp32, then M C 16 bit), which grows like the workspace does.
-  int keep_tail(hipStream_t s) {
-    const size_t M = (size_t)B * p.Np, xb = kept_x2_bytes(M, p.C), need = xb + M * p.C * 2;
-    if (int r = grow_retired(h, &h->tail_kept, &h->tail_kept_bytes, need, s)) return r;
-    HIPCHK(hipMemcpyAsync(h->tail_kept, p.xq, M * p.C * 4, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(static_cast<char*>(h->tail_kept) + xb, p.dhid, M * p.C * 2, hipMemcpyDeviceToDevice, s));
-    h->census["tail_keep"] += 2;
-    tail_kept = true;
+  // What a forward keeps for the backwards.  The level is the deepest scope whose switch is on; the layer switch counts
+  // for its own pieces only where there is a self-attention to keep them from, and as the cross switch otherwise.
+  FitScope keep_level() const {
+    if (h->cfg.dec_layers <= 0) return FIT_HEAD;
+    if (h->layer_keep) return h->cfg.do_self_attn ? FIT_LAYER : FIT_CROSS;
+    return h->cross_keep ? FIT_CROSS : h->tail_keep ? FIT_TAIL : FIT_HEAD;
+  }
+  // the handle's kept region, grown like the workspace and carved for this call's level (the backwards read the same carve: cs_fit::kept_carve)
+  int ensure_kept(hipStream_t s) {
+    kept = keep_level();
+    if (kept == FIT_HEAD) return 0;
+    const int heads = h->cfg.dec_heads;
+    if (int r = grow_retired(h, &h->fit_kept, &h->fit_kept_bytes, cs_fit::kept_carve(nullptr, kept, B, p.Np, p.C, heads).end, s)) return r;
+    kp = cs_fit::kept_carve(h->fit_kept, kept, B, p.Np, p.C, heads);
     return 0;
   }
-
-  // cs_fit_cross_keep: in front of the last layer's norm2 closing p.xq holds x1, the rows that entered the cross-attention
-  // block (norm1's output, or the layer's input without self-attention); the closing overwrites it, so it is copied into the handle's own region.
-  // Q', the packed K | V rows, O and lse stay where they are: nothing behind the last layer's cross-attention writes p.dq (only a NOT-last layer's
-  // closing projects the next query into it), p.kv (written once, before the first layer), p.dob (the self-attention writes it, in front of the
-  // cross-attention) or p.lse, and mem is the caller's ref_tokens or p.mem_bf, which only the encoder / the gather write.
-  int keep_x1(hipStream_t s) {
-    const size_t need = (size_t)B * p.Np * p.C * 4;
-    if (int r = grow_retired(h, &h->cross_kept, &h->cross_kept_bytes, need, s)) return r;
-    HIPCHK(hipMemcpyAsync(h->cross_kept, p.xq, need, hipMemcpyDeviceToDevice, s));
-    h->census["cross_keep"] += 1;
-    cross_kept = true;
-    return 0;
-  }
-
-  // cs_fit_layer_keep: in front of the last layer's self-attention p.xq holds x0, the rows that enter the layer; the norm1
-  // closing overwrites it.  The self-attention's output Os (p.dob) is overwritten by the cross-attention's, and p.lse by that attention's own lse.
-  // So the handle's own region takes x0 here (M C fp32), then Os (M C 16 bit) behind the attention (keep_Os), and the self-attention writes its
-  // lse (B heads Np fp32) straight into it.  The packed Q' | K | V rows stay where they are: nothing behind the last layer's self-attention
-  // writes p.dqkv (only a layer's own in_proj GEMM does, in front of its self-attention).
-  size_t layer_kept_x0_bytes() const { return cs_fit::up256((size_t)B * p.Np * p.C * 4); }
-  size_t layer_kept_Os_bytes() const { return cs_fit::up256((size_t)B * p.Np * p.C * 2); }
-  int keep_x0(hipStream_t s, float** lse_s) {
-    const size_t need = layer_kept_x0_bytes() + layer_kept_Os_bytes() + (size_t)B * h->cfg.dec_heads * p.Np * 4;
-    if (int r = grow_retired(h, &h->layer_kept, &h->layer_kept_bytes, need, s)) return r;
-    HIPCHK(hipMemcpyAsync(h->layer_kept, p.xq, (size_t)B * p.Np * p.C * 4, hipMemcpyDeviceToDevice, s));
-    *lse_s = reinterpret_cast<float*>(static_cast<char*>(h->layer_kept) + layer_kept_x0_bytes() + layer_kept_Os_bytes());
-    return 0;
-  }
-  int keep_Os(hipStream_t s) {
-    HIPCHK(hipMemcpyAsync(static_cast<char*>(h->layer_kept) + layer_kept_x0_bytes(), p.dob, (size_t)B * p.Np * p.C * 2, hipMemcpyDeviceToDevice, s));
-    h->census["layer_keep"] += 2;
-    layer_kept = true;
+  // One kept piece: M C elements copied on s into the kept region, counted in the census under the switch's name.  The decoder below keeps
+  //   FIT_TAIL: x2 = p.xq and H = relu(linear1(x2)) = p.dhid between the last layer's norm2 and norm3 closings; both are overwritten by the time
+  //     the forward returns.
+  //   FIT_CROSS: x1 = p.xq, the rows that entered the cross-attention block (norm1's output, or the layer's input without self-attention), in front
+  //     of the norm2 closing that overwrites it.  Q', the packed K | V rows, O and lse stay where they are: nothing behind the last layer's
+  //     cross-attention writes p.dq (only a NOT-last layer's closing projects the next query into it), p.kv (written once, before the first layer),
+  //     p.dob (the self-attention writes it, in front of the cross-attention) or p.lse, and mem is the caller's ref_tokens or p.mem_bf, which only
+  //     the encoder / the gather write.
+  //   FIT_LAYER: x0 = p.xq in front of the last layer's self-attention (the norm1 closing overwrites it) and Os = p.dob behind it (the
+  //     cross-attention's output overwrites it); the self-attention writes its lse straight into kp.lse_s, since p.lse ends up with the
+  //     cross-attention's.  The packed Q' | K | V rows stay where they are: nothing behind the last layer's self-attention writes p.dqkv.
+  int keep_rows(void* dst, const void* src, size_t elem_bytes, const char* switch_name, hipStream_t s) {
+    HIPCHK(hipMemcpyAsync(dst, src, (size_t)B * p.Np * p.C * elem_bytes, hipMemcpyDeviceToDevice, s));
+    h->census[switch_name] += 1;
     return 0;
   }
 
@@ -823,6 +805,7 @@ struct Fwd {
     } else {
       L.gemm(kvp, CS_EPI_BIAS_F16);
     }
+    if (!L.rc) L.rc = ensure_kept(s);
     bool have_q = false, have_head0 = false;  // which projection a closing launch has already made
     for (int l = 0; l < c.dec_layers; ++l) {
       const DecLayer& D = h->dec[l];
@@ -830,27 +813,27 @@ struct Fwd {
       const float* shortcut = c.do_short_cut ? p.xq : nullptr;
       if (c.do_self_attn) {
         L.gemm(gp(p.q_bf, C, D.sa_Win, C, M, 3 * C, C, D.sa_bin, p.dqkv, 3 * C), CS_EPI_BIAS_F16);
-        const bool keep_l = last_l && h->layer_keep;  // whole-layer fit: x0, Os and the self-attention's lse kept
-        float* lse_s = nullptr;
-        if (keep_l && !L.rc) L.rc = keep_x0(s, &lse_s);
-        const CsAttnParams a = attn_params(p.dqkv, 3 * C, p.dqkv + C, p.dqkv + 2 * C, 3 * C, p.dob, p.Np, p.Np, c.dec_heads, lse_s);
+        const bool keep_l = last_l && kept >= FIT_LAYER;  // whole-layer fit: x0, Os and the self-attention's lse kept
+        if (keep_l && !L.rc) L.rc = keep_rows(kp.x0, p.xq, 4, "layer_keep", s);
+        const CsAttnParams a = attn_params(p.dqkv, 3 * C, p.dqkv + C, p.dqkv + 2 * C, 3 * C, p.dob, p.Np, p.Np, c.dec_heads, keep_l ? kp.lse_s : nullptr);
         L.attn(a, dec_dh, B);
-        if (keep_l && !L.rc) L.rc = keep_Os(s);
+        if (keep_l && !L.rc) L.rc = keep_rows(kp.Os, p.dob, 2, "layer_keep", s);
         have_q = dec_close(L, p.dob, D.sa_Wo, D.sa_bo, shortcut, D.n1g, D.n1b, "norm1", next_of(D.ca_Wq, D.ca_bq, p.dq, 0));
       }
       if (kv_side && l == 0 && !L.rc && hipStreamWaitEvent(s, h->ev_kv1, 0) != hipSuccess) L.rc = CS_ERR_HIP;
       if (!have_q) L.gemm(gp(p.q_bf, C, D.ca_Wq, C, M, C, C, D.ca_bq, p.dq, C), CS_EPI_BIAS_F16);
       const bool want_w = attn_out && last_l;  // only the last layer's weights are returned (transformer.py:266-268)
       const bool want_use = last_l && use.any();  // reference use: the same layer, the same lse
-      const bool want_fit = last_l && (h->cross_keep || h->layer_keep);  // cross-attention fit: lse for the backward, x1 kept below
+      const bool want_fit = last_l && kept >= FIT_CROSS;  // cross-attention fit: lse for the backward, x1 kept below
       const CsAttnParams a = attn_params(p.dq, C, p.kv + (size_t)l * 2 * C, p.kv + (size_t)l * 2 * C + C, KV, p.dob, p.Np, N * p.Np, c.dec_heads, want_w || want_use || want_fit ? p.lse : nullptr);
       L.attn(a, dec_dh, B);
       if (want_w) L.small("attn_weights", [&] { return cs_attn_weights_launch(&a, dec_dh, B, head_id, attn_out, s); });
       if (want_use) reference_use(L, a, dec_dh);
-      if (want_fit && !L.rc) L.rc = keep_x1(s);
+      if (want_fit && !L.rc) L.rc = keep_rows(kp.x1, p.xq, 4, "cross_keep", s);
       if (!dec_close(L, p.dob, D.ca_Wo, D.ca_bo, shortcut, D.n2g, D.n2b, "norm2", next_of(D.l1W, D.l1b, p.dhid, 1)))
         L.gemm(gp(p.q_bf, C, D.l1W, C, M, C, C, D.l1b, p.dhid, C), CS_EPI_BIAS_RELU_F16);
-      if (last_l && (h->tail_keep || h->cross_keep || h->layer_keep) && !L.rc) L.rc = keep_tail(s);
+      if (last_l && kept >= FIT_TAIL && !L.rc) L.rc = keep_rows(kp.x2, p.xq, 4, "tail_keep", s);
+      if (last_l && kept >= FIT_TAIL && !L.rc) L.rc = keep_rows(kp.H, p.dhid, 2, "tail_keep", s);
       // behind norm3: the head's first linear (its hidden rows replace linear1's in dhid: a workgroup writes exactly the 64 rows it staged into
       // LDS at its start), or -- without self-attention -- the next layer's Q projection
       NextLinear next{};
@@ -926,13 +909,13 @@ int forward_impl(Fwd f) {
   const int rc = f.body();
   if (f.u8) cs_preprocess_tables_hold(0);
   // what cs_head_backward works on: the tokens behind the last norm3 and the head's hidden rows of THIS call (f.p: the plan body() carved)
-  h->last_fwd = cs_model::LastForward{rc == 0, f.mode, f.B, f.H, f.W, f.p.xq, f.p.dhid, f.tail_kept};
-  if (f.cross_kept) {  // (the decoder ran: the plan is carved and the handle has a last layer)
+  h->last_fwd = cs_model::LastForward{rc == 0, f.mode, f.B, f.H, f.W, f.p.xq, f.p.dhid, f.kept};
+  if (f.kept >= FIT_CROSS) {  // (the decoder ran: the plan is carved and the handle has a last layer)
     cs_model::LastForward& lf = h->last_fwd;
     const int C = h->cfg.hidden, L = h->cfg.dec_layers;
-    lf.cross_kept = true; lf.N = f.N; lf.dq = f.p.dq; lf.k = f.p.kv + (size_t)(L - 1) * 2 * C; lf.ldkv = 2 * C * L; lf.dob = f.p.dob; lf.lse = f.p.lse;
+    lf.N = f.N; lf.dq = f.p.dq; lf.k = f.p.kv + (size_t)(L - 1) * 2 * C; lf.ldkv = 2 * C * L; lf.dob = f.p.dob; lf.lse = f.p.lse;
     lf.mem = f.mode == 1 ? f.ref_tokens : f.p.mem_bf;
-    lf.layer_kept = f.layer_kept; lf.dqkv = f.p.dqkv;
+    lf.dqkv = f.p.dqkv;
   }
   h->host_enqueue_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   if (int r = call_leave(h, f.st)) return r;
@@ -1027,262 +1010,6 @@ int cs_forward_select_grouped_u8(cs_handle h, const cs_u8_image* query, const ui
   const U8In u{query, nullptr, mean3, std3};
   const SelectIn s{bank_unit, centre, R, exclude, index_out, sim_out, offsets, G, query_group, blank_row};
   return forward_select(h, nullptr, &u, bank_tokens, s, B, N, H, W, score_out, attn_out, head_id, mean_out, stream);
-}
-
-}  // extern "C"
-
-// ---- fitting on the device: the backward of a fit scope over what the last forward left behind ----
-// The scopes are nested.  FIT_HEAD (f15) is the regression head; the closing launch of the decoder writes the normalised rows in fp32 (p.xq) and,
-// where the head's first linear rides along (rowln.hip), no 16-bit copy, so X is rounded here from p.xq, the rounding the forward's own operand
-// went through.  FIT_TAIL (f16) adds the last layer's feed-forward block and norm3: the last forward must have kept x2 and H (cs_fit_tail_keep).
-// FIT_CROSS (f17) adds that layer's cross-attention and norm2: x1 and lse kept as well (cs_fit_cross_keep).  FIT_LAYER (f18) adds its self-attention
-// and norm1: x0, Os and the self-attention's lse kept as well (cs_fit_layer_keep).  The workspace of a backward is the
-// handle's own allocation (X, then the scope's cs_*_backward_workspace, each of which begins with its parent's), grown like the forward's.
-namespace {
-
-enum FitScope { FIT_HEAD, FIT_TAIL, FIT_CROSS, FIT_LAYER };
-
-int last_rows(const cs_model* h) { return h->last_fwd.B * (h->last_fwd.H / h->cfg.patch) * (h->last_fwd.W / h->cfg.patch); }
-
-const h16_t* kept_H(const cs_model* h, size_t M) {
-  return reinterpret_cast<const h16_t*>(static_cast<const char*>(h->tail_kept) + kept_x2_bytes(M, h->cfg.hidden));
-}
-
-// what a caller of the three backwards can get wrong, refused before fit_inputs allocates or queues the rounding of X (the *_backward_run of
-// ops.hip check again, with the handle's own operands)
-int fit_args_check(const char* op, const cs_model* h, int B, const float* gt, std::initializer_list<const float*> outs, const double* loss,
-                   double inv_count, bool needs_decoder) {
-  if (B <= 0) return fail(CS_ERR_BAD_ARG, "%s: empty batch", op);
-  bool null = !gt || !loss;
-  uintptr_t bits = (uintptr_t)gt;
-  for (const float* o : outs) { null = null || !o; bits |= (uintptr_t)o; }
-  if (null) return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
-  if ((bits & 3) || ((uintptr_t)loss & 7)) return fail(CS_ERR_BAD_ARG, "%s: misaligned pointer (fp32 4 bytes, the loss 8)", op);
-  if (!(inv_count > 0.0)) return fail(CS_ERR_BAD_ARG, "%s: inv_count must be positive", op);
-  if (h && h->cfg.act == 1 && h->cfg.pow_p != 1.0f) return fail(CS_ERR_UNSUPPORTED, "%s: tanh with a power factor other than 1 is not built", op);
-  if (needs_decoder && h && h->finalized && h->dec.empty()) return fail(CS_ERR_STATE, "%s: the handle has no decoder layer", op);
-  return 0;
-}
-
-// the state a fit call of `scope` needs, without touching the handle; B > 0: the shape the caller names is the last forward's
-int fit_state_check(cs_model* h, int B, int H, int W, const char* op, FitScope scope) {
-  if (!h) return fail(CS_ERR_BAD_ARG, "null handle");
-  if (!h->finalized) return fail(CS_ERR_STATE, "%s before cs_finalize", op);
-  const cs_model::LastForward& lf = h->last_fwd;
-  if (!lf.ok || lf.mode < 0) return fail(CS_ERR_STATE, "%s: no successful cs_forward* call on this handle yet", op);
-  if (lf.mode == 2) return fail(CS_ERR_STATE, "%s: the last call on this handle only encoded references", op);
-  if (B > 0 && (lf.B != B || lf.H != H || lf.W != W))
-    return fail(CS_ERR_STATE, "%s: the last forward ran (B %d, H %d, W %d), this call names (%d, %d, %d)", op, lf.B, lf.H, lf.W, B, H, W);
-  const cs_config& c = h->cfg;
-  if (!cs_headfit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden a multiple of 64 and patch 14 (hidden %d, patch %d)", op, c.hidden, c.patch);
-  if (scope >= FIT_TAIL && !cs_tail_fit_supported(c.hidden, c.patch)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden <= 2048 (hidden %d)", op, c.hidden);
-  if (scope >= FIT_CROSS && !cs_cross_fit_supported(c.hidden, c.dec_heads, c.patch))
-    return fail(CS_ERR_UNSUPPORTED, "%s: the attention backward is built for head dims 16, 48 and 96 (hidden %d, %d heads)", op, c.hidden, c.dec_heads);
-  if (scope >= FIT_LAYER && !c.do_self_attn) return fail(CS_ERR_UNSUPPORTED, "%s: the decoder has no self-attention (decoder_do_self_attn = 0): nothing to fit", op);
-  if (scope >= FIT_LAYER && !(lf.layer_kept && lf.cross_kept && lf.tail_kept)) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_layer_keep off", op);
-  if (scope >= FIT_CROSS && !(lf.cross_kept && lf.tail_kept)) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_cross_keep off", op);
-  if (scope >= FIT_TAIL && !lf.tail_kept) return fail(CS_ERR_STATE, "%s: the last forward on this handle ran with cs_fit_tail_keep off", op);
-  return 0;
-}
-
-// the three cs_debug_*_inputs: the caller's row count against the last forward's, where there is one (fit_state_check refuses the rest)
-int debug_rows_check(const cs_model* h, int rows, const char* op) {
-  if (h && h->finalized && h->last_fwd.ok && h->last_fwd.mode != 2 && rows != last_rows(h))
-    return fail(CS_ERR_BAD_ARG, "%s: the last forward left %d rows, the caller names %d", op, last_rows(h), rows);
-  return 0;
-}
-
-// What a backward of `scope` starts from: the last forward's rows M, X (M, C) rounded to 16 bits at the front of the handle's region, and the
-// scope's workspace behind it.  Enters the call (call_enter): the caller leaves it with call_leave.
-struct FitIn { int M = 0; h16_t* X = nullptr; void* ws = nullptr; };
-int fit_inputs(cs_model* h, int B, int H, int W, hipStream_t st, const char* op, FitScope scope, FitIn* in) {
-  if (int r = fit_state_check(h, B, H, W, op, scope)) return r;
-  const cs_model::LastForward& lf = h->last_fwd;
-  const cs_config& c = h->cfg;
-  const int M = last_rows(h), C = c.hidden;
-  const size_t xbytes = cs_fit::up256((size_t)M * C * 2),
-               need = xbytes + (scope == FIT_LAYER ? cs_layer_backward_workspace(lf.B, M / lf.B, lf.N, C, c.dec_heads)
-                                : scope == FIT_CROSS ? cs_cross_backward_workspace(lf.B, M / lf.B, lf.N, C, c.dec_heads)
-                                : scope == FIT_TAIL ? cs_tail_backward_workspace(M, C) : cs_head_backward_workspace(M, C));
-  if (int r = call_enter(h, st)) return r;
-  if (int r = grow_retired(h, &h->hfit_ws, &h->hfit_ws_bytes, need, st)) return r;
-  in->M = M; in->X = static_cast<h16_t*>(h->hfit_ws); in->ws = static_cast<char*>(h->hfit_ws) + xbytes;
-  HIPCHK(cs_pack_f16_launch(lf.xq, M, C, in->X, C, nullptr, nullptr, c.operand_dtype, st));
-  return 0;
-}
-
-CsHeadBackward fill_head_backward(const cs_model* h, const h16_t* X, const float* gt, int B, int H, int W, double inv_count, int accumulate,
-                                  float* dWa, float* dba, float* dWb, float* dbb, double* loss) {
-  const cs_config& c = h->cfg;
-  const int C = c.hidden;
-  CsHeadBackward q{};
-  q.X = X; q.ldx = C; q.A = h->last_fwd.dhid; q.lda = C; q.Wb = h->Wh2; q.ldw = C; q.bb = h->bh2; q.gt = gt; q.B = B; q.gh = H / c.patch; q.gw = W / c.patch;
-  q.P = c.patch; q.C = C; q.act = c.act; q.powp = c.pow_p; q.inv_count = inv_count; q.accumulate = accumulate != 0;
-  q.dWa = dWa; q.dba = dba; q.dWb = dWb; q.dbb = dbb; q.loss = loss;
-  return q;
-}
-
-// (everything but .head)
-CsTailBackward fill_tail_backward(const cs_model* h, int M, float* dW1, float* db1, float* dW2, float* db2, float* dg3, float* db3) {
-  const int C = h->cfg.hidden;
-  const DecLayer& D = h->dec.back();
-  CsTailBackward q{};
-  q.x2 = static_cast<const float*>(h->tail_kept); q.H = kept_H(h, M); q.ldh = C;
-  q.W2 = D.l2W; q.ldw2 = C; q.b2 = D.l2b; q.gamma3 = D.n3g; q.eps = 1e-5f; q.Wa = h->Wh0; q.ldwa = C;
-  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dg3; q.db3 = db3;
-  return q;
-}
-
-// (everything but .tail)
-CsCrossBackward fill_cross_backward(const cs_model* h, float* dWin, float* dbin, float* dWo, float* dbo, float* dgamma2, float* dbeta2) {
-  const cs_config& c = h->cfg;
-  const int C = c.hidden;
-  const DecLayer& D = h->dec.back();
-  const cs_model::LastForward& lf = h->last_fwd;
-  CsCrossBackward x{};
-  x.x1 = static_cast<const float*>(h->cross_kept); x.Qp = lf.dq; x.ldq = C; x.K = lf.k; x.V = lf.k + C; x.ldkv = lf.ldkv; x.O = lf.dob; x.ldo = C;
-  x.lse = lf.lse; x.mem = lf.mem; x.ldm = C; x.W1 = D.l1W; x.ldw1 = C; x.Wo = D.ca_Wo; x.ldwo = C; x.bo = D.ca_bo; x.gamma2 = D.n2g;
-  x.N = lf.N; x.heads = c.dec_heads; x.short_cut = c.do_short_cut != 0;
-  x.dWin = dWin; x.dbin = dbin; x.dWo = dWo; x.dbo = dbo; x.dg2 = dgamma2; x.db2 = dbeta2;
-  return x;
-}
-
-// the pieces of cs_model::layer_kept (keep_x0 / keep_Os write them): x0 (M, C) fp32, Os (M, C) 16 bit, lse_s (B, heads, Np) fp32, each from a 256-byte boundary
-const float* kept_x0(const cs_model* h) { return static_cast<const float*>(h->layer_kept); }
-const h16_t* kept_Os(const cs_model* h, size_t M) {
-  return reinterpret_cast<const h16_t*>(static_cast<const char*>(h->layer_kept) + cs_fit::up256(M * h->cfg.hidden * 4));
-}
-const float* kept_lse_s(const cs_model* h, size_t M) {
-  return reinterpret_cast<const float*>(static_cast<const char*>(h->layer_kept) + cs_fit::up256(M * h->cfg.hidden * 4) + cs_fit::up256(M * h->cfg.hidden * 2));
-}
-
-}  // namespace
-
-extern "C" {
-
-int cs_head_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWa, float* dba, float* dWb,
-                     float* dbb, double* loss, cs_stream stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (int r = fit_args_check("cs_head_backward", h, B, gt, {dWa, dba, dWb, dbb}, loss, inv_count, false)) return r;
-  FitIn in;
-  if (int r = fit_inputs(h, B, H, W, st, "cs_head_backward", FIT_HEAD, &in)) return r;
-  const CsHeadBackward q = fill_head_backward(h, in.X, gt, B, H, W, inv_count, accumulate, dWa, dba, dWb, dbb, loss);
-  const int rc = head_backward_run("cs_head_backward", q, in.ws, h->cfg.operand_dtype, st);
-  const int r = call_leave(h, st);
-  return r ? r : rc;
-}
-
-int cs_debug_head_inputs(cs_handle h, uint16_t* X_out, uint16_t* A_out, int rows, cs_stream stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (int r = debug_rows_check(h, rows, "cs_debug_head_inputs")) return r;
-  FitIn in;
-  if (int r = fit_inputs(h, 0, 0, 0, st, "cs_debug_head_inputs", FIT_HEAD, &in)) return r;
-  const size_t bytes = (size_t)in.M * h->cfg.hidden * 2;
-  if (X_out) HIPCHK(hipMemcpyAsync(X_out, in.X, bytes, hipMemcpyDeviceToDevice, st));
-  if (A_out) HIPCHK(hipMemcpyAsync(A_out, h->last_fwd.dhid, bytes, hipMemcpyDeviceToDevice, st));
-  return call_leave(h, st);
-}
-
-int cs_tail_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dW1, float* db1, float* dW2,
-                     float* db2, float* dg3, float* db3, float* dWa, float* dba, float* dWb, float* dbb, double* loss, cs_stream stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (int r = fit_args_check("cs_tail_backward", h, B, gt, {dW1, db1, dW2, db2, dg3, db3, dWa, dba, dWb, dbb}, loss, inv_count, true)) return r;
-  FitIn in;
-  if (int r = fit_inputs(h, B, H, W, st, "cs_tail_backward", FIT_TAIL, &in)) return r;
-  CsTailBackward q = fill_tail_backward(h, in.M, dW1, db1, dW2, db2, dg3, db3);
-  q.head = fill_head_backward(h, in.X, gt, B, H, W, inv_count, accumulate, dWa, dba, dWb, dbb, loss);
-  const int rc = tail_backward_run("cs_tail_backward", q, in.ws, h->cfg.operand_dtype, st);
-  const int r = call_leave(h, st);
-  return r ? r : rc;
-}
-
-int cs_debug_tail_inputs(cs_handle h, float* x2_out, uint16_t* H_out, int rows, cs_stream stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (int r = debug_rows_check(h, rows, "cs_debug_tail_inputs")) return r;
-  FitIn in;
-  if (int r = fit_inputs(h, 0, 0, 0, st, "cs_debug_tail_inputs", FIT_TAIL, &in)) return r;
-  const size_t n = (size_t)in.M * h->cfg.hidden;
-  if (x2_out) HIPCHK(hipMemcpyAsync(x2_out, h->tail_kept, n * 4, hipMemcpyDeviceToDevice, st));
-  if (H_out) HIPCHK(hipMemcpyAsync(H_out, kept_H(h, in.M), n * 2, hipMemcpyDeviceToDevice, st));
-  return call_leave(h, st);
-}
-
-int cs_cross_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWin, float* dbin, float* dWo,
-                      float* dbo, float* dgamma2, float* dbeta2, float* dW1, float* db1, float* dW2, float* db2, float* dg3, float* db3, float* dWa,
-                      float* dba, float* dWb, float* dbb, double* loss, cs_stream stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (int r = fit_args_check("cs_cross_backward", h, B, gt, {dWin, dbin, dWo, dbo, dgamma2, dbeta2, dW1, db1, dW2, db2, dg3, db3, dWa, dba, dWb, dbb},
-                             loss, inv_count, true))
-    return r;
-  FitIn in;
-  if (int r = fit_inputs(h, B, H, W, st, "cs_cross_backward", FIT_CROSS, &in)) return r;
-  CsCrossBackward x = fill_cross_backward(h, dWin, dbin, dWo, dbo, dgamma2, dbeta2);
-  x.tail = fill_tail_backward(h, in.M, dW1, db1, dW2, db2, dg3, db3);
-  x.tail.head = fill_head_backward(h, in.X, gt, B, H, W, inv_count, accumulate, dWa, dba, dWb, dbb, loss);
-  const int rc = cross_backward_run("cs_cross_backward", x, in.ws, h->cfg.operand_dtype, st);
-  const int r = call_leave(h, st);
-  return r ? r : rc;
-}
-
-int cs_debug_cross_inputs(cs_handle h, float* x1_out, uint16_t* q_out, uint16_t* o_out, float* lse_out, uint16_t* k_out, uint16_t* v_out, int rows,
-                          cs_stream stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (int r = debug_rows_check(h, rows, "cs_debug_cross_inputs")) return r;
-  // (the state checks alone: six copies need neither X nor the backward's workspace, which fit_inputs would grow the handle's region to)
-  if (int r = fit_state_check(h, 0, 0, 0, "cs_debug_cross_inputs", FIT_CROSS)) return r;
-  if (int r = call_enter(h, st)) return r;
-  const cs_model::LastForward& lf = h->last_fwd;
-  const size_t M = last_rows(h), C = h->cfg.hidden, n = M * C, Mk = M * lf.N;
-  if (x1_out) HIPCHK(hipMemcpyAsync(x1_out, h->cross_kept, n * 4, hipMemcpyDeviceToDevice, st));
-  if (q_out) HIPCHK(hipMemcpyAsync(q_out, lf.dq, n * 2, hipMemcpyDeviceToDevice, st));
-  if (o_out) HIPCHK(hipMemcpyAsync(o_out, lf.dob, n * 2, hipMemcpyDeviceToDevice, st));
-  if (lse_out) HIPCHK(hipMemcpyAsync(lse_out, lf.lse, M * h->cfg.dec_heads * 4, hipMemcpyDeviceToDevice, st));
-  if (k_out) HIPCHK(hipMemcpy2DAsync(k_out, C * 2, lf.k, (size_t)lf.ldkv * 2, C * 2, Mk, hipMemcpyDeviceToDevice, st));
-  if (v_out) HIPCHK(hipMemcpy2DAsync(v_out, C * 2, lf.k + C, (size_t)lf.ldkv * 2, C * 2, Mk, hipMemcpyDeviceToDevice, st));
-  return call_leave(h, st);
-}
-
-int cs_layer_backward(cs_handle h, const float* gt, int B, int H, int W, double inv_count, int accumulate, float* dWin_s, float* dbin_s, float* dWo_s,
-                      float* dbo_s, float* dgamma1, float* dbeta1, float* dWin, float* dbin, float* dWo, float* dbo, float* dgamma2, float* dbeta2,
-                      float* dW1, float* db1, float* dW2, float* db2, float* dg3, float* db3, float* dWa, float* dba, float* dWb, float* dbb, double* loss,
-                      cs_stream stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (int r = fit_args_check("cs_layer_backward", h, B, gt, {dWin_s, dbin_s, dWo_s, dbo_s, dgamma1, dbeta1, dWin, dbin, dWo, dbo, dgamma2, dbeta2, dW1, db1,
-                                                             dW2, db2, dg3, db3, dWa, dba, dWb, dbb},
-                             loss, inv_count, true))
-    return r;
-  FitIn in;
-  if (int r = fit_inputs(h, B, H, W, st, "cs_layer_backward", FIT_LAYER, &in)) return r;
-  const int C = h->cfg.hidden;
-  const DecLayer& D = h->dec.back();
-  const cs_model::LastForward& lf = h->last_fwd;
-  CsLayerBackward y{};
-  y.x0 = kept_x0(h); y.Qs = lf.dqkv; y.Ks = lf.dqkv + C; y.Vs = lf.dqkv + 2 * C; y.ldqkv = 3 * C; y.Os = kept_Os(h, in.M); y.ldos = C;
-  y.lse_s = kept_lse_s(h, in.M); y.Wq = D.ca_Wq; y.ldwq = C; y.Wo_s = D.sa_Wo; y.ldwos = C; y.bo_s = D.sa_bo; y.gamma1 = D.n1g;
-  y.dWin_s = dWin_s; y.dbin_s = dbin_s; y.dWo_s = dWo_s; y.dbo_s = dbo_s; y.dg1 = dgamma1; y.db1 = dbeta1;
-  y.cross = fill_cross_backward(h, dWin, dbin, dWo, dbo, dgamma2, dbeta2);
-  y.cross.tail = fill_tail_backward(h, in.M, dW1, db1, dW2, db2, dg3, db3);
-  y.cross.tail.head = fill_head_backward(h, in.X, gt, B, H, W, inv_count, accumulate, dWa, dba, dWb, dbb, loss);
-  const int rc = layer_backward_run("cs_layer_backward", y, in.ws, h->cfg.operand_dtype, st);
-  const int r = call_leave(h, st);
-  return r ? r : rc;
-}
-
-int cs_debug_layer_inputs(cs_handle h, float* x0_out, uint16_t* q_out, uint16_t* k_out, uint16_t* v_out, uint16_t* o_out, float* lse_out, int rows,
-                          cs_stream stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (int r = debug_rows_check(h, rows, "cs_debug_layer_inputs")) return r;
-  if (int r = fit_state_check(h, 0, 0, 0, "cs_debug_layer_inputs", FIT_LAYER)) return r;  // (the state checks alone, as cs_debug_cross_inputs)
-  if (int r = call_enter(h, st)) return r;
-  const cs_model::LastForward& lf = h->last_fwd;
-  const size_t M = last_rows(h), C = h->cfg.hidden, n = M * C;
-  if (x0_out) HIPCHK(hipMemcpyAsync(x0_out, kept_x0(h), n * 4, hipMemcpyDeviceToDevice, st));
-  uint16_t* const outs[3] = {q_out, k_out, v_out};
-  for (int j = 0; j < 3; ++j)
-    if (outs[j]) HIPCHK(hipMemcpy2DAsync(outs[j], C * 2, lf.dqkv + j * C, 3 * C * 2, C * 2, M, hipMemcpyDeviceToDevice, st));
-  if (o_out) HIPCHK(hipMemcpyAsync(o_out, kept_Os(h, M), n * 2, hipMemcpyDeviceToDevice, st));
-  if (lse_out) HIPCHK(hipMemcpyAsync(lse_out, kept_lse_s(h, M), M * h->cfg.dec_heads * 4, hipMemcpyDeviceToDevice, st));
-  return call_leave(h, st);
 }
 
 int cs_u8_input_supported(cs_handle h, const cs_u8_image* im, int H, int W) {

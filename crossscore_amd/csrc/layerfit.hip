@@ -11,8 +11,6 @@
 // The gradient stops at x0.  Every sum has a fixed order; nothing is accumulated with atomics.
 #include "fit_shared.h"
 
-#include <cmath>
-
 namespace {
 
 using namespace cs_fit;
@@ -49,68 +47,39 @@ extern "C" {
 size_t cs_layer_backward_workspace(int B, int Np, int N, int C, int heads) { return cs_fit::layer_carve(nullptr, B, Np, N, C, heads).end; }
 
 // The self-attention backward of one layer backward, as the launch below queues it: Q', K and V in place in their packed rows, every batch item
-// attending to its own Np keys, dQu_s | dKu_s | dV_s side by side.  layer_backward_run (ops.hip) builds it too and puts it through
+// attending to its own Np keys, dQu_s | dKu_s | dV_s side by side.  layer_backward_run (fit_host.hip) builds it too and puts it through
 // cs_attnbwd_check with every other check, before the first launch.
 void cs_layer_backward_attn_params(const CsLayerBackward* q, void* ws, int bf, CsAttnBwdParams* out) {
   const CsHeadBackward& hq = q->cross.tail.head;
   const int B = hq.B, Np = hq.gh * hq.gw, C = hq.C;
   const LayerWs k = layer_carve(q, ws);
-  CsAttnBwdParams a{};
-  a.Q = q->Qs; a.K = q->Ks; a.V = q->Vs; a.O = q->Os; a.dO = k.dOsh; a.lse = q->lse_s;
-  a.ldq = q->ldqkv; a.ldk = q->ldqkv; a.ldv = q->ldqkv; a.ldo = q->ldos; a.lddo = C;
-  a.q_bs = (long long)Np * q->ldqkv; a.k_bs = a.q_bs; a.v_bs = a.q_bs; a.o_bs = (long long)Np * q->ldos; a.do_bs = (long long)Np * C;
-  a.nbatch = B; a.heads = q->cross.heads; a.Lq = Np; a.Lk = Np; a.scale_log2e = 1.0f;
-  a.dQ = k.dQKV; a.dK = k.dQKV + C; a.dV = k.dQKV + 2 * C;
-  a.lddq = a.lddk = a.lddv = 3 * C;
-  a.dq_bs = a.dk_bs = a.dv_bs = (long long)Np * 3 * C;
-  a.D = static_cast<float*>(k.aws); a.bf16 = bf;
-  *out = a;
+  *out = attn_bwd_params(q->Qs, q->ldqkv, q->Ks, q->Vs, q->ldqkv, q->Os, q->ldos, q->lse_s, k.dOsh, B, q->cross.heads, Np, Np, C, k.dQKV, 3 * C,
+                         k.dQKV + C, k.dQKV + 2 * C, 3 * C, k.aws, bf);
 }
 
 hipError_t cs_layer_backward_launch(const CsLayerBackward* q, void* ws, int bf, hipStream_t st) {
   const CsCrossBackward& x = q->cross;
   const CsHeadBackward& hq = x.tail.head;
-  const int B = hq.B, Np = hq.gh * hq.gw, M = B * Np, C = hq.C, dh = C / x.heads;
-  const size_t mc = (size_t)M * C;
+  const int M = hq.B * hq.gh * hq.gw, C = hq.C;
   const LayerWs k = layer_carve(q, ws);
   const float scale = (float)hq.inv_count;
   hipError_t e = cs_cross_backward_launch(&x, ws, bf, st);  // the sixteen gradients of the three inner scopes, the loss; dy2h and dQu stay in the workspace
   if (e != hipSuccess) return e;
   if ((e = hipMemsetAsync(k.zb, 0, (size_t)C * 4, st)) != hipSuccess) return e;
   // dx1 = (short cut ? f32(dy2h) : 0) + ln2 dQu Wq'
-  if ((e = cs_transpose16_launch(q->Wq, q->ldwq, C, C, k.WT, C, st)) != hipSuccess) return e;
-  if ((e = gemm_go(gemm_params(k.dQu, C, k.WT, C, M, C, k.zb, k.dx1, bf), CS_EPI_RESID_F32, st)) != hipSuccess) return e;
-  const long long n8 = (long long)(mc / 8);
+  if ((e = through_weight(k.dQu, q->Wq, q->ldwq, M, C, k.WT, k.zb, nullptr, k.dx1, CS_EPI_RESID_F32, bf, st)) != hipSuccess) return e;
+  const long long n8 = (long long)((size_t)M * C / 8);
   dx1_close_kernel<<<(unsigned)((n8 + 255) / 256), 256, 0, st>>>(k.dx1, x.short_cut ? k.dy2h : nullptr, n8, bf);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  // y1 = (short cut ? x0 : 0) + Os Wo_s^T + bo_s
-  CsGemmParams gy = gemm_params(q->Os, q->ldos, q->Wo_s, q->ldwos, M, C, q->bo_s, k.y1, bf);
-  gy.resid = x.short_cut ? q->x0 : nullptr; gy.ldr = C;
-  if ((e = gemm_go(gy, CS_EPI_RESID_F32, st)) != hipSuccess) return e;
-  CsLnBackward ln{};
-  ln.y = k.y1; ln.ldy = C; ln.dx = k.dx1; ln.ldx = C; ln.gamma = q->gamma1; ln.eps = x.tail.eps; ln.M = M; ln.C = C; ln.scale = scale; ln.accumulate = hq.accumulate;
-  ln.dyh = k.dy1h; ln.ldd = C; ln.dgamma = q->dg1; ln.dbeta = q->db1;
-  if ((e = cs_ln_backward_launch(&ln, k.lws, bf, st)) != hipSuccess) return e;
-  // dWo_s, dbo_s
-  CsGemmTn t{};
-  t.G = k.dy1h; t.ldg = C; t.X = q->Os; t.ldx = q->ldos; t.M = M; t.N = C; t.K = C; t.scale = scale; t.accumulate = hq.accumulate;
-  t.out = q->dWo_s; t.ldo = C; t.colsum = q->dbo_s;
-  if ((e = cs_gemm_tn_launch(&t, k.tws, bf, st)) != hipSuccess) return e;
-  // dOsh = dy1h Wo_s
-  if ((e = cs_transpose16_launch(q->Wo_s, q->ldwos, C, C, k.WT, C, st)) != hipSuccess) return e;  // (stream order: dx1's GEMM has read WT)
-  if ((e = gemm_go(gemm_params(k.dy1h, C, k.WT, C, M, C, k.zb, k.dOsh, bf), CS_EPI_BIAS_F16, st)) != hipSuccess) return e;
-  // the attention backward (its parameters: cs_layer_backward_attn_params above; checked by the caller with everything else)
+  // y1 = (short cut ? x0 : 0) + Os Wo_s^T + bo_s and norm1: dg1, db1, dy1h; dWo_s, dbo_s; dOsh = dy1h Wo_s
+  const Closing c{q->Os, q->ldos, q->Wo_s, q->ldwos, q->bo_s, x.short_cut ? q->x0 : nullptr, q->gamma1, x.tail.eps};
+  if ((e = closing_backward(c, k.dx1, {k.y1, k.dy1h, k.WT, k.zb, k.lws, k.tws}, {q->dWo_s, q->dbo_s, q->dg1, q->db1, k.dOsh}, M, C, scale, hq.accumulate,
+                            bf, st)) != hipSuccess)
+    return e;
+  // the self-attention backward (its parameters: cs_layer_backward_attn_params above) and in_proj: all three blocks against x0h, the one rounding of x0
   CsAttnBwdParams a{};
   cs_layer_backward_attn_params(q, ws, bf, &a);
-  if ((e = cs_attnbwd_launch(&a, dh, st)) != hipSuccess) return e;
-  // in_proj: all three blocks reduce against x0h, the one rounding of x0; the scalars ride in the reductions' fp32 scale as in crossfit.hip
-  if ((e = cs_pack_f16_launch(q->x0, M, C, k.x0h, C, nullptr, nullptr, bf, st)) != hipSuccess) return e;
-  t.G = k.dQKV; t.ldg = 3 * C; t.X = k.x0h; t.ldx = C; t.scale = scale * (1.0f / std::sqrt((float)dh)); t.out = q->dWin_s; t.colsum = q->dbin_s;
-  if ((e = cs_gemm_tn_launch(&t, k.tws, bf, st)) != hipSuccess) return e;
-  t.G = k.dQKV + C; t.scale = scale * kLn2; t.out = q->dWin_s + (size_t)C * C; t.colsum = q->dbin_s + C;
-  if ((e = cs_gemm_tn_launch(&t, k.tws, bf, st)) != hipSuccess) return e;
-  t.G = k.dQKV + 2 * C; t.scale = scale; t.out = q->dWin_s + (size_t)2 * C * C; t.colsum = q->dbin_s + 2 * C;
-  return cs_gemm_tn_launch(&t, k.tws, bf, st);
+  return attn_block_backward(a, q->x0, k.x0h, M, C, k.x0h, C, M, scale, hq.accumulate, q->dWin_s, q->dbin_s, k.tws, bf, st);
 }
 
 }

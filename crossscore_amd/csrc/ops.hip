@@ -716,355 +716,4 @@ int cs_op_select_references_grouped(const float* q_mean, int B, const int32_t* q
   return stage_done(sl, st);
 }
 
-// ---- head fit (headfit.hip): checks first, then the launches ----
-int cs_head_fit_supported(int hidden, int patch) { return cs_headfit_supported(hidden, patch); }
-int cs_head_fit_row_tile(void) { return CS_HEADFIT_ROW_TILE; }
-int cs_head_fit_row_chunk(void) { return CS_HEADFIT_ROW_CHUNK; }
-int cs_head_fit_g_columns(void) { return CS_HEADFIT_NPAD; }
-
-size_t cs_head_backward_workspace_bytes(int M, int C, int P) {
-  if (M <= 0 || !cs_headfit_supported(C, P)) return 0;
-  return cs_head_backward_workspace(M, C);
-}
-
-size_t cs_gemm_tn_workspace_bytes(int M, int N, int K) {
-  if (M <= 0 || N <= 0 || K <= 0) return 0;
-  return cs_gemm_tn_workspace(M, N, K);
-}
-
-static bool misaligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
-// what every head-fit entry asks of the head's shape and of the 16-bit operands A (M, C) and Wb (P P, C)
-static int head_fit_shape_check(const char* op, const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B,
-                                int gh, int gw, int P, int C, int act, float powp, const void* ws) {
-  if (!A || !Wb || !bb || !gt || !ws) return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
-  if (B <= 0 || gh <= 0 || gw <= 0) return fail(CS_ERR_BAD_ARG, "%s: empty batch or patch grid", op);
-  if (!cs_headfit_supported(C, P)) return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden a multiple of 64 in [64, 4096] and patch 14 (hidden %d, patch %d)", op, C, P);
-  if (act != 0 && act != 1) return fail(CS_ERR_BAD_ARG, "%s: act must be 0 (sigmoid) or 1 (tanh)", op);
-  if (!(powp > 0.f)) return fail(CS_ERR_BAD_ARG, "%s: power factor must be positive", op);
-  // (the reference forces p = 1 with tanh, regression_layer.py:48-56: a power of a negative base has no gradient worth defining)
-  if (act == 1 && powp != 1.0f) return fail(CS_ERR_UNSUPPORTED, "%s: tanh with a power factor other than 1 is not built", op);
-  if ((long long)B * gh * gw > (1ll << 22)) return fail(CS_ERR_UNSUPPORTED, "%s: more than 2^22 token rows; split the batch", op);
-  if (lda < C || ldw < C || lda % 8 || ldw % 8) return fail(CS_ERR_BAD_ARG, "%s: row strides must be multiples of 8 elements and at least C", op);
-  if (misaligned(A, 16) || misaligned(Wb, 16) || misaligned(bb, 4) || misaligned(gt, 4) || misaligned(ws, 256))
-    return fail(CS_ERR_BAD_ARG, "%s: misaligned pointer (16-bit operands 16 bytes, fp32 4, workspace 256)", op);
-  return 0;
-}
-
-static int head_grad_z_op(const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P, int C,
-                          int act, float powp, uint16_t* g, int ldg, double* loss_sum, float* colsum_part, float* s_tap, void* ws, cs_stream stream) {
-  if (int r = head_fit_shape_check("head_grad_z", A, lda, Wb, ldw, bb, gt, B, gh, gw, P, C, act, powp, ws)) return r;
-  if (!g || !loss_sum) return fail(CS_ERR_BAD_ARG, "head_grad_z: null pointer");
-  if (ldg < CS_HEADFIT_NPAD || ldg % 8 || misaligned(g, 16) || misaligned(loss_sum, 8) || misaligned(colsum_part, 4))
-    return fail(CS_ERR_BAD_ARG, "head_grad_z: g needs rows of at least %d elements, a multiple of 8 apart, 16-byte aligned; the loss 8-byte aligned", CS_HEADFIT_NPAD);
-  CsHeadGradZ z{};
-  z.A = A; z.lda = lda; z.Wb = Wb; z.ldw = ldw; z.bb = bb; z.gt = gt; z.B = B; z.gh = gh; z.gw = gw; z.P = P; z.C = C; z.act = act; z.powp = powp;
-  z.g = g; z.ldg = ldg; z.loss = loss_sum; z.loss_scale = 1.0; z.loss_accumulate = 1; z.colsum_part = colsum_part; z.s_tap = s_tap;
-  HIPCHK(cs_head_grad_z_launch(&z, ws, g_op_bf16, (hipStream_t)stream));
-  return 0;
-}
-
-int cs_op_head_grad_z(const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P, int C,
-                      int act, float powp, uint16_t* g, int ldg, double* loss_sum, float* colsum_part, void* ws, cs_stream stream) {
-  return head_grad_z_op(A, lda, Wb, ldw, bb, gt, B, gh, gw, P, C, act, powp, g, ldg, loss_sum, colsum_part, nullptr, ws, stream);
-}
-
-// tests: the same call with s (M, P P) fp32 as the epilogue formed it
-int cs_debug_op_head_grad_z_tap(const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P,
-                                int C, int act, float powp, uint16_t* g, int ldg, double* loss_sum, float* colsum_part, float* s_out, void* ws,
-                                cs_stream stream) {
-  if (!s_out || misaligned(s_out, 4)) return fail(CS_ERR_BAD_ARG, "head_grad_z tap: s_out missing or misaligned");
-  return head_grad_z_op(A, lda, Wb, ldw, bb, gt, B, gh, gw, P, C, act, powp, g, ldg, loss_sum, colsum_part, s_out, ws, stream);
-}
-
-int cs_op_gemm_tn(const uint16_t* G, int ldg, const uint16_t* X, int ldx, int M, int N, int K, float scale, int accumulate, float* out, int ldo,
-                  float* colsum, void* ws, cs_stream stream) {
-  if (!G || !X || !out || !ws) return fail(CS_ERR_BAD_ARG, "gemm_tn: null pointer");
-  if (M <= 0 || N <= 0 || K <= 0) return fail(CS_ERR_BAD_ARG, "gemm_tn: empty shape");
-  if (K % 8 || N > 65535 * 64 || (long long)M > (1ll << 22) || (long long)N * K >= (1ll << 31))
-    return fail(CS_ERR_UNSUPPORTED, "gemm_tn: K must be a multiple of 8, M <= 2^22, N K < 2^31 (M %d, N %d, K %d)", M, N, K);
-  if (ldg < N || ldx < K || ldo < K || ldg % 8 || ldx % 8) return fail(CS_ERR_BAD_ARG, "gemm_tn: row strides must cover the rows; those of G and X must be multiples of 8 elements");
-  if (misaligned(G, 16) || misaligned(X, 16) || misaligned(out, 4) || misaligned(colsum, 4) || misaligned(ws, 256))
-    return fail(CS_ERR_BAD_ARG, "gemm_tn: misaligned pointer (16-bit operands 16 bytes, fp32 4, workspace 256)");
-  CsGemmTn t{};
-  t.G = G; t.ldg = ldg; t.X = X; t.ldx = ldx; t.M = M; t.N = N; t.K = K; t.scale = scale; t.accumulate = accumulate != 0; t.out = out; t.ldo = ldo;
-  t.colsum = colsum;
-  HIPCHK(cs_gemm_tn_launch(&t, ws, g_op_bf16, (hipStream_t)stream));
-  return 0;
-}
-
-}  // extern "C"
-
-// cs_op_head_backward and cs_head_backward (forward.hip) come through here
-int cs_host::head_backward_run(const char* op, const CsHeadBackward& q, void* ws, int bf, hipStream_t st) {
-  if (int r = head_fit_shape_check(op, q.A, q.lda, q.Wb, q.ldw, q.bb, q.gt, q.B, q.gh, q.gw, q.P, q.C, q.act, q.powp, ws)) return r;
-  if (!q.X || !q.dWa || !q.dba || !q.dWb || !q.dbb || !q.loss) return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
-  if (q.ldx < q.C || q.ldx % 8 || misaligned(q.X, 16)) return fail(CS_ERR_BAD_ARG, "%s: X needs 16-byte aligned rows a multiple of 8 elements apart", op);
-  if (misaligned(q.dWa, 4) || misaligned(q.dba, 4) || misaligned(q.dWb, 4) || misaligned(q.dbb, 4) || misaligned(q.loss, 8))
-    return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
-  if (!(q.inv_count > 0.0)) return fail(CS_ERR_BAD_ARG, "%s: inv_count must be positive", op);
-  HIPCHK(cs_head_backward_launch(&q, ws, bf, st));
-  return 0;
-}
-
-extern "C" {
-
-int cs_op_head_backward(const uint16_t* X, int ldx, const uint16_t* A, int lda, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B,
-                        int gh, int gw, int P, int C, int act, float powp, double inv_count, int accumulate, float* dWa, float* dba, float* dWb,
-                        float* dbb, double* loss, void* ws, cs_stream stream) {
-  CsHeadBackward q{};
-  q.X = X; q.ldx = ldx; q.A = A; q.lda = lda; q.Wb = Wb; q.ldw = ldw; q.bb = bb; q.gt = gt; q.B = B; q.gh = gh; q.gw = gw; q.P = P; q.C = C;
-  q.act = act; q.powp = powp; q.inv_count = inv_count; q.accumulate = accumulate != 0; q.dWa = dWa; q.dba = dba; q.dWb = dWb; q.dbb = dbb; q.loss = loss;
-  return head_backward_run("head_backward", q, ws, g_op_bf16, (hipStream_t)stream);
-}
-
-// ---- tail fit (tailfit.hip) ----
-// (the head's condition, inside the widths layernorm_kernel -- and with it the forward's decoder -- takes)
-int cs_tail_fit_supported(int hidden, int patch) { return cs_headfit_supported(hidden, patch) && hidden <= 2048; }
-int cs_tail_fit_ln_row_tile(void) { return CS_TAILFIT_LN_ROW_TILE; }
-
-size_t cs_ln_backward_workspace_bytes(int M, int C) {
-  if (M <= 0 || C < 64 || C % 64 || C > 2048) return 0;
-  return cs_ln_backward_workspace(M, C);
-}
-
-size_t cs_tail_backward_workspace_bytes(int M, int C, int P) {
-  if (M <= 0 || !cs_tail_fit_supported(C, P)) return 0;
-  return cs_tail_backward_workspace(M, C);
-}
-
-int cs_op_ln_backward(const float* y, int ldy, const float* dx, int ldx, const float* gamma, int M, int C, float eps, int bf16, float inv_count,
-                      int accumulate, uint16_t* dyh, int ldd, float* dgamma, float* dbeta, void* ws, cs_stream stream) {
-  if (!y || !dx || !gamma || !dyh || !dgamma || !dbeta || !ws) return fail(CS_ERR_BAD_ARG, "ln_backward: null pointer");
-  if (M <= 0) return fail(CS_ERR_BAD_ARG, "ln_backward: empty shape");
-  if (C < 64 || C % 64 || C > 2048 || M > (1 << 22)) return fail(CS_ERR_UNSUPPORTED, "ln_backward: built for C a multiple of 64 in [64, 2048] and M <= 2^22 (M %d, C %d)", M, C);
-  if (ldy < C || ldx < C || ldd < C || ldy % 4 || ldx % 4 || ldd % 4) return fail(CS_ERR_BAD_ARG, "ln_backward: row strides must be multiples of 4 elements and at least C");
-  if (!(eps >= 0.f) || !(inv_count > 0.f)) return fail(CS_ERR_BAD_ARG, "ln_backward: eps must be >= 0 and inv_count positive");
-  if (bf16 != 0 && bf16 != 1) return fail(CS_ERR_BAD_ARG, "ln_backward: bf16 must be 0 or 1");
-  if (misaligned(y, 16) || misaligned(dx, 16) || misaligned(gamma, 16) || misaligned(dyh, 8) || misaligned(dgamma, 4) || misaligned(dbeta, 4) || misaligned(ws, 256))
-    return fail(CS_ERR_BAD_ARG, "ln_backward: misaligned pointer (fp32 rows and gamma 16 bytes, dyh 8, the sums 4, workspace 256)");
-  CsLnBackward p{};
-  p.y = y; p.ldy = ldy; p.dx = dx; p.ldx = ldx; p.gamma = gamma; p.eps = eps; p.M = M; p.C = C; p.scale = inv_count; p.accumulate = accumulate != 0;
-  p.dyh = dyh; p.ldd = ldd; p.dgamma = dgamma; p.dbeta = dbeta;
-  HIPCHK(cs_ln_backward_launch(&p, ws, bf16, (hipStream_t)stream));
-  return 0;
-}
-
-}  // extern "C"
-
-// every check of the head's and the tail's backward (cs_op_tail_backward, cs_tail_backward and the cross-attention fit's come through here)
-static int tail_backward_check(const char* op, const CsTailBackward& q, void* ws) {
-  const CsHeadBackward& hq = q.head;
-  if (int r = head_fit_shape_check(op, hq.A, hq.lda, hq.Wb, hq.ldw, hq.bb, hq.gt, hq.B, hq.gh, hq.gw, hq.P, hq.C, hq.act, hq.powp, ws)) return r;
-  const int C = hq.C;
-  if (!cs_tail_fit_supported(C, hq.P) || (long long)hq.B * hq.gh * hq.gw * C >= (1ll << 31))
-    return fail(CS_ERR_UNSUPPORTED, "%s: built for hidden <= 2048 and fewer than 2^31 token elements; split the batch", op);
-  if (!hq.X || !hq.dWa || !hq.dba || !hq.dWb || !hq.dbb || !hq.loss || !q.x2 || !q.H || !q.W2 || !q.b2 || !q.gamma3 || !q.Wa || !q.dW1 || !q.db1 ||
-      !q.dW2 || !q.db2 || !q.dg3 || !q.db3)
-    return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
-  for (int ld : {hq.ldx, q.ldh, q.ldw2, q.ldwa})
-    if (ld < C || ld % 8) return fail(CS_ERR_BAD_ARG, "%s: row strides must be multiples of 8 elements and at least C", op);
-  if (misaligned(hq.X, 16) || misaligned(q.x2, 16) || misaligned(q.H, 16) || misaligned(q.W2, 16) || misaligned(q.Wa, 16) || misaligned(q.b2, 16) || misaligned(q.gamma3, 16))
-    return fail(CS_ERR_BAD_ARG, "%s: misaligned input (16-bit operands, x2, b2 and gamma 16 bytes)", op);
-  for (const float* o : {hq.dWa, hq.dba, hq.dWb, hq.dbb, q.dW1, q.db1, q.dW2, q.db2, q.dg3, q.db3})
-    if (misaligned(o, 4)) return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
-  if (misaligned(hq.loss, 8)) return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
-  if (!(hq.inv_count > 0.0) || !(q.eps >= 0.f)) return fail(CS_ERR_BAD_ARG, "%s: inv_count must be positive and eps >= 0", op);
-  return 0;
-}
-
-// cs_op_tail_backward and cs_tail_backward (forward.hip) come through here: every check of both backwards first, then the launches
-int cs_host::tail_backward_run(const char* op, const CsTailBackward& q, void* ws, int bf, hipStream_t st) {
-  if (int r = tail_backward_check(op, q, ws)) return r;
-  HIPCHK(cs_tail_backward_launch(&q, ws, bf, st));
-  return 0;
-}
-
-// every check of the cross-attention fit's backward: the tail's, then the block's own (its attention backward's parameters included)
-static int cross_backward_check(const char* op, const CsCrossBackward& q, void* ws, int bf) {
-  if (int r = tail_backward_check(op, q.tail, ws)) return r;
-  const CsHeadBackward& hq = q.tail.head;
-  const int C = hq.C;
-  if (q.heads <= 0 || C % q.heads || !cs_attnbwd_supported(C / q.heads))
-    return fail(CS_ERR_UNSUPPORTED, "%s: the attention backward is built for head dims 16, 48 and 96 (hidden %d, %d heads)", op, C, q.heads);
-  if (q.N <= 0) return fail(CS_ERR_BAD_ARG, "%s: N must be positive", op);
-  const long long Mk = (long long)hq.B * hq.gh * hq.gw * q.N;
-  if (Mk * 2 * C >= (1ll << 31)) return fail(CS_ERR_UNSUPPORTED, "%s: built for fewer than 2^31 K | V elements; split the batch", op);
-  if (!q.x1 || !q.Qp || !q.K || !q.V || !q.O || !q.lse || !q.mem || !q.W1 || !q.Wo || !q.bo || !q.gamma2 || !q.dWin || !q.dbin || !q.dWo || !q.dbo ||
-      !q.dg2 || !q.db2)
-    return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
-  for (int ld : {q.ldq, q.ldo, q.ldm, q.ldw1, q.ldwo})
-    if (ld < C || ld % 8) return fail(CS_ERR_BAD_ARG, "%s: row strides must be multiples of 8 elements and at least C", op);
-  if (q.ldkv < C || q.ldkv % 8 || (long long)hq.gh * hq.gw * q.N * q.ldkv >= (1ll << 30))
-    return fail(CS_ERR_BAD_ARG, "%s: the K | V row stride must be a multiple of 8 elements, at least C, and N Np times it below 2^30", op);
-  if (misaligned(q.x1, 16) || misaligned(q.Qp, 16) || misaligned(q.K, 16) || misaligned(q.V, 16) || misaligned(q.O, 16) || misaligned(q.mem, 16) ||
-      misaligned(q.W1, 16) || misaligned(q.Wo, 16) || misaligned(q.bo, 16) || misaligned(q.gamma2, 16) || misaligned(q.lse, 4))
-    return fail(CS_ERR_BAD_ARG, "%s: misaligned input (16-bit operands, x1, bo and gamma 16 bytes, lse 4)", op);
-  for (const float* o : {q.dWin, q.dbin, q.dWo, q.dbo, q.dg2, q.db2})
-    if (misaligned(o, 4)) return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
-  CsAttnBwdParams a{};
-  cs_cross_backward_attn_params(&q, ws, bf, &a);
-  if (const char* e = cs_attnbwd_check(&a)) return fail(CS_ERR_BAD_ARG, "%s: %s", op, e);
-  return 0;
-}
-
-// cs_op_cross_backward and cs_cross_backward (forward.hip): every check first, then the launches
-int cs_host::cross_backward_run(const char* op, const CsCrossBackward& q, void* ws, int bf, hipStream_t st) {
-  if (int r = cross_backward_check(op, q, ws, bf)) return r;
-  HIPCHK(cs_cross_backward_launch(&q, ws, bf, st));
-  return 0;
-}
-
-// cs_op_layer_backward and cs_layer_backward (forward.hip): the cross-attention fit's checks, the self-attention block's own, then the launches
-int cs_host::layer_backward_run(const char* op, const CsLayerBackward& q, void* ws, int bf, hipStream_t st) {
-  if (int r = cross_backward_check(op, q.cross, ws, bf)) return r;
-  const CsHeadBackward& hq = q.cross.tail.head;
-  const int C = hq.C;
-  if ((long long)hq.B * hq.gh * hq.gw * 3 * C >= (1ll << 31)) return fail(CS_ERR_UNSUPPORTED, "%s: built for fewer than 2^31 Q | K | V elements; split the batch", op);
-  if (!q.x0 || !q.Qs || !q.Ks || !q.Vs || !q.Os || !q.lse_s || !q.Wq || !q.Wo_s || !q.bo_s || !q.gamma1 || !q.dWin_s || !q.dbin_s || !q.dWo_s || !q.dbo_s ||
-      !q.dg1 || !q.db1)
-    return fail(CS_ERR_BAD_ARG, "%s: null pointer", op);
-  for (int ld : {q.ldqkv, q.ldos, q.ldwq, q.ldwos})
-    if (ld < C || ld % 8) return fail(CS_ERR_BAD_ARG, "%s: row strides must be multiples of 8 elements and at least C", op);
-  if (misaligned(q.x0, 16) || misaligned(q.Qs, 16) || misaligned(q.Ks, 16) || misaligned(q.Vs, 16) || misaligned(q.Os, 16) || misaligned(q.Wq, 16) ||
-      misaligned(q.Wo_s, 16) || misaligned(q.bo_s, 16) || misaligned(q.gamma1, 16) || misaligned(q.lse_s, 4))
-    return fail(CS_ERR_BAD_ARG, "%s: misaligned input (16-bit operands, x0, bo and gamma 16 bytes, lse 4)", op);
-  for (const float* o : {q.dWin_s, q.dbin_s, q.dWo_s, q.dbo_s, q.dg1, q.db1})
-    if (misaligned(o, 4)) return fail(CS_ERR_BAD_ARG, "%s: misaligned output", op);
-  CsAttnBwdParams a{};
-  cs_layer_backward_attn_params(&q, ws, bf, &a);
-  if (const char* e = cs_attnbwd_check(&a)) return fail(CS_ERR_BAD_ARG, "%s: %s", op, e);
-  HIPCHK(cs_layer_backward_launch(&q, ws, bf, st));
-  return 0;
-}
-
-extern "C" {
-
-int cs_op_tail_backward(const float* x2, const uint16_t* H, int ldh, const uint16_t* X, int ldx, const uint16_t* A, int lda, const uint16_t* W2,
-                        int ldw2, const float* b2, const float* gamma3, float eps, const uint16_t* Wa, int ldwa, const uint16_t* Wb, int ldw,
-                        const float* bb, const float* gt, int B, int gh, int gw, int P, int C, int act, float powp, double inv_count,
-                        int accumulate, float* dW1, float* db1, float* dW2, float* db2, float* dg3, float* db3, float* dWa, float* dba,
-                        float* dWb, float* dbb, double* loss, void* ws, cs_stream stream) {
-  CsTailBackward q{};
-  q.x2 = x2; q.H = H; q.ldh = ldh; q.W2 = W2; q.ldw2 = ldw2; q.b2 = b2; q.gamma3 = gamma3; q.eps = eps; q.Wa = Wa; q.ldwa = ldwa;
-  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dg3; q.db3 = db3;
-  CsHeadBackward& hq = q.head;
-  hq.X = X; hq.ldx = ldx; hq.A = A; hq.lda = lda; hq.Wb = Wb; hq.ldw = ldw; hq.bb = bb; hq.gt = gt; hq.B = B; hq.gh = gh; hq.gw = gw; hq.P = P; hq.C = C;
-  hq.act = act; hq.powp = powp; hq.inv_count = inv_count; hq.accumulate = accumulate != 0; hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb;
-  hq.loss = loss;
-  return tail_backward_run("tail_backward", q, ws, g_op_bf16, (hipStream_t)stream);
-}
-
-int cs_op_adamw(float* p, float* m, float* v, const float* g, long long n, float lr, float beta1, float beta2, float eps, float weight_decay,
-                int step, uint16_t* p16, cs_stream stream) {
-  if (!p || !m || !v || !g) return fail(CS_ERR_BAD_ARG, "adamw: null pointer");
-  if (n <= 0 || n > (1ll << 38)) return fail(CS_ERR_BAD_ARG, "adamw: n must be in [1, 2^38]");
-  if (step < 1) return fail(CS_ERR_BAD_ARG, "adamw: steps count from 1");
-  if (!(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps >= 0.f) || !(weight_decay >= 0.f))
-    return fail(CS_ERR_BAD_ARG, "adamw: lr, eps, weight_decay must be >= 0 and the betas in [0, 1)");
-  if (misaligned(p, 4) || misaligned(m, 4) || misaligned(v, 4) || misaligned(g, 4) || misaligned(p16, 2)) return fail(CS_ERR_BAD_ARG, "adamw: misaligned pointer");
-  HIPCHK(cs_adamw_launch(p, m, v, g, n, lr, beta1, beta2, eps, weight_decay, step, p16, g_op_bf16, (hipStream_t)stream));
-  return 0;
-}
-
-// ---- attention backward (attnbwd.hip) ----
-size_t cs_attention_backward_workspace_bytes(int batch, int heads, int Lq, int Lk, int dh) {
-  if (batch <= 0 || heads <= 0 || Lq <= 0 || Lk <= 0 || !cs_attnbwd_supported(dh)) return 0;
-  return cs_attnbwd_workspace(batch, heads, Lq);
-}
-
-int cs_attention_backward_tiles(int dh, int* q_tile, int* k_tile) {
-  if (!cs_attnbwd_supported(dh)) return fail(CS_ERR_UNSUPPORTED, "attention_backward: built for head dims 16, 48 and 96 (got %d)", dh);
-  if (q_tile) *q_tile = 64;
-  if (k_tile) *k_tile = 64;
-  return 0;
-}
-
-int cs_op_attention_backward(const uint16_t* Q, const uint16_t* K, const uint16_t* V, const uint16_t* O, const uint16_t* dO, const float* lse,
-                             int ldq, int ldk, int ldv, int ldo, int lddo, long long q_bs, long long k_bs, long long v_bs, long long o_bs,
-                             long long do_bs, int batch, int heads, int Lq, int Lk, int dh, float q_scale, uint16_t* dQ, int lddq,
-                             long long dq_bs, uint16_t* dK, int lddk, long long dk_bs, uint16_t* dV, int lddv, long long dv_bs, void* ws,
-                             cs_stream stream) {
-  CsAttnBwdParams a{};
-  a.Q = Q; a.K = K; a.V = V; a.O = O; a.dO = dO; a.lse = lse; a.ldq = ldq; a.ldk = ldk; a.ldv = ldv; a.ldo = ldo; a.lddo = lddo;
-  a.q_bs = q_bs; a.k_bs = k_bs; a.v_bs = v_bs; a.o_bs = o_bs; a.do_bs = do_bs; a.nbatch = batch; a.heads = heads; a.Lq = Lq; a.Lk = Lk;
-  a.dQ = dQ; a.lddq = lddq; a.dq_bs = dq_bs; a.dK = dK; a.lddk = lddk; a.dk_bs = dk_bs; a.dV = dV; a.lddv = lddv; a.dv_bs = dv_bs;
-  a.D = static_cast<float*>(ws); a.bf16 = g_op_bf16;
-  if (!(q_scale >= 0.f)) return fail(CS_ERR_BAD_ARG, "attention_backward: q_scale must be >= 0 (0 = log2(e)/sqrt(dh))");
-  if (const char* e = cs_attnbwd_check(&a)) return fail(CS_ERR_BAD_ARG, "%s", e);
-  if (!cs_attnbwd_supported(dh)) return fail(CS_ERR_UNSUPPORTED, "attention_backward: built for head dims 16, 48 and 96 (got %d)", dh);
-  a.scale_log2e = q_scale == 0.f ? LOG2E / std::sqrt((float)dh) : q_scale;
-  HIPCHK(cs_attnbwd_launch(&a, dh, (hipStream_t)stream));
-  return 0;
-}
-
-// ---- cross-attention fit (crossfit.hip) ----
-int cs_cross_fit_supported(int hidden, int heads, int patch) {
-  return cs_tail_fit_supported(hidden, patch) && heads > 0 && hidden % heads == 0 && cs_attnbwd_supported(hidden / heads);
-}
-
-size_t cs_cross_backward_workspace_bytes(int B, int Np, int N, int C, int P, int heads) {
-  if (B <= 0 || Np <= 0 || N <= 0 || !cs_cross_fit_supported(C, heads, P) || (long long)B * Np * N * 2 * C >= (1ll << 31)) return 0;
-  return cs_cross_backward_workspace(B, Np, N, C, heads);
-}
-
-int cs_op_cross_backward(const float* x1, const uint16_t* Qp, int ldq, const uint16_t* K, const uint16_t* V, int ldkv, const uint16_t* O, int ldo,
-                         const float* lse, const uint16_t* mem, int ldm, const uint16_t* W1, int ldw1, const uint16_t* Wo, int ldwo, const float* bo,
-                         const float* gamma2, int N, int heads, int short_cut, const float* x2, const uint16_t* H, int ldh, const uint16_t* X,
-                         int ldx, const uint16_t* A, int lda, const uint16_t* W2, int ldw2, const float* b2, const float* gamma3, float eps,
-                         const uint16_t* Wa, int ldwa, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P,
-                         int C, int act, float powp, double inv_count, int accumulate, float* dWin, float* dbin, float* dWo, float* dbo,
-                         float* dgamma2, float* dbeta2, float* dW1, float* db1, float* dW2, float* db2, float* dgamma3, float* dbeta3, float* dWa,
-                         float* dba, float* dWb, float* dbb, double* loss, void* ws, cs_stream stream) {
-  CsCrossBackward c{};
-  c.x1 = x1; c.Qp = Qp; c.ldq = ldq; c.K = K; c.V = V; c.ldkv = ldkv; c.O = O; c.ldo = ldo; c.lse = lse; c.mem = mem; c.ldm = ldm;
-  c.W1 = W1; c.ldw1 = ldw1; c.Wo = Wo; c.ldwo = ldwo; c.bo = bo; c.gamma2 = gamma2; c.N = N; c.heads = heads; c.short_cut = short_cut != 0;
-  c.dWin = dWin; c.dbin = dbin; c.dWo = dWo; c.dbo = dbo; c.dg2 = dgamma2; c.db2 = dbeta2;
-  CsTailBackward& q = c.tail;
-  q.x2 = x2; q.H = H; q.ldh = ldh; q.W2 = W2; q.ldw2 = ldw2; q.b2 = b2; q.gamma3 = gamma3; q.eps = eps; q.Wa = Wa; q.ldwa = ldwa;
-  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dgamma3; q.db3 = dbeta3;
-  CsHeadBackward& hq = q.head;
-  hq.X = X; hq.ldx = ldx; hq.A = A; hq.lda = lda; hq.Wb = Wb; hq.ldw = ldw; hq.bb = bb; hq.gt = gt; hq.B = B; hq.gh = gh; hq.gw = gw; hq.P = P; hq.C = C;
-  hq.act = act; hq.powp = powp; hq.inv_count = inv_count; hq.accumulate = accumulate != 0; hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb;
-  hq.loss = loss;
-  return cross_backward_run("cross_backward", c, ws, g_op_bf16, (hipStream_t)stream);
-}
-
-// ---- whole-layer fit (layerfit.hip) ----
-int cs_layer_fit_supported(int hidden, int heads, int patch, int do_self_attn) { return do_self_attn != 0 && cs_cross_fit_supported(hidden, heads, patch); }
-
-size_t cs_layer_backward_workspace_bytes(int B, int Np, int N, int C, int P, int heads) {
-  if (!cs_cross_backward_workspace_bytes(B, Np, N, C, P, heads) || (long long)B * Np * 3 * C >= (1ll << 31)) return 0;
-  return cs_layer_backward_workspace(B, Np, N, C, heads);
-}
-
-int cs_op_layer_backward(const float* x0, const uint16_t* Qs, const uint16_t* Ks, const uint16_t* Vs, int ldqkv, const uint16_t* Os, int ldos,
-                         const float* lse_s, const uint16_t* Wq, int ldwq, const uint16_t* Wo_s, int ldwos, const float* bo_s, const float* gamma1,
-                         const float* x1, const uint16_t* Qp, int ldq, const uint16_t* K, const uint16_t* V, int ldkv, const uint16_t* O, int ldo,
-                         const float* lse, const uint16_t* mem, int ldm, const uint16_t* W1, int ldw1, const uint16_t* Wo, int ldwo, const float* bo,
-                         const float* gamma2, int N, int heads, int short_cut, const float* x2, const uint16_t* H, int ldh, const uint16_t* X,
-                         int ldx, const uint16_t* A, int lda, const uint16_t* W2, int ldw2, const float* b2, const float* gamma3, float eps,
-                         const uint16_t* Wa, int ldwa, const uint16_t* Wb, int ldw, const float* bb, const float* gt, int B, int gh, int gw, int P,
-                         int C, int act, float powp, double inv_count, int accumulate, float* dWin_s, float* dbin_s, float* dWo_s, float* dbo_s,
-                         float* dgamma1, float* dbeta1, float* dWin, float* dbin, float* dWo, float* dbo, float* dgamma2, float* dbeta2, float* dW1,
-                         float* db1, float* dW2, float* db2, float* dgamma3, float* dbeta3, float* dWa, float* dba, float* dWb, float* dbb,
-                         double* loss, void* ws, cs_stream stream) {
-  CsLayerBackward y{};
-  y.x0 = x0; y.Qs = Qs; y.Ks = Ks; y.Vs = Vs; y.ldqkv = ldqkv; y.Os = Os; y.ldos = ldos; y.lse_s = lse_s; y.Wq = Wq; y.ldwq = ldwq;
-  y.Wo_s = Wo_s; y.ldwos = ldwos; y.bo_s = bo_s; y.gamma1 = gamma1;
-  y.dWin_s = dWin_s; y.dbin_s = dbin_s; y.dWo_s = dWo_s; y.dbo_s = dbo_s; y.dg1 = dgamma1; y.db1 = dbeta1;
-  CsCrossBackward& c = y.cross;
-  c.x1 = x1; c.Qp = Qp; c.ldq = ldq; c.K = K; c.V = V; c.ldkv = ldkv; c.O = O; c.ldo = ldo; c.lse = lse; c.mem = mem; c.ldm = ldm;
-  c.W1 = W1; c.ldw1 = ldw1; c.Wo = Wo; c.ldwo = ldwo; c.bo = bo; c.gamma2 = gamma2; c.N = N; c.heads = heads; c.short_cut = short_cut != 0;
-  c.dWin = dWin; c.dbin = dbin; c.dWo = dWo; c.dbo = dbo; c.dg2 = dgamma2; c.db2 = dbeta2;
-  CsTailBackward& q = c.tail;
-  q.x2 = x2; q.H = H; q.ldh = ldh; q.W2 = W2; q.ldw2 = ldw2; q.b2 = b2; q.gamma3 = gamma3; q.eps = eps; q.Wa = Wa; q.ldwa = ldwa;
-  q.dW1 = dW1; q.db1 = db1; q.dW2 = dW2; q.db2 = db2; q.dg3 = dgamma3; q.db3 = dbeta3;
-  CsHeadBackward& hq = q.head;
-  hq.X = X; hq.ldx = ldx; hq.A = A; hq.lda = lda; hq.Wb = Wb; hq.ldw = ldw; hq.bb = bb; hq.gt = gt; hq.B = B; hq.gh = gh; hq.gw = gw; hq.P = P; hq.C = C;
-  hq.act = act; hq.powp = powp; hq.inv_count = inv_count; hq.accumulate = accumulate != 0; hq.dWa = dWa; hq.dba = dba; hq.dWb = dWb; hq.dbb = dbb;
-  hq.loss = loss;
-  return layer_backward_run("layer_backward", y, ws, g_op_bf16, (hipStream_t)stream);
-}
-
 }  // extern "C"

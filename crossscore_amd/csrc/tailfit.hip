@@ -183,38 +183,23 @@ hipError_t cs_tail_backward_launch(const CsTailBackward* q, void* ws, int bf, hi
   const CsHeadBackward& hq = q->head;
   const int M = hq.B * hq.gh * hq.gw, C = hq.C;
   const TailWs k = tail_carve(ws, M, C);
-  const h16_t* dpre = k.head.dpre;
-  h16_t *WT = k.WT, *dyh = k.dyh, *dH = k.dH, *x2h = k.x2h;
-  float *zb = k.zb, *dX = k.dX, *y = k.y;
-  void *lws = k.lws, *tws = k.tws;
   const float scale = (float)hq.inv_count;
   hipError_t e = cs_head_backward_launch(&hq, ws, bf, st);  // dWa, dba, dWb, dbb, the loss; dpre stays in the workspace
   if (e != hipSuccess) return e;
-  if ((e = hipMemsetAsync(zb, 0, (size_t)C * 4, st)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(k.zb, 0, (size_t)C * 4, st)) != hipSuccess) return e;
   // dX = dpre Wa
-  if ((e = cs_transpose16_launch(q->Wa, q->ldwa, C, C, WT, C, st)) != hipSuccess) return e;
-  if ((e = gemm_go(gemm_params(dpre, C, WT, C, M, C, zb, dX, bf), CS_EPI_RESID_F32, st)) != hipSuccess) return e;
-  // y = x2 + H W2^T + b2
-  CsGemmParams gy = gemm_params(q->H, q->ldh, q->W2, q->ldw2, M, C, q->b2, y, bf);
-  gy.resid = q->x2; gy.ldr = C;
-  if ((e = gemm_go(gy, CS_EPI_RESID_F32, st)) != hipSuccess) return e;
-  CsLnBackward ln{};
-  ln.y = y; ln.ldy = C; ln.dx = dX; ln.ldx = C; ln.gamma = q->gamma3; ln.eps = q->eps; ln.M = M; ln.C = C; ln.scale = scale; ln.accumulate = hq.accumulate;
-  ln.dyh = dyh; ln.ldd = C; ln.dgamma = q->dg3; ln.dbeta = q->db3;
-  if ((e = cs_ln_backward_launch(&ln, lws, bf, st)) != hipSuccess) return e;
-  CsGemmTn t{};
-  t.G = dyh; t.ldg = C; t.X = q->H; t.ldx = q->ldh; t.M = M; t.N = C; t.K = C; t.scale = scale; t.accumulate = hq.accumulate;
-  t.out = q->dW2; t.ldo = C; t.colsum = q->db2;
-  if ((e = cs_gemm_tn_launch(&t, tws, bf, st)) != hipSuccess) return e;
-  // dHh = (dyh W2) * [H > 0]
-  if ((e = cs_transpose16_launch(q->W2, q->ldw2, C, C, WT, C, st)) != hipSuccess) return e;  // (stream order: dX's GEMM has read WT)
-  if ((e = gemm_go(gemm_params(dyh, C, WT, C, M, C, zb, dH, bf), CS_EPI_BIAS_F16, st)) != hipSuccess) return e;
+  if ((e = through_weight(k.head.dpre, q->Wa, q->ldwa, M, C, k.WT, k.zb, nullptr, k.dX, CS_EPI_RESID_F32, bf, st)) != hipSuccess) return e;
+  // y = x2 + H W2^T + b2 and norm3: dg3, db3, dyh; dW2, db2; dH = dyh W2
+  const Closing c{q->H, q->ldh, q->W2, q->ldw2, q->b2, q->x2, q->gamma3, q->eps};
+  if ((e = closing_backward(c, k.dX, {k.y, k.dyh, k.WT, k.zb, k.lws, k.tws}, {q->dW2, q->db2, q->dg3, q->db3, k.dH}, M, C, scale, hq.accumulate, bf, st)) !=
+      hipSuccess)
+    return e;
+  // dHh = dH * [H > 0], then dW1, db1 against x2 rounded to the operand type
   const long long n8 = (long long)M * (C / 8);
-  relu_mask_kernel<<<(unsigned)((n8 + 255) / 256), 256, 0, st>>>(dH, q->H, q->ldh, M, C / 8);
+  relu_mask_kernel<<<(unsigned)((n8 + 255) / 256), 256, 0, st>>>(k.dH, q->H, q->ldh, M, C / 8);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  if ((e = cs_pack_f16_launch(q->x2, M, C, x2h, C, nullptr, nullptr, bf, st)) != hipSuccess) return e;
-  t.G = dH; t.X = x2h; t.ldx = C; t.out = q->dW1; t.colsum = q->db1;
-  return cs_gemm_tn_launch(&t, tws, bf, st);
+  if ((e = cs_pack_f16_launch(q->x2, M, C, k.x2h, C, nullptr, nullptr, bf, st)) != hipSuccess) return e;
+  return reduce_tn(k.dH, C, k.x2h, C, M, C, scale, hq.accumulate, q->dW1, q->db1, k.tws, bf, st);
 }
 
 }

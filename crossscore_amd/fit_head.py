@@ -34,7 +34,7 @@ import torch
 from .config import load_config
 from .data import EMPTY, ReferenceTokenCache, decode_items, load_batch, metric_mode
 from .evaluate import gt_file, gt_inputs, gt_map_kind, gt_metric_maps_choice, limit_batches
-from .model import ALL_FIT_SCOPES, FIT_SCOPES as SCOPE_TABLE, HeadFitState, arch_from_cfg, check_fit_supported, save_lightning_checkpoint
+from .model import FIT_SCOPES as SCOPE_TABLE, HeadFitState, arch_from_cfg, check_fit_supported, save_lightning_checkpoint
 from .nvs import NvsItems, random_order
 from .scoring import build_net, nvs_input_stage, seed_everything
 
@@ -44,15 +44,15 @@ def step_lr(lr0: float, step_size: int, gamma: float, n: int) -> float:
     return lr0 * gamma ** (n // step_size)
 
 
-FIT_SCOPES = tuple(SCOPE_TABLE)  # head, tail, cross: the names of model.FIT_SCOPES
+FIT_SCOPES = tuple(SCOPE_TABLE)  # head, tail, cross, layer: the names of model.FIT_SCOPES
 
 
 def fit_scope(cfg) -> str:
     """this_main.fit_scope: head (default; ref_cross.head.{0,2}), tail (the last decoder layer's feed-forward block and norm3 as well) or cross
     (that layer's cross-attention and norm2 as well) or layer (its self-attention and norm1 as well: the whole last decoder layer)"""
     scope = str(cfg.this_main.get("fit_scope", "head"))
-    if scope not in ALL_FIT_SCOPES:  # (FIT_SCOPES above keeps the three names its tests pin; the names are resolved through model.ALL_FIT_SCOPES)
-        raise ValueError(f"this_main.fit_scope={scope}: " + " | ".join(ALL_FIT_SCOPES))
+    if scope not in FIT_SCOPES:
+        raise ValueError(f"this_main.fit_scope={scope}: " + " | ".join(FIT_SCOPES))
     return scope
 
 

@@ -113,15 +113,13 @@ FIT_LAYER = FitScope("layer", FIT_CROSS, _LAST_LAYER, ("self_attn.in_proj_weight
                      "cs_layer_fit_supported", ("hidden", "dec_heads", "patch", "do_self_attn"), "cs_fit_layer_keep", "cs_layer_backward",
                      "cs_set_layer_weights", NotImplementedError, "whole-layer fit is built for the cross-attention fit's shapes "
                                                                   "(hidden {a.hidden}, {a.dec_heads} heads, patch {a.patch})")
-FIT_SCOPES = {s.name: s for s in (FIT_HEAD, FIT_TAIL, FIT_CROSS)}
-# two tables: FIT_SCOPES keeps the three scopes its tests pin; every lookup by name goes through ALL_FIT_SCOPES, which has the whole-layer scope too
-ALL_FIT_SCOPES = {**FIT_SCOPES, "layer": FIT_LAYER}
+FIT_SCOPES = {s.name: s for s in (FIT_HEAD, FIT_TAIL, FIT_CROSS, FIT_LAYER)}  # the one table: every lookup by name goes through it
 
 
 def check_fit_supported(arch: ArchSpec, scope) -> None:
     """Raises the scope's error unless its backward is built for `arch`; scope: a FitScope or its name.  The whole-layer scope without a decoder
     self-attention is a ValueError: there is nothing to fit."""
-    s = ALL_FIT_SCOPES[scope] if isinstance(scope, str) else scope
+    s = FIT_SCOPES[scope] if isinstance(scope, str) else scope
     if s is FIT_LAYER and not arch.do_self_attn:
         raise ValueError("fit_scope=layer needs model.decoder_do_self_attn=True: without the self-attention the layer scope has nothing to fit "
                          "beyond fit_scope=cross")

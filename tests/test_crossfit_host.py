@@ -223,7 +223,7 @@ def test_block_defects_exceed_the_op_bounds(B, N, gh, gw, short_cut, Cc, h, bf16
 def test_fit_scope_option():
     from crossscore_amd.fit_head import FIT_SCOPES, check_config, fit_scope
 
-    assert FIT_SCOPES == ("head", "tail", "cross")
+    assert FIT_SCOPES == ("head", "tail", "cross", "layer")
     cfg = load_config("default_fit_head", ["this_main.fit_scope=cross"])
     check_config(cfg)
     assert fit_scope(cfg) == "cross"

@@ -118,8 +118,8 @@ def test_defects_exceed_the_op_bounds(B, N, gh, gw, short_cut, Cc, h, bf16):
 def test_scope_table_and_options():
     from crossscore_amd import fit_head
 
-    assert list(model.FIT_SCOPES) == ["head", "tail", "cross"] and fit_head.FIT_SCOPES == ("head", "tail", "cross")  # the two pinned tuples
-    assert list(model.ALL_FIT_SCOPES) == ["head", "tail", "cross", "layer"] and model.ALL_FIT_SCOPES["layer"] is model.FIT_LAYER
+    assert list(model.FIT_SCOPES) == ["head", "tail", "cross", "layer"] and fit_head.FIT_SCOPES == ("head", "tail", "cross", "layer")  # one table
+    assert model.FIT_SCOPES["layer"] is model.FIT_LAYER and not hasattr(model, "ALL_FIT_SCOPES")
     assert [s.name for s in model.FIT_LAYER.chain()] == ["layer", "cross", "tail", "head"]
     net = CrossScoreNet(model_config(**{"backbone.from_pretrained": "synthetic/dinov2-tiny"}))
     keys = net.LAYER_KEYS
